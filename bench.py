@@ -12,6 +12,12 @@ the elapsed time.  For N > 1 two more measurements ride in the same JSON line (e
 (BASELINE config C4: 512 host-resident pairs over the ranks through the pair pipeline, PCIe included) and
 `c5_slab` (config C5: one 16384^2 frame in row slabs, halo rows exchanged with RCCL send/recv).
 
+A plain run measures the headline and nothing else: set-up, warm-up, exactly --steps timed steps, the outputs of the
+last timed step if --dump-outputs is given, and the result line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config).  --full adds everything beside it: the spread over further timed blocks, the other termination
+form, the one-context loop, per-kernel times and the roofline, the classic discretisation, the reference's default
+workload, the CPU baselines and, for N > 1, the C4 / C5 configurations.
+
 Launch: python bench.py [--gpus N]   (for N > 1 without WORLD_SIZE in the environment this process starts the N
         ranks itself -- fresh child processes under torch.distributed.run, before anything here touches the GPU --
         relays rank 0's JSON line and exits with the children's status), or, as the driver does for N > 1,
@@ -49,7 +55,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps (the first one is `value`; the rest give the spread)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too (spread, other termination form, one-context loop, roofline, "
+                         "classic mode, the reference's default workload, CPU baselines, C4 / C5 for N > 1); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the flow of the last timed step as DIR/u.npy and DIR/v.npy (float32; rank 0; "
+                         "a fixed sample of each when the two together exceed 60 MB)")
+    ap.add_argument("--blocks", type=int, default=5, help="with --full: timed blocks of --steps steps (the first one is `value`; the rest give the spread)")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--iters", type=int, default=100)
@@ -75,7 +87,7 @@ def parse():
     ap.add_argument("--skip-cpu", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU work of the single-thread cpu_baseline sample")
     ap.add_argument("--cpu-iters", type=int, default=0, help="iterations of the CPU sample (0: same as --iters)")
-    # multi-GPU extras (default: on for N > 1, off for N = 1)
+    # multi-GPU extras, --full only (default: on for N > 1, off for N = 1; without --full neither runs)
     ap.add_argument("--c4", choices=["auto", "on", "off"], default="auto", help="config C4: host-resident pairs through the pair pipeline")
     ap.add_argument("--c4-pairs", type=int, default=512, help="pairs of config C4 over all ranks")
     ap.add_argument("--c4-pool", type=int, default=8, help="distinct synthetic pairs per rank that the C4 submissions cycle through")
@@ -195,6 +207,22 @@ def read_pgm(path):
         raise ValueError("not an 8-bit binary PGM")
     w, h = int(tok[1]), int(tok[2])
     return np.frombuffer(data, np.uint8, w * h, pos + 1).reshape(h, w).copy()
+
+
+DUMP_BYTES = 60 << 20  # --dump-outputs writes at most this much array data (files and headers stay below 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """{name: array} -> path/<name>.npy in float32.  An array larger than its even share of DUMP_BYTES is replaced by a
+    fixed sample of its elements: flat indices drawn with seed 0 and sorted, the same for every run of the same shape."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def run_reference_default(args, hs, synth, torch, local_rank, with_cpu):
@@ -351,6 +379,21 @@ def self_launch(args):
     return subprocess.call(cmd, env=env, cwd=ROOT)
 
 
+def finish(out, rank, world, dist):
+    """Rank 0 prints the result line; with N > 1 the ranks then leave together."""
+    if rank == 0:
+        print(json.dumps(out))
+        sys.stdout.flush()
+    if world > 1:
+        import threading
+        bye = threading.Timer(30.0, lambda: os._exit(0))  # a peer that gave up (the watchdog in main) never reaches this barrier: the line is out, leave
+        bye.daemon = True
+        bye.start()
+        dist.barrier()
+        dist.destroy_process_group()
+        bye.cancel()
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -466,13 +509,16 @@ def main():
                 return pl.submit_device(a, b, params=p)
             return step
 
+        last_ticket = [None]
+
         def timed_block(step):  # noqa: F811 -- K submissions, then everything in flight drained, inside the bracket
             barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(args.steps):
-                step()
+                t = step()
             pl.drain()
+            last_ticket[0] = t
             torch.cuda.synchronize()
             barrier()
             return reduce_max(time.perf_counter() - t0)
@@ -480,10 +526,12 @@ def main():
     # Warm-up: --warmup untimed steps, and further untimed steps until WARM_SECONDS have passed -- an idle MI355X needs
     # ~30 ms of back-to-back work to reach the clock it then holds (profiles/r02_clock_ramp.txt: 0.196 -> 0.175 ms per
     # step over the first 150 steps), and a timed region that starts inside that ramp measures the ramp.
+    # In the stream loop the warm-up ends after an even number of steps, so that the timed steps always start on the first
+    # seed pair and the last timed step solves the same pair in every run with the same arguments (--dump-outputs).
     WARM_SECONDS = 0.1
     t_w = time.perf_counter()
     n_warm = 0
-    while n_warm < args.warmup or time.perf_counter() - t_w < WARM_SECONDS:
+    while n_warm < args.warmup or time.perf_counter() - t_w < WARM_SECONDS or (pl is not None and n_warm % 2):
         step()
         n_warm += 1
         if n_warm % 16 == 0:
@@ -492,10 +540,61 @@ def main():
 
     # THE timed region of the contract: exactly --steps steps between barrier + synchronize, max over ranks
     elapsed = timed_block(step)
+    # the flow of the last timed step, as a caller of the timed path receives it (stream: that pair's slot; repeat: the context)
+    if args.dump_outputs and rank == 0:
+        if pl is not None:
+            du, dv = pl.flow_device(last_ticket[0])
+            flow = {"u": du.cpu().numpy(), "v": dv.cpu().numpy()}
+        else:
+            us, vs = zip(*(ctx.flow(pair=i) for i in range(pairs)))
+            flow = {"u": us[0], "v": vs[0]} if pairs == 1 else {"u": np.stack(us), "v": np.stack(vs)}
+        dump_outputs(args.dump_outputs, flow)
     # (settles the last solve's early-stop check: iterations_done / eps_rerun are final)
     info = pl.info(step()) if pl else ctx.info()
+
+    KNAME = {hs.KERNEL_SIMPLE: "simple", hs.KERNEL_FUSED: "fused", hs.KERNEL_STRIP: "strip", hs.KERNEL_FOLD: "fold"}
+    px = W * H * pairs
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * px * iters * args.steps / elapsed / 1e6
+    out = {
+        "metric": "Mpixel*iterations/sec (Horn-Schunck: derivative pass + Jacobi u/v sweeps, frames resident in HBM)",
+        "value": value, "unit": "Mpix*iter/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "warmup_steps_run": n_warm,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": ("a stream of %dx%d translating-texture pairs resident in HBM, a new pair every step (two seed pairs alternating), "
+                                "lambda %g, %d Jacobi iterations, %s termination" % (W, H, args.lam, iters, head_name)) if pl else
+                               ("%dx%d translating-texture pair(s), %d pair(s) per GPU per step, lambda %g, %d Jacobi iterations, %s termination"
+                                % (W, H, pairs, args.lam, iters, head_name)),
+                   "width": W, "height": H, "iters": iters, "pairs_per_gpu": pairs, "lambda": args.lam,
+                   "kernel": KNAME[info["kernel"]],
+                   "fuse_steps": info["fuse_steps"], "tile": [info["tile_w"], info["tile_h"]],
+                   "threads": info["threads"], "rows_per_lane_or_groups": info["groups_per_thread"], "tiles_per_launch": info["tiles"],
+                   "lds_bytes": info["lds_bytes"], "hipgraph": not args.no_graph, "termination": head_name,
+                   "loop": loop,
+                   "call": ("hsflow_pipeline_submit_device, %d slots on %d streams" % (args.stream_depth, min(args.stream_lanes, args.stream_depth))) if pl else
+                           ("hsflow_solve" if args.sync_solves else "hsflow_solve_async"),
+                   "iterations_done": info["iterations_done"], "eps_rerun": info["eps_rerun"],
+                   "eps_check": "n/a (ITER)" if args.iter_only else (
+                       "every pair's own check: witness words reduced and read when the pair's slot comes round again, a pair whose early stop fired "
+                       "is re-solved from its slot's frames" if pl else "settled per solve (hsflow_solve)" if args.sync_solves else
+                       "carried over identical repeats: every step solves the SAME resident pair, so a step takes over the early-stop "
+                       "check the previous one owes and one check is settled after the timed region; a new pair per step is `fresh_frames`"),
+                   "sharding": "independent pairs per rank, no collective"},
+    }
+    if world > 1:
+        out["rccl_ranks"] = dist.get_world_size()
+        out["backend"] = backend
+    if not args.full:  # a plain run: the headline is all it measures
+        if pl is not None:
+            pl.close()
+        ctx.close()
+        finish(out, rank, world, dist)
+        return
+
+    # --- --full: everything beside the headline ---------------------------------------------------------------
     # spread: the same block again, --blocks - 1 more times
-    block_ms = [elapsed / args.steps * 1e3] + [timed_block(step) / args.steps * 1e3 for _ in range(max(0, args.blocks - 1))]
+    block_ms = [ms_per_step] + [timed_block(step) / args.steps * 1e3 for _ in range(max(0, args.blocks - 1))]
     # the other termination form beside it (same steps, same block structure)
     side_ms, info2 = [float("nan")], info
     if not args.no_side:
@@ -544,10 +643,6 @@ def main():
         der_ms += pi["deriv_ms"]
         launches += pi["jacobi_launches"]
 
-    KNAME = {hs.KERNEL_SIMPLE: "simple", hs.KERNEL_FUSED: "fused", hs.KERNEL_STRIP: "strip", hs.KERNEL_FOLD: "fold"}
-    px = W * H * pairs
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * px * iters * args.steps / elapsed / 1e6
     avg_launch_ms = jac_ms / max(launches, 1)
     sweeps_per_launch = iters * nprof / max(launches, 1)
     jac_us_per_step = jac_ms / nprof * 1e3
@@ -622,31 +717,7 @@ def main():
                                    "frac_of_hbm_peak": tr["hbm_bytes_per_launch"] / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
             break
 
-    out = {
-        "metric": "Mpixel*iterations/sec (Horn-Schunck: derivative pass + Jacobi u/v sweeps, frames resident in HBM)",
-        "value": value, "unit": "Mpix*iter/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "warmup_steps_run": n_warm,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": ("a stream of %dx%d translating-texture pairs resident in HBM, a new pair every step (two seed pairs alternating), "
-                                "lambda %g, %d Jacobi iterations, %s termination" % (W, H, args.lam, iters, head_name)) if pl else
-                               ("%dx%d translating-texture pair(s), %d pair(s) per GPU per step, lambda %g, %d Jacobi iterations, %s termination"
-                                % (W, H, pairs, args.lam, iters, head_name)),
-                   "width": W, "height": H, "iters": iters, "pairs_per_gpu": pairs, "lambda": args.lam,
-                   "kernel": KNAME[info["kernel"]],
-                   "fuse_steps": info["fuse_steps"], "tile": [info["tile_w"], info["tile_h"]],
-                   "threads": info["threads"], "rows_per_lane_or_groups": info["groups_per_thread"], "tiles_per_launch": info["tiles"],
-                   "lds_bytes": info["lds_bytes"], "hipgraph": not args.no_graph, "termination": head_name,
-                   "loop": loop,
-                   "call": ("hsflow_pipeline_submit_device, %d slots on %d streams" % (args.stream_depth, min(args.stream_lanes, args.stream_depth))) if pl else
-                           ("hsflow_solve" if args.sync_solves else "hsflow_solve_async"),
-                   "iterations_done": info["iterations_done"], "eps_rerun": info["eps_rerun"],
-                   "eps_check": "n/a (ITER)" if args.iter_only else (
-                       "every pair's own check: witness words reduced and read when the pair's slot comes round again, a pair whose early stop fired "
-                       "is re-solved from its slot's frames" if pl else "settled per solve (hsflow_solve)" if args.sync_solves else
-                       "carried over identical repeats: every step solves the SAME resident pair, so a step takes over the early-stop "
-                       "check the previous one owes and one check is settled after the timed region; a new pair per step is `fresh_frames`"),
-                   "sharding": "independent pairs per rank, no collective"},
+    out.update({
         "ms_per_step_blocks": block_ms, "ms_per_step_min": min(block_ms), "ms_per_step_median": statistics.median(block_ms),
         "ms_per_step_max": max(block_ms),
         "roofline": roof,
@@ -654,10 +725,7 @@ def main():
         "other_termination": {"termination": side_name, "ms_per_step": statistics.median(side_ms), "ms_per_step_blocks": side_ms,
                               "value": world * px * iters / (statistics.median(side_ms) * 1e-3) / 1e6,
                               "iterations_done": info2["iterations_done"], "eps_rerun": info2["eps_rerun"]},
-    }
-    if world > 1:
-        out["rccl_ranks"] = dist.get_world_size()
-        out["backend"] = backend
+    })
 
     # what a plain device-to-device copy reaches on this box (1 GiB read + 1 GiB written per copy,
     # torch's copy kernel, HIP events on torch's stream) -- context for the hbm figures
@@ -803,17 +871,7 @@ def main():
         n2, t2 = timed(0, 0.3 * args.cpu_seconds)
         out["cpu_baseline_all_cores"] = {"value": W * H * cit * n2 / t2 / 1e6, "unit": "Mpix*iter/s", "cores": nth, "kind": "port",
                                          "sample": "%d solves of the same pair, OpenMP row-parallel form, %.1f s" % (n2, t2)}
-    if rank == 0:
-        print(json.dumps(out))
-        sys.stdout.flush()
-    if world > 1:
-        import threading
-        bye = threading.Timer(30.0, lambda: os._exit(0))  # a peer that gave up (above) never reaches this barrier: the line is out, leave
-        bye.daemon = True
-        bye.start()
-        dist.barrier()
-        dist.destroy_process_group()
-        bye.cancel()
+    finish(out, rank, world, dist)
 
 
 if __name__ == "__main__":

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -23,7 +24,7 @@ def _json_line(out):
 
 
 def test_bench_single_gpu_line(gpu_ok):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--cpu-iters", "5", "--cpu-seconds", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "3", "--cpu-iters", "5", "--cpu-seconds", "1"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -73,13 +74,54 @@ def test_bench_single_gpu_line(gpu_ok):
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and cb["unit"] == "Mpix*iter/s"
 
 
+FULL_ONLY = ["roofline", "kernel_ms_per_step", "other_termination", "single_context", "fresh_frames", "classic_mode",
+             "reference_default_workload", "cpu_baseline", "cpu_baseline_all_cores", "ms_per_step_blocks", "c4_pipeline", "c5_slab"]
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(gpu_ok, oracle, tmp_path):
+    """A plain run (no --full) measures the headline and nothing beside it: exactly --steps timed steps, the line with the
+    headline keys.  --dump-outputs writes the flow of the last timed step.  Two runs with the same arguments give
+    bit-identical files, and the flow is that step's pair: the timed steps start on seed pair 1 and alternate, so the
+    10th solves seed pair 2 (oracle, 1e-4 RMS; seed pair 1's flow is far from it)."""
+    from opticalflowhs_amd import synth
+    dumps = []
+    for k in range(2):
+        dump = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3",
+                            "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _json_line(r.stdout)
+        for key in KEYS:
+            assert (key in d) == (key not in FULL_ONLY), key
+        for key in FULL_ONLY:
+            assert key not in d, key
+        assert d["n_gpus"] == 1 and d["steps"] == 10 and d["warmup"] == 3 and d["warmup_steps_run"] % 2 == 0
+        assert d["unit"] == "Mpix*iter/s" and d["dtype"] == "f32" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+        assert abs(d["value"] - 1920 * 1080 * 100 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-3 * d["value"]
+        assert d["config"]["loop"] == "stream" and d["config"]["termination"].startswith("ITER|EPS") and d["config"]["iterations_done"] == 100
+        assert sorted(os.listdir(dump)) == ["u.npy", "v.npy"]
+        u, v = np.load(dump / "u.npy"), np.load(dump / "v.npy")
+        assert u.dtype == np.float32 and v.dtype == np.float32 and u.shape == v.shape == (1080, 1920)
+        assert np.isfinite(u).all() and np.isfinite(v).all()
+        dumps.append((u, v))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+    u, v = dumps[0]
+    eps6 = float(np.float32(1e-6))
+    for seed, near in ((2, True), (1, False)):
+        A, B = synth.translating_pair(1920, 1080, seed=seed)
+        uo, vo = oracle.calc_optical_flow_hs(A, B, 1.0, 100, eps6, oracle.TERMCRIT_ITER | oracle.TERMCRIT_EPS)
+        ru = float(np.sqrt(np.mean((u.astype(np.float64) - uo) ** 2)))
+        rv = float(np.sqrt(np.mean((v.astype(np.float64) - vo) ** 2)))
+        assert (ru < 1e-4 and rv < 1e-4) == near, (seed, ru, rv)
+
+
 def test_bench_two_ranks_rehearsal(gpu_ok):
     """The N > 1 line as the driver's SCALE run would produce it, rehearsed with two ranks sharing the one card
     over gloo (halo rows staged through the host): the headline plus the C4 pipeline and the C5 slab
     measurements (shrunk: 16 pairs, a 2048^2 frame, 70 sweeps), the slab result checked bit for bit."""
     env = dict(os.environ, HSFLOW_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3",
+                        "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "3",
                         "--c4-pairs", "16", "--c5-size", "2048", "--c5-iters", "70", "--c5-halo", "16"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
@@ -99,7 +141,7 @@ def test_bench_gpus_2_launches_its_own_ranks(gpu_ok):
     relays rank 0's line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["HSFLOW_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "3",
                         "--c4-pairs", "16", "--c5-size", "2048", "--c5-iters", "70", "--c5-halo", "16"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
@@ -115,7 +157,7 @@ def test_bench_ranks_give_up_on_a_hung_side_measurement(gpu_ok):
     headline: after --side-timeout every rank ends itself, rank 0 having printed the line with the error under the key."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["HSFLOW_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--no-side",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "10", "--warmup", "3", "--no-side",
                         "--c4-pairs", "8", "--c5-size", "1024", "--c5-iters", "20", "--side-timeout", "20", "--debug-hang", "c5"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])

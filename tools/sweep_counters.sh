@@ -19,7 +19,7 @@ PY
 cat "$OUT/top5.txt"
 cd /tmp && export TMPDIR=/tmp
 while read -r name T R NT ms tiles tw th; do
-  ARGS="--width $W --height $H --iters $IT --steps 3 --warmup 1 --blocks 1 --skip-cpu --no-side --iter-only --no-graph --kernel strip --fuse-steps $T --strip-rows $R --threads $NT"
+  ARGS="--full --width $W --height $H --iters $IT --steps 3 --warmup 1 --blocks 1 --skip-cpu --no-side --iter-only --no-graph --kernel strip --fuse-steps $T --strip-rows $R --threads $NT"
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/$name/fetch" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/$name.fetch.json" 2> "$OUT/$name.fetch.err" || exit 2
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/$name/write" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/$name.write.json" 2> "$OUT/$name.write.err" || exit 3
   echo "$name done"
