@@ -159,10 +159,11 @@ int hsflow_destroy(hsflow_ctx *ctx); /* NULL is accepted; idempotent per handle 
 int hsflow_set_row_origin(hsflow_ctx *ctx, int first_row);
 
 /* The launch planners count on `compute_units` CUs instead of the whole chip (0: the whole chip again).  For a context
- * whose solves run BESIDE other contexts' solves -- the slots of a pair pipeline do this by themselves, with
- * CUs / depth -- so that each solve takes the shape that costs the least CU-time (few large tiles, little halo
- * redundancy) rather than the one that spreads a small frame over every CU to shorten its own latency: at the reference's
- * 600x480 default (main.cpp:4-8) that is the difference between 210 tiles of 88x16 and 36 of 216x40 per launch.
+ * whose solves run BESIDE other contexts' solves, so that each solve takes the shape that costs the least CU-time (few
+ * large tiles, little halo redundancy) rather than the one that spreads a small frame over every CU to shorten its own
+ * latency: at the reference's 600x480 default (main.cpp:4-8) that is the difference between 210 tiles of 88x16 and 36 of
+ * 216x40 per launch.  The slots of a pair pipeline do NOT set a share by themselves (the planners' cost models picked
+ * worse shapes with one than without); HSFLOW_PIPELINE_CU_SHARE=<n> makes every slot plan for n CUs, as an experiment.
  * Results are bit-identical whatever the shape. */
 int hsflow_set_cu_share(hsflow_ctx *ctx, int compute_units);
 
@@ -258,7 +259,9 @@ int hsflow_get_flow_async(hsflow_ctx *ctx, int pair, float *u, size_t u_stride, 
  * owes (they wait for the stream in that case); after an ITER-only solve they only enqueue. */
 /* Where the context holds the current flow of `pair`, without a copy: device pointers to row 0 and the row
  * stride in bytes (rows are `width` floats; the pitch is that of hsflow_info).  Settles an ITER|EPS check that
- * hsflow_solve_async still owes and waits for the stream, so the planes are final; they stay valid and unchanged
+ * hsflow_solve_async still owes and waits for the stream -- with hsflow_set_async_reduce, for the marker behind the last
+ * solve unless flow rows were copied in or out (set_flow_device, get_flow_device, get_flow_async) since, in which case
+ * for the stream -- so that nothing of this context that touches the planes is left in flight; they stay valid and unchanged
  * until the next call that changes this context's flow (solve, set_flow_device).  What a consumer on the device
  * (rendering, the next stage of a pipeline) reads instead of HSOpticalFlowOpenCL.cpp:655-675's blocking read-back. */
 int hsflow_flow_view_device(hsflow_ctx *ctx, int pair, const float **d_u, const float **d_v, size_t *stride_bytes);
@@ -314,10 +317,18 @@ int hsflow_pipeline_create(hsflow_pipeline **out, int device, int width, int hei
  * two solves side by side is what fills the chip's gaps, and the further slots keep both streams' queues
  * full while the host settles and refills the oldest slot -- 0.125 ms per 1080p / 100 pair against 0.139 with two slots
  * on two streams. */
+/* With THREE OR MORE lanes the pipeline picks the launch shape itself for a pair whose caller left it to the planner (CV
+ * mode, kernel AUTO, fuse_steps = strip_rows = threads = tile_w = tile_h = 0, ITER in term_type, max_iter > 0) when the
+ * frame is at least 256 x 80 and at most 1.5 Mpixel: the strip kernel with min(20, max_iter) sweeps per launch, 5 rows
+ * per lane and 1024 threads per workgroup (768 where 1024 would leave fewer than ~50 tiles) -- the shape that costs the
+ * least CU-time while other slots' solves share the chip.  hsflow_pipeline_info reports it.  The flow is bit-identical to
+ * that of the planner's shape, except for values below ~1e-30 (flow decaying to nothing on synthetic flat frames), whose
+ * last bits depend on where the launch boundaries fall.  HSFLOW_PIPELINE_AUTO_SHAPE=0 turns this off. */
 int hsflow_pipeline_create_lanes(hsflow_pipeline **out, int device, int width, int height, int depth, int lanes);
 int hsflow_pipeline_destroy(hsflow_pipeline *pl); /* drains first; NULL accepted */
 /* ticket (optional out): 0, 1, 2, ... in submission order.  Blocks only while the slot it is
- * about to reuse (ticket - depth) is still running. */
+ * about to reuse (ticket - depth) is still running.  With three or more lanes the launch shape may be the
+ * pipeline's own (hsflow_pipeline_create_lanes). */
 int hsflow_pipeline_submit(hsflow_pipeline *pl, const uint8_t *prev, size_t prev_stride,
                            const uint8_t *curr, size_t curr_stride, float *u, size_t u_stride,
                            float *v, size_t v_stride, const hsflow_params *params, uint64_t *ticket);

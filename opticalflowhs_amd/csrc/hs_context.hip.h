@@ -56,7 +56,8 @@ struct SolveSetup {
     int T;              // sweeps per full launch
     JPlan plan;         // launch plan for T sweeps
     bool persist;       // the whole budget as ONE persistent launch in phases of T sweeps (HSFLOW_KERNEL_PERSIST)
-    hsflow_params eff;  // the caller's parameters as the solve paths use them (strip_rows may have been fixed, see prepare_solve)
+    hsflow_params eff;  // the parameters of THIS call (a cached setup gets them replaced: use_previous, reuse_derivatives, use_graph
+                        // and profile do not enter the plan)
 };
 
 // prepare_solve's result for one set of parameters (hsflow_ctx::plan_cache)
@@ -114,6 +115,8 @@ struct hsflow_ctx {
     float *dZero = nullptr; // one row of zeros (P floats): stands in for u and v in strip / fold launches that start from zero flow
     unsigned mark_issued = 0;       // markers enqueued so far = the value the last one will write
     bool last_marked = false;       // the last solve was followed by a marker
+    bool flow_after_mark = false;   // copies into / out of the flow planes were enqueued behind that marker (hsflow_set_flow_device,
+                                    // hsflow_get_flow_device, hsflow_get_flow_async): the marker no longer says "the planes are final"
     bool async_reduce = false;      // hsflow_set_async_reduce
     int cu_share = 0;            // > 0: the planners count on this many CUs only (hsflow_set_cu_share); 0: the whole chip
     int num_cu = 0;              // compute units of the device (one workgroup of the persistent launch per CU)

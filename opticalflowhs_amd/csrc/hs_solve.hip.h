@@ -760,9 +760,9 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
     return HSFLOW_OK;
 }
 
-// CV mode: argument checks, kernel choice (AUTO rule) and launch plan.  Touches no device state, so the
-// planner can also be queried without a GPU (hsflow_plan_query).  Fills c->info's plan fields.
-int prepare_solve(hsflow_ctx *c, const hsflow_params &p, bool async, SolveSetup &S)
+// CV mode: the checks of the arguments themselves.  Run on every solve, also where the plan comes from the cache: the cache
+// key leaves out what does not enter the plan (profile among it), so a cached plan vouches for none of this.
+int check_solve_args(hsflow_ctx *c, const hsflow_params &p, bool async)
 {
     const bool use_iter = (p.term_type & HSFLOW_TERM_ITER) != 0, use_eps = (p.term_type & HSFLOW_TERM_EPS) != 0;
     if (!use_iter && !use_eps) return fail(c, HSFLOW_E_ARG, "term_type must include ITER and/or EPS");
@@ -776,7 +776,16 @@ int prepare_solve(hsflow_ctx *c, const hsflow_params &p, bool async, SolveSetup 
     if (use_eps && !(use_iter && p.max_iter > 0) && !(p.epsilon > 0.0 && std::isfinite(p.epsilon)))
         return fail(c, HSFLOW_E_NOTERM, "EPS termination without a sweep budget needs a finite epsilon > 0");
     if (async && p.profile) return fail(c, HSFLOW_E_ARG, "solve_async does not support profiling");
+    return HSFLOW_OK;
+}
 
+// CV mode: argument checks, kernel choice (AUTO rule) and launch plan.  Touches no device state, so the
+// planner can also be queried without a GPU (hsflow_plan_query).  Fills c->info's plan fields.
+int prepare_solve(hsflow_ctx *c, const hsflow_params &p, bool async, SolveSetup &S)
+{
+    int st = check_solve_args(c, p, async);
+    if (st) return st;
+    const bool use_iter = (p.term_type & HSFLOW_TERM_ITER) != 0, use_eps = (p.term_type & HSFLOW_TERM_EPS) != 0;
     // Ilambda = fl32(1/fl32(lambda)), cv210.dll VA 0x1012e054-0x1012e085.  Kept out of the denormal range
     // (lambda > 8.5e37): v_rsq_f32 in sweep_coefs flushes denormals, and where it matters -- a pixel with
     // Ix = Iy = 0 -- any finite value gives the same update (al = be = 0).
@@ -878,6 +887,7 @@ int solve_impl(hsflow_ctx *c, const hsflow_params *pp, bool async)
         if (by_reduce || hipGetLastError() == hipSuccess) {
             c->mark_issued++;
             c->last_marked = true;
+            c->flow_after_mark = false; // (the new marker is behind whatever was enqueued before this solve)
             if (c->pend.active) c->pend.mark = c->mark_issued;
         } else if (c->pend.active) c->pend.reduced = false; // (no marker: the owed check is settled the slow way)
     }
@@ -922,6 +932,7 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
         for (const PlanEntry &e : c->plan_cache)
             if (std::memcmp(&e.key, &key, sizeof(key)) == 0) { hit = &e; break; }
     if (hit) {
+        if ((st = check_solve_args(c, p, async))) return st;
         S = hit->S;
         S.eff = p; // (the cached copy carries the first caller's use_previous / reuse_derivatives / use_graph)
         hsflow_info &i = c->info;

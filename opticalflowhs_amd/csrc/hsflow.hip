@@ -510,6 +510,7 @@ int hsflow_get_flow_async(hsflow_ctx *c, int pair, float *u, size_t us, float *v
     if ((us & 3) || (vs & 3) || us < rowb || vs < rowb) return fail(c, HSFLOW_E_SIZE, "flow stride must be a multiple of 4 and >= 4*width");
     HS_HIP(c, copy_rows_async(c, u, us, c->dU[c->cur] + pair * c->plane, (size_t)c->P * 4, rowb, c->H, hipMemcpyDeviceToHost));
     HS_HIP(c, copy_rows_async(c, v, vs, c->dV[c->cur] + pair * c->plane, (size_t)c->P * 4, rowb, c->H, hipMemcpyDeviceToHost));
+    c->flow_after_mark = true;
     return HSFLOW_OK;
 }
 
@@ -530,8 +531,12 @@ int hsflow_flow_view_device(hsflow_ctx *c, int pair, const float **du, const flo
     if (st) return st;
     if (!du || !dv || !stride_bytes) return fail(c, HSFLOW_E_ARG, "null out pointer");
     if ((st = settle_pending(c))) return st;
-    if (c->last_marked) { if ((st = wait_marker(c, c->mark_issued))) return st; } // (the flow is final behind the last solve)
-    else HS_HIP(c, hipStreamSynchronize(c->stream));
+    // the flow is final behind the last solve -- unless copies into or out of the planes were enqueued since: then the stream
+    if (c->last_marked && !c->flow_after_mark) { if ((st = wait_marker(c, c->mark_issued))) return st; }
+    else {
+        HS_HIP(c, hipStreamSynchronize(c->stream));
+        c->flow_after_mark = false;
+    }
     if ((st = check_persist(c))) return st;
     *du = c->dU[c->cur] + pair * c->plane;
     *dv = c->dV[c->cur] + pair * c->plane;
@@ -550,6 +555,7 @@ int hsflow_get_flow_device(hsflow_ctx *c, int pair, int row0, int nrows, void *d
     const long long off = pair * c->plane + (long long)row0 * c->P;
     HS_HIP(c, hipMemcpy2DAsync(du, us, c->dU[c->cur] + off, (size_t)c->P * 4, rowb, nrows, hipMemcpyDeviceToDevice, c->stream));
     HS_HIP(c, hipMemcpy2DAsync(dv, vs, c->dV[c->cur] + off, (size_t)c->P * 4, rowb, nrows, hipMemcpyDeviceToDevice, c->stream));
+    c->flow_after_mark = true;
     return HSFLOW_OK;
 }
 
@@ -563,6 +569,7 @@ int hsflow_set_flow_device(hsflow_ctx *c, int pair, int row0, int nrows, const v
     const long long off = pair * c->plane + (long long)row0 * c->P;
     HS_HIP(c, hipMemcpy2DAsync(c->dU[c->cur] + off, (size_t)c->P * 4, du, us, rowb, nrows, hipMemcpyDeviceToDevice, c->stream));
     HS_HIP(c, hipMemcpy2DAsync(c->dV[c->cur] + off, (size_t)c->P * 4, dv, vs, rowb, nrows, hipMemcpyDeviceToDevice, c->stream));
+    c->flow_after_mark = true;
     return HSFLOW_OK;
 }
 

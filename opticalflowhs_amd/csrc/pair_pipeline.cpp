@@ -59,7 +59,8 @@ int ctx_fail(hsflow_pipeline *pl, hsflow_ctx *ctx, int code, const char *what)
 // 5 rows per lane; 16 wavefronts, or 12 where that would leave fewer than ~50 tiles).  Measured at depth 8 on MI355X,
 // ms per pair, planner's shape -> this one: 424x240 0.066 -> 0.051, 640x480 0.085 -> 0.053, 800x600 0.093 -> 0.061,
 // 1280x720 0.114 -> 0.075 (depth 3: 0.107 -> 0.066); from 1080p on the planner's shape is already this one
-// (profiles/r03_pipeline_shapes.txt).  Results are bit-identical whatever the shape.  HSFLOW_PIPELINE_AUTO_SHAPE=0: off.
+// (profiles/r03_pipeline_shapes.txt).  Results are bit-identical whatever the shape (apart from values below ~1e-30,
+// DESIGN.md 5).  HSFLOW_PIPELINE_AUTO_SHAPE=0: off.
 hsflow_params stream_shape(const hsflow_pipeline *pl, const hsflow_params &in)
 {
     static const bool off = getenv("HSFLOW_PIPELINE_AUTO_SHAPE") && atoi(getenv("HSFLOW_PIPELINE_AUTO_SHAPE")) == 0;

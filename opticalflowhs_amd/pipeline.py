@@ -37,7 +37,9 @@ class _DeviceView(object):
 
 
 class PairPipeline(object):
-    """`depth` single-pair contexts used round-robin.  Termination: ITER (default) or ITER|EPS."""
+    """`depth` single-pair contexts used round-robin.  Termination: ITER (default) or ITER|EPS.
+    With lanes >= 3 a pair that leaves the launch shape to the planner gets the pipeline's own (strip kernel, up to 20 sweeps
+    per launch, 5 rows per lane) on frames of 256 x 80 .. 1.5 Mpixel: same flow bits (include/hsflow.h, hsflow_pipeline_create_lanes)."""
 
     def __init__(self, width, height, depth=4, device=0, lanes=None):
         """lanes: streams the slots are spread over (default: one per slot -- host-memory pairs; device-resident streams

@@ -123,7 +123,7 @@ def test_switches_do_not_change_a_bit_and_the_flow_view_is_the_flow(hs, gpu_ok):
 
 def test_cached_plans_do_not_carry_a_callers_flags(hs, gpu_ok):
     """A context plans once per parameter set (the planner's sweep costs tens of microseconds per solve); what does not enter the
-    plan -- use_previous, reuse_derivatives, use_graph -- must still be honoured on every call."""
+    plan -- use_previous, reuse_derivatives, use_graph, profile -- must still be honoured, and checked, on every call."""
     W, H, it = 700, 300, 24
     A, B = synth.translating_pair(W, H, seed=17)
     A2, B2 = synth.translating_pair(W, H, seed=18)
@@ -150,6 +150,80 @@ def test_cached_plans_do_not_carry_a_callers_flags(hs, gpu_ok):
         u, v = ctx.flow()
         uo, vo = fresh((A2, B2), [dict()])
         assert np.array_equal(u, uo) and np.array_equal(v, vo)
+        # profile = 1 is refused by solve_async whatever was planned before: also where an asynchronous solve of the same
+        # parameters has put its plan in the cache, every time
+        for tt in (ITER, ITER | EPS):
+            kw = dict(lam=0.9, max_iter=it, term_type=tt, epsilon=1e-6)
+            ctx.solve_async(**kw)
+            ctx.synchronize()
+            for _ in range(3):
+                with pytest.raises(hs.HsflowError) as err:
+                    ctx.solve_async(profile=True, **kw)
+                assert err.value.status == hs._lib.E_ARG, (tt, err.value)
+            # ... while the synchronous solve takes it: the kernels timed, the flow the same bits as without profiling
+            ctx.solve(**kw)
+            u, v = ctx.flow()
+            i = ctx.solve(profile=True, **kw)
+            assert i["deriv_ms"] > 0 and i["jacobi_ms"] > 0, (tt, i)
+            up, vp = ctx.flow()
+            assert np.array_equal(u, up) and np.array_equal(v, vp), tt
+            ctx.solve_async(**kw)             # and the context goes on as before
+            assert np.array_equal(ctx.flow()[0], u), tt
+
+
+def _view(hs, ctx, W, H):
+    """hsflow_flow_view_device: the context's own flow planes as CUDA tensors (no copy)."""
+    import torch
+    from opticalflowhs_amd.pipeline import _DeviceView
+    pu, pv, sb = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+    assert hs._lib.load().hsflow_flow_view_device(ctx._h, 0, ctypes.byref(pu), ctypes.byref(pv), ctypes.byref(sb)) == 0
+    return tuple(torch.as_tensor(_DeviceView(p.value, (H, W), (sb.value, 4)), device="cuda") for p in (pu, pv))
+
+
+def test_flow_view_waits_for_flow_copies_queued_behind_the_solve(hs, gpu_ok):
+    """hsflow_flow_view_device promises planes that are final.  On an async-reduce context (every pipeline slot is one) it
+    waits for the marker behind the last solve; flow rows copied in or out AFTER that solve sit behind the marker, and
+    the view must wait for them as well: when it returns, nothing of this context is left on its stream."""
+    import torch
+    W, H, rows = 3840, 2160, 8
+    A, B = synth.random_pair(W, H, seed=23)
+    kw = dict(lam=1.0, max_iter=2000, term_type=ITER)   # long enough that every copy below is enqueued while it runs
+    g = torch.Generator().manual_seed(5)
+    U, V = (torch.randn((H, W), generator=g).cuda() for _ in range(2))
+    Du, Dv = torch.full((H, W), float("nan"), device="cuda"), torch.full((H, W), float("nan"), device="cuda")
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with hs.HSFlow(W, H, 1, stream=s.cuda_stream) as ctx:
+        assert hs._lib.load().hsflow_set_async_reduce(ctx._h, 1) == 0
+        ctx.set_frames(A, B)
+        ctx.solve(**kw)
+        ref = tuple(x.clone() for x in _view(hs, ctx, W, H))
+        torch.cuda.synchronize()
+        # 1. solve_async, then the planes overwritten row range by row range
+        ctx.solve_async(**kw)
+        for r in range(0, H, rows):
+            ctx.set_flow_rows_from(U[r:r + rows], V[r:r + rows], r, rows)
+        u, v = _view(hs, ctx, W, H)
+        assert s.query(), "flow_view returned while the flow copies were still in flight"
+        assert torch.equal(u.clone(), U) and torch.equal(v.clone(), V)   # (read on another stream)
+        # 2. solve_async, then the planes copied out row range by row range
+        ctx.solve_async(**kw)
+        for r in range(0, H, rows):
+            ctx.flow_rows_to(Du[r:r + rows], Dv[r:r + rows], r, rows)
+        u, v = _view(hs, ctx, W, H)
+        assert s.query(), "flow_view returned while the flow copies were still in flight"
+        assert torch.equal(u.clone(), ref[0]) and torch.equal(v.clone(), ref[1])
+        assert torch.equal(Du, ref[0]) and torch.equal(Dv, ref[1])
+        # 3. solve_async, then a synchronous solve
+        ctx.solve_async(**kw)
+        ctx.solve(**kw)
+        u, v = _view(hs, ctx, W, H)
+        assert s.query()
+        assert torch.equal(u.clone(), ref[0]) and torch.equal(v.clone(), ref[1])
+        # 4. and a solve after the copies: the view waits for that solve's marker only, as before
+        ctx.solve_async(**kw)
+        u, v = _view(hs, ctx, W, H)
+        assert torch.equal(u.clone(), ref[0]) and torch.equal(v.clone(), ref[1])
 
 
 @pytest.mark.parametrize("shape", [(1920, 1080), (600, 480), (333, 150), (258, 81)])
