@@ -119,8 +119,10 @@ typedef struct hsflow_params {
 typedef struct hsflow_info {
     uint32_t struct_size;
     int32_t width, height, n_pairs, pitch; /* pitch in elements, same for every plane    */
-    int32_t iterations_done;  /* sweeps executed by the last solve                        */
-    float last_eps;           /* Eps of the last sweep (EPS termination only).  An asynchronous
+    int32_t iterations_done;  /* sweeps executed by the last solve; the same for every pair of the
+                                 context (a batch stops as one, see hsflow_solve)               */
+    float last_eps;           /* Eps of the last sweep (EPS termination only): the maximum over all
+                                 pairs of the context, like every Eps of a batch.  An asynchronous
                                  ITER|EPS solve does not measure it; hsflow_get_info then runs that
                                  solve's last launch once more to obtain it (NaN if the flow was
                                  changed through hsflow_set_flow_device in between)               */
@@ -145,7 +147,10 @@ typedef struct hsflow_info {
 /* Fills p with the defaults (CV mode, lambda 1, ITER|EPS, 100 iterations, eps 1e-6f, auto). */
 void hsflow_default_params(hsflow_params *p);
 
-/* n_pairs independent image pairs of width x height live in one context (n_pairs >= 1).
+/* n_pairs independent image pairs of width x height live in one context (n_pairs >= 1).  Under ITER termination
+ * the pairs are independent: each one's flow is bit for bit what a context of its own computes.  Under EPS they share
+ * ONE stopping sweep (hsflow_solve): a pair's flow then depends on the others it is solved with.  Any n_pairs is
+ * accepted here; one whose launches would exceed the device's grid limits has no plan (HSFLOW_E_SIZE at the solve).
  * device: HIP ordinal.  stream: the hipStream_t all work is issued on (e.g. torch's current
  * stream; NULL is the device's default stream).  own_stream != 0: ignore `stream` and create a
  * private non-blocking stream instead. */
@@ -189,7 +194,8 @@ int hsflow_wait_solve(hsflow_ctx *ctx);
  * (cv210.dll@0x1012ed2f-0x1012eda5 takes the maximum over the frame).  Strip and simple kernels. */
 int hsflow_set_eps_rows(hsflow_ctx *ctx, int first_row, int rows);
 /* Exactly params->max_iter sweeps (whatever params->term_type says: nothing stops them) with the Eps of every sweep
- * -- over the rows of hsflow_set_eps_rows -- written to sweep_eps[0 .. max_iter).  Synchronous.  What a driver needs to
+ * -- over the rows of hsflow_set_eps_rows, the maximum over all pairs of the context (the Eps an EPS-terminated solve
+ * of the batch stops on) -- written to sweep_eps[0 .. max_iter).  Synchronous.  What a driver needs to
  * find the stopping sweep of a solve that is spread over several contexts: Eps_k of the frame = the maximum of the
  * contexts' Eps_k. */
 int hsflow_solve_probe(hsflow_ctx *ctx, const hsflow_params *params, float *sweep_eps);
@@ -231,7 +237,11 @@ int hsflow_push_frame_u8(hsflow_ctx *ctx, int pair, const uint8_t *next, size_t 
 
 /* --- solve -------------------------------------------------------------------------------- */
 
-/* Derivative pass + Jacobi iterations for every pair of the context.  hsflow_solve returns
+/* Derivative pass + Jacobi iterations for every pair of the context.  EPS termination on a batch: the Eps of a sweep
+ * is the maximum over ALL pairs of the context (each over the rows of hsflow_set_eps_rows), and the whole batch stops
+ * at the first sweep whose Eps is below epsilon -- every pair runs the same number of sweeps, a pair that converged
+ * early goes on while its neighbours do (cvCalcOpticalFlowHS, called per pair, would stop each one on its own).
+ * hsflow_solve returns
  * after the device finished; hsflow_solve_async only enqueues (no profile) and the caller
  * synchronises the stream or calls hsflow_synchronize.  Asynchronous solves take ITER termination
  * with any kernel, or ITER|EPS (the reference's call, OpticalFlowOpenCV.cpp:29) with the strip /

@@ -120,6 +120,7 @@ struct hsflow_ctx {
     bool async_reduce = false;      // hsflow_set_async_reduce
     int cu_share = 0;            // > 0: the planners count on this many CUs only (hsflow_set_cu_share); 0: the whole chip
     int num_cu = 0;              // compute units of the device (one workgroup of the persistent launch per CU)
+    int max_grid_z = 65535;      // the device's grid limit in z: launches with one layer of workgroups per pair take at most this many
     void *dScratch = nullptr;   // staging for colour frames / derivative read-back
     size_t scratch_bytes = 0;
     int cur = 0;                // which of dU/dV holds the current flow

@@ -16,6 +16,11 @@ bool eps_windowed(const hsflow_ctx *c) { return c->eps_rows > 0 && (c->eps_row0 
 int plan_cus(const hsflow_ctx *c) { return c->cu_share > 0 ? c->cu_share : kNumCU; }
 bool plan_shared(const hsflow_ctx *c) { return c->cu_share > 0 && c->cu_share < kNumCU; }
 
+// A launch of `tiles` workgroups of `threads` lanes along x stays within HIP's grid limits only below 2^32 work-items
+// (and so below 2^31 workgroups, what hsflow_info.tiles holds).  The tiles grow with the pairs of the context: shapes
+// past this have no plan, and a batch too large for every shape is refused (HSFLOW_E_SIZE).
+bool grid_fits(long long tiles, int threads) { return tiles * threads <= 0xFFFFFFFFLL; }
+
 // ------------------------------------------------------------------------------------------
 // Tile planner for the fused kernel.  Cost model: the launch takes ceil(tiles / CUs) rounds of
 // one workgroup per CU; a round costs the region area (LDS sweeps dominate) plus a fixed part.
@@ -45,6 +50,7 @@ bool make_plan(const hsflow_ctx *c, int T, int tw, int th, int nt, FusedPlan &be
                 if (lds > kLdsLimit) break;
                 const int tx = (W + CW - 1) / CW, ty = (H + CH - 1) / CH;
                 const long long tiles = (long long)tx * ty * c->N;
+                if (!grid_fits(tiles, NT)) continue;
                 const int K = (int)((G + NT - 1) / NT);
                 const long long ncu = plan_cus(c);
                 const long long rounds = (tiles + ncu * wg_per_cu - 1) / (ncu * wg_per_cu);
@@ -210,6 +216,7 @@ bool make_classic_strip_plan(const hsflow_ctx *c, int T, int rows, int threads, 
             hsk::ClassicStripGeom g;
             if (!classic_strip_geom(c, T, R, NW, g)) continue;
             const long long tiles = (long long)g.tiles_x * g.tiles_y * c->N;
+            if (!grid_fits(tiles, NW * 64)) continue;
             // (equal in the model: the same rows per SIMD in fewer, longer wavefronts measure 1 - 3 % faster)
             const double cost = classic_strip_launch_us(c, g, R, tiles) * (1.0 - 0.004 * R);
             if (cost < best_cost) {
@@ -334,6 +341,7 @@ bool make_strip_plan(const hsflow_ctx *c, int T, int rows, int threads, int fold
             if (lds > kLdsLimit) continue;
             const int tx = (W + CW - 1) / CW, ty = (H + CH - 1) / CH;
             const long long tiles = (long long)tx * ty * c->N;
+            if (!grid_fits(tiles, NW * 64)) continue;
             const double cost = strip_launch_cost(c, T, R, NW, tiles, fold, (double)W * H * c->N);
             if (cost < best_cost - 1e-9) {
                 best_cost = cost;
@@ -666,25 +674,43 @@ void plan_to_info(hsflow_ctx *c, const JPlan &pl)
     }
 }
 
+// The per-pixel kernels (derivatives, simple sweep, classic planes) take one layer of workgroups per pair: blockIdx.z =
+// pair.  A context may hold more pairs than the device allows in z (hipDeviceAttributeMaxGridDimZ), so they go out in
+// batches of at most max_grid_z pairs, batch by batch the same launch with every plane pointer moved on by its first pair
+// (`launch(first_pair_offset_in_elements, pairs)`).  One launch whenever the pairs fit, as before.
+template <typename Launch>
+hipError_t for_pair_batches(const hsflow_ctx *c, Launch launch)
+{
+    const int zmax = std::max(1, c->max_grid_z);
+    for (int z0 = 0; z0 < c->N; z0 += zmax) {
+        launch((long long)z0 * c->plane, std::min(zmax, c->N - z0));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_simple(const hsflow_ctx *c, bool eps, const float *ui, const float *vi, float *uo,
                          float *vo, float coeff, int zero_in = 0)
 {
-    const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4, c->N), block(64, 4);
+    return for_pair_batches(c, [&](long long o, int n) {
+        const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4, n), block(64, 4);
 #define HS_SIMPLE(E, Z)                                                                            \
-    hipLaunchKernelGGL((hsk::k_jacobi_simple<E, Z>), grid, block, 0, c->stream, c->dCoef, ui, vi, uo, vo, \
-                       c->W, c->H, c->P, c->plane, coeff, c->epsPtr, c->org, eps_row0(c), eps_row1(c))
-    if (eps) { if (zero_in) HS_SIMPLE(true, true); else HS_SIMPLE(true, false); }
-    else { if (zero_in) HS_SIMPLE(false, true); else HS_SIMPLE(false, false); }
+        hipLaunchKernelGGL((hsk::k_jacobi_simple<E, Z>), grid, block, 0, c->stream, c->dCoef + o, ui + o, vi + o, uo + o, vo + o, \
+                           c->W, c->H, c->P, c->plane, coeff, c->epsPtr, c->org, eps_row0(c), eps_row1(c))
+        if (eps) { if (zero_in) HS_SIMPLE(true, true); else HS_SIMPLE(true, false); }
+        else { if (zero_in) HS_SIMPLE(false, true); else HS_SIMPLE(false, false); }
 #undef HS_SIMPLE
-    return hipGetLastError();
+    });
 }
 
 hipError_t launch_deriv(const hsflow_ctx *c)
 {
-    const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4, c->N), block(64, 4);
-    hipLaunchKernelGGL(hsk::k_deriv_cv, grid, block, 0, c->stream, c->dA, c->dB, c->dCoef, c->W, c->H,
-                       c->P, c->plane);
-    return hipGetLastError();
+    return for_pair_batches(c, [&](long long o, int n) {
+        const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4, n), block(64, 4);
+        hipLaunchKernelGGL(hsk::k_deriv_cv, grid, block, 0, c->stream, c->dA + o, c->dB + o, c->dCoef + o, c->W, c->H,
+                           c->P, c->plane);
+    });
 }
 
 } // namespace

@@ -230,7 +230,8 @@ int solve_classic(hsflow_ctx *c, const hsflow_params &p, bool async)
     if (st) return st;
     if (p.profile && (p.use_graph || async)) return fail(c, HSFLOW_E_ARG, "CLASSIC mode: profiling needs a synchronous solve without use_graph");
     Profiler prof{c, p.profile != 0};
-    const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4, c->N), block(64, 4);
+    const dim3 block(64, 4);
+    auto grid = [&](int pairs) { return dim3((c->W + 255) / 256, (c->H + 3) / 4, pairs); }; // for_pair_batches
     const bool do_deriv = !(p.reuse_derivatives && c->coef_valid && c->coef_mode == HSFLOW_MODE_CLASSIC);
     const float a2 = p.alpha * p.alpha; // Kernels.cl:85
     const bool write_v = p.mode != HSFLOW_MODE_CLASSIC_AS_SHIPPED;
@@ -250,14 +251,17 @@ int solve_classic(hsflow_ctx *c, const hsflow_params &p, bool async)
     auto enqueue = [&](int *n) -> int {
         if (do_deriv) {
             prof.begin(0);
-            hipLaunchKernelGGL(hsk::k_deriv_classic_packed, grid, block, 0, c->stream, c->dA, c->dB, c->dCoef, c->W, c->H, c->P, c->plane);
-            HS_HIP(c, hipGetLastError());
+            HS_HIP(c, for_pair_batches(c, [&](long long o, int pairs) {
+                hipLaunchKernelGGL(hsk::k_deriv_classic_packed, grid(pairs), block, 0, c->stream, c->dA + o, c->dB + o, c->dCoef + o,
+                                   c->W, c->H, c->P, c->plane);
+            }));
             prof.end();
         }
         if (do_unpack) {
-            hipLaunchKernelGGL(hsk::k_unpack_classic_deriv, grid, block, 0, c->stream, c->dCoef, c->dE[0], c->dE[1], c->dE[2],
-                               c->W, c->H, c->P, c->plane);
-            HS_HIP(c, hipGetLastError());
+            HS_HIP(c, for_pair_batches(c, [&](long long o, int pairs) {
+                hipLaunchKernelGGL(hsk::k_unpack_classic_deriv, grid(pairs), block, 0, c->stream, c->dCoef + o, c->dE[0] + o, c->dE[1] + o,
+                                   c->dE[2] + o, c->W, c->H, c->P, c->plane);
+            }));
         }
         int zero = zero0 ? 1 : 0;
         if (zero) c->cur = 0;
@@ -278,9 +282,10 @@ int solve_classic(hsflow_ctx *c, const hsflow_params &p, bool async)
             } else {
                 auto kern = zero ? (write_v ? hsk::k_jacobi_classic<true, true> : hsk::k_jacobi_classic<true, false>)
                                  : (write_v ? hsk::k_jacobi_classic<false, true> : hsk::k_jacobi_classic<false, false>);
-                hipLaunchKernelGGL(kern, grid, block, 0, c->stream, c->dE[0], c->dE[1], c->dE[2], c->dU[a], c->dV[a], c->dU[b], c->dV[b],
-                                   c->W, c->H, c->P, c->plane, a2);
-                e = hipGetLastError();
+                e = for_pair_batches(c, [&](long long o, int pairs) {
+                    hipLaunchKernelGGL(kern, grid(pairs), block, 0, c->stream, c->dE[0] + o, c->dE[1] + o, c->dE[2] + o, c->dU[a] + o,
+                                       c->dV[a] + o, c->dU[b] + o, c->dV[b] + o, c->W, c->H, c->P, c->plane, a2);
+                });
             }
             prof.end();
             HS_HIP(c, e);

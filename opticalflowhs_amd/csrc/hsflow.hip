@@ -151,6 +151,9 @@ int hsflow_create(hsflow_ctx **out, int device, int width, int height, int n_pai
         int ncu = 0;
         HS_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
         c->num_cu = ncu;
+        int gz = 0;
+        HS_TRY(hipDeviceGetAttribute(&gz, hipDeviceAttributeMaxGridDimZ, device));
+        if (gz > 0) c->max_grid_z = gz;
     }
     if (getenv("HSFLOW_DEBUG_STAMPS")) HS_TRY(hipMalloc((void **)&c->dStamps, (size_t)kStampTiles * 8 * sizeof(unsigned long long)));
     // deterministic contents for padding columns and the initial flow

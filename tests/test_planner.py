@@ -114,3 +114,27 @@ def test_eps_without_budget_needs_a_usable_epsilon(hs):
     # with a sweep budget any epsilon is fine: ITER ends the solve
     for eps in (0.0, -1.0, float("nan")):
         assert hs.plan_query(64, 64, max_iter=7, term_type=hs.TERM_ITER | hs.TERM_EPS, epsilon=eps)["jacobi_launches"] >= 1
+
+
+def test_plans_for_very_large_batches_stay_launchable(hs):
+    """The tiles of a plan are multiplied by the pairs of the context: every plan's grid must stay within what a launch
+    can take (fewer than 2^32 work-items along x, so hsflow_info.tiles -- an int -- holds the count without wrapping),
+    and a batch no shape fits is refused, never planned with a wrapped count."""
+    cases = [(4, 4, 70000), (4, 4, 1 << 20), (300, 200, 65537), (600, 480, 100003), (1, 1, (1 << 31) - 1), (3, 2, 1 << 28),
+             (1920, 1080, 1 << 20), (4096, 2048, 4 << 20), (16384, 16384, 1 << 16)]
+    planned = refused = 0
+    for W, H, N in cases:
+        for kernel in (hs.KERNEL_AUTO, hs.KERNEL_SIMPLE, hs.KERNEL_FUSED, hs.KERNEL_STRIP, hs.KERNEL_FOLD):
+            for tt, it in ((hs.TERM_ITER, 37), (hs.TERM_ITER | hs.TERM_EPS, 100)):
+                try:
+                    info = hs.plan_query(W, H, N, lam=1.0, max_iter=it, term_type=tt, kernel=kernel)
+                except hs.HsflowError as e:
+                    assert e.status == hs._lib.E_SIZE and "no feasible" in str(e), (W, H, N, kernel, e)
+                    assert kernel != hs.KERNEL_SIMPLE  # the one-sweep kernel has no tiles: any batch is plannable
+                    refused += 1
+                    continue
+                planned += 1
+                check_plan(hs, W, H, N, it, info, {})
+                if info["kernel"] != hs.KERNEL_SIMPLE:
+                    assert 0 < info["tiles"] and info["tiles"] * info["threads"] < 1 << 32, (W, H, N, kernel, info)
+    assert planned >= 30 and refused >= 4, (planned, refused)
