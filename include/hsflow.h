@@ -21,6 +21,9 @@
  *   hsflow_get_flow[_device] ............ clEnqueueReadBuffer of uBuffer/vBuffer
  *                                          (HSOpticalFlowOpenCL.cpp:655-675); read at :765-767
  *   hsflow_get_derivatives .............. clEnqueueReadBuffer of Ex/Ey/Et (:437-468)
+ *   hsflow_render_flow[_device] ......... the arrow drawing after the read-back: cvCircle + cvLine per grid point
+ *                                          (OpticalFlowOpenCV.cpp:33-46, HSOpticalFlowOpenCL.cpp:759-769), from the
+ *                                          flow where it lies -- no read-back
  *   hsflow_calc_optical_flow_hs_8u32f ... one-shot form with the argument list of OpenCV's
  *                                          icvCalcOpticalFlowHS_8u32fR (cv210.dll VA 0x1012e040)
  *   status codes ........................ SDK_SUCCESS 0 / SDK_FAILURE 1 (SDKUtil/include/SDKCommon.hpp:23-24)
@@ -40,7 +43,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 5 /* 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 6 /* 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -286,6 +289,56 @@ int hsflow_get_derivatives(hsflow_ctx *ctx, int pair, float *dx, float *dy, floa
 int hsflow_get_frames_u8(hsflow_ctx *ctx, int pair, uint8_t *prev, size_t prev_stride,
                          uint8_t *curr, size_t curr_stride);
 
+/* --- the flow picture --------------------------------------------------------------------- */
+
+/* What the reference delivers is a picture (OpticalFlowOpenCV.cpp:33-46, HSOpticalFlowOpenCL.cpp:759-769): on a black
+ * image, for the grid points in raster order (y outer, x inner; y and x multiples of `step`), with a = u[y][x],
+ * b = v[y][x]:
+ *   1. drawn iff a > threshold || b > threshold || a < -threshold || b < -threshold (NaN in both draws nothing);
+ *   2. the dot: the 13 pixels with dx*dx + dy*dy <= 4 around (x, y) (cvCircle, radius 2, filled) in dot_rgb;
+ *   3. the line from (x, y) to ((int)((float)x + a*scale), (int)((float)y + b*scale)) -- fp32 arithmetic, truncation
+ *      toward zero, as cvPoint(float, float) -- in line_rgb, rasterised as OpenCV 2.1's cvLine(thickness 1) does: from
+ *      the LEFT end point, error term major - 2*minor, a diagonal step while the error is negative;
+ *   4. every pixel clipped to the image, and LATER WRITES WIN: a grid point's line lies over its own dot, and all of a
+ *      later grid point lies over all of an earlier one.
+ * The device draws exactly that, byte for byte what the host drawing of the drop-in class (csrc/host) draws from the
+ * same flow, without the flow ever leaving the device: every write gets a number (2k + 1 the dot, 2k + 2 the line of
+ * grid point k), a pixel shows the highest number that reached it, so the picture does not depend on the order of
+ * execution.  The work per line is bounded by the image, whatever the flow's magnitude.
+ * Out of the host's defined range: where an end-point coordinate (float)x + a*scale or (float)y + b*scale is not finite
+ * or its magnitude is >= 2^20 -- the host's (int) conversion is undefined there -- the dot is drawn and NO line.
+ * The picture is RGB, 3 bytes per pixel, rows `stride` bytes apart; the bytes of a row beyond 3*width are left alone. */
+#define HSFLOW_RENDER_CV 0   /* OpticalFlowOpenCV.cpp:33-46: threshold 1, scale 0.5   */
+#define HSFLOW_RENDER_CL 1   /* HSOpticalFlowOpenCL.cpp:759-769: threshold 0.5, scale 1 */
+typedef struct hsflow_render_params {
+    uint32_t struct_size;    /* = sizeof(hsflow_render_params)                                   */
+    int32_t step;            /* grid spacing in pixels, >= 1 (the reference: 4)                  */
+    float threshold, scale;  /* threshold finite and >= 0; scale finite (negative: arrows point backwards) */
+    uint8_t dot_rgb[3], line_rgb[3], pad[2];
+} hsflow_render_params;
+/* One of the reference's two drawings: step 4, dot (0, 0, 255), line (255, 0, 0) and the preset's threshold and scale
+ * (any preset other than HSFLOW_RENDER_CL gives HSFLOW_RENDER_CV). */
+void hsflow_default_render_params(hsflow_render_params *rp, int preset);
+/* The picture of the current flow of `pair` into device memory (on ctx's device), only enqueued on ctx's stream: two
+ * launches behind whatever produced the flow; complete after hsflow_synchronize / a wait for the stream.  Settles an
+ * ITER|EPS check that hsflow_solve_async still owes first (like hsflow_get_flow_device: a re-run would change the
+ * flow).  Reads the flow and never changes it: pointers from hsflow_flow_view_device stay valid.  On a context with
+ * hsflow_set_async_reduce, hsflow_wait_solve and hsflow_flow_view_device called after it wait for the stream -- and
+ * with it for the render -- not only for the marker behind the last solve.  The first render of a context allocates a
+ * plane of width x height words; contexts that never render pay nothing.
+ * HSFLOW_E_ARG: null pointer, wrong struct_size, step < 1, threshold not finite or negative, scale not finite, bad pair;
+ * HSFLOW_E_SIZE: stride < 3*width. */
+int hsflow_render_flow_device(hsflow_ctx *ctx, int pair, const hsflow_render_params *rp, void *d_rgb, size_t stride);
+/* The same into host memory, synchronous: drawn into a picture the context keeps on the device (allocated by the first
+ * call), copied to rgb (6.2 MB at 1080p where both flow planes are 16.6 MB), complete on return.  Replaces the
+ * read-back of u and v AND the host loop over the grid (HSOpticalFlowOpenCL.cpp:759-769).  Waits only for what this
+ * context enqueued.  Page-locked destination for the full PCIe rate. */
+int hsflow_render_flow(hsflow_ctx *ctx, int pair, const hsflow_render_params *rp, uint8_t *rgb, size_t stride);
+/* The in-image pixels of the line (x0, y0) -> (x1, y1) on a width x height image, in drawing order, by the closed form the
+ * render kernel uses to skip the part of a line outside the image (host arithmetic, no device needed): returns their
+ * number and writes the first `capacity` of them to xy as x, y pairs.  -1: non-positive size or xy null. */
+int hsflow_render_line_pixels(int x0, int y0, int x1, int y1, int width, int height, int32_t *xy, int capacity);
+
 /* --- introspection ------------------------------------------------------------------------ */
 
 int hsflow_get_info(hsflow_ctx *ctx, hsflow_info *info);
@@ -366,6 +419,12 @@ int hsflow_pipeline_submit_device(hsflow_pipeline *pl, const void *d_prev, size_
  * pairs have been submitted.  HSFLOW_E_STATE if the slot has been reused already. */
 int hsflow_pipeline_flow_device(hsflow_pipeline *pl, uint64_t ticket, const float **d_u, const float **d_v, size_t *stride_bytes);
 int hsflow_pipeline_wait(hsflow_pipeline *pl, uint64_t ticket); /* u, v of that pair are complete */
+/* wait(ticket) + the picture of that pair's flow (hsflow_render_flow / hsflow_render_flow_device of its slot, on the
+ * slot's stream): a pair whose early stop fired has been re-solved by then.  Both return when the picture is complete,
+ * after device-resident and host-buffer submits alike.  HSFLOW_E_STATE if the slot has been reused already; argument
+ * errors as hsflow_render_flow_device. */
+int hsflow_pipeline_render(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, uint8_t *rgb, size_t stride);
+int hsflow_pipeline_render_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, void *d_rgb, size_t stride);
 /* wait(ticket) + iterations_done, last_eps, eps_rerun ... of that pair; HSFLOW_E_STATE once a later
  * pair has finished on the same slot (ask before submitting `depth` more pairs). */
 int hsflow_pipeline_info(hsflow_pipeline *pl, uint64_t ticket, hsflow_info *info);

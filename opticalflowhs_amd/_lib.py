@@ -15,6 +15,7 @@ TERM_ITER, TERM_EPS = 1, 2
 MODE_CV, MODE_CLASSIC, MODE_CLASSIC_AS_SHIPPED = 0, 1, 2
 KERNEL_AUTO, KERNEL_SIMPLE, KERNEL_FUSED, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST = 0, 1, 2, 3, 4, 5
 FRAMES_GRAY8, FRAMES_GRAY8_BLUR, FRAMES_BGR8, FRAMES_BGR8_BLUR = 0, 1, 2, 3
+RENDER_CV, RENDER_CL = 0, 1
 
 
 class HsflowParams(ctypes.Structure):
@@ -42,8 +43,15 @@ class HsflowInfo(ctypes.Structure):
                 ("deriv_fused", ctypes.c_int32), ("persistent", ctypes.c_int32)]
 
 
+class HsflowRenderParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("step", ctypes.c_int32),
+                ("threshold", ctypes.c_float), ("scale", ctypes.c_float),
+                ("dot_rgb", ctypes.c_uint8 * 3), ("line_rgb", ctypes.c_uint8 * 3), ("pad", ctypes.c_uint8 * 2)]
+
+
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 _pp = ctypes.POINTER(HsflowParams)
+_rp = ctypes.POINTER(HsflowRenderParams)
 
 # name -> (restype, argtypes).  tests/test_abi.py checks this table against include/hsflow.h.
 PROTOTYPES = {
@@ -75,6 +83,10 @@ PROTOTYPES = {
     "hsflow_set_flow_device": (_i, [_vp, _i, _i, _i, _vp, _sz, _vp, _sz]),
     "hsflow_get_derivatives": (_i, [_vp, _i, _vp, _vp, _vp, _sz]),
     "hsflow_get_frames_u8": (_i, [_vp, _i, _vp, _sz, _vp, _sz]),
+    "hsflow_default_render_params": (None, [_rp, _i]),
+    "hsflow_render_flow_device": (_i, [_vp, _i, _rp, _vp, _sz]),
+    "hsflow_render_flow": (_i, [_vp, _i, _rp, _vp, _sz]),
+    "hsflow_render_line_pixels": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i]),
     "hsflow_get_info": (_i, [_vp, ctypes.POINTER(HsflowInfo)]),
     "hsflow_get_info_ex": (_i, [_vp, ctypes.POINTER(HsflowInfo), _i]),
     "hsflow_last_error": (ctypes.c_char_p, [_vp]),
@@ -95,6 +107,8 @@ PROTOTYPES = {
     "hsflow_pipeline_submit_device": (_i, [_vp, _vp, _sz, _vp, _sz, _pp, ctypes.POINTER(ctypes.c_uint64)]),
     "hsflow_pipeline_flow_device": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
     "hsflow_pipeline_wait": (_i, [_vp, ctypes.c_uint64]),
+    "hsflow_pipeline_render": (_i, [_vp, ctypes.c_uint64, _rp, _vp, _sz]),
+    "hsflow_pipeline_render_device": (_i, [_vp, ctypes.c_uint64, _rp, _vp, _sz]),
     "hsflow_pipeline_info": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(HsflowInfo)]),
     "hsflow_pipeline_drain": (_i, [_vp]),
     "hsflow_pipeline_depth": (_i, [_vp]),

@@ -29,6 +29,26 @@ std::string camera_frame(int i)
     return base + name;
 }
 
+// HSFLOW_RENDER_DEVICE=1: the picture is drawn on the device from the flow where the solver left it
+// (hsflow_render_flow) and u, v are never downloaded; otherwise they are, and the host draws (pnm.hpp).
+bool render_on_device()
+{
+    const char *e = getenv("HSFLOW_RENDER_DEVICE");
+    return e && atoi(e) != 0;
+}
+
+// The device route of both drawings: the picture of ctx's current flow into imgFlow.
+int draw_on_device(hsflow_ctx *ctx, int preset, int W, int H, pnm::Image &imgFlow)
+{
+    imgFlow.width = W; imgFlow.height = H; imgFlow.channels = 3;
+    imgFlow.data.resize((size_t)W * H * 3);
+    hsflow_render_params rp;
+    hsflow_default_render_params(&rp, preset);
+    const int st = hsflow_render_flow(ctx, 0, &rp, imgFlow.data.data(), (size_t)W * 3);
+    if (st != HSFLOW_OK) std::cout << hsflow_last_error(ctx) << std::endl;
+    return st == HSFLOW_OK ? SDK_SUCCESS : SDK_FAILURE;
+}
+
 } // namespace
 
 HSOpticalFlowOpenCL::HSOpticalFlowOpenCL(const char *name, char *src_, char *in1, char *in2, char *out, float alp,
@@ -89,16 +109,17 @@ int HSOpticalFlowOpenCL::solvePair(const pnm::Image &a, const pnm::Image &b, boo
     p.max_iter = iterations;
     const double t0 = now_ms();
     st = hsflow_solve(ctx, &p);
-    if (st == HSFLOW_OK) st = hsflow_get_flow(ctx, 0, u.data(), (size_t)width * 4, v.data(), (size_t)width * 4);
+    if (st == HSFLOW_OK && !render_on_device()) st = hsflow_get_flow(ctx, 0, u.data(), (size_t)width * 4, v.data(), (size_t)width * 4);
     lastMs = now_ms() - t0;
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
     return SDK_SUCCESS;
 }
 
 // Arrow rendering of the reference (HSOpticalFlowOpenCL.cpp:762-770): 4-pixel grid, |u| or |v| > 0.5,
-// blue dot + red full-length line.
-void HSOpticalFlowOpenCL::drawFlow(pnm::Image &imgFlow) const
+// blue dot + red full-length line.  With HSFLOW_RENDER_DEVICE=1 the device draws it (u and v stay where they are).
+int HSOpticalFlowOpenCL::drawFlow(pnm::Image &imgFlow) const
 {
+    if (render_on_device()) return draw_on_device(ctx, HSFLOW_RENDER_CL, (int)width, (int)height, imgFlow);
     imgFlow.width = width; imgFlow.height = height; imgFlow.channels = 3;
     imgFlow.data.assign((size_t)width * height * 3, 0);
     const int step = 4;
@@ -110,6 +131,7 @@ void HSOpticalFlowOpenCL::drawFlow(pnm::Image &imgFlow) const
                 pnm::line(imgFlow, j, i, (int)(j + fu), (int)(i + fv), 255, 0, 0);
             }
         }
+    return SDK_SUCCESS;
 }
 
 int HSOpticalFlowOpenCL::run()
@@ -135,7 +157,7 @@ int HSOpticalFlowOpenCL::run()
         if (solvePair(g1, g2, false) != SDK_SUCCESS) return SDK_FAILURE;
         std::cout << "Avg time: " << lastMs << " [ms]" << std::endl; // :755
         pnm::Image imgFlow;
-        drawFlow(imgFlow);
+        if (drawFlow(imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
         if (!output.empty() && !pnm::save_image(output, imgFlow)) return SDK_FAILURE;
         return 0;
     }
@@ -154,7 +176,7 @@ int HSOpticalFlowOpenCL::run()
         count++;
         if (getenv("HSFLOW_CAMERA_OUT")) {
             pnm::Image imgFlow;
-            drawFlow(imgFlow);
+            if (drawFlow(imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
             char name[64];
             snprintf(name, sizeof(name), "/flow_%04d.ppm", i);
             pnm::save_image(std::string(getenv("HSFLOW_CAMERA_OUT")) + name, imgFlow);
@@ -205,14 +227,17 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     hsflow_default_params(&p);          // ITER|EPS, eps = (float)1e-6 as at OpticalFlowOpenCV.cpp:29
     p.lambda = lambda;
     p.max_iter = it;
-    std::vector<float> u((size_t)W * H), v((size_t)W * H);
+    const bool on_device = render_on_device();
+    std::vector<float> u, v;
+    if (!on_device) { u.resize((size_t)W * H); v.resize((size_t)W * H); }
     if (st == HSFLOW_OK) st = hsflow_solve(ctx, &p);
-    if (st == HSFLOW_OK) st = hsflow_get_flow(ctx, 0, u.data(), (size_t)W * 4, v.data(), (size_t)W * 4);
+    if (st == HSFLOW_OK && !on_device) st = hsflow_get_flow(ctx, 0, u.data(), (size_t)W * 4, v.data(), (size_t)W * 4);
     const double ms = now_ms() - t0;
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; hsflow_destroy(ctx); return 1; }
-    hsflow_destroy(ctx);
     pnm::Image imgFlow;
-    draw_cv_flow(imgFlow, u, v, W, H);
+    if (on_device && draw_on_device(ctx, HSFLOW_RENDER_CV, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
+    hsflow_destroy(ctx);
+    if (!on_device) draw_cv_flow(imgFlow, u, v, W, H);
     pnm::save_image(output, imgFlow);
     std::cout << "Avg time: " << ms << " [ms]" << std::endl;
     return 0;
@@ -235,7 +260,9 @@ int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
     hsflow_default_params(&p);                                   // ITER|EPS, eps (float)1e-6 :94
     p.lambda = lambda;
     p.max_iter = it;
-    std::vector<float> u((size_t)W * H), v((size_t)W * H);
+    const bool on_device = render_on_device();
+    std::vector<float> u, v;
+    if (!on_device) { u.resize((size_t)W * H); v.resize((size_t)W * H); }
     std::vector<uint8_t> scratch((size_t)W * H);
     double total = 0.0;
     int count = 0;
@@ -245,7 +272,7 @@ int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
         const double t0 = now_ms();
         int st = hsflow_set_frames_gray8_blur(ctx, 0, gold.data.data(), (size_t)W, gnew.data.data(), (size_t)W); // :92-93
         if (st == HSFLOW_OK) st = hsflow_solve(ctx, &p);
-        if (st == HSFLOW_OK) st = hsflow_get_flow(ctx, 0, u.data(), (size_t)W * 4, v.data(), (size_t)W * 4);
+        if (st == HSFLOW_OK && !on_device) st = hsflow_get_flow(ctx, 0, u.data(), (size_t)W * 4, v.data(), (size_t)W * 4);
         total += now_ms() - t0;
         // imgOld = imgNew (:117): the blurred new frame
         if (st == HSFLOW_OK) st = hsflow_get_frames_u8(ctx, 0, scratch.data(), (size_t)W, gold.data.data(), (size_t)W);
@@ -253,7 +280,8 @@ int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
         count++;
         if (getenv("HSFLOW_CAMERA_OUT")) {
             pnm::Image imgFlow;
-            draw_cv_flow(imgFlow, u, v, W, H);
+            if (!on_device) draw_cv_flow(imgFlow, u, v, W, H);
+            else if (draw_on_device(ctx, HSFLOW_RENDER_CV, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
             char name[64];
             snprintf(name, sizeof(name), "/flow_%04d.ppm", i);
             pnm::save_image(std::string(getenv("HSFLOW_CAMERA_OUT")) + name, imgFlow);

@@ -35,7 +35,7 @@ public:
 
 class HSOpticalFlowOpenCL : public SDKSample {
     hsflow_ctx *ctx = nullptr;
-    std::vector<float> u, v;      // flow of the last pair, planar, pitch = width
+    std::vector<float> u, v;      // flow of the last pair, planar, pitch = width (not filled with HSFLOW_RENDER_DEVICE=1)
     float alpha;                  // flow smoothness coefficient (reference: cl_float alpha)
     int iterations;
     int blockSizeX;               // "gs": accepted for compatibility (work-group size hint), unused
@@ -46,7 +46,7 @@ class HSOpticalFlowOpenCL : public SDKSample {
 
     int ensureContext(int w, int h);
     int solvePair(const pnm::Image &a, const pnm::Image &b, bool streaming);
-    void drawFlow(pnm::Image &imgFlow) const;
+    int drawFlow(pnm::Image &imgFlow) const; // host loop over u, v; HSFLOW_RENDER_DEVICE=1: hsflow_render_flow, no read-back
 
 public:
     HSOpticalFlowOpenCL(const char *name, char *src, char *input1, char *input2, char *output, float alp,

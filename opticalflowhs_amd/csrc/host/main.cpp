@@ -6,6 +6,8 @@
 //   -cv -cam lambda iterations                                   (5)
 // Images are binary PGM/PPM; the interactive getchar() pause of the original (main.cpp:87) is
 // kept only when HSFLOW_PAUSE is set.
+// HSFLOW_RENDER_DEVICE=1: the arrow picture is drawn on the device (hsflow_render_flow) and the flow is not
+// downloaded; the files written are the same.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>

@@ -122,6 +122,13 @@ struct hsflow_ctx {
     int num_cu = 0;              // compute units of the device (one workgroup of the persistent launch per CU)
     int max_grid_z = 65535;      // the device's grid limit in z: launches with one layer of workgroups per pair take at most this many
     void *dScratch = nullptr;   // staging for colour frames / derivative read-back
+    // hsflow_render_flow[_device] (hs_render.hip.h), allocated by the first render: the priority plane (P x H words, zero
+    // between renders), the picture hsflow_render_flow draws into before it copies it out (3*W x H bytes), and the
+    // event behind that copy
+    unsigned *dPrio = nullptr;
+    bool prio_dirty = false;    // a render failed between its two launches: clear the plane before the next one
+    uint8_t *dRgb = nullptr;
+    hipEvent_t evRender = nullptr;
     size_t scratch_bytes = 0;
     int cur = 0;                // which of dU/dV holds the current flow
     bool frames_set = false;

@@ -1,0 +1,111 @@
+// hs_render.hip.h -- part of libhsflow.so (one translation unit, see hsflow.hip): hsflow_render_flow[_device], the
+// flow picture of the reference (OpticalFlowOpenCV.cpp:33-46, HSOpticalFlowOpenCL.cpp:759-769) drawn from the flow
+// where the solver left it.  Two launches on the context's stream (hs_kernels_render.hip.h); a context that never
+// renders allocates and launches nothing here.
+#pragma once
+
+namespace {
+
+int check_render_params(hsflow_ctx *c, const hsflow_render_params *rp)
+{
+    if (!rp || rp->struct_size != sizeof(hsflow_render_params)) return fail(c, HSFLOW_E_ARG, "render params null or struct_size mismatch");
+    if (rp->step < 1) return fail(c, HSFLOW_E_ARG, "render step must be >= 1");
+    if (!std::isfinite(rp->threshold) || rp->threshold < 0.f) return fail(c, HSFLOW_E_ARG, "render threshold must be finite and >= 0");
+    if (!std::isfinite(rp->scale)) return fail(c, HSFLOW_E_ARG, "render scale must be finite");
+    return HSFLOW_OK;
+}
+
+// Both launches, enqueued on c's stream.  The caller has checked every argument.
+int enqueue_render(hsflow_ctx *c, int pair, const hsflow_render_params &rp, uint8_t *d_rgb, size_t stride)
+{
+    const size_t words = (size_t)c->plane;
+    if (!c->dPrio) {
+        HS_HIP(c, hipMalloc((void **)&c->dPrio, words * sizeof(unsigned)));
+        c->prio_dirty = true;
+    }
+    if (c->prio_dirty) {
+        HS_HIP(c, hipMemsetAsync(c->dPrio, 0, words * sizeof(unsigned), c->stream));
+        c->prio_dirty = false;
+    }
+    const int gx = (c->W + rp.step - 1) / rp.step, gy = (c->H + rp.step - 1) / rp.step;
+    const unsigned n = (unsigned)((long long)gx * gy); // <= W * H <= 2^30: 2n + 2 fits a word
+    const unsigned dot = rp.dot_rgb[0] | (unsigned)rp.dot_rgb[1] << 8 | (unsigned)rp.dot_rgb[2] << 16;
+    const unsigned line = rp.line_rgb[0] | (unsigned)rp.line_rgb[1] << 8 | (unsigned)rp.line_rgb[2] << 16;
+    c->prio_dirty = true; // until the resolve pass has been enqueued behind the scatter pass
+    hipLaunchKernelGGL(hsk::k_render_scatter, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->dU[c->cur] + pair * c->plane,
+                       c->dV[c->cur] + pair * c->plane, c->dPrio, c->W, c->H, c->P, c->P, rp.step, gx, n, rp.threshold, rp.scale);
+    HS_HIP(c, hipGetLastError());
+    const int wide = (((uintptr_t)d_rgb | stride) & 3u) == 0;
+    const dim3 grid((c->W + 1023) / 1024, c->H < 65535 ? c->H : 65535);
+    hipLaunchKernelGGL(hsk::k_render_resolve, grid, dim3(256), 0, c->stream, c->dPrio, d_rgb, (long long)stride, c->W, c->H, c->P, dot, line, wide);
+    HS_HIP(c, hipGetLastError());
+    c->prio_dirty = false;
+    // work that reads the flow planes now lies behind the marker of the last solve: hsflow_wait_solve and
+    // hsflow_flow_view_device wait for the stream, not for that marker
+    c->last_marked = false;
+    return HSFLOW_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void hsflow_default_render_params(hsflow_render_params *rp, int preset)
+{
+    if (!rp) return;
+    std::memset(rp, 0, sizeof(*rp));
+    rp->struct_size = sizeof(*rp);
+    rp->step = 4;                                        // OpticalFlowOpenCV.cpp:35-36, HSOpticalFlowOpenCL.cpp:760-761
+    const bool cl = preset == HSFLOW_RENDER_CL;
+    rp->threshold = cl ? 0.5f : 1.0f;                    // HSOpticalFlowOpenCL.cpp:764 / OpticalFlowOpenCV.cpp:40
+    rp->scale = cl ? 1.0f : 0.5f;                        // HSOpticalFlowOpenCL.cpp:767 / OpticalFlowOpenCV.cpp:44
+    rp->dot_rgb[2] = 255;                                // CV_RGB(0, 0, 255)
+    rp->line_rgb[0] = 255;                               // CV_RGB(255, 0, 0)
+}
+
+int hsflow_render_flow_device(hsflow_ctx *c, int pair, const hsflow_render_params *rp, void *d_rgb, size_t stride)
+{
+    int st = check_ctx(c, pair);
+    if (st) return st;
+    if ((st = check_render_params(c, rp))) return st;
+    if (!d_rgb) return fail(c, HSFLOW_E_ARG, "null picture pointer");
+    if (stride < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
+    // the picture of a flow that a re-run would change is worth nothing: an owed ITER|EPS check is settled first
+    if ((st = settle_pending(c))) return st;
+    return enqueue_render(c, pair, *rp, (uint8_t *)d_rgb, stride);
+}
+
+int hsflow_render_flow(hsflow_ctx *c, int pair, const hsflow_render_params *rp, uint8_t *rgb, size_t stride)
+{
+    int st = check_ctx(c, pair);
+    if (st) return st;
+    if ((st = check_render_params(c, rp))) return st;
+    if (!rgb) return fail(c, HSFLOW_E_ARG, "null picture pointer");
+    const size_t rowb = (size_t)c->W * 3;
+    if (stride < rowb) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
+    if ((st = settle_pending(c))) return st;
+    if (!c->dRgb) HS_HIP(c, hipMalloc((void **)&c->dRgb, rowb * c->H));
+    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
+    const bool marked = c->last_marked;
+    if ((st = enqueue_render(c, pair, *rp, c->dRgb, rowb))) return st;
+    HS_HIP(c, copy_rows_async(c, rgb, stride, c->dRgb, rowb, rowb, c->H, hipMemcpyDeviceToHost));
+    // only what THIS context enqueued is waited for (the slots of a pair pipeline share streams)
+    HS_HIP(c, hipEventRecord(c->evRender, c->stream));
+    HS_HIP(c, hipEventSynchronize(c->evRender));
+    c->last_marked = marked; // nothing of the render is in flight any more: the solve's marker speaks for the context again
+    return check_persist(c);
+}
+
+int hsflow_render_line_pixels(int x0, int y0, int x1, int y1, int width, int height, int32_t *xy, int capacity)
+{
+    if (width <= 0 || height <= 0 || capacity < 0 || (capacity > 0 && !xy)) return -1;
+    hsline::Walk w = hsline::clip(x0, y0, x1, y1, width, height);
+    const long long n = w.count;
+    for (long long i = 0; i < n; i++) {
+        if (i < capacity) { xy[2 * i] = w.x; xy[2 * i + 1] = w.y; }
+        hsline::advance(w);
+    }
+    return (int)n;
+}
+
+} // extern "C"

@@ -10,6 +10,7 @@
 #include "hs_kernels_pre.hip.h"
 #include "hs_kernels_classic.hip.h"
 #include "hs_kernels_classic_strip.hip.h"
+#include "hs_kernels_render.hip.h"
 
 #include <atomic>
 #include <chrono>
@@ -225,6 +226,8 @@ int hsflow_destroy(hsflow_ctx *c)
     if (c->counted) g_live_ctx[c->device & 63]--;
     hipFree(c->dStamps);
     hipFree(c->dScratch);
+    hipFree(c->dPrio); hipFree(c->dRgb);
+    if (c->evRender) hipEventDestroy(c->evRender);
     if (c->hEps) hipHostFree(c->hEps);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -712,3 +715,5 @@ void hsflow_release_cached(void)
 }
 
 } // extern "C"
+
+#include "hs_render.hip.h" // hsflow_render_flow[_device], hsflow_default_render_params

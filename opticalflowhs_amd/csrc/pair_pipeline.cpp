@@ -268,6 +268,42 @@ int hsflow_pipeline_flow_device(hsflow_pipeline *pl, uint64_t ticket, const floa
     return HSFLOW_OK;
 }
 
+// wait(ticket), then the slot that still holds that pair (nullptr and the error set otherwise)
+static hsflow_pipeline::Slot *slot_of_finished(hsflow_pipeline *pl, uint64_t ticket, int *st)
+{
+    if ((*st = hsflow_pipeline_wait(pl, ticket))) return nullptr;
+    hsflow_pipeline::Slot &s = pl->slots[ticket % pl->slots.size()];
+    if (s.busy || !s.has_done || s.done_ticket != ticket) {
+        *st = pfail(pl, HSFLOW_E_STATE, "the slot of that ticket has been reused by a later pair");
+        return nullptr;
+    }
+    return &s;
+}
+
+int hsflow_pipeline_render(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, uint8_t *rgb, size_t stride)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    // (hsflow_render_flow waits for an event behind its own copy, not for what other slots have queued on the lane)
+    if ((st = hsflow_render_flow(s->ctx, 0, rp, rgb, stride))) return ctx_fail(pl, s->ctx, st, "hsflow_render_flow");
+    return HSFLOW_OK;
+}
+
+int hsflow_pipeline_render_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, void *d_rgb, size_t stride)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    if ((st = hsflow_render_flow_device(s->ctx, 0, rp, d_rgb, stride))) return ctx_fail(pl, s->ctx, st, "hsflow_render_flow_device");
+    // the slot is idle, so its event is free: behind the two launches, and only they are waited for
+    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
+        return pfail(pl, HSFLOW_E_DEVICE, "waiting for the slot's render failed");
+    return HSFLOW_OK;
+}
+
 int hsflow_pipeline_wait(hsflow_pipeline *pl, uint64_t ticket)
 {
     if (!pl) return HSFLOW_E_ARG;

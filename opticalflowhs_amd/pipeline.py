@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HsflowError, HsflowInfo, TERM_ITER
-from .solver import make_params
+from .solver import _is_device_tensor, _render_host, _render_target, make_params, make_render_params
 
 
 def pinned_empty(shape, dtype):
@@ -115,6 +115,21 @@ class PairPipeline(object):
             view = torch.as_tensor(_DeviceView(p.value, (self.height, self.width), (sb.value, 4)), device="cuda")
             out.append(view.clone() if copy else view)
         return tuple(out)
+
+    def render(self, ticket, route="cv", out=None, params=None, **kw):
+        """wait(ticket) + the reference's picture of that pair's flow, drawn on the device on the slot's stream
+        (`HSFlow.render`): an (H, W, 3) uint8 NumPy array, or into the CUDA uint8 tensor `out`; complete on return
+        either way.  Raises HsflowError (E_STATE) once `depth` more pairs have been submitted."""
+        rp = params if params is not None else make_render_params(route, **kw)
+        if _is_device_tensor(out):
+            ptr, stride = _render_target(out, self.height, self.width)
+            self._check(self._lib.hsflow_pipeline_render_device(self._h, int(ticket), ctypes.byref(rp), ptr, stride))
+            self._held.pop(int(ticket), None)
+            return out
+        img = _render_host(out, self.height, self.width)
+        self._check(self._lib.hsflow_pipeline_render(self._h, int(ticket), ctypes.byref(rp), ctypes.c_void_p(img.ctypes.data), img.strides[0]))
+        self._held.pop(int(ticket), None)
+        return img
 
     def wait(self, ticket):
         self._check(self._lib.hsflow_pipeline_wait(self._h, int(ticket)))

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (HsflowError, HsflowInfo, HsflowParams, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (HsflowError, HsflowInfo, HsflowParams, HsflowRenderParams, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -61,6 +61,45 @@ def make_params(lam=1.0, max_iter=100, epsilon=1e-6, term_type=TERM_ITER | TERM_
     p.use_graph = 1 if use_graph else 0
     p.profile = 1 if profile else 0
     return p
+
+
+def make_render_params(route="cv", step=None, threshold=None, scale=None, dot_rgb=None, line_rgb=None):
+    """hsflow_render_params of one of the reference's two drawings -- route "cv" (OpticalFlowOpenCV.cpp:33-46:
+    threshold 1, half-length lines) or "cl" (HSOpticalFlowOpenCL.cpp:759-769: threshold 0.5, full-length lines), both on a
+    4-pixel grid with blue dots and red lines -- with any field replaced."""
+    if route not in ("cv", "cl"):
+        raise ValueError("route must be 'cv' or 'cl'")
+    rp = HsflowRenderParams()
+    _lib.load().hsflow_default_render_params(ctypes.byref(rp), RENDER_CL if route == "cl" else RENDER_CV)
+    if step is not None:
+        rp.step = int(step)
+    if threshold is not None:
+        rp.threshold = threshold
+    if scale is not None:
+        rp.scale = scale
+    for name, val in (("dot_rgb", dot_rgb), ("line_rgb", line_rgb)):
+        if val is not None:
+            if len(val) != 3:
+                raise ValueError("%s must be three bytes" % name)
+            setattr(rp, name, (ctypes.c_uint8 * 3)(*[int(t) for t in val]))
+    return rp
+
+
+def _render_target(out, height, width):
+    """(pointer, row stride in bytes) of a CUDA uint8 tensor of shape (height, width, 3) with packed pixels."""
+    if str(out.dtype) != "torch.uint8" or tuple(out.shape) != (height, width, 3) or out.stride(2) != 1 or out.stride(1) != 3:
+        raise ValueError("out must be a CUDA uint8 tensor of shape (height, width, 3) with packed pixels")
+    return ctypes.c_void_p(out.data_ptr()), out.stride(0)
+
+
+def _render_host(out, height, width):
+    """The host picture to draw into: `out` if given (uint8, (height, width, 3), packed pixels), else a new array."""
+    if out is None:
+        return np.empty((height, width, 3), np.uint8)
+    if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.shape != (height, width, 3) or out.strides[2] != 1 or out.strides[1] != 3 \
+            or not out.flags.writeable:
+        raise ValueError("out must be a writeable uint8 array of shape (height, width, 3) with packed pixels")
+    return out
 
 
 class HSFlow(object):
@@ -201,6 +240,20 @@ class HSFlow(object):
     def set_flow_rows_from(self, u_dev, v_dev, row0, nrows, pair=0):
         self._check(self._lib.hsflow_set_flow_device(self._h, pair, row0, nrows, _ptr(u_dev),
                                                      u_dev.stride(0) * 4, _ptr(v_dev), v_dev.stride(0) * 4))
+
+    def render(self, route="cv", out=None, pair=0, params=None, **kw):
+        """The reference's picture of the current flow of `pair`, drawn on the device (`make_render_params`: route, step,
+        threshold, scale, dot_rgb, line_rgb).  out=None or a host array: returns an (H, W, 3) uint8 NumPy array, complete
+        on return -- the flow itself is never downloaded.  out = a CUDA uint8 tensor of shape (H, W, 3): only enqueued on
+        the context's stream (complete after `synchronize()`), returns `out`."""
+        rp = params if params is not None else make_render_params(route, **kw)
+        if _is_device_tensor(out):
+            ptr, stride = _render_target(out, self.height, self.width)
+            self._check(self._lib.hsflow_render_flow_device(self._h, pair, ctypes.byref(rp), ptr, stride))
+            return out
+        img = _render_host(out, self.height, self.width)
+        self._check(self._lib.hsflow_render_flow(self._h, pair, ctypes.byref(rp), _ptr(img), img.strides[0]))
+        return img
 
     def derivatives(self, pair=0):
         d = [np.empty((self.height, self.width), np.float32) for _ in range(3)]
