@@ -24,6 +24,8 @@
  *   hsflow_render_flow[_device] ......... the arrow drawing after the read-back: cvCircle + cvLine per grid point
  *                                          (OpticalFlowOpenCV.cpp:33-46, HSOpticalFlowOpenCL.cpp:759-769), from the
  *                                          flow where it lies -- no read-back
+ *   hsflow_verify ....................... HSOpticalFlowOpenCL::verifyResults (HSOpticalFlowOpenCL.cpp:894), the hook of
+ *                                          SDKUtil/include/SDKApplication.hpp that the reference left a stub
  *   hsflow_calc_optical_flow_hs_8u32f ... one-shot form with the argument list of OpenCV's
  *                                          icvCalcOpticalFlowHS_8u32fR (cv210.dll VA 0x1012e040)
  *   status codes ........................ SDK_SUCCESS 0 / SDK_FAILURE 1 (SDKUtil/include/SDKCommon.hpp:23-24)
@@ -43,7 +45,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 6 /* 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 7 /* 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -339,6 +341,94 @@ int hsflow_render_flow(hsflow_ctx *ctx, int pair, const hsflow_render_params *rp
  * number and writes the first `capacity` of them to xy as x, y pairs.  -1: non-positive size or xy null. */
 int hsflow_render_line_pixels(int x0, int y0, int x1, int y1, int width, int height, int32_t *xy, int capacity);
 
+/* --- is it right?  (verifyResults) -------------------------------------------------------- */
+
+/* The reference's class has a verifyResults() like every SDK sample (SDKUtil/include/SDKApplication.hpp) and left it
+ * a stub that returns SDK_SUCCESS (HSOpticalFlowOpenCL.cpp:894).  Here it is real, and needs no second implementation to
+ * compare with: every fast path of this library (LDS tile, register strip, folded strip, the persistent launch,
+ * launches replayed from a hipGraph, the derivative pass folded into the first launch, the speculative ITER|EPS pass)
+ * is specified to give, bit for bit, what the one-sweep-per-launch kernel behind the stand-alone derivative kernel
+ * gives.  hsflow_verify runs exactly that on the frames the context holds, into memory of its own, compares on the
+ * device (k_plane_compare) and hands back a report of 120 bytes -- no plane is downloaded.
+ *
+ * The comparison rule (csrc/hs_verify_rule.h, one header for the kernel and for hsflow_compare_planes_host), for one
+ * pair of fp32 values a (what the context holds) and b (the reference side):
+ *   differing    the 32 bits differ: +0 and -0 differ, two NaNs with the same bits do not;
+ *   failing      differing and not covered by the one exemption this project has (the strip
+ *                kernels carry a scaled state inside a launch, so flow that would be denormal keeps bits that depend
+ *                on where the launch boundaries fall): a differing pair is exempt iff both values are finite and
+ *                fabsf(a) < HSFLOW_VERIFY_TINY && fabsf(b) < HSFLOW_VERIFY_TINY;
+ *   nonfinite    a is NaN or Inf, whether or not it differs;
+ *   max_abs_diff the maximum of fabsf(a - b) over the differing pairs whose two values are finite, 0 if there is none;
+ *   max_ulp      the maximum over the same pairs of the distance on the ordered integer line (i = bits; if (i < 0)
+ *                i = INT32_MIN - i; distance as unsigned): a flip of the lowest mantissa bit is 1 apart.  +0 against -0
+ *                is the one differing pair that is 0 apart and 0 in max_abs_diff: differing, exempt, not failing;
+ *   first_failing the lowest raster index y * width + x of a failing element, -1 if there is none.
+ * Counts, maxima and a minimum only: a record is the same on every run, whatever the order of execution. */
+#define HSFLOW_VERIFY_TINY 1e-30f /* "bit for bit, except where both values lie below 1e-30" */
+typedef struct hsflow_plane_diff { /* 40 bytes */
+    uint64_t differing, failing, nonfinite;
+    int64_t first_failing;
+    float max_abs_diff;
+    uint32_t max_ulp;
+} hsflow_plane_diff;
+
+/* The rule over two planes in HOST memory (the same header compiled for the host; no device needed).  Strides in
+ * bytes, multiples of 4 and >= 4 * width.  HSFLOW_E_ARG: null pointer; HSFLOW_E_SIZE: size or stride. */
+int hsflow_compare_planes_host(const float *a, size_t a_stride, const float *b, size_t b_stride, int width, int height,
+                               hsflow_plane_diff *out);
+
+/* The context's CURRENT flow of `pair` (side a) against planes the caller holds in device memory on the context's
+ * device (side b; 4-byte aligned, strides in bytes, multiples of 4 and >= 4 * width; 16-byte alignment of base and
+ * stride gets the kernel's wide loads).  What a consumer on the device otherwise does through hsflow_get_flow and a
+ * loop on the host.  Synchronous: complete on return; waits only for what this context enqueued.  Settles an ITER|EPS
+ * check that hsflow_solve_async still owes first, reads the flow and never changes it: pointers from
+ * hsflow_flow_view_device stay valid (the ordering rules of hsflow_render_flow_device apply word for word).  The first
+ * call allocates a few hundred bytes on the device and in page-locked memory. */
+int hsflow_compare_flow_device(hsflow_ctx *ctx, int pair, const void *d_u, size_t u_stride, const void *d_v, size_t v_stride,
+                               hsflow_plane_diff *u, hsflow_plane_diff *v);
+
+typedef struct hsflow_verify_report { /* 120 bytes */
+    uint32_t struct_size;    /* = sizeof(hsflow_verify_report), set by the caller                             */
+    int32_t ok;              /* 1 iff u.failing == 0 && v.failing == 0 && deriv_differing == 0 &&
+                                iterations_ref == iterations_done                                             */
+    int32_t pair;            /* pair = -1 calls: the lowest pair with a failing element (flow or derivative
+                                words), -1 if none; else the pair asked for                                   */
+    int32_t iterations_done; /* sweeps of the solve under test (iterations_done of hsflow_get_info)           */
+    int32_t iterations_ref;  /* sweeps the reference pass ran: its own stopping sweep under EPS                */
+    int32_t reserved;
+    hsflow_plane_diff u, v;  /* pair = -1: counts summed and maxima over all pairs; first_failing is the raster
+                                index within the lowest pair in which that plane fails                        */
+    uint64_t deriv_differing; /* packed derivative words that differ from the stand-alone derivative kernel's  */
+    int64_t deriv_first;      /* raster index of the first one (pair = -1: in the lowest such pair), -1 if none */
+} hsflow_verify_report;
+
+/* Is the flow this context holds NOW what a sweep-by-sweep solve of the frames it holds, with the parameters of its
+ * last solve, produces?  (hsflow_solve, hsflow_solve_async, a pipeline slot's solve; hsflow_solve_probe counts as an
+ * ITER solve of max_iter sweeps.)
+ * The reference pass: the stand-alone derivative kernel into a coefficient plane of its own, then the one-sweep kernel
+ * of the mode (HSFLOW_KERNEL_SIMPLE), launch by launch -- no hipGraph, no derivative pass inside a Jacobi launch, no
+ * speculation -- from zero flow, with the same mode, lambda / alpha, term_type, max_iter, epsilon, row origin and Eps
+ * rows.  Under EPS it finds its OWN stopping sweep from Eps measured in every sweep (iterations_ref).  It always covers
+ * every pair of the context, because under EPS a batch stops as one.  Then k_plane_compare over the flow planes
+ * (a = the context's, b = the reference's) and over the packed derivative words, of `pair`, or of all pairs aggregated
+ * (pair = -1).
+ * It leaves the context as it found it: flow, derivatives, hsflow_info, pointers handed out by
+ * hsflow_flow_view_device, the cached graphs and plans, and what hsflow_get_info needs to measure last_eps later.  Its
+ * scratch (two flow buffers and a coefficient plane, context-sized) is allocated by the first call and kept until
+ * hsflow_destroy; contexts that never verify pay nothing, and the scratch does not count as a context for
+ * HSFLOW_KERNEL_PERSIST's "only one alive" rule.  Like a render it first settles an ITER|EPS check that
+ * hsflow_solve_async still owes.  Synchronous: complete on return.  A check, not a hot path: at max_iter launches it
+ * costs several solves.
+ * Writing the flow through hsflow_set_flow_device is NOT a refusal: the flow held now is what is compared.
+ * HSFLOW_E_ARG: null pointer, wrong struct_size, pair outside [-1, n_pairs).  HSFLOW_E_STATE, with a text that says
+ * which: no solve yet; the last solve failed or ended in HSFLOW_E_NOTERM; the last solve had use_previous = 1 (its
+ * starting flow is gone: warm starts cannot be verified); frames were set or pushed since the last solve.
+ * Out of scope: hsflow_multi_* and hsflow_slab_* (a slab's contexts refuse anyway: their solves are warm-started
+ * chunks), and flow that is not finite (lambda beyond ~1e30): NaNs of different bits fail, and nonfinite > 0 in the
+ * report says why. */
+int hsflow_verify(hsflow_ctx *ctx, int pair, hsflow_verify_report *report);
+
 /* --- introspection ------------------------------------------------------------------------ */
 
 int hsflow_get_info(hsflow_ctx *ctx, hsflow_info *info);
@@ -425,6 +515,10 @@ int hsflow_pipeline_wait(hsflow_pipeline *pl, uint64_t ticket); /* u, v of that 
  * errors as hsflow_render_flow_device. */
 int hsflow_pipeline_render(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, uint8_t *rgb, size_t stride);
 int hsflow_pipeline_render_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, void *d_rgb, size_t stride);
+/* wait(ticket) -- a pair whose early stop fired has been re-solved by then -- + hsflow_verify of that pair on its slot:
+ * what the slot actually ran is verified, including a launch shape the pipeline chose itself (three or more lanes).
+ * HSFLOW_E_STATE if the slot has been reused already. */
+int hsflow_pipeline_verify(hsflow_pipeline *pl, uint64_t ticket, hsflow_verify_report *report);
 /* wait(ticket) + iterations_done, last_eps, eps_rerun ... of that pair; HSFLOW_E_STATE once a later
  * pair has finished on the same slot (ask before submitting `depth` more pairs). */
 int hsflow_pipeline_info(hsflow_pipeline *pl, uint64_t ticket, hsflow_info *info);

@@ -49,9 +49,28 @@ class HsflowRenderParams(ctypes.Structure):
                 ("dot_rgb", ctypes.c_uint8 * 3), ("line_rgb", ctypes.c_uint8 * 3), ("pad", ctypes.c_uint8 * 2)]
 
 
+class HsflowPlaneDiff(ctypes.Structure):
+    _fields_ = [("differing", ctypes.c_uint64), ("failing", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64),
+                ("first_failing", ctypes.c_int64), ("max_abs_diff", ctypes.c_float), ("max_ulp", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class HsflowVerifyReport(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("ok", ctypes.c_int32), ("pair", ctypes.c_int32),
+                ("iterations_done", ctypes.c_int32), ("iterations_ref", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("u", HsflowPlaneDiff), ("v", HsflowPlaneDiff),
+                ("deriv_differing", ctypes.c_uint64), ("deriv_first", ctypes.c_int64)]
+
+
+VERIFY_TINY = 1e-30  # HSFLOW_VERIFY_TINY
+
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 _pp = ctypes.POINTER(HsflowParams)
 _rp = ctypes.POINTER(HsflowRenderParams)
+_dp = ctypes.POINTER(HsflowPlaneDiff)
+_vr = ctypes.POINTER(HsflowVerifyReport)
 
 # name -> (restype, argtypes).  tests/test_abi.py checks this table against include/hsflow.h.
 PROTOTYPES = {
@@ -87,6 +106,10 @@ PROTOTYPES = {
     "hsflow_render_flow_device": (_i, [_vp, _i, _rp, _vp, _sz]),
     "hsflow_render_flow": (_i, [_vp, _i, _rp, _vp, _sz]),
     "hsflow_render_line_pixels": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i]),
+    "hsflow_compare_planes_host": (_i, [_vp, _sz, _vp, _sz, _i, _i, _dp]),
+    "hsflow_compare_flow_device": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _dp, _dp]),
+    "hsflow_verify": (_i, [_vp, _i, _vr]),
+    "hsflow_pipeline_verify": (_i, [_vp, ctypes.c_uint64, _vr]),
     "hsflow_get_info": (_i, [_vp, ctypes.POINTER(HsflowInfo)]),
     "hsflow_get_info_ex": (_i, [_vp, ctypes.POINTER(HsflowInfo), _i]),
     "hsflow_last_error": (ctypes.c_char_p, [_vp]),

@@ -37,6 +37,28 @@ bool render_on_device()
     return e && atoi(e) != 0;
 }
 
+// HSFLOW_VERIFY=1: every solved pair is verified on the device before its context goes away (hsflow_verify), one
+// "Passed!" / "Failed" line per pair on stdout; a pair that fails makes the exit status SDK_FAILURE.
+bool verify_wanted()
+{
+    const char *e = getenv("HSFLOW_VERIFY");
+    return e && atoi(e) != 0;
+}
+
+// hsflow_verify of ctx's pair and its line; SDK_SUCCESS iff the report says ok.
+int verify_pair(hsflow_ctx *ctx, int W, hsflow_verify_report &report)
+{
+    std::memset(&report, 0, sizeof(report));
+    report.struct_size = sizeof(report);
+    const int st = hsflow_verify(ctx, 0, &report);
+    if (st != HSFLOW_OK) {
+        std::cout << "Failed: " << hsflow_last_error(ctx) << std::endl;
+        return SDK_FAILURE;
+    }
+    std::cout << verify_line(report, W) << std::endl;
+    return report.ok ? SDK_SUCCESS : SDK_FAILURE;
+}
+
 // The device route of both drawings: the picture of ctx's current flow into imgFlow.
 int draw_on_device(hsflow_ctx *ctx, int preset, int W, int H, pnm::Image &imgFlow)
 {
@@ -69,11 +91,18 @@ HSOpticalFlowOpenCL::~HSOpticalFlowOpenCL() { cleanup(); }
 
 int HSOpticalFlowOpenCL::initialize() { return SDKSample::initialize(); }
 int HSOpticalFlowOpenCL::setup() { return SDK_SUCCESS; }
-int HSOpticalFlowOpenCL::verifyResults() { return SDK_SUCCESS; }
+
+// The reference's stub (:894) answered SDK_SUCCESS whatever happened; before any pair has been solved that answer is kept.
+int HSOpticalFlowOpenCL::verifyResults()
+{
+    if (!ctx || !solved) return SDK_SUCCESS;
+    return verify_pair(ctx, (int)width, report);
+}
 
 int HSOpticalFlowOpenCL::cleanup()
 {
     if (ctx) { hsflow_destroy(ctx); ctx = nullptr; }
+    solved = false;
     return SDK_SUCCESS;
 }
 
@@ -112,6 +141,7 @@ int HSOpticalFlowOpenCL::solvePair(const pnm::Image &a, const pnm::Image &b, boo
     if (st == HSFLOW_OK && !render_on_device()) st = hsflow_get_flow(ctx, 0, u.data(), (size_t)width * 4, v.data(), (size_t)width * 4);
     lastMs = now_ms() - t0;
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+    solved = true;
     return SDK_SUCCESS;
 }
 
@@ -156,10 +186,11 @@ int HSOpticalFlowOpenCL::run()
         if (ensureContext(g1.width, g1.height) != SDK_SUCCESS) return SDK_FAILURE;
         if (solvePair(g1, g2, false) != SDK_SUCCESS) return SDK_FAILURE;
         std::cout << "Avg time: " << lastMs << " [ms]" << std::endl; // :755
+        const int verdict = verify_wanted() ? verifyResults() : SDK_SUCCESS;
         pnm::Image imgFlow;
         if (drawFlow(imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
         if (!output.empty() && !pnm::save_image(output, imgFlow)) return SDK_FAILURE;
-        return 0;
+        return verdict;
     }
     // "-cam": previous frame stays on the device, only the new frame is uploaded (:810-834)
     pnm::Image prev, cur, gprev, gcur;
@@ -167,13 +198,14 @@ int HSOpticalFlowOpenCL::run()
     pnm::to_gray(prev, gprev);
     if (ensureContext(gprev.width, gprev.height) != SDK_SUCCESS) return SDK_FAILURE;
     double total = 0.0;
-    int count = 0;
+    int count = 0, verdict = SDK_SUCCESS;
     for (int i = 1; pnm::load_image(camera_frame(i), cur); i++) {
         pnm::to_gray(cur, gcur);
         if (gcur.width != gprev.width || gcur.height != gprev.height) break;
         if (solvePair(gprev, gcur, count > 0) != SDK_SUCCESS) return SDK_FAILURE;
         total += lastMs;
         count++;
+        if (verify_wanted() && verifyResults() != SDK_SUCCESS) verdict = SDK_FAILURE;
         if (getenv("HSFLOW_CAMERA_OUT")) {
             pnm::Image imgFlow;
             if (drawFlow(imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
@@ -184,7 +216,7 @@ int HSOpticalFlowOpenCL::run()
         gprev = gcur;
     }
     if (count) std::cout << "Avg time: " << total / count << " [ms]" << std::endl; // :838
-    return SDK_SUCCESS;
+    return verdict;
 }
 
 // ---- GPU counterpart of OpticalFlowOpenCV (OpticalFlowHS/OpticalFlowOpenCV.cpp:7-52) --------------
@@ -234,13 +266,15 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     if (st == HSFLOW_OK && !on_device) st = hsflow_get_flow(ctx, 0, u.data(), (size_t)W * 4, v.data(), (size_t)W * 4);
     const double ms = now_ms() - t0;
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; hsflow_destroy(ctx); return 1; }
+    hsflow_verify_report report;
+    const int verdict = verify_wanted() ? verify_pair(ctx, W, report) : SDK_SUCCESS; // (the context goes away below)
     pnm::Image imgFlow;
     if (on_device && draw_on_device(ctx, HSFLOW_RENDER_CV, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     hsflow_destroy(ctx);
     if (!on_device) draw_cv_flow(imgFlow, u, v, W, H);
     pnm::save_image(output, imgFlow);
     std::cout << "Avg time: " << ms << " [ms]" << std::endl;
-    return 0;
+    return verdict;
 }
 
 // The camera loop of the CPU route (OpticalFlowOpenCV.cpp:56-131) on numbered frame files instead of a
@@ -265,7 +299,7 @@ int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
     if (!on_device) { u.resize((size_t)W * H); v.resize((size_t)W * H); }
     std::vector<uint8_t> scratch((size_t)W * H);
     double total = 0.0;
-    int count = 0;
+    int count = 0, verdict = SDK_SUCCESS;
     for (int i = 1; pnm::load_image(camera_frame(i), frame); i++) {
         pnm::to_gray(frame, gnew);
         if (gnew.width != W || gnew.height != H) break;
@@ -278,6 +312,8 @@ int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
         if (st == HSFLOW_OK) st = hsflow_get_frames_u8(ctx, 0, scratch.data(), (size_t)W, gold.data.data(), (size_t)W);
         if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; hsflow_destroy(ctx); return 1; }
         count++;
+        hsflow_verify_report report;
+        if (verify_wanted() && verify_pair(ctx, W, report) != SDK_SUCCESS) verdict = SDK_FAILURE;
         if (getenv("HSFLOW_CAMERA_OUT")) {
             pnm::Image imgFlow;
             if (!on_device) draw_cv_flow(imgFlow, u, v, W, H);
@@ -289,5 +325,5 @@ int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
     }
     hsflow_destroy(ctx);
     if (count) std::cout << "Avg time: " << total / count << " [ms]" << std::endl; // :122 (per frame)
-    return 0;
+    return verdict;
 }

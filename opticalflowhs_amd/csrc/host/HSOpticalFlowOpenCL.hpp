@@ -9,7 +9,9 @@
 //   * planar u8 / fp32 buffers instead of float4 per pixel;
 //   * no per-iteration host<->device copies;
 //   * image files are binary PGM/PPM (no OpenCV highgui on this platform);
-//   * dType "CPU" is refused: this build has no CPU path.
+//   * dType "CPU" is refused: this build has no CPU path;
+//   * verifyResults() verifies: the last pair is re-solved sweep by sweep on the device and compared there
+//     (hsflow_verify).  run() calls it after every pair when HSFLOW_VERIFY=1.
 // The "-cl" route runs the reference kernels' own discretisation (HSFLOW_MODE_CLASSIC, alpha);
 // the "-cv" route (class OpticalFlowOpenCV below) runs the OpenCV one (graded semantics).
 #pragma once
@@ -19,6 +21,7 @@
 #include "../../../include/hsflow.h"
 #include "jpeg_baseline.hpp"
 #include "jpeg_encode.hpp"
+#include "verify_line.hpp"
 
 #define SDK_SUCCESS 0 /* SDKUtil/include/SDKCommon.hpp:23 */
 #define SDK_FAILURE 1 /* SDKUtil/include/SDKCommon.hpp:24 */
@@ -43,6 +46,8 @@ class HSOpticalFlowOpenCL : public SDKSample {
     bool gpu = true;
     std::string src, input1, input2, output;
     double lastMs = 0.0;
+    bool solved = false;          // a pair has been solved on ctx: verifyResults has something to verify
+    hsflow_verify_report report{}; // of the last verifyResults
 
     int ensureContext(int w, int h);
     int solvePair(const pnm::Image &a, const pnm::Image &b, bool streaming);
@@ -58,7 +63,9 @@ public:
     int setup();           // reference: no-op (:895)
     int run();             // load pair / stream frames, derivatives + iterations, draw, save
     int cleanup();         // releases the context (:849-892)
-    int verifyResults();   // reference: stub returning SDK_SUCCESS (:894)
+    int verifyResults();   // reference: stub returning SDK_SUCCESS (:894).  Here: hsflow_verify of the last pair solved
+                           // (SDK_SUCCESS before any), one "Passed!" / "Failed" line (verify_line.hpp) on stdout
+    const hsflow_verify_report &verifyReport() const { return report; }
 
     const std::vector<float> &flowU() const { return u; }
     const std::vector<float> &flowV() const { return v; }

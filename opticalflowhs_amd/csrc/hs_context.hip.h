@@ -129,6 +129,19 @@ struct hsflow_ctx {
     bool prio_dirty = false;    // a render failed between its two launches: clear the plane before the next one
     uint8_t *dRgb = nullptr;
     hipEvent_t evRender = nullptr;
+    // hsflow_verify / hsflow_compare_flow_device (hs_verify.hip.h), all allocated by the first call: the parameters of the
+    // last solve asked for through the ABI and how it ended; the reference pass's own buffers, held as a second context
+    // object that borrows this one's frames and stream (`shadow`; it is `borrowed`: not counted in g_live_ctx, and it frees
+    // neither the frames nor the stream); the comparison records on the device and in page-locked memory; the event behind
+    // their copy
+    hsflow_params vparams;
+    int vstate = 0;             // 0: no solve yet, 1: the last solve succeeded, 2: it failed
+    int v_org = 0, v_eps_row0 = 0, v_eps_rows = 0; // row origin and Eps rows that solve ran with
+    hsflow_ctx *shadow = nullptr;
+    bool borrowed = false;
+    unsigned long long *dCmp = nullptr, *hCmp = nullptr;
+    int cmp_cap = 0;            // records both hold
+    hipEvent_t evVerify = nullptr;
     size_t scratch_bytes = 0;
     int cur = 0;                // which of dU/dV holds the current flow
     bool frames_set = false;

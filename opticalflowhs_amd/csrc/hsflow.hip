@@ -11,6 +11,7 @@
 #include "hs_kernels_classic.hip.h"
 #include "hs_kernels_classic_strip.hip.h"
 #include "hs_kernels_render.hip.h"
+#include "hs_kernels_verify.hip.h"
 
 #include <atomic>
 #include <chrono>
@@ -208,6 +209,11 @@ int hsflow_destroy(hsflow_ctx *c)
     if (!c) return HSFLOW_OK;
     hipSetDevice(c->device);
     if (c->stream || !c->own_stream) hipStreamSynchronize(c->stream);
+    if (c->shadow) { hsflow_destroy(c->shadow); c->shadow = nullptr; } // hsflow_verify's scratch
+    if (c->borrowed) c->dA = c->dB = nullptr;                           // (the owner's frames)
+    hipFree(c->dCmp);
+    if (c->hCmp) hipHostFree(c->hCmp);
+    if (c->evVerify) hipEventDestroy(c->evVerify);
     for (auto &kv : c->graphs) {
         if (kv.second.exec) hipGraphExecDestroy(kv.second.exec);
         if (kv.second.graph) hipGraphDestroy(kv.second.graph);
@@ -436,6 +442,18 @@ int hsflow_set_eps_rows(hsflow_ctx *c, int first_row, int rows)
     return HSFLOW_OK;
 }
 
+// What hsflow_verify re-solves: the parameters of the last solve asked for through the ABI, and how that ended.
+static int note_solve(hsflow_ctx *c, const hsflow_params *p, int st)
+{
+    if (!c) return st;
+    c->vstate = st ? 2 : 1;
+    if (!st) {
+        c->vparams = *p;
+        c->v_org = c->org; c->v_eps_row0 = c->eps_row0; c->v_eps_rows = c->eps_rows;
+    }
+    return st;
+}
+
 int hsflow_solve_probe(hsflow_ctx *c, const hsflow_params *pp, float *sweep_eps)
 {
     int st = check_ctx(c, 0);
@@ -452,6 +470,11 @@ int hsflow_solve_probe(hsflow_ctx *c, const hsflow_params *pp, float *sweep_eps)
     c->force_exact = true; // the per-sweep pass, not the witness pass
     st = solve_impl(c, &q, false);
     c->force_exact = false;
+    {   // to hsflow_verify a probe is an ITER solve of max_iter sweeps
+        hsflow_params v = *pp;
+        v.term_type = HSFLOW_TERM_ITER;
+        note_solve(c, &v, st);
+    }
     if (st) return st;
     if ((int)c->sweep_eps.size() != pp->max_iter) return fail(c, HSFLOW_E_STATE, "hsflow_solve_probe: the per-sweep pass did not run");
     std::memcpy(sweep_eps, c->sweep_eps.data(), (size_t)pp->max_iter * sizeof(float));
@@ -468,8 +491,8 @@ int hsflow_take_verdict(hsflow_ctx *c, int *proven)
     return settle_pending(c, proven);
 }
 
-int hsflow_solve(hsflow_ctx *c, const hsflow_params *p) { return solve_impl(c, p, false); }
-int hsflow_solve_async(hsflow_ctx *c, const hsflow_params *p) { return solve_impl(c, p, true); }
+int hsflow_solve(hsflow_ctx *c, const hsflow_params *p) { return note_solve(c, p, solve_impl(c, p, false)); }
+int hsflow_solve_async(hsflow_ctx *c, const hsflow_params *p) { return note_solve(c, p, solve_impl(c, p, true)); }
 
 int hsflow_wait_solve(hsflow_ctx *c)
 {
@@ -717,3 +740,4 @@ void hsflow_release_cached(void)
 } // extern "C"
 
 #include "hs_render.hip.h" // hsflow_render_flow[_device], hsflow_default_render_params
+#include "hs_verify.hip.h" // hsflow_verify, hsflow_compare_flow_device, hsflow_compare_planes_host

@@ -304,6 +304,18 @@ int hsflow_pipeline_render_device(hsflow_pipeline *pl, uint64_t ticket, const hs
     return HSFLOW_OK;
 }
 
+int hsflow_pipeline_verify(hsflow_pipeline *pl, uint64_t ticket, hsflow_verify_report *report)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    if (!report || report->struct_size != sizeof(hsflow_verify_report)) return pfail(pl, HSFLOW_E_ARG, "report null or struct_size mismatch");
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    // the slot's context remembers what it ran -- the pipeline's own launch shape included (stream_shape)
+    if ((st = hsflow_verify(s->ctx, 0, report))) return ctx_fail(pl, s->ctx, st, "hsflow_verify");
+    return HSFLOW_OK;
+}
+
 int hsflow_pipeline_wait(hsflow_pipeline *pl, uint64_t ticket)
 {
     if (!pl) return HSFLOW_E_ARG;

@@ -11,7 +11,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import HsflowError, HsflowInfo, TERM_ITER
+from ._lib import HsflowError, HsflowInfo, HsflowVerifyReport, TERM_ITER
 from .solver import _is_device_tensor, _render_host, _render_target, make_params, make_render_params
 
 
@@ -130,6 +130,15 @@ class PairPipeline(object):
         self._check(self._lib.hsflow_pipeline_render(self._h, int(ticket), ctypes.byref(rp), ctypes.c_void_p(img.ctypes.data), img.strides[0]))
         self._held.pop(int(ticket), None)
         return img
+
+    def verify(self, ticket):
+        """wait(ticket) + `HSFlow.verify` of that pair on its slot (what the slot actually ran, the pipeline's own launch
+        shape included): an `HsflowVerifyReport`.  Raises HsflowError (E_STATE) once `depth` more pairs have been submitted."""
+        r = HsflowVerifyReport()
+        r.struct_size = ctypes.sizeof(HsflowVerifyReport)
+        self._check(self._lib.hsflow_pipeline_verify(self._h, int(ticket), ctypes.byref(r)))
+        self._held.pop(int(ticket), None)
+        return r
 
     def wait(self, ticket):
         self._check(self._lib.hsflow_pipeline_wait(self._h, int(ticket)))

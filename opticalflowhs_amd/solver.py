@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (HsflowError, HsflowInfo, HsflowParams, HsflowRenderParams, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (HsflowError, HsflowInfo, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -255,6 +255,28 @@ class HSFlow(object):
         self._check(self._lib.hsflow_render_flow(self._h, pair, ctypes.byref(rp), _ptr(img), img.strides[0]))
         return img
 
+    def verify(self, pair=-1):
+        """Is the flow held now what a sweep-by-sweep solve of the frames held, with the parameters of the last solve,
+        produces?  Re-solves on the device with the one-sweep kernel behind the stand-alone derivative kernel into
+        scratch of its own and compares there (`hsflow_verify`); nothing is downloaded but the report, an
+        `HsflowVerifyReport` (`ok`, `u`, `v`, `deriv_differing`, `iterations_ref`, ...).  pair=-1: all pairs aggregated."""
+        r = HsflowVerifyReport()
+        r.struct_size = ctypes.sizeof(HsflowVerifyReport)
+        self._check(self._lib.hsflow_verify(self._h, int(pair), ctypes.byref(r)))
+        return r
+
+    def compare_flow(self, u_dev, v_dev, pair=0):
+        """The current flow of `pair` (side a) against two CUDA fp32 tensors of shape (height, width) with unit column
+        stride and any row stride (side b), compared on the device: returns two `HsflowPlaneDiff` (u, v)."""
+        for t in (u_dev, v_dev):
+            if not _is_device_tensor(t) or str(t.dtype) != "torch.float32" or tuple(t.shape) != (self.height, self.width) or \
+                    (self.width > 1 and t.stride(1) != 1):
+                raise ValueError("expected CUDA float32 tensors of shape (height, width) with unit column stride")
+        du, dv = HsflowPlaneDiff(), HsflowPlaneDiff()
+        self._check(self._lib.hsflow_compare_flow_device(self._h, int(pair), _ptr(u_dev), u_dev.stride(0) * 4, _ptr(v_dev),
+                                                         v_dev.stride(0) * 4, ctypes.byref(du), ctypes.byref(dv)))
+        return du, dv
+
     def derivatives(self, pair=0):
         d = [np.empty((self.height, self.width), np.float32) for _ in range(3)]
         self._check(self._lib.hsflow_get_derivatives(self._h, pair, _ptr(d[0]), _ptr(d[1]), _ptr(d[2]),
@@ -272,6 +294,26 @@ class HSFlow(object):
         i.struct_size = ctypes.sizeof(HsflowInfo)
         self._check(self._lib.hsflow_get_info(self._h, ctypes.byref(i)))
         return {name: getattr(i, name) for name, _ in HsflowInfo._fields_}
+
+
+def compare_planes(a, b):
+    """The comparison rule of `HSFlow.verify` over two host fp32 arrays of one 2-D shape (a: the side under test,
+    b: the reference side), on the host -- the same header the device kernel is compiled from; no device needed.
+    Returns an `HsflowPlaneDiff` (differing, failing, nonfinite, first_failing, max_abs_diff, max_ulp)."""
+    lib = _lib.load()
+    a = np.asarray(a)
+    b = np.asarray(b)
+    if a.dtype != np.float32 or b.dtype != np.float32 or a.ndim != 2 or a.shape != b.shape:
+        raise ValueError("expected two float32 arrays of the same 2-D shape")
+    if a.shape[1] > 1 and a.strides[1] != 4:
+        a = np.ascontiguousarray(a)
+    if b.shape[1] > 1 and b.strides[1] != 4:
+        b = np.ascontiguousarray(b)
+    d = HsflowPlaneDiff()
+    st = lib.hsflow_compare_planes_host(_ptr(a), a.strides[0], _ptr(b), b.strides[0], a.shape[1], a.shape[0], ctypes.byref(d))
+    if st:
+        raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
+    return d
 
 
 def plan_query(width, height, n_pairs=1, params=None, **kw):
