@@ -29,6 +29,20 @@ struct JPlan {
     StripPlan s{};
 };
 
+// What a Jacobi launch records about Eps = max |u_k - u_{k-1}|, |v_k - v_{k-1}| (the kernels' EPS template argument).
+enum class EpsMode : int {
+    None = 0,
+    EverySweep = 1,  // the exact Eps of every sweep
+    Witness = 2,     // strip / fold: one lower bound per launch and workgroup that proves "no sweep of mine fell below epsilon"
+    WitnessLast = 3, // the witness, and the exact Eps of the last sweep (two words per workgroup)
+};
+
+// Layout of the Eps words of one pass in dEpsTiles (k_eps_reduce's arguments): `slots` rows of `stride` words; the
+// first n_first rows hold cnt_first valid words (one per workgroup of a full launch), the others cnt_last.
+struct EpsLayout {
+    int slots = 0, stride = 1, n_first = 0, cnt_first = 0, cnt_last = 0;
+};
+
 struct GraphKey {
     int mode, kernel, max_iter, T, tw, th, nt, lr, cur, use_prev; // lr: K (fused) or R (strip)
     float coeff;
@@ -152,8 +166,8 @@ struct hsflow_ctx {
     struct Pending {
         bool active = false;
         hsflow_params params;
-        int iters = 0, slots = 0, launches = 0, cur0 = 0;
-        int stride = 1, n_first = 0, cnt_first = 0, cnt_last = 0; // layout of its witness words (k_eps_reduce's arguments)
+        int iters = 0, launches = 0, cur0 = 0;
+        EpsLayout words;        // its witness words
         bool reduced = false;   // the reduction into hEps was enqueued with the solve (async_reduce)
         unsigned mark = 0;      // ... and the marker behind it
         bool marked_by_reduce = false; // ... written by the reduction kernel's last workgroup
@@ -163,11 +177,15 @@ struct hsflow_ctx {
     struct LastLaunch {
         bool valid = false;    // last_eps not measured yet
         JPlan plan;
-        int in = 0, zero_in = 0;
+        int zero_in = 0;
         float coeff = 0.f, eps_thr = 0.f;
         bool from_third = false; // its input lies in dUp / dVp (last phase of a persistent launch), not the other ping-pong buffer
     } lastl;
     bool force_exact = false; // the exact per-sweep pass is wanted (set while a pending solve is settled)
+    // A dry run of an enqueue sequence ahead of its stream capture (run_captured): kernel attributes cannot be set inside a
+    // capture, so the sequence is walked once with this set -- the launch wrappers then only raise the dynamic-LDS cap of
+    // the kernel variant they would launch, and whatever else enqueues work returns at once.
+    bool configuring = false;
     std::map<GraphKey, GraphEntry> graphs;
     std::vector<PlanEntry> plan_cache; // prepare_solve's results by parameters; cleared when what they rest on changes
     std::vector<hipEvent_t> events;

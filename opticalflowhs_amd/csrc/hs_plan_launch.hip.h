@@ -3,16 +3,16 @@
 #pragma once
 
 namespace {
-// How many compute units the planners count on.  A context that shares the device with other contexts' solves in flight
-// (the slots of a pair pipeline: hsflow_set_cu_share) plans for its share of the chip: the shapes that minimise the
-// CU-time of a solve -- few large tiles, little halo redundancy -- instead of those that spread one small frame thinly
-// over all 256 CUs to shorten ITS latency while the other solves wait.  With a share the launch has no round structure
-// of its own (its workgroups start wherever a CU falls free), so the cost models then count fractional rounds.
 // rows whose changes count for Eps / the witness (hsflow_set_eps_rows; the whole frame unless narrowed)
 int eps_row0(const hsflow_ctx *c) { return c->eps_rows > 0 ? c->eps_row0 : 0; }
 int eps_row1(const hsflow_ctx *c) { return c->eps_rows > 0 ? c->eps_row0 + c->eps_rows : c->H; }
 bool eps_windowed(const hsflow_ctx *c) { return c->eps_rows > 0 && (c->eps_row0 > 0 || c->eps_rows < c->H); }
 
+// How many compute units the planners count on.  A context that shares the device with other contexts' solves in flight
+// (the slots of a pair pipeline: hsflow_set_cu_share) plans for its share of the chip: the shapes that minimise the
+// CU-time of a solve -- few large tiles, little halo redundancy -- instead of those that spread one small frame thinly
+// over all 256 CUs to shorten ITS latency while the other solves wait.  With a share the launch has no round structure
+// of its own (its workgroups start wherever a CU falls free), so the cost models then count fractional rounds.
 int plan_cus(const hsflow_ctx *c) { return c->cu_share > 0 ? c->cu_share : kNumCU; }
 bool plan_shared(const hsflow_ctx *c) { return c->cu_share > 0 && c->cu_share < kNumCU; }
 
@@ -76,75 +76,73 @@ bool make_plan(const hsflow_ctx *c, int T, int tw, int th, int nt, FusedPlan &be
     return found;
 }
 
-template <int NT, int K, bool EPS, int LR>
-hipError_t launch_fused_t(const hsflow_ctx *c, const FusedPlan &p, const float *ui, const float *vi,
-                          float *uo, float *vo, float coeff, bool configure_only)
+// Raises the dynamic-LDS cap of the kernel Kern to the whole LDS of a CU, once per kernel (one flag array per instantiation
+// of this template) and device; several host threads may get here.
+template <auto Kern>
+hipError_t raise_lds_cap(const hsflow_ctx *c)
 {
-    auto kern = hsk::k_jacobi_fused<NT, K, EPS, LR>;
-    static std::atomic<bool> configured[64]; // per instantiation and device: raise the dynamic-LDS cap once (several host threads may get here)
-    if (p.lds_bytes > 32 * 1024 && !configured[c->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
+    static std::atomic<bool> done[64];
+    if (done[c->device & 63]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
+    if (e == hipSuccess) done[c->device & 63] = true;
+    return e;
+}
+
+// Launches Kern on the context's stream; a launch that needs more dynamic LDS than the default cap has the cap raised first.
+// In a dry run ahead of a stream capture (hsflow_ctx::configuring) that is all it does.
+template <auto Kern, class... Args>
+hipError_t launch_lds(const hsflow_ctx *c, int tiles, int threads, int lds_bytes, Args... args)
+{
+    if (lds_bytes > 32 * 1024) {
+        const hipError_t e = raise_lds_cap<Kern>(c);
         if (e != hipSuccess) return e;
-        configured[c->device & 63] = true;
     }
-    if (configure_only) return hipSuccess; // done ahead of a stream capture
-    hipLaunchKernelGGL(kern, dim3(p.tiles), dim3(NT), p.lds_bytes, c->stream, c->dCoef, ui, vi, uo,
-                       vo, p.g, coeff, c->epsPtr, c->epsStride);
+    if (c->configuring) return hipSuccess;
+    hipLaunchKernelGGL(Kern, dim3(tiles), dim3(threads), lds_bytes, c->stream, args...);
     return hipGetLastError();
 }
 
-template <bool EPS, int LR>
-hipError_t launch_fused_e(const hsflow_ctx *c, const FusedPlan &p, const float *ui, const float *vi,
-                          float *uo, float *vo, float coeff, bool cfg)
+// The shapes (threads, groups per thread) the LDS-tile kernels are compiled for
+#define HS_FUSED_SHAPES(X)                                                                        \
+    X(1024, 1) X(1024, 2) X(1024, 3) X(512, 1) X(512, 2) X(512, 3) X(512, 4) X(256, 1) X(256, 2) X(256, 3) X(256, 4)
+
+template <bool EPS>
+hipError_t launch_fused_e(const hsflow_ctx *c, const FusedPlan &p, const float *ui, const float *vi, float *uo, float *vo, float coeff)
 {
 #define HS_CASE(NT_, K_)                                                                          \
-    if (p.NT == NT_ && p.K == K_) return launch_fused_t<NT_, K_, EPS, LR>(c, p, ui, vi, uo, vo, coeff, cfg);
-    HS_CASE(1024, 1) HS_CASE(1024, 2) HS_CASE(1024, 3)
-    HS_CASE(512, 1) HS_CASE(512, 2) HS_CASE(512, 3) HS_CASE(512, 4)
-    HS_CASE(256, 1) HS_CASE(256, 2) HS_CASE(256, 3) HS_CASE(256, 4)
+    if (p.NT == NT_ && p.K == K_)                                                                 \
+        return launch_lds<hsk::k_jacobi_fused<NT_, K_, EPS, 1>>(c, p.tiles, NT_, p.lds_bytes, c->dCoef, ui, vi, uo, vo, p.g, coeff, \
+                                                                c->epsPtr, c->epsStride);
+    HS_FUSED_SHAPES(HS_CASE)
 #undef HS_CASE
     return hipErrorInvalidConfiguration;
 }
 
-hipError_t launch_fused(const hsflow_ctx *c, const FusedPlan &p, bool eps, int lr, const float *ui,
-                        const float *vi, float *uo, float *vo, float coeff, bool cfg = false)
+hipError_t launch_fused(const hsflow_ctx *c, const FusedPlan &p, bool eps, const float *ui, const float *vi, float *uo, float *vo,
+                        float coeff)
 {
-    if (eps) return lr ? launch_fused_e<true, 1>(c, p, ui, vi, uo, vo, coeff, cfg)
-                       : launch_fused_e<true, 0>(c, p, ui, vi, uo, vo, coeff, cfg);
-    return lr ? launch_fused_e<false, 1>(c, p, ui, vi, uo, vo, coeff, cfg)
-              : launch_fused_e<false, 0>(c, p, ui, vi, uo, vo, coeff, cfg);
+    return eps ? launch_fused_e<true>(c, p, ui, vi, uo, vo, coeff) : launch_fused_e<false>(c, p, ui, vi, uo, vo, coeff);
 }
 
-
-template <int NT, int K>
-hipError_t launch_classic_fused_t(const hsflow_ctx *c, const FusedPlan &p, bool write_v, const float *ui, const float *vi,
-                                  float *uo, float *vo, float alpha2, bool configure_only)
+template <bool WRITE_V>
+hipError_t launch_classic_fused_w(const hsflow_ctx *c, const FusedPlan &p, const float *ui, const float *vi, float *uo, float *vo,
+                                  float alpha2)
 {
-    auto kern = write_v ? hsk::k_jacobi_classic_fused<NT, K, true> : hsk::k_jacobi_classic_fused<NT, K, false>;
-    static std::atomic<bool> configured[2][64];
-    if (p.lds_bytes > 32 * 1024 && !configured[write_v][c->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-        if (e != hipSuccess) return e;
-        configured[write_v][c->device & 63] = true;
-    }
-    if (configure_only) return hipSuccess;
-    hipLaunchKernelGGL(kern, dim3(p.tiles), dim3(NT), p.lds_bytes, c->stream, c->dE[0], c->dE[1], c->dE[2], ui, vi, uo, vo, p.g, alpha2);
-    return hipGetLastError();
+#define HS_CASE(NT_, K_)                                                                          \
+    if (p.NT == NT_ && p.K == K_)                                                                 \
+        return launch_lds<hsk::k_jacobi_classic_fused<NT_, K_, WRITE_V>>(c, p.tiles, NT_, p.lds_bytes, c->dE[0], c->dE[1], c->dE[2], ui, \
+                                                                         vi, uo, vo, p.g, alpha2);
+    HS_FUSED_SHAPES(HS_CASE)
+#undef HS_CASE
+    return hipErrorInvalidConfiguration;
 }
 
 hipError_t launch_classic_fused(const hsflow_ctx *c, const FusedPlan &p, bool write_v, const float *ui, const float *vi,
-                                float *uo, float *vo, float alpha2, bool cfg = false)
+                                float *uo, float *vo, float alpha2)
 {
-#define HS_CASE(NT_, K_)                                                                          \
-    if (p.NT == NT_ && p.K == K_) return launch_classic_fused_t<NT_, K_>(c, p, write_v, ui, vi, uo, vo, alpha2, cfg);
-    HS_CASE(1024, 1) HS_CASE(1024, 2) HS_CASE(1024, 3)
-    HS_CASE(512, 1) HS_CASE(512, 2) HS_CASE(512, 3) HS_CASE(512, 4)
-    HS_CASE(256, 1) HS_CASE(256, 2) HS_CASE(256, 3) HS_CASE(256, 4)
-#undef HS_CASE
-    return hipErrorInvalidConfiguration;
+    return write_v ? launch_classic_fused_w<true>(c, p, ui, vi, uo, vo, alpha2) : launch_classic_fused_w<false>(c, p, ui, vi, uo, vo, alpha2);
 }
+
 
 // ------------------------------------------------------------------------------------------
 // Classic mode, register strip kernel (hs_kernels_classic_strip.hip.h): plan and launch.
@@ -250,39 +248,34 @@ int pick_classic_strip_T(const hsflow_ctx *c, int iters, int rows, int threads)
 
 template <int R, int NTMAX>
 hipError_t launch_classic_strip_t(const hsflow_ctx *c, const ClassicStripPlan &p, bool write_v, const float *ui, const float *vi,
-                                  float *uo, float *vo, float alpha2, bool configure_only)
+                                  float *uo, float *vo, float alpha2)
 {
-    const bool ghost = (p.g.W & 3) != 0;
-    auto kern = write_v ? (ghost ? hsk::k_classic_strip<R, NTMAX, true, true> : hsk::k_classic_strip<R, NTMAX, true, false>)
-                        : (ghost ? hsk::k_classic_strip<R, NTMAX, false, true> : hsk::k_classic_strip<R, NTMAX, false, false>);
-    static std::atomic<bool> configured[4][64];
-    const int ki = (write_v ? 2 : 0) + (ghost ? 1 : 0);
-    if (p.lds_bytes > 32 * 1024 && !configured[ki][c->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-        if (e != hipSuccess) return e;
-        configured[ki][c->device & 63] = true;
-    }
-    if (configure_only) return hipSuccess;
     if (p.g.zero_in) ui = vi = c->dZero; // (flow from zero: one row of zeros stands in for both planes)
-    hipLaunchKernelGGL(kern, dim3(p.tiles), dim3(p.g.NW * 64), p.lds_bytes, c->stream, c->dCoef, ui, vi, uo, vo, p.g, alpha2);
-    return hipGetLastError();
+    auto go = [&](auto wv, auto ghost) {
+        return launch_lds<hsk::k_classic_strip<R, NTMAX, decltype(wv)::value, decltype(ghost)::value>>(
+            c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dCoef, ui, vi, uo, vo, p.g, alpha2);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    const bool ghost = (p.g.W & 3) != 0;
+    return write_v ? (ghost ? go(yes, yes) : go(yes, no)) : (ghost ? go(no, yes) : go(no, no));
 }
 
 hipError_t launch_classic_strip(const hsflow_ctx *c, const ClassicStripPlan &p, bool write_v, const float *ui, const float *vi,
-                                float *uo, float *vo, float alpha2, bool cfg = false)
+                                float *uo, float *vo, float alpha2)
 {
     switch (p.R) {
-    case 2: return launch_classic_strip_t<2, 1024>(c, p, write_v, ui, vi, uo, vo, alpha2, cfg);
-    case 3: return launch_classic_strip_t<3, 1024>(c, p, write_v, ui, vi, uo, vo, alpha2, cfg);
-    case 4: return launch_classic_strip_t<4, 768>(c, p, write_v, ui, vi, uo, vo, alpha2, cfg);
-    case 5: return launch_classic_strip_t<5, 768>(c, p, write_v, ui, vi, uo, vo, alpha2, cfg);
-    case 6: return launch_classic_strip_t<6, 512>(c, p, write_v, ui, vi, uo, vo, alpha2, cfg);
-    case 7: return launch_classic_strip_t<7, 512>(c, p, write_v, ui, vi, uo, vo, alpha2, cfg);
-    case 8: return launch_classic_strip_t<8, 512>(c, p, write_v, ui, vi, uo, vo, alpha2, cfg);
+    case 2: return launch_classic_strip_t<2, 1024>(c, p, write_v, ui, vi, uo, vo, alpha2);
+    case 3: return launch_classic_strip_t<3, 1024>(c, p, write_v, ui, vi, uo, vo, alpha2);
+    case 4: return launch_classic_strip_t<4, 768>(c, p, write_v, ui, vi, uo, vo, alpha2);
+    case 5: return launch_classic_strip_t<5, 768>(c, p, write_v, ui, vi, uo, vo, alpha2);
+    case 6: return launch_classic_strip_t<6, 512>(c, p, write_v, ui, vi, uo, vo, alpha2);
+    case 7: return launch_classic_strip_t<7, 512>(c, p, write_v, ui, vi, uo, vo, alpha2);
+    case 8: return launch_classic_strip_t<8, 512>(c, p, write_v, ui, vi, uo, vo, alpha2);
     }
     return hipErrorInvalidConfiguration;
 }
+
 
 // ------------------------------------------------------------------------------------------
 // Planner for the strip kernel: rows per lane R and wavefronts per workgroup NW.
@@ -386,118 +379,98 @@ int pick_strip_T(const hsflow_ctx *c, int iters, const hsflow_params &p, int fol
 // (strips that start on an odd row keep their rows in reverse order instead).
 int strip_phase(const StripPlan &p) { return (p.fold || (p.R & 1) == 0) ? ((p.g.T + p.g.org) & 1) : 0; }
 
-template <int R, int NTMAX, int EPS, bool FOLD, int E0> // EPS: 0 none, 1 every sweep, 2 witness, 3 witness + last sweep measured
-hipError_t launch_strip_te(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi,
-                           float *uo, float *vo, float coeff, bool configure_only)
+// One chain from (R, NW, fold, Eps mode, deriv, phase) to the kernel instantiation, outermost choice first: launch_j picks
+// the Eps mode, then fold / deriv (launch_strip_m), the rows per lane (launch_strip_e), the thread limit (launch_strip_r),
+// the phase (launch_strip_t); launch_strip_k launches.  Choices that rest on template constants alone are `if constexpr`,
+// so a combination no caller reaches is not compiled.
+// DERIV: the strip / folded kernel with the derivative pass in its load phase (first launch of a solve); compiled for up
+// to 6 rows per lane and never with EpsMode::EverySweep (the exact pass runs the derivative kernel: strip_deriv_fusable).
+template <int R, int NTMAX, int EPS, bool FOLD, bool DERIV, int E0>
+constexpr auto strip_kernel()
 {
-    auto kern = [] {
-        if constexpr (FOLD) return hsk::k_jacobi_fold<R, NTMAX, EPS, E0>;
-        else return hsk::k_jacobi_strip<R, NTMAX, EPS, E0>;
-    }();
-    static std::atomic<bool> configured[64];
-    if (p.lds_bytes > 32 * 1024 && !configured[c->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-        if (e != hipSuccess) return e;
-        configured[c->device & 63] = true;
-    }
-    if (configure_only) return hipSuccess;
-    if (p.g.zero_in) ui = vi = c->dZero; // flow from zero: one row of zeros stands in for both planes (StripGeom::zero_in)
-    hipLaunchKernelGGL(kern, dim3(p.tiles), dim3(p.g.NW * 64), p.lds_bytes, c->stream, c->dCoef, ui, vi,
-                       uo, vo, p.g, coeff, c->epsPtr, c->epsStride, p.tiles <= 65536 ? c->dStamps : nullptr, c->epsThr);
-    return hipGetLastError();
+    if constexpr (FOLD && DERIV) return hsk::k_jacobi_fold_deriv<R, NTMAX, EPS, E0>;
+    else if constexpr (FOLD) return hsk::k_jacobi_fold<R, NTMAX, EPS, E0>;
+    else if constexpr (DERIV) return hsk::k_jacobi_strip_deriv<R, NTMAX, EPS, E0>;
+    else return hsk::k_jacobi_strip<R, NTMAX, EPS, E0>;
 }
 
-template <int R, int NTMAX, int EPS, bool FOLD>
-hipError_t launch_strip_t(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi,
-                          float *uo, float *vo, float coeff, bool cfg)
+template <int R, int NTMAX, EpsMode EPS, bool FOLD, bool DERIV, int E0>
+hipError_t launch_strip_k(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi, float *uo, float *vo, float coeff)
+{
+    constexpr auto kern = strip_kernel<R, NTMAX, (int)EPS, FOLD, DERIV, E0>();
+    if (p.g.zero_in) ui = vi = c->dZero; // flow from zero: one row of zeros stands in for both planes (StripGeom::zero_in)
+    unsigned long long *stamps = p.tiles <= 65536 ? c->dStamps : nullptr;
+    if constexpr (DERIV) // (the kernel takes the two frames ahead of the coefficient plane it writes)
+        return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dA, c->dB, c->dCoef, ui, vi, uo, vo, p.g, coeff, c->epsPtr,
+                                c->epsStride, stamps, c->epsThr);
+    else
+        return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dCoef, ui, vi, uo, vo, p.g, coeff, c->epsPtr, c->epsStride,
+                                stamps, c->epsThr);
+}
+
+template <int R, int NTMAX, EpsMode EPS, bool FOLD, bool DERIV>
+hipError_t launch_strip_t(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi, float *uo, float *vo, float coeff)
 {
     if constexpr (FOLD || (R & 1) == 0) {
-        if (strip_phase(p)) return launch_strip_te<R, NTMAX, EPS, FOLD, 1>(c, p, ui, vi, uo, vo, coeff, cfg);
+        if (strip_phase(p)) return launch_strip_k<R, NTMAX, EPS, FOLD, DERIV, 1>(c, p, ui, vi, uo, vo, coeff);
     }
-    return launch_strip_te<R, NTMAX, EPS, FOLD, 0>(c, p, ui, vi, uo, vo, coeff, cfg);
+    return launch_strip_k<R, NTMAX, EPS, FOLD, DERIV, 0>(c, p, ui, vi, uo, vo, coeff);
 }
 
-template <int EPS, bool FOLD>
-hipError_t launch_strip_e(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi,
-                          float *uo, float *vo, float coeff, bool cfg)
+// The thread limit (__launch_bounds__) the kernels for R rows per lane are compiled with.  narrow: an Eps mode is on and
+// the plan has at most 12 wavefronts, which only the 5-row strip kernel tells apart.
+constexpr int strip_ntmax(int R, bool fold, bool narrow)
+{
+    return R <= 4 ? 1024 : R == 5 ? (fold || narrow ? 768 : 1024) : R == 6 ? (fold ? 512 : 768) : 512;
+}
+
+template <int R, EpsMode EPS, bool FOLD, bool DERIV>
+hipError_t launch_strip_r(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi, float *uo, float *vo, float coeff)
+{
+    constexpr int NT = strip_ntmax(R, FOLD, false), NT_NARROW = strip_ntmax(R, FOLD, EPS != EpsMode::None);
+    if constexpr (NT_NARROW != NT) {
+        if (p.g.NW <= 12) return launch_strip_t<R, NT_NARROW, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+    }
+    return launch_strip_t<R, NT, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+}
+
+template <EpsMode EPS, bool FOLD, bool DERIV>
+hipError_t launch_strip_e(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi, float *uo, float *vo, float coeff)
 {
 #ifdef HS_DIAG_MIN /* diagnostic builds (tools/diag_build.sh): the R = 4 / 5 / 6 strip kernels without Eps only */
-    if constexpr (!FOLD && EPS == 0) {
-        if (p.R == 4) return launch_strip_t<4, 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-        if (p.R == 5) return launch_strip_t<5, 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-        if (p.R == 6) return launch_strip_t<6, 768, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
+    if constexpr (!FOLD && !DERIV && EPS == EpsMode::None) {
+        if (p.R == 4) return launch_strip_r<4, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+        if (p.R == 5) return launch_strip_r<5, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+        if (p.R == 6) return launch_strip_r<6, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
     }
-    return hipErrorInvalidConfiguration;
 #else
     switch (p.R) {
-    case 1: return launch_strip_t<1, 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 2: return launch_strip_t<2, 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 3: return launch_strip_t<3, 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 4: return launch_strip_t<4, 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 5:
-        if (!FOLD && EPS && p.g.NW <= 12) return launch_strip_t<5, 768, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-        return launch_strip_t<5, FOLD ? 768 : 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 6: return launch_strip_t<6, FOLD ? 512 : 768, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 7: return launch_strip_t<7, 512, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 8: return launch_strip_t<8, 512, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
+    case 1: return launch_strip_r<1, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+    case 2: return launch_strip_r<2, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+    case 3: return launch_strip_r<3, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+    case 4: return launch_strip_r<4, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+    case 5: return launch_strip_r<5, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+    case 6: return launch_strip_r<6, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
     }
-    return hipErrorInvalidConfiguration;
+    if constexpr (!DERIV) {
+        if (p.R == 7) return launch_strip_r<7, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+        if (p.R == 8) return launch_strip_r<8, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+    }
 #endif
-}
-
-// The strip / folded kernel with the derivative pass in its load phase (first launch of a solve).
-template <int R, int NTMAX, int EPS, bool FOLD, int E0>
-hipError_t launch_strip_deriv_te(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi,
-                                 float *uo, float *vo, float coeff, bool configure_only)
-{
-    auto kern = [] {
-        if constexpr (FOLD) return hsk::k_jacobi_fold_deriv<R, NTMAX, EPS, E0>;
-        else return hsk::k_jacobi_strip_deriv<R, NTMAX, EPS, E0>;
-    }();
-    static std::atomic<bool> configured[64];
-    if (p.lds_bytes > 32 * 1024 && !configured[c->device & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-        if (e != hipSuccess) return e;
-        configured[c->device & 63] = true;
-    }
-    if (configure_only) return hipSuccess;
-    if (p.g.zero_in) ui = vi = c->dZero;
-    hipLaunchKernelGGL(kern, dim3(p.tiles), dim3(p.g.NW * 64), p.lds_bytes, c->stream, c->dA, c->dB, c->dCoef, ui, vi,
-                       uo, vo, p.g, coeff, c->epsPtr, c->epsStride, p.tiles <= 65536 ? c->dStamps : nullptr, c->epsThr);
-    return hipGetLastError();
-}
-
-template <int R, int NTMAX, int EPS, bool FOLD>
-hipError_t launch_strip_deriv_t(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi,
-                                float *uo, float *vo, float coeff, bool cfg)
-{
-    if constexpr (FOLD || (R & 1) == 0) {
-        if (strip_phase(p)) return launch_strip_deriv_te<R, NTMAX, EPS, FOLD, 1>(c, p, ui, vi, uo, vo, coeff, cfg);
-    }
-    return launch_strip_deriv_te<R, NTMAX, EPS, FOLD, 0>(c, p, ui, vi, uo, vo, coeff, cfg);
-}
-
-template <int EPS, bool FOLD>
-hipError_t launch_strip_deriv_e(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi,
-                                float *uo, float *vo, float coeff, bool cfg)
-{
-#ifdef HS_DIAG_MIN
     return hipErrorInvalidConfiguration;
-#else
-    switch (p.R) { // the same thread limits as launch_strip_e
-    case 1: return launch_strip_deriv_t<1, 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 2: return launch_strip_deriv_t<2, 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 3: return launch_strip_deriv_t<3, 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 4: return launch_strip_deriv_t<4, 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 5:
-        if (!FOLD && EPS && p.g.NW <= 12) return launch_strip_deriv_t<5, 768, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-        return launch_strip_deriv_t<5, FOLD ? 768 : 1024, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
-    case 6: return launch_strip_deriv_t<6, FOLD ? 512 : 768, EPS, FOLD>(c, p, ui, vi, uo, vo, coeff, cfg);
+}
+
+template <EpsMode EPS>
+hipError_t launch_strip_m(const hsflow_ctx *c, const StripPlan &p, bool deriv, const float *ui, const float *vi, float *uo, float *vo,
+                          float coeff)
+{
+    if constexpr (EPS != EpsMode::EverySweep) {
+        if (deriv) return p.fold ? launch_strip_e<EPS, true, true>(c, p, ui, vi, uo, vo, coeff)
+                                 : launch_strip_e<EPS, false, true>(c, p, ui, vi, uo, vo, coeff);
     }
-    return hipErrorInvalidConfiguration;
-#endif
+    if (deriv) return hipErrorInvalidConfiguration;
+    return p.fold ? launch_strip_e<EPS, true, false>(c, p, ui, vi, uo, vo, coeff)
+                  : launch_strip_e<EPS, false, false>(c, p, ui, vi, uo, vo, coeff);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -523,15 +496,15 @@ const char *persist_obstacle(const hsflow_ctx *c, const StripPlan &sp, int iters
     return nullptr;
 }
 
-template <int R, int NTMAX, int EPS, bool DERIV, int E0>
-hipError_t launch_persist_te(hsflow_ctx *c, const StripPlan &p, const hsk::PersistArgs &pa, const float *ui, const float *vi,
-                             float coeff, bool configure_only)
+// (compiled for 5 rows per lane, up to 1024 threads, plain or witness phases: persist_obstacle)
+template <EpsMode EPS, bool DERIV>
+hipError_t launch_persist_t(hsflow_ctx *c, const StripPlan &p, const hsk::PersistArgs &pa, const float *ui, const float *vi, float coeff)
 {
-    auto kern = hsk::k_jacobi_strip_persist<R, NTMAX, EPS, E0, DERIV>;
+    constexpr auto kern = hsk::k_jacobi_strip_persist<5, 1024, (int)EPS, 0, DERIV>;
     static std::atomic<int> resident[64]; // workgroups per CU the runtime promises for this shape (0: not asked yet)
     const int dv = c->device & 63;
     if (resident[dv].load() == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
+        hipError_t e = raise_lds_cap<kern>(c);
         if (e != hipSuccess) return e;
         int nb = 0;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kern), p.g.NW * 64, (size_t)p.lds_bytes);
@@ -539,23 +512,22 @@ hipError_t launch_persist_te(hsflow_ctx *c, const StripPlan &p, const hsk::Persi
         resident[dv] = nb >= 1 ? nb : -1;
     }
     if (resident[dv].load() < 1) return hipErrorCooperativeLaunchTooLarge;
-    if (configure_only) return hipSuccess;
     if (p.g.zero_in) ui = vi = c->dZero;
-    hipLaunchKernelGGL(kern, dim3(p.tiles), dim3(p.g.NW * 64), p.lds_bytes, c->stream, c->dA, c->dB, c->dCoef, ui, vi, p.g, coeff,
-                       c->epsPtr, c->epsStride, p.tiles <= 8192 ? c->dStamps : nullptr, c->epsThr, pa);
-    return hipGetLastError();
+    return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dA, c->dB, c->dCoef, ui, vi, p.g, coeff, c->epsPtr, c->epsStride,
+                            p.tiles <= 8192 ? c->dStamps : nullptr, c->epsThr, pa);
 }
 
-// eps: 0 plain phases, 2 witness phases (one row of c->epsStride words per phase at c->epsPtr)
-hipError_t launch_persist(hsflow_ctx *c, const StripPlan &sp, const hsk::PersistArgs &pa, int eps, bool deriv, const float *ui,
-                          const float *vi, float coeff, bool cfg = false)
+// eps: None plain phases, Witness witness phases (one row of c->epsStride words per phase at c->epsPtr)
+hipError_t launch_persist(hsflow_ctx *c, const StripPlan &sp, const hsk::PersistArgs &pa, EpsMode eps, bool deriv, const float *ui,
+                          const float *vi, float coeff)
 {
     if (sp.R != 5) return hipErrorInvalidConfiguration;
-    if (eps == 2) return deriv ? launch_persist_te<5, 1024, 2, true, 0>(c, sp, pa, ui, vi, coeff, cfg)
-                               : launch_persist_te<5, 1024, 2, false, 0>(c, sp, pa, ui, vi, coeff, cfg);
-    return deriv ? launch_persist_te<5, 1024, 0, true, 0>(c, sp, pa, ui, vi, coeff, cfg)
-                 : launch_persist_te<5, 1024, 0, false, 0>(c, sp, pa, ui, vi, coeff, cfg);
+    if (eps == EpsMode::Witness) return deriv ? launch_persist_t<EpsMode::Witness, true>(c, sp, pa, ui, vi, coeff)
+                                              : launch_persist_t<EpsMode::Witness, false>(c, sp, pa, ui, vi, coeff);
+    return deriv ? launch_persist_t<EpsMode::None, true>(c, sp, pa, ui, vi, coeff)
+                 : launch_persist_t<EpsMode::None, false>(c, sp, pa, ui, vi, coeff);
 }
+
 
 // Can the first launch of a solve compute the derivatives itself (k_jacobi_strip_deriv / k_jacobi_fold_deriv)?
 // The kernels' reflection argument wants a single bounce: an image at least as large as one workgroup's
@@ -628,38 +600,27 @@ bool make_witness_jplan(const hsflow_ctx *c, int kind, int T, const hsflow_param
     return false;
 }
 
-// eps: 0 none, 1 Eps of every sweep, 2 witness (strip / fold: one lower bound per launch), 3 witness + the exact Eps
-// of the last sweep (two words per workgroup)
+// One launch of pl.T sweeps.  eps: what it records (the LDS-tile kernel knows None and EverySweep only)
 // deriv: this launch also does the derivative pass (only where strip_deriv_fusable() said so)
-hipError_t launch_j(const hsflow_ctx *c, const JPlan &pl, int eps, const float *ui, const float *vi,
-                    float *uo, float *vo, float coeff, bool cfg = false, int zero_in = 0, bool deriv = false)
+hipError_t launch_j(const hsflow_ctx *c, const JPlan &pl, EpsMode eps, const float *ui, const float *vi,
+                    float *uo, float *vo, float coeff, int zero_in = 0, bool deriv = false)
 {
     if (pl.kind == HSFLOW_KERNEL_STRIP || pl.kind == HSFLOW_KERNEL_FOLD) {
         StripPlan sp = pl.s;
         sp.g.zero_in = zero_in;
-        if (eps == 3) { // witness + exact Eps of the last sweep
-            if (sp.fold) return deriv ? launch_strip_deriv_e<3, true>(c, sp, ui, vi, uo, vo, coeff, cfg)
-                                      : launch_strip_e<3, true>(c, sp, ui, vi, uo, vo, coeff, cfg);
-            return deriv ? launch_strip_deriv_e<3, false>(c, sp, ui, vi, uo, vo, coeff, cfg)
-                         : launch_strip_e<3, false>(c, sp, ui, vi, uo, vo, coeff, cfg);
+        switch (eps) {
+        case EpsMode::None: return launch_strip_m<EpsMode::None>(c, sp, deriv, ui, vi, uo, vo, coeff);
+        case EpsMode::EverySweep: return launch_strip_m<EpsMode::EverySweep>(c, sp, deriv, ui, vi, uo, vo, coeff);
+        case EpsMode::Witness: return launch_strip_m<EpsMode::Witness>(c, sp, deriv, ui, vi, uo, vo, coeff);
+        case EpsMode::WitnessLast: return launch_strip_m<EpsMode::WitnessLast>(c, sp, deriv, ui, vi, uo, vo, coeff);
         }
-        if (deriv && sp.fold) return eps == 2 ? launch_strip_deriv_e<2, true>(c, sp, ui, vi, uo, vo, coeff, cfg)
-                                     : eps  ? launch_strip_deriv_e<1, true>(c, sp, ui, vi, uo, vo, coeff, cfg)
-                                            : launch_strip_deriv_e<0, true>(c, sp, ui, vi, uo, vo, coeff, cfg);
-        if (deriv) return eps == 2 ? launch_strip_deriv_e<2, false>(c, sp, ui, vi, uo, vo, coeff, cfg)
-                          : eps  ? launch_strip_deriv_e<1, false>(c, sp, ui, vi, uo, vo, coeff, cfg)
-                                 : launch_strip_deriv_e<0, false>(c, sp, ui, vi, uo, vo, coeff, cfg);
-        if (sp.fold) return eps == 2 ? launch_strip_e<2, true>(c, sp, ui, vi, uo, vo, coeff, cfg)
-                            : eps  ? launch_strip_e<1, true>(c, sp, ui, vi, uo, vo, coeff, cfg)
-                                   : launch_strip_e<0, true>(c, sp, ui, vi, uo, vo, coeff, cfg);
-        return eps == 2 ? launch_strip_e<2, false>(c, sp, ui, vi, uo, vo, coeff, cfg)
-               : eps  ? launch_strip_e<1, false>(c, sp, ui, vi, uo, vo, coeff, cfg)
-                      : launch_strip_e<0, false>(c, sp, ui, vi, uo, vo, coeff, cfg);
+        return hipErrorInvalidConfiguration;
     }
     FusedPlan fp = pl.f;
     fp.g.zero_in = zero_in;
-    return launch_fused(c, fp, eps != 0, 1, ui, vi, uo, vo, coeff, cfg);
+    return launch_fused(c, fp, eps != EpsMode::None, ui, vi, uo, vo, coeff);
 }
+
 
 void plan_to_info(hsflow_ctx *c, const JPlan &pl)
 {
@@ -678,9 +639,11 @@ void plan_to_info(hsflow_ctx *c, const JPlan &pl)
 // pair.  A context may hold more pairs than the device allows in z (hipDeviceAttributeMaxGridDimZ), so they go out in
 // batches of at most max_grid_z pairs, batch by batch the same launch with every plane pointer moved on by its first pair
 // (`launch(first_pair_offset_in_elements, pairs)`).  One launch whenever the pairs fit, as before.
+// In a dry run ahead of a capture (hsflow_ctx::configuring) nothing goes out: these kernels need no attribute.
 template <typename Launch>
 hipError_t for_pair_batches(const hsflow_ctx *c, Launch launch)
 {
+    if (c->configuring) return hipSuccess;
     const int zmax = std::max(1, c->max_grid_z);
     for (int z0 = 0; z0 < c->N; z0 += zmax) {
         launch((long long)z0 * c->plane, std::min(zmax, c->N - z0));

@@ -108,22 +108,34 @@ int persist_prepare_flags(hsflow_ctx *c, int tiles)
 }
 
 // A persistent launch gave up waiting (another grid held part of the CUs, a neighbour never came): the flow it left is
-// invalid.  The context goes back to a launch per fuse_steps iterations for good.
+// invalid, and so is the derivative plane (a workgroup that never started left its part unwritten).  The context goes
+// back to a launch per fuse_steps iterations for good.
 void persist_failed(hsflow_ctx *c)
 {
     if (c->hErr) *c->hErr = 0u;
     c->persist_tiles = 0;
     c->persist_off = true;
     c->persist_unchecked = false;
+    c->coef_valid = false;
     c->plan_cache.clear();
 }
 
 // Did the last persistent launch(es) of this context give up?  Only meaningful once the stream has drained.
 bool persist_error(const hsflow_ctx *c) { return c->hErr && *(volatile unsigned *)c->hErr != 0u; }
 
+// After the stream has drained: looks at the error word an asynchronous persistent solve left unchecked.  True if that
+// launch gave up (persist_failed has been dealt with then; the caller reports it or solves again).
+bool persist_gave_up(hsflow_ctx *c)
+{
+    const bool gave_up = c->persist_unchecked && persist_error(c);
+    c->persist_unchecked = false;
+    if (gave_up) persist_failed(c);
+    return gave_up;
+}
+
 // One persistent launch = `iters` sweeps in phases of sp.g.T: input dU[cur] (or zero), output dU[cur ^ 1]; the phases
 // alternate between that buffer and the third one so that the last phase lands in it.
-int enqueue_persist(hsflow_ctx *c, const StripPlan &sp0, int iters, int eps, bool deriv, int zero_in, float coeff)
+int enqueue_persist(hsflow_ctx *c, const StripPlan &sp0, int iters, EpsMode eps, bool deriv, int zero_in, float coeff)
 {
     StripPlan sp = sp0;
     sp.g.zero_in = zero_in;
@@ -143,6 +155,17 @@ int enqueue_persist(hsflow_ctx *c, const StripPlan &sp0, int iters, int eps, boo
     pa.ub[lastb ^ 1] = c->dUp; pa.vb[lastb ^ 1] = c->dVp;
     HS_HIP(c, launch_persist(c, sp, pa, eps, deriv, c->dU[a], c->dV[a], coeff));
     c->cur = b;
+    return HSFLOW_OK;
+}
+
+// Asks, before anything of a solve is enqueued, whether the persistent kernel it will launch can be resident (and raises
+// its LDS cap): a refusal then leaves the stream and the flow untouched.
+int configure_persist(hsflow_ctx *c, const StripPlan &sp, EpsMode eps, bool deriv, float coeff)
+{
+    c->configuring = true;
+    const hipError_t e = launch_persist(c, sp, hsk::PersistArgs{}, eps, deriv, nullptr, nullptr, coeff);
+    c->configuring = false;
+    HS_HIP(c, e);
     return HSFLOW_OK;
 }
 
@@ -166,7 +189,7 @@ int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters,
     int left = iters, launches = 0;
     if (persist) { // the whole budget as one launch
         prof.begin(1);
-        const int st = enqueue_persist(c, plan->s, iters, 0, fuse, zero_in, coeff);
+        const int st = enqueue_persist(c, plan->s, iters, EpsMode::None, fuse, zero_in, coeff);
         prof.end();
         if (st) return st;
         left = 0;
@@ -182,7 +205,7 @@ int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters,
         } else {
             const JPlan *pl = (left >= T) ? plan : tail_plan;
             prof.begin(1);
-            HS_HIP(c, launch_j(c, *pl, false, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, false, zero_in, fuse));
+            HS_HIP(c, launch_j(c, *pl, EpsMode::None, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, zero_in, fuse));
             prof.end();
             fuse = false;
             left -= pl->T;
@@ -195,10 +218,9 @@ int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters,
     return HSFLOW_OK;
 }
 
-// Eps bookkeeping of an EPS-terminated solve: `sweeps` rows of `stride` words, cleared, plus the
-// reduction of the rows into hEps[0..sweeps).
-// Buffers for `sweeps` Eps words of `stride` workgroups each (device) and their host copy; allocation
-// only, so that what follows can be captured in a graph.
+// Eps bookkeeping of an EPS-terminated solve: `sweeps` rows of `stride` words (one per workgroup) on the device, and
+// the host buffer k_eps_reduce reduces the rows into, hEps[0..sweeps).  eps_reserve allocates only, so that what
+// follows can be captured in a graph; eps_prepare also clears the rows.
 int eps_reserve(hsflow_ctx *c, int sweeps, int stride)
 {
     const size_t need = (size_t)sweeps * stride;
@@ -235,23 +257,24 @@ int eps_prepare(hsflow_ctx *c, int sweeps, int stride)
     return st ? st : eps_clear(c, sweeps, stride);
 }
 
-// Reduces the rows of per-workgroup words to one word per row, straight into the host's buffer (no copy
-// node).  Rows [0, n_first) hold cnt_first valid words, the others cnt_last (defaults: every row is
-// epsStride words, which then must have been cleared where a launch had fewer workgroups).
+// Reduces the rows of per-workgroup words to one word per row, straight into the host's buffer (no copy node), and
+// points the launches that follow back at the Eps sink.
 // mark: the kernel's last workgroup also writes the context's marker (hsflow_set_async_reduce; the caller counts it).
-int eps_collect_enqueue(hsflow_ctx *c, int sweeps, int n_first = 0, int cnt_first = 0, int cnt_last = -1, bool mark = false)
+int eps_collect_enqueue(hsflow_ctx *c, const EpsLayout &w, bool mark = false)
 {
-    hipLaunchKernelGGL(hsk::k_eps_reduce, dim3(sweeps), dim3(256), 0, c->stream, c->dEpsTiles, c->epsStride, c->hEpsDev,
-                       n_first, cnt_first, cnt_last < 0 ? c->epsStride : cnt_last, mark ? c->dSeq : nullptr, mark ? c->hMarkDev : nullptr);
-    HS_HIP(c, hipGetLastError());
     c->epsPtr = c->dEps;
     c->epsStride = 1;
+    if (c->configuring) return HSFLOW_OK;
+    hipLaunchKernelGGL(hsk::k_eps_reduce, dim3(w.slots), dim3(256), 0, c->stream, c->dEpsTiles, w.stride, c->hEpsDev, w.n_first,
+                       w.cnt_first, w.cnt_last, mark ? c->dSeq : nullptr, mark ? c->hMarkDev : nullptr);
+    HS_HIP(c, hipGetLastError());
     return HSFLOW_OK;
 }
 
+// The exact pass: every row is epsStride words, cleared where a launch had fewer workgroups (eps_prepare).
 int eps_collect(hsflow_ctx *c, int sweeps, std::vector<unsigned> &host)
 {
-    int st = eps_collect_enqueue(c, sweeps);
+    int st = eps_collect_enqueue(c, EpsLayout{sweeps, c->epsStride, 0, 0, c->epsStride});
     if (st) return st;
     HS_HIP(c, hipStreamSynchronize(c->stream));
     host.assign(c->hEps, c->hEps + sweeps);

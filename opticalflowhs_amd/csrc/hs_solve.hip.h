@@ -5,23 +5,15 @@
 namespace {
 int solve_impl(hsflow_ctx *c, const hsflow_params *pp, bool async);
 
-// Settles an ITER|EPS solve that hsflow_solve_async left unverified: waits for the stream, looks at the
-// witness words and, if they do not prove "no early stop", runs the exact pass from the saved start.
 // After the stream has drained: did an asynchronous persistent launch give up?  Its flow is invalid then; the context
 // goes back to a launch per fuse_steps iterations and the caller is told.
 int check_persist(hsflow_ctx *c)
 {
-    if (!c->persist_unchecked) return HSFLOW_OK;
-    c->persist_unchecked = false;
-    if (!persist_error(c)) return HSFLOW_OK;
-    persist_failed(c);
-    c->coef_valid = false;
+    if (!persist_gave_up(c)) return HSFLOW_OK;
     return fail(c, HSFLOW_E_DEVICE, "a persistent launch of an asynchronous solve timed out (another grid on the device?): its flow is invalid; "
                                     "this context now launches per fuse_steps iterations, solve again");
 }
 
-// verdict_only: report whether the witness words prove "no early stop" and leave it at that (no exact pass; the flow of
-// the whole budget stands) -- for a driver that decides over several contexts (row slabs: hsflow_take_verdict).
 // Waits until the marker kernel that wrote `target` has run (k_mark_done: everything enqueued before it is done, and what the
 // reduction kernel wrote to host memory is visible).  Polls page-locked memory; gives the stream a proper wait after 2 s.
 int wait_marker(hsflow_ctx *c, unsigned target)
@@ -38,6 +30,30 @@ int wait_marker(hsflow_ctx *c, unsigned target)
     return HSFLOW_OK;
 }
 
+// ITER|EPS with use_previous: the ping-pong buffers get overwritten, so the starting flow is kept in dUb / dVb
+// (allocated by solve_iter_eps) for an exact pass that has to start over from it ...
+int save_start(hsflow_ctx *c)
+{
+    if (c->configuring) return HSFLOW_OK;
+    const size_t bytes = (size_t)c->plane * c->N * sizeof(float);
+    HS_HIP(c, hipMemcpyAsync(c->dUb, c->dU[c->cur], bytes, hipMemcpyDeviceToDevice, c->stream));
+    HS_HIP(c, hipMemcpyAsync(c->dVb, c->dV[c->cur], bytes, hipMemcpyDeviceToDevice, c->stream));
+    return HSFLOW_OK;
+}
+
+// ... which copies it back into the current buffer.
+int restore_start(hsflow_ctx *c)
+{
+    const size_t bytes = (size_t)c->plane * c->N * sizeof(float);
+    HS_HIP(c, hipMemcpyAsync(c->dU[c->cur], c->dUb, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HS_HIP(c, hipMemcpyAsync(c->dV[c->cur], c->dVb, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return HSFLOW_OK;
+}
+
+// Settles an ITER|EPS solve that hsflow_solve_async left unverified: waits for the stream, looks at the
+// witness words and, if they do not prove "no early stop", runs the exact pass from the saved start.
+// verdict_only: report whether the witness words prove "no early stop" and leave it at that (no exact pass; the flow of
+// the whole budget stands) -- for a driver that decides over several contexts (row slabs: hsflow_take_verdict).
 int settle_pending(hsflow_ctx *c, int *verdict_only = nullptr)
 {
     if (!c->pend.active) return HSFLOW_OK;
@@ -47,8 +63,7 @@ int settle_pending(hsflow_ctx *c, int *verdict_only = nullptr)
     // reduction (a stream of solves would pay a kernel and a boundary per solve for words nobody reads); now
     // that somebody wants the verdict, reduce them into the host's buffer and wait
     if (!c->pend.reduced) { // (hsflow_set_async_reduce: the solve enqueued the reduction itself, right behind its last launch)
-        c->epsStride = c->pend.stride;
-        int st0 = eps_collect_enqueue(c, c->pend.slots, c->pend.n_first, c->pend.cnt_first, c->pend.cnt_last);
+        int st0 = eps_collect_enqueue(c, c->pend.words);
         if (st0) return st0;
         HS_HIP(c, hipStreamSynchronize(c->stream));
     } else {
@@ -58,13 +73,8 @@ int settle_pending(hsflow_ctx *c, int *verdict_only = nullptr)
         if (stw) return stw;
     }
     float last = 0.f;
-    const bool gave_up = c->persist_unchecked && persist_error(c); // a persistent launch that timed out proves nothing
-    c->persist_unchecked = false;
-    if (gave_up) {
-        persist_failed(c);
-        c->coef_valid = false;
-    }
-    if (!gave_up && witness_proven(c->hEps, c->pend.slots, c->pend.params.epsilon, &last, false)) {
+    const bool gave_up = persist_gave_up(c); // a persistent launch that timed out proves nothing
+    if (!gave_up && witness_proven(c->hEps, c->pend.words.slots, c->pend.params.epsilon, &last, false)) {
         c->info.iterations_done = c->pend.iters;
         c->info.last_eps = NAN; // not measured by an asynchronous solve; hsflow_get_info measures it on demand (c->lastl)
         if (verdict_only) *verdict_only = 1;
@@ -81,10 +91,9 @@ int settle_pending(hsflow_ctx *c, int *verdict_only = nullptr)
     q.reuse_derivatives = gave_up ? 0 : 1; // the coefficient plane of that solve is still in place
     if (q.kernel == HSFLOW_KERNEL_PERSIST) q.kernel = HSFLOW_KERNEL_STRIP;
     if (q.use_previous) {
-        const size_t px = (size_t)c->plane * c->N;
         c->cur = c->pend.cur0;
-        HS_HIP(c, hipMemcpyAsync(c->dU[c->cur], c->dUb, px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        HS_HIP(c, hipMemcpyAsync(c->dV[c->cur], c->dVb, px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        int str = restore_start(c);
+        if (str) return str;
     }
     c->force_exact = true;
     const int st = solve_impl(c, &q, false);
@@ -96,7 +105,7 @@ int settle_pending(hsflow_ctx *c, int *verdict_only = nullptr)
 
 // last_eps of an asynchronous ITER|EPS solve, on demand: the solve ran witness launches only (they prove "no early
 // stop" but measure nothing).  Its last launch left its input buffer intact, so that launch is simply run again with
-// the final sweep's Eps measured (mode 3); it rewrites the flow with the same values.
+// the final sweep's Eps measured (EpsMode::WitnessLast); it rewrites the flow with the same values.
 int measure_last_eps(hsflow_ctx *c)
 {
     if (!c->lastl.valid) return HSFLOW_OK;
@@ -110,9 +119,9 @@ int measure_last_eps(hsflow_ctx *c)
     c->epsStride = stride;
     c->epsThr = L.eps_thr;
     const float *ui = L.from_third ? c->dUp : c->dU[a], *vi = L.from_third ? c->dVp : c->dV[a];
-    const hipError_t e = launch_j(c, L.plan, 3, ui, vi, c->dU[b], c->dV[b], L.coeff, false, L.zero_in, false);
+    const hipError_t e = launch_j(c, L.plan, EpsMode::WitnessLast, ui, vi, c->dU[b], c->dV[b], L.coeff, L.zero_in);
     HS_HIP(c, e);
-    if ((st = eps_collect_enqueue(c, 2, 0, 0, stride))) return st; // (resets epsPtr / epsStride)
+    if ((st = eps_collect_enqueue(c, EpsLayout{2, stride, 0, 0, stride}))) return st; // (resets epsPtr / epsStride)
     HS_HIP(c, hipStreamSynchronize(c->stream));
     float last = 0.f;
     std::memcpy(&last, &c->hEps[1], sizeof(float));
@@ -120,22 +129,26 @@ int measure_last_eps(hsflow_ctx *c)
     return HSFLOW_OK;
 }
 
-// Replays the hipGraph cached under `key`, capturing it first if needed.  `configure` sets kernel
-// attributes (not allowed inside a capture), `enqueue` issues the launch sequence on c->stream and
-// reports how many Jacobi launches it made.  On return c->cur is where the sequence leaves the flow.
-template <class Configure, class Enqueue>
-int run_captured(hsflow_ctx *c, const GraphKey &key, Configure configure, Enqueue enqueue, int *launches)
+// Replays the hipGraph cached under `key`, capturing it first if needed.  `enqueue` issues the launch sequence on
+// c->stream and reports how many Jacobi launches it made.  Kernel attributes cannot be set inside a capture, so ahead
+// of one the sequence is walked once as a dry run (hsflow_ctx::configuring), which sets those of exactly the kernel
+// variants the sequence launches.  On return c->cur is where the sequence leaves the flow.
+template <class Enqueue>
+int run_captured(hsflow_ctx *c, const GraphKey &key, Enqueue enqueue, int *launches)
 {
     if (!c->stream)
         return fail(c, HSFLOW_E_ARG, "use_graph: the default (NULL) stream cannot be captured; create the "
                                      "context on a non-default stream or with own_stream");
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
-        int st = configure();
-        if (st) return st;
-        HS_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         const int cur0 = c->cur;
         int n = 0;
+        c->configuring = true;
+        int st = enqueue(&n);
+        c->configuring = false;
+        c->cur = cur0;
+        if (st) return st;
+        HS_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         st = enqueue(&n);
         hipGraph_t graph = nullptr;
         const hipError_t e = hipStreamEndCapture(c->stream, &graph);
@@ -297,22 +310,12 @@ int solve_classic(hsflow_ctx *c, const hsflow_params &p, bool async)
         *n = launches;
         return HSFLOW_OK;
     };
-    auto configure = [&]() -> int { // kernel attributes cannot be set inside a capture
-        if (kernel == HSFLOW_KERNEL_STRIP) {
-            HS_HIP(c, launch_classic_strip(c, splan, write_v, nullptr, nullptr, nullptr, nullptr, a2, true));
-            if (p.max_iter % T) HS_HIP(c, launch_classic_strip(c, stail, write_v, nullptr, nullptr, nullptr, nullptr, a2, true));
-        } else if (kernel == HSFLOW_KERNEL_FUSED) {
-            HS_HIP(c, launch_classic_fused(c, fplan, write_v, nullptr, nullptr, nullptr, nullptr, a2, true));
-            if (p.max_iter % T) HS_HIP(c, launch_classic_fused(c, ftail, write_v, nullptr, nullptr, nullptr, nullptr, a2, true));
-        }
-        return HSFLOW_OK;
-    };
     hsflow_info &i = c->info;
     int launches = 0;
     if (p.use_graph) {
         GraphKey key{p.mode, kernel, p.max_iter, T, i.tile_w, i.tile_h, i.threads, i.groups_per_thread, zero0 ? 0 : c->cur,
                      p.use_previous * 2 + (do_deriv ? 1 : 0) + (do_unpack ? 4 : 0), p.alpha};
-        if ((st = run_captured(c, key, configure, enqueue, &launches))) return st;
+        if ((st = run_captured(c, key, enqueue, &launches))) return st;
     } else if ((st = enqueue(&launches))) return st;
     c->coef_valid = true;
     c->coef_mode = HSFLOW_MODE_CLASSIC;
@@ -326,309 +329,203 @@ int solve_classic(hsflow_ctx *c, const hsflow_params &p, bool async)
     return HSFLOW_OK;
 }
 
-
 // ITER termination: a fixed sweep count, nothing on the host between launches (optionally one hipGraph).
 int solve_fixed(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Profiler &prof, bool async)
 {
-    const float coeff = S.coeff;
-    const int kernel = S.kernel, T = S.T;
-    const bool multi = S.multi;
-    const JPlan &plan = S.plan;
+    const int iters = (int)S.budget, T = S.T;
     int st = HSFLOW_OK;
-    const long long budget = S.budget;
     JPlan tail;
-    const int iters = (int)budget;
-    const bool persist = S.persist;
-    const int rem = (multi && !persist) ? iters % T : 0;
-    if (rem && !make_jplan(c, kernel, rem, p, tail))
+    const int rem = (S.multi && !S.persist) ? iters % T : 0;
+    if (rem && !make_jplan(c, S.kernel, rem, p, tail))
         return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the tail launch");
     const bool zero = !p.use_previous;
     const bool do_deriv = !(p.reuse_derivatives && c->coef_valid && c->coef_mode == HSFLOW_MODE_CV);
-    c->info.deriv_fused = do_deriv && !p.profile && multi && strip_deriv_fusable(c, iters >= T ? plan : tail); // enqueue_fixed's rule
-    if (persist) { // buffers and phase counters: outside any capture
-        if ((st = persist_reserve(c)) || (st = persist_prepare_flags(c, plan.s.tiles))) return st;
+    c->info.deriv_fused = do_deriv && !p.profile && S.multi && strip_deriv_fusable(c, iters >= T ? S.plan : tail); // enqueue_fixed's rule
+    if (S.persist) { // buffers and phase counters: outside any capture
+        if ((st = persist_reserve(c)) || (st = persist_prepare_flags(c, S.plan.s.tiles))) return st;
     }
+    auto enqueue = [&](int *n) -> int {
+        const int e = enqueue_fixed(c, p, S.coeff, iters, S.kernel, T, &S.plan, &tail, prof, do_deriv, zero, S.persist);
+        *n = c->info.jacobi_launches;
+        return e;
+    };
+    int n = 0;
     if (p.use_graph && !p.profile) {
-        GraphKey key{p.mode, persist ? HSFLOW_KERNEL_PERSIST : kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
-                     c->info.groups_per_thread, zero ? 0 : c->cur, p.use_previous * 2 + (do_deriv ? 1 : 0), coeff};
-        auto configure = [&]() -> int {
-            if (persist) {
-                hsk::PersistArgs none{};
-                HS_HIP(c, launch_persist(c, plan.s, none, 0, c->info.deriv_fused != 0, nullptr, nullptr, coeff, true));
-                return HSFLOW_OK;
-            }
-            if (multi) {
-                HS_HIP(c, launch_j(c, plan, false, nullptr, nullptr, nullptr, nullptr, coeff, true));
-                if (rem) HS_HIP(c, launch_j(c, tail, false, nullptr, nullptr, nullptr, nullptr, coeff, true));
-                const JPlan &first = iters >= T ? plan : tail;
-                if (do_deriv && strip_deriv_fusable(c, first))
-                    HS_HIP(c, launch_j(c, first, false, nullptr, nullptr, nullptr, nullptr, coeff, true, 0, true));
-            }
-            return HSFLOW_OK;
-        };
-        auto enqueue = [&](int *n) -> int {
-            const int e = enqueue_fixed(c, p, coeff, iters, kernel, T, &plan, &tail, prof, do_deriv, zero, persist);
-            *n = c->info.jacobi_launches;
-            return e;
-        };
-        int n = 0;
-        if ((st = run_captured(c, key, configure, enqueue, &n))) return st;
+        GraphKey key{p.mode, S.persist ? HSFLOW_KERNEL_PERSIST : S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
+                     c->info.groups_per_thread, zero ? 0 : c->cur, p.use_previous * 2 + (do_deriv ? 1 : 0), S.coeff};
+        if ((st = run_captured(c, key, enqueue, &n))) return st;
         c->info.jacobi_launches = n;
     } else {
-        if (persist) {
-            hsk::PersistArgs none{};
-            HS_HIP(c, launch_persist(c, plan.s, none, 0, c->info.deriv_fused != 0, nullptr, nullptr, coeff, true));
-        }
-        st = enqueue_fixed(c, p, coeff, iters, kernel, T, &plan, &tail, prof, do_deriv, zero, persist);
-        if (st) return st;
+        if (S.persist && (st = configure_persist(c, S.plan.s, EpsMode::None, c->info.deriv_fused != 0, S.coeff))) return st;
+        if ((st = enqueue(&n))) return st;
     }
     c->coef_valid = true;
     c->coef_mode = HSFLOW_MODE_CV;
     c->info.iterations_done = iters;
-    if (persist && async) c->persist_unchecked = true; // looked at when the stream is next drained (check_persist)
+    if (S.persist && async) c->persist_unchecked = true; // looked at when the stream is next drained (check_persist)
     if (!async) {
         HS_HIP(c, hipStreamSynchronize(c->stream));
-        if (persist && persist_error(c)) { // a wait timed out: back to a launch per fuse_steps iterations, for good
+        if (S.persist && persist_error(c)) { // a wait timed out: back to a launch per fuse_steps iterations, for good
             persist_failed(c);
-            c->cur ^= 1;            // the starting flow is intact (the phases wrote the other two buffers)
-            c->coef_valid = false;  // a workgroup that never started left its part of the derivative plane unwritten
+            c->cur ^= 1; // the starting flow is intact (the phases wrote the other two buffers)
             hsflow_params q = p;
             if (q.kernel == HSFLOW_KERNEL_PERSIST) q.kernel = HSFLOW_KERNEL_STRIP;
             q.reuse_derivatives = 0;
             return solve_impl(c, &q, false);
         }
         prof.collect();
-        if (c->dStamps && (kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD)) dump_stamps(c, plan.s.tiles);
+        if (c->dStamps && (S.kernel == HSFLOW_KERNEL_STRIP || S.kernel == HSFLOW_KERNEL_FOLD)) dump_stamps(c, S.plan.s.tiles);
     }
     return HSFLOW_OK;
 }
 
-// ITER|EPS -- the way the reference calls the solver (OpticalFlowOpenCV.cpp:29).  On real image
-// pairs Eps never drops below 1e-6 within the sweep budget, so the budget is run SPECULATIVELY at
-// full speed (no host round trip between launches) while every sweep records its Eps on the device;
-// one read-back at the end finds the first sweep k with Eps_k < epsilon.  If there is none the
-// result stands; otherwise exactly k sweeps are re-run from the saved starting flow, which
-// reproduces the oracle's stopping sweep.
-int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Profiler &prof, bool async)
+// Index of the first of n Eps words below epsilon, -1 if there is none.  *last: that word, else the last one.
+int first_eps_hit(const unsigned *w, int n, double epsilon, float *last)
 {
-    const float coeff = S.coeff;
-    const int kernel = S.kernel, T = S.T;
-    const bool multi = S.multi;
+    for (int s = 0; s < n; s++) {
+        std::memcpy(last, &w[s], sizeof(float));
+        if ((double)*last < epsilon) return s;
+    }
+    return -1;
+}
+
+// The threshold of witness launches: the smallest float >= epsilon, so that "change >= threshold" implies "Eps >= epsilon".
+float witness_threshold(double epsilon)
+{
+    float thr = epsilon > 0 ? (float)epsilon : 0.f;
+    if ((double)thr < epsilon) thr = std::nextafterf(thr, INFINITY);
+    if (thr < FLT_MIN) thr = thr > 0.f ? FLT_MIN : 0.f; // the kernels scale it through its exponent bits
+    return thr;
+}
+
+// The witness pass of ITER|EPS: the budget runs at full speed, nothing on the host between launches.  All launches but
+// the last run the kernels' witness mode, which costs almost nothing over the ITER-only kernel and yields one number per
+// launch that proves "Eps >= epsilon in every one of my sweeps" when it is >= epsilon.  If every bound holds, the early
+// stop cannot have fired before the budget ran out (a stop AT the final sweep is the budget) and the result stands.
+// Synchronous solves report last_eps at once: their last launch measures its final sweep too (WitnessLast: two words per
+// workgroup, the witness and that sweep's Eps).  Asynchronous solves run witness launches only and leave the check owed
+// (c->pend: settle_pending); their last_eps is measured if and when hsflow_get_info asks for it (c->lastl:
+// measure_last_eps).
+// tailp: the plan of a short last launch; stride: words per row; *launches: Jacobi launches enqueued.
+// *rerun: nothing is proven (a flat or converged input) -- the starting flow is back in place for the exact pass.
+int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, const JPlan &tailp, int stride, bool do_deriv,
+                 Profiler &prof, bool async, int *launches, bool *rerun)
+{
+    const int iters = (int)S.budget, T = S.T, cur0 = c->cur;
     const JPlan &plan = S.plan;
     int st = HSFLOW_OK;
-    const long long budget = S.budget;
-    const int iters = (int)budget;
-    const size_t px = (size_t)c->plane * c->N;
-    bool witness = (kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD) && !c->force_exact && strip_has_witness(plan);
-    const bool do_deriv = !(p.reuse_derivatives && c->coef_valid && c->coef_mode == HSFLOW_MODE_CV);
-    if (p.use_previous) { // the starting flow is kept: the ping-pong buffers get overwritten
-        if (!c->dUb) HS_HIP(c, hipMalloc((void **)&c->dUb, px * sizeof(float)));
-        if (!c->dVb) HS_HIP(c, hipMalloc((void **)&c->dVb, px * sizeof(float)));
-    }
-    auto save_start = [&]() -> int {
-        if (!p.use_previous) return HSFLOW_OK;
-        HS_HIP(c, hipMemcpyAsync(c->dUb, c->dU[c->cur], px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        HS_HIP(c, hipMemcpyAsync(c->dVb, c->dV[c->cur], px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        return HSFLOW_OK;
-    };
-    // every launch of this solve uses the same number of workgroups or fewer (tail): stride = max
-    int stride = multi ? plan_eps_stride(kernel, plan) : 1;
-    JPlan tailp;
-    const bool has_tail = multi && iters % T;
-    if (has_tail) {
-        if (!make_jplan(c, kernel, iters % T, p, tailp)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
-        if (witness && !strip_has_witness(tailp)) { // as in prepare_solve
-            JPlan alt;
-            if (make_witness_jplan(c, kernel, iters % T, p, alt)) tailp = alt;
-        }
-        stride = std::max(stride, plan_eps_stride(kernel, tailp));
-        // (a tail of one sweep is measured, not witnessed: the synchronous pass's mode 3; an asynchronous pass needs it able)
-        if (witness && !S.persist && (async || iters % T > 1) && !strip_has_witness(tailp)) witness = false; // (persist: the tail phase keeps the plan's geometry)
-    }
-    if (async && !witness)
-        return fail(c, HSFLOW_E_ARG, "solve_async with ITER|EPS: this launch plan (core tile thinner than a strip) cannot run witness launches; "
-                                     "use hsflow_solve or other tuning parameters");
-    int launches = 0;
-    if (witness) {
-        // Witness pass: all launches but the last run k_jacobi_strip<.., 2>, which costs almost
-        // nothing over the ITER-only kernel and yields one number per launch that proves "Eps >=
-        // epsilon in every one of my sweeps" when it is >= epsilon.  The last launch also provides
-        // last_eps: it witnesses its sweeps but measures the final one (mode 3).  If every bound
-        // holds, the early stop cannot have fired before the budget ran out (a stop AT the final
-        // sweep is the budget) and the result stands.  Otherwise (a flat or converged input) the
-        // exact per-sweep path below starts over from the saved flow.
-        // threshold as the smallest float >= epsilon: "change >= epsThr" then implies "Eps >= epsilon"
-        c->epsThr = p.epsilon > 0 ? (float)p.epsilon : 0.f;
-        if ((double)c->epsThr < p.epsilon) c->epsThr = std::nextafterf(c->epsThr, INFINITY);
-        if (c->epsThr < FLT_MIN) c->epsThr = c->epsThr > 0.f ? FLT_MIN : 0.f; // the kernels scale it through its exponent bits
-        const bool persist = S.persist && async; // (prepare_solve grants it to asynchronous solves only)
-        const int n_launch = (iters + T - 1) / T; // persist: phases of the one launch; the witness words are laid out alike
-        const int last_chunk = iters - (n_launch - 1) * T;
-        if (persist && ((st = persist_reserve(c)) || (st = persist_prepare_flags(c, plan.s.tiles)))) return st;
-        // Synchronous solves report last_eps at once: their last launch measures its final sweep (mode 3: two words
-        // per workgroup, the witness and that sweep's Eps).  Asynchronous solves run witness launches only; their
-        // last_eps is measured if and when hsflow_get_info asks for it (measure_last_eps).
-        const int last_mode = async ? 2 : 3;
-        const int slots = async ? n_launch : (n_launch - 1) + 2;
-        if ((st = eps_reserve(c, slots, stride))) return st;
-        const int cur0 = c->cur;
-        // the first launch also does the derivative pass where the kernel can (hs_plan_launch.hip.h)
-        const JPlan &firstp = (n_launch == 1 && last_chunk != T) ? tailp : plan;
-        const bool fuse_deriv = do_deriv && !p.profile && strip_deriv_fusable(c, firstp);
-        c->info.deriv_fused = fuse_deriv;
-        // the whole pass as one enqueue sequence (nothing allocated, nothing synchronised: capturable)
-        auto enqueue = [&]() -> int {
-            int e0 = save_start();
-            if (e0) return e0;
-            c->epsStride = stride; // (no clearing: every launch writes all its words, the reduction reads only those)
-            bool fuse = fuse_deriv;
-            if (do_deriv && !fuse) {
-                prof.begin(0);
-                HS_HIP(c, launch_deriv(c));
-                prof.end();
-            }
-            int zero_w = p.use_previous ? 0 : 1;
-            if (zero_w) c->cur = 0;
-            if (persist) { // one launch, a row of witness words per phase
-                c->epsPtr = c->dEpsTiles;
-                prof.begin(1);
-                const int e = enqueue_persist(c, plan.s, iters, 2, fuse, zero_w, coeff);
-                prof.end();
-                if (e) return e;
-                // what measure_last_eps needs: the last phase again as an ordinary launch, from the third buffer
-                c->lastl.plan = last_chunk != T ? tailp : plan; c->lastl.zero_in = 0; c->lastl.coeff = coeff; c->lastl.eps_thr = c->epsThr;
-                c->lastl.from_third = true;
-                launches = 1;
-            }
-            for (int L = persist ? n_launch : 0; L < n_launch; L++) {
-                const bool is_last = L == n_launch - 1;
-                const JPlan &cp = (is_last && last_chunk != T) ? tailp : plan;
-                const int a = c->cur, b = a ^ 1;
-                c->epsPtr = c->dEpsTiles + (size_t)L * stride;
-                prof.begin(1);
-                hipError_t e = launch_j(c, cp, is_last ? last_mode : 2, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, false, zero_w, fuse);
-                prof.end();
-                HS_HIP(c, e);
-                if (is_last && async) { // what measure_last_eps needs
-                    c->lastl.plan = cp; c->lastl.zero_in = zero_w; c->lastl.coeff = coeff; c->lastl.eps_thr = c->epsThr;
-                    c->lastl.from_third = false;
-                }
-                c->cur = b;
-                zero_w = 0;
-                fuse = false;
-                launches++;
-            }
-            if (async && !c->async_reduce) { // the reduction of the witness words waits until somebody settles the check (settle_pending)
-                c->epsPtr = c->dEps;
-                c->epsStride = 1;
-                return HSFLOW_OK;
-            }
-            // (an asynchronous solve gets here only with the in-stream reduction on: its last workgroup writes the marker too)
-            return eps_collect_enqueue(c, slots, n_launch - 1, plan_eps_stride(kernel, plan),
-                                       plan_eps_stride(kernel, (last_chunk != T && !persist) ? tailp : plan), async && c->hMark != nullptr);
-        };
-        if (p.use_graph && !p.profile) {
-            GraphKey key{p.mode, persist ? HSFLOW_KERNEL_PERSIST : kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
-                         c->info.groups_per_thread, p.use_previous ? c->cur : 0, p.use_previous * 2 + (do_deriv ? 1 : 0) + (async ? 4 : 0) + (async && c->async_reduce ? 8 : 0), coeff, c->epsThr};
-            auto configure = [&]() -> int {
-                if (persist) {
-                    hsk::PersistArgs none{};
-                    HS_HIP(c, launch_persist(c, plan.s, none, 2, fuse_deriv, nullptr, nullptr, coeff, true));
-                    HS_HIP(c, launch_j(c, has_tail ? tailp : plan, 3, nullptr, nullptr, nullptr, nullptr, coeff, true)); // measure_last_eps
-                    return HSFLOW_OK;
-                }
-                HS_HIP(c, launch_j(c, plan, 2, nullptr, nullptr, nullptr, nullptr, coeff, true));
-                HS_HIP(c, launch_j(c, plan, last_mode, nullptr, nullptr, nullptr, nullptr, coeff, true));
-                if (has_tail) HS_HIP(c, launch_j(c, tailp, last_mode, nullptr, nullptr, nullptr, nullptr, coeff, true));
-                if (fuse_deriv) HS_HIP(c, launch_j(c, firstp, n_launch == 1 ? last_mode : 2, nullptr, nullptr, nullptr, nullptr, coeff, true, 0, true));
-                return HSFLOW_OK;
-            };
-            const hsflow_ctx::LastLaunch keep = c->lastl;
-            bool captured = false;
-            auto enqueue_n = [&](int *n) -> int {
-                launches = 0;
-                captured = true;
-                const int e = enqueue();
-                *n = launches;
-                return e;
-            };
-            if ((st = run_captured(c, key, configure, enqueue_n, &launches))) return st;
-            c->epsPtr = c->dEps;
-            c->epsStride = 1;
-            if (async && !captured) { // a replay: the description of the last launch is what the capture recorded
-                const bool is_tail = last_chunk != T;
-                c->lastl = keep;
-                c->lastl.plan = is_tail ? tailp : plan;
-                c->lastl.zero_in = (n_launch == 1 && !p.use_previous) ? 1 : 0;
-                c->lastl.coeff = coeff;
-                c->lastl.eps_thr = c->epsThr;
-                c->lastl.from_third = persist;
-            }
-        } else {
-            if (persist) {
-                hsk::PersistArgs none{};
-                HS_HIP(c, launch_persist(c, plan.s, none, 2, fuse_deriv, nullptr, nullptr, coeff, true));
-            }
-            if ((st = enqueue())) return st;
-        }
-        c->coef_valid = true;
-        c->coef_mode = HSFLOW_MODE_CV;
-        if (persist) c->persist_unchecked = true;
-        if (async) { // the check is owed: hsflow_synchronize (or the next call that needs results) settles it
-            c->lastl.valid = true;
-            c->pend.active = true;
-            c->pend.params = p;
-            c->pend.iters = iters; c->pend.slots = slots; c->pend.launches = launches; c->pend.cur0 = cur0;
-            c->pend.stride = stride; c->pend.n_first = n_launch - 1; c->pend.cnt_first = plan_eps_stride(kernel, plan);
-            c->pend.cnt_last = plan_eps_stride(kernel, (last_chunk != T && !persist) ? tailp : plan);
-            c->pend.reduced = c->async_reduce;
-            c->pend.marked_by_reduce = c->async_reduce && c->hMark != nullptr;
-            c->info.iterations_done = iters;
-            c->info.jacobi_launches = launches;
-            return HSFLOW_OK;
-        }
-        HS_HIP(c, hipStreamSynchronize(c->stream));
-        std::vector<unsigned> hw(c->hEps, c->hEps + slots);
-
-        float last = 0.f;
-        if (witness_proven(hw.data(), slots, p.epsilon, &last, true)) {
-            c->info.iterations_done = iters;
-            c->info.last_eps = last;
-            c->info.jacobi_launches = launches;
-            prof.collect();
-            return HSFLOW_OK;
-        }
-        c->info.eps_rerun = 1;
-        // not proven: restore the starting flow and measure every sweep
-        if (p.use_previous) {
-            c->cur = cur0;
-            HS_HIP(c, hipMemcpyAsync(c->dU[c->cur], c->dUb, px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            HS_HIP(c, hipMemcpyAsync(c->dV[c->cur], c->dVb, px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        }
-        if ((st = eps_prepare(c, iters, stride))) return st;
-    } else {
-        if ((st = save_start())) return st;
-        if ((st = eps_prepare(c, iters, stride))) return st;
-        if (do_deriv) {
+    c->epsThr = witness_threshold(p.epsilon);
+    const bool persist = S.persist && async; // (prepare_solve grants it to asynchronous solves only)
+    const int n_launch = (iters + T - 1) / T; // persist: phases of the one launch; the witness words are laid out alike
+    const JPlan &lastp = iters % T ? tailp : plan;
+    const JPlan &firstp = n_launch == 1 ? lastp : plan;
+    if (persist && ((st = persist_reserve(c)) || (st = persist_prepare_flags(c, plan.s.tiles)))) return st;
+    const EpsMode last_mode = async ? EpsMode::Witness : EpsMode::WitnessLast;
+    // (persist: the tail phase keeps the plan's geometry)
+    const EpsLayout words{n_launch - 1 + (async ? 1 : 2), stride, n_launch - 1, plan_eps_stride(S.kernel, plan),
+                          plan_eps_stride(S.kernel, persist ? plan : lastp)};
+    if ((st = eps_reserve(c, words.slots, stride))) return st;
+    // the first launch also does the derivative pass where the kernel can (hs_plan_launch.hip.h)
+    const bool fuse_deriv = do_deriv && !p.profile && strip_deriv_fusable(c, firstp);
+    c->info.deriv_fused = fuse_deriv;
+    // the whole pass as one enqueue sequence (nothing allocated, nothing synchronised: capturable)
+    auto enqueue = [&](int *n) -> int {
+        if (p.use_previous && (st = save_start(c))) return st;
+        c->epsStride = stride; // (no clearing: every launch writes all its words, the reduction reads only those)
+        if (do_deriv && !fuse_deriv) {
             prof.begin(0);
             HS_HIP(c, launch_deriv(c));
             prof.end();
         }
-        c->coef_valid = true;
-        c->coef_mode = HSFLOW_MODE_CV;
+        const int zero_w = p.use_previous ? 0 : 1;
+        if (zero_w) c->cur = 0;
+        if (persist) { // one launch, a row of witness words per phase
+            c->epsPtr = c->dEpsTiles;
+            prof.begin(1);
+            const int e = enqueue_persist(c, plan.s, iters, EpsMode::Witness, fuse_deriv, zero_w, S.coeff);
+            prof.end();
+            if (e) return e;
+        } else for (int L = 0; L < n_launch; L++) {
+            const bool is_last = L == n_launch - 1;
+            const int a = c->cur, b = a ^ 1;
+            c->epsPtr = c->dEpsTiles + (size_t)L * stride;
+            prof.begin(1);
+            hipError_t e = launch_j(c, is_last ? lastp : plan, is_last ? last_mode : EpsMode::Witness, c->dU[a], c->dV[a], c->dU[b],
+                                    c->dV[b], S.coeff, L == 0 ? zero_w : 0, L == 0 && fuse_deriv);
+            prof.end();
+            HS_HIP(c, e);
+            c->cur = b;
+        }
+        *n = persist ? 1 : n_launch;
+        if (async && !c->async_reduce) { // the reduction of the witness words waits until somebody settles the check (settle_pending)
+            c->epsPtr = c->dEps;
+            c->epsStride = 1;
+            return HSFLOW_OK;
+        }
+        // (an asynchronous solve gets here only with the in-stream reduction on: its last workgroup writes the marker too)
+        return eps_collect_enqueue(c, words, async && c->hMark != nullptr);
+    };
+    if (p.use_graph && !p.profile) {
+        GraphKey key{p.mode, persist ? HSFLOW_KERNEL_PERSIST : S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
+                     c->info.groups_per_thread, p.use_previous ? c->cur : 0,
+                     p.use_previous * 2 + (do_deriv ? 1 : 0) + (async ? 4 : 0) + (async && c->async_reduce ? 8 : 0), S.coeff, c->epsThr};
+        if ((st = run_captured(c, key, enqueue, launches))) return st;
+        c->epsPtr = c->dEps; // (a replay ran none of the sequence's host side)
+        c->epsStride = 1;
+    } else {
+        if (persist && (st = configure_persist(c, plan.s, EpsMode::Witness, fuse_deriv, S.coeff))) return st;
+        if ((st = enqueue(launches))) return st;
     }
-    int zero_in = p.use_previous ? 0 : 1, done = 0;
+    c->coef_valid = true;
+    c->coef_mode = HSFLOW_MODE_CV;
+    if (persist) c->persist_unchecked = true;
+    c->info.iterations_done = iters;
+    c->info.jacobi_launches = *launches;
+    if (async) { // the check is owed: hsflow_synchronize (or the next call that needs results) settles it
+        // what measure_last_eps needs: the last launch again (persist: the last phase as an ordinary launch, from the third buffer)
+        const int zero_in = (n_launch == 1 && !p.use_previous && !persist) ? 1 : 0; // a single launch from zero flow
+        c->lastl = hsflow_ctx::LastLaunch{true, lastp, zero_in, S.coeff, c->epsThr, persist};
+        c->pend.active = true;
+        c->pend.params = p;
+        c->pend.iters = iters; c->pend.launches = *launches; c->pend.cur0 = cur0;
+        c->pend.words = words;
+        c->pend.reduced = c->async_reduce;
+        c->pend.marked_by_reduce = c->async_reduce && c->hMark != nullptr;
+        return HSFLOW_OK;
+    }
+    HS_HIP(c, hipStreamSynchronize(c->stream));
+    float last = 0.f;
+    if (witness_proven(c->hEps, words.slots, p.epsilon, &last, true)) {
+        c->info.last_eps = last;
+        prof.collect();
+        return HSFLOW_OK;
+    }
+    // not proven: restore the starting flow and measure every sweep
+    *rerun = true;
+    c->info.eps_rerun = 1;
+    c->cur = cur0;
+    return p.use_previous ? restore_start(c) : HSFLOW_OK;
+}
+
+// The exact pass of ITER|EPS: every sweep records its Eps on the device (one row of `stride` words per sweep, reserved
+// and cleared by the caller); one read-back at the end finds the first sweep k with Eps_k < epsilon.  If there is none
+// the result stands; otherwise exactly k sweeps are re-run from the saved starting flow, which reproduces the oracle's
+// stopping sweep.  launches: those of a witness pass that proved nothing, which this pass then follows.
+int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int stride, Profiler &prof, int launches)
+{
+    const int iters = (int)S.budget, T = S.T;
+    int st = HSFLOW_OK, zero_in = p.use_previous ? 0 : 1, done = 0;
     if (zero_in) c->cur = 0;
     while (done < iters) {
-        const int chunk = multi ? std::min(T, iters - done) : 1;
-        JPlan cp = plan;
-        if (multi && chunk != T && !make_jplan(c, kernel, chunk, p, cp))
+        const int chunk = S.multi ? std::min(T, iters - done) : 1;
+        JPlan cp = S.plan;
+        if (S.multi && chunk != T && !make_jplan(c, S.kernel, chunk, p, cp))
             return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
         const int a = c->cur, b = a ^ 1;
         c->epsPtr = c->dEpsTiles + (size_t)done * stride;
         prof.begin(1);
-        hipError_t e = multi ? launch_j(c, cp, true, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, false, zero_in)
-                             : launch_simple(c, true, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, zero_in);
+        hipError_t e = S.multi ? launch_j(c, cp, EpsMode::EverySweep, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff, zero_in)
+                               : launch_simple(c, true, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff, zero_in);
         prof.end();
         HS_HIP(c, e);
         c->cur = b;
@@ -640,26 +537,19 @@ int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, P
     if ((st = eps_collect(c, iters, heps))) return st;
     c->sweep_eps.resize((size_t)iters); // (hsflow_solve_probe hands these out)
     std::memcpy(c->sweep_eps.data(), heps.data(), (size_t)iters * sizeof(float));
-    int hit = -1;
     float last = 0.f;
-    for (int s2 = 0; s2 < iters; s2++) {
-        std::memcpy(&last, &heps[(size_t)s2], sizeof(float));
-        if ((double)last < p.epsilon) { hit = s2; break; }
-    }
+    const int hit = first_eps_hit(heps.data(), iters, p.epsilon, &last);
     if (hit >= 0 && hit + 1 < iters) { // converged early: redo exactly hit+1 sweeps from the start
         const int k = hit + 1;
-        if (p.use_previous) {
-            HS_HIP(c, hipMemcpyAsync(c->dU[c->cur], c->dUb, px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            HS_HIP(c, hipMemcpyAsync(c->dV[c->cur], c->dVb, px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        }
+        if (p.use_previous && (st = restore_start(c))) return st;
         JPlan kp, kt;
         int Tk = 1;
-        if (multi) {
+        if (S.multi) {
             Tk = std::min(T, k);
-            if (!make_jplan(c, kernel, Tk, p, kp)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the re-run");
-            if (k % Tk && !make_jplan(c, kernel, k % Tk, p, kt)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the re-run tail");
+            if (!make_jplan(c, S.kernel, Tk, p, kp)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the re-run");
+            if (k % Tk && !make_jplan(c, S.kernel, k % Tk, p, kt)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the re-run tail");
         }
-        st = enqueue_fixed(c, p, coeff, k, kernel, Tk, &kp, &kt, prof, false, !p.use_previous);
+        st = enqueue_fixed(c, p, S.coeff, k, S.kernel, Tk, &kp, &kt, prof, false, !p.use_previous);
         if (st) return st;
         launches += c->info.jacobi_launches;
         HS_HIP(c, hipStreamSynchronize(c->stream));
@@ -673,19 +563,67 @@ int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, P
     return HSFLOW_OK;
 }
 
+// ITER|EPS -- the way the reference calls the solver (OpticalFlowOpenCV.cpp:29).  On real image pairs Eps never drops
+// below 1e-6 within the sweep budget, so the budget is run SPECULATIVELY wherever the kernel has a witness mode
+// (witness_pass); the exact pass measures every sweep where there is none, where a solve is being settled
+// (force_exact) and where the witness proved nothing.
+int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Profiler &prof, bool async)
+{
+    const int iters = (int)S.budget, T = S.T, kernel = S.kernel;
+    int st = HSFLOW_OK;
+    bool witness = (kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD) && !c->force_exact && strip_has_witness(S.plan);
+    const bool do_deriv = !(p.reuse_derivatives && c->coef_valid && c->coef_mode == HSFLOW_MODE_CV);
+    if (p.use_previous) { // the starting flow is kept (save_start)
+        const size_t px = (size_t)c->plane * c->N;
+        if (!c->dUb) HS_HIP(c, hipMalloc((void **)&c->dUb, px * sizeof(float)));
+        if (!c->dVb) HS_HIP(c, hipMalloc((void **)&c->dVb, px * sizeof(float)));
+    }
+    // every launch of this solve uses the same number of workgroups or fewer (tail): stride = max
+    int stride = S.multi ? plan_eps_stride(kernel, S.plan) : 1;
+    JPlan tailp;
+    if (S.multi && iters % T) {
+        if (!make_jplan(c, kernel, iters % T, p, tailp)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
+        if (witness && !strip_has_witness(tailp)) { // as in prepare_solve
+            JPlan alt;
+            if (make_witness_jplan(c, kernel, iters % T, p, alt)) tailp = alt;
+        }
+        stride = std::max(stride, plan_eps_stride(kernel, tailp));
+        // (a tail of one sweep is measured, not witnessed: the synchronous pass's WitnessLast; an asynchronous pass needs it able)
+        if (witness && !S.persist && (async || iters % T > 1) && !strip_has_witness(tailp)) witness = false; // (persist: the tail phase keeps the plan's geometry)
+    }
+    if (async && !witness)
+        return fail(c, HSFLOW_E_ARG, "solve_async with ITER|EPS: this launch plan (core tile thinner than a strip) cannot run witness launches; "
+                                     "use hsflow_solve or other tuning parameters");
+    int launches = 0;
+    if (witness) {
+        bool rerun = false;
+        if ((st = witness_pass(c, p, S, tailp, stride, do_deriv, prof, async, &launches, &rerun)) || !rerun) return st;
+        if ((st = eps_prepare(c, iters, stride))) return st;
+    } else {
+        if (p.use_previous && (st = save_start(c))) return st;
+        if ((st = eps_prepare(c, iters, stride))) return st;
+        if (do_deriv) {
+            prof.begin(0);
+            HS_HIP(c, launch_deriv(c));
+            prof.end();
+        }
+        c->coef_valid = true;
+        c->coef_mode = HSFLOW_MODE_CV;
+    }
+    return exact_pass(c, p, S, stride, prof, launches);
+}
+
+
 // EPS without a usable sweep budget (CV_TERMCRIT_EPS alone): Eps_k = max |u_k - u_{k-1}|, |v_k - v_{k-1}|
 // is produced per sweep by the kernel; the host looks at it after every chunk and, if the
 // threshold was crossed inside the chunk, replays the chunk up to that sweep (its input buffer
 // is still intact), which reproduces the oracle's stopping sweep exactly.
 int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Profiler &prof)
 {
-    const float coeff = S.coeff;
     const int kernel = S.kernel, T = S.T;
     const bool multi = S.multi;
-    const JPlan &plan = S.plan;
-    int st = HSFLOW_OK;
     const long long budget = S.budget;
-    const bool use_iter = S.use_iter;
+    int st = HSFLOW_OK;
     if (!p.use_previous) {
         c->cur = 0;
         HS_HIP(c, hipMemsetAsync(c->dU[0], 0, (size_t)c->plane * c->N * sizeof(float), c->stream));
@@ -712,7 +650,7 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
     bool stalled = false;
     while (!stop) {
         const int chunk = (int)std::min<long long>(T, budget - done);
-        JPlan cp = plan;
+        JPlan cp = S.plan;
         if (multi && chunk != T && !make_jplan(c, kernel, chunk, p, cp))
             return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
         const int a = c->cur, b = a ^ 1;
@@ -721,27 +659,25 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
         c->epsPtr = c->dEpsTiles;
         prof.begin(1);
         if (!multi)
-            HS_HIP(c, launch_simple(c, true, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff));
+            HS_HIP(c, launch_simple(c, true, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
         else
-            HS_HIP(c, launch_j(c, cp, true, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff));
+            HS_HIP(c, launch_j(c, cp, EpsMode::EverySweep, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
         prof.end();
         launches++;
         std::vector<unsigned> heps;
         if ((st = eps_collect(c, n, heps))) return st;
-        int hit = -1;
-        for (int s = 0; s < n; s++) {
+        const int hit = first_eps_hit(heps.data(), n, p.epsilon, &last);
+        for (int s = 0; s < n && hit < 0; s++) { // (the stall rule)
             float e;
             std::memcpy(&e, &heps[(size_t)s], sizeof(float));
-            last = e;
             if (e < best_eps) { best_eps = e; best_at = done + s; }
-            if ((double)e < p.epsilon) { hit = s; break; }
         }
         if (hit >= 0 && hit < n - 1) { // crossed inside the chunk: redo exactly hit+1 sweeps
             JPlan rp;
             if (!make_jplan(c, kernel, hit + 1, p, rp))
                 return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the replay");
             prof.begin(1);
-            HS_HIP(c, launch_j(c, rp, false, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff));
+            HS_HIP(c, launch_j(c, rp, EpsMode::None, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
             prof.end();
             launches++;
             done += hit + 1;
@@ -751,7 +687,7 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
             if (hit >= 0) stop = true;
         }
         c->cur = b;
-        if (use_iter && p.max_iter > 0 && done >= budget) stop = true;
+        if (S.use_iter && p.max_iter > 0 && done >= budget) stop = true;
         if (!stop && budget > kMaxSweeps && (done - best_at >= kStallSweeps || done >= kMaxSweeps)) stop = stalled = true;
     }
     HS_HIP(c, hipStreamSynchronize(c->stream));
