@@ -259,6 +259,21 @@ int hsflow_push_frame_u8(hsflow_ctx *ctx, int pair, const uint8_t *next, size_t 
  * recomputes the same result and takes the owed check over instead of waiting for it. */
 int hsflow_solve(hsflow_ctx *ctx, const hsflow_params *params);
 int hsflow_solve_async(hsflow_ctx *ctx, const hsflow_params *params);
+/* hsflow_set_frames_u8_device(ctx, 0, ...) + hsflow_solve_async(ctx, params) as ONE call, for a stream of resident pairs
+ * (what hsflow_pipeline_submit_device does per pair).  Same results, same state afterwards -- the context holds its own
+ * copy of both frames -- but where the solve's first Jacobi launch is the strip kernel with the derivative pass in it
+ * (hsflow_info.deriv_fused, kernel STRIP: frames at least one region large, up to 6 rows per lane, CV mode, no
+ * profiling, not the persistent launch), the context holds one pair, both pointers are 4-byte aligned and both strides
+ * multiples of 4, that launch reads the caller's planes where they lie and its core lanes store the context's copy next
+ * to the derivative words: no copy kernel runs (1080 workgroups, 4 MB read and written and one more kernel in every
+ * pair's chain at 1080p).  In every other case the copy kernel runs first, as with the two calls.  With use_graph the
+ * first launch, which carries this call's pointers, is issued by itself and the cached graph replays the launches after
+ * it: one launch and one graph launch per call, as before.  The caller's planes must stay unchanged until the solve has
+ * been waited for (hsflow_wait_solve, hsflow_synchronize).  HSFLOW_KEEP_FRAME_COPY=1 in the environment: always copy. */
+int hsflow_solve_async_frames_device(hsflow_ctx *ctx, const void *d_prev, size_t prev_stride, const void *d_curr,
+                                     size_t curr_stride, const hsflow_params *params);
+/* How many hsflow_solve_async_frames_device calls of this context went without the copy kernel so far. */
+int hsflow_frame_copies_elided(hsflow_ctx *ctx, uint64_t *count);
 int hsflow_synchronize(hsflow_ctx *ctx);
 
 /* --- results out -------------------------------------------------------------------------- */
@@ -495,13 +510,14 @@ int hsflow_pipeline_submit_ex(hsflow_pipeline *pl, int format, const uint8_t *pr
                               const uint8_t *curr, size_t curr_stride, float *u, size_t u_stride,
                               float *v, size_t v_stride, const hsflow_params *params, uint64_t *ticket);
 /* The same for a stream of pairs that are ALREADY IN DEVICE MEMORY (a decoder's or a camera's output, the frames of a
- * resident sequence): the frames are copied device to device into the slot, the flow stays in the slot and is handed
+ * resident sequence): the slot gets its own copy of the frames (hsflow_solve_async_frames_device: written by the solve's
+ * first launch where that can read the caller's planes, by a copy kernel ahead of it otherwise), the flow stays in the slot and is handed
  * out by hsflow_pipeline_flow_device -- no host buffer anywhere.  This is the reference's camera loop
  * (OpticalFlowOpenCV.cpp:91-95: fresh frames, ITER|EPS, every pair) at the speed of the solver: while pair k's
  * early-stop check is still owed, pair k+1 is already running on the next slot's stream; the check is looked at when
  * somebody asks for pair k (wait / flow_device / info / the slot's reuse `depth` submissions later), and a pair whose
  * early stop fired is re-solved from its slot's frames, which nothing has touched.  The caller's frame buffers must
- * be complete when submit is called (they are read by a copy enqueued on the slot's stream) and may be reused once
+ * be complete when submit is called (they are read by work enqueued on the slot's stream) and may be reused once
  * any later call on the pipeline has returned that waited for this ticket. */
 int hsflow_pipeline_submit_device(hsflow_pipeline *pl, const void *d_prev, size_t prev_stride, const void *d_curr,
                                   size_t curr_stride, const hsflow_params *params, uint64_t *ticket);
@@ -519,11 +535,17 @@ int hsflow_pipeline_render_device(hsflow_pipeline *pl, uint64_t ticket, const hs
  * what the slot actually ran is verified, including a launch shape the pipeline chose itself (three or more lanes).
  * HSFLOW_E_STATE if the slot has been reused already. */
 int hsflow_pipeline_verify(hsflow_pipeline *pl, uint64_t ticket, hsflow_verify_report *report);
+/* wait(ticket) + the slot's own copy of that pair's frames into host memory (hsflow_get_frames_u8 of its slot): what a
+ * re-solve, a verify or a render of that ticket works from.  HSFLOW_E_STATE if the slot has been reused already. */
+int hsflow_pipeline_frames_u8(hsflow_pipeline *pl, uint64_t ticket, uint8_t *prev, size_t prev_stride, uint8_t *curr,
+                              size_t curr_stride);
 /* wait(ticket) + iterations_done, last_eps, eps_rerun ... of that pair; HSFLOW_E_STATE once a later
  * pair has finished on the same slot (ask before submitting `depth` more pairs). */
 int hsflow_pipeline_info(hsflow_pipeline *pl, uint64_t ticket, hsflow_info *info);
 int hsflow_pipeline_drain(hsflow_pipeline *pl);                 /* wait for everything submitted */
 int hsflow_pipeline_depth(hsflow_pipeline *pl);
+/* Submissions so far whose frame copy rode in the solve's first launch (sum of hsflow_frame_copies_elided over the slots). */
+int hsflow_pipeline_copies_elided(hsflow_pipeline *pl, uint64_t *count);
 const char *hsflow_pipeline_last_error(hsflow_pipeline *pl);    /* pl may be NULL: create() error */
 
 /* --- several GPUs from one host process ----------------------------------------------------- */

@@ -93,6 +93,8 @@ PROTOTYPES = {
     "hsflow_push_frame_u8": (_i, [_vp, _i, _vp, _sz]),
     "hsflow_solve": (_i, [_vp, _pp]),
     "hsflow_solve_async": (_i, [_vp, _pp]),
+    "hsflow_solve_async_frames_device": (_i, [_vp, _vp, _sz, _vp, _sz, _pp]),
+    "hsflow_frame_copies_elided": (_i, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
     "hsflow_synchronize": (_i, [_vp]),
     "hsflow_wait_solve": (_i, [_vp]),
     "hsflow_get_flow": (_i, [_vp, _i, _vp, _sz, _vp, _sz]),
@@ -135,6 +137,8 @@ PROTOTYPES = {
     "hsflow_pipeline_info": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(HsflowInfo)]),
     "hsflow_pipeline_drain": (_i, [_vp]),
     "hsflow_pipeline_depth": (_i, [_vp]),
+    "hsflow_pipeline_copies_elided": (_i, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "hsflow_pipeline_frames_u8": (_i, [_vp, ctypes.c_uint64, _vp, _sz, _vp, _sz]),
     "hsflow_pipeline_last_error": (ctypes.c_char_p, [_vp]),
     "hsflow_multi_create": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i, _i]),
     "hsflow_multi_destroy": (_i, [_vp]),

@@ -158,6 +158,15 @@ struct hsflow_ctx {
     hipEvent_t evVerify = nullptr;
     size_t scratch_bytes = 0;
     int cur = 0;                // which of dU/dV holds the current flow
+    // hsflow_solve_async_frames_device: the caller's frames, while the solve has not yet decided who copies them (`lazy`:
+    // only inside that call), and -- once it has decided that its first Jacobi launch reads them in place and leaves the
+    // copy in dA / dB itself -- what that one launch is given (`src`: until the launch is out)
+    struct FrameRef {
+        bool active = false;
+        const uint8_t *A = nullptr, *B = nullptr;
+        long long PA = 0, PB = 0; // row pitches in bytes
+    } lazy, src;
+    unsigned long long copies_elided = 0; // submissions whose frame copy rode in the first Jacobi launch (hsflow_frame_copies_elided)
     bool frames_set = false;
     bool coef_valid = false;
     hsflow_info info;

@@ -237,11 +237,22 @@ __device__ __forceinline__ void strip_row_update(f2 &uP, f2 &uQ, f2 &vP, f2 &vQ,
 // large as the region, so that one bounce suffices.
 // Register row r of the lane is image row y0 + dir * r (dir = -1: the folded kernel's lower half, whose
 // registers run bottom-up).
-template <int R>
+// FrameSrc (the strip kernel's launches): the frames may lie in the CALLER's planes, with row pitches of their own; the
+// lanes named by `keep` (bit r: register row r is a core row of a core lane) then store the frame words of their rows
+// into the context's planes as soon as they have arrived -- the first launch of a stream submission replaces the frame
+// copy (hsflow_solve_async_frames_device).
+struct FrameSrc {
+    int PA, PB;             // row pitches of fA / fB in bytes (the context's own planes: g.P)
+    uint8_t *keepA, *keepB; // the context's frame planes when fA / fB are the caller's, else NULL: nothing is stored
+};
+
+template <int R, bool EXT = false>
 __device__ __forceinline__ void strip_derive(const uint8_t *__restrict__ fA, const uint8_t *__restrict__ fB,
                                              const StripGeom &g, long long base, int x0, int y0, int dir, bool xin,
-                                             uint4 (&lc)[R])
+                                             uint4 (&lc)[R], const FrameSrc fs = FrameSrc{0, 0, nullptr, nullptr},
+                                             const unsigned keep = 0)
 {
+    const int PA = EXT ? fs.PA : g.P, PB = EXT ? fs.PB : g.P;
     // How this lane reads its four columns of a frame row: 0 an aligned word (group inside the image), 1 an
     // aligned word read backwards (group wholly mirrored: left of the image, or right of it when W % 4 == 0),
     // 2 four reflected bytes (W % 4 != 0: the group that straddles column W-1 and those right of it).
@@ -264,10 +275,10 @@ __device__ __forceinline__ void strip_derive(const uint8_t *__restrict__ fA, con
     uint32_t wa[R + 2], wbv[R];
 #pragma unroll
     for (int j = 0; j < R + 2; j++)
-        wa[j] = *(const uint32_t *)(fA + base + (long long)mirror_index(y0 + dir * (j - 1), g.H) * g.P + (mode == 2 ? 0 : xg));
+        wa[j] = *(const uint32_t *)(fA + base + (long long)mirror_index(y0 + dir * (j - 1), g.H) * PA + (mode == 2 ? 0 : xg));
 #pragma unroll
     for (int r = 0; r < R; r++)
-        wbv[r] = *(const uint32_t *)(fB + base + (long long)mirror_index(y0 + dir * r, g.H) * g.P + (mode == 2 ? 0 : xg));
+        wbv[r] = *(const uint32_t *)(fB + base + (long long)mirror_index(y0 + dir * r, g.H) * PB + (mode == 2 ? 0 : xg));
     if (mode == 1) {
 #pragma unroll
         for (int j = 0; j < R + 2; j++) wa[j] = __builtin_bswap32(wa[j]);
@@ -280,9 +291,24 @@ __device__ __forceinline__ void strip_derive(const uint8_t *__restrict__ fA, con
                 return (uint32_t)row[xb[0]] | ((uint32_t)row[xb[1]] << 8) | ((uint32_t)row[xb[2]] << 16) | ((uint32_t)row[xb[3]] << 24);
             };
 #pragma unroll
-            for (int j = 0; j < R + 2; j++) wa[j] = bytes(fA + base + (long long)mirror_index(y0 + dir * (j - 1), g.H) * g.P);
+            for (int j = 0; j < R + 2; j++) wa[j] = bytes(fA + base + (long long)mirror_index(y0 + dir * (j - 1), g.H) * PA);
 #pragma unroll
-            for (int r = 0; r < R; r++) wbv[r] = bytes(fB + base + (long long)mirror_index(y0 + dir * r, g.H) * g.P);
+            for (int r = 0; r < R; r++) wbv[r] = bytes(fB + base + (long long)mirror_index(y0 + dir * r, g.H) * PB);
+        }
+    }
+    if constexpr (EXT) {
+        // The frames are the caller's: the core lanes leave the context's own copy behind (the cores tile the image, and no
+        // workgroup of this launch reads those planes; mirrored groups are never core lanes).  A group that straddles
+        // column W-1 stores reflected bytes into the row's padding, which nothing reads.
+        if (fs.keepA != nullptr) { // launch-uniform
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                if ((keep >> r) & 1u) {
+                    const long long o = base + (long long)(y0 + dir * r) * g.P + x0;
+                    *(uint32_t *)(fs.keepA + o) = wa[r + 1];
+                    *(uint32_t *)(fs.keepB + o) = wbv[r];
+                }
+            }
         }
     }
     int a[R + 2][6]; // columns x0-1 .. x0+4 of the reflected rows y0 - dir, y0, ..., y0 + dir * R
@@ -323,7 +349,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
                                                         unsigned long long *__restrict__ stamps,
                                                         const float eps_thr, const uint8_t *__restrict__ fA,
                                                         const uint8_t *__restrict__ fB, uint32_t *__restrict__ coef_w,
-                                                        const PersistArgs pa = PersistArgs())
+                                                        const FrameSrc fs, const PersistArgs pa = PersistArgs())
 {
     static_assert(!PERSIST || EPS == 0 || EPS == 2, "the persistent form runs plain or witness phases");
     // EPS == 1: eps_out[sweep * eps_stride + workgroup] receives that workgroup's max |new - old| over
@@ -482,7 +508,15 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
         }
     }
     if constexpr (DERIV) {
-        strip_derive<R>(fA, fB, g, base, x0, rev ? y0 + R - 1 : y0, rev ? -1 : 1, xin, lc);
+        unsigned keep = 0; // (the core rows of a core lane: rowcore and lanecore, below)
+        if (fs.keepA != nullptr && (x0 >= 0) && (x0 < g.W) && (4 * lane >= g.HX) && (4 * lane < g.HX + g.CW)) {
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const int j = w * R + img_row(r), y = y0 + img_row(r);
+                if (j >= g.T && j < g.T + g.CH && y >= 0 && y < g.H) keep |= 1u << r;
+            }
+        }
+        strip_derive<R, true>(fA, fB, g, base, x0, rev ? y0 + R - 1 : y0, rev ? -1 : 1, xin, lc, fs, keep);
 #pragma unroll
         for (int r = 0; r < R; r++) unpack_row(r);
     }
@@ -931,14 +965,15 @@ __global__ __launch_bounds__(NTMAX) void k_jacobi_strip(const uint32_t *__restri
                                                         const float eps_thr)
 {
     strip_body<R, NTMAX, EPS, E0, false>(coef, u_in, v_in, u_out, v_out, g, ilambda, eps_out, eps_stride, stamps, eps_thr,
-                                     nullptr, nullptr, nullptr);
+                                     nullptr, nullptr, nullptr, FrameSrc{0, 0, nullptr, nullptr});
 }
 
 // First launch of a solve with the derivative pass folded in: reads the two frames instead of the packed
 // derivative plane and writes that plane for the launches that follow (and for hsflow_get_derivatives).
+// fs: where the frames lie -- the context's planes, or the caller's, which this launch then also copies (FrameSrc).
 template <int R, int NTMAX, int EPS, int E0>
 __global__ __launch_bounds__(NTMAX) void k_jacobi_strip_deriv(const uint8_t *__restrict__ fA,
-                                                              const uint8_t *__restrict__ fB,
+                                                              const uint8_t *__restrict__ fB, const FrameSrc fs,
                                                               uint32_t *__restrict__ coef_w,
                                                               const float *__restrict__ u_in,
                                                               const float *__restrict__ v_in,
@@ -950,7 +985,7 @@ __global__ __launch_bounds__(NTMAX) void k_jacobi_strip_deriv(const uint8_t *__r
                                                               const float eps_thr)
 {
     strip_body<R, NTMAX, EPS, E0, true>(nullptr, u_in, v_in, u_out, v_out, g, ilambda, eps_out, eps_stride, stamps, eps_thr,
-                                    fA, fB, coef_w);
+                                    fA, fB, coef_w, fs);
 }
 
 // One launch for the whole solve (PersistArgs above).  DERIV: phase 0 computes the derivative words from the frames and
@@ -967,7 +1002,7 @@ __global__ __launch_bounds__(NTMAX) void k_jacobi_strip_persist(const uint8_t *_
                                                                 const float eps_thr, const PersistArgs pa)
 {
     strip_body<R, NTMAX, EPS, E0, DERIV, true>(coef_rw, u_in, v_in, nullptr, nullptr, g, ilambda, eps_out, eps_stride, stamps, eps_thr,
-                                               fA, fB, coef_rw, pa);
+                                               fA, fB, coef_rw, FrameSrc{g.P, g.P, nullptr, nullptr}, pa);
 }
 
 // ------------------------------------------------------------------------------------------

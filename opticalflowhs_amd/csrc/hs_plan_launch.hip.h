@@ -400,7 +400,13 @@ hipError_t launch_strip_k(const hsflow_ctx *c, const StripPlan &p, const float *
     constexpr auto kern = strip_kernel<R, NTMAX, (int)EPS, FOLD, DERIV, E0>();
     if (p.g.zero_in) ui = vi = c->dZero; // flow from zero: one row of zeros stands in for both planes (StripGeom::zero_in)
     unsigned long long *stamps = p.tiles <= 65536 ? c->dStamps : nullptr;
-    if constexpr (DERIV) // (the kernel takes the two frames ahead of the coefficient plane it writes)
+    if constexpr (DERIV && !FOLD) { // (the kernel takes the two frames ahead of the coefficient plane it writes)
+        // the frames: the context's planes, or the caller's, which this launch then also copies into them (resolve_lazy_frames)
+        const bool ext = c->src.active;
+        const hsk::FrameSrc fs{ext ? (int)c->src.PA : c->P, ext ? (int)c->src.PB : c->P, ext ? c->dA : nullptr, ext ? c->dB : nullptr};
+        return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, ext ? c->src.A : c->dA, ext ? c->src.B : c->dB, fs, c->dCoef, ui, vi, uo, vo,
+                                p.g, coeff, c->epsPtr, c->epsStride, stamps, c->epsThr);
+    } else if constexpr (DERIV)
         return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dA, c->dB, c->dCoef, ui, vi, uo, vo, p.g, coeff, c->epsPtr,
                                 c->epsStride, stamps, c->epsThr);
     else

@@ -33,6 +33,48 @@ int check_ctx(hsflow_ctx *c, int pair)
     return HSFLOW_OK;
 }
 
+// Both frames of a pair from device memory into the context's planes: ONE launch on the context's stream (two 2-D copies
+// cost two launches and their gaps: 5 % of a 1080p / 100 solve).
+hipError_t launch_frame_copy(hsflow_ctx *c, int pair, const void *dprev, size_t ps, const void *dcurr, size_t cs)
+{
+    const dim3 grid((c->W + 1023) / 1024, (c->H + 3) / 4, 2), block(64, 4);
+    const bool aligned = (((uintptr_t)dprev | (uintptr_t)dcurr | ps | cs) & 15u) == 0;
+    uint8_t *dA = c->dA + pair * c->plane, *dB = c->dB + pair * c->plane;
+    if (aligned)
+        hipLaunchKernelGGL(hsk::k_copy_pair_u8<true>, grid, block, 0, c->stream, (const uint8_t *)dprev, (long long)ps, (const uint8_t *)dcurr,
+                           (long long)cs, dA, dB, c->W, c->H, c->P);
+    else
+        hipLaunchKernelGGL(hsk::k_copy_pair_u8<false>, grid, block, 0, c->stream, (const uint8_t *)dprev, (long long)ps, (const uint8_t *)dcurr,
+                           (long long)cs, dA, dB, c->W, c->H, c->P);
+    return hipGetLastError();
+}
+
+// Could the first Jacobi launch of a solve read these frames where they lie (hsk::FrameSrc)?  It reads a lane's four
+// columns as one word, so both planes must be word-aligned with pitches that keep every row so; one pair per context.
+// HSFLOW_KEEP_FRAME_COPY=1: never (A/B runs).  Whether the solve HAS such a launch it decides itself (resolve_lazy_frames).
+bool frames_readable_in_place(const hsflow_ctx *c, const void *dprev, size_t ps, const void *dcurr, size_t cs)
+{
+    static const bool keep = getenv("HSFLOW_KEEP_FRAME_COPY") && atoi(getenv("HSFLOW_KEEP_FRAME_COPY")) != 0;
+    return !keep && c->N == 1 && (((uintptr_t)dprev | (uintptr_t)dcurr | ps | cs) & 3u) == 0 && ps <= (size_t)INT32_MAX && cs <= (size_t)INT32_MAX;
+}
+
+// The frames of hsflow_solve_async_frames_device, once the solve knows its first launch: in_place -- that launch carries
+// the derivative pass on the strip kernel, reads the caller's planes and stores the context's copy (c->src, for that one
+// launch); otherwise the copy kernel goes out now, ahead of whatever reads dA / dB.  Never inside a capture or a dry run.
+int resolve_lazy_frames(hsflow_ctx *c, bool in_place)
+{
+    if (!c->lazy.active) return HSFLOW_OK;
+    c->lazy.active = false;
+    if (in_place) {
+        c->src = c->lazy;
+        c->src.active = true;
+        c->copies_elided++;
+        return HSFLOW_OK;
+    }
+    HS_HIP(c, launch_frame_copy(c, 0, c->lazy.A, (size_t)c->lazy.PA, c->lazy.B, (size_t)c->lazy.PB));
+    return HSFLOW_OK;
+}
+
 struct Profiler { // brackets kernels with events when params.profile is set
     hsflow_ctx *c;
     bool on;
@@ -171,17 +213,21 @@ int configure_persist(hsflow_ctx *c, const StripPlan &sp, EpsMode eps, bool deri
 
 // Enqueue derivative pass + `iters` Jacobi sweeps (no host synchronisation inside).
 int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters, int kernel, int T,
-                  const JPlan *plan, const JPlan *tail_plan, Profiler &prof, bool do_deriv, bool zero_flow, bool persist = false)
+                  const JPlan *plan, const JPlan *tail_plan, Profiler &prof, bool do_deriv, bool zero_flow, bool persist = false,
+                  int part = 0)
 {
+    // part: 0 the whole sequence; 1 up to and including the first Jacobi launch; 2 what follows it (c->cur as part 1 left
+    // it).  A solve whose first launch reads the caller's frames (c->src) issues that launch by itself, with this
+    // submission's pointers, and replays the rest from the graph cache.
     // u = v = 0 at the start (reference behaviour, use_previous = 0): instead of clearing two
     // planes and reading them back, the first launch is told that its input is zero.
     int zero_in = zero_flow ? 1 : 0;
-    if (zero_flow) c->cur = 0;
+    if (zero_flow && part != 2) c->cur = 0;
     // the derivative pass rides in the first Jacobi launch where the kernel can do it (not when profiling:
     // deriv_ms / jacobi_ms then keep their meaning)
     bool fuse = do_deriv && !p.profile && kernel != HSFLOW_KERNEL_SIMPLE &&
                 strip_deriv_fusable(c, iters >= T ? *plan : *tail_plan);
-    if (do_deriv && !fuse) {
+    if (do_deriv && !fuse && part != 2) {
         prof.begin(0);
         HS_HIP(c, launch_deriv(c));
         prof.end();
@@ -204,6 +250,13 @@ int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters,
             left -= 1;
         } else {
             const JPlan *pl = (left >= T) ? plan : tail_plan;
+            if (part == 2 && launches == 0) { // (part 1 issued it)
+                fuse = false;
+                left -= pl->T;
+                zero_in = 0;
+                launches++;
+                continue;
+            }
             prof.begin(1);
             HS_HIP(c, launch_j(c, *pl, EpsMode::None, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, zero_in, fuse));
             prof.end();
@@ -213,6 +266,7 @@ int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters,
         c->cur = b;
         zero_in = 0;
         launches++;
+        if (part == 1) break;
     }
     c->info.jacobi_launches = launches;
     return HSFLOW_OK;

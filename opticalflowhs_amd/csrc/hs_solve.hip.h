@@ -344,20 +344,38 @@ int solve_fixed(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Prof
     if (S.persist) { // buffers and phase counters: outside any capture
         if ((st = persist_reserve(c)) || (st = persist_prepare_flags(c, S.plan.s.tiles))) return st;
     }
+    // the frames of hsflow_solve_async_frames_device: read in place by the first launch where that is the strip kernel with
+    // the derivative pass, else copied now
+    const bool in_place = c->lazy.active && c->info.deriv_fused && !S.persist && (iters >= T ? S.plan : tail).kind == HSFLOW_KERNEL_STRIP;
+    if ((st = resolve_lazy_frames(c, in_place))) return st;
+    int part = 0;
     auto enqueue = [&](int *n) -> int {
-        const int e = enqueue_fixed(c, p, S.coeff, iters, S.kernel, T, &S.plan, &tail, prof, do_deriv, zero, S.persist);
+        const int e = enqueue_fixed(c, p, S.coeff, iters, S.kernel, T, &S.plan, &tail, prof, do_deriv, zero, S.persist, part);
         *n = c->info.jacobi_launches;
         return e;
     };
     int n = 0;
-    if (p.use_graph && !p.profile) {
+    if (p.use_graph && !p.profile && in_place) {
+        // that launch carries this submission's pointers: issued by itself; the cached graph holds the launches after it
+        GraphKey key{p.mode, S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
+                     c->info.groups_per_thread, zero ? 0 : c->cur, p.use_previous * 2 + (do_deriv ? 1 : 0) + 16, S.coeff};
+        part = 1;
+        st = enqueue(&n);
+        c->src.active = false;
+        if (st) return st;
+        part = 2;
+        if (iters > T && (st = run_captured(c, key, enqueue, &n))) return st;
+        c->info.jacobi_launches = n;
+    } else if (p.use_graph && !p.profile) {
         GraphKey key{p.mode, S.persist ? HSFLOW_KERNEL_PERSIST : S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
                      c->info.groups_per_thread, zero ? 0 : c->cur, p.use_previous * 2 + (do_deriv ? 1 : 0), S.coeff};
         if ((st = run_captured(c, key, enqueue, &n))) return st;
         c->info.jacobi_launches = n;
     } else {
         if (S.persist && (st = configure_persist(c, S.plan.s, EpsMode::None, c->info.deriv_fused != 0, S.coeff))) return st;
-        if ((st = enqueue(&n))) return st;
+        st = enqueue(&n);
+        c->src.active = false;
+        if (st) return st;
     }
     c->coef_valid = true;
     c->coef_mode = HSFLOW_MODE_CV;
@@ -428,24 +446,31 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
     // the first launch also does the derivative pass where the kernel can (hs_plan_launch.hip.h)
     const bool fuse_deriv = do_deriv && !p.profile && strip_deriv_fusable(c, firstp);
     c->info.deriv_fused = fuse_deriv;
-    // the whole pass as one enqueue sequence (nothing allocated, nothing synchronised: capturable)
+    // the frames of hsflow_solve_async_frames_device: read in place by the first launch where that is the strip kernel with
+    // the derivative pass, else copied now
+    const bool in_place = c->lazy.active && fuse_deriv && !persist && firstp.kind == HSFLOW_KERNEL_STRIP;
+    if ((st = resolve_lazy_frames(c, in_place))) return st;
+    // the whole pass as one enqueue sequence (nothing allocated, nothing synchronised: capturable).  part: 0 all of it; 1 up
+    // to and including the first Jacobi launch; 2 what follows it (c->cur as part 1 left it) -- a first launch that reads
+    // the caller's frames carries this submission's pointers, so it goes out by itself and the cached graph holds the rest
+    int part = 0;
     auto enqueue = [&](int *n) -> int {
-        if (p.use_previous && (st = save_start(c))) return st;
+        if (part != 2 && p.use_previous && (st = save_start(c))) return st;
         c->epsStride = stride; // (no clearing: every launch writes all its words, the reduction reads only those)
-        if (do_deriv && !fuse_deriv) {
+        if (part != 2 && do_deriv && !fuse_deriv) {
             prof.begin(0);
             HS_HIP(c, launch_deriv(c));
             prof.end();
         }
         const int zero_w = p.use_previous ? 0 : 1;
-        if (zero_w) c->cur = 0;
+        if (zero_w && part != 2) c->cur = 0;
         if (persist) { // one launch, a row of witness words per phase
             c->epsPtr = c->dEpsTiles;
             prof.begin(1);
             const int e = enqueue_persist(c, plan.s, iters, EpsMode::Witness, fuse_deriv, zero_w, S.coeff);
             prof.end();
             if (e) return e;
-        } else for (int L = 0; L < n_launch; L++) {
+        } else for (int L = part == 2 ? 1 : 0; L < (part == 1 ? 1 : n_launch); L++) {
             const bool is_last = L == n_launch - 1;
             const int a = c->cur, b = a ^ 1;
             c->epsPtr = c->dEpsTiles + (size_t)L * stride;
@@ -457,6 +482,7 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
             c->cur = b;
         }
         *n = persist ? 1 : n_launch;
+        if (part == 1) return HSFLOW_OK;
         if (async && !c->async_reduce) { // the reduction of the witness words waits until somebody settles the check (settle_pending)
             c->epsPtr = c->dEps;
             c->epsStride = 1;
@@ -465,16 +491,27 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
         // (an asynchronous solve gets here only with the in-stream reduction on: its last workgroup writes the marker too)
         return eps_collect_enqueue(c, words, async && c->hMark != nullptr);
     };
-    if (p.use_graph && !p.profile) {
+    // (a single launch read in place leaves nothing worth a graph behind it)
+    if (p.use_graph && !p.profile && !(in_place && n_launch == 1)) {
         GraphKey key{p.mode, persist ? HSFLOW_KERNEL_PERSIST : S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
                      c->info.groups_per_thread, p.use_previous ? c->cur : 0,
-                     p.use_previous * 2 + (do_deriv ? 1 : 0) + (async ? 4 : 0) + (async && c->async_reduce ? 8 : 0), S.coeff, c->epsThr};
+                     p.use_previous * 2 + (do_deriv ? 1 : 0) + (async ? 4 : 0) + (async && c->async_reduce ? 8 : 0) + (in_place ? 16 : 0),
+                     S.coeff, c->epsThr};
+        if (in_place) {
+            part = 1;
+            st = enqueue(launches);
+            c->src.active = false;
+            if (st) return st;
+            part = 2;
+        }
         if ((st = run_captured(c, key, enqueue, launches))) return st;
         c->epsPtr = c->dEps; // (a replay ran none of the sequence's host side)
         c->epsStride = 1;
     } else {
         if (persist && (st = configure_persist(c, plan.s, EpsMode::Witness, fuse_deriv, S.coeff))) return st;
-        if ((st = enqueue(launches))) return st;
+        st = enqueue(launches);
+        c->src.active = false;
+        if (st) return st;
     }
     c->coef_valid = true;
     c->coef_mode = HSFLOW_MODE_CV;
@@ -600,6 +637,7 @@ int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, P
         if ((st = witness_pass(c, p, S, tailp, stride, do_deriv, prof, async, &launches, &rerun)) || !rerun) return st;
         if ((st = eps_prepare(c, iters, stride))) return st;
     } else {
+        if ((st = resolve_lazy_frames(c, false))) return st;
         if (p.use_previous && (st = save_start(c))) return st;
         if ((st = eps_prepare(c, iters, stride))) return st;
         if (do_deriv) {
@@ -853,7 +891,10 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
         return fail(c, HSFLOW_E_ARG, "params null or struct_size mismatch");
     const hsflow_params &p = *pp;
     if (!c->frames_set) return fail(c, HSFLOW_E_STATE, "frames were not set");
-    if (p.mode == HSFLOW_MODE_CLASSIC || p.mode == HSFLOW_MODE_CLASSIC_AS_SHIPPED) return solve_classic(c, p, async);
+    if (p.mode == HSFLOW_MODE_CLASSIC || p.mode == HSFLOW_MODE_CLASSIC_AS_SHIPPED) {
+        if ((st = resolve_lazy_frames(c, false))) return st; // (the classic kernels read the context's planes)
+        return solve_classic(c, p, async);
+    }
     if (p.mode != HSFLOW_MODE_CV) return fail(c, HSFLOW_E_ARG, "unknown mode");
     c->info.eps_rerun = 0;
     c->info.deriv_fused = 0;
@@ -893,6 +934,7 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
     if (!S.use_eps) return solve_fixed(c, S.eff, S, prof, async);
     constexpr long long kSpecMax = 1 << 16; // speculative ITER|EPS: the whole budget in one go
     if (S.use_iter && p.max_iter > 0 && S.budget <= kSpecMax) return solve_iter_eps(c, S.eff, S, prof, async);
+    if ((st = resolve_lazy_frames(c, false))) return st;
     return solve_eps_chunks(c, S.eff, S, prof);
 }
 

@@ -286,18 +286,7 @@ int hsflow_set_frames_u8_device(hsflow_ctx *c, int pair, const void *dprev, size
     if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
     if (!dprev || !dcurr) return fail(c, HSFLOW_E_ARG, "null frame pointer");
     if (ps < (size_t)c->W || cs < (size_t)c->W) return fail(c, HSFLOW_E_SIZE, "frame stride smaller than width");
-    { // both frames in one launch (two 2-D copies cost two launches and their gaps: 5 % of a 1080p / 100 solve)
-        const dim3 grid((c->W + 1023) / 1024, (c->H + 3) / 4, 2), block(64, 4);
-        const bool aligned = (((uintptr_t)dprev | (uintptr_t)dcurr | ps | cs) & 15u) == 0;
-        uint8_t *dA = c->dA + pair * c->plane, *dB = c->dB + pair * c->plane;
-        if (aligned)
-            hipLaunchKernelGGL(hsk::k_copy_pair_u8<true>, grid, block, 0, c->stream, (const uint8_t *)dprev, (long long)ps, (const uint8_t *)dcurr,
-                               (long long)cs, dA, dB, c->W, c->H, c->P);
-        else
-            hipLaunchKernelGGL(hsk::k_copy_pair_u8<false>, grid, block, 0, c->stream, (const uint8_t *)dprev, (long long)ps, (const uint8_t *)dcurr,
-                               (long long)cs, dA, dB, c->W, c->H, c->P);
-        HS_HIP(c, hipGetLastError());
-    }
+    HS_HIP(c, launch_frame_copy(c, pair, dprev, ps, dcurr, cs));
     c->frames_set = true;
     c->coef_valid = false;
     return HSFLOW_OK;
@@ -494,6 +483,36 @@ int hsflow_take_verdict(hsflow_ctx *c, int *proven)
 
 int hsflow_solve(hsflow_ctx *c, const hsflow_params *p) { return note_solve(c, p, solve_impl(c, p, false)); }
 int hsflow_solve_async(hsflow_ctx *c, const hsflow_params *p) { return note_solve(c, p, solve_impl(c, p, true)); }
+
+int hsflow_solve_async_frames_device(hsflow_ctx *c, const void *dprev, size_t ps, const void *dcurr, size_t cs, const hsflow_params *p)
+{
+    int st = check_ctx(c, 0);
+    if (st) return st;
+    if (!dprev || !dcurr || !frames_readable_in_place(c, dprev, ps, dcurr, cs)) { // the two calls it stands for
+        if ((st = hsflow_set_frames_u8_device(c, 0, dprev, ps, dcurr, cs))) return st;
+        return hsflow_solve_async(c, p);
+    }
+    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
+    if (ps < (size_t)c->W || cs < (size_t)c->W) return fail(c, HSFLOW_E_SIZE, "frame stride smaller than width");
+    // who copies the frames is the solve's decision (resolve_lazy_frames); a solve that fails before it has decided leaves
+    // the copy to this call, so that the context holds the new frames either way, as after hsflow_set_frames_u8_device
+    c->lazy.active = true;
+    c->lazy.A = (const uint8_t *)dprev; c->lazy.B = (const uint8_t *)dcurr;
+    c->lazy.PA = (long long)ps; c->lazy.PB = (long long)cs;
+    c->frames_set = true;
+    c->coef_valid = false;
+    st = note_solve(c, p, solve_impl(c, p, true));
+    c->src.active = false;
+    const int st2 = resolve_lazy_frames(c, false);
+    return st ? st : st2;
+}
+
+int hsflow_frame_copies_elided(hsflow_ctx *c, uint64_t *count)
+{
+    if (!c || !count) return HSFLOW_E_ARG;
+    *count = c->copies_elided;
+    return HSFLOW_OK;
+}
 
 int hsflow_wait_solve(hsflow_ctx *c)
 {

@@ -237,16 +237,14 @@ int hsflow_pipeline_submit_device(hsflow_pipeline *pl, const void *d_prev, size_
     hsflow_pipeline::Slot &s = pl->slots[pl->next % pl->slots.size()];
     int st = finish_slot(pl, s); // the job that used this slot `depth` submissions ago
     if (st) return st;
-    if ((st = hsflow_set_frames_u8_device(s.ctx, 0, d_prev, ps, d_curr, cs))) {
-        hsflow_synchronize(s.ctx);
-        return ctx_fail(pl, s.ctx, st, "hsflow_set_frames_u8_device");
-    }
     hsflow_params shaped;
     const hsflow_params *use = params; // (a struct of another size is not copied: hsflow_solve_async refuses it)
     if (params->struct_size == sizeof(hsflow_params)) { shaped = stream_shape(pl, *params); use = &shaped; }
-    if ((st = hsflow_solve_async(s.ctx, use))) {
-        hsflow_synchronize(s.ctx); // the frame copies were queued: do not leave them reading caller memory
-        return ctx_fail(pl, s.ctx, st, "hsflow_solve_async");
+    // frames and solve in one call: where the solve's first launch can read the caller's planes (strip kernel with the
+    // derivative pass, word-aligned sources) it also leaves the slot's copy of them behind, and no copy kernel runs
+    if ((st = hsflow_solve_async_frames_device(s.ctx, d_prev, ps, d_curr, cs, use))) {
+        hsflow_synchronize(s.ctx); // whatever was queued: do not leave it reading caller memory
+        return ctx_fail(pl, s.ctx, st, "hsflow_solve_async_frames_device");
     }
     s.busy = true;
     s.ticket = pl->next;
@@ -316,6 +314,16 @@ int hsflow_pipeline_verify(hsflow_pipeline *pl, uint64_t ticket, hsflow_verify_r
     return HSFLOW_OK;
 }
 
+int hsflow_pipeline_frames_u8(hsflow_pipeline *pl, uint64_t ticket, uint8_t *prev, size_t ps, uint8_t *curr, size_t cs)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    if ((st = hsflow_get_frames_u8(s->ctx, 0, prev, ps, curr, cs))) return ctx_fail(pl, s->ctx, st, "hsflow_get_frames_u8");
+    return HSFLOW_OK;
+}
+
 int hsflow_pipeline_wait(hsflow_pipeline *pl, uint64_t ticket)
 {
     if (!pl) return HSFLOW_E_ARG;
@@ -353,6 +361,19 @@ int hsflow_pipeline_drain(hsflow_pipeline *pl)
         if (st && !first) first = st;
     }
     return first;
+}
+
+int hsflow_pipeline_copies_elided(hsflow_pipeline *pl, uint64_t *count)
+{
+    if (!pl || !count) return HSFLOW_E_ARG;
+    *count = 0;
+    for (auto &s : pl->slots) {
+        uint64_t n = 0;
+        const int st = hsflow_frame_copies_elided(s.ctx, &n);
+        if (st) return st;
+        *count += n;
+    }
+    return HSFLOW_OK;
 }
 
 int hsflow_pipeline_depth(hsflow_pipeline *pl) { return pl ? (int)pl->slots.size() : 0; }

@@ -88,7 +88,8 @@ class PairPipeline(object):
 
     def submit_device(self, prev, curr, params=None, **kw):
         """A pair that already lies in device memory (CUDA uint8 tensors of shape (height, width), unit column stride):
-        device-to-device copy into the slot -> solve; the flow stays in the slot (`flow_device`).  The tensors are held
+        the slot gets its own copy of the frames (from the solve's first launch where that can read the tensors in place,
+        `copies_elided`) -> solve; the flow stays in the slot (`flow_device`).  The tensors are held
         until the ticket has been waited for."""
         for a in (prev, curr):
             if not (hasattr(a, "is_cuda") and a.is_cuda) or str(a.dtype) != "torch.uint8" or tuple(a.shape) != (self.height, self.width) or a.stride(1) != 1:
@@ -139,6 +140,21 @@ class PairPipeline(object):
         self._check(self._lib.hsflow_pipeline_verify(self._h, int(ticket), ctypes.byref(r)))
         self._held.pop(int(ticket), None)
         return r
+
+    def frames(self, ticket):
+        """wait(ticket) + the slot's own copy of that pair's frames as two (H, W) uint8 NumPy arrays."""
+        a = np.empty((self.height, self.width), np.uint8)
+        b = np.empty((self.height, self.width), np.uint8)
+        self._check(self._lib.hsflow_pipeline_frames_u8(self._h, int(ticket), ctypes.c_void_p(a.ctypes.data), a.strides[0],
+                                                        ctypes.c_void_p(b.ctypes.data), b.strides[0]))
+        self._held.pop(int(ticket), None)
+        return a, b
+
+    def copies_elided(self):
+        """Submissions so far whose frame copy rode in the solve's first launch (hsflow_pipeline_copies_elided)."""
+        n = ctypes.c_uint64()
+        self._check(self._lib.hsflow_pipeline_copies_elided(self._h, ctypes.byref(n)))
+        return n.value
 
     def wait(self, ticket):
         self._check(self._lib.hsflow_pipeline_wait(self._h, int(ticket)))
