@@ -45,7 +45,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 7 /* 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 8 /* 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -125,9 +125,12 @@ typedef struct hsflow_info {
     uint32_t struct_size;
     int32_t width, height, n_pairs, pitch; /* pitch in elements, same for every plane    */
     int32_t iterations_done;  /* sweeps executed by the last solve; the same for every pair of the
-                                 context (a batch stops as one, see hsflow_solve)               */
+                                 context while a batch stops as one (see hsflow_solve); with
+                                 hsflow_set_pair_termination the maximum over the pairs        */
     float last_eps;           /* Eps of the last sweep (EPS termination only): the maximum over all
-                                 pairs of the context, like every Eps of a batch.  An asynchronous
+                                 pairs of the context, like every Eps of a batch that stops as one;
+                                 with hsflow_set_pair_termination that of the lowest pair that ran
+                                 iterations_done sweeps.  An asynchronous
                                  ITER|EPS solve does not measure it; hsflow_get_info then runs that
                                  solve's last launch once more to obtain it (NaN if the flow was
                                  changed through hsflow_set_flow_device in between)               */
@@ -140,7 +143,8 @@ typedef struct hsflow_info {
     float jacobi_ms;          /* profile=1: sum of Jacobi kernel times                    */
     float solve_ms;           /* profile=1: first event to last event of the solve        */
     int32_t eps_rerun;        /* ITER|EPS: 1 if the fast pass could not prove "no early stop"
-                                 and the solve was repeated with Eps measured in every sweep */
+                                 and the solve was repeated with Eps measured in every sweep
+                                 (hsflow_set_pair_termination: for any pair of the context)  */
     int32_t deriv_fused;      /* 1 if the derivative pass ran inside the first Jacobi launch of the
                                  last solve instead of as a kernel of its own                    */
     int32_t persistent;       /* phases of the one persistent launch the last solve ran as
@@ -154,7 +158,8 @@ void hsflow_default_params(hsflow_params *p);
 
 /* n_pairs independent image pairs of width x height live in one context (n_pairs >= 1).  Under ITER termination
  * the pairs are independent: each one's flow is bit for bit what a context of its own computes.  Under EPS they share
- * ONE stopping sweep (hsflow_solve): a pair's flow then depends on the others it is solved with.  Any n_pairs is
+ * ONE stopping sweep by default (hsflow_solve): a pair's flow then depends on the others it is solved with; with
+ * hsflow_set_pair_termination every pair stops on its own Eps and is independent under EPS too.  Any n_pairs is
  * accepted here; one whose launches would exceed the device's grid limits has no plan (HSFLOW_E_SIZE at the solve).
  * device: HIP ordinal.  stream: the hipStream_t all work is issued on (e.g. torch's current
  * stream; NULL is the device's default stream).  own_stream != 0: ignore `stream` and create a
@@ -185,6 +190,53 @@ int hsflow_set_cu_share(hsflow_ctx *ctx, int compute_units);
  * the stream.  Off by default: back-to-back solves on ONE stream would pay the kernel and its boundary every time. */
 int hsflow_set_async_reduce(hsflow_ctx *ctx, int on);
 
+/* How a context of several pairs stops under EPS termination (HSFLOW_MODE_CV, term_type EPS or ITER|EPS).
+ * per_pair = 0 (the default): the batch stops as one, on the maximum of its pairs' Eps (hsflow_solve).
+ * per_pair = 1: every pair stops on its OWN Eps, as cvCalcOpticalFlowHS called pair by pair does
+ * (OpticalFlowOpenCV.cpp:29,94): pair i's flow, iterations_done and last_eps (hsflow_get_pair_result) are bit for bit
+ * what a one-pair context computes for the same frames with the same parameters -- mode, lambda, criteria, kernel
+ * choice, use_previous, row origin, Eps rows -- through hsflow_solve and hsflow_solve_async alike (with or without
+ * use_graph and hsflow_set_async_reduce), once the owed check is settled; the one exemption is the project's own, values
+ * below 1e-30 between different launch shapes (HSFLOW_VERIFY_TINY).  A batch then behaves like n_pairs calls of
+ * cvCalcOpticalFlowHS.
+ * How: the speculative witness pass of ITER|EPS runs over ALL pairs to the budget exactly as before (same launches,
+ * same graph) and its words are reduced per pair; a proven pair stands at the budget.  The pairs that are not proven --
+ * and every pair where there is no witness pass: the simple and the LDS-tile kernel, EPS alone -- go through the exact
+ * pass TOGETHER: chunk launches over a device list of the pairs still running (n_active x tiles_per_pair workgroups),
+ * hsflow_info.fuse_steps sweeps per chunk (HSFLOW_KERNEL_SIMPLE: HSFLOW_PAIR_STOP_SIMPLE_CHUNK one-sweep launches), ONE
+ * read-back of every active pair's Eps per chunk.  A pair whose stop lies in the chunk is replayed from the chunk's intact
+ * input for exactly the missing sweeps and dropped from the list; the next chunk is launched for the rest.  A pair that
+ * stops at sweep k therefore costs at most ceil(k / T) * T + k sweeps beyond the witness pass, and nothing once it has
+ * stopped.  Its final flow is copied into the other ping-pong buffer as well, so that every entry that reads or hands out
+ * a pair's flow (hsflow_get_flow*, hsflow_flow_view_device, hsflow_render_*, hsflow_compare_flow_device, hsflow_verify,
+ * hsflow_set_flow_device followed by a warm start) sees that pair's final flow, however many sweeps its neighbours ran.
+ * profile = 1: deriv_ms / jacobi_ms / solve_ms cover the witness pass; the chunk launches behind it are not bracketed.
+ * EPS alone: the stall rule (4 096 sweeps without a new minimum of Eps) runs per pair; a stalled pair keeps its flow and
+ * reports HSFLOW_E_NOTERM in hsflow_get_pair_result, and the solve returns HSFLOW_E_NOTERM after every other pair has
+ * stopped.  ITER alone and the classic modes have no Eps: nothing changes.  hsflow_solve_probe* do not depend on it.
+ * HSFLOW_KERNEL_PERSIST on a context of several pairs with EPS in term_type is refused while the switch is on
+ * (HSFLOW_E_ARG: the one launch holds every pair to its last phase).
+ * Takes effect from the next solve; settles an owed check first.  On a one-pair context it is accepted and changes
+ * nothing.  The existing take-over of an owed check by a bit-identical repeat solve keeps working. */
+#define HSFLOW_PAIR_STOP_SIMPLE_CHUNK 32 /* one-sweep launches between two read-backs of the per-pair exact pass (a design constant) */
+int hsflow_set_pair_termination(hsflow_ctx *ctx, int per_pair);
+
+/* What the last solve did for ONE pair of the context. */
+typedef struct hsflow_pair_result {
+    uint32_t struct_size;     /* = sizeof(hsflow_pair_result), set by the caller                          */
+    int32_t pair;
+    int32_t status;           /* HSFLOW_OK, or HSFLOW_E_NOTERM for a pair the stall rule gave up on       */
+    int32_t iterations_done;  /* sweeps this pair's flow has run                                          */
+    float last_eps;           /* this pair's Eps at its last sweep                                        */
+    int32_t eps_rerun;        /* 1: the witness pass proved nothing for this pair; it took the exact pass */
+    int64_t sweeps_executed;  /* every sweep the device ran for this pair in the last solve, speculative
+                                 and repeated ones included                                               */
+} hsflow_pair_result;
+/* With hsflow_set_pair_termination off (and for every solve without EPS) each pair reports the batch's values, status
+ * being what the solve returned.  Like hsflow_get_info it settles an owed check and measures an unmeasured last_eps.
+ * HSFLOW_E_STATE before the first solve; HSFLOW_E_ARG: null pointer, wrong struct_size, bad pair. */
+int hsflow_get_pair_result(hsflow_ctx *ctx, int pair, hsflow_pair_result *out);
+
 /* Waits until the last solve of THIS context has finished and settles the early-stop check it may owe.  With
  * hsflow_set_async_reduce on, that is a poll of the marker behind the solve: unlike hsflow_synchronize it does not wait for
  * what other contexts have enqueued on the same stream since (the slots of a pair pipeline share streams); without it,
@@ -204,10 +256,18 @@ int hsflow_set_eps_rows(hsflow_ctx *ctx, int first_row, int rows);
  * find the stopping sweep of a solve that is spread over several contexts: Eps_k of the frame = the maximum of the
  * contexts' Eps_k. */
 int hsflow_solve_probe(hsflow_ctx *ctx, const hsflow_params *params, float *sweep_eps);
+/* The same solve with the Eps of every sweep PER PAIR: sweep_eps[k * n_pairs + i] is pair i's Eps of sweep k over the rows
+ * of hsflow_set_eps_rows -- what a one-pair context's hsflow_solve_probe returns for that pair; the maximum of a row over
+ * the pairs is what hsflow_solve_probe returns.  Independent of hsflow_set_pair_termination.  The strip and the folded
+ * kernel (what AUTO picks) reduce the batch pass's words per pair in one launch; the simple and the LDS-tile kernel
+ * write one word per (sweep, pair) in this pass.  max_iter x n_pairs <= 2^28
+ * (HSFLOW_E_SIZE). */
+int hsflow_solve_probe_pairs(hsflow_ctx *ctx, const hsflow_params *params, float *sweep_eps /* [max_iter][n_pairs] */);
 /* The early-stop check an asynchronous ITER|EPS solve still owes, looked at WITHOUT acting on it: waits for the stream;
  * *proven = 1 if the witness words prove that Eps stayed >= epsilon in every sweep (over the rows of
  * hsflow_set_eps_rows), 0 if they do not -- the flow of the whole budget stands either way and nothing is re-run.  A
- * proof from ANY context of a spread solve covers the frame (its Eps is the maximum).  HSFLOW_E_STATE if nothing is owed. */
+ * proof from ANY context of a spread solve covers the frame (its Eps is the maximum).  HSFLOW_E_STATE if nothing is owed.
+ * With hsflow_set_pair_termination on a context of several pairs: *proven = 1 iff EVERY pair is proven. */
 int hsflow_take_verdict(hsflow_ctx *ctx, int *proven);
 
 /* --- frames in ---------------------------------------------------------------------------- */
@@ -242,10 +302,11 @@ int hsflow_push_frame_u8(hsflow_ctx *ctx, int pair, const uint8_t *next, size_t 
 
 /* --- solve -------------------------------------------------------------------------------- */
 
-/* Derivative pass + Jacobi iterations for every pair of the context.  EPS termination on a batch: the Eps of a sweep
- * is the maximum over ALL pairs of the context (each over the rows of hsflow_set_eps_rows), and the whole batch stops
- * at the first sweep whose Eps is below epsilon -- every pair runs the same number of sweeps, a pair that converged
- * early goes on while its neighbours do (cvCalcOpticalFlowHS, called per pair, would stop each one on its own).
+/* Derivative pass + Jacobi iterations for every pair of the context.  EPS termination on a batch, by default: the Eps
+ * of a sweep is the maximum over ALL pairs of the context (each over the rows of hsflow_set_eps_rows), and the whole
+ * batch stops at the first sweep whose Eps is below epsilon -- every pair runs the same number of sweeps, a pair that
+ * converged early goes on while its neighbours do.  cvCalcOpticalFlowHS, called per pair, stops each one on its own:
+ * hsflow_set_pair_termination makes the batch do the same.
  * hsflow_solve returns
  * after the device finished; hsflow_solve_async only enqueues (no profile) and the caller
  * synchronises the stream or calls hsflow_synchronize.  Asynchronous solves take ITER termination
@@ -425,7 +486,10 @@ typedef struct hsflow_verify_report { /* 120 bytes */
  * of the mode (HSFLOW_KERNEL_SIMPLE), launch by launch -- no hipGraph, no derivative pass inside a Jacobi launch, no
  * speculation -- from zero flow, with the same mode, lambda / alpha, term_type, max_iter, epsilon, row origin and Eps
  * rows.  Under EPS it finds its OWN stopping sweep from Eps measured in every sweep (iterations_ref).  It always covers
- * every pair of the context, because under EPS a batch stops as one.  Then k_plane_compare over the flow planes
+ * every pair of the context, because under EPS a batch stops as one.  After a solve whose pairs stopped each on its own
+ * (hsflow_set_pair_termination) it finds EVERY pair's own stopping sweep, from the one-sweep kernel's Eps of that pair
+ * alone: pair = i reports pair i's iterations_done / iterations_ref; pair = -1 is ok only if every pair's counts agree,
+ * and reports the counts of the lowest pair where they differ, else the maxima.  Then k_plane_compare over the flow planes
  * (a = the context's, b = the reference's) and over the packed derivative words, of `pair`, or of all pairs aggregated
  * (pair = -1).
  * It leaves the context as it found it: flow, derivatives, hsflow_info, pointers handed out by

@@ -64,7 +64,17 @@ class HsflowVerifyReport(ctypes.Structure):
                 ("deriv_differing", ctypes.c_uint64), ("deriv_first", ctypes.c_int64)]
 
 
+class HsflowPairResult(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("pair", ctypes.c_int32), ("status", ctypes.c_int32),
+                ("iterations_done", ctypes.c_int32), ("last_eps", ctypes.c_float), ("eps_rerun", ctypes.c_int32),
+                ("sweeps_executed", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
 VERIFY_TINY = 1e-30  # HSFLOW_VERIFY_TINY
+PAIR_STOP_SIMPLE_CHUNK = 32  # HSFLOW_PAIR_STOP_SIMPLE_CHUNK
 
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 _pp = ctypes.POINTER(HsflowParams)
@@ -82,6 +92,9 @@ PROTOTYPES = {
     "hsflow_set_async_reduce": (_i, [_vp, _i]),
     "hsflow_set_eps_rows": (_i, [_vp, _i, _i]),
     "hsflow_solve_probe": (_i, [_vp, _pp, ctypes.POINTER(ctypes.c_float)]),
+    "hsflow_solve_probe_pairs": (_i, [_vp, _pp, ctypes.POINTER(ctypes.c_float)]),
+    "hsflow_set_pair_termination": (_i, [_vp, _i]),
+    "hsflow_get_pair_result": (_i, [_vp, _i, ctypes.POINTER(HsflowPairResult)]),
     "hsflow_take_verdict": (_i, [_vp, ctypes.POINTER(_i)]),
     "hsflow_set_frames_u8": (_i, [_vp, _i, _vp, _sz, _vp, _sz]),
     "hsflow_set_frames_u8_async": (_i, [_vp, _i, _vp, _sz, _vp, _sz]),

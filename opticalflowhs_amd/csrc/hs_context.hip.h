@@ -39,8 +39,11 @@ enum class EpsMode : int {
 
 // Layout of the Eps words of one pass in dEpsTiles (k_eps_reduce's arguments): `slots` rows of `stride` words; the
 // first n_first rows hold cnt_first valid words (one per workgroup of a full launch), the others cnt_last.
+// pairs > 0: the pass is reduced PER PAIR (k_eps_reduce_pairs: one word per (slot, pair), hEps[slot * pairs + pair]); the
+// words of a row are then per workgroup of a strip / fold launch, cnt_first / cnt_last = tiles per pair x pairs.
 struct EpsLayout {
     int slots = 0, stride = 1, n_first = 0, cnt_first = 0, cnt_last = 0;
+    int pairs = 0;
 };
 
 struct GraphKey {
@@ -108,6 +111,10 @@ struct hsflow_ctx {
     unsigned *hEpsDev = nullptr; // the device's address of hEps
     size_t hEpsCap = 0;
     int epsStride = 1;          // words per sweep: one per workgroup (strip / fold), else 1
+    int epsPair = 0;            // simple / LDS-tile kernel: 1 = one Eps word per (sweep, pair) instead of one per sweep
+    const int *pairList = nullptr; // the running launches work on these pairs only (device array of listCount indices), NULL: on all
+    int listCount = 0;
+    int *dPairs = nullptr;      // 3 * N indices: the identity, the list of active pairs, the lists of a chunk's replays
     unsigned *dEpsTiles = nullptr; // per-sweep, per-workgroup Eps of the launches of one solve
     size_t epsTilesCap = 0;
     float *dUb = nullptr, *dVb = nullptr; // backup of the starting flow (ITER|EPS with use_previous)
@@ -123,6 +130,21 @@ struct hsflow_ctx {
     bool counted = false;        // this context is in g_live_ctx
     int eps_row0 = 0, eps_rows = 0; // hsflow_set_eps_rows: rows whose changes count for Eps (0 rows: the whole frame)
     std::vector<float> sweep_eps;   // Eps of every sweep of the last exact (per-sweep) pass: hsflow_solve_probe hands it out
+    // hsflow_set_pair_termination: under EPS termination every pair of the context stops on its own Eps (hs_solve.hip.h,
+    // "per-pair stop").  What the last solve did pair by pair (hsflow_get_pair_result); empty while the batch stops as one.
+    bool per_pair = false;
+    struct PairResult {
+        int status = 0, iterations_done = 0, eps_rerun = 0;
+        float last_eps = 0.f;
+        long long sweeps = 0;
+        bool eps_owed = false;   // stands at the budget of an asynchronous witness pass: last_eps is measured when somebody asks
+        bool in_both = false;    // took the exact pass: its final flow lies in both ping-pong buffers
+    };
+    std::vector<PairResult> pair_res;
+    bool pair_res_valid = false;    // pair_res belongs to the last solve (a per-pair solve ran)
+    long long sweeps_run = 0;       // sweeps the device ran in the last solve, speculative and repeated ones included
+    bool probe_pairs = false;       // hsflow_solve_probe_pairs: the exact pass also reduces its Eps words per pair ...
+    std::vector<float> sweep_eps_pairs; // ... into this, [sweep][pair]
     // hsflow_set_async_reduce: every asynchronous solve is followed by k_mark_done; the host waits for a solve by polling the
     // page-locked word (hsflow_wait_solve) instead of waiting for the stream
     unsigned *dSeq = nullptr, *hMark = nullptr, *hMarkDev = nullptr;
@@ -150,6 +172,8 @@ struct hsflow_ctx {
     // their copy
     hsflow_params vparams;
     int vstate = 0;             // 0: no solve yet, 1: the last solve succeeded, 2: it failed
+    int last_status = 0;        // ... and what it returned (hsflow_get_pair_result on a batch that stops as one)
+    bool v_per_pair = false;    // ... and whether its pairs stopped each on its own
     int v_org = 0, v_eps_row0 = 0, v_eps_rows = 0; // row origin and Eps rows that solve ran with
     hsflow_ctx *shadow = nullptr;
     bool borrowed = false;

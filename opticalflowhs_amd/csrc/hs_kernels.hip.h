@@ -231,8 +231,11 @@ __global__ __launch_bounds__(256) void k_jacobi_simple(const uint32_t *__restric
                                                        float *__restrict__ u_out,
                                                        float *__restrict__ v_out, int W, int H,
                                                        int P, long long plane, float ilambda,
-                                                       unsigned *__restrict__ eps_out, int org, int ey0, int ey1)
+                                                       unsigned *__restrict__ eps_out, int org, int ey0, int ey1,
+                                                       const int *__restrict__ pair_list, int eps_pair)
 {
+    // pair_list: NULL, or the pairs the grid's layers work on (layer z: pair pair_list[z]); eps_pair: 0 one Eps word for the
+    // launch, 1 one word per layer (eps_out[blockIdx.z])
     // ey0, ey1: rows whose changes count for Eps (hsflow_set_eps_rows; the whole frame by default)
     // org: frame row of this context's row 0, modulo 2 (row slabs: the checkerboard of update_cv is the whole frame's)
     // ZERO: the incoming flow is identically zero (first sweep of a solve): nothing is read
@@ -242,7 +245,7 @@ __global__ __launch_bounds__(256) void k_jacobi_simple(const uint32_t *__restric
     const bool active = (x0 < W) && (y < H);
     float e = 0.f;
     if (active) {
-        const long long base = (long long)blockIdx.z * plane;
+        const long long base = (long long)(pair_list ? pair_list[blockIdx.z] : (int)blockIdx.z) * plane;
         const long long rc = base + (long long)y * P + x0;
         const long long ru = base + (long long)clampi(y - 1, 0, H - 1) * P + x0;
         const long long rd = base + (long long)clampi(y + 1, 0, H - 1) * P + x0;
@@ -278,7 +281,7 @@ __global__ __launch_bounds__(256) void k_jacobi_simple(const uint32_t *__restric
     }
     if (EPS) {
         e = wave_max(e);
-        if (threadIdx.x == 0) atomicMax(eps_out, __float_as_uint(e));
+        if (threadIdx.x == 0) atomicMax(eps_out + (eps_pair ? blockIdx.z : 0u), __float_as_uint(e));
     }
 }
 
@@ -297,6 +300,8 @@ struct FusedGeom {
     int tiles_x, tiles_y;
     int zero_in;            // incoming flow is identically zero: do not read u_in / v_in
     int org;                // frame row of this context's row 0, modulo 2 (checkerboard phase of update_cv)
+    const int *pair_list;   // NULL, or the pairs the launch works on: workgroups [k * tiles_x * tiles_y, ...) on pair pair_list[k]
+    int eps_pair;           // 0: one Eps word per sweep; 1: one per sweep and k (eps_out[s * eps_stride + k])
 };
 
 enum : unsigned { F_ACTIVE = 1u, F_CORE = 2u, F_GU = 4u, F_GD = 8u, F_GL = 16u, F_GR = 32u };
@@ -337,11 +342,12 @@ __global__ __launch_bounds__(NT) void k_jacobi_fused(const uint32_t *__restrict_
     const int tid = threadIdx.x;
     const int tpp = g.tiles_x * g.tiles_y;
     const int tile = xcd_contiguous_tile(blockIdx.x, gridDim.x);
-    const int pair = tile / tpp;
-    const int t2 = tile - pair * tpp;
+    const int slot = tile / tpp;
+    const int t2 = tile - slot * tpp;
     const int by = t2 / g.tiles_x, bx = t2 - by * g.tiles_x;
     const int rx0 = bx * g.CW - g.HX, ry0 = by * g.CH - g.T;
-    const long long base = (long long)pair * g.plane;
+    const long long base = (long long)(g.pair_list ? g.pair_list[slot] : slot) * g.plane;
+    const int eps_word = g.eps_pair ? slot : 0;
 
     int o[K];            // LDS float offset of the group's first pixel
     int go[K];           // global element offset (within the pair) of the group's first pixel
@@ -444,7 +450,7 @@ __global__ __launch_bounds__(NT) void k_jacobi_fused(const uint32_t *__restrict_
         }
         if (EPS) {
             e = wave_max(e);
-            if (lane == 0) atomicMax(eps_out + (size_t)s * eps_stride, __float_as_uint(e));
+            if (lane == 0) atomicMax(eps_out + (size_t)s * eps_stride + eps_word, __float_as_uint(e));
         }
         if (s == g.T - 1) break;
         __syncthreads(); // every LDS read of sweep s is done
@@ -504,6 +510,62 @@ __global__ __launch_bounds__(256) void k_eps_reduce(const unsigned *__restrict__
                 seq[0] = s;
                 __hip_atomic_store(host_mark, s, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             }
+        }
+    }
+}
+
+// The block a tile runs in: the inverse of xcd_contiguous_tile (tile t of nb lies in the range of XCD x at place i).
+__device__ __forceinline__ int xcd_block_of_tile(int t, int nb)
+{
+    const int q = nb >> 3, r = nb & 7;
+    const int split = r * (q + 1); // tiles of the XCDs that hold q + 1
+    const int x = t < split ? t / (q + 1) : r + (q ? (t - split) / q : 0);
+    const int i = t < split ? t - x * (q + 1) : t - split - (x - r) * q;
+    return i * 8 + x;
+}
+
+// The same reduction PER PAIR (hsflow_set_pair_termination, hsflow_solve_probe_pairs): out[row * pairs + pair] = maximum
+// over the words of that pair's workgroups.  A strip / fold launch of n workgroups writes word blockIdx.x, and its
+// workgroup blockIdx.x works on tile xcd_contiguous_tile(blockIdx.x, n) of pair tile / (n / pairs): the words of a pair are
+// found through the inverse of that permutation (they lie 8 words apart: 4-byte loads).  One wavefront per (row, pair), four
+// to a workgroup -- or, per_lane, one lane per (row, pair), 256 to a workgroup; one launch per pass.
+// Rows and the marker as in k_eps_reduce.
+__global__ __launch_bounds__(256) void k_eps_reduce_pairs(const unsigned *__restrict__ tiles, int stride,
+                                                          unsigned *__restrict__ out, int n_first, int cnt_first, int cnt_last,
+                                                          int pairs, int pair_blocks, int per_lane, unsigned *__restrict__ seq,
+                                                          unsigned *__restrict__ host_mark)
+{
+    const int slot = blockIdx.x / pair_blocks;
+    const unsigned *row = tiles + (size_t)slot * stride;
+    const int n = slot < n_first ? cnt_first : cnt_last;
+    const int tpp = n / pairs;
+    if (per_lane) { // few tiles per pair (many small frames): a lane per (row, pair) instead of a wavefront with most lanes idle
+        const int pair = (blockIdx.x - slot * pair_blocks) * 256 + threadIdx.x;
+        if (pair < pairs) {
+            unsigned m = 0;
+            for (int t = pair * tpp; t < (pair + 1) * tpp && t < n; t++) m = max(m, row[xcd_block_of_tile(t, n)]);
+            out[(size_t)slot * pairs + pair] = m;
+            __threadfence_system();
+        }
+    }
+    const int pair = (blockIdx.x - slot * pair_blocks) * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (!per_lane && pair < pairs) {
+        unsigned m = 0;
+        for (int t = pair * tpp + lane; t < (pair + 1) * tpp && t < n; t += 64) m = max(m, row[xcd_block_of_tile(t, n)]);
+        const float f = wave_max(__uint_as_float(m));
+        if (lane == 0) {
+            out[(size_t)slot * pairs + pair] = __float_as_uint(f);
+            __threadfence_system();
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && seq) {
+        if (atomicAdd(&seq[1], 1u) == gridDim.x - 1u) {
+            seq[1] = 0u;
+            const unsigned s = seq[0] + 1u;
+            seq[0] = s;
+            __hip_atomic_store(host_mark, s, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }

@@ -70,6 +70,9 @@ struct StripGeom {
     int org;            // frame row of this context's row 0, modulo 2 (row slabs; checkerboard phase of update_cv)
     int ey0, ey1;       // rows [ey0, ey1) of the context whose changes count for Eps and the witness (hsflow_set_eps_rows: a row slab's
                         // owned rows -- its halo rows repeat a neighbour's, stale towards the slab's edge); the strip kernel only
+    const int *pair_list; // NULL: workgroups [k * tiles_x * tiles_y, ...) work on pair k.  Else a device array of pair indices: they work
+                        // on pair pair_list[k] (the per-pair stop's launches over the pairs that are still running).  Read once per
+                        // workgroup, ahead of the load phase (a scalar load; only the pair's plane offset lives on)
 };
 
 // index of the even reflection: ..., 1, 0 | 0, 1, ..., n-1 | n-1, n-2, ...
@@ -379,8 +382,12 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     // directly above and below.)
     const int tpp = g.tiles_x * g.tiles_y;
     const int tile = xcd_contiguous_tile(blockIdx.x, gridDim.x);
-    const int pair = tile / tpp;
-    const int t2 = tile - pair * tpp;
+    const int slot = tile / tpp;
+    const int t2 = tile - slot * tpp;
+    int pair = slot;
+    if constexpr (!PERSIST) { // (the persistent launch always works on every pair: no list, and not a scalar register for one)
+        if (g.pair_list) pair = g.pair_list[slot];
+    }
     const int by = t2 / g.tiles_x, bx = t2 - by * g.tiles_x;
     const int x0 = bx * g.CW - g.HX + 4 * lane;
     const int y0 = by * g.CH - g.T + w * R;
@@ -880,7 +887,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
             if (lane < 8) {
                 const int k = lane < 4 ? lane : lane + 1; // 0..8 without the centre
                 const int nx = bx + k % 3 - 1, ny = by + k / 3 - 1;
-                if (nx >= 0 && nx < g.tiles_x && ny >= 0 && ny < g.tiles_y) nb = pair * tpp + ny * g.tiles_x + nx;
+                if (nx >= 0 && nx < g.tiles_x && ny >= 0 && ny < g.tiles_y) nb = slot * tpp + ny * g.tiles_x + nx;
             } else if (lane == 8) nb = (int)gridDim.x;
             const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
             int dead = 0;
@@ -1051,8 +1058,9 @@ __device__ __forceinline__ void fold_body(const uint32_t *__restrict__ coef,
     float *eps_lds = (float *)(ex + (size_t)2 * NW * 2 * 2 * 32);
     const int tpp = g.tiles_x * g.tiles_y;
     const int tile = xcd_contiguous_tile(blockIdx.x, gridDim.x);
-    const int pair = tile / tpp;
-    const int t2 = tile - pair * tpp;
+    const int slot = tile / tpp;
+    const int t2 = tile - slot * tpp;
+    const int pair = __builtin_amdgcn_readfirstlane(g.pair_list ? g.pair_list[slot] : slot); // (kept scalar: no register of a lane)
     const int by = t2 / g.tiles_x, bx = t2 - by * g.tiles_x;
     const int rx0 = bx * g.CW - g.HX;
     const int x0 = rx0 + 4 * hl;

@@ -68,7 +68,7 @@ bool make_plan(const hsflow_ctx *c, int T, int tw, int th, int nt, FusedPlan &be
                     g.W = W; g.H = H; g.P = c->P; g.plane = c->plane;
                     g.CW = CW; g.CH = CH; g.T = T; g.HX = HX;
                     g.RW4 = RW4; g.RH = RH; g.RS = RS; g.G = (int)G;
-                    g.tiles_x = tx; g.tiles_y = ty; g.zero_in = 0; g.org = c->org;
+                    g.tiles_x = tx; g.tiles_y = ty; g.zero_in = 0; g.org = c->org; g.pair_list = nullptr; g.eps_pair = 0;
                 }
             }
         }
@@ -346,7 +346,7 @@ bool make_strip_plan(const hsflow_ctx *c, int T, int rows, int threads, int fold
                 hsk::StripGeom &g = best.g;
                 g.W = W; g.H = H; g.P = c->P; g.plane = c->plane;
                 g.T = T; g.HX = HX; g.CW = CW; g.CH = CH; g.NW = NW;
-                g.tiles_x = tx; g.tiles_y = ty; g.zero_in = 0; g.org = c->org;
+                g.tiles_x = tx; g.tiles_y = ty; g.zero_in = 0; g.org = c->org; g.pair_list = nullptr;
                 g.ey0 = eps_row0(c); g.ey1 = eps_row1(c);
             }
         }
@@ -614,6 +614,10 @@ hipError_t launch_j(const hsflow_ctx *c, const JPlan &pl, EpsMode eps, const flo
     if (pl.kind == HSFLOW_KERNEL_STRIP || pl.kind == HSFLOW_KERNEL_FOLD) {
         StripPlan sp = pl.s;
         sp.g.zero_in = zero_in;
+        if (c->pairList) { // the pairs of the list only (the per-pair stop): n_active x tiles_per_pair workgroups
+            sp.g.pair_list = c->pairList;
+            sp.tiles = sp.tiles / c->N * c->listCount;
+        }
         switch (eps) {
         case EpsMode::None: return launch_strip_m<EpsMode::None>(c, sp, deriv, ui, vi, uo, vo, coeff);
         case EpsMode::EverySweep: return launch_strip_m<EpsMode::EverySweep>(c, sp, deriv, ui, vi, uo, vo, coeff);
@@ -624,6 +628,11 @@ hipError_t launch_j(const hsflow_ctx *c, const JPlan &pl, EpsMode eps, const flo
     }
     FusedPlan fp = pl.f;
     fp.g.zero_in = zero_in;
+    fp.g.eps_pair = c->epsPair;
+    if (c->pairList) {
+        fp.g.pair_list = c->pairList;
+        fp.tiles = fp.tiles / c->N * c->listCount;
+    }
     return launch_fused(c, fp, eps != EpsMode::None, ui, vi, uo, vo, coeff);
 }
 
@@ -662,15 +671,31 @@ hipError_t for_pair_batches(const hsflow_ctx *c, Launch launch)
 hipError_t launch_simple(const hsflow_ctx *c, bool eps, const float *ui, const float *vi, float *uo,
                          float *vo, float coeff, int zero_in = 0)
 {
-    return for_pair_batches(c, [&](long long o, int n) {
+    // c->epsPair: one Eps word per pair of the launch (at c->epsPtr) instead of one for all; c->pairList: the launch works on
+    // the listed pairs only, layer z on pair pairList[z] -- in batches of max_grid_z layers like the whole context's pairs
+    const int *list = c->pairList;
+    auto go = [&](long long o, int first, int n) {
         const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4, n), block(64, 4);
+        unsigned *ep = c->epsPtr + (c->epsPair ? first : 0);
+        const int *pl = list ? list + first : nullptr;
 #define HS_SIMPLE(E, Z)                                                                            \
         hipLaunchKernelGGL((hsk::k_jacobi_simple<E, Z>), grid, block, 0, c->stream, c->dCoef + o, ui + o, vi + o, uo + o, vo + o, \
-                           c->W, c->H, c->P, c->plane, coeff, c->epsPtr, c->org, eps_row0(c), eps_row1(c))
+                           c->W, c->H, c->P, c->plane, coeff, ep, c->org, eps_row0(c), eps_row1(c), pl, c->epsPair)
         if (eps) { if (zero_in) HS_SIMPLE(true, true); else HS_SIMPLE(true, false); }
         else { if (zero_in) HS_SIMPLE(false, true); else HS_SIMPLE(false, false); }
 #undef HS_SIMPLE
-    });
+    };
+    if (list) {
+        if (c->configuring) return hipSuccess;
+        const int zmax = std::max(1, c->max_grid_z);
+        for (int z0 = 0; z0 < c->listCount; z0 += zmax) {
+            go(0, z0, std::min(zmax, c->listCount - z0));
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    return for_pair_batches(c, [&](long long o, int n) { go(o, (int)(o / c->plane), n); });
 }
 
 hipError_t launch_deriv(const hsflow_ctx *c)

@@ -275,9 +275,11 @@ int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters,
 // Eps bookkeeping of an EPS-terminated solve: `sweeps` rows of `stride` words (one per workgroup) on the device, and
 // the host buffer k_eps_reduce reduces the rows into, hEps[0..sweeps).  eps_reserve allocates only, so that what
 // follows can be captured in a graph; eps_prepare also clears the rows.
-int eps_reserve(hsflow_ctx *c, int sweeps, int stride)
+// host_words: words the reduction writes to the host (a per-pair reduction: sweeps x pairs), 0: one per row.
+int eps_reserve(hsflow_ctx *c, int sweeps, int stride, size_t host_words = 0)
 {
     const size_t need = (size_t)sweeps * stride;
+    if (host_words < (size_t)sweeps) host_words = (size_t)sweeps;
     if (c->epsTilesCap < need) {
         drop_graphs(c); // captured launches hold the old address (this also waits for the stream)
         hipFree(c->dEpsTiles);
@@ -285,12 +287,12 @@ int eps_reserve(hsflow_ctx *c, int sweeps, int stride)
         HS_HIP(c, hipMalloc((void **)&c->dEpsTiles, need * sizeof(unsigned)));
         c->epsTilesCap = need;
     }
-    if (c->hEpsCap < (size_t)sweeps) {
+    if (c->hEpsCap < host_words) {
         drop_graphs(c);
         HS_HIP(c, hipStreamSynchronize(c->stream)); // nothing in flight may still write the old buffer
         if (c->hEps) hipHostFree(c->hEps);
         c->hEps = c->hEpsDev = nullptr; c->hEpsCap = 0;
-        const size_t cap = std::max<size_t>(256, (size_t)sweeps * 2);
+        const size_t cap = std::max<size_t>(256, host_words * 2);
         HS_HIP(c, hipHostMalloc((void **)&c->hEps, cap * sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
         HS_HIP(c, hipHostGetDevicePointer((void **)&c->hEpsDev, c->hEps, 0));
         c->hEpsCap = cap;
@@ -319,6 +321,18 @@ int eps_collect_enqueue(hsflow_ctx *c, const EpsLayout &w, bool mark = false)
     c->epsPtr = c->dEps;
     c->epsStride = 1;
     if (c->configuring) return HSFLOW_OK;
+    if (w.pairs > 0) { // one word per (row, pair): hEps[row * pairs + pair]
+        // (pairs of fewer than 8 workgroups: a lane each; the rows of one pass differ by a short last launch at most)
+        const int per_lane = std::max(w.cnt_first, w.cnt_last) / w.pairs < 8 ? 1 : 0;
+        const int pair_blocks = per_lane ? (w.pairs + 255) / 256 : (w.pairs + 3) / 4;
+        if ((long long)w.slots * pair_blocks > (long long)INT32_MAX)
+            return fail(c, HSFLOW_E_SIZE, "the per-pair Eps reduction of this many launches x pairs exceeds the grid limit");
+        hipLaunchKernelGGL(hsk::k_eps_reduce_pairs, dim3((unsigned)w.slots * (unsigned)pair_blocks), dim3(256), 0, c->stream, c->dEpsTiles,
+                           w.stride, c->hEpsDev, w.n_first, w.cnt_first, w.cnt_last, w.pairs, pair_blocks, per_lane, mark ? c->dSeq : nullptr,
+                           mark ? c->hMarkDev : nullptr);
+        HS_HIP(c, hipGetLastError());
+        return HSFLOW_OK;
+    }
     hipLaunchKernelGGL(hsk::k_eps_reduce, dim3(w.slots), dim3(256), 0, c->stream, c->dEpsTiles, w.stride, c->hEpsDev, w.n_first,
                        w.cnt_first, w.cnt_last, mark ? c->dSeq : nullptr, mark ? c->hMarkDev : nullptr);
     HS_HIP(c, hipGetLastError());
@@ -339,11 +353,12 @@ int eps_collect(hsflow_ctx *c, int sweeps, std::vector<unsigned> &host)
 // cannot have fired before the budget ran out; *last = Eps of the final sweep.
 // last_is_exact: the last slot is the measured Eps of the final sweep (a stop there IS the budget, so it proves
 // nothing and fails nothing); otherwise every slot is a witness word and all of them must clear epsilon.
-bool witness_proven(const unsigned *w, int slots, double epsilon, float *last, bool last_is_exact)
+// step: words between two slots (a per-pair reduction lays them out [slot][pair]: w = the pair's first word, step = pairs).
+bool witness_proven(const unsigned *w, int slots, double epsilon, float *last, bool last_is_exact, int step = 1)
 {
     float e = 0.f;
     for (int i = 0; i < slots; i++) {
-        std::memcpy(&e, &w[i], sizeof(float));
+        std::memcpy(&e, &w[(size_t)i * step], sizeof(float));
         if (!((double)e >= epsilon) && !(last_is_exact && i == slots - 1)) return false;
     }
     *last = e;

@@ -4,6 +4,7 @@
 
 namespace {
 int solve_impl(hsflow_ctx *c, const hsflow_params *pp, bool async);
+int prepare_solve(hsflow_ctx *c, const hsflow_params &p, bool async, SolveSetup &S);
 
 // After the stream has drained: did an asynchronous persistent launch give up?  Its flow is invalid then; the context
 // goes back to a launch per fuse_steps iterations and the caller is told.
@@ -50,6 +51,252 @@ int restore_start(hsflow_ctx *c)
     return HSFLOW_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Per-pair stop (hsflow_set_pair_termination): under EPS termination every pair of a batch stops on its own Eps, as
+// cvCalcOpticalFlowHS called pair by pair does (OpticalFlowOpenCV.cpp:29,94).  The speculative witness pass runs over
+// all pairs exactly as for a batch that stops as one -- same launches, same graph -- and its words are reduced per pair
+// (k_eps_reduce_pairs).  A proven pair stands at the budget.  The pairs that are not proven go through the exact pass
+// TOGETHER (solve_pairs_exact): chunk launches over a device list of the pairs still running, one read-back of their
+// per-pair Eps per chunk, a replay from the chunk's intact input for exactly the missing sweeps of a pair whose stop lies
+// in the chunk, which is then dropped from the list.  A stopped pair's final flow is copied into the other ping-pong
+// buffer too: whichever buffer the context calls current, every pair's final flow lies in it.
+// ------------------------------------------------------------------------------------------------------------------
+enum class PairStart : int { Zero = 0, Saved = 1, Current = 2 }; // zero flow; dUb / dVb (save_start); the flow held now
+
+// hsflow_info of a per-pair solve: iterations_done the maximum over the pairs, last_eps that of the lowest pair that ran
+// that long, eps_rerun 1 if any pair was re-run.
+void pairs_to_info(hsflow_ctx *c)
+{
+    int most = 0, rerun = 0;
+    for (const hsflow_ctx::PairResult &r : c->pair_res) { most = std::max(most, r.iterations_done); rerun |= r.eps_rerun; }
+    for (const hsflow_ctx::PairResult &r : c->pair_res)
+        if (r.iterations_done == most) { c->info.last_eps = r.eps_owed ? NAN : r.last_eps; break; }
+    c->info.iterations_done = most;
+    c->info.eps_rerun = rerun;
+    c->pair_res_valid = true;
+}
+
+// The exact pass for the pairs of `list`, together.  Chunk length: the plan's sweeps per launch (a shorter tail at the end
+// of the budget); the one-sweep kernel runs HSFLOW_PAIR_STOP_SIMPLE_CHUNK launches between read-backs and keeps the
+// chunk's input in dUb / dVb (its ping-pong overwrites it).  Afterwards the stream is idle and hsflow_info is that of the
+// whole solve.  rerun: a witness pass ran before and proved nothing for these pairs.
+int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, const std::vector<int> &list, PairStart start, bool rerun);
+int solve_pairs_exact(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, const std::vector<int> &list, PairStart start, bool rerun)
+{
+    const int st = solve_pairs_exact_body(c, p, S, list, start, rerun);
+    // however it ended: the launches that follow work on every pair again and record no Eps
+    c->pairList = nullptr; c->listCount = 0; c->epsPair = 0; c->epsPtr = c->dEps; c->epsStride = 1;
+    return st;
+}
+
+int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, const std::vector<int> &list, PairStart start, bool rerun)
+{
+    const int N = c->N, kernel = S.kernel;
+    const bool multi = S.multi, strip = kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD;
+    const int T = multi ? S.T : HSFLOW_PAIR_STOP_SIMPLE_CHUNK;
+    const long long budget = S.budget;
+    const size_t bytes = (size_t)c->plane * sizeof(float);
+    constexpr long long kStallSweeps = 4096, kMaxSweeps = 1LL << 24; // (solve_eps_chunks)
+    int st = HSFLOW_OK;
+    if (list.empty()) { pairs_to_info(c); return HSFLOW_OK; }
+    if (!c->dPairs) { // the identity, then room for the list of active pairs and for the lists of a chunk's replays
+        std::vector<int> ident((size_t)N);
+        for (int i = 0; i < N; i++) ident[(size_t)i] = i;
+        HS_HIP(c, hipMalloc((void **)&c->dPairs, 3 * (size_t)N * sizeof(int)));
+        HS_HIP(c, hipMemcpy(c->dPairs, ident.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+    }
+    if (!multi) {
+        const size_t px = (size_t)c->plane * N;
+        if (!c->dUb) HS_HIP(c, hipMalloc((void **)&c->dUb, px * sizeof(float)));
+        if (!c->dVb) HS_HIP(c, hipMalloc((void **)&c->dVb, px * sizeof(float)));
+    }
+    JPlan tail;
+    const int rem = (multi && budget < (1LL << 30)) ? (int)(budget % T) : 0;
+    if (rem && !make_jplan(c, kernel, rem, p, tail)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
+    const int stride = strip ? std::max(S.plan.s.tiles, rem ? tail.s.tiles : 0) : N;
+    if ((st = eps_reserve(c, T, stride, (size_t)T * N))) return st;
+    int cur = c->cur; // the buffer that holds the active pairs' flow
+    bool zero = start == PairStart::Zero;
+    if (start == PairStart::Saved)
+        for (int pair : list) {
+            const long long o = (long long)pair * c->plane;
+            HS_HIP(c, hipMemcpyAsync(c->dU[cur] + o, c->dUb + o, bytes, hipMemcpyDeviceToDevice, c->stream));
+            HS_HIP(c, hipMemcpyAsync(c->dV[cur] + o, c->dVb + o, bytes, hipMemcpyDeviceToDevice, c->stream));
+        }
+    auto both = [&](int pair, int from) -> hipError_t { // a stopped pair's final flow into the other buffer as well
+        const long long o = (long long)pair * c->plane;
+        hipError_t e = hipMemcpyAsync(c->dU[from ^ 1] + o, c->dU[from] + o, bytes, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->dV[from ^ 1] + o, c->dV[from] + o, bytes, hipMemcpyDeviceToDevice, c->stream);
+        return e;
+    };
+    std::vector<int> active = list, next, rlist;
+    std::map<int, std::vector<int>> replays;    // sweeps to replay -> the pairs that stopped there in this chunk
+    std::vector<std::pair<int, int>> stopped;   // (pair, buffer its final flow lies in)
+    std::vector<unsigned> words;
+    std::vector<float> best_eps((size_t)N, INFINITY);
+    std::vector<long long> best_at((size_t)N, 0);
+    long long done = 0;
+    int launches = 0, stalled = -1;
+    for (int pair : list) c->pair_res[(size_t)pair].eps_rerun = rerun ? 1 : 0;
+    while (!active.empty()) {
+        const int n_act = (int)active.size();
+        const int chunk = (int)std::min<long long>(T, budget - done);
+        HS_HIP(c, hipMemcpyAsync(c->dPairs + N, active.data(), (size_t)n_act * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        c->pairList = c->dPairs + N;
+        c->listCount = n_act;
+        const int a0 = cur;
+        const JPlan &cp = chunk == T ? S.plan : tail;
+        if (multi) {
+            c->epsPtr = c->dEpsTiles;
+            if (strip) c->epsStride = stride; // (every launch writes all its words)
+            else {
+                if ((st = eps_clear(c, chunk, n_act))) return st;
+                c->epsStride = n_act;
+                c->epsPair = 1;
+            }
+            const hipError_t e = launch_j(c, cp, EpsMode::EverySweep, c->dU[cur], c->dV[cur], c->dU[cur ^ 1], c->dV[cur ^ 1], S.coeff, zero ? 1 : 0);
+            HS_HIP(c, e);
+            cur ^= 1;
+            launches++;
+        } else {
+            if (!zero)
+                for (int pair : active) { // the chunk's input, for a replay
+                    const long long o = (long long)pair * c->plane;
+                    HS_HIP(c, hipMemcpyAsync(c->dUb + o, c->dU[cur] + o, bytes, hipMemcpyDeviceToDevice, c->stream));
+                    HS_HIP(c, hipMemcpyAsync(c->dVb + o, c->dV[cur] + o, bytes, hipMemcpyDeviceToDevice, c->stream));
+                }
+            if ((st = eps_clear(c, chunk, n_act))) return st;
+            c->epsPair = 1;
+            for (int s = 0; s < chunk; s++) {
+                c->epsPtr = c->dEpsTiles + (size_t)s * n_act;
+                const hipError_t e = launch_simple(c, true, c->dU[cur], c->dV[cur], c->dU[cur ^ 1], c->dV[cur ^ 1], S.coeff, (zero && s == 0) ? 1 : 0);
+                HS_HIP(c, e);
+                cur ^= 1;
+                launches++;
+            }
+        }
+        c->sweeps_run += chunk;
+        // one read-back for all active pairs: words[s * n_act + k]
+        words.resize((size_t)chunk * n_act);
+        if (strip) {
+            const int tiles = cp.s.tiles / N * n_act;
+            st = eps_collect_enqueue(c, EpsLayout{chunk, stride, 0, 0, tiles, n_act});
+            if (st) return st;
+            HS_HIP(c, hipStreamSynchronize(c->stream));
+            std::memcpy(words.data(), c->hEps, words.size() * sizeof(unsigned));
+        } else {
+            HS_HIP(c, hipMemcpyAsync(words.data(), c->dEpsTiles, words.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+            HS_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        c->epsPair = 0;
+        c->epsPtr = c->dEps;
+        c->epsStride = 1;
+        next.clear();
+        replays.clear();
+        stopped.clear();
+        for (int k = 0; k < n_act; k++) {
+            const int pair = active[(size_t)k];
+            hsflow_ctx::PairResult &r = c->pair_res[(size_t)pair];
+            r.sweeps += chunk;
+            int hit = -1;
+            float e = 0.f;
+            for (int s = 0; s < chunk && hit < 0; s++) {
+                std::memcpy(&e, &words[(size_t)s * n_act + k], sizeof(float));
+                if ((double)e < p.epsilon) hit = s;
+                else if (e < best_eps[(size_t)pair]) { best_eps[(size_t)pair] = e; best_at[(size_t)pair] = done + s; }
+            }
+            r.last_eps = e;
+            r.eps_owed = false;
+            bool stop = hit >= 0;
+            const int k1 = (hit >= 0 && hit < chunk - 1) ? hit + 1 : 0; // the stop lies inside the chunk: a replay of hit + 1 sweeps
+            if (k1) {
+                replays[k1].push_back(pair);
+                r.sweeps += k1;
+            }
+            const long long ran = hit >= 0 ? done + hit + 1 : done + chunk;
+            if (!stop && S.use_iter && p.max_iter > 0 && ran >= budget) stop = true;
+            if (!stop && budget > kMaxSweeps && (ran - best_at[(size_t)pair] >= kStallSweeps || ran >= kMaxSweeps)) { // (the stall rule)
+                stop = true;
+                r.status = HSFLOW_E_NOTERM;
+                if (stalled < 0) stalled = pair;
+            }
+            r.iterations_done = (int)std::min<long long>(ran, INT32_MAX);
+            if (stop) {
+                r.in_both = true;
+                // where the pair's final flow lies: behind the chunk, or behind its replay from the chunk's input
+                stopped.push_back({pair, !k1 ? cur : multi ? (a0 ^ 1) : (a0 ^ (k1 & 1))});
+            } else next.push_back(pair);
+        }
+        // the replays: exactly hit + 1 sweeps from the chunk's intact input, ONE launch sequence for all pairs that share the count
+        rlist.clear();
+        for (const auto &g : replays) rlist.insert(rlist.end(), g.second.begin(), g.second.end());
+        if (!rlist.empty())
+            HS_HIP(c, hipMemcpyAsync(c->dPairs + 2 * (size_t)N, rlist.data(), rlist.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        size_t at = 0;
+        for (const auto &g : replays) {
+            const int k1 = g.first, n = (int)g.second.size();
+            c->pairList = c->dPairs + 2 * (size_t)N + at;
+            c->listCount = n;
+            at += (size_t)n;
+            if (multi) {
+                JPlan rp;
+                if (!make_jplan(c, kernel, k1, p, rp)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the replay");
+                const hipError_t er = launch_j(c, rp, EpsMode::None, c->dU[a0], c->dV[a0], c->dU[a0 ^ 1], c->dV[a0 ^ 1], S.coeff, zero ? 1 : 0);
+                HS_HIP(c, er);
+                launches++;
+            } else {
+                if (!zero)
+                    for (int pair : g.second) {
+                        const long long o = (long long)pair * c->plane;
+                        HS_HIP(c, hipMemcpyAsync(c->dU[a0] + o, c->dUb + o, bytes, hipMemcpyDeviceToDevice, c->stream));
+                        HS_HIP(c, hipMemcpyAsync(c->dV[a0] + o, c->dVb + o, bytes, hipMemcpyDeviceToDevice, c->stream));
+                    }
+                int from = a0;
+                for (int s = 0; s < k1; s++) {
+                    const hipError_t er = launch_simple(c, false, c->dU[from], c->dV[from], c->dU[from ^ 1], c->dV[from ^ 1], S.coeff, (zero && s == 0) ? 1 : 0);
+                    HS_HIP(c, er);
+                    from ^= 1;
+                    launches++;
+                }
+            }
+            c->sweeps_run += k1;
+        }
+        for (const auto &sp : stopped) HS_HIP(c, both(sp.first, sp.second));
+        c->pairList = nullptr;
+        active.swap(next); // (the list uploaded this round is not written again before the next round's read-back)
+        done += chunk;
+        zero = false;
+    }
+    c->info.jacobi_launches += launches;
+    pairs_to_info(c);
+    if (stalled >= 0)
+        return fail(c, HSFLOW_E_NOTERM, "EPS termination: Eps of pair " + std::to_string(stalled) + " stopped decreasing above epsilon (fp32 limit "
+                                        "cycle) -- its flow of the sweeps done so far is kept; every other pair has stopped "
+                                        "(hsflow_get_pair_result)");
+    return HSFLOW_OK;
+}
+
+// Does this solve stop pair by pair?  (Not the per-sweep pass of hsflow_solve_probe*, nor a one-pair context.)
+bool stops_per_pair(const hsflow_ctx *c) { return c->per_pair && c->N > 1 && !c->force_exact; }
+
+// Per-pair verdicts over the witness words of a pass that was reduced per pair (hEps[slot * N + pair]): fills pair_res
+// for the proven pairs (standing at the budget) and lists the others.  last_is_exact: as witness_proven.
+void pair_verdicts(hsflow_ctx *c, const EpsLayout &words, double epsilon, int iters, bool last_is_exact, std::vector<int> &unproven)
+{
+    c->pair_res.assign((size_t)c->N, hsflow_ctx::PairResult());
+    unproven.clear();
+    for (int i = 0; i < c->N; i++) {
+        hsflow_ctx::PairResult &r = c->pair_res[(size_t)i];
+        float last = 0.f;
+        const bool proven = witness_proven(c->hEps + i, words.slots, epsilon, &last, last_is_exact, c->N);
+        r.iterations_done = iters;
+        r.sweeps = iters;
+        r.last_eps = last_is_exact ? last : NAN;
+        r.eps_owed = !last_is_exact; // (measure_last_eps; a pair that takes the exact pass measures its own)
+        if (!proven) unproven.push_back(i);
+    }
+}
+
 // Settles an ITER|EPS solve that hsflow_solve_async left unverified: waits for the stream, looks at the
 // witness words and, if they do not prove "no early stop", runs the exact pass from the saved start.
 // verdict_only: report whether the witness words prove "no early stop" and leave it at that (no exact pass; the flow of
@@ -71,6 +318,18 @@ int settle_pending(hsflow_ctx *c, int *verdict_only = nullptr)
         // since (the slots of a pair pipeline share streams: pair_pipeline.cpp)
         int stw = wait_marker(c, c->pend.mark);
         if (stw) return stw;
+    }
+    if (c->pend.words.pairs > 0) { // every pair on its own verdict (hsflow_set_pair_termination)
+        std::vector<int> unproven;
+        pair_verdicts(c, c->pend.words, c->pend.params.epsilon, c->pend.iters, false, unproven);
+        pairs_to_info(c);
+        if (verdict_only) *verdict_only = unproven.empty() ? 1 : 0;
+        if (verdict_only || unproven.empty()) return HSFLOW_OK; // (last_eps of the proven pairs: measure_last_eps)
+        SolveSetup S; // (the plan of that solve once more: the chunk launches are its kernel's)
+        hsflow_params q = c->pend.params;
+        const int st = prepare_solve(c, q, false, S);
+        if (st) return st;
+        return solve_pairs_exact(c, q, S, unproven, q.use_previous ? PairStart::Saved : PairStart::Zero, true);
     }
     float last = 0.f;
     const bool gave_up = persist_gave_up(c); // a persistent launch that timed out proves nothing
@@ -95,11 +354,13 @@ int settle_pending(hsflow_ctx *c, int *verdict_only = nullptr)
         int str = restore_start(c);
         if (str) return str;
     }
+    const long long sweeps = c->sweeps_run; // (those of the witness pass)
     c->force_exact = true;
     const int st = solve_impl(c, &q, false);
     c->force_exact = false;
     c->info.eps_rerun = 1;
     c->info.jacobi_launches += c->pend.launches;
+    c->sweeps_run += sweeps;
     return st;
 }
 
@@ -111,8 +372,13 @@ int measure_last_eps(hsflow_ctx *c)
     if (!c->lastl.valid) return HSFLOW_OK;
     c->lastl.valid = false;
     const hsflow_ctx::LastLaunch &L = c->lastl;
+    if (c->pair_res_valid) { // (a per-pair solve whose pairs were all re-run owes nothing)
+        bool owed = false;
+        for (const hsflow_ctx::PairResult &r : c->pair_res) owed = owed || r.eps_owed;
+        if (!owed) return HSFLOW_OK;
+    }
     const int stride = L.plan.s.tiles;
-    int st = eps_reserve(c, 2, stride);
+    int st = eps_reserve(c, 2, stride, c->pair_res_valid ? 2 * (size_t)c->N : 0);
     if (st) return st;
     const int b = c->cur, a = b ^ 1;
     c->epsPtr = c->dEpsTiles;
@@ -121,6 +387,26 @@ int measure_last_eps(hsflow_ctx *c)
     const float *ui = L.from_third ? c->dUp : c->dU[a], *vi = L.from_third ? c->dVp : c->dV[a];
     const hipError_t e = launch_j(c, L.plan, EpsMode::WitnessLast, ui, vi, c->dU[b], c->dV[b], L.coeff, L.zero_in);
     HS_HIP(c, e);
+    if (c->pair_res_valid) { // a per-pair solve: the proven pairs' last sweep, each over its own workgroups
+        if ((st = eps_collect_enqueue(c, EpsLayout{2, stride, 0, 0, stride, c->N}))) return st;
+        // the launch also ran over the pairs that stopped early: their final flow comes back from the other buffer
+        const size_t bytes = (size_t)c->plane * sizeof(float);
+        for (int i = 0; i < c->N; i++) {
+            if (!c->pair_res[(size_t)i].in_both) continue;
+            const long long o = (long long)i * c->plane;
+            HS_HIP(c, hipMemcpyAsync(c->dU[b] + o, c->dU[a] + o, bytes, hipMemcpyDeviceToDevice, c->stream));
+            HS_HIP(c, hipMemcpyAsync(c->dV[b] + o, c->dV[a] + o, bytes, hipMemcpyDeviceToDevice, c->stream));
+        }
+        HS_HIP(c, hipStreamSynchronize(c->stream));
+        for (int i = 0; i < c->N; i++) {
+            hsflow_ctx::PairResult &r = c->pair_res[(size_t)i];
+            if (!r.eps_owed) continue;
+            std::memcpy(&r.last_eps, &c->hEps[(size_t)c->N + i], sizeof(float));
+            r.eps_owed = false;
+        }
+        pairs_to_info(c);
+        return HSFLOW_OK;
+    }
     if ((st = eps_collect_enqueue(c, EpsLayout{2, stride, 0, 0, stride}))) return st; // (resets epsPtr / epsStride)
     HS_HIP(c, hipStreamSynchronize(c->stream));
     float last = 0.f;
@@ -321,6 +607,7 @@ int solve_classic(hsflow_ctx *c, const hsflow_params &p, bool async)
     c->coef_mode = HSFLOW_MODE_CLASSIC;
     c->dE_valid = do_unpack || (c->dE_valid && !do_deriv);
     i.jacobi_launches = launches;
+    c->sweeps_run += p.max_iter;
     i.iterations_done = p.max_iter; i.last_eps = 0.f; i.deriv_ms = i.jacobi_ms = i.solve_ms = 0.f;
     if (!async) {
         HS_HIP(c, hipStreamSynchronize(c->stream));
@@ -380,6 +667,7 @@ int solve_fixed(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Prof
     c->coef_valid = true;
     c->coef_mode = HSFLOW_MODE_CV;
     c->info.iterations_done = iters;
+    c->sweeps_run += iters;
     if (S.persist && async) c->persist_unchecked = true; // looked at when the stream is next drained (check_persist)
     if (!async) {
         HS_HIP(c, hipStreamSynchronize(c->stream));
@@ -427,8 +715,9 @@ float witness_threshold(double epsilon)
 // tailp: the plan of a short last launch; stride: words per row; *launches: Jacobi launches enqueued.
 // *rerun: nothing is proven (a flat or converged input) -- the starting flow is back in place for the exact pass.
 int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, const JPlan &tailp, int stride, bool do_deriv,
-                 Profiler &prof, bool async, int *launches, bool *rerun)
+                 Profiler &prof, bool async, int *launches, bool *rerun, std::vector<int> *unproven = nullptr)
 {
+    const bool per_pair = stops_per_pair(c); // the words are reduced per pair, and each pair gets its own verdict
     const int iters = (int)S.budget, T = S.T, cur0 = c->cur;
     const JPlan &plan = S.plan;
     int st = HSFLOW_OK;
@@ -441,8 +730,8 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
     const EpsMode last_mode = async ? EpsMode::Witness : EpsMode::WitnessLast;
     // (persist: the tail phase keeps the plan's geometry)
     const EpsLayout words{n_launch - 1 + (async ? 1 : 2), stride, n_launch - 1, plan_eps_stride(S.kernel, plan),
-                          plan_eps_stride(S.kernel, persist ? plan : lastp)};
-    if ((st = eps_reserve(c, words.slots, stride))) return st;
+                          plan_eps_stride(S.kernel, persist ? plan : lastp), per_pair ? c->N : 0};
+    if ((st = eps_reserve(c, words.slots, stride, per_pair ? (size_t)words.slots * c->N : 0))) return st;
     // the first launch also does the derivative pass where the kernel can (hs_plan_launch.hip.h)
     const bool fuse_deriv = do_deriv && !p.profile && strip_deriv_fusable(c, firstp);
     c->info.deriv_fused = fuse_deriv;
@@ -495,7 +784,8 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
     if (p.use_graph && !p.profile && !(in_place && n_launch == 1)) {
         GraphKey key{p.mode, persist ? HSFLOW_KERNEL_PERSIST : S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
                      c->info.groups_per_thread, p.use_previous ? c->cur : 0,
-                     p.use_previous * 2 + (do_deriv ? 1 : 0) + (async ? 4 : 0) + (async && c->async_reduce ? 8 : 0) + (in_place ? 16 : 0),
+                     p.use_previous * 2 + (do_deriv ? 1 : 0) + (async ? 4 : 0) + (async && c->async_reduce ? 8 : 0) + (in_place ? 16 : 0) +
+                         (per_pair ? 32 : 0),
                      S.coeff, c->epsThr};
         if (in_place) {
             part = 1;
@@ -518,6 +808,7 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
     if (persist) c->persist_unchecked = true;
     c->info.iterations_done = iters;
     c->info.jacobi_launches = *launches;
+    c->sweeps_run += iters;
     if (async) { // the check is owed: hsflow_synchronize (or the next call that needs results) settles it
         // what measure_last_eps needs: the last launch again (persist: the last phase as an ordinary launch, from the third buffer)
         const int zero_in = (n_launch == 1 && !p.use_previous && !persist) ? 1 : 0; // a single launch from zero flow
@@ -531,6 +822,13 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
         return HSFLOW_OK;
     }
     HS_HIP(c, hipStreamSynchronize(c->stream));
+    if (per_pair) { // the proven pairs stand at the budget, where this pass left them; the others take the exact pass (caller)
+        pair_verdicts(c, words, p.epsilon, iters, true, *unproven);
+        pairs_to_info(c);
+        *rerun = !unproven->empty();
+        if (!*rerun) prof.collect();
+        return HSFLOW_OK;
+    }
     float last = 0.f;
     if (witness_proven(c->hEps, words.slots, p.epsilon, &last, true)) {
         c->info.last_eps = last;
@@ -552,28 +850,50 @@ int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int s
 {
     const int iters = (int)S.budget, T = S.T;
     int st = HSFLOW_OK, zero_in = p.use_previous ? 0 : 1, done = 0;
+    int tail_tiles = S.multi ? plan_eps_stride(S.kernel, S.plan) : 1; // words of a row of the short last launch
+    if (c->probe_pairs && c->N > 1 && (st = eps_reserve(c, iters, stride, (size_t)iters * c->N))) return st;
+    const bool strip_words = S.kernel == HSFLOW_KERNEL_STRIP || S.kernel == HSFLOW_KERNEL_FOLD;
+    const bool pair_words = c->probe_pairs && c->N > 1 && !strip_words; // (stride = N: solve_iter_eps)
+    c->epsPair = pair_words ? 1 : 0;
     if (zero_in) c->cur = 0;
     while (done < iters) {
         const int chunk = S.multi ? std::min(T, iters - done) : 1;
         JPlan cp = S.plan;
         if (S.multi && chunk != T && !make_jplan(c, S.kernel, chunk, p, cp))
             return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
+        if (S.multi && chunk != T) tail_tiles = plan_eps_stride(S.kernel, cp);
         const int a = c->cur, b = a ^ 1;
         c->epsPtr = c->dEpsTiles + (size_t)done * stride;
+        if (pair_words) c->epsStride = stride;
         prof.begin(1);
         hipError_t e = S.multi ? launch_j(c, cp, EpsMode::EverySweep, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff, zero_in)
                                : launch_simple(c, true, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff, zero_in);
         prof.end();
+        if (e != hipSuccess) c->epsPair = 0;
         HS_HIP(c, e);
         c->cur = b;
         zero_in = 0;
         done += chunk;
         launches++;
     }
+    c->epsPair = 0;
+    c->sweeps_run += iters;
     std::vector<unsigned> heps;
     if ((st = eps_collect(c, iters, heps))) return st;
     c->sweep_eps.resize((size_t)iters); // (hsflow_solve_probe hands these out)
     std::memcpy(c->sweep_eps.data(), heps.data(), (size_t)iters * sizeof(float));
+    if (pair_words) { // the rows ARE per pair (the batch's Eps above is their maximum, by k_eps_reduce over N words a row)
+        c->sweep_eps_pairs.resize((size_t)iters * c->N);
+        HS_HIP(c, hipMemcpy(c->sweep_eps_pairs.data(), c->dEpsTiles, (size_t)iters * c->N * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    if (c->probe_pairs && c->N > 1 && strip_words) {
+        // hsflow_solve_probe_pairs: the same rows once more, per pair (the rows of a short last launch hold fewer words)
+        const EpsLayout pw{iters, stride, iters / T * T, plan_eps_stride(S.kernel, S.plan), tail_tiles, c->N};
+        if ((st = eps_collect_enqueue(c, pw))) return st;
+        HS_HIP(c, hipStreamSynchronize(c->stream));
+        c->sweep_eps_pairs.resize((size_t)iters * c->N);
+        std::memcpy(c->sweep_eps_pairs.data(), c->hEps, (size_t)iters * c->N * sizeof(float));
+    }
     float last = 0.f;
     const int hit = first_eps_hit(heps.data(), iters, p.epsilon, &last);
     if (hit >= 0 && hit + 1 < iters) { // converged early: redo exactly hit+1 sweeps from the start
@@ -589,6 +909,7 @@ int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int s
         st = enqueue_fixed(c, p, S.coeff, k, S.kernel, Tk, &kp, &kt, prof, false, !p.use_previous);
         if (st) return st;
         launches += c->info.jacobi_launches;
+        c->sweeps_run += k;
         HS_HIP(c, hipStreamSynchronize(c->stream));
         c->info.iterations_done = k;
     } else {
@@ -598,6 +919,22 @@ int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int s
     c->info.jacobi_launches = launches;
     prof.collect();
     return HSFLOW_OK;
+}
+
+// Per-pair stop without a witness pass (the simple and the LDS-tile kernel, EPS alone): the derivative pass for all pairs,
+// then every pair through the exact pass from the flow it starts with.
+int solve_pairs_all(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, bool do_deriv)
+{
+    int st = resolve_lazy_frames(c, false);
+    if (st) return st;
+    if (do_deriv) HS_HIP(c, launch_deriv(c));
+    c->coef_valid = true;
+    c->coef_mode = HSFLOW_MODE_CV;
+    c->pair_res.assign((size_t)c->N, hsflow_ctx::PairResult());
+    c->info.jacobi_launches = 0;
+    std::vector<int> all((size_t)c->N);
+    for (int i = 0; i < c->N; i++) all[(size_t)i] = i;
+    return solve_pairs_exact(c, p, S, all, p.use_previous ? PairStart::Current : PairStart::Zero, false);
 }
 
 // ITER|EPS -- the way the reference calls the solver (OpticalFlowOpenCV.cpp:29).  On real image pairs Eps never drops
@@ -617,6 +954,9 @@ int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, P
     }
     // every launch of this solve uses the same number of workgroups or fewer (tail): stride = max
     int stride = S.multi ? plan_eps_stride(kernel, S.plan) : 1;
+    // hsflow_solve_probe_pairs on the simple / LDS-tile kernel: one word per (sweep, pair) instead of one per sweep
+    const bool pair_words = c->probe_pairs && c->N > 1 && kernel != HSFLOW_KERNEL_STRIP && kernel != HSFLOW_KERNEL_FOLD;
+    if (pair_words) stride = c->N;
     JPlan tailp;
     if (S.multi && iters % T) {
         if (!make_jplan(c, kernel, iters % T, p, tailp)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
@@ -632,6 +972,17 @@ int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, P
         return fail(c, HSFLOW_E_ARG, "solve_async with ITER|EPS: this launch plan (core tile thinner than a strip) cannot run witness launches; "
                                      "use hsflow_solve or other tuning parameters");
     int launches = 0;
+    if (stops_per_pair(c)) { // every pair on its own Eps: the pairs the witness pass could not vouch for, or all of them
+        std::vector<int> list;
+        if (witness) {
+            bool rerun = false;
+            if ((st = witness_pass(c, p, S, tailp, stride, do_deriv, prof, async, &launches, &rerun, &list)) || !rerun) return st;
+            st = solve_pairs_exact(c, p, S, list, p.use_previous ? PairStart::Saved : PairStart::Zero, true);
+            prof.collect(); // (profile = 1: the times of the witness pass; the chunk launches behind it are not bracketed)
+            return st;
+        }
+        return solve_pairs_all(c, p, S, do_deriv);
+    }
     if (witness) {
         bool rerun = false;
         if ((st = witness_pass(c, p, S, tailp, stride, do_deriv, prof, async, &launches, &rerun)) || !rerun) return st;
@@ -702,6 +1053,7 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
             HS_HIP(c, launch_j(c, cp, EpsMode::EverySweep, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
         prof.end();
         launches++;
+        c->sweeps_run += n;
         std::vector<unsigned> heps;
         if ((st = eps_collect(c, n, heps))) return st;
         const int hit = first_eps_hit(heps.data(), n, p.epsilon, &last);
@@ -718,6 +1070,7 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
             HS_HIP(c, launch_j(c, rp, EpsMode::None, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
             prof.end();
             launches++;
+            c->sweeps_run += hit + 1;
             done += hit + 1;
             stop = true;
         } else {
@@ -887,6 +1240,8 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
     if (repeat) { c->pend.active = false; *took_over = true; }
     else if ((st = settle_pending(c))) return st;
     c->lastl.valid = false;
+    c->pair_res_valid = false;
+    c->sweeps_run = 0;
     if (!pp || pp->struct_size != sizeof(hsflow_params))
         return fail(c, HSFLOW_E_ARG, "params null or struct_size mismatch");
     const hsflow_params &p = *pp;
@@ -896,6 +1251,10 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
         return solve_classic(c, p, async);
     }
     if (p.mode != HSFLOW_MODE_CV) return fail(c, HSFLOW_E_ARG, "unknown mode");
+    if (stops_per_pair(c) && (p.term_type & HSFLOW_TERM_EPS) && p.kernel == HSFLOW_KERNEL_PERSIST)
+        return fail(c, HSFLOW_E_ARG, "HSFLOW_KERNEL_PERSIST with hsflow_set_pair_termination on a batch under EPS termination: the persistent "
+                                     "launch holds every pair of the batch until its last phase, so no pair can stop on its own; "
+                                     "use HSFLOW_KERNEL_STRIP, or switch the per-pair stop off");
     c->info.eps_rerun = 0;
     c->info.deriv_fused = 0;
     // The plan of a solve depends on the parameters, not on the frames: a stream of solves with the same parameters plans
@@ -928,12 +1287,18 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
             c->plan_cache.push_back(PlanEntry{key, S, c->info});
         }
     }
+    if (stops_per_pair(c) && S.use_eps && S.persist) { // (HSFLOW_PERSIST_AUTO: AUTO may not take the one launch here either)
+        S.persist = false;
+        c->info.persistent = 0;
+    }
     c->info.deriv_ms = c->info.jacobi_ms = c->info.solve_ms = 0.f;
     c->info.last_eps = 0.f;
     Profiler prof{c, p.profile != 0};
     if (!S.use_eps) return solve_fixed(c, S.eff, S, prof, async);
     constexpr long long kSpecMax = 1 << 16; // speculative ITER|EPS: the whole budget in one go
     if (S.use_iter && p.max_iter > 0 && S.budget <= kSpecMax) return solve_iter_eps(c, S.eff, S, prof, async);
+    if (stops_per_pair(c)) // (no budget to speculate on: every pair through its own chunk loop, stall rule included)
+        return solve_pairs_all(c, S.eff, S, !(p.reuse_derivatives && c->coef_valid && c->coef_mode == HSFLOW_MODE_CV));
     if ((st = resolve_lazy_frames(c, false))) return st;
     return solve_eps_chunks(c, S.eff, S, prof);
 }

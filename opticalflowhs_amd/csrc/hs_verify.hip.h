@@ -218,6 +218,7 @@ int hsflow_verify(hsflow_ctx *c, int pair, hsflow_verify_report *report)
     q.fuse_steps = q.tile_w = q.tile_h = q.threads = q.strip_rows = 0;
     q.use_previous = q.reuse_derivatives = q.use_graph = q.profile = 0;
     s->coef_valid = false;
+    s->per_pair = c->v_per_pair; // every pair's own stopping sweep, from the one-sweep kernel's Eps of that pair alone
     if ((st = solve_impl(s, &q, false))) return fail(c, st, "hsflow_verify: the reference pass failed: " + s->err);
     const int first = pair < 0 ? 0 : pair, count = pair < 0 ? c->N : 1;
     if ((st = cmp_reserve(c, 3 * count)) || (st = cmp_clear(c, 3 * count))) return st;
@@ -233,8 +234,24 @@ int hsflow_verify(hsflow_ctx *c, int pair, hsflow_verify_report *report)
     std::memset(&r, 0, sizeof(r));
     r.struct_size = sizeof(r);
     r.pair = pair;
-    r.iterations_done = c->info.iterations_done;
-    r.iterations_ref = s->info.iterations_done;
+    // sweeps per pair where the pairs stop each on its own, else the batch's for every pair
+    auto done = [](const hsflow_ctx *x, int i) { return x->pair_res_valid ? x->pair_res[(size_t)i].iterations_done : x->info.iterations_done; };
+    bool counts_agree = true;
+    if (pair >= 0) {
+        r.iterations_done = done(c, pair);
+        r.iterations_ref = done(s, pair);
+    } else { // the counts of the lowest pair where they differ, else the maxima
+        for (int i = 0; i < c->N; i++) {
+            r.iterations_done = std::max(r.iterations_done, done(c, i));
+            r.iterations_ref = std::max(r.iterations_ref, done(s, i));
+        }
+        for (int i = 0; i < c->N && counts_agree; i++)
+            if (done(c, i) != done(s, i)) {
+                counts_agree = false;
+                r.iterations_done = done(c, i);
+                r.iterations_ref = done(s, i);
+            }
+    }
     r.u.first_failing = r.v.first_failing = r.deriv_first = -1;
     for (int k = 0; k < count; k++) {
         const hsflow_plane_diff du = cmp_record(c, 3 * k), dv = cmp_record(c, 3 * k + 1), dd = cmp_record(c, 3 * k + 2);
@@ -244,7 +261,7 @@ int hsflow_verify(hsflow_ctx *c, int pair, hsflow_verify_report *report)
         if (r.deriv_first < 0) r.deriv_first = dd.first_failing;
         if (pair < 0 && r.pair < 0 && (du.failing || dv.failing || dd.differing)) r.pair = first + k;
     }
-    r.ok = r.u.failing == 0 && r.v.failing == 0 && r.deriv_differing == 0 && r.iterations_ref == r.iterations_done;
+    r.ok = r.u.failing == 0 && r.v.failing == 0 && r.deriv_differing == 0 && r.iterations_ref == r.iterations_done && counts_agree;
     *report = r;
     return HSFLOW_OK;
 }

@@ -224,6 +224,7 @@ int hsflow_destroy(hsflow_ctx *c)
     for (int i = 0; i < 3; i++) hipFree(c->dE[i]);
     for (int i = 0; i < 2; i++) { hipFree(c->dU[i]); hipFree(c->dV[i]); }
     hipFree(c->dEps);
+    hipFree(c->dPairs);
     hipFree(c->dEpsTiles); hipFree(c->dUb); hipFree(c->dVb);
     hipFree(c->dUp); hipFree(c->dVp); hipFree(c->dFlags);
     hipFree(c->dSeq);
@@ -437,14 +438,17 @@ static int note_solve(hsflow_ctx *c, const hsflow_params *p, int st)
 {
     if (!c) return st;
     c->vstate = st ? 2 : 1;
+    c->last_status = st;
     if (!st) {
         c->vparams = *p;
         c->v_org = c->org; c->v_eps_row0 = c->eps_row0; c->v_eps_rows = c->eps_rows;
+        c->v_per_pair = c->per_pair;
     }
     return st;
 }
 
-int hsflow_solve_probe(hsflow_ctx *c, const hsflow_params *pp, float *sweep_eps)
+// hsflow_solve_probe and hsflow_solve_probe_pairs (pairs: c->sweep_eps_pairs is filled too)
+static int probe_impl(hsflow_ctx *c, const hsflow_params *pp, const float *sweep_eps, bool pairs)
 {
     int st = check_ctx(c, 0);
     if (st) return st;
@@ -452,14 +456,20 @@ int hsflow_solve_probe(hsflow_ctx *c, const hsflow_params *pp, float *sweep_eps)
     if (!sweep_eps) return fail(c, HSFLOW_E_ARG, "sweep_eps is null");
     if (pp->mode != HSFLOW_MODE_CV) return fail(c, HSFLOW_E_ARG, "hsflow_solve_probe: CV mode only");
     if (pp->max_iter <= 0 || pp->max_iter > (1 << 16)) return fail(c, HSFLOW_E_ARG, "hsflow_solve_probe: max_iter must be 1 .. 65536");
+    if (pairs && (long long)pp->max_iter * c->N > (1LL << 28))
+        return fail(c, HSFLOW_E_SIZE, "hsflow_solve_probe_pairs: max_iter x n_pairs must not exceed 2^28");
     hsflow_params q = *pp;
     q.term_type = HSFLOW_TERM_ITER | HSFLOW_TERM_EPS;
     q.epsilon = 0.0;  // Eps < 0 never holds: every sweep of the budget runs
     q.profile = 0;
     if (q.kernel == HSFLOW_KERNEL_PERSIST) q.kernel = HSFLOW_KERNEL_STRIP;
     c->force_exact = true; // the per-sweep pass, not the witness pass
+    c->probe_pairs = pairs;
+    c->sweep_eps.clear();
+    c->sweep_eps_pairs.clear();
     st = solve_impl(c, &q, false);
     c->force_exact = false;
+    c->probe_pairs = false;
     {   // to hsflow_verify a probe is an ITER solve of max_iter sweeps
         hsflow_params v = *pp;
         v.term_type = HSFLOW_TERM_ITER;
@@ -467,7 +477,61 @@ int hsflow_solve_probe(hsflow_ctx *c, const hsflow_params *pp, float *sweep_eps)
     }
     if (st) return st;
     if ((int)c->sweep_eps.size() != pp->max_iter) return fail(c, HSFLOW_E_STATE, "hsflow_solve_probe: the per-sweep pass did not run");
-    std::memcpy(sweep_eps, c->sweep_eps.data(), (size_t)pp->max_iter * sizeof(float));
+    if (!pairs) return HSFLOW_OK;
+    const size_t n = (size_t)pp->max_iter, N = (size_t)c->N;
+    if (c->N == 1) c->sweep_eps_pairs = c->sweep_eps;
+    else if (c->sweep_eps_pairs.size() != n * N) return fail(c, HSFLOW_E_STATE, "hsflow_solve_probe_pairs: the per-pair words were not collected");
+    return HSFLOW_OK;
+}
+
+int hsflow_solve_probe(hsflow_ctx *c, const hsflow_params *pp, float *sweep_eps)
+{
+    const int st = probe_impl(c, pp, sweep_eps, false);
+    if (st) return st;
+    std::memcpy(sweep_eps, c->sweep_eps.data(), c->sweep_eps.size() * sizeof(float));
+    return HSFLOW_OK;
+}
+
+int hsflow_solve_probe_pairs(hsflow_ctx *c, const hsflow_params *pp, float *sweep_eps)
+{
+    const int st = probe_impl(c, pp, sweep_eps, true);
+    if (st) return st;
+    std::memcpy(sweep_eps, c->sweep_eps_pairs.data(), c->sweep_eps_pairs.size() * sizeof(float));
+    return HSFLOW_OK;
+}
+
+int hsflow_set_pair_termination(hsflow_ctx *c, int per_pair)
+{
+    int st = check_ctx(c, 0);
+    if (st) return st;
+    if ((st = settle_pending(c))) return st; // the owed check belongs to a solve under the old rule
+    c->per_pair = per_pair != 0; // (graphs are keyed by it; the plans do not depend on it)
+    return HSFLOW_OK;
+}
+
+int hsflow_get_pair_result(hsflow_ctx *c, int pair, hsflow_pair_result *out)
+{
+    if (!c) return fail(nullptr, HSFLOW_E_ARG, "null context");
+    if (!out || out->struct_size != sizeof(hsflow_pair_result)) return fail(c, HSFLOW_E_ARG, "hsflow_get_pair_result: out null or struct_size mismatch");
+    if (pair < 0 || pair >= c->N) return fail(c, HSFLOW_E_ARG, "pair index out of range");
+    if (c->vstate == 0) return fail(c, HSFLOW_E_STATE, "hsflow_get_pair_result: no solve yet on this context");
+    int st = settle_pending(c);
+    if (st) return st;
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, HSFLOW_E_DEVICE, "hipSetDevice failed");
+    if ((st = measure_last_eps(c))) return st;
+    hsflow_pair_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.struct_size = sizeof(r);
+    r.pair = pair;
+    if (c->pair_res_valid) { // the pairs stopped each on its own
+        const hsflow_ctx::PairResult &q = c->pair_res[(size_t)pair];
+        r.status = q.status; r.iterations_done = q.iterations_done; r.last_eps = q.last_eps; r.eps_rerun = q.eps_rerun;
+        r.sweeps_executed = q.sweeps;
+    } else { // the batch stopped as one: its values for every pair
+        r.status = c->last_status; r.iterations_done = c->info.iterations_done; r.last_eps = c->info.last_eps;
+        r.eps_rerun = c->info.eps_rerun; r.sweeps_executed = c->sweeps_run;
+    }
+    *out = r;
     return HSFLOW_OK;
 }
 

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (HsflowError, HsflowInfo, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -214,6 +214,30 @@ class HSFlow(object):
         p = params if params is not None else self.make_params(**kw)
         out = np.empty(int(p.max_iter), np.float32)
         self._check(self._lib.hsflow_solve_probe(self._h, ctypes.byref(p), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
+
+    def solve_probe_pairs(self, params=None, **kw):
+        """`solve_probe` with the Eps of every sweep per pair: an fp32 array of shape (max_iter, n_pairs).  Column i is what a
+        one-pair context's `solve_probe` returns for pair i; the maximum of a row is what `solve_probe` returns."""
+        p = params if params is not None else self.make_params(**kw)
+        out = np.empty((int(p.max_iter), self.n_pairs), np.float32)
+        self._check(self._lib.hsflow_solve_probe_pairs(self._h, ctypes.byref(p), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
+
+    def set_pair_termination(self, on):
+        """on: under EPS termination every pair of the context stops on its own Eps, as cvCalcOpticalFlowHS called pair by
+        pair does; off (the default): the batch stops as one, on the maximum of its pairs' Eps."""
+        self._check(self._lib.hsflow_set_pair_termination(self._h, 1 if on else 0))
+
+    def pair_results(self):
+        """What the last solve did pair by pair: a list of dicts (pair, status, iterations_done, last_eps, eps_rerun,
+        sweeps_executed).  While the batch stops as one, every pair reports the batch's values."""
+        out = []
+        for i in range(self.n_pairs):
+            r = HsflowPairResult()
+            r.struct_size = ctypes.sizeof(HsflowPairResult)
+            self._check(self._lib.hsflow_get_pair_result(self._h, i, ctypes.byref(r)))
+            out.append(r.as_dict())
         return out
 
     def take_verdict(self):
