@@ -105,15 +105,9 @@ struct hsflow_ctx {
     float *dU[2] = {nullptr, nullptr}, *dV[2] = {nullptr, nullptr};
     unsigned long long *dStamps = nullptr; // diagnostic phase stamps (HSFLOW_DEBUG_STAMPS), else NULL
     unsigned *dEps = nullptr;   // kMaxFuse words: Eps sink of launches that do not collect it
-    unsigned *epsPtr = nullptr; // where the running launch records Eps: [sweep][epsStride] words
-    float epsThr = 0.f;         // witness launches: smallest float >= epsilon
     unsigned *hEps = nullptr;   // page-locked, device-visible: k_eps_reduce writes the per-sweep Eps words here
     unsigned *hEpsDev = nullptr; // the device's address of hEps
     size_t hEpsCap = 0;
-    int epsStride = 1;          // words per sweep: one per workgroup (strip / fold), else 1
-    int epsPair = 0;            // simple / LDS-tile kernel: 1 = one Eps word per (sweep, pair) instead of one per sweep
-    const int *pairList = nullptr; // the running launches work on these pairs only (device array of listCount indices), NULL: on all
-    int listCount = 0;
     int *dPairs = nullptr;      // 3 * N indices: the identity, the list of active pairs, the lists of a chunk's replays
     unsigned *dEpsTiles = nullptr; // per-sweep, per-workgroup Eps of the launches of one solve
     size_t epsTilesCap = 0;
@@ -183,13 +177,13 @@ struct hsflow_ctx {
     size_t scratch_bytes = 0;
     int cur = 0;                // which of dU/dV holds the current flow
     // hsflow_solve_async_frames_device: the caller's frames, while the solve has not yet decided who copies them (`lazy`:
-    // only inside that call), and -- once it has decided that its first Jacobi launch reads them in place and leaves the
-    // copy in dA / dB itself -- what that one launch is given (`src`: until the launch is out)
+    // only inside that call).  Once it has decided that its first Jacobi launch reads them in place and leaves the copy in
+    // dA / dB itself, that one launch is handed them (resolve_lazy_frames, LaunchIo::frames).
     struct FrameRef {
         bool active = false;
         const uint8_t *A = nullptr, *B = nullptr;
         long long PA = 0, PB = 0; // row pitches in bytes
-    } lazy, src;
+    } lazy;
     unsigned long long copies_elided = 0; // submissions whose frame copy rode in the first Jacobi launch (hsflow_frame_copies_elided)
     bool frames_set = false;
     bool coef_valid = false;
@@ -225,6 +219,21 @@ struct hsflow_ctx {
 };
 
 namespace {
+
+// What a Jacobi launch is handed besides its plan and its flow planes.  The solve paths build one from their locals at the
+// place of the launch; nothing of it lives in the context.  (Here, not next to EpsMode: it names hsflow_ctx::FrameRef.)
+struct LaunchIo {
+    unsigned *eps;         // where the launch records Eps: rows of `stride` words, one row per sweep (EverySweep) or launch
+    int stride = 1;        // words per row: one per workgroup (strip / fold), else 1
+    float thr = 0.f;       // witness launches: smallest float >= epsilon
+    int eps_pair = 0;      // simple / LDS-tile kernel: 1 = one Eps word per (sweep, pair) instead of one per sweep
+    const int *pairs = nullptr; // the launch works on these pairs only (device array of n_pairs indices), NULL: on all
+    int n_pairs = 0;
+    const hsflow_ctx::FrameRef *frames = nullptr; // a first launch with the derivative pass reads these, NULL: dA / dB
+};
+
+// The default: Eps into the sink nobody reads, all pairs, the context's own frames.
+LaunchIo default_io(const hsflow_ctx *c) { return LaunchIo{c->dEps}; }
 
 // live contexts per device (this process): the persistent launch wants the device to itself -- two persistent grids
 // from two contexts could each hold part of the CUs and wait for workgroups that cannot start

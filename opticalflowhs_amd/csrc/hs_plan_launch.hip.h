@@ -107,21 +107,22 @@ hipError_t launch_lds(const hsflow_ctx *c, int tiles, int threads, int lds_bytes
     X(1024, 1) X(1024, 2) X(1024, 3) X(512, 1) X(512, 2) X(512, 3) X(512, 4) X(256, 1) X(256, 2) X(256, 3) X(256, 4)
 
 template <bool EPS>
-hipError_t launch_fused_e(const hsflow_ctx *c, const FusedPlan &p, const float *ui, const float *vi, float *uo, float *vo, float coeff)
+hipError_t launch_fused_e(const hsflow_ctx *c, const FusedPlan &p, const LaunchIo &io, const float *ui, const float *vi, float *uo, float *vo,
+                         float coeff)
 {
 #define HS_CASE(NT_, K_)                                                                          \
     if (p.NT == NT_ && p.K == K_)                                                                 \
         return launch_lds<hsk::k_jacobi_fused<NT_, K_, EPS, 1>>(c, p.tiles, NT_, p.lds_bytes, c->dCoef, ui, vi, uo, vo, p.g, coeff, \
-                                                                c->epsPtr, c->epsStride);
+                                                                io.eps, io.stride);
     HS_FUSED_SHAPES(HS_CASE)
 #undef HS_CASE
     return hipErrorInvalidConfiguration;
 }
 
-hipError_t launch_fused(const hsflow_ctx *c, const FusedPlan &p, bool eps, const float *ui, const float *vi, float *uo, float *vo,
-                        float coeff)
+hipError_t launch_fused(const hsflow_ctx *c, const FusedPlan &p, bool eps, const LaunchIo &io, const float *ui, const float *vi, float *uo,
+                        float *vo, float coeff)
 {
-    return eps ? launch_fused_e<true>(c, p, ui, vi, uo, vo, coeff) : launch_fused_e<false>(c, p, ui, vi, uo, vo, coeff);
+    return eps ? launch_fused_e<true>(c, p, io, ui, vi, uo, vo, coeff) : launch_fused_e<false>(c, p, io, ui, vi, uo, vo, coeff);
 }
 
 template <bool WRITE_V>
@@ -395,32 +396,31 @@ constexpr auto strip_kernel()
 }
 
 template <int R, int NTMAX, EpsMode EPS, bool FOLD, bool DERIV, int E0>
-hipError_t launch_strip_k(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi, float *uo, float *vo, float coeff)
+hipError_t launch_strip_k(const hsflow_ctx *c, const StripPlan &p, const LaunchIo &io, const float *ui, const float *vi, float *uo, float *vo, float coeff)
 {
     constexpr auto kern = strip_kernel<R, NTMAX, (int)EPS, FOLD, DERIV, E0>();
     if (p.g.zero_in) ui = vi = c->dZero; // flow from zero: one row of zeros stands in for both planes (StripGeom::zero_in)
     unsigned long long *stamps = p.tiles <= 65536 ? c->dStamps : nullptr;
     if constexpr (DERIV && !FOLD) { // (the kernel takes the two frames ahead of the coefficient plane it writes)
         // the frames: the context's planes, or the caller's, which this launch then also copies into them (resolve_lazy_frames)
-        const bool ext = c->src.active;
-        const hsk::FrameSrc fs{ext ? (int)c->src.PA : c->P, ext ? (int)c->src.PB : c->P, ext ? c->dA : nullptr, ext ? c->dB : nullptr};
-        return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, ext ? c->src.A : c->dA, ext ? c->src.B : c->dB, fs, c->dCoef, ui, vi, uo, vo,
-                                p.g, coeff, c->epsPtr, c->epsStride, stamps, c->epsThr);
+        const hsflow_ctx::FrameRef *f = io.frames;
+        const hsk::FrameSrc fs{f ? (int)f->PA : c->P, f ? (int)f->PB : c->P, f ? c->dA : nullptr, f ? c->dB : nullptr};
+        return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, f ? f->A : c->dA, f ? f->B : c->dB, fs, c->dCoef, ui, vi, uo, vo, p.g, coeff,
+                                io.eps, io.stride, stamps, io.thr);
     } else if constexpr (DERIV)
-        return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dA, c->dB, c->dCoef, ui, vi, uo, vo, p.g, coeff, c->epsPtr,
-                                c->epsStride, stamps, c->epsThr);
+        return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dA, c->dB, c->dCoef, ui, vi, uo, vo, p.g, coeff, io.eps, io.stride,
+                                stamps, io.thr);
     else
-        return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dCoef, ui, vi, uo, vo, p.g, coeff, c->epsPtr, c->epsStride,
-                                stamps, c->epsThr);
+        return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dCoef, ui, vi, uo, vo, p.g, coeff, io.eps, io.stride, stamps, io.thr);
 }
 
 template <int R, int NTMAX, EpsMode EPS, bool FOLD, bool DERIV>
-hipError_t launch_strip_t(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi, float *uo, float *vo, float coeff)
+hipError_t launch_strip_t(const hsflow_ctx *c, const StripPlan &p, const LaunchIo &io, const float *ui, const float *vi, float *uo, float *vo, float coeff)
 {
     if constexpr (FOLD || (R & 1) == 0) {
-        if (strip_phase(p)) return launch_strip_k<R, NTMAX, EPS, FOLD, DERIV, 1>(c, p, ui, vi, uo, vo, coeff);
+        if (strip_phase(p)) return launch_strip_k<R, NTMAX, EPS, FOLD, DERIV, 1>(c, p, io, ui, vi, uo, vo, coeff);
     }
-    return launch_strip_k<R, NTMAX, EPS, FOLD, DERIV, 0>(c, p, ui, vi, uo, vo, coeff);
+    return launch_strip_k<R, NTMAX, EPS, FOLD, DERIV, 0>(c, p, io, ui, vi, uo, vo, coeff);
 }
 
 // The thread limit (__launch_bounds__) the kernels for R rows per lane are compiled with.  narrow: an Eps mode is on and
@@ -431,52 +431,52 @@ constexpr int strip_ntmax(int R, bool fold, bool narrow)
 }
 
 template <int R, EpsMode EPS, bool FOLD, bool DERIV>
-hipError_t launch_strip_r(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi, float *uo, float *vo, float coeff)
+hipError_t launch_strip_r(const hsflow_ctx *c, const StripPlan &p, const LaunchIo &io, const float *ui, const float *vi, float *uo, float *vo, float coeff)
 {
     constexpr int NT = strip_ntmax(R, FOLD, false), NT_NARROW = strip_ntmax(R, FOLD, EPS != EpsMode::None);
     if constexpr (NT_NARROW != NT) {
-        if (p.g.NW <= 12) return launch_strip_t<R, NT_NARROW, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+        if (p.g.NW <= 12) return launch_strip_t<R, NT_NARROW, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
     }
-    return launch_strip_t<R, NT, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+    return launch_strip_t<R, NT, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
 }
 
 template <EpsMode EPS, bool FOLD, bool DERIV>
-hipError_t launch_strip_e(const hsflow_ctx *c, const StripPlan &p, const float *ui, const float *vi, float *uo, float *vo, float coeff)
+hipError_t launch_strip_e(const hsflow_ctx *c, const StripPlan &p, const LaunchIo &io, const float *ui, const float *vi, float *uo, float *vo, float coeff)
 {
 #ifdef HS_DIAG_MIN /* diagnostic builds (tools/diag_build.sh): the R = 4 / 5 / 6 strip kernels without Eps only */
     if constexpr (!FOLD && !DERIV && EPS == EpsMode::None) {
-        if (p.R == 4) return launch_strip_r<4, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
-        if (p.R == 5) return launch_strip_r<5, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
-        if (p.R == 6) return launch_strip_r<6, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+        if (p.R == 4) return launch_strip_r<4, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
+        if (p.R == 5) return launch_strip_r<5, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
+        if (p.R == 6) return launch_strip_r<6, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
     }
 #else
     switch (p.R) {
-    case 1: return launch_strip_r<1, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
-    case 2: return launch_strip_r<2, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
-    case 3: return launch_strip_r<3, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
-    case 4: return launch_strip_r<4, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
-    case 5: return launch_strip_r<5, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
-    case 6: return launch_strip_r<6, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+    case 1: return launch_strip_r<1, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
+    case 2: return launch_strip_r<2, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
+    case 3: return launch_strip_r<3, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
+    case 4: return launch_strip_r<4, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
+    case 5: return launch_strip_r<5, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
+    case 6: return launch_strip_r<6, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
     }
     if constexpr (!DERIV) {
-        if (p.R == 7) return launch_strip_r<7, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
-        if (p.R == 8) return launch_strip_r<8, EPS, FOLD, DERIV>(c, p, ui, vi, uo, vo, coeff);
+        if (p.R == 7) return launch_strip_r<7, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
+        if (p.R == 8) return launch_strip_r<8, EPS, FOLD, DERIV>(c, p, io, ui, vi, uo, vo, coeff);
     }
 #endif
     return hipErrorInvalidConfiguration;
 }
 
 template <EpsMode EPS>
-hipError_t launch_strip_m(const hsflow_ctx *c, const StripPlan &p, bool deriv, const float *ui, const float *vi, float *uo, float *vo,
-                          float coeff)
+hipError_t launch_strip_m(const hsflow_ctx *c, const StripPlan &p, bool deriv, const LaunchIo &io, const float *ui, const float *vi, float *uo,
+                          float *vo, float coeff)
 {
     if constexpr (EPS != EpsMode::EverySweep) {
-        if (deriv) return p.fold ? launch_strip_e<EPS, true, true>(c, p, ui, vi, uo, vo, coeff)
-                                 : launch_strip_e<EPS, false, true>(c, p, ui, vi, uo, vo, coeff);
+        if (deriv) return p.fold ? launch_strip_e<EPS, true, true>(c, p, io, ui, vi, uo, vo, coeff)
+                                 : launch_strip_e<EPS, false, true>(c, p, io, ui, vi, uo, vo, coeff);
     }
     if (deriv) return hipErrorInvalidConfiguration;
-    return p.fold ? launch_strip_e<EPS, true, false>(c, p, ui, vi, uo, vo, coeff)
-                  : launch_strip_e<EPS, false, false>(c, p, ui, vi, uo, vo, coeff);
+    return p.fold ? launch_strip_e<EPS, true, false>(c, p, io, ui, vi, uo, vo, coeff)
+                  : launch_strip_e<EPS, false, false>(c, p, io, ui, vi, uo, vo, coeff);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -504,7 +504,8 @@ const char *persist_obstacle(const hsflow_ctx *c, const StripPlan &sp, int iters
 
 // (compiled for 5 rows per lane, up to 1024 threads, plain or witness phases: persist_obstacle)
 template <EpsMode EPS, bool DERIV>
-hipError_t launch_persist_t(hsflow_ctx *c, const StripPlan &p, const hsk::PersistArgs &pa, const float *ui, const float *vi, float coeff)
+hipError_t launch_persist_t(hsflow_ctx *c, const StripPlan &p, const hsk::PersistArgs &pa, const LaunchIo &io, const float *ui, const float *vi,
+                            float coeff)
 {
     constexpr auto kern = hsk::k_jacobi_strip_persist<5, 1024, (int)EPS, 0, DERIV>;
     static std::atomic<int> resident[64]; // workgroups per CU the runtime promises for this shape (0: not asked yet)
@@ -519,19 +520,19 @@ hipError_t launch_persist_t(hsflow_ctx *c, const StripPlan &p, const hsk::Persis
     }
     if (resident[dv].load() < 1) return hipErrorCooperativeLaunchTooLarge;
     if (p.g.zero_in) ui = vi = c->dZero;
-    return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dA, c->dB, c->dCoef, ui, vi, p.g, coeff, c->epsPtr, c->epsStride,
-                            p.tiles <= 8192 ? c->dStamps : nullptr, c->epsThr, pa);
+    return launch_lds<kern>(c, p.tiles, p.g.NW * 64, p.lds_bytes, c->dA, c->dB, c->dCoef, ui, vi, p.g, coeff, io.eps, io.stride,
+                            p.tiles <= 8192 ? c->dStamps : nullptr, io.thr, pa);
 }
 
-// eps: None plain phases, Witness witness phases (one row of c->epsStride words per phase at c->epsPtr)
-hipError_t launch_persist(hsflow_ctx *c, const StripPlan &sp, const hsk::PersistArgs &pa, EpsMode eps, bool deriv, const float *ui,
-                          const float *vi, float coeff)
+// eps: None plain phases, Witness witness phases (one row of io.stride words per phase at io.eps)
+hipError_t launch_persist(hsflow_ctx *c, const StripPlan &sp, const hsk::PersistArgs &pa, EpsMode eps, bool deriv, const LaunchIo &io,
+                          const float *ui, const float *vi, float coeff)
 {
     if (sp.R != 5) return hipErrorInvalidConfiguration;
-    if (eps == EpsMode::Witness) return deriv ? launch_persist_t<EpsMode::Witness, true>(c, sp, pa, ui, vi, coeff)
-                                              : launch_persist_t<EpsMode::Witness, false>(c, sp, pa, ui, vi, coeff);
-    return deriv ? launch_persist_t<EpsMode::None, true>(c, sp, pa, ui, vi, coeff)
-                 : launch_persist_t<EpsMode::None, false>(c, sp, pa, ui, vi, coeff);
+    if (eps == EpsMode::Witness) return deriv ? launch_persist_t<EpsMode::Witness, true>(c, sp, pa, io, ui, vi, coeff)
+                                              : launch_persist_t<EpsMode::Witness, false>(c, sp, pa, io, ui, vi, coeff);
+    return deriv ? launch_persist_t<EpsMode::None, true>(c, sp, pa, io, ui, vi, coeff)
+                 : launch_persist_t<EpsMode::None, false>(c, sp, pa, io, ui, vi, coeff);
 }
 
 
@@ -606,34 +607,35 @@ bool make_witness_jplan(const hsflow_ctx *c, int kind, int T, const hsflow_param
     return false;
 }
 
-// One launch of pl.T sweeps.  eps: what it records (the LDS-tile kernel knows None and EverySweep only)
+// One launch of pl.T sweeps.  eps: what it records (the LDS-tile kernel knows None and EverySweep only), io: where, over
+// which pairs and from which frames (LaunchIo; EpsMode::None goes with default_io's sink)
 // deriv: this launch also does the derivative pass (only where strip_deriv_fusable() said so)
-hipError_t launch_j(const hsflow_ctx *c, const JPlan &pl, EpsMode eps, const float *ui, const float *vi,
+hipError_t launch_j(const hsflow_ctx *c, const JPlan &pl, EpsMode eps, const LaunchIo &io, const float *ui, const float *vi,
                     float *uo, float *vo, float coeff, int zero_in = 0, bool deriv = false)
 {
     if (pl.kind == HSFLOW_KERNEL_STRIP || pl.kind == HSFLOW_KERNEL_FOLD) {
         StripPlan sp = pl.s;
         sp.g.zero_in = zero_in;
-        if (c->pairList) { // the pairs of the list only (the per-pair stop): n_active x tiles_per_pair workgroups
-            sp.g.pair_list = c->pairList;
-            sp.tiles = sp.tiles / c->N * c->listCount;
+        if (io.pairs) { // the pairs of the list only (the per-pair stop): n_active x tiles_per_pair workgroups
+            sp.g.pair_list = io.pairs;
+            sp.tiles = sp.tiles / c->N * io.n_pairs;
         }
         switch (eps) {
-        case EpsMode::None: return launch_strip_m<EpsMode::None>(c, sp, deriv, ui, vi, uo, vo, coeff);
-        case EpsMode::EverySweep: return launch_strip_m<EpsMode::EverySweep>(c, sp, deriv, ui, vi, uo, vo, coeff);
-        case EpsMode::Witness: return launch_strip_m<EpsMode::Witness>(c, sp, deriv, ui, vi, uo, vo, coeff);
-        case EpsMode::WitnessLast: return launch_strip_m<EpsMode::WitnessLast>(c, sp, deriv, ui, vi, uo, vo, coeff);
+        case EpsMode::None: return launch_strip_m<EpsMode::None>(c, sp, deriv, io, ui, vi, uo, vo, coeff);
+        case EpsMode::EverySweep: return launch_strip_m<EpsMode::EverySweep>(c, sp, deriv, io, ui, vi, uo, vo, coeff);
+        case EpsMode::Witness: return launch_strip_m<EpsMode::Witness>(c, sp, deriv, io, ui, vi, uo, vo, coeff);
+        case EpsMode::WitnessLast: return launch_strip_m<EpsMode::WitnessLast>(c, sp, deriv, io, ui, vi, uo, vo, coeff);
         }
         return hipErrorInvalidConfiguration;
     }
     FusedPlan fp = pl.f;
     fp.g.zero_in = zero_in;
-    fp.g.eps_pair = c->epsPair;
-    if (c->pairList) {
-        fp.g.pair_list = c->pairList;
-        fp.tiles = fp.tiles / c->N * c->listCount;
+    fp.g.eps_pair = io.eps_pair;
+    if (io.pairs) {
+        fp.g.pair_list = io.pairs;
+        fp.tiles = fp.tiles / c->N * io.n_pairs;
     }
-    return launch_fused(c, fp, eps != EpsMode::None, ui, vi, uo, vo, coeff);
+    return launch_fused(c, fp, eps != EpsMode::None, io, ui, vi, uo, vo, coeff);
 }
 
 
@@ -668,19 +670,19 @@ hipError_t for_pair_batches(const hsflow_ctx *c, Launch launch)
     return hipSuccess;
 }
 
-hipError_t launch_simple(const hsflow_ctx *c, bool eps, const float *ui, const float *vi, float *uo,
+hipError_t launch_simple(const hsflow_ctx *c, bool eps, const LaunchIo &io, const float *ui, const float *vi, float *uo,
                          float *vo, float coeff, int zero_in = 0)
 {
-    // c->epsPair: one Eps word per pair of the launch (at c->epsPtr) instead of one for all; c->pairList: the launch works on
-    // the listed pairs only, layer z on pair pairList[z] -- in batches of max_grid_z layers like the whole context's pairs
-    const int *list = c->pairList;
+    // io.eps_pair: one Eps word per pair of the launch (at io.eps) instead of one for all; io.pairs: the launch works on
+    // the listed pairs only, layer z on pair pairs[z] -- in batches of max_grid_z layers like the whole context's pairs
+    const int *list = io.pairs;
     auto go = [&](long long o, int first, int n) {
         const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4, n), block(64, 4);
-        unsigned *ep = c->epsPtr + (c->epsPair ? first : 0);
+        unsigned *ep = io.eps + (io.eps_pair ? first : 0);
         const int *pl = list ? list + first : nullptr;
 #define HS_SIMPLE(E, Z)                                                                            \
         hipLaunchKernelGGL((hsk::k_jacobi_simple<E, Z>), grid, block, 0, c->stream, c->dCoef + o, ui + o, vi + o, uo + o, vo + o, \
-                           c->W, c->H, c->P, c->plane, coeff, ep, c->org, eps_row0(c), eps_row1(c), pl, c->epsPair)
+                           c->W, c->H, c->P, c->plane, coeff, ep, c->org, eps_row0(c), eps_row1(c), pl, io.eps_pair)
         if (eps) { if (zero_in) HS_SIMPLE(true, true); else HS_SIMPLE(true, false); }
         else { if (zero_in) HS_SIMPLE(false, true); else HS_SIMPLE(false, false); }
 #undef HS_SIMPLE
@@ -688,8 +690,8 @@ hipError_t launch_simple(const hsflow_ctx *c, bool eps, const float *ui, const f
     if (list) {
         if (c->configuring) return hipSuccess;
         const int zmax = std::max(1, c->max_grid_z);
-        for (int z0 = 0; z0 < c->listCount; z0 += zmax) {
-            go(0, z0, std::min(zmax, c->listCount - z0));
+        for (int z0 = 0; z0 < io.n_pairs; z0 += zmax) {
+            go(0, z0, std::min(zmax, io.n_pairs - z0));
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
         }

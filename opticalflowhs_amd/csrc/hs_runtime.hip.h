@@ -59,15 +59,16 @@ bool frames_readable_in_place(const hsflow_ctx *c, const void *dprev, size_t ps,
 }
 
 // The frames of hsflow_solve_async_frames_device, once the solve knows its first launch: in_place -- that launch carries
-// the derivative pass on the strip kernel, reads the caller's planes and stores the context's copy (c->src, for that one
-// launch); otherwise the copy kernel goes out now, ahead of whatever reads dA / dB.  Never inside a capture or a dry run.
-int resolve_lazy_frames(hsflow_ctx *c, bool in_place)
+// the derivative pass on the strip kernel, reads the caller's planes and stores the context's copy (*first: what the
+// caller hands that one launch as LaunchIo::frames); otherwise the copy kernel goes out now, ahead of whatever reads
+// dA / dB.  Never inside a capture or a dry run.
+int resolve_lazy_frames(hsflow_ctx *c, bool in_place, hsflow_ctx::FrameRef *first = nullptr)
 {
     if (!c->lazy.active) return HSFLOW_OK;
     c->lazy.active = false;
     if (in_place) {
-        c->src = c->lazy;
-        c->src.active = true;
+        *first = c->lazy;
+        first->active = true;
         c->copies_elided++;
         return HSFLOW_OK;
     }
@@ -176,8 +177,8 @@ bool persist_gave_up(hsflow_ctx *c)
 }
 
 // One persistent launch = `iters` sweeps in phases of sp.g.T: input dU[cur] (or zero), output dU[cur ^ 1]; the phases
-// alternate between that buffer and the third one so that the last phase lands in it.
-int enqueue_persist(hsflow_ctx *c, const StripPlan &sp0, int iters, EpsMode eps, bool deriv, int zero_in, float coeff)
+// alternate between that buffer and the third one so that the last phase lands in it.  io.eps: a row of Eps words per phase.
+int enqueue_persist(hsflow_ctx *c, const StripPlan &sp0, int iters, EpsMode eps, const LaunchIo &io, bool deriv, int zero_in, float coeff)
 {
     StripPlan sp = sp0;
     sp.g.zero_in = zero_in;
@@ -195,7 +196,7 @@ int enqueue_persist(hsflow_ctx *c, const StripPlan &sp0, int iters, EpsMode eps,
     const int lastb = (pa.n_phase - 1) & 1;
     pa.ub[lastb] = c->dU[b]; pa.vb[lastb] = c->dV[b];
     pa.ub[lastb ^ 1] = c->dUp; pa.vb[lastb ^ 1] = c->dVp;
-    HS_HIP(c, launch_persist(c, sp, pa, eps, deriv, c->dU[a], c->dV[a], coeff));
+    HS_HIP(c, launch_persist(c, sp, pa, eps, deriv, io, c->dU[a], c->dV[a], coeff));
     c->cur = b;
     return HSFLOW_OK;
 }
@@ -205,19 +206,19 @@ int enqueue_persist(hsflow_ctx *c, const StripPlan &sp0, int iters, EpsMode eps,
 int configure_persist(hsflow_ctx *c, const StripPlan &sp, EpsMode eps, bool deriv, float coeff)
 {
     c->configuring = true;
-    const hipError_t e = launch_persist(c, sp, hsk::PersistArgs{}, eps, deriv, nullptr, nullptr, coeff);
+    const hipError_t e = launch_persist(c, sp, hsk::PersistArgs{}, eps, deriv, default_io(c), nullptr, nullptr, coeff);
     c->configuring = false;
     HS_HIP(c, e);
     return HSFLOW_OK;
 }
 
-// Enqueue derivative pass + `iters` Jacobi sweeps (no host synchronisation inside).
-int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters, int kernel, int T,
-                  const JPlan *plan, const JPlan *tail_plan, Profiler &prof, bool do_deriv, bool zero_flow, bool persist = false,
-                  int part = 0)
+// Enqueue derivative pass + `iters` Jacobi sweeps (no host synchronisation inside).  io: what every launch is handed
+// (no Eps is recorded: default_io, with the caller's frames for the first launch where that reads them in place).
+int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters, int kernel, int T, const JPlan *plan,
+                  const JPlan *tail_plan, Profiler &prof, const LaunchIo &io, bool do_deriv, bool zero_flow, bool persist = false, int part = 0)
 {
     // part: 0 the whole sequence; 1 up to and including the first Jacobi launch; 2 what follows it (c->cur as part 1 left
-    // it).  A solve whose first launch reads the caller's frames (c->src) issues that launch by itself, with this
+    // it).  A solve whose first launch reads the caller's frames (io.frames) issues that launch by itself, with this
     // submission's pointers, and replays the rest from the graph cache.
     // u = v = 0 at the start (reference behaviour, use_previous = 0): instead of clearing two
     // planes and reading them back, the first launch is told that its input is zero.
@@ -235,7 +236,7 @@ int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters,
     int left = iters, launches = 0;
     if (persist) { // the whole budget as one launch
         prof.begin(1);
-        const int st = enqueue_persist(c, plan->s, iters, EpsMode::None, fuse, zero_in, coeff);
+        const int st = enqueue_persist(c, plan->s, iters, EpsMode::None, io, fuse, zero_in, coeff);
         prof.end();
         if (st) return st;
         left = 0;
@@ -245,7 +246,7 @@ int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters,
         const int a = c->cur, b = a ^ 1;
         if (kernel == HSFLOW_KERNEL_SIMPLE) {
             prof.begin(1);
-            HS_HIP(c, launch_simple(c, false, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, zero_in));
+            HS_HIP(c, launch_simple(c, false, io, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, zero_in));
             prof.end();
             left -= 1;
         } else {
@@ -258,7 +259,7 @@ int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters,
                 continue;
             }
             prof.begin(1);
-            HS_HIP(c, launch_j(c, *pl, EpsMode::None, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, zero_in, fuse));
+            HS_HIP(c, launch_j(c, *pl, EpsMode::None, io, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, zero_in, fuse));
             prof.end();
             fuse = false;
             left -= pl->T;
@@ -274,7 +275,8 @@ int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters,
 
 // Eps bookkeeping of an EPS-terminated solve: `sweeps` rows of `stride` words (one per workgroup) on the device, and
 // the host buffer k_eps_reduce reduces the rows into, hEps[0..sweeps).  eps_reserve allocates only, so that what
-// follows can be captured in a graph; eps_prepare also clears the rows.
+// follows can be captured in a graph; eps_prepare also clears the rows.  Neither tells the launches anything: the caller
+// hands them the rows (LaunchIo).
 // host_words: words the reduction writes to the host (a per-pair reduction: sweeps x pairs), 0: one per row.
 int eps_reserve(hsflow_ctx *c, int sweeps, int stride, size_t host_words = 0)
 {
@@ -297,7 +299,6 @@ int eps_reserve(hsflow_ctx *c, int sweeps, int stride, size_t host_words = 0)
         HS_HIP(c, hipHostGetDevicePointer((void **)&c->hEpsDev, c->hEps, 0));
         c->hEpsCap = cap;
     }
-    c->epsStride = stride;
     return HSFLOW_OK;
 }
 
@@ -313,13 +314,10 @@ int eps_prepare(hsflow_ctx *c, int sweeps, int stride)
     return st ? st : eps_clear(c, sweeps, stride);
 }
 
-// Reduces the rows of per-workgroup words to one word per row, straight into the host's buffer (no copy node), and
-// points the launches that follow back at the Eps sink.
+// Reduces the rows of per-workgroup words to one word per row, straight into the host's buffer (no copy node).
 // mark: the kernel's last workgroup also writes the context's marker (hsflow_set_async_reduce; the caller counts it).
 int eps_collect_enqueue(hsflow_ctx *c, const EpsLayout &w, bool mark = false)
 {
-    c->epsPtr = c->dEps;
-    c->epsStride = 1;
     if (c->configuring) return HSFLOW_OK;
     if (w.pairs > 0) { // one word per (row, pair): hEps[row * pairs + pair]
         // (pairs of fewer than 8 workgroups: a lane each; the rows of one pass differ by a short last launch at most)
@@ -339,10 +337,10 @@ int eps_collect_enqueue(hsflow_ctx *c, const EpsLayout &w, bool mark = false)
     return HSFLOW_OK;
 }
 
-// The exact pass: every row is epsStride words, cleared where a launch had fewer workgroups (eps_prepare).
-int eps_collect(hsflow_ctx *c, int sweeps, std::vector<unsigned> &host)
+// The exact pass: every row is `stride` words, cleared where a launch had fewer workgroups (eps_prepare).
+int eps_collect(hsflow_ctx *c, int sweeps, int stride, std::vector<unsigned> &host)
 {
-    int st = eps_collect_enqueue(c, EpsLayout{sweeps, c->epsStride, 0, 0, c->epsStride});
+    int st = eps_collect_enqueue(c, EpsLayout{sweeps, stride, 0, 0, stride});
     if (st) return st;
     HS_HIP(c, hipStreamSynchronize(c->stream));
     host.assign(c->hEps, c->hEps + sweeps);

@@ -31,25 +31,66 @@ int wait_marker(hsflow_ctx *c, unsigned target)
     return HSFLOW_OK;
 }
 
+// Pair `pair`'s u and v planes (n planes each, from that pair on) from (su, sv) to (du, dv), on the context's stream.
+hipError_t copy_pair_flow(hsflow_ctx *c, float *du, float *dv, const float *su, const float *sv, int pair, int n = 1)
+{
+    const long long o = (long long)pair * c->plane;
+    const size_t bytes = (size_t)c->plane * n * sizeof(float);
+    const hipError_t e = hipMemcpyAsync(du + o, su + o, bytes, hipMemcpyDeviceToDevice, c->stream);
+    return e != hipSuccess ? e : hipMemcpyAsync(dv + o, sv + o, bytes, hipMemcpyDeviceToDevice, c->stream);
+}
+
+// dUb / dVb: the backup of a starting flow (save_start; the chunk input of the per-pair stop on the one-sweep kernel).
+int reserve_start_backup(hsflow_ctx *c)
+{
+    const size_t px = (size_t)c->plane * c->N;
+    if (!c->dUb) HS_HIP(c, hipMalloc((void **)&c->dUb, px * sizeof(float)));
+    if (!c->dVb) HS_HIP(c, hipMalloc((void **)&c->dVb, px * sizeof(float)));
+    return HSFLOW_OK;
+}
+
 // ITER|EPS with use_previous: the ping-pong buffers get overwritten, so the starting flow is kept in dUb / dVb
 // (allocated by solve_iter_eps) for an exact pass that has to start over from it ...
 int save_start(hsflow_ctx *c)
 {
     if (c->configuring) return HSFLOW_OK;
-    const size_t bytes = (size_t)c->plane * c->N * sizeof(float);
-    HS_HIP(c, hipMemcpyAsync(c->dUb, c->dU[c->cur], bytes, hipMemcpyDeviceToDevice, c->stream));
-    HS_HIP(c, hipMemcpyAsync(c->dVb, c->dV[c->cur], bytes, hipMemcpyDeviceToDevice, c->stream));
+    HS_HIP(c, copy_pair_flow(c, c->dUb, c->dVb, c->dU[c->cur], c->dV[c->cur], 0, c->N));
     return HSFLOW_OK;
 }
 
 // ... which copies it back into the current buffer.
 int restore_start(hsflow_ctx *c)
 {
-    const size_t bytes = (size_t)c->plane * c->N * sizeof(float);
-    HS_HIP(c, hipMemcpyAsync(c->dU[c->cur], c->dUb, bytes, hipMemcpyDeviceToDevice, c->stream));
-    HS_HIP(c, hipMemcpyAsync(c->dV[c->cur], c->dVb, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HS_HIP(c, copy_pair_flow(c, c->dU[c->cur], c->dV[c->cur], c->dUb, c->dVb, 0, c->N));
     return HSFLOW_OK;
 }
+
+// Do the derivatives have to be computed, or does the coefficient plane hold those of this mode and may be reused?
+bool needs_deriv(const hsflow_ctx *c, const hsflow_params &p, int mode) { return !(p.reuse_derivatives && c->coef_valid && c->coef_mode == mode); }
+
+// The bits of GraphKey::use_prev: what, besides the shapes, decides which launches a captured sequence holds.
+// (p.use_previous enters as p.use_previous * kKeyUsePrev.)
+enum : int {
+    kKeyDeriv = 1,       // the sequence computes the derivatives
+    kKeyUsePrev = 2,
+    kKeyAsync = 4,       // CV mode: an asynchronous witness pass (Witness last launch, reduction owed)
+    kKeyUnpack = 4,      // classic mode: the derivative planes are unpacked
+    kKeyAsyncReduce = 8, // ... with the reduction in the stream
+    kKeyInPlace = 16,    // the first launch went out by itself (it reads the caller's frames): the launches after it
+    kKeyPerPair = 32,    // the witness words are reduced per pair
+};
+
+// EPS termination without a usable sweep budget stops only on Eps < epsilon.  A positive epsilon below the fp32 limit
+// cycle of the iteration (Eps stalls around 1e-7 * |flow|) would keep the host launching for ever -- the original does
+// exactly that; here a solve (a pair, under the per-pair stop) gives up with HSFLOW_E_NOTERM (flow, iterations_done and
+// last_eps stay valid) once Eps has not reached a new minimum for kStallSweeps sweeps or after kMaxSweeps.
+constexpr long long kStallSweeps = 4096, kMaxSweeps = 1LL << 24;
+struct StallWatch {
+    float best = INFINITY; // the lowest Eps so far ...
+    long long at = 0;      // ... and the sweep it occurred in
+    void seen(float e, long long sweep) { if (e < best) { best = e; at = sweep; } }
+    bool give_up(long long ran, long long budget) const { return budget > kMaxSweeps && (ran - at >= kStallSweeps || ran >= kMaxSweeps); }
+};
 
 // ------------------------------------------------------------------------------------------------------------------
 // Per-pair stop (hsflow_set_pair_termination): under EPS termination every pair of a batch stops on its own Eps, as
@@ -80,23 +121,12 @@ void pairs_to_info(hsflow_ctx *c)
 // of the budget); the one-sweep kernel runs HSFLOW_PAIR_STOP_SIMPLE_CHUNK launches between read-backs and keeps the
 // chunk's input in dUb / dVb (its ping-pong overwrites it).  Afterwards the stream is idle and hsflow_info is that of the
 // whole solve.  rerun: a witness pass ran before and proved nothing for these pairs.
-int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, const std::vector<int> &list, PairStart start, bool rerun);
 int solve_pairs_exact(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, const std::vector<int> &list, PairStart start, bool rerun)
-{
-    const int st = solve_pairs_exact_body(c, p, S, list, start, rerun);
-    // however it ended: the launches that follow work on every pair again and record no Eps
-    c->pairList = nullptr; c->listCount = 0; c->epsPair = 0; c->epsPtr = c->dEps; c->epsStride = 1;
-    return st;
-}
-
-int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, const std::vector<int> &list, PairStart start, bool rerun)
 {
     const int N = c->N, kernel = S.kernel;
     const bool multi = S.multi, strip = kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD;
     const int T = multi ? S.T : HSFLOW_PAIR_STOP_SIMPLE_CHUNK;
     const long long budget = S.budget;
-    const size_t bytes = (size_t)c->plane * sizeof(float);
-    constexpr long long kStallSweeps = 4096, kMaxSweeps = 1LL << 24; // (solve_eps_chunks)
     int st = HSFLOW_OK;
     if (list.empty()) { pairs_to_info(c); return HSFLOW_OK; }
     if (!c->dPairs) { // the identity, then room for the list of active pairs and for the lists of a chunk's replays
@@ -105,11 +135,7 @@ int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSet
         HS_HIP(c, hipMalloc((void **)&c->dPairs, 3 * (size_t)N * sizeof(int)));
         HS_HIP(c, hipMemcpy(c->dPairs, ident.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
     }
-    if (!multi) {
-        const size_t px = (size_t)c->plane * N;
-        if (!c->dUb) HS_HIP(c, hipMalloc((void **)&c->dUb, px * sizeof(float)));
-        if (!c->dVb) HS_HIP(c, hipMalloc((void **)&c->dVb, px * sizeof(float)));
-    }
+    if (!multi && (st = reserve_start_backup(c))) return st;
     JPlan tail;
     const int rem = (multi && budget < (1LL << 30)) ? (int)(budget % T) : 0;
     if (rem && !make_jplan(c, kernel, rem, p, tail)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
@@ -118,23 +144,12 @@ int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSet
     int cur = c->cur; // the buffer that holds the active pairs' flow
     bool zero = start == PairStart::Zero;
     if (start == PairStart::Saved)
-        for (int pair : list) {
-            const long long o = (long long)pair * c->plane;
-            HS_HIP(c, hipMemcpyAsync(c->dU[cur] + o, c->dUb + o, bytes, hipMemcpyDeviceToDevice, c->stream));
-            HS_HIP(c, hipMemcpyAsync(c->dV[cur] + o, c->dVb + o, bytes, hipMemcpyDeviceToDevice, c->stream));
-        }
-    auto both = [&](int pair, int from) -> hipError_t { // a stopped pair's final flow into the other buffer as well
-        const long long o = (long long)pair * c->plane;
-        hipError_t e = hipMemcpyAsync(c->dU[from ^ 1] + o, c->dU[from] + o, bytes, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->dV[from ^ 1] + o, c->dV[from] + o, bytes, hipMemcpyDeviceToDevice, c->stream);
-        return e;
-    };
+        for (int pair : list) HS_HIP(c, copy_pair_flow(c, c->dU[cur], c->dV[cur], c->dUb, c->dVb, pair));
     std::vector<int> active = list, next, rlist;
     std::map<int, std::vector<int>> replays;    // sweeps to replay -> the pairs that stopped there in this chunk
     std::vector<std::pair<int, int>> stopped;   // (pair, buffer its final flow lies in)
     std::vector<unsigned> words;
-    std::vector<float> best_eps((size_t)N, INFINITY);
-    std::vector<long long> best_at((size_t)N, 0);
+    std::vector<StallWatch> stall((size_t)N);
     long long done = 0;
     int launches = 0, stalled = -1;
     for (int pair : list) c->pair_res[(size_t)pair].eps_rerun = rerun ? 1 : 0;
@@ -142,35 +157,23 @@ int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSet
         const int n_act = (int)active.size();
         const int chunk = (int)std::min<long long>(T, budget - done);
         HS_HIP(c, hipMemcpyAsync(c->dPairs + N, active.data(), (size_t)n_act * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        c->pairList = c->dPairs + N;
-        c->listCount = n_act;
         const int a0 = cur;
         const JPlan &cp = chunk == T ? S.plan : tail;
+        // the chunk's launches: the active pairs; strip / fold a row of `stride` words per sweep (every launch writes all its
+        // words), the other kernels one word per (sweep, active pair), cleared first
+        LaunchIo io{c->dEpsTiles, strip ? stride : n_act, 0.f, strip ? 0 : 1, c->dPairs + N, n_act};
         if (multi) {
-            c->epsPtr = c->dEpsTiles;
-            if (strip) c->epsStride = stride; // (every launch writes all its words)
-            else {
-                if ((st = eps_clear(c, chunk, n_act))) return st;
-                c->epsStride = n_act;
-                c->epsPair = 1;
-            }
-            const hipError_t e = launch_j(c, cp, EpsMode::EverySweep, c->dU[cur], c->dV[cur], c->dU[cur ^ 1], c->dV[cur ^ 1], S.coeff, zero ? 1 : 0);
-            HS_HIP(c, e);
+            if (!strip && (st = eps_clear(c, chunk, n_act))) return st;
+            HS_HIP(c, launch_j(c, cp, EpsMode::EverySweep, io, c->dU[cur], c->dV[cur], c->dU[cur ^ 1], c->dV[cur ^ 1], S.coeff, zero ? 1 : 0));
             cur ^= 1;
             launches++;
         } else {
-            if (!zero)
-                for (int pair : active) { // the chunk's input, for a replay
-                    const long long o = (long long)pair * c->plane;
-                    HS_HIP(c, hipMemcpyAsync(c->dUb + o, c->dU[cur] + o, bytes, hipMemcpyDeviceToDevice, c->stream));
-                    HS_HIP(c, hipMemcpyAsync(c->dVb + o, c->dV[cur] + o, bytes, hipMemcpyDeviceToDevice, c->stream));
-                }
+            if (!zero) // the chunk's input, for a replay
+                for (int pair : active) HS_HIP(c, copy_pair_flow(c, c->dUb, c->dVb, c->dU[cur], c->dV[cur], pair));
             if ((st = eps_clear(c, chunk, n_act))) return st;
-            c->epsPair = 1;
             for (int s = 0; s < chunk; s++) {
-                c->epsPtr = c->dEpsTiles + (size_t)s * n_act;
-                const hipError_t e = launch_simple(c, true, c->dU[cur], c->dV[cur], c->dU[cur ^ 1], c->dV[cur ^ 1], S.coeff, (zero && s == 0) ? 1 : 0);
-                HS_HIP(c, e);
+                io.eps = c->dEpsTiles + (size_t)s * n_act;
+                HS_HIP(c, launch_simple(c, true, io, c->dU[cur], c->dV[cur], c->dU[cur ^ 1], c->dV[cur ^ 1], S.coeff, (zero && s == 0) ? 1 : 0));
                 cur ^= 1;
                 launches++;
             }
@@ -188,9 +191,6 @@ int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSet
             HS_HIP(c, hipMemcpyAsync(words.data(), c->dEpsTiles, words.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
             HS_HIP(c, hipStreamSynchronize(c->stream));
         }
-        c->epsPair = 0;
-        c->epsPtr = c->dEps;
-        c->epsStride = 1;
         next.clear();
         replays.clear();
         stopped.clear();
@@ -203,7 +203,7 @@ int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSet
             for (int s = 0; s < chunk && hit < 0; s++) {
                 std::memcpy(&e, &words[(size_t)s * n_act + k], sizeof(float));
                 if ((double)e < p.epsilon) hit = s;
-                else if (e < best_eps[(size_t)pair]) { best_eps[(size_t)pair] = e; best_at[(size_t)pair] = done + s; }
+                else stall[(size_t)pair].seen(e, done + s);
             }
             r.last_eps = e;
             r.eps_owed = false;
@@ -215,7 +215,7 @@ int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSet
             }
             const long long ran = hit >= 0 ? done + hit + 1 : done + chunk;
             if (!stop && S.use_iter && p.max_iter > 0 && ran >= budget) stop = true;
-            if (!stop && budget > kMaxSweeps && (ran - best_at[(size_t)pair] >= kStallSweeps || ran >= kMaxSweeps)) { // (the stall rule)
+            if (!stop && stall[(size_t)pair].give_up(ran, budget)) {
                 stop = true;
                 r.status = HSFLOW_E_NOTERM;
                 if (stalled < 0) stalled = pair;
@@ -235,34 +235,29 @@ int solve_pairs_exact_body(hsflow_ctx *c, const hsflow_params &p, const SolveSet
         size_t at = 0;
         for (const auto &g : replays) {
             const int k1 = g.first, n = (int)g.second.size();
-            c->pairList = c->dPairs + 2 * (size_t)N + at;
-            c->listCount = n;
+            LaunchIo io = default_io(c); // (a replay records no Eps)
+            io.pairs = c->dPairs + 2 * (size_t)N + at;
+            io.n_pairs = n;
             at += (size_t)n;
             if (multi) {
                 JPlan rp;
                 if (!make_jplan(c, kernel, k1, p, rp)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the replay");
-                const hipError_t er = launch_j(c, rp, EpsMode::None, c->dU[a0], c->dV[a0], c->dU[a0 ^ 1], c->dV[a0 ^ 1], S.coeff, zero ? 1 : 0);
-                HS_HIP(c, er);
+                HS_HIP(c, launch_j(c, rp, EpsMode::None, io, c->dU[a0], c->dV[a0], c->dU[a0 ^ 1], c->dV[a0 ^ 1], S.coeff, zero ? 1 : 0));
                 launches++;
             } else {
                 if (!zero)
-                    for (int pair : g.second) {
-                        const long long o = (long long)pair * c->plane;
-                        HS_HIP(c, hipMemcpyAsync(c->dU[a0] + o, c->dUb + o, bytes, hipMemcpyDeviceToDevice, c->stream));
-                        HS_HIP(c, hipMemcpyAsync(c->dV[a0] + o, c->dVb + o, bytes, hipMemcpyDeviceToDevice, c->stream));
-                    }
+                    for (int pair : g.second) HS_HIP(c, copy_pair_flow(c, c->dU[a0], c->dV[a0], c->dUb, c->dVb, pair));
                 int from = a0;
                 for (int s = 0; s < k1; s++) {
-                    const hipError_t er = launch_simple(c, false, c->dU[from], c->dV[from], c->dU[from ^ 1], c->dV[from ^ 1], S.coeff, (zero && s == 0) ? 1 : 0);
-                    HS_HIP(c, er);
+                    HS_HIP(c, launch_simple(c, false, io, c->dU[from], c->dV[from], c->dU[from ^ 1], c->dV[from ^ 1], S.coeff, (zero && s == 0) ? 1 : 0));
                     from ^= 1;
                     launches++;
                 }
             }
             c->sweeps_run += k1;
         }
-        for (const auto &sp : stopped) HS_HIP(c, both(sp.first, sp.second));
-        c->pairList = nullptr;
+        for (const auto &sp : stopped) // a stopped pair's final flow into the other buffer as well
+            HS_HIP(c, copy_pair_flow(c, c->dU[sp.second ^ 1], c->dV[sp.second ^ 1], c->dU[sp.second], c->dV[sp.second], sp.first));
         active.swap(next); // (the list uploaded this round is not written again before the next round's read-back)
         done += chunk;
         zero = false;
@@ -381,22 +376,13 @@ int measure_last_eps(hsflow_ctx *c)
     int st = eps_reserve(c, 2, stride, c->pair_res_valid ? 2 * (size_t)c->N : 0);
     if (st) return st;
     const int b = c->cur, a = b ^ 1;
-    c->epsPtr = c->dEpsTiles;
-    c->epsStride = stride;
-    c->epsThr = L.eps_thr;
     const float *ui = L.from_third ? c->dUp : c->dU[a], *vi = L.from_third ? c->dVp : c->dV[a];
-    const hipError_t e = launch_j(c, L.plan, EpsMode::WitnessLast, ui, vi, c->dU[b], c->dV[b], L.coeff, L.zero_in);
-    HS_HIP(c, e);
+    HS_HIP(c, launch_j(c, L.plan, EpsMode::WitnessLast, LaunchIo{c->dEpsTiles, stride, L.eps_thr}, ui, vi, c->dU[b], c->dV[b], L.coeff, L.zero_in));
     if (c->pair_res_valid) { // a per-pair solve: the proven pairs' last sweep, each over its own workgroups
         if ((st = eps_collect_enqueue(c, EpsLayout{2, stride, 0, 0, stride, c->N}))) return st;
         // the launch also ran over the pairs that stopped early: their final flow comes back from the other buffer
-        const size_t bytes = (size_t)c->plane * sizeof(float);
-        for (int i = 0; i < c->N; i++) {
-            if (!c->pair_res[(size_t)i].in_both) continue;
-            const long long o = (long long)i * c->plane;
-            HS_HIP(c, hipMemcpyAsync(c->dU[b] + o, c->dU[a] + o, bytes, hipMemcpyDeviceToDevice, c->stream));
-            HS_HIP(c, hipMemcpyAsync(c->dV[b] + o, c->dV[a] + o, bytes, hipMemcpyDeviceToDevice, c->stream));
-        }
+        for (int i = 0; i < c->N; i++)
+            if (c->pair_res[(size_t)i].in_both) HS_HIP(c, copy_pair_flow(c, c->dU[b], c->dV[b], c->dU[a], c->dV[a], i));
         HS_HIP(c, hipStreamSynchronize(c->stream));
         for (int i = 0; i < c->N; i++) {
             hsflow_ctx::PairResult &r = c->pair_res[(size_t)i];
@@ -407,7 +393,7 @@ int measure_last_eps(hsflow_ctx *c)
         pairs_to_info(c);
         return HSFLOW_OK;
     }
-    if ((st = eps_collect_enqueue(c, EpsLayout{2, stride, 0, 0, stride}))) return st; // (resets epsPtr / epsStride)
+    if ((st = eps_collect_enqueue(c, EpsLayout{2, stride, 0, 0, stride}))) return st;
     HS_HIP(c, hipStreamSynchronize(c->stream));
     float last = 0.f;
     std::memcpy(&last, &c->hEps[1], sizeof(float));
@@ -531,7 +517,7 @@ int solve_classic(hsflow_ctx *c, const hsflow_params &p, bool async)
     Profiler prof{c, p.profile != 0};
     const dim3 block(64, 4);
     auto grid = [&](int pairs) { return dim3((c->W + 255) / 256, (c->H + 3) / 4, pairs); }; // for_pair_batches
-    const bool do_deriv = !(p.reuse_derivatives && c->coef_valid && c->coef_mode == HSFLOW_MODE_CLASSIC);
+    const bool do_deriv = needs_deriv(c, p, HSFLOW_MODE_CLASSIC);
     const float a2 = p.alpha * p.alpha; // Kernels.cl:85
     const bool write_v = p.mode != HSFLOW_MODE_CLASSIC_AS_SHIPPED;
     const bool zero0 = !p.use_previous;
@@ -600,7 +586,7 @@ int solve_classic(hsflow_ctx *c, const hsflow_params &p, bool async)
     int launches = 0;
     if (p.use_graph) {
         GraphKey key{p.mode, kernel, p.max_iter, T, i.tile_w, i.tile_h, i.threads, i.groups_per_thread, zero0 ? 0 : c->cur,
-                     p.use_previous * 2 + (do_deriv ? 1 : 0) + (do_unpack ? 4 : 0), p.alpha};
+                     p.use_previous * kKeyUsePrev + (do_deriv ? kKeyDeriv : 0) + (do_unpack ? kKeyUnpack : 0), p.alpha};
         if ((st = run_captured(c, key, enqueue, &launches))) return st;
     } else if ((st = enqueue(&launches))) return st;
     c->coef_valid = true;
@@ -626,7 +612,7 @@ int solve_fixed(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Prof
     if (rem && !make_jplan(c, S.kernel, rem, p, tail))
         return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the tail launch");
     const bool zero = !p.use_previous;
-    const bool do_deriv = !(p.reuse_derivatives && c->coef_valid && c->coef_mode == HSFLOW_MODE_CV);
+    const bool do_deriv = needs_deriv(c, p, HSFLOW_MODE_CV);
     c->info.deriv_fused = do_deriv && !p.profile && S.multi && strip_deriv_fusable(c, iters >= T ? S.plan : tail); // enqueue_fixed's rule
     if (S.persist) { // buffers and phase counters: outside any capture
         if ((st = persist_reserve(c)) || (st = persist_prepare_flags(c, S.plan.s.tiles))) return st;
@@ -634,10 +620,13 @@ int solve_fixed(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Prof
     // the frames of hsflow_solve_async_frames_device: read in place by the first launch where that is the strip kernel with
     // the derivative pass, else copied now
     const bool in_place = c->lazy.active && c->info.deriv_fused && !S.persist && (iters >= T ? S.plan : tail).kind == HSFLOW_KERNEL_STRIP;
-    if ((st = resolve_lazy_frames(c, in_place))) return st;
+    hsflow_ctx::FrameRef frames;
+    if ((st = resolve_lazy_frames(c, in_place, &frames))) return st;
+    LaunchIo io = default_io(c);
+    if (in_place) io.frames = &frames;
     int part = 0;
     auto enqueue = [&](int *n) -> int {
-        const int e = enqueue_fixed(c, p, S.coeff, iters, S.kernel, T, &S.plan, &tail, prof, do_deriv, zero, S.persist, part);
+        const int e = enqueue_fixed(c, p, S.coeff, iters, S.kernel, T, &S.plan, &tail, prof, io, do_deriv, zero, S.persist, part);
         *n = c->info.jacobi_launches;
         return e;
     };
@@ -645,24 +634,20 @@ int solve_fixed(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Prof
     if (p.use_graph && !p.profile && in_place) {
         // that launch carries this submission's pointers: issued by itself; the cached graph holds the launches after it
         GraphKey key{p.mode, S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
-                     c->info.groups_per_thread, zero ? 0 : c->cur, p.use_previous * 2 + (do_deriv ? 1 : 0) + 16, S.coeff};
+                     c->info.groups_per_thread, zero ? 0 : c->cur, p.use_previous * kKeyUsePrev + (do_deriv ? kKeyDeriv : 0) + kKeyInPlace, S.coeff};
         part = 1;
-        st = enqueue(&n);
-        c->src.active = false;
-        if (st) return st;
+        if ((st = enqueue(&n))) return st;
         part = 2;
         if (iters > T && (st = run_captured(c, key, enqueue, &n))) return st;
         c->info.jacobi_launches = n;
     } else if (p.use_graph && !p.profile) {
         GraphKey key{p.mode, S.persist ? HSFLOW_KERNEL_PERSIST : S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
-                     c->info.groups_per_thread, zero ? 0 : c->cur, p.use_previous * 2 + (do_deriv ? 1 : 0), S.coeff};
+                     c->info.groups_per_thread, zero ? 0 : c->cur, p.use_previous * kKeyUsePrev + (do_deriv ? kKeyDeriv : 0), S.coeff};
         if ((st = run_captured(c, key, enqueue, &n))) return st;
         c->info.jacobi_launches = n;
     } else {
         if (S.persist && (st = configure_persist(c, S.plan.s, EpsMode::None, c->info.deriv_fused != 0, S.coeff))) return st;
-        st = enqueue(&n);
-        c->src.active = false;
-        if (st) return st;
+        if ((st = enqueue(&n))) return st;
     }
     c->coef_valid = true;
     c->coef_mode = HSFLOW_MODE_CV;
@@ -721,7 +706,7 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
     const int iters = (int)S.budget, T = S.T, cur0 = c->cur;
     const JPlan &plan = S.plan;
     int st = HSFLOW_OK;
-    c->epsThr = witness_threshold(p.epsilon);
+    const float thr = witness_threshold(p.epsilon);
     const bool persist = S.persist && async; // (prepare_solve grants it to asynchronous solves only)
     const int n_launch = (iters + T - 1) / T; // persist: phases of the one launch; the witness words are laid out alike
     const JPlan &lastp = iters % T ? tailp : plan;
@@ -738,14 +723,14 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
     // the frames of hsflow_solve_async_frames_device: read in place by the first launch where that is the strip kernel with
     // the derivative pass, else copied now
     const bool in_place = c->lazy.active && fuse_deriv && !persist && firstp.kind == HSFLOW_KERNEL_STRIP;
-    if ((st = resolve_lazy_frames(c, in_place))) return st;
+    hsflow_ctx::FrameRef frames;
+    if ((st = resolve_lazy_frames(c, in_place, &frames))) return st;
     // the whole pass as one enqueue sequence (nothing allocated, nothing synchronised: capturable).  part: 0 all of it; 1 up
     // to and including the first Jacobi launch; 2 what follows it (c->cur as part 1 left it) -- a first launch that reads
     // the caller's frames carries this submission's pointers, so it goes out by itself and the cached graph holds the rest
     int part = 0;
     auto enqueue = [&](int *n) -> int {
         if (part != 2 && p.use_previous && (st = save_start(c))) return st;
-        c->epsStride = stride; // (no clearing: every launch writes all its words, the reduction reads only those)
         if (part != 2 && do_deriv && !fuse_deriv) {
             prof.begin(0);
             HS_HIP(c, launch_deriv(c));
@@ -753,18 +738,20 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
         }
         const int zero_w = p.use_previous ? 0 : 1;
         if (zero_w && part != 2) c->cur = 0;
+        // launch (phase) L writes row L of the witness words (no clearing: every launch writes all its words, the reduction
+        // reads only those)
         if (persist) { // one launch, a row of witness words per phase
-            c->epsPtr = c->dEpsTiles;
             prof.begin(1);
-            const int e = enqueue_persist(c, plan.s, iters, EpsMode::Witness, fuse_deriv, zero_w, S.coeff);
+            const int e = enqueue_persist(c, plan.s, iters, EpsMode::Witness, LaunchIo{c->dEpsTiles, stride, thr}, fuse_deriv, zero_w, S.coeff);
             prof.end();
             if (e) return e;
         } else for (int L = part == 2 ? 1 : 0; L < (part == 1 ? 1 : n_launch); L++) {
             const bool is_last = L == n_launch - 1;
             const int a = c->cur, b = a ^ 1;
-            c->epsPtr = c->dEpsTiles + (size_t)L * stride;
+            LaunchIo io{c->dEpsTiles + (size_t)L * stride, stride, thr};
+            if (L == 0 && in_place) io.frames = &frames;
             prof.begin(1);
-            hipError_t e = launch_j(c, is_last ? lastp : plan, is_last ? last_mode : EpsMode::Witness, c->dU[a], c->dV[a], c->dU[b],
+            hipError_t e = launch_j(c, is_last ? lastp : plan, is_last ? last_mode : EpsMode::Witness, io, c->dU[a], c->dV[a], c->dU[b],
                                     c->dV[b], S.coeff, L == 0 ? zero_w : 0, L == 0 && fuse_deriv);
             prof.end();
             HS_HIP(c, e);
@@ -772,11 +759,7 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
         }
         *n = persist ? 1 : n_launch;
         if (part == 1) return HSFLOW_OK;
-        if (async && !c->async_reduce) { // the reduction of the witness words waits until somebody settles the check (settle_pending)
-            c->epsPtr = c->dEps;
-            c->epsStride = 1;
-            return HSFLOW_OK;
-        }
+        if (async && !c->async_reduce) return HSFLOW_OK; // the reduction of the witness words waits until somebody settles the check (settle_pending)
         // (an asynchronous solve gets here only with the in-stream reduction on: its last workgroup writes the marker too)
         return eps_collect_enqueue(c, words, async && c->hMark != nullptr);
     };
@@ -784,24 +767,18 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
     if (p.use_graph && !p.profile && !(in_place && n_launch == 1)) {
         GraphKey key{p.mode, persist ? HSFLOW_KERNEL_PERSIST : S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
                      c->info.groups_per_thread, p.use_previous ? c->cur : 0,
-                     p.use_previous * 2 + (do_deriv ? 1 : 0) + (async ? 4 : 0) + (async && c->async_reduce ? 8 : 0) + (in_place ? 16 : 0) +
-                         (per_pair ? 32 : 0),
-                     S.coeff, c->epsThr};
+                     p.use_previous * kKeyUsePrev + (do_deriv ? kKeyDeriv : 0) + (async ? kKeyAsync : 0) +
+                         (async && c->async_reduce ? kKeyAsyncReduce : 0) + (in_place ? kKeyInPlace : 0) + (per_pair ? kKeyPerPair : 0),
+                     S.coeff, thr};
         if (in_place) {
             part = 1;
-            st = enqueue(launches);
-            c->src.active = false;
-            if (st) return st;
+            if ((st = enqueue(launches))) return st;
             part = 2;
         }
         if ((st = run_captured(c, key, enqueue, launches))) return st;
-        c->epsPtr = c->dEps; // (a replay ran none of the sequence's host side)
-        c->epsStride = 1;
     } else {
         if (persist && (st = configure_persist(c, plan.s, EpsMode::Witness, fuse_deriv, S.coeff))) return st;
-        st = enqueue(launches);
-        c->src.active = false;
-        if (st) return st;
+        if ((st = enqueue(launches))) return st;
     }
     c->coef_valid = true;
     c->coef_mode = HSFLOW_MODE_CV;
@@ -812,7 +789,7 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
     if (async) { // the check is owed: hsflow_synchronize (or the next call that needs results) settles it
         // what measure_last_eps needs: the last launch again (persist: the last phase as an ordinary launch, from the third buffer)
         const int zero_in = (n_launch == 1 && !p.use_previous && !persist) ? 1 : 0; // a single launch from zero flow
-        c->lastl = hsflow_ctx::LastLaunch{true, lastp, zero_in, S.coeff, c->epsThr, persist};
+        c->lastl = hsflow_ctx::LastLaunch{true, lastp, zero_in, S.coeff, thr, persist};
         c->pend.active = true;
         c->pend.params = p;
         c->pend.iters = iters; c->pend.launches = *launches; c->pend.cur0 = cur0;
@@ -843,8 +820,8 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
 }
 
 // The exact pass of ITER|EPS: every sweep records its Eps on the device (one row of `stride` words per sweep, reserved
-// and cleared by the caller); one read-back at the end finds the first sweep k with Eps_k < epsilon.  If there is none
-// the result stands; otherwise exactly k sweeps are re-run from the saved starting flow, which reproduces the oracle's
+// and cleared by the caller, solve_iter_eps); one read-back at the end finds the first sweep k with Eps_k < epsilon.  If
+// there is none the result stands; otherwise exactly k sweeps are re-run from the saved starting flow, which reproduces the oracle's
 // stopping sweep.  launches: those of a witness pass that proved nothing, which this pass then follows.
 int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int stride, Profiler &prof, int launches)
 {
@@ -854,7 +831,6 @@ int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int s
     if (c->probe_pairs && c->N > 1 && (st = eps_reserve(c, iters, stride, (size_t)iters * c->N))) return st;
     const bool strip_words = S.kernel == HSFLOW_KERNEL_STRIP || S.kernel == HSFLOW_KERNEL_FOLD;
     const bool pair_words = c->probe_pairs && c->N > 1 && !strip_words; // (stride = N: solve_iter_eps)
-    c->epsPair = pair_words ? 1 : 0;
     if (zero_in) c->cur = 0;
     while (done < iters) {
         const int chunk = S.multi ? std::min(T, iters - done) : 1;
@@ -863,23 +839,20 @@ int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int s
             return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
         if (S.multi && chunk != T) tail_tiles = plan_eps_stride(S.kernel, cp);
         const int a = c->cur, b = a ^ 1;
-        c->epsPtr = c->dEpsTiles + (size_t)done * stride;
-        if (pair_words) c->epsStride = stride;
+        const LaunchIo io{c->dEpsTiles + (size_t)done * stride, stride, 0.f, pair_words ? 1 : 0};
         prof.begin(1);
-        hipError_t e = S.multi ? launch_j(c, cp, EpsMode::EverySweep, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff, zero_in)
-                               : launch_simple(c, true, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff, zero_in);
+        hipError_t e = S.multi ? launch_j(c, cp, EpsMode::EverySweep, io, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff, zero_in)
+                               : launch_simple(c, true, io, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff, zero_in);
         prof.end();
-        if (e != hipSuccess) c->epsPair = 0;
         HS_HIP(c, e);
         c->cur = b;
         zero_in = 0;
         done += chunk;
         launches++;
     }
-    c->epsPair = 0;
     c->sweeps_run += iters;
     std::vector<unsigned> heps;
-    if ((st = eps_collect(c, iters, heps))) return st;
+    if ((st = eps_collect(c, iters, stride, heps))) return st;
     c->sweep_eps.resize((size_t)iters); // (hsflow_solve_probe hands these out)
     std::memcpy(c->sweep_eps.data(), heps.data(), (size_t)iters * sizeof(float));
     if (pair_words) { // the rows ARE per pair (the batch's Eps above is their maximum, by k_eps_reduce over N words a row)
@@ -906,7 +879,7 @@ int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int s
             if (!make_jplan(c, S.kernel, Tk, p, kp)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the re-run");
             if (k % Tk && !make_jplan(c, S.kernel, k % Tk, p, kt)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the re-run tail");
         }
-        st = enqueue_fixed(c, p, S.coeff, k, S.kernel, Tk, &kp, &kt, prof, false, !p.use_previous);
+        st = enqueue_fixed(c, p, S.coeff, k, S.kernel, Tk, &kp, &kt, prof, default_io(c), false, !p.use_previous);
         if (st) return st;
         launches += c->info.jacobi_launches;
         c->sweeps_run += k;
@@ -946,12 +919,8 @@ int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, P
     const int iters = (int)S.budget, T = S.T, kernel = S.kernel;
     int st = HSFLOW_OK;
     bool witness = (kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD) && !c->force_exact && strip_has_witness(S.plan);
-    const bool do_deriv = !(p.reuse_derivatives && c->coef_valid && c->coef_mode == HSFLOW_MODE_CV);
-    if (p.use_previous) { // the starting flow is kept (save_start)
-        const size_t px = (size_t)c->plane * c->N;
-        if (!c->dUb) HS_HIP(c, hipMalloc((void **)&c->dUb, px * sizeof(float)));
-        if (!c->dVb) HS_HIP(c, hipMalloc((void **)&c->dVb, px * sizeof(float)));
-    }
+    const bool do_deriv = needs_deriv(c, p, HSFLOW_MODE_CV);
+    if (p.use_previous && (st = reserve_start_backup(c))) return st; // the starting flow is kept (save_start)
     // every launch of this solve uses the same number of workgroups or fewer (tail): stride = max
     int stride = S.multi ? plan_eps_stride(kernel, S.plan) : 1;
     // hsflow_solve_probe_pairs on the simple / LDS-tile kernel: one word per (sweep, pair) instead of one per sweep
@@ -1018,7 +987,7 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
         HS_HIP(c, hipMemsetAsync(c->dU[0], 0, (size_t)c->plane * c->N * sizeof(float), c->stream));
         HS_HIP(c, hipMemsetAsync(c->dV[0], 0, (size_t)c->plane * c->N * sizeof(float), c->stream));
     }
-    if (!(p.reuse_derivatives && c->coef_valid && c->coef_mode == HSFLOW_MODE_CV)) {
+    if (needs_deriv(c, p, HSFLOW_MODE_CV)) {
         prof.begin(0);
         HS_HIP(c, launch_deriv(c));
         prof.end();
@@ -1029,13 +998,7 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
     int launches = 0;
     float last = 0.f;
     bool stop = false;
-    // Without a sweep budget the only exit is Eps < epsilon.  A positive epsilon below the fp32 limit cycle of
-    // the iteration (Eps stalls around 1e-7 * |flow|) would keep the host launching for ever -- the original
-    // does exactly that; here the solve gives up with HSFLOW_E_NOTERM (flow, iterations_done and last_eps
-    // stay valid) once Eps has not reached a new minimum for kStallSweeps sweeps or after kMaxSweeps.
-    constexpr long long kStallSweeps = 4096, kMaxSweeps = 1LL << 24;
-    float best_eps = INFINITY;
-    long long best_at = 0;
+    StallWatch stall; // (without a sweep budget the only other exit is Eps < epsilon)
     bool stalled = false;
     while (!stop) {
         const int chunk = (int)std::min<long long>(T, budget - done);
@@ -1044,30 +1007,31 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
             return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
         const int a = c->cur, b = a ^ 1;
         const int n = multi ? chunk : 1;
-        if ((st = eps_prepare(c, n, multi ? plan_eps_stride(kernel, cp) : 1))) return st;
-        c->epsPtr = c->dEpsTiles;
+        const int stride = multi ? plan_eps_stride(kernel, cp) : 1;
+        if ((st = eps_prepare(c, n, stride))) return st;
+        const LaunchIo io{c->dEpsTiles, stride};
         prof.begin(1);
         if (!multi)
-            HS_HIP(c, launch_simple(c, true, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
+            HS_HIP(c, launch_simple(c, true, io, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
         else
-            HS_HIP(c, launch_j(c, cp, EpsMode::EverySweep, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
+            HS_HIP(c, launch_j(c, cp, EpsMode::EverySweep, io, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
         prof.end();
         launches++;
         c->sweeps_run += n;
         std::vector<unsigned> heps;
-        if ((st = eps_collect(c, n, heps))) return st;
+        if ((st = eps_collect(c, n, stride, heps))) return st;
         const int hit = first_eps_hit(heps.data(), n, p.epsilon, &last);
         for (int s = 0; s < n && hit < 0; s++) { // (the stall rule)
             float e;
             std::memcpy(&e, &heps[(size_t)s], sizeof(float));
-            if (e < best_eps) { best_eps = e; best_at = done + s; }
+            stall.seen(e, done + s);
         }
         if (hit >= 0 && hit < n - 1) { // crossed inside the chunk: redo exactly hit+1 sweeps
             JPlan rp;
             if (!make_jplan(c, kernel, hit + 1, p, rp))
                 return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the replay");
             prof.begin(1);
-            HS_HIP(c, launch_j(c, rp, EpsMode::None, c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
+            HS_HIP(c, launch_j(c, rp, EpsMode::None, default_io(c), c->dU[a], c->dV[a], c->dU[b], c->dV[b], S.coeff));
             prof.end();
             launches++;
             c->sweeps_run += hit + 1;
@@ -1079,7 +1043,7 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
         }
         c->cur = b;
         if (S.use_iter && p.max_iter > 0 && done >= budget) stop = true;
-        if (!stop && budget > kMaxSweeps && (done - best_at >= kStallSweeps || done >= kMaxSweeps)) stop = stalled = true;
+        if (!stop && stall.give_up(done, budget)) stop = stalled = true;
     }
     HS_HIP(c, hipStreamSynchronize(c->stream));
     c->info.iterations_done = (int)std::min<long long>(done, INT32_MAX);
@@ -1298,7 +1262,7 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
     constexpr long long kSpecMax = 1 << 16; // speculative ITER|EPS: the whole budget in one go
     if (S.use_iter && p.max_iter > 0 && S.budget <= kSpecMax) return solve_iter_eps(c, S.eff, S, prof, async);
     if (stops_per_pair(c)) // (no budget to speculate on: every pair through its own chunk loop, stall rule included)
-        return solve_pairs_all(c, S.eff, S, !(p.reuse_derivatives && c->coef_valid && c->coef_mode == HSFLOW_MODE_CV));
+        return solve_pairs_all(c, S.eff, S, needs_deriv(c, p, HSFLOW_MODE_CV));
     if ((st = resolve_lazy_frames(c, false))) return st;
     return solve_eps_chunks(c, S.eff, S, prof);
 }

@@ -123,7 +123,6 @@ int verify_reserve(hsflow_ctx *c)
         return fail(c, e == hipErrorOutOfMemory ? HSFLOW_E_OOM : HSFLOW_E_DEVICE,
                     std::string("hsflow_verify: scratch for the reference pass: ") + hipGetErrorString(e));
     }
-    s->epsPtr = s->dEps;
     s->frames_set = true;
     c->shadow = s;
     return HSFLOW_OK;

@@ -148,7 +148,6 @@ int hsflow_create(hsflow_ctx **out, int device, int width, int height, int n_pai
         HS_TRY(hipMalloc((void **)&c->dV[i], px * sizeof(float)));
     }
     HS_TRY(hipMalloc((void **)&c->dEps, kMaxFuse * sizeof(unsigned)));
-    c->epsPtr = c->dEps;
     HS_TRY(hipMalloc((void **)&c->dZero, ((size_t)c->P + 64) * sizeof(float)));
     {
         int ncu = 0;
@@ -566,7 +565,6 @@ int hsflow_solve_async_frames_device(hsflow_ctx *c, const void *dprev, size_t ps
     c->frames_set = true;
     c->coef_valid = false;
     st = note_solve(c, p, solve_impl(c, p, true));
-    c->src.active = false;
     const int st2 = resolve_lazy_frames(c, false);
     return st ? st : st2;
 }

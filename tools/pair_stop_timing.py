@@ -4,7 +4,8 @@
 16 pairs of 600x480 in one context, lambda 0.1, ITER|EPS with epsilon 1e-6, 100 sweeps, asynchronous graph solves:
   (a) 16 translating pairs -- nothing stops: a parent build of the library (--parent, optional), this build with the
       switch off, this build with the switch on;
-  (b) 12 pairs of identical frames (they stop after sweep 1) + 4 translating pairs: switch off and on.
+  (b) 12 pairs of identical frames (they stop after sweep 1) + 4 translating pairs: switch off and on, and the parent
+      build with the switch on where it has one.
 Two figures per case, in ms per solve of the whole batch, five blocks each, the cases taking turns inside every block:
   stream   300 solves enqueued back to back (each takes the owed check of the one before over), one synchronize;
   settled  100 solves, each followed by synchronize -- the early-stop check settled every time: the re-runs of (b).
@@ -82,7 +83,7 @@ class Case(object):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--parent", help="libhsflow.so of the parent commit (case (a) only)")
+    ap.add_argument("--parent", help="libhsflow.so of the parent commit: case (a), and (b) with the switch on if it has the switch")
     ap.add_argument("--blocks", type=int, default=5)
     args = ap.parse_args()
     import torch
@@ -93,10 +94,13 @@ def main():
     mixed = still + moving[12:]
     this = open_lib(hs._lib.LIB_PATH)
     cases = []
-    if args.parent:
-        cases.append(Case("(a) parent", open_lib(args.parent), moving, False))
+    parent = open_lib(args.parent) if args.parent else None
+    if parent:
+        cases.append(Case("(a) parent", parent, moving, False))
     cases += [Case("(a) switch off", this, moving, False), Case("(a) switch on", this, moving, True),
               Case("(b) switch off", this, mixed, False), Case("(b) switch on", this, mixed, True)]
+    if parent and hasattr(parent, "hsflow_set_pair_termination"):
+        cases.insert(-1, Case("(b) parent on", parent, mixed, True))
     for c in cases:   # warm-up: every shape, the graph capture, the clocks
         c.run_stream(100)
         c.run_settled(20)
