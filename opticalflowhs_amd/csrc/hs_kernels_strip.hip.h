@@ -4,29 +4,16 @@
 #include <type_traits>
 
 // Last sweep of a launch as a second copy of the sweep code after the loop (the loop then publishes and
-// meets the barrier unconditionally).  Folded kernel: far fewer spills (R = 4: 33 -> 7, R = 5: 33 -> 1) and
-// 15 VGPRs less at R = 3; strip kernel: slightly worse (R = 5 / 16 wavefronts: 2 -> 11 spills), so not there.
+// meets the barrier unconditionally), in both kernels (run_sweeps).  Folded kernel: far fewer spills (R = 4: 33 -> 7,
+// R = 5: 33 -> 1) and 15 VGPRs less at R = 3, and with two sweeps per loop trip the register copies at the loop's back
+// edge halve (profiles/r01_fold_peel_ab.txt, r01_fold_unroll2_ab.txt); strip kernel: the compiler ended every loop trip
+// with 44 - 64 register copies until the last sweep was peeled out of the loop, after which 4 remain.
 // Scaled state: inside a launch the flow is carried as 4^k * u after k sweeps, so that the neighbour SUM is
 // the average at the next scale and the multiplication by 0.25 disappears (the constant term ga is rescaled
 // instead: one packed multiply per pair of pixels where there were two).  Powers of 4 commute with every
 // rounding, so the result is bit-identical to the canonical arithmetic of update_cv<> -- except for values that
 // would be denormal there (below 1.2e-38), which keep their bits here.  T <= 24: 4^24 = 2.8e14, no overflow for
 // any flow a valid lambda allows.
-#ifndef HS_SCALED
-#define HS_SCALED 1
-#endif
-#ifndef HS_UNROLL2_FOLD
-#define HS_UNROLL2_FOLD 1
-#endif
-#ifndef HS_PEEL_LAST_STRIP
-#define HS_PEEL_LAST_STRIP 1
-#endif
-#ifndef HS_PEEL_LAST_FOLD
-#define HS_PEEL_LAST_FOLD 1
-#endif
-#ifndef HS_CORE_PRIO /* s_setprio for the wavefronts that are busy in every sweep (0: off); 1: -0.3 % one context, -0.7 % in the stream */
-#define HS_CORE_PRIO 1
-#endif
 #ifndef HS_SWEEP_STAMPS
 #define HS_SWEEP_STAMPS 0
 #endif
@@ -146,14 +133,9 @@ __device__ __forceinline__ int hs_lane_now()
 
 __device__ __forceinline__ f2 f2_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f2 f2_swap(f2 a) { return __builtin_shufflevector(a, a, 1, 0); }
-// old - new of a sweep, in the NEW value's scale (HS_SCALED: the old one is a factor 4 behind)
-#if HS_SCALED
-#define HS_DIFF(o, n) f2_fma((o), f2{4.0f, 4.0f}, -(n))
-#define HS_DIFF1(o, n) fmaf(4.0f, (o), -(n))
-#else
-#define HS_DIFF(o, n) ((o) - (n))
-#define HS_DIFF1(o, n) ((o) - (n))
-#endif
+// old - new of a sweep, in the NEW value's scale (scaled state: the old one is a factor 4 behind)
+__device__ __forceinline__ f2 sweep_diff(f2 o, f2 n) { return f2_fma(o, f2{4.0f, 4.0f}, -n); }
+__device__ __forceinline__ float sweep_diff(float o, float n) { return fmaf(4.0f, o, -n); }
 
 // One row of one lane: pixels (p0,p3) = P and (p1,p2) = Q as two register pairs (p0 is an even image column: the
 // region starts at a multiple of 4), so that all arithmetic is packed (2 pixels per v_pk_add/mul/fma_f32; cross_rows).
@@ -198,35 +180,28 @@ __device__ __forceinline__ void cross_rows(Cross &s, const f2 cuP, const f2 cuQ,
 }
 
 // One row: neighbour sums from the cross sums below (sc) and above (sp) it, then the update in place.
-// E = parity of the row's p0.  HS_SCALED: the sums ARE the averages at the next scale (file header).
+// E = parity of the row's p0.  Scaled state: the sums ARE the averages at the next scale (file header).
 template <int E>
 __device__ __forceinline__ void strip_row_update(f2 &uP, f2 &uQ, f2 &vP, f2 &vQ, const Cross &sc, const Cross &sp, RowCoef &c)
 {
-    f2 tP, tQ, sP, sQ;
+    f2 ubP, ubQ, vbP, vbQ; // 4^(k+1) * average
     if (E == 0) {
-        tQ = pk_add_swapped(sc.uQ, sp.uQ);
-        tP.x = sc.uP.x + wave_from_prev_lane(sp.uP.y); tP.y = sc.uP.y + wave_from_next_lane(sp.uP.x);
-        sQ = pk_add_swapped(sc.vQ, sp.vQ);
-        sP.x = sc.vP.x + wave_from_prev_lane(sp.vP.y); sP.y = sc.vP.y + wave_from_next_lane(sp.vP.x);
+        ubQ = pk_add_swapped(sc.uQ, sp.uQ);
+        ubP.x = sc.uP.x + wave_from_prev_lane(sp.uP.y); ubP.y = sc.uP.y + wave_from_next_lane(sp.uP.x);
+        vbQ = pk_add_swapped(sc.vQ, sp.vQ);
+        vbP.x = sc.vP.x + wave_from_prev_lane(sp.vP.y); vbP.y = sc.vP.y + wave_from_next_lane(sp.vP.x);
     } else {
-        tP = sc.uP + sp.uQ; tQ = sc.uQ + sp.uP;
-        sP = sc.vP + sp.vQ; sQ = sc.vQ + sp.vP;
+        ubP = sc.uP + sp.uQ; ubQ = sc.uQ + sp.uP;
+        vbP = sc.vP + sp.vQ; vbQ = sc.vQ + sp.vP;
     }
-#if HS_SCALED
-    const f2 ubP = tP, ubQ = tQ, vbP = sP, vbQ = sQ; // 4^(k+1) * average
-#else
-    const f2 ubP = tP * 0.25f, ubQ = tQ * 0.25f, vbP = sP * 0.25f, vbQ = sQ * 0.25f;
-#endif
     const f2 qP = f2_fma(c.alP, ubP, f2_fma(c.beP, vbP, c.gaP));
     const f2 qQ = f2_fma(c.alQ, ubQ, f2_fma(c.beQ, vbQ, c.gaQ));
     uP = f2_fma(-c.alP, qP, ubP);
     vP = f2_fma(-c.beP, qP, vbP);
     uQ = f2_fma(-c.alQ, qQ, ubQ);
     vQ = f2_fma(-c.beQ, qQ, vbQ);
-#if HS_SCALED
     c.gaP *= 4.0f; // the constant term at the next sweep's scale
     c.gaQ *= 4.0f;
-#endif
 }
 
 // The packed derivative words of a lane's R rows straight from the two frames (DERIV launches: the first
@@ -259,6 +234,8 @@ __device__ __forceinline__ void strip_derive(const uint8_t *__restrict__ fA, con
     // How this lane reads its four columns of a frame row: 0 an aligned word (group inside the image), 1 an
     // aligned word read backwards (group wholly mirrored: left of the image, or right of it when W % 4 == 0),
     // 2 four reflected bytes (W % 4 != 0: the group that straddles column W-1 and those right of it).
+    // (column_rule, below, states the same rule for the flow and coefficient loads: mode 1 is its rev, mode 2 its slow.
+    // Whether strip_derive compiles the same with it has not been tried; the rule stays written out here.)
     const int mode = xin ? 0 : ((x0 < 0 || (g.W & 3) == 0) ? 1 : 2);
     int xg = x0, xb[4] = {0, 0, 0, 0};
     unsigned flipx = 0; // pixels of the group that are mirrored columns: their Ix changes sign
@@ -341,6 +318,344 @@ __device__ __forceinline__ void strip_derive(const uint8_t *__restrict__ fA, con
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// What k_jacobi_strip and k_jacobi_fold share: everything around the sweep.  A kernel family owns its row mapping (which
+// image row a register row holds, handed to the helpers below as a callable), its exchange of edge rows and its sweep;
+// the strip kernel owns the persistent phases as well.
+// ------------------------------------------------------------------------------------------
+
+// Workgroup -> tile (XCD-contiguous), the slot of pairs it belongs to and that slot's pair, the tile's place in the
+// pair's grid.  LISTED: the launch may carry a pair list (StripGeom::pair_list); SCALAR: the pair is kept in a scalar register.
+struct TileId { int tile, slot, pair, bx, by; };
+template <bool LISTED, bool SCALAR>
+__device__ __forceinline__ TileId tile_decode(const StripGeom &g)
+{
+    const int tpp = g.tiles_x * g.tiles_y;
+    const int tile = xcd_contiguous_tile(blockIdx.x, gridDim.x);
+    const int slot = tile / tpp;
+    const int t2 = tile - slot * tpp;
+    int pair = slot;
+    if constexpr (LISTED) {
+        if (g.pair_list) pair = g.pair_list[slot];
+    }
+    if constexpr (SCALAR) pair = __builtin_amdgcn_readfirstlane(pair);
+    const int by = t2 / g.tiles_x, bx = t2 - by * g.tiles_x;
+    return TileId{tile, slot, pair, bx, by};
+}
+
+// Core membership (for the stores and for Eps) and the trapezoid.  j: row of the region, y: its image row; xl: the lane's
+// first column within the region, x0: its image column; T, CH, H: StripGeom's.
+// (The forms are what the register allocator of the R = 4 / 5 kernels tolerates.  row_in_core: the rule is the macro, and
+// a change to it is one edit; its uses are strip_body (two) and fold_body.  As the condition of the caller's `if` it
+// compiles like the parent's code everywhere but in the strip kernel's DERIV launches, where the R = 5 kernels gain a
+// spill: those, and only those, take it as the function's value.  (The value everywhere else costs
+// k_jacobi_strip<5, 1024, 0, 0> two branches per sweep and moves 30 of the 36 k_jacobi_fold_deriv kernels by 1 - 8
+// registers.)  row_dist takes the numbers: with the geometry by reference the same R = 5 _deriv kernels gain a spill.)
+#define HS_ROW_IN_CORE(j, y, T, CH, H) ((j) >= (T) && (j) < (T) + (CH) && (y) >= 0 && (y) < (H))
+__device__ __forceinline__ bool row_in_core(const int j, const int y, const int T, const int CH, const int H)
+{
+    return HS_ROW_IN_CORE(j, y, T, CH, H);
+}
+__device__ __forceinline__ int row_dist(const int j, const int T, const int CH) // distance from the core rows (0 inside)
+{
+    return j < T ? T - j : (j >= T + CH ? j - (T + CH - 1) : 0);
+}
+__device__ __forceinline__ bool lane_in_core(const int x0, const int xl, const StripGeom &g)
+{
+    return (x0 >= 0) && (x0 < g.W) && (xl >= g.HX) && (xl < g.HX + g.CW);
+}
+
+// Where does a lane read its four columns x0 .. x0+3?  Inside the image: at x0.  A group that lies completely outside the
+// image on the left mirrors onto an aligned group read backwards (columns -1-k <-> k); the same holds on the right when
+// W % 4 == 0: those lanes keep the 16-byte loads (from the mirrored address xg, components reversed afterwards: rev).
+// Only groups that straddle column W-1 or sit right of it when W % 4 != 0 (and images narrower than the halo) need four
+// reflected scalar loads per plane (slow).  side: the region sticks out of the image (workgroup-uniform), inside: the
+// group lies wholly inside the image; only a group outside -- side && !inside -- is anything but plain.
+// (Two flags in, not their conjunction, and ints out: the conjunction as a value costs k_jacobi_strip<5, 1024, 3, 0> a
+// spill, and a struct of 8 bytes is returned as one word, out of which bool flags come as lane values, not as masks.)
+__device__ __forceinline__ bool group_inside(const int x0, const int W) { return (x0 >= 0) && (x0 + 3 < W); }
+struct ColRule { int xg, rev, slow; };
+__device__ __forceinline__ ColRule column_rule(const int x0, const int W, const bool side, const bool inside)
+{
+    ColRule c{x0, 0, 0};
+    if (side && !inside) {
+        if (x0 < 0 && -x0 <= W) { c.xg = -x0 - 4; c.rev = 1; }
+        else if (x0 >= W && (W & 3) == 0 && 2 * W - x0 - 4 >= 0) { c.xg = 2 * W - x0 - 4; c.rev = 1; }
+        else { c.xg = 0; c.slow = 1; }
+    }
+    return c;
+}
+
+// One row of a lane as loaded -> as swept: the pixels p0..p3 go into the register pairs P = (p0, p3), Q = (p1, p2)
+// (cross_rows); the packed derivative word becomes the three coefficients of the update (sweep_coefs: one v_rsq per
+// pixel), the constant term at the first sweep's scale (scaled state, file header).
+__device__ __forceinline__ void unpack(const float4 u, const float4 v, const uint4 cw, const float ilambda,
+                                       f2 &uP, f2 &uQ, f2 &vP, f2 &vQ, RowCoef &c)
+{
+    constexpr int iPx = 0, iPy = 3, iQx = 1, iQy = 2;
+    const float lu4[4] = {u.x, u.y, u.z, u.w}, lv4[4] = {v.x, v.y, v.z, v.w};
+    uP = f2{lu4[iPx], lu4[iPy]}; uQ = f2{lu4[iQx], lu4[iQy]};
+    vP = f2{lv4[iPx], lv4[iPy]}; vQ = f2{lv4[iQx], lv4[iQy]};
+    float al[4], be[4], ga[4];
+    const uint32_t cc[4] = {cw.x, cw.y, cw.z, cw.w};
+#pragma unroll
+    for (int p = 0; p < 4; p++) sweep_coefs(cc[p], ilambda, al[p], be[p], ga[p]);
+    c.alP = f2{al[iPx], al[iPy]}; c.alQ = f2{al[iQx], al[iQy]};
+    c.beP = f2{be[iPx], be[iPy]}; c.beQ = f2{be[iQx], be[iQy]};
+    c.gaP = f2{ga[iPx], ga[iPy]} * 4.0f; c.gaQ = f2{ga[iQx], ga[iQy]} * 4.0f;
+}
+
+// The load phase (HS_LOAD_PHASE, below, is what the kernels call): load_rows, then (!DERIV) unpack row by row, then
+// for a side tile (workgroup-uniform: the region sticks out of the image on the left or right; the vast majority of
+// tiles do not and load with plain aligned 16-byte accesses only) HS_MIRROR_ROW and load_rows_slow.
+// load_rows: a lane's R rows of flow and coefficients as loaded, from image rows image_row(r) (reflected here) at column xg
+// (column_rule).  ALL rows' loads are issued first and unconditionally -- side tiles then load as fast as interior ones
+// (with a branch per row their loads did not overlap: +5 000 cycles per launch on the two edge tile columns, which every
+// launch then waited for); zero_in: u_in = v_in = one row of zeros (StripGeom), because under a branch per row the
+// compiler waits for each row's two loads before it issues the next row's.  The launch with the derivative pass (DERIV)
+// is nearly always the one that starts from zero flow: it reads no flow then and goes straight to the frames
+// (strip_derive); otherwise ONE branch around all the rows' loads.
+// The rows are unpacked as they arrive, straight behind the loads with no branch in between (a third of the launch's
+// set-up is this arithmetic: behind the side tiles' fix-ups the compiler waits for ALL loads first).  So a mirrored
+// group is fixed after unpacking (HS_MIRROR_ROW).
+template <int R, bool DERIV, class RowOf>
+__device__ __forceinline__ void load_rows(const uint32_t *coef, const float *u_in, const float *v_in, const StripGeom &g,
+                                          const long long base, const int xg, const RowOf image_row,
+                                          float4 (&lu)[R], float4 (&lv)[R], uint4 (&lc)[R])
+{
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const long long off = base + (long long)mirror_index(image_row(r), g.H) * g.P + xg;
+        const long long off_uv = g.zero_in ? (long long)xg : off;
+        lc[r] = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (!DERIV) {
+            lu[r] = *(const float4 *)(u_in + off_uv);
+            lv[r] = *(const float4 *)(v_in + off_uv);
+            lc[r] = *(const uint4 *)(coef + off);
+        } else {
+            lu[r] = lv[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    if constexpr (DERIV) {
+        if (!g.zero_in) {
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const long long off = base + (long long)mirror_index(image_row(r), g.H) * g.P + xg;
+                lu[r] = *(const float4 *)(u_in + off);
+                lv[r] = *(const float4 *)(v_in + off);
+            }
+        }
+    }
+}
+
+// The slow lanes of a side tile (column_rule) fetch their rows as four reflected scalars per plane, and unpack them (!DERIV).
+// Wave-uniform: rare (W % 4 != 0, or an image narrower than the halo).
+template <int R, bool DERIV, class RowOf>
+__device__ __forceinline__ void load_rows_slow(const uint32_t *coef, const float *u_in, const float *v_in, const StripGeom &g,
+                                               const float ilambda, const long long base, const int x0, const bool slow,
+                                               const RowOf image_row, float4 (&lu)[R], float4 (&lv)[R], uint4 (&lc)[R],
+                                               f2 (&uP)[R], f2 (&uQ)[R], f2 (&vP)[R], f2 (&vQ)[R], RowCoef (&cf)[R])
+{
+    if (__builtin_amdgcn_ballot_w64(slow) != 0) {
+        if (slow) {
+            const int xa = mirror_index(x0, g.W), xb = mirror_index(x0 + 1, g.W),
+                      xc = mirror_index(x0 + 2, g.W), xd = mirror_index(x0 + 3, g.W);
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const long long row = base + (long long)mirror_index(image_row(r), g.H) * g.P;
+                {
+                    const float *uv = u_in + (g.zero_in ? 0 : row), *vv = v_in + (g.zero_in ? 0 : row);
+                    lu[r] = make_float4(uv[xa], uv[xb], uv[xc], uv[xd]);
+                    lv[r] = make_float4(vv[xa], vv[xb], vv[xc], vv[xd]);
+                }
+                if constexpr (!DERIV) {
+                    const uint32_t *cv = coef + row;
+                    lc[r] = make_uint4(cv[xa], cv[xb], cv[xc], cv[xd]);
+                    unpack(lu[r], lv[r], lc[r], ilambda, uP[r], uQ[r], vP[r], vQ[r], cf[r]);
+                }
+            }
+        }
+    }
+}
+
+// A mirrored group (column_rule: rev) arrives reversed: (p0, p1, p2, p3) -> (p3, p2, p1, p0).  Unpacked (!DERIV) that is a
+// swap of the halves of every register pair; a DERIV launch has not unpacked yet (the derivative words come in lane order
+// from strip_derive) and turns the flow as loaded.
+// (A macro on purpose: the R = 4 folded and R = 5 strip kernels sit on the register limit, and with these selects in a
+// function of their own -- by reference, by value, per row or for all rows -- the allocator ends up elsewhere: 14 of the 32
+// k_jacobi_fold kernels with R <= 4 change registers or spills, k_jacobi_fold<4, 1024, 2, 1> from 5 to 10 spills.)
+#define HS_MIRROR_ROW(DERIV, rev, lu, lv, uP, uQ, vP, vQ, cf)                                      \
+    do {                                                                                           \
+        if constexpr (DERIV) {                                                                     \
+            if (rev) {                                                                             \
+                lu = make_float4(lu.w, lu.z, lu.y, lu.x);                                          \
+                lv = make_float4(lv.w, lv.z, lv.y, lv.x);                                          \
+            }                                                                                      \
+        } else {                                                                                   \
+            uP = rev ? f2_swap(uP) : uP; uQ = rev ? f2_swap(uQ) : uQ;                              \
+            vP = rev ? f2_swap(vP) : vP; vQ = rev ? f2_swap(vQ) : vQ;                              \
+            cf.alP = rev ? f2_swap(cf.alP) : cf.alP; cf.alQ = rev ? f2_swap(cf.alQ) : cf.alQ;      \
+            cf.beP = rev ? f2_swap(cf.beP) : cf.beP; cf.beQ = rev ? f2_swap(cf.beQ) : cf.beQ;      \
+            cf.gaP = rev ? f2_swap(cf.gaP) : cf.gaP; cf.gaQ = rev ? f2_swap(cf.gaQ) : cf.gaQ;      \
+        }                                                                                          \
+    } while (0)
+
+// The load phase as both kernels run it: the steps above in their one order.  side: the region sticks out of the image
+// (workgroup-uniform), inside: this lane's group lies in the image; lu, lv, lc: the rows as loaded (float4 / uint4 [R]),
+// uP .. cf: the rows as swept.  Taken from the kernel body by name: its arguments coef, u_in, v_in, g and ilambda.
+// (A macro for the reason given at HS_MIRROR_ROW: the steps must meet in the kernel's body.)
+#define HS_LOAD_PHASE(R, DERIV, side, inside, x0, base, image_row, lu, lv, lc, uP, uQ, vP, vQ, cf)                     \
+    do {                                                                                                               \
+        const ColRule col_ = column_rule(x0, g.W, side, inside);                                                       \
+        const bool mirrored_ = col_.rev != 0;                                                                          \
+        load_rows<R, DERIV>(coef, u_in, v_in, g, base, col_.xg, image_row, lu, lv, lc);                                \
+        if constexpr (!DERIV) {                                                                                        \
+            _Pragma("unroll") for (int r = 0; r < R; r++)                                                              \
+                unpack(lu[r], lv[r], lc[r], ilambda, uP[r], uQ[r], vP[r], vQ[r], cf[r]);                               \
+        }                                                                                                              \
+        if (side) {                                                                                                    \
+            _Pragma("unroll") for (int r = 0; r < R; r++)                                                              \
+                HS_MIRROR_ROW(DERIV, mirrored_, lu[r], lv[r], uP[r], uQ[r], vP[r], vQ[r], cf[r]);                      \
+            load_rows_slow<R, DERIV>(coef, u_in, v_in, g, ilambda, base, x0, col_.slow != 0, image_row, lu, lv, lc,    \
+                                     uP, uQ, vP, vQ, cf);                                                              \
+        }                                                                                                              \
+    } while (0)
+
+// A DERIV launch leaves the complete derivative plane behind: the cores tile the image.
+template <int R, class RowOf>
+__device__ __forceinline__ void store_deriv_rows(uint32_t *coef_w, const StripGeom &g, const long long base,
+                                                 const int x0, const unsigned rowcore, const RowOf image_row, const uint4 (&lc)[R])
+{
+#pragma unroll
+    for (int r = 0; r < R; r++)
+        if ((rowcore >> r) & 1u) *(uint4 *)(coef_w + base + (long long)image_row(r) * g.P + x0) = lc[r];
+}
+
+// The launch's result: a core lane's core rows, back at scale 1 (exact).
+// (non-temporal and agent-scope write-through stores were tried here: both slower)
+template <int R, class RowOf>
+__device__ __forceinline__ void store_flow_rows(float *u_out, float *v_out, const StripGeom &g,
+                                                const long long base, const int x0, const unsigned rowcore, const RowOf image_row,
+                                                const f2 (&uP)[R], const f2 (&uQ)[R], const f2 (&vP)[R], const f2 (&vQ)[R])
+{
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if ((rowcore >> r) & 1u) {
+            const long long off = base + (long long)image_row(r) * g.P + x0;
+            const float fin = __builtin_ldexpf(1.0f, -2 * g.T);
+            // P = (p0, p3), Q = (p1, p2)
+            *(float4 *)(u_out + off) = make_float4(uP[r].x * fin, uQ[r].x * fin, uQ[r].y * fin, uP[r].y * fin);
+            *(float4 *)(v_out + off) = make_float4(vP[r].x * fin, vQ[r].x * fin, vQ[r].y * fin, vP[r].y * fin);
+        }
+    }
+}
+
+// The diagnostic stamps of a workgroup (its thread 0, stamps != NULL only); returns the closing stamp.
+__device__ __forceinline__ unsigned long long store_stamps(unsigned long long *stamps, const unsigned long long st0,
+                                                           const unsigned long long sr0, const unsigned long long st1,
+                                                           const unsigned long long st2, const int tile)
+{
+    __builtin_amdgcn_s_waitcnt(0); // stores issued and acknowledged
+    unsigned long long *o = stamps + (size_t)blockIdx.x * 8;
+    o[0] = st0; o[1] = st1; o[2] = st2;
+    const unsigned long long st3 = __builtin_amdgcn_s_memtime();
+    o[3] = st3;
+    o[4] = sr0; o[5] = __builtin_amdgcn_s_memrealtime();
+    o[6] = (unsigned long long)__builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20); // XCC_ID
+    o[7] = (unsigned long long)tile;
+    return st3;
+}
+
+// Eps, the workgroup's part.  eps_lds: 32 floats behind the exchange buffers.  lane_id: the lane number as a callable (the
+// strip kernel's Eps forms read it from the hardware at every use, see there).
+// Wavefront 0 folds up to 16 per-wavefront values and stores the maximum as one word.
+template <class Lane>
+__device__ __forceinline__ void eps_put_max(const float *vals, const int NW, const Lane lane_id, unsigned *word)
+{
+    float x = lane_id() < NW ? vals[lane_id()] : 0.f;
+    x = wave_max_nonneg(x);
+    if (lane_id() == 0) *word = __float_as_uint(x);
+}
+// Behind a measured sweep s: e = the lane's max |new - old| over its core pixels, at the sweep's scale (4^(s+1): scaled
+// state).  EPS == 1: the per-wavefront maximum goes to LDS and wavefront 0 folds the PREVIOUS sweep's values into
+// eps_out[(s-1) * eps_stride + workgroup] (so the sweep's one barrier orders both); EPS == 3: the one measured sweep,
+// folded after the loop (eps_tail).  lane: the lane number as an expression (evaluated at every use).
+// (A macro: this sits inside the sweep loop, and as a function the offsets (s & 1) * 16 and ((s - 1) & 1) * 16 are formed
+// apart from the sweep's own s & 1 -- two to three scalar instructions more per sweep in every k_jacobi_strip<R, ., 1, .>.)
+#define HS_EPS_FOLD_SWEEP(EPS, e, s, w, NW, lane, eps_lds, eps_out, eps_stride)                                        \
+    do {                                                                                                               \
+        const float unscale_ = __builtin_ldexpf(1.0f, -2 * ((s) + 1));                                                 \
+        if (EPS == 3) {                                                                                                \
+            const float e_ = wave_max_nonneg(e) * unscale_;                                                            \
+            if ((lane) == 0) eps_lds[16 + (w)] = e_;                                                                   \
+        }                                                                                                              \
+        if (EPS == 1) {                                                                                                \
+            const float e_ = wave_max_nonneg(e) * unscale_;                                                            \
+            if ((lane) == 0) eps_lds[((s) & 1) * 16 + (w)] = e_;                                                       \
+            if ((s) > 0 && (w) == 0) {                                                                                 \
+                float x_ = (lane) < (NW) ? eps_lds[(((s) - 1) & 1) * 16 + (lane)] : 0.f;                               \
+                x_ = wave_max_nonneg(x_);                                                                              \
+                if ((lane) == 0) eps_out[(size_t)((s) - 1) * (eps_stride) + blockIdx.x] = __float_as_uint(x_);         \
+            }                                                                                                          \
+        }                                                                                                              \
+    } while (0)
+// Behind the T sweeps.  EPS == 1: the last sweep's fold.  EPS == 2 / 3: the witness word wit_out[workgroup] = +inf if
+// the wavefronts vouch for every sweep that ran in witness mode -- seen_n of them each -- and for EPS == 3 the exact
+// second word, Eps of the last sweep.  COUNTS (the strip kernel): the wavefronts hand in their counts; where they took
+// turns (wit_sum) the counts add up to that number, otherwise one wavefront must have all.  !COUNTS (the folded kernel,
+// where every wavefront looks in every sweep): each hands in its own verdict.
+template <int EPS, bool COUNTS, class Lane>
+__device__ __forceinline__ void eps_tail(const int T, const int seen_n, const bool wit_sum, const int w, const int NW, const Lane lane_id,
+                                         float *eps_lds, unsigned *eps_out, unsigned *wit_out, const int eps_stride)
+{
+    if (EPS == 1) {
+        __syncthreads();
+        if (w == 0) eps_put_max(eps_lds + ((T - 1) & 1) * 16, NW, lane_id, eps_out + (size_t)(T - 1) * eps_stride + blockIdx.x);
+    }
+    if (EPS == 2 || EPS == 3) {
+        const int witnessed = EPS == 3 ? T - 1 : T;
+        if (lane_id() == 0) eps_lds[w] = COUNTS ? (float)seen_n : (seen_n == witnessed ? __builtin_inff() : 0.f);
+        __syncthreads();
+        if (w == 0) {
+            const float x = lane_id() < NW ? eps_lds[lane_id()] : 0.f;
+            const float n = wit_sum ? wave_sum16(x) : wave_max_nonneg(x);
+            if (lane_id() == 0) wit_out[blockIdx.x] = __float_as_uint(!COUNTS ? n : n == (float)witnessed ? __builtin_inff() : 0.f);
+            if (EPS == 3) eps_put_max(eps_lds + 16, NW, lane_id, eps_out + (size_t)eps_stride + blockIdx.x);
+        }
+    }
+}
+
+// The T sweeps of a launch (or phase).  sweep(s, tag): sweep s in the Eps mode the tag names -- the launch's own (EPS 0, 1,
+// 2), or for EPS == 3 witness (2) in all sweeps but the last and measured (1) in the last: a second copy of the sweep code
+// after the loop, so that the loop keeps the registers of the witness kernel.  The last sweep is peeled off in the other
+// forms too (file header) except EPS == 1; TWO: two sweeps per loop trip (the folded kernel).  (T by reference: the
+// strip kernel's sweep reads the same variable, the phase's count; by value the R = 5 derivative kernels take a register more.)
+template <int EPS, bool TWO, class Sweep>
+__device__ __forceinline__ void run_sweeps(const int &T, const Sweep &sweep)
+{
+    if constexpr (EPS == 3) {
+#pragma unroll 1
+        for (int s = 0; s + 1 < T; s++) sweep(s, std::integral_constant<int, 2>{});
+        sweep(T - 1, std::integral_constant<int, 1>{});
+    } else if constexpr (EPS != 1) {
+        int s = 0;
+        if constexpr (TWO) {
+#pragma unroll 1
+            for (; s + 2 < T; s += 2) {
+                sweep(s, std::integral_constant<int, EPS>{});
+                sweep(s + 1, std::integral_constant<int, EPS>{});
+            }
+        }
+#pragma unroll 1
+        for (; s + 1 < T; s++) sweep(s, std::integral_constant<int, EPS>{});
+        sweep(T - 1, std::integral_constant<int, EPS>{});
+    } else {
+        const int n = T; // (a copy: against the reference the every-sweep strip loops come out 2 blocks and 2 branches larger)
+#pragma unroll 1
+        for (int s = 0; s < n; s++) sweep(s, std::integral_constant<int, EPS>{});
+    }
+}
+
 template <int R, int NTMAX, int EPS, int E0, bool DERIV, bool PERSIST = false>
 __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
                                                         const float *__restrict__ u_in,
@@ -380,19 +695,11 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     // Synchronisation between sweeps: ONE workgroup barrier per sweep.  (Tried and measured slower, 0.220 vs 0.200 ms
     // at 1080p / 100 sweeps in round 1: per-wavefront counters in LDS, each wavefront waiting only for the strips
     // directly above and below.)
-    const int tpp = g.tiles_x * g.tiles_y;
-    const int tile = xcd_contiguous_tile(blockIdx.x, gridDim.x);
-    const int slot = tile / tpp;
-    const int t2 = tile - slot * tpp;
-    int pair = slot;
-    if constexpr (!PERSIST) { // (the persistent launch always works on every pair: no list, and not a scalar register for one)
-        if (g.pair_list) pair = g.pair_list[slot];
-    }
-    const int by = t2 / g.tiles_x, bx = t2 - by * g.tiles_x;
-    const int x0 = bx * g.CW - g.HX + 4 * lane;
-    const int y0 = by * g.CH - g.T + w * R;
-    const long long base = (long long)pair * g.plane;
-    const bool xin = (x0 >= 0) && (x0 + 3 < g.W); // the whole group lies inside the image
+    const TileId tl = tile_decode<!PERSIST, false>(g); // (the persistent launch always works on every pair: no list, and not a scalar register for one)
+    const int x0 = tl.bx * g.CW - g.HX + 4 * lane;
+    const int y0 = tl.by * g.CH - g.T + w * R;
+    const long long base = (long long)tl.pair * g.plane;
+    const bool xin = group_inside(x0, g.W);
     // The sweep code is written for ONE checkerboard phase: pixel p0 of register row 0 must be an "E0" pixel
     // (x0 % 4 == 0, so that is the parity of the row, counted from the frame's row 0: g.org).  R even: every strip
     // of the launch starts on a row of the parity of T + org (CH is even), which is the template parameter E0 -- the
@@ -403,161 +710,52 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     // addressing knows: which image row a register row is, and which exchange slot holds a neighbour's edge row.
     const bool rev = (R & 1) != 0 && ((y0 + g.org) & 1) != 0; // wave-uniform
     auto img_row = [&](int r) { return rev ? R - 1 - r : r; }; // row of the strip that register row r holds
+    auto image_row = [&](int r) { return y0 + img_row(r); };
 
     f2 uP[R], uQ[R], vP[R], vQ[R];
     RowCoef cf[R];
     float4 lu[R], lv[R];
     uint4 lc[R];
-    // Workgroup-uniform: does the region (core + halo) stick out of the image on the left or right?
-    // Tiles that do not (the vast majority) load with plain aligned 16-byte accesses only.
-    const int rx0 = bx * g.CW - g.HX;
-    const bool xedge = !(rx0 >= 0 && rx0 + 256 <= g.W);
-    // Where does this lane read its four columns?  Inside the image: at x0.  A group that lies completely outside the
-    // image on the left mirrors onto an aligned group read backwards (columns -1-k <-> k); the same holds on the right
-    // when W % 4 == 0: those lanes keep the 16-byte loads (from the mirrored address, components reversed afterwards).
-    // Only groups that straddle column W-1 or sit right of it when W % 4 != 0 (and images narrower than the halo) need
-    // four reflected scalar loads per plane ("slow").  ALL rows' loads are issued first, branch-free -- edge tiles then
-    // load as fast as interior ones (with a branch per row their loads did not overlap: +5 000 cycles per launch on
-    // the two edge tile columns, which every launch then waited for) -- and the fix-ups follow.
-    int xg = x0;
-    bool xrev = false, slow = false;
-    if (xedge && !xin) {
-        if (x0 < 0 && -x0 <= g.W) { xg = -x0 - 4; xrev = true; }
-        else if (x0 >= g.W && (g.W & 3) == 0 && 2 * g.W - x0 - 4 >= 0) { xg = 2 * g.W - x0 - 4; xrev = true; }
-        else { xg = 0; slow = true; }
-    }
+    const int rx0 = tl.bx * g.CW - g.HX;
+    const bool xedge = !(rx0 >= 0 && rx0 + 256 <= g.W); // workgroup-uniform: the region sticks out of the image on the left or right
+    HS_LOAD_PHASE(R, DERIV, xedge, xin, x0, base, image_row, lu, lv, lc, uP, uQ, vP, vQ, cf);
+    // core membership (for the stores and for Eps): rows as a bit mask, lanes as a flag
+    unsigned rowcore = 0;
+    int rdist[R]; // distance of each row from the core rows: wave-uniform
 #pragma unroll
     for (int r = 0; r < R; r++) {
-        const long long off = base + (long long)mirror_index(y0 + img_row(r), g.H) * g.P + xg;
-        // (zero_in: u_in = v_in = one row of zeros, see StripGeom -- the loads stay unconditional: under a branch per
-        // row the compiler waits for each row's two loads before it issues the next row's)
-        const long long off_uv = g.zero_in ? (long long)xg : off;
-        lc[r] = make_uint4(0u, 0u, 0u, 0u);
-        if constexpr (!DERIV) {
-            lu[r] = *(const float4 *)(u_in + off_uv);
-            lv[r] = *(const float4 *)(v_in + off_uv);
-            lc[r] = *(const uint4 *)(coef + off);
+        const int j = w * R + img_row(r);
+        const int y = image_row(r);
+        if constexpr (DERIV) {
+            if (row_in_core(j, y, g.T, g.CH, g.H)) rowcore |= 1u << r;
         } else {
-            lu[r] = lv[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (HS_ROW_IN_CORE(j, y, g.T, g.CH, g.H)) rowcore |= 1u << r;
         }
+        rdist[r] = row_dist(j, g.T, g.CH);
     }
+    const bool lanecore = lane_in_core(x0, 4 * lane, g);
     if constexpr (DERIV) {
-        // The launch with the derivative pass is nearly always the one that starts from zero flow: then it reads no flow at
-        // all and goes straight to the frames (strip_derive); otherwise ONE branch around all the rows' loads.
-        if (!g.zero_in) {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const long long off = base + (long long)mirror_index(y0 + img_row(r), g.H) * g.P + xg;
-                lu[r] = *(const float4 *)(u_in + off);
-                lv[r] = *(const float4 *)(v_in + off);
-            }
-        }
-    }
-    // The lane's pixels p0..p3 go into the register pairs P = (p0, p3), Q = (p1, p2) (cross_rows); the packed derivative
-    // word becomes the three coefficients of the update (sweep_coefs: one v_rsq per pixel).
-    auto unpack_row = [&](const int r) __attribute__((always_inline)) {
-        const float4 lu_ = lu[r], lv_ = lv[r];
-        const uint4 cw = lc[r];
-        constexpr int iPx = 0, iPy = 3, iQx = 1, iQy = 2;
-        const float lu4[4] = {lu_.x, lu_.y, lu_.z, lu_.w}, lv4[4] = {lv_.x, lv_.y, lv_.z, lv_.w};
-        uP[r] = f2{lu4[iPx], lu4[iPy]}; uQ[r] = f2{lu4[iQx], lu4[iQy]};
-        vP[r] = f2{lv4[iPx], lv4[iPy]}; vQ[r] = f2{lv4[iQx], lv4[iQy]};
-        float al[4], be[4], ga[4];
-        const uint32_t cc[4] = {cw.x, cw.y, cw.z, cw.w};
-#pragma unroll
-        for (int p = 0; p < 4; p++) sweep_coefs(cc[p], ilambda, al[p], be[p], ga[p]);
-        cf[r].alP = f2{al[iPx], al[iPy]}; cf[r].alQ = f2{al[iQx], al[iQy]};
-        cf[r].beP = f2{be[iPx], be[iPy]}; cf[r].beQ = f2{be[iQx], be[iQy]};
-        cf[r].gaP = f2{ga[iPx], ga[iPy]} * (HS_SCALED ? 4.0f : 1.0f); cf[r].gaQ = f2{ga[iQx], ga[iQy]} * (HS_SCALED ? 4.0f : 1.0f);
-    };
-    // The rows are unpacked as they arrive, straight behind the loads with no branch in between (a third of the launch's
-    // set-up is this arithmetic: behind the side tiles' fix-ups the compiler waits for ALL loads first).  A mirrored
-    // group arrives reversed: (p0, p1, p2, p3) -> (p3, p2, p1, p0) is a swap of the halves of every register pair.
-    if constexpr (!DERIV) {
-#pragma unroll
-        for (int r = 0; r < R; r++) unpack_row(r);
-    }
-    if (xedge) { // workgroup-uniform
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            if constexpr (DERIV) { // (not unpacked yet; the derivative words come in lane order from strip_derive)
-                if (xrev) {
-                    lu[r] = make_float4(lu[r].w, lu[r].z, lu[r].y, lu[r].x);
-                    lv[r] = make_float4(lv[r].w, lv[r].z, lv[r].y, lv[r].x);
-                }
-            } else {
-                uP[r] = xrev ? f2_swap(uP[r]) : uP[r]; uQ[r] = xrev ? f2_swap(uQ[r]) : uQ[r];
-                vP[r] = xrev ? f2_swap(vP[r]) : vP[r]; vQ[r] = xrev ? f2_swap(vQ[r]) : vQ[r];
-                cf[r].alP = xrev ? f2_swap(cf[r].alP) : cf[r].alP; cf[r].alQ = xrev ? f2_swap(cf[r].alQ) : cf[r].alQ;
-                cf[r].beP = xrev ? f2_swap(cf[r].beP) : cf[r].beP; cf[r].beQ = xrev ? f2_swap(cf[r].beQ) : cf[r].beQ;
-                cf[r].gaP = xrev ? f2_swap(cf[r].gaP) : cf[r].gaP; cf[r].gaQ = xrev ? f2_swap(cf[r].gaQ) : cf[r].gaQ;
-            }
-        }
-        if (__builtin_amdgcn_ballot_w64(slow) != 0) { // wave-uniform: rare (W % 4 != 0, or an image narrower than the halo)
-            if (slow) {
-                const int xa = mirror_index(x0, g.W), xb = mirror_index(x0 + 1, g.W),
-                          xc = mirror_index(x0 + 2, g.W), xd = mirror_index(x0 + 3, g.W);
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const long long row = base + (long long)mirror_index(y0 + img_row(r), g.H) * g.P;
-                    {
-                        const float *uv = u_in + (g.zero_in ? 0 : row), *vv = v_in + (g.zero_in ? 0 : row);
-                        lu[r] = make_float4(uv[xa], uv[xb], uv[xc], uv[xd]);
-                        lv[r] = make_float4(vv[xa], vv[xb], vv[xc], vv[xd]);
-                    }
-                    if constexpr (!DERIV) {
-                        const uint32_t *cv = coef + row;
-                        lc[r] = make_uint4(cv[xa], cv[xb], cv[xc], cv[xd]);
-                        unpack_row(r);
-                    }
-                }
-            }
-        }
-    }
-    if constexpr (DERIV) {
-        unsigned keep = 0; // (the core rows of a core lane: rowcore and lanecore, below)
-        if (fs.keepA != nullptr && (x0 >= 0) && (x0 < g.W) && (4 * lane >= g.HX) && (4 * lane < g.HX + g.CW)) {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const int j = w * R + img_row(r), y = y0 + img_row(r);
-                if (j >= g.T && j < g.T + g.CH && y >= 0 && y < g.H) keep |= 1u << r;
-            }
-        }
+        const unsigned keep = (fs.keepA != nullptr && lanecore) ? rowcore : 0u; // the core rows of a core lane
         strip_derive<R, true>(fA, fB, g, base, x0, rev ? y0 + R - 1 : y0, rev ? -1 : 1, xin, lc, fs, keep);
 #pragma unroll
-        for (int r = 0; r < R; r++) unpack_row(r);
+        for (int r = 0; r < R; r++) unpack(lu[r], lv[r], lc[r], ilambda, uP[r], uQ[r], vP[r], vQ[r], cf[r]);
     }
-    // core membership (for the store and for Eps): rows as a bit mask, lanes as a flag
-    unsigned rowcore = 0;
-    int rdist[R]; // distance of each row from the core rows (0 inside): wave-uniform
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int j = w * R + img_row(r), y = y0 + img_row(r);
-        if (j >= g.T && j < g.T + g.CH && y >= 0 && y < g.H) rowcore |= 1u << r;
-        rdist[r] = j < g.T ? g.T - j : (j >= g.T + g.CH ? j - (g.T + g.CH - 1) : 0);
-    }
-    const bool lanecore = (x0 >= 0) && (x0 < g.W) && (4 * lane >= g.HX) && (4 * lane < g.HX + g.CW);
     const int pr = g.W - 1 - x0; // image columns of this group: 0..min(pr,3)
-    // From here on the Eps / witness kernels read `lane` from the hardware where it is used (hs_lane_now): nothing below
-    // keeps it in a register, and with the three LDS addresses of a sweep formed from that one value the witness kernel
+    // From here on the Eps / witness kernels read the lane number from the hardware where it is used (hs_lane_now): nothing
+    // below keeps it in a register, and with the three LDS addresses of a sweep formed from that one value the witness kernel
     // no longer spills (it reloaded a coefficient pair in every sweep: ITER|EPS stream 0.1325 -> 0.1254 ms per pair).  The
     // plain kernel has the registers and is 0.8 % faster with the lane number kept.
-    const int lane_kept = lane;
     constexpr bool LANE_HW = EPS != 0 || PERSIST;
-#define lane (LANE_HW ? hs_lane_now() : lane_kept)
+    const auto lane_id = [&]() __attribute__((always_inline)) { return LANE_HW ? hs_lane_now() : lane; };
     unsigned epscore = 0; // the core rows that lie in the Eps window (wave-uniform; all of them unless hsflow_set_eps_rows narrowed it)
     if (EPS != 0) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            const int y = y0 + img_row(r);
+            const int y = image_row(r);
             if (((rowcore >> r) & 1u) && y >= g.ey0 && y < g.ey1) epscore |= 1u << r;
         }
     }
-    if (DERIV && lanecore) { // the cores tile the image: this launch leaves the complete derivative plane behind
-#pragma unroll
-        for (int r = 0; r < R; r++)
-            if ((rowcore >> r) & 1u) *(uint4 *)(coef_w + base + (long long)(y0 + img_row(r)) * g.P + x0) = lc[r];
-    }
+    if (DERIV && lanecore) store_deriv_rows<R>(coef_w, g, base, x0, rowcore, image_row, lc);
 
     // One row: neighbour sums from the cross sums of its two boundaries (sc below, sp above), update in place.
     // A row at distance d from the core is only needed through sweep T-1-d (trapezoid): later sweeps skip it
@@ -572,7 +770,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
             else strip_row_update<PE>(uP[r], uQ[r], vP[r], vQ[r], SC, SP, cf[r]);                  \
             if (EM == 1) {                                                                         \
                 if ((epscore >> (r)) & 1u) { /* wave-uniform; lanes outside the core are masked once per sweep */ \
-                    const f2 dUP = HS_DIFF(ouP, uP[r]), dUQ = HS_DIFF(ouQ, uQ[r]), dVP = HS_DIFF(ovP, vP[r]), dVQ = HS_DIFF(ovQ, vQ[r]); \
+                    const f2 dUP = sweep_diff(ouP, uP[r]), dUQ = sweep_diff(ouQ, uQ[r]), dVP = sweep_diff(ovP, vP[r]), dVQ = sweep_diff(ovQ, vQ[r]); \
                     if (!xedge) { /* workgroup-uniform: every column of the region is an image column */ \
                         e = fmaxf(fmaxf(e, fabsf(dUP.x)), fabsf(dUP.y));                           \
                         e = fmaxf(fmaxf(e, fabsf(dUQ.x)), fabsf(dUQ.y));                           \
@@ -597,9 +795,9 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
             else cross_rows<PE>(S, uP[A], uQ[A], vP[A], vQ[A], uP[B], uQ[B], vP[B], vQ[B]);        \
         }                                                                                          \
     } while (0)
-#define HS_PUBLISH(buf)                                                                            \
+#define HS_PUBLISH(buf, ln)                                                                         \
     do {                                                                                           \
-        float4 *exw = ex + ((size_t)((buf) * NW + w) * 4) * 64 + HS_LANE;                          \
+        float4 *exw = ex + ((size_t)((buf) * NW + w) * 4) * 64 + (ln);                             \
         exw[0] = make_float4(uP[0].x, uP[0].y, uQ[0].x, uQ[0].y);                                  \
         exw[64] = make_float4(vP[0].x, vP[0].y, vQ[0].x, vQ[0].y);                                 \
         exw[128] = make_float4(uP[R - 1].x, uP[R - 1].y, uQ[R - 1].x, uQ[R - 1].y);                \
@@ -628,7 +826,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     // needs ONE witness in the workgroup; sixteen wavefronts looking in every sweep cost 4 % of the launch).  A
     // workgroup without such a wavefront (thin cores, clipped bottom tiles) keeps the old rule: every wavefront whose
     // register row 0 is a core row looks in every sweep.  wit_cnt counts down to this wavefront's next turn.
-    const int core_here = min(g.CH, g.H - by * g.CH);
+    const int core_here = min(g.CH, g.H - tl.by * g.CH);
     const int wit_lo = (g.T + R - 1) / R, wit_n = (g.T + core_here) / R - wit_lo; // wavefronts wit_lo .. wit_lo + wit_n - 1
     const bool wit_rot = wit_n > 0;
     const int wit_per = wit_rot ? wit_n : 1;
@@ -653,12 +851,11 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
 #else
         const int last = Tp - 1 - s; // rows with rdist <= last are still swept
 #endif
-        // HS_SCALED: this sweep takes the flow from scale 4^s to 4^(s+1)
-        const float unscale = HS_SCALED ? __builtin_ldexpf(1.0f, -2 * (s + 1)) : 1.0f;
+        // (scaled state: this sweep takes the flow from scale 4^s to 4^(s+1))
         // eps_thr * 4^(s+1) by integer arithmetic on the exponent: scalar instructions only (v_ldexp + v_readfirstlane put
         // a vector-to-scalar round trip into every sweep).  Exact for a normal eps_thr; eps_thr = 0 or a product beyond
         // the float range merely makes the witness fail, and the exact pass decides (the host never sends a denormal).
-        const float thr_s = HS_SCALED ? __int_as_float(__float_as_int(eps_thr) + ((s + 1) << 24)) : eps_thr;
+        const float thr_s = __int_as_float(__float_as_int(eps_thr) + ((s + 1) << 24));
 #if HS_DIAG & 1 /* diagnostic build (wrong results): no LDS traffic, the strip's own edge rows stand in */
         const float4 hu4 = make_float4(uP[0].x, uP[0].y, uQ[0].x, uQ[0].y), hv4 = make_float4(vP[0].x, vP[0].y, vQ[0].x, vQ[0].y);
         const float4 du4 = make_float4(uP[R - 1].x, uP[R - 1].y, uQ[R - 1].x, uQ[R - 1].y), dv4 = make_float4(vP[R - 1].x, vP[R - 1].y, vQ[R - 1].x, vQ[R - 1].y);
@@ -667,8 +864,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
         // hardware gives it at this point (hs_lane_now): left alone the compiler keeps three loop-invariant address
         // registers alive across the sweep loop, which has none to spare -- the witness kernel then reloaded a spilled
         // coefficient pair in every sweep.)
-        const int lane_l = lane;
-#define HS_LANE lane_l
+        const int lane_l = lane_id();
         const float4 *eu = ex + ((size_t)((s & 1) * NW + wu) * 4 + su) * 64 + lane_l;
         const float4 *ed = ex + ((size_t)((s & 1) * NW + wd) * 4 + sd) * 64 + lane_l;
         // (Idle strips -- late sweeps, halo wavefronts -- still read and publish their edge rows.  Gating the reads makes the
@@ -698,7 +894,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
         // witness: did u change by >= eps_thr at column x0 of register row 0 (where that is a core row) in any lane?
         // (The host runs witness launches only with plans in which some wavefront has such a row: strip_has_witness.)
         if (EM == 2) { // (wit_mask: the core lanes if register row 0 is a core row, else none)
-            if (wturn) seen_n += (__builtin_amdgcn_ballot_w64(fabsf(HS_DIFF1(w0, uP[0].x)) >= thr_s) & wit_mask) != 0 ? 1 : 0;
+            if (wturn) seen_n += (__builtin_amdgcn_ballot_w64(fabsf(sweep_diff(w0, uP[0].x)) >= thr_s) & wit_mask) != 0 ? 1 : 0;
             wit_cnt = wturn ? wit_per - 1 : wit_cnt - 1;
         }
         if (R >= 2) {
@@ -710,7 +906,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
             else HS_ROW(R - 1, EL, sL, sK);
         }
 #if !(HS_DIAG & 1)
-        if (s + 1 < Tp) HS_PUBLISH((s + 1) & 1);
+        if (s + 1 < Tp) HS_PUBLISH((s + 1) & 1, lane_l);
 #endif
         // --- interior rows, top to bottom: each needs the cross sum above it (kept) and the one below (new)
         if (R >= 3) {
@@ -729,19 +925,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
                 sp = sc;
             }
         }
-        if (EM == 1 && EPS == 3) { // the one measured sweep of a witness launch: folded after the loop
-            e = wave_max_nonneg(lanecore ? e : 0.f) * unscale;
-            if (lane == 0) eps_lds[16 + w] = e;
-        }
-        if (EM == 1 && EPS == 1) { // per-wavefront maximum -> LDS; wavefront 0 folds the previous sweep's 16 values
-            e = wave_max_nonneg(lanecore ? e : 0.f) * unscale;
-            if (lane == 0) eps_lds[(s & 1) * 16 + w] = e;
-            if (s > 0 && w == 0) {
-                float x = lane < NW ? eps_lds[((s - 1) & 1) * 16 + lane] : 0.f;
-                x = wave_max_nonneg(x);
-                if (lane == 0) eps_out[(size_t)(s - 1) * eps_stride + blockIdx.x] = __float_as_uint(x);
-            }
-        }
+        if constexpr (EM == 1) HS_EPS_FOLD_SWEEP(EPS, lanecore ? e : 0.f, s, w, NW, lane_id(), eps_lds, eps_out, eps_stride);
 #if !(HS_DIAG & 2) /* diagnostic build: no barrier */
         if (s + 1 < Tp) __syncthreads();
 #endif
@@ -752,17 +936,15 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
             stamps[(size_t)gridDim.x * 8 + (size_t)blockIdx.x * 32 + (s & 31)] = __builtin_amdgcn_s_memtime();
 #endif
     };
-#if HS_CORE_PRIO
     // Wavefronts whose rows are all core rows never drop out of a sweep (trapezoid): they are the ones every barrier waits
-    // for, so they go first at the issue port.
-    if (rowcore == (1u << R) - 1u) __builtin_amdgcn_s_setprio(HS_CORE_PRIO);
-#endif
+    // for, so they go first at the issue port (-0.3 % one context, -0.7 % in the stream).
+    if (rowcore == (1u << R) - 1u) __builtin_amdgcn_s_setprio(1);
     // PERSIST: the phases of the solve; otherwise one pass (the `break` after the store is unconditional).
     int ph = 0;
     unsigned flag_base = 0; // this tile's phase counter at the start of the launch (all tiles agree; wavefront 0 only)
     unsigned long long pt_sweep = 0, pt_pub = 0, pt_wait = 0, pt_load = 0, pt0 = 0, pt_first = 0; // PERSIST diagnostics (stamps)
     if constexpr (PERSIST) {
-        if (w == 0) flag_base = (unsigned)__builtin_amdgcn_readfirstlane((int)load_u32_sc1(pa.flags + tile));
+        if (w == 0) flag_base = (unsigned)__builtin_amdgcn_readfirstlane((int)load_u32_sc1(pa.flags + tl.tile));
     }
 #pragma unroll 1
     for (;;) {
@@ -772,96 +954,47 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
         wit_cnt = wit_cnt0;
         if (stamps && ph == 0) pt_first = pt0 = __builtin_amdgcn_s_memtime();
     }
-#undef HS_LANE
-#define HS_LANE lane
-    HS_PUBLISH(0);
+    HS_PUBLISH(0, lane_id());
     __syncthreads();
     if (PERSIST && stamps && ph > 0) { // (the reloaded rows are first used by the publish above: their latency belongs to the reload)
         const unsigned long long t = __builtin_amdgcn_s_memtime();
         pt_load += t - pt0;
         pt0 = t;
     }
-    if constexpr (EPS == 3) {
-#pragma unroll 1
-        for (int s = 0; s + 1 < Tp; s++) sweep(s, std::integral_constant<int, 2>{});
-        sweep(Tp - 1, std::integral_constant<int, 1>{});
-    } else if constexpr (HS_PEEL_LAST_STRIP && EPS != 1) {
-#pragma unroll 1
-        for (int s = 0; s + 1 < Tp; s++) sweep(s, std::integral_constant<int, EPS>{});
-        sweep(Tp - 1, std::integral_constant<int, EPS>{});
-    } else {
-#pragma unroll 1
-        for (int s = 0; s < Tp; s++) sweep(s, std::integral_constant<int, EPS>{});
-    }
+    run_sweeps<EPS, false>(Tp, sweep);
     unsigned *const eps_ph = PERSIST ? eps_out + (size_t)ph * eps_stride : eps_out; // PERSIST: one row of words per phase
-    if (EPS == 1) {
-        __syncthreads();
-        if (w == 0) {
-            float x = lane < NW ? eps_lds[((Tp - 1) & 1) * 16 + lane] : 0.f;
-            x = wave_max_nonneg(x);
-            if (lane == 0) eps_out[(size_t)(Tp - 1) * eps_stride + blockIdx.x] = __float_as_uint(x);
-        }
-    }
-    if (EPS == 2 || EPS == 3) {
-        const int witnessed = EPS == 3 ? Tp - 1 : Tp; // sweeps that ran in witness mode
-        // sweeps this wavefront vouches for; taking turns they add up to the launch, otherwise one wavefront must have all
-        if (lane == 0) eps_lds[w] = (float)seen_n;
-        __syncthreads();
-        if (w == 0) {
-            const float x = lane < NW ? eps_lds[lane] : 0.f;
-            const float n = wit_rot ? wave_sum16(x) : wave_max_nonneg(x);
-            if (lane == 0) eps_ph[blockIdx.x] = __float_as_uint(n == (float)witnessed ? __builtin_inff() : 0.f);
-            if (EPS == 3) { // second word: Eps of the last sweep, exact
-                const float x = wave_max_nonneg(lane < NW ? eps_lds[16 + lane] : 0.f);
-                if (lane == 0) eps_out[(size_t)eps_stride + blockIdx.x] = __float_as_uint(x);
-            }
-        }
-    }
+    eps_tail<EPS, true>(Tp, seen_n, wit_rot, w, NW, lane_id, eps_lds, eps_out, eps_ph, eps_stride);
     if (stamps) st2 = __builtin_amdgcn_s_memtime();
 
     if constexpr (!PERSIST) {
         // (the lane's column is worked out afresh from a copy of the lane number the optimiser cannot see through: kept
         // alive across the sweep loop it is one of the three registers the loop has no room for -- every spilled register
         // is 250 KB of scratch written and read per launch, which showed up as HBM writes: profiles/r03_traffic_by_kernel.json)
-        int lane_s = lane;
+        int lane_s = lane_id();
         if constexpr (!LANE_HW) asm volatile("" : "+v"(lane_s)); // (the kept lane number: a copy the optimiser cannot see through)
-        const int x0s = bx * g.CW - g.HX + 4 * lane_s;
-        if (lanecore) {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                if ((rowcore >> r) & 1u) {
-                    const long long off = base + (long long)(y0 + img_row(r)) * g.P + x0s;
-                    // (non-temporal and agent-scope write-through stores were tried here: both slower)
-                    const float fin = HS_SCALED ? __builtin_ldexpf(1.0f, -2 * g.T) : 1.0f; // back to scale 1 (exact)
-                    // P = (p0, p3), Q = (p1, p2)
-                    *(float4 *)(u_out + off) = make_float4(uP[r].x * fin, uQ[r].x * fin, uQ[r].y * fin, uP[r].y * fin);
-                    *(float4 *)(v_out + off) = make_float4(vP[r].x * fin, vQ[r].x * fin, vQ[r].y * fin, vP[r].y * fin);
-                }
-            }
-        }
+        const int x0s = tl.bx * g.CW - g.HX + 4 * lane_s;
+        if (lanecore) store_flow_rows<R>(u_out, v_out, g, base, x0s, rowcore, image_row, uP, uQ, vP, vQ);
         break;
     } else {
         if (stamps) { pt_sweep += st2 - pt0; pt0 = st2; }
         // --- publish: the core rows go back to scale 1 in their registers (exact) and out with write-through stores
         const __amdgpu_buffer_rsrc_t pu = plane_rsrc(pa.ub[ph & 1]), pv = plane_rsrc(pa.vb[ph & 1]);
-        const float fin = HS_SCALED ? __builtin_ldexpf(1.0f, -2 * Tp) : 1.0f;
+        const float fin = __builtin_ldexpf(1.0f, -2 * Tp);
         // The lane's column and where it reads its halo from are worked out afresh in every phase, from a copy of the
         // lane number the optimiser cannot see through: hoisted out of the phase loop they would be two more registers
         // alive across the sweep loop, which has none to spare (the sweep then reloads spilled coefficients).
-        const int lane_x = lane;
-        const int x0x = bx * g.CW - g.HX + 4 * lane_x;
-        int xgx = x0x;
-        bool xrevx = false;
-        if (xedge && !((x0x >= 0) && (x0x + 3 < g.W))) { // (host: W % 4 == 0 and W >= 256, so no group straddles the border)
-            xgx = x0x < 0 ? -x0x - 4 : 2 * g.W - x0x - 4;
-            xrevx = true;
-        }
+        const int lane_x = lane_id();
+        const int x0x = tl.bx * g.CW - g.HX + 4 * lane_x;
+        // (host: W % 4 == 0 and W >= 256, so no group straddles the border: never slow)
+        const ColRule colx = column_rule(x0x, g.W, xedge, group_inside(x0x, g.W));
+        const int xgx = colx.xg;
+        const bool xrevx = colx.rev != 0;
 #pragma unroll
         for (int r = 0; r < R; r++) {
             if ((rowcore >> r) & 1u) { // wave-uniform
                 uP[r] *= fin; uQ[r] *= fin; vP[r] *= fin; vQ[r] *= fin;
                 if (lanecore) {
-                    const unsigned row = 4u * (unsigned)(base + (long long)(y0 + img_row(r)) * g.P); // wave-uniform
+                    const unsigned row = 4u * (unsigned)(base + (long long)image_row(r) * g.P); // wave-uniform
                     store_f4_sc1(pu, row, 4u * (unsigned)x0x, f4{uP[r].x, uQ[r].x, uQ[r].y, uP[r].y});
                     store_f4_sc1(pv, row, 4u * (unsigned)x0x, f4{vP[r].x, vQ[r].x, vQ[r].y, vP[r].y});
                 }
@@ -872,7 +1005,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const int nact = Tp - rdist[r] > 0 ? Tp - rdist[r] : 0;
-            const float back = HS_SCALED ? __builtin_ldexpf(1.0f, -2 * nact) : 1.0f;
+            const float back = __builtin_ldexpf(1.0f, -2 * nact);
             cf[r].gaP *= back; cf[r].gaQ *= back;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wavefront's stores have been written through
@@ -881,26 +1014,26 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
         int *const dead_lds = (int *)(eps_lds + 31);
         if (w == 0) {
             const unsigned target = flag_base + (unsigned)ph + 1u; // "phase ph of this tile is published"
-            if (lane == 0) __hip_atomic_store(pa.flags + tile, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane_id() == 0) __hip_atomic_store(pa.flags + tl.tile, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // lanes 0..7 watch the 8 neighbouring tiles (same pair), lane 8 the abort word
             int nb = -1;
-            if (lane < 8) {
-                const int k = lane < 4 ? lane : lane + 1; // 0..8 without the centre
-                const int nx = bx + k % 3 - 1, ny = by + k / 3 - 1;
-                if (nx >= 0 && nx < g.tiles_x && ny >= 0 && ny < g.tiles_y) nb = slot * tpp + ny * g.tiles_x + nx;
-            } else if (lane == 8) nb = (int)gridDim.x;
+            if (lane_id() < 8) {
+                const int k = lane_id() < 4 ? lane_id() : lane_id() + 1; // 0..8 without the centre
+                const int nx = tl.bx + k % 3 - 1, ny = tl.by + k / 3 - 1;
+                if (nx >= 0 && nx < g.tiles_x && ny >= 0 && ny < g.tiles_y) nb = tl.slot * g.tiles_x * g.tiles_y + ny * g.tiles_x + nx;
+            } else if (lane_id() == 8) nb = (int)gridDim.x;
             const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
             int dead = 0;
             for (;;) {
                 unsigned v = target;
                 if (nb >= 0) v = load_u32_sc1(pa.flags + nb);
-                const bool aborted = lane == 8 && v != 0u;
-                const bool behind = lane < 8 && (int)(v - target) < 0;
+                const bool aborted = lane_id() == 8 && v != 0u;
+                const bool behind = lane_id() < 8 && (int)(v - target) < 0;
                 if (__builtin_amdgcn_ballot_w64(aborted) != 0) { dead = 1; break; }
                 if (__builtin_amdgcn_ballot_w64(behind) == 0) break;
                 if (__builtin_amdgcn_s_memrealtime() - t0 > (unsigned long long)pa.wait_ticks) { // a neighbour never came
                     dead = 1;
-                    if (lane == 0) {
+                    if (lane_id() == 0) {
                         __hip_atomic_store(pa.flags + gridDim.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         __hip_atomic_store(pa.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     }
@@ -908,7 +1041,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
                 }
                 __builtin_amdgcn_s_sleep(4);
             }
-            if (lane == 0) *dead_lds = dead;
+            if (lane_id() == 0) *dead_lds = dead;
         }
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(*dead_lds)) return; // workgroup-uniform (and said so: a divergent exit would put the loop's counters into VGPRs)
@@ -919,7 +1052,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
             f4 tu[R], tv[R];
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                const unsigned row = 4u * (unsigned)(base + (long long)mirror_index(y0 + img_row(r), g.H) * g.P); // wave-uniform
+                const unsigned row = 4u * (unsigned)(base + (long long)mirror_index(image_row(r), g.H) * g.P); // wave-uniform
                 tu[r] = f4{uP[r].x, uQ[r].x, uQ[r].y, uP[r].y};
                 tv[r] = f4{vP[r].x, vQ[r].x, vQ[r].y, vP[r].y};
                 if (!((rowcore >> r) & 1u) || !lanecore) {
@@ -944,18 +1077,11 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
 #undef HS_ACT
 #undef HS_CROSS
 #undef HS_PUBLISH
-#undef HS_LANE
-#undef lane
     if (stamps && threadIdx.x == 0) {
-        __builtin_amdgcn_s_waitcnt(0); // stores issued and acknowledged
-        unsigned long long *o = stamps + (size_t)blockIdx.x * 8;
-        o[0] = st0; o[1] = st1; o[2] = st2; o[3] = __builtin_amdgcn_s_memtime();
-        o[4] = sr0; o[5] = __builtin_amdgcn_s_memrealtime();
-        o[6] = (unsigned long long)__builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20); // XCC_ID
-        o[7] = (unsigned long long)tile;
+        const unsigned long long st3 = store_stamps(stamps, st0, sr0, st1, st2, tl.tile);
         if (PERSIST && gridDim.x <= 8192) { // totals over the phases: sweeps, publish, wait, reload (cycles)
             unsigned long long *q = stamps + (size_t)gridDim.x * 8 + (size_t)blockIdx.x * 32;
-            q[0] = pt_sweep; q[1] = pt_pub; q[2] = pt_wait; q[3] = pt_load; q[4] = pt_first - st1; q[5] = o[3] - st2;
+            q[0] = pt_sweep; q[1] = pt_pub; q[2] = pt_wait; q[3] = pt_load; q[4] = pt_first - st1; q[5] = st3 - st2;
         }
     }
 }
@@ -1035,8 +1161,8 @@ __device__ __forceinline__ float lane_xor32(float x, bool lower)
 }
 
 // E0 = parity of pixel p0 of register row 0 of BOTH halves: yb has the parity of T (CH is even) and the lower half's
-// reversed order turns its rows' parities around (k_jacobi_strip explains the reversal), so one code path serves both.
-template <int R, int NTMAX, int EPS, int E0, bool DERIV> // EPS: 0 none, 1 Eps of every sweep, 2 witness (see k_jacobi_strip)
+// reversed order turns its rows' parities around (strip_body explains the reversal), so one code path serves both.
+template <int R, int NTMAX, int EPS, int E0, bool DERIV> // EPS: 0 none, 1 Eps of every sweep, 2 witness, 3 witness + last sweep (strip_body)
 __device__ __forceinline__ void fold_body(const uint32_t *__restrict__ coef,
                                                        const float *__restrict__ u_in,
                                                        const float *__restrict__ v_in,
@@ -1056,139 +1182,41 @@ __device__ __forceinline__ void fold_body(const uint32_t *__restrict__ coef,
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int NW = g.NW;
     float *eps_lds = (float *)(ex + (size_t)2 * NW * 2 * 2 * 32);
-    const int tpp = g.tiles_x * g.tiles_y;
-    const int tile = xcd_contiguous_tile(blockIdx.x, gridDim.x);
-    const int slot = tile / tpp;
-    const int t2 = tile - slot * tpp;
-    const int pair = __builtin_amdgcn_readfirstlane(g.pair_list ? g.pair_list[slot] : slot); // (kept scalar: no register of a lane)
-    const int by = t2 / g.tiles_x, bx = t2 - by * g.tiles_x;
-    const int rx0 = bx * g.CW - g.HX;
+    const TileId tl = tile_decode<true, true>(g); // (the pair kept scalar: no register of a lane)
+    const int rx0 = tl.bx * g.CW - g.HX;
     const int x0 = rx0 + 4 * hl;
-    const int yb = by * g.CH - g.T + w * 2 * R; // first block row of this wavefront
-    const long long base = (long long)pair * g.plane;
-    const bool xin = (x0 >= 0) && (x0 + 3 < g.W);
+    const int yb = tl.by * g.CH - g.T + w * 2 * R; // first block row of this wavefront
+    const long long base = (long long)tl.pair * g.plane;
+    const bool xin = group_inside(x0, g.W);
+    auto blk_row = [&](int r) { return lower ? 2 * R - 1 - r : r; }; // row of the wavefront's block that register row r holds
+    auto image_row = [&](int r) { return yb + blk_row(r); };
+    const auto lane_id = [&]() { return lane; };
 
     f2 uP[R], uQ[R], vP[R], vQ[R];
     RowCoef cf[R];
     float4 lu[R], lv[R];
     uint4 lc[R];
     const bool side = !(rx0 >= 0 && rx0 + 128 <= g.W); // workgroup-uniform
-    int xg = x0;
-    bool rev = false, slow = false;
-    if (side && !xin) { // see k_jacobi_strip: mirrored aligned group, or the general scalar path
-        if (x0 < 0 && -x0 <= g.W) { xg = -x0 - 4; rev = true; }
-        else if (x0 >= g.W && (g.W & 3) == 0 && 2 * g.W - x0 - 4 >= 0) { xg = 2 * g.W - x0 - 4; rev = true; }
-        else { xg = 0; slow = true; }
-    }
-    // all rows' loads first, branch-free; then the fix-ups of the side tiles (k_jacobi_strip explains why)
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int y = yb + (lower ? 2 * R - 1 - r : r);
-        const long long off = base + (long long)mirror_index(y, g.H) * g.P + xg;
-        const long long off_uv = g.zero_in ? (long long)xg : off; // (zero_in: one row of zeros, k_jacobi_strip)
-        lc[r] = make_uint4(0u, 0u, 0u, 0u);
-        if constexpr (!DERIV) {
-            lu[r] = *(const float4 *)(u_in + off_uv);
-            lv[r] = *(const float4 *)(v_in + off_uv);
-            lc[r] = *(const uint4 *)(coef + off);
-        } else {
-            lu[r] = lv[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    if constexpr (DERIV) { // (k_jacobi_strip: no flow loads for a solve from zero flow, one branch around them otherwise)
-        if (!g.zero_in) {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const int y = yb + (lower ? 2 * R - 1 - r : r);
-                const long long off = base + (long long)mirror_index(y, g.H) * g.P + xg;
-                lu[r] = *(const float4 *)(u_in + off);
-                lv[r] = *(const float4 *)(v_in + off);
-            }
-        }
-    }
-    // the lane's pixels p0..p3 go into the register pairs P = (p0, p3), Q = (p1, p2) (cross_rows); rows are unpacked as they
-    // arrive, before the side tiles' fix-ups (k_jacobi_strip: a reversed group = the halves of every pair swapped)
-    auto unpack_row = [&](const int r) __attribute__((always_inline)) {
-        constexpr int iPx = 0, iPy = 3, iQx = 1, iQy = 2;
-        const float lu4[4] = {lu[r].x, lu[r].y, lu[r].z, lu[r].w}, lv4[4] = {lv[r].x, lv[r].y, lv[r].z, lv[r].w};
-        uP[r] = f2{lu4[iPx], lu4[iPy]}; uQ[r] = f2{lu4[iQx], lu4[iQy]};
-        vP[r] = f2{lv4[iPx], lv4[iPy]}; vQ[r] = f2{lv4[iQx], lv4[iQy]};
-        float al[4], be[4], ga[4];
-        const uint32_t cc[4] = {lc[r].x, lc[r].y, lc[r].z, lc[r].w};
-#pragma unroll
-        for (int p = 0; p < 4; p++) sweep_coefs(cc[p], ilambda, al[p], be[p], ga[p]);
-        cf[r].alP = f2{al[iPx], al[iPy]}; cf[r].alQ = f2{al[iQx], al[iQy]};
-        cf[r].beP = f2{be[iPx], be[iPy]}; cf[r].beQ = f2{be[iQx], be[iQy]};
-        cf[r].gaP = f2{ga[iPx], ga[iPy]} * (HS_SCALED ? 4.0f : 1.0f); cf[r].gaQ = f2{ga[iQx], ga[iQy]} * (HS_SCALED ? 4.0f : 1.0f);
-    };
-    if constexpr (!DERIV) {
-#pragma unroll
-        for (int r = 0; r < R; r++) unpack_row(r);
-    }
-    if (side) { // workgroup-uniform
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            if constexpr (DERIV) {
-                if (rev) {
-                    lu[r] = make_float4(lu[r].w, lu[r].z, lu[r].y, lu[r].x);
-                    lv[r] = make_float4(lv[r].w, lv[r].z, lv[r].y, lv[r].x);
-                }
-            } else {
-                uP[r] = rev ? f2_swap(uP[r]) : uP[r]; uQ[r] = rev ? f2_swap(uQ[r]) : uQ[r];
-                vP[r] = rev ? f2_swap(vP[r]) : vP[r]; vQ[r] = rev ? f2_swap(vQ[r]) : vQ[r];
-                cf[r].alP = rev ? f2_swap(cf[r].alP) : cf[r].alP; cf[r].alQ = rev ? f2_swap(cf[r].alQ) : cf[r].alQ;
-                cf[r].beP = rev ? f2_swap(cf[r].beP) : cf[r].beP; cf[r].beQ = rev ? f2_swap(cf[r].beQ) : cf[r].beQ;
-                cf[r].gaP = rev ? f2_swap(cf[r].gaP) : cf[r].gaP; cf[r].gaQ = rev ? f2_swap(cf[r].gaQ) : cf[r].gaQ;
-            }
-        }
-        if (__builtin_amdgcn_ballot_w64(slow) != 0) { // wave-uniform, rare
-            if (slow) {
-                const int xa = mirror_index(x0, g.W), xb = mirror_index(x0 + 1, g.W),
-                          xc = mirror_index(x0 + 2, g.W), xd = mirror_index(x0 + 3, g.W);
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const int y = yb + (lower ? 2 * R - 1 - r : r);
-                    const long long row = base + (long long)mirror_index(y, g.H) * g.P;
-                    {
-                        const float *uv = u_in + (g.zero_in ? 0 : row), *vv = v_in + (g.zero_in ? 0 : row);
-                        lu[r] = make_float4(uv[xa], uv[xb], uv[xc], uv[xd]);
-                        lv[r] = make_float4(vv[xa], vv[xb], vv[xc], vv[xd]);
-                    }
-                    if constexpr (!DERIV) {
-                        const uint32_t *cv = coef + row;
-                        lc[r] = make_uint4(cv[xa], cv[xb], cv[xc], cv[xd]);
-                        unpack_row(r);
-                    }
-                }
-            }
-        }
-    }
+    HS_LOAD_PHASE(R, DERIV, side, xin, x0, base, image_row, lu, lv, lc, uP, uQ, vP, vQ, cf);
     // (the wave shifts in strip_derive cross the lane 31/32 seam like those of the sweep: region-edge columns)
     if constexpr (DERIV) {
         strip_derive<R>(fA, fB, g, base, x0, lower ? yb + 2 * R - 1 : yb, lower ? -1 : 1, xin, lc);
 #pragma unroll
-        for (int r = 0; r < R; r++) unpack_row(r);
+        for (int r = 0; r < R; r++) unpack(lu[r], lv[r], lc[r], ilambda, uP[r], uQ[r], vP[r], vQ[r], cf[r]);
     }
     // core membership: per lane (the two halves hold different rows); skip distances: per wavefront
     unsigned rowcore = 0;
     int rdist[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-        const int jl = w * 2 * R + (lower ? 2 * R - 1 - r : r), y = yb + (lower ? 2 * R - 1 - r : r);
-        if (jl >= g.T && jl < g.T + g.CH && y >= 0 && y < g.H) rowcore |= 1u << r;
-        const int ju = w * 2 * R + r, jd = w * 2 * R + 2 * R - 1 - r;
-        const int du = ju < g.T ? g.T - ju : (ju >= g.T + g.CH ? ju - (g.T + g.CH - 1) : 0);
-        const int dd = jd < g.T ? g.T - jd : (jd >= g.T + g.CH ? jd - (g.T + g.CH - 1) : 0);
+        const int jl = w * 2 * R + blk_row(r), y = image_row(r); // (per lane: the two halves hold different rows)
+        if (HS_ROW_IN_CORE(jl, y, g.T, g.CH, g.H)) rowcore |= 1u << r;
+        const int du = row_dist(w * 2 * R + r, g.T, g.CH), dd = row_dist(w * 2 * R + 2 * R - 1 - r, g.T, g.CH);
         rdist[r] = du < dd ? du : dd; // the row is computed while either half still needs it
     }
-    const bool lanecore = (x0 >= 0) && (x0 < g.W) && (4 * hl >= g.HX) && (4 * hl < g.HX + g.CW);
+    const bool lanecore = lane_in_core(x0, 4 * hl, g);
     const int pr = g.W - 1 - x0;
-    if (DERIV && lanecore) { // the cores tile the image: this launch leaves the complete derivative plane behind
-#pragma unroll
-        for (int r = 0; r < R; r++)
-            if ((rowcore >> r) & 1u)
-                *(uint4 *)(coef_w + base + (long long)(yb + (lower ? 2 * R - 1 - r : r)) * g.P + x0) = lc[r];
-    }
+    if (DERIV && lanecore) store_deriv_rows<R>(coef_w, g, base, x0, rowcore, image_row, lc);
 
 #define HF_ROW(r, PE, SC, SP)                                                                      \
     do {                                                                                           \
@@ -1199,10 +1227,10 @@ __device__ __forceinline__ void fold_body(const uint32_t *__restrict__ coef,
             if (EM == 1) {                                                                         \
                 if (((rowcore >> (r)) & 1u) && lanecore) {                                         \
                     /* image columns of the group are p0 .. p(pr); P = (p0, p3), Q = (p1, p2) */   \
-                    e = fmaxf(e, fmaxf(fabsf(HS_DIFF1(ouP.x, uP[r].x)), fabsf(HS_DIFF1(ovP.x, vP[r].x))));           \
-                    if (pr >= 1) e = fmaxf(e, fmaxf(fabsf(HS_DIFF1(ouQ.x, uQ[r].x)), fabsf(HS_DIFF1(ovQ.x, vQ[r].x)))); \
-                    if (pr >= 2) e = fmaxf(e, fmaxf(fabsf(HS_DIFF1(ouQ.y, uQ[r].y)), fabsf(HS_DIFF1(ovQ.y, vQ[r].y)))); \
-                    if (pr >= 3) e = fmaxf(e, fmaxf(fabsf(HS_DIFF1(ouP.y, uP[r].y)), fabsf(HS_DIFF1(ovP.y, vP[r].y)))); \
+                    e = fmaxf(e, fmaxf(fabsf(sweep_diff(ouP.x, uP[r].x)), fabsf(sweep_diff(ovP.x, vP[r].x))));           \
+                    if (pr >= 1) e = fmaxf(e, fmaxf(fabsf(sweep_diff(ouQ.x, uQ[r].x)), fabsf(sweep_diff(ovQ.x, vQ[r].x)))); \
+                    if (pr >= 2) e = fmaxf(e, fmaxf(fabsf(sweep_diff(ouQ.y, uQ[r].y)), fabsf(sweep_diff(ovQ.y, vQ[r].y)))); \
+                    if (pr >= 3) e = fmaxf(e, fmaxf(fabsf(sweep_diff(ouP.y, uP[r].y)), fabsf(sweep_diff(ovP.y, vP[r].y)))); \
                 }                                                                                  \
             }                                                                                      \
         }                                                                                          \
@@ -1232,12 +1260,11 @@ __device__ __forceinline__ void fold_body(const uint32_t *__restrict__ coef,
     const int ho = lower ? (w < NW - 1 ? 0 : 1) : (w > 0 ? 1 : 0);
     int seen_n = 0; // EPS == 2: sweeps in which some lane of this wavefront saw a change >= eps_thr
     const unsigned long long wit_mask = __builtin_amdgcn_ballot_w64((rowcore & 1u) && lanecore); // lanes whose answer counts
-    // one sweep in Eps mode EM (k_jacobi_strip explains EPS == 3: witness sweeps, then one measured sweep)
+    // one sweep in Eps mode EM (run_sweeps)
     auto sweep = [&](const int s, auto em_tag) __attribute__((always_inline)) {
         constexpr int EM = decltype(em_tag)::value;
         const int last = g.T - 1 - s; // rows with rdist <= last are still swept
-        const float unscale = HS_SCALED ? __builtin_ldexpf(1.0f, -2 * (s + 1)) : 1.0f;
-        const float thr_s = HS_SCALED ? __int_as_float(__float_as_int(eps_thr) + ((s + 1) << 24)) : eps_thr; // (see k_jacobi_strip)
+        const float thr_s = __int_as_float(__float_as_int(eps_thr) + ((s + 1) << 24)); // eps_thr * 4^(s+1), as in the strip kernel
         const float4 *eo = HF_SLOT(s & 1, wo, ho) + hl;
         const float4 h4u = eo[0], h4v = eo[32];
         const f2 ouP_ = f2{h4u.x, h4u.y}, ouQ_ = f2{h4u.z, h4u.w}, ovP_ = f2{h4v.x, h4v.y}, ovQ_ = f2{h4v.z, h4v.w};
@@ -1266,95 +1293,26 @@ __device__ __forceinline__ void fold_body(const uint32_t *__restrict__ coef,
             if (r & 1) HF_ROW(r, E0 ^ 1, sc, sp);
             else HF_ROW(r, E0, sc, sp);
             if (r == 0) {
-                // witness (k_jacobi_strip explains it): old and new value of the published row at column x0
+                // witness (strip_body explains it): old and new value of the published row at column x0
                 if (EM == 2)
-                    seen_n += (__builtin_amdgcn_ballot_w64(fabsf(HS_DIFF1(w0, uP[0].x)) >= thr_s) & wit_mask) != 0 ? 1 : 0;
+                    seen_n += (__builtin_amdgcn_ballot_w64(fabsf(sweep_diff(w0, uP[0].x)) >= thr_s) & wit_mask) != 0 ? 1 : 0;
                 if (s + 1 < g.T) HF_PUBLISH((s + 1) & 1);
             }
             sp = sc;
         }
-        if (EM == 1 && EPS == 3) {
-            e = wave_max(e) * unscale;
-            if (lane == 0) eps_lds[16 + w] = e;
-        }
-        if (EM == 1 && EPS == 1) {
-            e = wave_max(e) * unscale;
-            if (lane == 0) eps_lds[(s & 1) * 16 + w] = e;
-            if (s > 0 && w == 0) {
-                float x = lane < NW ? eps_lds[((s - 1) & 1) * 16 + lane] : 0.f;
-                x = wave_max(x);
-                if (lane == 0) eps_out[(size_t)(s - 1) * eps_stride + blockIdx.x] = __float_as_uint(x);
-            }
-        }
+        if constexpr (EM == 1) HS_EPS_FOLD_SWEEP(EPS, e, s, w, NW, lane, eps_lds, eps_out, eps_stride); // (e: core pixels only, HF_ROW)
         if (s + 1 < g.T) __syncthreads();
     };
-    if constexpr (EPS == 3) {
-#pragma unroll 1
-        for (int s = 0; s + 1 < g.T; s++) sweep(s, std::integral_constant<int, 2>{});
-        sweep(g.T - 1, std::integral_constant<int, 1>{});
-    } else if constexpr (HS_PEEL_LAST_FOLD && EPS != 1) {
-        int s = 0;
-        if constexpr (HS_UNROLL2_FOLD) { // two sweeps per trip: the register copies at the loop's back edge halve
-#pragma unroll 1
-            for (; s + 2 < g.T; s += 2) {
-                sweep(s, std::integral_constant<int, EPS>{});
-                sweep(s + 1, std::integral_constant<int, EPS>{});
-            }
-        }
-#pragma unroll 1
-        for (; s + 1 < g.T; s++) sweep(s, std::integral_constant<int, EPS>{});
-        sweep(g.T - 1, std::integral_constant<int, EPS>{});
-    } else {
-#pragma unroll 1
-        for (int s = 0; s < g.T; s++) sweep(s, std::integral_constant<int, EPS>{});
-    }
-    if (EPS == 1) {
-        __syncthreads();
-        if (w == 0) {
-            float x = lane < NW ? eps_lds[((g.T - 1) & 1) * 16 + lane] : 0.f;
-            x = wave_max(x);
-            if (lane == 0) eps_out[(size_t)(g.T - 1) * eps_stride + blockIdx.x] = __float_as_uint(x);
-        }
-    }
-    if (EPS == 2 || EPS == 3) {
-        if (lane == 0) eps_lds[w] = seen_n == (EPS == 3 ? g.T - 1 : g.T) ? __builtin_inff() : 0.f;
-        __syncthreads();
-        if (w == 0) {
-            const float y = wave_max_nonneg(lane < NW ? eps_lds[lane] : 0.f);
-            if (lane == 0) eps_out[blockIdx.x] = __float_as_uint(y);
-            if (EPS == 3) { // second word: Eps of the last sweep, exact
-                const float x = wave_max_nonneg(lane < NW ? eps_lds[16 + lane] : 0.f);
-                if (lane == 0) eps_out[(size_t)eps_stride + blockIdx.x] = __float_as_uint(x);
-            }
-        }
-    }
+    run_sweeps<EPS, true>(g.T, sweep);
+    eps_tail<EPS, false>(g.T, seen_n, false, w, NW, lane_id, eps_lds, eps_out, eps_out, eps_stride); // (every wavefront looks in every sweep)
 #undef HF_ROW
 #undef HF_CROSS
 #undef HF_PUBLISH
 #undef HF_SLOT
     if (stamps) st2 = __builtin_amdgcn_s_memtime();
 
-    if (lanecore) {
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            if ((rowcore >> r) & 1u) {
-                const int y = yb + (lower ? 2 * R - 1 - r : r);
-                const long long off = base + (long long)y * g.P + x0;
-                const float fin = HS_SCALED ? __builtin_ldexpf(1.0f, -2 * g.T) : 1.0f; // back to scale 1 (exact)
-                // P = (p0, p3), Q = (p1, p2)
-                *(float4 *)(u_out + off) = make_float4(uP[r].x * fin, uQ[r].x * fin, uQ[r].y * fin, uP[r].y * fin);
-                *(float4 *)(v_out + off) = make_float4(vP[r].x * fin, vQ[r].x * fin, vQ[r].y * fin, vP[r].y * fin);
-            }
-        }
-    }
-    if (stamps && threadIdx.x == 0) {
-        __builtin_amdgcn_s_waitcnt(0);
-        unsigned long long *o = stamps + (size_t)blockIdx.x * 8;
-        o[0] = st0; o[1] = st1; o[2] = st2; o[3] = __builtin_amdgcn_s_memtime();
-        o[4] = sr0; o[5] = __builtin_amdgcn_s_memrealtime();
-        o[6] = (unsigned long long)__builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20);
-        o[7] = (unsigned long long)tile;
-    }
+    if (lanecore) store_flow_rows<R>(u_out, v_out, g, base, x0, rowcore, image_row, uP, uQ, vP, vQ);
+    if (stamps && threadIdx.x == 0) store_stamps(stamps, st0, sr0, st1, st2, tl.tile);
 }
 
 template <int R, int NTMAX, int EPS, int E0>
@@ -1389,5 +1347,10 @@ __global__ __launch_bounds__(NTMAX) void k_jacobi_fold_deriv(const uint8_t *__re
     fold_body<R, NTMAX, EPS, E0, true>(nullptr, u_in, v_in, u_out, v_out, g, ilambda, eps_out, eps_stride, stamps, eps_thr,
                                    fA, fB, coef_w);
 }
+
+#undef HS_ROW_IN_CORE
+#undef HS_EPS_FOLD_SWEEP
+#undef HS_LOAD_PHASE
+#undef HS_MIRROR_ROW
 
 } // namespace hsk
