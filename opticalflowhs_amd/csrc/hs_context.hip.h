@@ -72,6 +72,8 @@ struct SolveSetup {
     long long budget;   // sweep budget (huge when ITER does not apply)
     int T;              // sweeps per full launch
     JPlan plan;         // launch plan for T sweeps
+    JPlan tail;         // ... and for the short last launch of budget % T sweeps (tail.T = 0: the budget has none)
+    bool witness;       // ITER|EPS runs the budget as witness launches (plan and tail can; no exact pass is being forced)
     bool persist;       // the whole budget as ONE persistent launch in phases of T sweeps (HSFLOW_KERNEL_PERSIST)
     hsflow_params eff;  // the parameters of THIS call (a cached setup gets them replaced: use_previous, reuse_derivatives, use_graph
                         // and profile do not enter the plan)
@@ -234,6 +236,27 @@ struct LaunchIo {
 
 // The default: Eps into the sink nobody reads, all pairs, the context's own frames.
 LaunchIo default_io(const hsflow_ctx *c) { return LaunchIo{c->dEps}; }
+
+// One pass of a CV-mode solve: `sweeps` Jacobi sweeps from the current flow, as n launches of `plan` with a short last one
+// (enqueue_pass walks it, issue_pass puts it on the stream).  The solve paths build one from their setup.
+struct Pass {
+    int sweeps = 0, n = 0;          // n: launches (persist: phases of the one launch)
+    const JPlan *plan = nullptr, *last = nullptr; // of every launch but the last, of the last (the one-sweep kernel: NULL)
+    float coeff = 0.f;
+    bool zero = false;              // the pass starts from u = v = 0 (a cold start)
+    bool persist = false;           // all of it as ONE persistent launch
+    EpsMode eps = EpsMode::None, eps_last = EpsMode::None; // what every launch but the last records, and the last
+    unsigned *eps_rows = nullptr;   // launch (phase) L records into row L of these (NULL: nothing, into the sink nobody reads) ...
+    int stride = 1;                 // ... of this many words ...
+    float thr = 0.f;                // ... against this threshold (LaunchIo)
+    const EpsLayout *reduce = nullptr; // behind the last launch the rows are reduced into hEps ...
+    bool mark = false;              // ... by a kernel whose last workgroup writes the context's marker
+    bool save_start = false;        // the starting flow is kept in dUb / dVb first
+    // how launch 0 is formed (form_first_launch):
+    bool deriv = false, fuse = false; // the derivatives are computed; by launch 0 itself, not by a kernel of their own
+    bool in_place = false;          // launch 0 reads the caller's frames, these:
+    hsflow_ctx::FrameRef frames;
+};
 
 // live contexts per device (this process): the persistent launch wants the device to itself -- two persistent grids
 // from two contexts could each hold part of the CUs and wait for workgroups that cannot start

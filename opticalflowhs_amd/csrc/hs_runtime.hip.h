@@ -212,67 +212,6 @@ int configure_persist(hsflow_ctx *c, const StripPlan &sp, EpsMode eps, bool deri
     return HSFLOW_OK;
 }
 
-// Enqueue derivative pass + `iters` Jacobi sweeps (no host synchronisation inside).  io: what every launch is handed
-// (no Eps is recorded: default_io, with the caller's frames for the first launch where that reads them in place).
-int enqueue_fixed(hsflow_ctx *c, const hsflow_params &p, float coeff, int iters, int kernel, int T, const JPlan *plan,
-                  const JPlan *tail_plan, Profiler &prof, const LaunchIo &io, bool do_deriv, bool zero_flow, bool persist = false, int part = 0)
-{
-    // part: 0 the whole sequence; 1 up to and including the first Jacobi launch; 2 what follows it (c->cur as part 1 left
-    // it).  A solve whose first launch reads the caller's frames (io.frames) issues that launch by itself, with this
-    // submission's pointers, and replays the rest from the graph cache.
-    // u = v = 0 at the start (reference behaviour, use_previous = 0): instead of clearing two
-    // planes and reading them back, the first launch is told that its input is zero.
-    int zero_in = zero_flow ? 1 : 0;
-    if (zero_flow && part != 2) c->cur = 0;
-    // the derivative pass rides in the first Jacobi launch where the kernel can do it (not when profiling:
-    // deriv_ms / jacobi_ms then keep their meaning)
-    bool fuse = do_deriv && !p.profile && kernel != HSFLOW_KERNEL_SIMPLE &&
-                strip_deriv_fusable(c, iters >= T ? *plan : *tail_plan);
-    if (do_deriv && !fuse && part != 2) {
-        prof.begin(0);
-        HS_HIP(c, launch_deriv(c));
-        prof.end();
-    }
-    int left = iters, launches = 0;
-    if (persist) { // the whole budget as one launch
-        prof.begin(1);
-        const int st = enqueue_persist(c, plan->s, iters, EpsMode::None, io, fuse, zero_in, coeff);
-        prof.end();
-        if (st) return st;
-        left = 0;
-        launches = 1;
-    }
-    while (left > 0) {
-        const int a = c->cur, b = a ^ 1;
-        if (kernel == HSFLOW_KERNEL_SIMPLE) {
-            prof.begin(1);
-            HS_HIP(c, launch_simple(c, false, io, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, zero_in));
-            prof.end();
-            left -= 1;
-        } else {
-            const JPlan *pl = (left >= T) ? plan : tail_plan;
-            if (part == 2 && launches == 0) { // (part 1 issued it)
-                fuse = false;
-                left -= pl->T;
-                zero_in = 0;
-                launches++;
-                continue;
-            }
-            prof.begin(1);
-            HS_HIP(c, launch_j(c, *pl, EpsMode::None, io, c->dU[a], c->dV[a], c->dU[b], c->dV[b], coeff, zero_in, fuse));
-            prof.end();
-            fuse = false;
-            left -= pl->T;
-        }
-        c->cur = b;
-        zero_in = 0;
-        launches++;
-        if (part == 1) break;
-    }
-    c->info.jacobi_launches = launches;
-    return HSFLOW_OK;
-}
-
 // Eps bookkeeping of an EPS-terminated solve: `sweeps` rows of `stride` words (one per workgroup) on the device, and
 // the host buffer k_eps_reduce reduces the rows into, hEps[0..sweeps).  eps_reserve allocates only, so that what
 // follows can be captured in a graph; eps_prepare also clears the rows.  Neither tells the launches anything: the caller

@@ -80,6 +80,15 @@ enum : int {
     kKeyPerPair = 32,    // the witness words are reduced per pair
 };
 
+// The key of a captured launch sequence: the call's parameters, the kernel and sweeps per launch of its setup, the launch
+// shape in c->info, the kKey* bits, the coefficient (Ilambda, or alpha in classic mode) and a witness pass's threshold.
+GraphKey graph_key(const hsflow_ctx *c, const hsflow_params &p, int kernel, int T, int flags, float coeff, float eps_thr = -1.f)
+{
+    const hsflow_info &i = c->info;
+    return GraphKey{p.mode, kernel, p.max_iter, T, i.tile_w, i.tile_h, i.threads, i.groups_per_thread, p.use_previous ? c->cur : 0,
+                    p.use_previous * kKeyUsePrev + flags, coeff, eps_thr};
+}
+
 // EPS termination without a usable sweep budget stops only on Eps < epsilon.  A positive epsilon below the fp32 limit
 // cycle of the iteration (Eps stalls around 1e-7 * |flow|) would keep the host launching for ever -- the original does
 // exactly that; here a solve (a pair, under the per-pair stop) gives up with HSFLOW_E_NOTERM (flow, iterations_done and
@@ -121,8 +130,9 @@ void pairs_to_info(hsflow_ctx *c)
 // of the budget); the one-sweep kernel runs HSFLOW_PAIR_STOP_SIMPLE_CHUNK launches between read-backs and keeps the
 // chunk's input in dUb / dVb (its ping-pong overwrites it).  Afterwards the stream is idle and hsflow_info is that of the
 // whole solve.  rerun: a witness pass ran before and proved nothing for these pairs.
-int solve_pairs_exact(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, const std::vector<int> &list, PairStart start, bool rerun)
+int solve_pairs_exact(hsflow_ctx *c, const SolveSetup &S, const std::vector<int> &list, PairStart start, bool rerun)
 {
+    const hsflow_params &p = S.eff;
     const int N = c->N, kernel = S.kernel;
     const bool multi = S.multi, strip = kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD;
     const int T = multi ? S.T : HSFLOW_PAIR_STOP_SIMPLE_CHUNK;
@@ -136,10 +146,7 @@ int solve_pairs_exact(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S
         HS_HIP(c, hipMemcpy(c->dPairs, ident.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
     }
     if (!multi && (st = reserve_start_backup(c))) return st;
-    JPlan tail;
-    const int rem = (multi && budget < (1LL << 30)) ? (int)(budget % T) : 0;
-    if (rem && !make_jplan(c, kernel, rem, p, tail)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
-    const int stride = strip ? std::max(S.plan.s.tiles, rem ? tail.s.tiles : 0) : N;
+    const int stride = strip ? std::max(S.plan.s.tiles, S.tail.T ? S.tail.s.tiles : 0) : N;
     if ((st = eps_reserve(c, T, stride, (size_t)T * N))) return st;
     int cur = c->cur; // the buffer that holds the active pairs' flow
     bool zero = start == PairStart::Zero;
@@ -158,7 +165,7 @@ int solve_pairs_exact(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S
         const int chunk = (int)std::min<long long>(T, budget - done);
         HS_HIP(c, hipMemcpyAsync(c->dPairs + N, active.data(), (size_t)n_act * sizeof(int), hipMemcpyHostToDevice, c->stream));
         const int a0 = cur;
-        const JPlan &cp = chunk == T ? S.plan : tail;
+        const JPlan &cp = chunk == T ? S.plan : S.tail;
         // the chunk's launches: the active pairs; strip / fold a row of `stride` words per sweep (every launch writes all its
         // words), the other kernels one word per (sweep, active pair), cleared first
         LaunchIo io{c->dEpsTiles, strip ? stride : n_act, 0.f, strip ? 0 : 1, c->dPairs + N, n_act};
@@ -324,7 +331,7 @@ int settle_pending(hsflow_ctx *c, int *verdict_only = nullptr)
         hsflow_params q = c->pend.params;
         const int st = prepare_solve(c, q, false, S);
         if (st) return st;
-        return solve_pairs_exact(c, q, S, unproven, q.use_previous ? PairStart::Saved : PairStart::Zero, true);
+        return solve_pairs_exact(c, S, unproven, q.use_previous ? PairStart::Saved : PairStart::Zero, true);
     }
     float last = 0.f;
     const bool gave_up = persist_gave_up(c); // a persistent launch that timed out proves nothing
@@ -585,8 +592,7 @@ int solve_classic(hsflow_ctx *c, const hsflow_params &p, bool async)
     hsflow_info &i = c->info;
     int launches = 0;
     if (p.use_graph) {
-        GraphKey key{p.mode, kernel, p.max_iter, T, i.tile_w, i.tile_h, i.threads, i.groups_per_thread, zero0 ? 0 : c->cur,
-                     p.use_previous * kKeyUsePrev + (do_deriv ? kKeyDeriv : 0) + (do_unpack ? kKeyUnpack : 0), p.alpha};
+        const GraphKey key = graph_key(c, p, kernel, T, (do_deriv ? kKeyDeriv : 0) + (do_unpack ? kKeyUnpack : 0), p.alpha);
         if ((st = run_captured(c, key, enqueue, &launches))) return st;
     } else if ((st = enqueue(&launches))) return st;
     c->coef_valid = true;
@@ -602,53 +608,113 @@ int solve_classic(hsflow_ctx *c, const hsflow_params &p, bool async)
     return HSFLOW_OK;
 }
 
-// ITER termination: a fixed sweep count, nothing on the host between launches (optionally one hipGraph).
-int solve_fixed(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Profiler &prof, bool async)
+// A pass of `sweeps` sweeps with the setup's kernel: launches of `plan` and, where the count leaves a remainder, a last
+// one of `tail`; the one-sweep kernel takes a launch per sweep.  Records nothing; the caller fills in what its pass adds.
+Pass sweeps_pass(const SolveSetup &S, int sweeps, const JPlan &plan, const JPlan &tail, bool zero)
 {
-    const int iters = (int)S.budget, T = S.T;
+    Pass P;
+    P.sweeps = sweeps;
+    P.n = S.multi ? (sweeps + plan.T - 1) / plan.T : sweeps;
+    if (S.multi) { P.plan = &plan; P.last = sweeps % plan.T ? &tail : &plan; }
+    P.coeff = S.coeff;
+    P.zero = zero;
+    return P;
+}
+
+// The plan of a budget pass's last launch.
+const JPlan &last_plan(const SolveSetup &S) { return S.tail.T ? S.tail : S.plan; }
+
+// How launch 0 of a solve's first pass is formed.  The derivative pass rides in it where the kernel can do it (not when
+// profiling: deriv_ms / jacobi_ms then keep their meaning).  The frames of hsflow_solve_async_frames_device are read in
+// place by it where it is the strip kernel with the derivative pass, else copied now, ahead of whatever reads dA / dB.
+// (Launch 0 is a launch of P.plan: a setup's T never exceeds its budget.)
+int form_first_launch(hsflow_ctx *c, const hsflow_params &p, Pass &P)
+{
+    P.deriv = needs_deriv(c, p, HSFLOW_MODE_CV);
+    P.fuse = P.deriv && !p.profile && P.plan && strip_deriv_fusable(c, *P.plan);
+    c->info.deriv_fused = P.fuse;
+    P.in_place = c->lazy.active && P.fuse && !P.persist && P.plan->kind == HSFLOW_KERNEL_STRIP;
+    return resolve_lazy_frames(c, P.in_place, &P.frames);
+}
+
+// Enqueues launches [first, last) of a pass (no host synchronisation, nothing allocated: capturable).  The range with
+// launch 0 opens the pass: the starting flow saved, the derivative kernel unless launch 0 carries that pass, a cold start
+// from buffer 0 -- u = v = 0 there means that launch 0 is TOLD its input is zero, instead of two planes cleared and read
+// back.  The range with the last launch closes it: the reduction of the Eps rows.  A later range takes c->cur as the
+// earlier one left it.
+int enqueue_pass(hsflow_ctx *c, const Pass &P, int first, int last, Profiler &prof)
+{
     int st = HSFLOW_OK;
-    JPlan tail;
-    const int rem = (S.multi && !S.persist) ? iters % T : 0;
-    if (rem && !make_jplan(c, S.kernel, rem, p, tail))
-        return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the tail launch");
-    const bool zero = !p.use_previous;
-    const bool do_deriv = needs_deriv(c, p, HSFLOW_MODE_CV);
-    c->info.deriv_fused = do_deriv && !p.profile && S.multi && strip_deriv_fusable(c, iters >= T ? S.plan : tail); // enqueue_fixed's rule
+    if (first == 0) {
+        if (P.save_start && (st = save_start(c))) return st;
+        if (P.deriv && !P.fuse) {
+            prof.begin(0);
+            HS_HIP(c, launch_deriv(c));
+            prof.end();
+        }
+        if (P.zero) c->cur = 0;
+    }
+    // launch (phase) L writes row L of the Eps rows (no clearing: every launch writes all its words, the reduction reads
+    // only those)
+    auto io_of = [&](int L) {
+        LaunchIo io = P.eps_rows ? LaunchIo{P.eps_rows + (size_t)L * P.stride, P.stride, P.thr} : default_io(c);
+        if (L == 0 && P.in_place) io.frames = &P.frames;
+        return io;
+    };
+    if (P.persist) { // the whole pass as one launch, a row of Eps words per phase
+        prof.begin(1);
+        st = enqueue_persist(c, P.plan->s, P.sweeps, P.eps, io_of(0), P.fuse, P.zero ? 1 : 0, P.coeff);
+        prof.end();
+        if (st) return st;
+    } else for (int L = first; L < last; L++) {
+        const bool is_last = L == P.n - 1;
+        const int a = c->cur, b = a ^ 1, zero_in = (L == 0 && P.zero) ? 1 : 0;
+        prof.begin(1);
+        const hipError_t e = P.plan ? launch_j(c, is_last ? *P.last : *P.plan, is_last ? P.eps_last : P.eps, io_of(L), c->dU[a], c->dV[a],
+                                               c->dU[b], c->dV[b], P.coeff, zero_in, L == 0 && P.fuse)
+                                    : launch_simple(c, false, io_of(L), c->dU[a], c->dV[a], c->dU[b], c->dV[b], P.coeff, zero_in);
+        prof.end();
+        HS_HIP(c, e);
+        c->cur = b;
+    }
+    return last == P.n && P.reduce ? eps_collect_enqueue(c, *P.reduce, P.mark) : HSFLOW_OK;
+}
+
+// Puts a solve's pass on the stream and reports its Jacobi launches.  use_graph: replayed from the graph cache
+// (run_captured), under a key of the setup, the pass and the caller's kKey* bits.  A launch 0 that reads the caller's
+// frames carries THIS submission's pointers, which a cached graph cannot: it goes out by itself, and the graph holds the
+// launches after it (none: nothing worth a graph).
+int issue_pass(hsflow_ctx *c, const SolveSetup &S, const Pass &P, int key_flags, Profiler &prof, int *launches)
+{
+    const hsflow_params &p = S.eff;
+    int st = HSFLOW_OK, first = 0;
+    const int n = *launches = P.persist ? 1 : P.n;
+    if (!p.use_graph || p.profile) {
+        if (P.persist && (st = configure_persist(c, P.plan->s, P.eps, P.fuse, P.coeff))) return st;
+        return enqueue_pass(c, P, 0, P.n, prof);
+    }
+    // (the key before anything moves c->cur)
+    const GraphKey key = graph_key(c, p, P.persist ? HSFLOW_KERNEL_PERSIST : S.kernel, S.T,
+                                   key_flags + (P.deriv ? kKeyDeriv : 0) + (P.in_place ? kKeyInPlace : 0), S.coeff, P.eps_rows ? P.thr : -1.f);
+    if (P.in_place) {
+        if ((st = enqueue_pass(c, P, 0, 1, prof)) || P.n == 1) return st;
+        first = 1;
+    }
+    return run_captured(c, key, [&](int *m) { *m = n; return enqueue_pass(c, P, first, P.n, prof); }, launches);
+}
+
+// ITER termination: a fixed sweep count, nothing on the host between launches (optionally one hipGraph).
+int solve_fixed(hsflow_ctx *c, const SolveSetup &S, Profiler &prof, bool async)
+{
+    const hsflow_params &p = S.eff;
+    const int iters = (int)S.budget;
+    int st = HSFLOW_OK;
     if (S.persist) { // buffers and phase counters: outside any capture
         if ((st = persist_reserve(c)) || (st = persist_prepare_flags(c, S.plan.s.tiles))) return st;
     }
-    // the frames of hsflow_solve_async_frames_device: read in place by the first launch where that is the strip kernel with
-    // the derivative pass, else copied now
-    const bool in_place = c->lazy.active && c->info.deriv_fused && !S.persist && (iters >= T ? S.plan : tail).kind == HSFLOW_KERNEL_STRIP;
-    hsflow_ctx::FrameRef frames;
-    if ((st = resolve_lazy_frames(c, in_place, &frames))) return st;
-    LaunchIo io = default_io(c);
-    if (in_place) io.frames = &frames;
-    int part = 0;
-    auto enqueue = [&](int *n) -> int {
-        const int e = enqueue_fixed(c, p, S.coeff, iters, S.kernel, T, &S.plan, &tail, prof, io, do_deriv, zero, S.persist, part);
-        *n = c->info.jacobi_launches;
-        return e;
-    };
-    int n = 0;
-    if (p.use_graph && !p.profile && in_place) {
-        // that launch carries this submission's pointers: issued by itself; the cached graph holds the launches after it
-        GraphKey key{p.mode, S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
-                     c->info.groups_per_thread, zero ? 0 : c->cur, p.use_previous * kKeyUsePrev + (do_deriv ? kKeyDeriv : 0) + kKeyInPlace, S.coeff};
-        part = 1;
-        if ((st = enqueue(&n))) return st;
-        part = 2;
-        if (iters > T && (st = run_captured(c, key, enqueue, &n))) return st;
-        c->info.jacobi_launches = n;
-    } else if (p.use_graph && !p.profile) {
-        GraphKey key{p.mode, S.persist ? HSFLOW_KERNEL_PERSIST : S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
-                     c->info.groups_per_thread, zero ? 0 : c->cur, p.use_previous * kKeyUsePrev + (do_deriv ? kKeyDeriv : 0), S.coeff};
-        if ((st = run_captured(c, key, enqueue, &n))) return st;
-        c->info.jacobi_launches = n;
-    } else {
-        if (S.persist && (st = configure_persist(c, S.plan.s, EpsMode::None, c->info.deriv_fused != 0, S.coeff))) return st;
-        if ((st = enqueue(&n))) return st;
-    }
+    Pass P = sweeps_pass(S, iters, S.plan, S.tail, !p.use_previous);
+    P.persist = S.persist;
+    if ((st = form_first_launch(c, p, P)) || (st = issue_pass(c, S, P, 0, prof, &c->info.jacobi_launches))) return st;
     c->coef_valid = true;
     c->coef_mode = HSFLOW_MODE_CV;
     c->info.iterations_done = iters;
@@ -697,89 +763,36 @@ float witness_threshold(double epsilon)
 // workgroup, the witness and that sweep's Eps).  Asynchronous solves run witness launches only and leave the check owed
 // (c->pend: settle_pending); their last_eps is measured if and when hsflow_get_info asks for it (c->lastl:
 // measure_last_eps).
-// tailp: the plan of a short last launch; stride: words per row; *launches: Jacobi launches enqueued.
+// stride: words per row; *launches: Jacobi launches enqueued.
 // *rerun: nothing is proven (a flat or converged input) -- the starting flow is back in place for the exact pass.
-int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, const JPlan &tailp, int stride, bool do_deriv,
-                 Profiler &prof, bool async, int *launches, bool *rerun, std::vector<int> *unproven = nullptr)
+int witness_pass(hsflow_ctx *c, const SolveSetup &S, int stride, Profiler &prof, bool async, int *launches, bool *rerun,
+                 std::vector<int> *unproven = nullptr)
 {
+    const hsflow_params &p = S.eff;
     const bool per_pair = stops_per_pair(c); // the words are reduced per pair, and each pair gets its own verdict
-    const int iters = (int)S.budget, T = S.T, cur0 = c->cur;
-    const JPlan &plan = S.plan;
+    const int iters = (int)S.budget, cur0 = c->cur;
+    const JPlan &plan = S.plan, &lastp = last_plan(S);
     int st = HSFLOW_OK;
-    const float thr = witness_threshold(p.epsilon);
     const bool persist = S.persist && async; // (prepare_solve grants it to asynchronous solves only)
-    const int n_launch = (iters + T - 1) / T; // persist: phases of the one launch; the witness words are laid out alike
-    const JPlan &lastp = iters % T ? tailp : plan;
-    const JPlan &firstp = n_launch == 1 ? lastp : plan;
     if (persist && ((st = persist_reserve(c)) || (st = persist_prepare_flags(c, plan.s.tiles)))) return st;
-    const EpsMode last_mode = async ? EpsMode::Witness : EpsMode::WitnessLast;
+    Pass P = sweeps_pass(S, iters, plan, S.tail, !p.use_previous); // (persist: its launches are the phases; the witness words are laid out alike)
+    P.persist = persist;
+    P.eps = EpsMode::Witness;
+    P.eps_last = async ? EpsMode::Witness : EpsMode::WitnessLast;
+    P.stride = stride;
+    P.thr = witness_threshold(p.epsilon);
+    P.save_start = p.use_previous != 0;
     // (persist: the tail phase keeps the plan's geometry)
-    const EpsLayout words{n_launch - 1 + (async ? 1 : 2), stride, n_launch - 1, plan_eps_stride(S.kernel, plan),
+    const EpsLayout words{P.n - 1 + (async ? 1 : 2), stride, P.n - 1, plan_eps_stride(S.kernel, plan),
                           plan_eps_stride(S.kernel, persist ? plan : lastp), per_pair ? c->N : 0};
     if ((st = eps_reserve(c, words.slots, stride, per_pair ? (size_t)words.slots * c->N : 0))) return st;
-    // the first launch also does the derivative pass where the kernel can (hs_plan_launch.hip.h)
-    const bool fuse_deriv = do_deriv && !p.profile && strip_deriv_fusable(c, firstp);
-    c->info.deriv_fused = fuse_deriv;
-    // the frames of hsflow_solve_async_frames_device: read in place by the first launch where that is the strip kernel with
-    // the derivative pass, else copied now
-    const bool in_place = c->lazy.active && fuse_deriv && !persist && firstp.kind == HSFLOW_KERNEL_STRIP;
-    hsflow_ctx::FrameRef frames;
-    if ((st = resolve_lazy_frames(c, in_place, &frames))) return st;
-    // the whole pass as one enqueue sequence (nothing allocated, nothing synchronised: capturable).  part: 0 all of it; 1 up
-    // to and including the first Jacobi launch; 2 what follows it (c->cur as part 1 left it) -- a first launch that reads
-    // the caller's frames carries this submission's pointers, so it goes out by itself and the cached graph holds the rest
-    int part = 0;
-    auto enqueue = [&](int *n) -> int {
-        if (part != 2 && p.use_previous && (st = save_start(c))) return st;
-        if (part != 2 && do_deriv && !fuse_deriv) {
-            prof.begin(0);
-            HS_HIP(c, launch_deriv(c));
-            prof.end();
-        }
-        const int zero_w = p.use_previous ? 0 : 1;
-        if (zero_w && part != 2) c->cur = 0;
-        // launch (phase) L writes row L of the witness words (no clearing: every launch writes all its words, the reduction
-        // reads only those)
-        if (persist) { // one launch, a row of witness words per phase
-            prof.begin(1);
-            const int e = enqueue_persist(c, plan.s, iters, EpsMode::Witness, LaunchIo{c->dEpsTiles, stride, thr}, fuse_deriv, zero_w, S.coeff);
-            prof.end();
-            if (e) return e;
-        } else for (int L = part == 2 ? 1 : 0; L < (part == 1 ? 1 : n_launch); L++) {
-            const bool is_last = L == n_launch - 1;
-            const int a = c->cur, b = a ^ 1;
-            LaunchIo io{c->dEpsTiles + (size_t)L * stride, stride, thr};
-            if (L == 0 && in_place) io.frames = &frames;
-            prof.begin(1);
-            hipError_t e = launch_j(c, is_last ? lastp : plan, is_last ? last_mode : EpsMode::Witness, io, c->dU[a], c->dV[a], c->dU[b],
-                                    c->dV[b], S.coeff, L == 0 ? zero_w : 0, L == 0 && fuse_deriv);
-            prof.end();
-            HS_HIP(c, e);
-            c->cur = b;
-        }
-        *n = persist ? 1 : n_launch;
-        if (part == 1) return HSFLOW_OK;
-        if (async && !c->async_reduce) return HSFLOW_OK; // the reduction of the witness words waits until somebody settles the check (settle_pending)
-        // (an asynchronous solve gets here only with the in-stream reduction on: its last workgroup writes the marker too)
-        return eps_collect_enqueue(c, words, async && c->hMark != nullptr);
-    };
-    // (a single launch read in place leaves nothing worth a graph behind it)
-    if (p.use_graph && !p.profile && !(in_place && n_launch == 1)) {
-        GraphKey key{p.mode, persist ? HSFLOW_KERNEL_PERSIST : S.kernel, iters, T, c->info.tile_w, c->info.tile_h, c->info.threads,
-                     c->info.groups_per_thread, p.use_previous ? c->cur : 0,
-                     p.use_previous * kKeyUsePrev + (do_deriv ? kKeyDeriv : 0) + (async ? kKeyAsync : 0) +
-                         (async && c->async_reduce ? kKeyAsyncReduce : 0) + (in_place ? kKeyInPlace : 0) + (per_pair ? kKeyPerPair : 0),
-                     S.coeff, thr};
-        if (in_place) {
-            part = 1;
-            if ((st = enqueue(launches))) return st;
-            part = 2;
-        }
-        if ((st = run_captured(c, key, enqueue, launches))) return st;
-    } else {
-        if (persist && (st = configure_persist(c, plan.s, EpsMode::Witness, fuse_deriv, S.coeff))) return st;
-        if ((st = enqueue(launches))) return st;
-    }
+    P.eps_rows = c->dEpsTiles;
+    // an asynchronous solve leaves the reduction of the witness words until somebody settles the check (settle_pending),
+    // unless the in-stream reduction is on: its last workgroup then writes the marker too
+    if (!async || c->async_reduce) P.reduce = &words;
+    P.mark = async && c->hMark != nullptr;
+    const int flags = (async ? kKeyAsync : 0) + (async && c->async_reduce ? kKeyAsyncReduce : 0) + (per_pair ? kKeyPerPair : 0);
+    if ((st = form_first_launch(c, p, P)) || (st = issue_pass(c, S, P, flags, prof, launches))) return st;
     c->coef_valid = true;
     c->coef_mode = HSFLOW_MODE_CV;
     if (persist) c->persist_unchecked = true;
@@ -788,8 +801,8 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
     c->sweeps_run += iters;
     if (async) { // the check is owed: hsflow_synchronize (or the next call that needs results) settles it
         // what measure_last_eps needs: the last launch again (persist: the last phase as an ordinary launch, from the third buffer)
-        const int zero_in = (n_launch == 1 && !p.use_previous && !persist) ? 1 : 0; // a single launch from zero flow
-        c->lastl = hsflow_ctx::LastLaunch{true, lastp, zero_in, S.coeff, thr, persist};
+        const int zero_in = (P.n == 1 && P.zero && !persist) ? 1 : 0; // a single launch from zero flow
+        c->lastl = hsflow_ctx::LastLaunch{true, lastp, zero_in, S.coeff, P.thr, persist};
         c->pend.active = true;
         c->pend.params = p;
         c->pend.iters = iters; c->pend.launches = *launches; c->pend.cur0 = cur0;
@@ -823,21 +836,18 @@ int witness_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, con
 // and cleared by the caller, solve_iter_eps); one read-back at the end finds the first sweep k with Eps_k < epsilon.  If
 // there is none the result stands; otherwise exactly k sweeps are re-run from the saved starting flow, which reproduces the oracle's
 // stopping sweep.  launches: those of a witness pass that proved nothing, which this pass then follows.
-int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int stride, Profiler &prof, int launches)
+int exact_pass(hsflow_ctx *c, const SolveSetup &S, int stride, Profiler &prof, int launches)
 {
+    const hsflow_params &p = S.eff;
     const int iters = (int)S.budget, T = S.T;
     int st = HSFLOW_OK, zero_in = p.use_previous ? 0 : 1, done = 0;
-    int tail_tiles = S.multi ? plan_eps_stride(S.kernel, S.plan) : 1; // words of a row of the short last launch
     if (c->probe_pairs && c->N > 1 && (st = eps_reserve(c, iters, stride, (size_t)iters * c->N))) return st;
     const bool strip_words = S.kernel == HSFLOW_KERNEL_STRIP || S.kernel == HSFLOW_KERNEL_FOLD;
     const bool pair_words = c->probe_pairs && c->N > 1 && !strip_words; // (stride = N: solve_iter_eps)
     if (zero_in) c->cur = 0;
     while (done < iters) {
         const int chunk = S.multi ? std::min(T, iters - done) : 1;
-        JPlan cp = S.plan;
-        if (S.multi && chunk != T && !make_jplan(c, S.kernel, chunk, p, cp))
-            return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
-        if (S.multi && chunk != T) tail_tiles = plan_eps_stride(S.kernel, cp);
+        const JPlan &cp = chunk == T ? S.plan : S.tail;
         const int a = c->cur, b = a ^ 1;
         const LaunchIo io{c->dEpsTiles + (size_t)done * stride, stride, 0.f, pair_words ? 1 : 0};
         prof.begin(1);
@@ -861,7 +871,7 @@ int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int s
     }
     if (c->probe_pairs && c->N > 1 && strip_words) {
         // hsflow_solve_probe_pairs: the same rows once more, per pair (the rows of a short last launch hold fewer words)
-        const EpsLayout pw{iters, stride, iters / T * T, plan_eps_stride(S.kernel, S.plan), tail_tiles, c->N};
+        const EpsLayout pw{iters, stride, iters / T * T, plan_eps_stride(S.kernel, S.plan), plan_eps_stride(S.kernel, last_plan(S)), c->N};
         if ((st = eps_collect_enqueue(c, pw))) return st;
         HS_HIP(c, hipStreamSynchronize(c->stream));
         c->sweep_eps_pairs.resize((size_t)iters * c->N);
@@ -872,16 +882,15 @@ int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int s
     if (hit >= 0 && hit + 1 < iters) { // converged early: redo exactly hit+1 sweeps from the start
         const int k = hit + 1;
         if (p.use_previous && (st = restore_start(c))) return st;
-        JPlan kp, kt;
-        int Tk = 1;
+        JPlan kp, kt; // (a data-dependent length: planned on demand)
         if (S.multi) {
-            Tk = std::min(T, k);
+            const int Tk = std::min(T, k);
             if (!make_jplan(c, S.kernel, Tk, p, kp)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the re-run");
             if (k % Tk && !make_jplan(c, S.kernel, k % Tk, p, kt)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the re-run tail");
         }
-        st = enqueue_fixed(c, p, S.coeff, k, S.kernel, Tk, &kp, &kt, prof, default_io(c), false, !p.use_previous);
-        if (st) return st;
-        launches += c->info.jacobi_launches;
+        const Pass rerun = sweeps_pass(S, k, kp, kt, !p.use_previous);
+        if ((st = enqueue_pass(c, rerun, 0, rerun.n, prof))) return st;
+        launches += rerun.n;
         c->sweeps_run += k;
         HS_HIP(c, hipStreamSynchronize(c->stream));
         c->info.iterations_done = k;
@@ -896,71 +905,58 @@ int exact_pass(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, int s
 
 // Per-pair stop without a witness pass (the simple and the LDS-tile kernel, EPS alone): the derivative pass for all pairs,
 // then every pair through the exact pass from the flow it starts with.
-int solve_pairs_all(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, bool do_deriv)
+int solve_pairs_all(hsflow_ctx *c, const SolveSetup &S)
 {
+    const hsflow_params &p = S.eff;
     int st = resolve_lazy_frames(c, false);
     if (st) return st;
-    if (do_deriv) HS_HIP(c, launch_deriv(c));
+    if (needs_deriv(c, p, HSFLOW_MODE_CV)) HS_HIP(c, launch_deriv(c));
     c->coef_valid = true;
     c->coef_mode = HSFLOW_MODE_CV;
     c->pair_res.assign((size_t)c->N, hsflow_ctx::PairResult());
     c->info.jacobi_launches = 0;
     std::vector<int> all((size_t)c->N);
     for (int i = 0; i < c->N; i++) all[(size_t)i] = i;
-    return solve_pairs_exact(c, p, S, all, p.use_previous ? PairStart::Current : PairStart::Zero, false);
+    return solve_pairs_exact(c, S, all, p.use_previous ? PairStart::Current : PairStart::Zero, false);
 }
 
 // ITER|EPS -- the way the reference calls the solver (OpticalFlowOpenCV.cpp:29).  On real image pairs Eps never drops
 // below 1e-6 within the sweep budget, so the budget is run SPECULATIVELY wherever the kernel has a witness mode
 // (witness_pass); the exact pass measures every sweep where there is none, where a solve is being settled
 // (force_exact) and where the witness proved nothing.
-int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Profiler &prof, bool async)
+int solve_iter_eps(hsflow_ctx *c, const SolveSetup &S, Profiler &prof, bool async)
 {
-    const int iters = (int)S.budget, T = S.T, kernel = S.kernel;
+    const hsflow_params &p = S.eff;
+    const int iters = (int)S.budget, kernel = S.kernel;
     int st = HSFLOW_OK;
-    bool witness = (kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD) && !c->force_exact && strip_has_witness(S.plan);
-    const bool do_deriv = needs_deriv(c, p, HSFLOW_MODE_CV);
     if (p.use_previous && (st = reserve_start_backup(c))) return st; // the starting flow is kept (save_start)
     // every launch of this solve uses the same number of workgroups or fewer (tail): stride = max
     int stride = S.multi ? plan_eps_stride(kernel, S.plan) : 1;
     // hsflow_solve_probe_pairs on the simple / LDS-tile kernel: one word per (sweep, pair) instead of one per sweep
     const bool pair_words = c->probe_pairs && c->N > 1 && kernel != HSFLOW_KERNEL_STRIP && kernel != HSFLOW_KERNEL_FOLD;
     if (pair_words) stride = c->N;
-    JPlan tailp;
-    if (S.multi && iters % T) {
-        if (!make_jplan(c, kernel, iters % T, p, tailp)) return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
-        if (witness && !strip_has_witness(tailp)) { // as in prepare_solve
-            JPlan alt;
-            if (make_witness_jplan(c, kernel, iters % T, p, alt)) tailp = alt;
-        }
-        stride = std::max(stride, plan_eps_stride(kernel, tailp));
-        // (a tail of one sweep is measured, not witnessed: the synchronous pass's WitnessLast; an asynchronous pass needs it able)
-        if (witness && !S.persist && (async || iters % T > 1) && !strip_has_witness(tailp)) witness = false; // (persist: the tail phase keeps the plan's geometry)
-    }
-    if (async && !witness)
-        return fail(c, HSFLOW_E_ARG, "solve_async with ITER|EPS: this launch plan (core tile thinner than a strip) cannot run witness launches; "
-                                     "use hsflow_solve or other tuning parameters");
+    if (S.tail.T) stride = std::max(stride, plan_eps_stride(kernel, S.tail));
     int launches = 0;
     if (stops_per_pair(c)) { // every pair on its own Eps: the pairs the witness pass could not vouch for, or all of them
         std::vector<int> list;
-        if (witness) {
+        if (S.witness) {
             bool rerun = false;
-            if ((st = witness_pass(c, p, S, tailp, stride, do_deriv, prof, async, &launches, &rerun, &list)) || !rerun) return st;
-            st = solve_pairs_exact(c, p, S, list, p.use_previous ? PairStart::Saved : PairStart::Zero, true);
+            if ((st = witness_pass(c, S, stride, prof, async, &launches, &rerun, &list)) || !rerun) return st;
+            st = solve_pairs_exact(c, S, list, p.use_previous ? PairStart::Saved : PairStart::Zero, true);
             prof.collect(); // (profile = 1: the times of the witness pass; the chunk launches behind it are not bracketed)
             return st;
         }
-        return solve_pairs_all(c, p, S, do_deriv);
+        return solve_pairs_all(c, S);
     }
-    if (witness) {
+    if (S.witness) {
         bool rerun = false;
-        if ((st = witness_pass(c, p, S, tailp, stride, do_deriv, prof, async, &launches, &rerun)) || !rerun) return st;
+        if ((st = witness_pass(c, S, stride, prof, async, &launches, &rerun)) || !rerun) return st;
         if ((st = eps_prepare(c, iters, stride))) return st;
     } else {
         if ((st = resolve_lazy_frames(c, false))) return st;
         if (p.use_previous && (st = save_start(c))) return st;
         if ((st = eps_prepare(c, iters, stride))) return st;
-        if (do_deriv) {
+        if (needs_deriv(c, p, HSFLOW_MODE_CV)) {
             prof.begin(0);
             HS_HIP(c, launch_deriv(c));
             prof.end();
@@ -968,7 +964,7 @@ int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, P
         c->coef_valid = true;
         c->coef_mode = HSFLOW_MODE_CV;
     }
-    return exact_pass(c, p, S, stride, prof, launches);
+    return exact_pass(c, S, stride, prof, launches);
 }
 
 
@@ -976,8 +972,9 @@ int solve_iter_eps(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, P
 // is produced per sweep by the kernel; the host looks at it after every chunk and, if the
 // threshold was crossed inside the chunk, replays the chunk up to that sweep (its input buffer
 // is still intact), which reproduces the oracle's stopping sweep exactly.
-int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S, Profiler &prof)
+int solve_eps_chunks(hsflow_ctx *c, const SolveSetup &S, Profiler &prof)
 {
+    const hsflow_params &p = S.eff;
     const int kernel = S.kernel, T = S.T;
     const bool multi = S.multi;
     const long long budget = S.budget;
@@ -1002,9 +999,7 @@ int solve_eps_chunks(hsflow_ctx *c, const hsflow_params &p, const SolveSetup &S,
     bool stalled = false;
     while (!stop) {
         const int chunk = (int)std::min<long long>(T, budget - done);
-        JPlan cp = S.plan;
-        if (multi && chunk != T && !make_jplan(c, kernel, chunk, p, cp))
-            return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for a chunk");
+        const JPlan &cp = chunk == T ? S.plan : S.tail;
         const int a = c->cur, b = a ^ 1;
         const int n = multi ? chunk : 1;
         const int stride = multi ? plan_eps_stride(kernel, cp) : 1;
@@ -1118,8 +1113,19 @@ int prepare_solve(hsflow_ctx *c, const hsflow_params &p, bool async, SolveSetup 
     const long long budget = (use_iter && p.max_iter > 0) ? p.max_iter : (1LL << 40);
 
     int T = 1;
-    JPlan plan;
+    JPlan plan, tail;
     hsflow_params eff = p;
+    // ITER|EPS with a sweep budget on a kernel with a witness mode
+    const bool spec = use_eps && use_iter && p.max_iter > 0 && (kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD);
+    // It runs witness launches, which watch an edge row of each strip: a plan whose core tile is thinner
+    // than a strip may have no wavefront with a core row there (thin frames, very short launches); another shape
+    // then takes its place as far as the caller left rows / wavefronts open (make_witness_jplan).
+    auto plan_sweeps = [&](int sweeps, JPlan &out) {
+        if (!make_jplan(c, kernel, sweeps, p, out)) return false;
+        JPlan alt;
+        if (spec && !strip_has_witness(out) && make_witness_jplan(c, kernel, sweeps, p, alt)) out = alt;
+        return true;
+    };
     if (multi) {
         const int horizon = budget > (1 << 30) ? 64 : (int)budget; // EPS-only runs: plan for chunks
         if (p.fuse_steps > 0) T = std::min(p.fuse_steps, kMaxFuse);
@@ -1132,16 +1138,11 @@ int prepare_solve(hsflow_ctx *c, const hsflow_params &p, bool async, SolveSetup 
         // constant term a pixel can have grow like sqrt(lambda); beyond lambda = 1e20 keep the launches
         // short so that 4^(T+1) times those stays far inside the float range.
         if ((kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD) && coeff < 1e-20f) T = std::min(T, 8);
-        if (!make_jplan(c, kernel, T, p, plan))
+        if (!plan_sweeps(T, plan))
             return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the requested tile/threads/rows/fuse_steps");
-        // ITER|EPS runs witness launches, which watch an edge row of each strip: a plan whose core tile is thinner
-        // than a strip may have no wavefront with a core row there (thin frames, very short launches); another shape
-        // then takes its place as far as the caller left rows / wavefronts open (make_witness_jplan).
-        if (use_eps && use_iter && p.max_iter > 0 && (kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD) &&
-            !strip_has_witness(plan)) {
-            JPlan alt;
-            if (make_witness_jplan(c, kernel, T, p, alt)) plan = alt;
-        }
+        // the short last launch of a real sweep budget: planned here, once per parameter set like the full launch
+        if (use_iter && p.max_iter > 0 && budget % T && !plan_sweeps((int)(budget % T), tail))
+            return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the tail launch");
         plan_to_info(c, plan);
     } else {
         c->info.fuse_steps = 1; c->info.tile_w = c->info.tile_h = 0; c->info.threads = 256;
@@ -1158,11 +1159,19 @@ int prepare_solve(hsflow_ctx *c, const hsflow_params &p, bool async, SolveSetup 
         const char *why = !(use_iter && p.max_iter > 0 && budget <= (1 << 16)) ? "needs a sweep budget (ITER)"
                                                                                : persist_obstacle(c, plan.s, (int)budget, p, async, use_eps);
         if (!why && use_eps && !strip_has_witness(plan)) why = "this launch plan cannot run witness phases";
+        if (!why && use_eps && stops_per_pair(c)) why = "every pair of the batch stops on its own"; // (solve_impl_inner says more when it was asked for)
         if (!why) persist = true;
         else if (persist_asked) return fail(c, HSFLOW_E_SIZE, std::string("HSFLOW_KERNEL_PERSIST: ") + why);
     }
     c->info.persistent = persist ? (int)((budget + T - 1) / T) : 0;
-    S = SolveSetup{coeff, kernel, multi, use_iter, use_eps, budget, T, plan, persist, eff};
+    // The budget runs as witness launches where plan and tail can (a tail of one sweep is measured, not witnessed: the
+    // synchronous pass's WitnessLast; an asynchronous pass needs it able; persist: the tail phase keeps the plan's geometry)
+    const bool witness = spec && !c->force_exact && strip_has_witness(plan) &&
+                         !(tail.T && !persist && (async || tail.T > 1) && !strip_has_witness(tail));
+    if (async && use_eps && !witness)
+        return fail(c, HSFLOW_E_ARG, "solve_async with ITER|EPS: this launch plan (core tile thinner than a strip) cannot run witness launches; "
+                                     "use hsflow_solve or other tuning parameters");
+    S = SolveSetup{coeff, kernel, multi, use_iter, use_eps, budget, T, plan, tail, witness, persist, eff};
     return HSFLOW_OK;
 }
 
@@ -1251,20 +1260,16 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
             c->plan_cache.push_back(PlanEntry{key, S, c->info});
         }
     }
-    if (stops_per_pair(c) && S.use_eps && S.persist) { // (HSFLOW_PERSIST_AUTO: AUTO may not take the one launch here either)
-        S.persist = false;
-        c->info.persistent = 0;
-    }
     c->info.deriv_ms = c->info.jacobi_ms = c->info.solve_ms = 0.f;
     c->info.last_eps = 0.f;
     Profiler prof{c, p.profile != 0};
-    if (!S.use_eps) return solve_fixed(c, S.eff, S, prof, async);
+    if (!S.use_eps) return solve_fixed(c, S, prof, async);
     constexpr long long kSpecMax = 1 << 16; // speculative ITER|EPS: the whole budget in one go
-    if (S.use_iter && p.max_iter > 0 && S.budget <= kSpecMax) return solve_iter_eps(c, S.eff, S, prof, async);
+    if (S.use_iter && p.max_iter > 0 && S.budget <= kSpecMax) return solve_iter_eps(c, S, prof, async);
     if (stops_per_pair(c)) // (no budget to speculate on: every pair through its own chunk loop, stall rule included)
-        return solve_pairs_all(c, S.eff, S, needs_deriv(c, p, HSFLOW_MODE_CV));
+        return solve_pairs_all(c, S);
     if ((st = resolve_lazy_frames(c, false))) return st;
-    return solve_eps_chunks(c, S.eff, S, prof);
+    return solve_eps_chunks(c, S, prof);
 }
 
 int copy_frame_in(hsflow_ctx *c, uint8_t *dst, const void *src, size_t stride, hipMemcpyKind kind, bool sync)

@@ -121,10 +121,11 @@ def test_switches_do_not_change_a_bit_and_the_flow_view_is_the_flow(hs, gpu_ok):
         assert lib.hsflow_flow_view_device(ctx._h, 2, ctypes.byref(pu), ctypes.byref(pv), ctypes.byref(sb)) == hs._lib.E_ARG
 
 
-def test_cached_plans_do_not_carry_a_callers_flags(hs, gpu_ok):
+@pytest.mark.parametrize("it", [24, 57])   # one launch of 24 sweeps; 22 + 22 + 13: the cached setup carries a tail plan too
+def test_cached_plans_do_not_carry_a_callers_flags(hs, gpu_ok, it):
     """A context plans once per parameter set (the planner's sweep costs tens of microseconds per solve); what does not enter the
     plan -- use_previous, reuse_derivatives, use_graph, profile -- must still be honoured, and checked, on every call."""
-    W, H, it = 700, 300, 24
+    W, H = 700, 300
     A, B = synth.translating_pair(W, H, seed=17)
     A2, B2 = synth.translating_pair(W, H, seed=18)
 

@@ -51,6 +51,9 @@ CASES = [
     (600, 480, 4, 2, HEADLINE, False),                                                               # AUTO: the folded kernel -> copy
     (1920, 1080, 2, 2, dict(lam=1.0, max_iter=20, term_type=ITER, kernel=2, use_graph=True), False),  # LDS-tile kernel -> copy
     (1920, 1080, 2, 2, dict(mode=1, alpha=15.0, max_iter=20, term_type=ITER, use_graph=True), False),  # classic mode -> copy
+    # the pipeline's own shape with a tail: launch 0 in place and alone, the cached graph holds 20 + 17 (ITER|EPS: a witness tail)
+    (600, 480, 4, 4, dict(lam=1.0, max_iter=57, term_type=ITER | EPS, epsilon=EPS6, use_graph=True), True),
+    (600, 480, 4, 4, dict(lam=1.0, max_iter=57, term_type=ITER, use_graph=True), True),
 ]
 
 
