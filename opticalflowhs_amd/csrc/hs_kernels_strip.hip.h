@@ -760,10 +760,16 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     // One row: neighbour sums from the cross sums of its two boundaries (sc below, sp above), update in place.
     // A row at distance d from the core is only needed through sweep T-1-d (trapezoid): later sweeps skip it
     // (wave-uniform branch), which trims the redundant halo work by about half.  PE = parity of the row's pixel p0.
-#define HS_ACT(r) (rdist[r] <= last)
+    // The guards read ONE scalar per sweep: bit r of `act` = register row r is still swept, bit r of `actb` = row r or
+    // row r + 1 is (the boundary between them is needed).  The rows of a strip that are still swept are an interval of
+    // its image rows, i = n0 + s .. R-1 - (m0 + s) (n0, m0 below: from the strip's place in the region; a strip of core
+    // rows has both far below zero and never loses a row), so the mask is two 64-bit tables of ones shifted by s and met
+    // in one word -- no compare per row.  The optimiser must not see through it (it turns the bits back into
+    // one compare and branch per row and boundary): the mask passes through an empty asm, as the lane number does.
+#define HS_ACT(r) (((act >> (r)) & 1u) != 0u)
 #define HS_ROW(r, PE, SC, SP)                                                                      \
     do {                                                                                           \
-        if (HS_ACT(r)) {                                                                           \
+        if (((actr >> (r)) & 1u) != 0u) {                                                          \
             f2 ouP, ouQ, ovP, ovQ;                                                                 \
             if (EM == 1) { ouP = uP[r]; ouQ = uQ[r]; ovP = vP[r]; ovQ = vQ[r]; }                   \
             if (HS_DIAG & 8) uP[r] += SC.uP + SP.uP;                                               \
@@ -790,7 +796,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     // cross sums of the boundary below register row A (row B underneath), needed while either row is still swept
 #define HS_CROSS(S, PE, A, B)                                                                      \
     do {                                                                                           \
-        if (HS_ACT(A) || HS_ACT(B)) {                                                              \
+        if (((actb >> (A)) & 1u) != 0u) { /* B is A + 1 */                                         \
             if (HS_DIAG & 8) S.uP = uP[A] + uP[B];                                                 \
             else cross_rows<PE>(S, uP[A], uQ[A], vP[A], vQ[A], uP[B], uQ[B], vP[B], vQ[B]);        \
         }                                                                                          \
@@ -835,6 +841,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     // Sweeps of the current phase: the launch's T, except in the last phase of a persistent launch (PERSIST).  A shorter
     // phase simply starts further down the trapezoid: rows further than Tp - 1 from the core are never swept.
     int Tp = g.T;
+    unsigned long long act_lo = 0, act_hi = 0; // the trapezoid's tables of the current phase (HS_ACT)
     // One sweep.  EM is the Eps mode of THIS sweep: the launch's own (EPS 0, 1, 2), or for EPS == 3 witness
     // (2) in all sweeps but the last and measured (1) in the last -- a second copy of the sweep code after the
     // loop, so that the loop keeps the registers of the witness kernel.  E0 = parity of pixel p0 of register
@@ -847,10 +854,14 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     auto sweep = [&](const int s, auto em_tag) __attribute__((always_inline)) {
         constexpr int EM = decltype(em_tag)::value;
 #if HS_DIAG & 4 /* diagnostic build: every row swept in every sweep (no trapezoid) */
-        const int last = 1 << 20;
+        unsigned act = ~0u;
 #else
-        const int last = Tp - 1 - s; // rows with rdist <= last are still swept
+        unsigned act = (unsigned)((act_lo << s) >> 32) & (unsigned)(act_hi >> (24 + s)); // (bits from R on: never looked at)
 #endif
+        unsigned actb = act | (act >> 1), actr = act; // (actr: the row's own guard, apart from the edge rows' first use of act)
+        // (not in the every-sweep kernels, which are off the hot path: at R = 6 they hold the sweep counter in a vector
+        // register, and the asm's scalar operand cannot be had from it)
+        if constexpr (EPS != 1) asm volatile("" : "+s"(act), "+s"(actb), "+s"(actr));
         // (scaled state: this sweep takes the flow from scale 4^s to 4^(s+1))
         // eps_thr * 4^(s+1) by integer arithmetic on the exponent: scalar instructions only (v_ldexp + v_readfirstlane put
         // a vector-to-scalar round trip into every sweep).  Exact for a normal eps_thr; eps_thr = 0 or a product beyond
@@ -953,6 +964,13 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
         seen_n = 0;
         wit_cnt = wit_cnt0;
         if (stamps && ph == 0) pt_first = pt0 = __builtin_amdgcn_s_memtime();
+    }
+    {   // The trapezoid of this phase: row j of the region is swept while T - j <= Tp-1 - s and j - (T + CH - 1) <= Tp-1 - s.
+        // Clamped to what the 32 sweeps a launch can have (kMaxFuse) tell apart, so that the tables fit 64 bits (R <= 8).
+        static_assert(R <= 8, "the trapezoid tables hold 8 rows per lane");
+        const int n0 = min(max(g.T - Tp + 1 - w * R, -32), R), m0 = min(max(w * R + R + 1 - g.T - g.CH - Tp, -32), R);
+        act_lo = ~0ull << (32 + (rev ? m0 : n0));     // ones from bit 32 + lo: << s, upper word = the bits r >= lo + s
+        act_hi = ~0ull >> (40 - R + (rev ? n0 : m0)); // ones up to bit 24 + R-1 - hi: >> (24 + s) = the bits r <= R-1 - (hi + s)
     }
     HS_PUBLISH(0, lane_id());
     __syncthreads();
