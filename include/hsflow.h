@@ -13,6 +13,12 @@
  *   hsflow_set_frames_u8[_device] ....... clEnqueueWriteBuffer of inputImageBuffer1/2
  *                                          (HSOpticalFlowOpenCL.cpp:339-357); frames are what
  *                                          readInputImage produced (:4-44) but kept as u8
+ *   hsflow_set_frames_device_ex ......... cvCvtColor + cvSmooth of both frames (OpticalFlowOpenCV.cpp:17,20,27-28) on
+ *                                          frames that already lie in device memory, one launch per pair
+ *   hsflow_push_frame[_device]_ex ....... one turn of the camera loop's frame handling (OpticalFlowOpenCV.cpp:85,92-93,
+ *                                          118): the blurred new frame becomes the old one and is blurred again
+ *   hsflow_pipeline_submit_device_ex .... the same pre-processing in front of every pair of a resident stream
+ *   hsflow_preprocess_frame_host ........ the arithmetic of both steps on the host, for checking
  *   hsflow_solve / hsflow_solve_async ... runDerivatives() + iterations x runCLKernels()
  *                                          (HSOpticalFlowOpenCL.cpp:321-474, :476-679, loop :749-751)
  *                                          and, argument for argument, cvCalcOpticalFlowHS
@@ -45,7 +51,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 8 /* 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 9 /* 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -299,6 +305,42 @@ int hsflow_set_frames_gray8_blur_async(hsflow_ctx *ctx, int pair, const uint8_t 
 /* Streaming (camera loop, HSOpticalFlowOpenCL.cpp:810-834): the current frame becomes the
  * previous one on the device and only the new frame is uploaded. */
 int hsflow_push_frame_u8(hsflow_ctx *ctx, int pair, const uint8_t *next, size_t next_stride);
+
+/* Frames in another layout (the values also name the layouts a pair pipeline takes, below); the CPU route's
+ * pre-processing (OpticalFlowOpenCV.cpp:17-28) then runs on the device. */
+#define HSFLOW_FRAMES_GRAY8 0      /* u8 gray, as is                                          */
+#define HSFLOW_FRAMES_GRAY8_BLUR 1 /* u8 gray, 3x3 box blur on the device (cvSmooth CV_BLUR)  */
+#define HSFLOW_FRAMES_BGR8 2       /* 8-bit BGR (3 bytes / pixel): BGR->gray on the device    */
+#define HSFLOW_FRAMES_BGR8_BLUR 3  /* BGR->gray and blur: what runFromImg does before solving */
+/* Frames ALREADY IN DEVICE MEMORY on ctx's device, in any of the four layouts; row strides in bytes (>= width for gray,
+ * >= 3 * width for BGR), any alignment.  Only enqueued on ctx's stream, like hsflow_set_frames_u8_device, which is what
+ * HSFLOW_FRAMES_GRAY8 runs.  The other three are ONE launch per pair: both frames go through gray conversion and blur
+ * in registers (a lane walks a strip of HSFLOW_PRE_STRIP_ROWS rows with a window of three rows of sums) and land in the
+ * context's planes -- no gray plane in between, every source byte read once plus one halo row per strip end.  Sources
+ * whose base and stride are multiples of 4 are read a word at a time, others byte by byte; the bytes written are those
+ * of hsflow_set_frames_bgr8 / hsflow_set_frames_gray8_blur from the same pixels (hsflow_preprocess_frame_host).
+ * HSFLOW_PRE_UNFUSED=1 in the environment when the context is created: the kernels of the host-pointer entries instead,
+ * two launches per frame through a gray scratch plane (A/B runs, and the fallback).
+ * HSFLOW_E_ARG: null pointer, unknown format; HSFLOW_E_SIZE: a stride below the row's bytes. */
+#define HSFLOW_PRE_STRIP_ROWS 8 /* rows a lane of the fused pre-processing kernel walks (a design constant) */
+int hsflow_set_frames_device_ex(hsflow_ctx *ctx, int pair, int format, const void *d_prev, size_t prev_stride,
+                                const void *d_curr, size_t curr_stride);
+/* The reference's camera sequence on the device: prev := reblur_prev ? box_blur3(curr) : curr, then
+ * curr := pre(format, next).  reblur_prev = 1 with a *_BLUR format is the reference's loop (OpticalFlowOpenCV.cpp:92-93,
+ * 118: cvSmooth works in place and the blurred new frame becomes the next old one, so from the second pair on the old
+ * frame enters the solver blurred twice); reblur_prev = 0 with HSFLOW_FRAMES_GRAY8 is hsflow_push_frame_u8.  Two launches
+ * in stream order into the planes the context has always had (cached graphs stay valid).  hsflow_push_frame_ex takes
+ * `next` from host memory, uploads it into the context's scratch and returns when everything is complete;
+ * hsflow_push_frame_device_ex takes it from device memory and only enqueues.
+ * HSFLOW_E_ARG: null pointer, unknown format, reblur_prev not 0 or 1; HSFLOW_E_SIZE: stride below the row's bytes;
+ * HSFLOW_E_STATE: no frames were set before. */
+int hsflow_push_frame_ex(hsflow_ctx *ctx, int pair, int format, const uint8_t *next, size_t stride, int reblur_prev);
+int hsflow_push_frame_device_ex(hsflow_ctx *ctx, int pair, int format, const void *d_next, size_t stride, int reblur_prev);
+/* The rule itself on the host, no device needed: dst = pre(format, src), bit for bit what the device entries write
+ * (csrc/hs_pre_rule.h, one header for the kernel and for this).  src and dst must not overlap; dst_stride >= width.
+ * HSFLOW_E_ARG: null pointer, unknown format; HSFLOW_E_SIZE: non-positive size, a stride below the row's bytes. */
+int hsflow_preprocess_frame_host(int format, const uint8_t *src, size_t src_stride, int width, int height,
+                                 uint8_t *dst, size_t dst_stride);
 
 /* --- solve -------------------------------------------------------------------------------- */
 
@@ -566,10 +608,7 @@ int hsflow_pipeline_submit(hsflow_pipeline *pl, const uint8_t *prev, size_t prev
                            float *v, size_t v_stride, const hsflow_params *params, uint64_t *ticket);
 /* Same with the frames in another layout; the CPU route's pre-processing (OpticalFlowOpenCV.cpp:17-28)
  * then runs on the device as part of the pair's queue. */
-#define HSFLOW_FRAMES_GRAY8 0      /* u8 gray, as hsflow_pipeline_submit                      */
-#define HSFLOW_FRAMES_GRAY8_BLUR 1 /* u8 gray, 3x3 box blur on the device (cvSmooth CV_BLUR)  */
-#define HSFLOW_FRAMES_BGR8 2       /* 8-bit BGR (3 bytes / pixel): BGR->gray on the device    */
-#define HSFLOW_FRAMES_BGR8_BLUR 3  /* BGR->gray and blur: what runFromImg does before solving */
+/* (format: HSFLOW_FRAMES_*, above; HSFLOW_FRAMES_GRAY8 is hsflow_pipeline_submit) */
 int hsflow_pipeline_submit_ex(hsflow_pipeline *pl, int format, const uint8_t *prev, size_t prev_stride,
                               const uint8_t *curr, size_t curr_stride, float *u, size_t u_stride,
                               float *v, size_t v_stride, const hsflow_params *params, uint64_t *ticket);
@@ -585,6 +624,13 @@ int hsflow_pipeline_submit_ex(hsflow_pipeline *pl, int format, const uint8_t *pr
  * any later call on the pipeline has returned that waited for this ticket. */
 int hsflow_pipeline_submit_device(hsflow_pipeline *pl, const void *d_prev, size_t prev_stride, const void *d_curr,
                                   size_t curr_stride, const hsflow_params *params, uint64_t *ticket);
+/* The same for resident frames in any HSFLOW_FRAMES_* layout.  HSFLOW_FRAMES_GRAY8 is hsflow_pipeline_submit_device, the
+ * in-place read included.  The other three run hsflow_set_frames_device_ex and hsflow_solve_async on the slot: the fused
+ * pre-processing launch takes the place of the copy kernel in the pair's chain, and everything behind it (tickets, the
+ * re-solve of a pair whose early stop fired, hsflow_pipeline_frames_u8 / _render / _verify) works from the slot's
+ * pre-processed planes, as after hsflow_pipeline_submit_ex.  The caller's buffers: as for hsflow_pipeline_submit_device. */
+int hsflow_pipeline_submit_device_ex(hsflow_pipeline *pl, int format, const void *d_prev, size_t prev_stride, const void *d_curr,
+                                     size_t curr_stride, const hsflow_params *params, uint64_t *ticket);
 /* wait(ticket) + where that pair's flow lies (hsflow_flow_view_device of its slot): valid until `depth` further
  * pairs have been submitted.  HSFLOW_E_STATE if the slot has been reused already. */
 int hsflow_pipeline_flow_device(hsflow_pipeline *pl, uint64_t ticket, const float **d_u, const float **d_v, size_t *stride_bytes);

@@ -16,6 +16,7 @@ MODE_CV, MODE_CLASSIC, MODE_CLASSIC_AS_SHIPPED = 0, 1, 2
 KERNEL_AUTO, KERNEL_SIMPLE, KERNEL_FUSED, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST = 0, 1, 2, 3, 4, 5
 FRAMES_GRAY8, FRAMES_GRAY8_BLUR, FRAMES_BGR8, FRAMES_BGR8_BLUR = 0, 1, 2, 3
 RENDER_CV, RENDER_CL = 0, 1
+FRAME_FORMATS = {"gray": FRAMES_GRAY8, "gray_blur": FRAMES_GRAY8_BLUR, "bgr": FRAMES_BGR8, "bgr_blur": FRAMES_BGR8_BLUR}
 
 
 class HsflowParams(ctypes.Structure):
@@ -75,6 +76,7 @@ class HsflowPairResult(ctypes.Structure):
 
 VERIFY_TINY = 1e-30  # HSFLOW_VERIFY_TINY
 PAIR_STOP_SIMPLE_CHUNK = 32  # HSFLOW_PAIR_STOP_SIMPLE_CHUNK
+PRE_STRIP_ROWS = 8  # HSFLOW_PRE_STRIP_ROWS
 
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 _pp = ctypes.POINTER(HsflowParams)
@@ -104,6 +106,10 @@ PROTOTYPES = {
     "hsflow_set_frames_bgr8_async": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _i]),
     "hsflow_set_frames_gray8_blur_async": (_i, [_vp, _i, _vp, _sz, _vp, _sz]),
     "hsflow_push_frame_u8": (_i, [_vp, _i, _vp, _sz]),
+    "hsflow_set_frames_device_ex": (_i, [_vp, _i, _i, _vp, _sz, _vp, _sz]),
+    "hsflow_push_frame_ex": (_i, [_vp, _i, _i, _vp, _sz, _i]),
+    "hsflow_push_frame_device_ex": (_i, [_vp, _i, _i, _vp, _sz, _i]),
+    "hsflow_preprocess_frame_host": (_i, [_i, _vp, _sz, _i, _i, _vp, _sz]),
     "hsflow_solve": (_i, [_vp, _pp]),
     "hsflow_solve_async": (_i, [_vp, _pp]),
     "hsflow_solve_async_frames_device": (_i, [_vp, _vp, _sz, _vp, _sz, _pp]),
@@ -143,6 +149,7 @@ PROTOTYPES = {
     "hsflow_pipeline_submit": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _pp, ctypes.POINTER(ctypes.c_uint64)]),
     "hsflow_pipeline_submit_ex": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _pp, ctypes.POINTER(ctypes.c_uint64)]),
     "hsflow_pipeline_submit_device": (_i, [_vp, _vp, _sz, _vp, _sz, _pp, ctypes.POINTER(ctypes.c_uint64)]),
+    "hsflow_pipeline_submit_device_ex": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _pp, ctypes.POINTER(ctypes.c_uint64)]),
     "hsflow_pipeline_flow_device": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
     "hsflow_pipeline_wait": (_i, [_vp, ctypes.c_uint64]),
     "hsflow_pipeline_render": (_i, [_vp, ctypes.c_uint64, _rp, _vp, _sz]),

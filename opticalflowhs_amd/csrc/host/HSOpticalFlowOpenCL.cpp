@@ -281,7 +281,8 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
 // capture device ($HSFLOW_CAMERA_DIR, see camera_frame).  Faithful to the reference's loop, including
 // its quirk: cvSmooth works in place and the blurred new frame becomes the next old frame (:93,:117),
 // so from the second pair on the old frame enters the solver blurred TWICE.  The blurred frames never
-// leave the device: the new one is read back only to be handed in again as the next old one.
+// leave the device: from the second pair on hsflow_push_frame_ex blurs the resident new frame once more into
+// the old one's plane and only the next gray frame is uploaded.
 int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
 {
     pnm::Image frame, gold, gnew;
@@ -297,19 +298,17 @@ int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
     const bool on_device = render_on_device();
     std::vector<float> u, v;
     if (!on_device) { u.resize((size_t)W * H); v.resize((size_t)W * H); }
-    std::vector<uint8_t> scratch((size_t)W * H);
     double total = 0.0;
     int count = 0, verdict = SDK_SUCCESS;
     for (int i = 1; pnm::load_image(camera_frame(i), frame); i++) {
         pnm::to_gray(frame, gnew);
         if (gnew.width != W || gnew.height != H) break;
         const double t0 = now_ms();
-        int st = hsflow_set_frames_gray8_blur(ctx, 0, gold.data.data(), (size_t)W, gnew.data.data(), (size_t)W); // :92-93
+        int st = i == 1 ? hsflow_set_frames_gray8_blur(ctx, 0, gold.data.data(), (size_t)W, gnew.data.data(), (size_t)W) // :92-93
+                        : hsflow_push_frame_ex(ctx, 0, HSFLOW_FRAMES_GRAY8_BLUR, gnew.data.data(), (size_t)W, 1); // imgOld = imgNew (:117), blurred again (:92)
         if (st == HSFLOW_OK) st = hsflow_solve(ctx, &p);
         if (st == HSFLOW_OK && !on_device) st = hsflow_get_flow(ctx, 0, u.data(), (size_t)W * 4, v.data(), (size_t)W * 4);
         total += now_ms() - t0;
-        // imgOld = imgNew (:117): the blurred new frame
-        if (st == HSFLOW_OK) st = hsflow_get_frames_u8(ctx, 0, scratch.data(), (size_t)W, gold.data.data(), (size_t)W);
         if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; hsflow_destroy(ctx); return 1; }
         count++;
         hsflow_verify_report report;

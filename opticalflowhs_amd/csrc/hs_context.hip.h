@@ -177,6 +177,7 @@ struct hsflow_ctx {
     int cmp_cap = 0;            // records both hold
     hipEvent_t evVerify = nullptr;
     size_t scratch_bytes = 0;
+    bool pre_unfused = false;   // HSFLOW_PRE_UNFUSED=1 at creation: the device entries pre-process with k_bgr2gray / k_box_blur3
     int cur = 0;                // which of dU/dV holds the current flow
     // hsflow_solve_async_frames_device: the caller's frames, while the solve has not yet decided who copies them (`lazy`:
     // only inside that call).  Once it has decided that its first Jacobi launch reads them in place and leaves the copy in

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hs_pre_rule.h"
+
 namespace hsk {
 
 // gray = (1868 B + 9617 G + 4899 R + 8192) >> 14 on interleaved BGR bytes (row stride in bytes)
@@ -74,6 +76,90 @@ __global__ __launch_bounds__(256) void k_copy_pair_u8(const uint8_t *__restrict_
     } else {
         const int n = W - x0 < 16 ? W - x0 : 16;
         for (int k = 0; k < n; k++) d[k] = s[k];
+    }
+}
+
+// Both frames of a pair from device memory through the whole pre-processing into the context's planes in ONE launch
+// (hsflow_set_frames_device_ex; the two kernels above cost a pair four launches and a round trip of the gray plane
+// through HBM).  COLOUR: the source is interleaved BGR, else gray; BLUR: 3x3 box blur behind it.  The arithmetic is
+// hs_pre_rule.h's, so the bytes are those of k_bgr2gray / k_box_blur3.
+// One lane = 4 consecutive columns (one 32-bit store per row) of a strip of HSFLOW_PRE_STRIP_ROWS rows; a wavefront = 256
+// columns of one strip; blockIdx.z: which frame, as in k_copy_pair_u8 (a launch with gridDim.z = 1 handles source A alone).
+// The lane walks down its strip: per source row it loads the gray of its four columns (or converts them) and of the two
+// columns beside them, x0 - 1 and x0 + 4 clamped to the frame -- two byte loads of its own, which measured faster than
+// taking them from the neighbour lanes by DPP wave shifts with a reload in lanes 0 and 63 -- forms the
+// four horizontal 3-sums and keeps those of the last three rows; an output row is the sum of the three through
+// round_div9.  A source row is read once per strip, plus one halo row above and below the strip; no gray plane exists
+// outside registers.
+// word_loads bit z: source z's base and stride are multiples of 4, so a lane's four gray pixels are one dword and its four
+// BGR pixels three; otherwise, and for the group that straddles column W - 1, byte by byte.
+template <bool COLOUR, bool BLUR>
+__global__ __launch_bounds__(256) void k_pre_pair(const uint8_t *__restrict__ srcA, long long strideA, const uint8_t *__restrict__ srcB,
+                                                  long long strideB, uint8_t *__restrict__ dstA, uint8_t *__restrict__ dstB, int W, int H,
+                                                  int P, unsigned word_loads)
+{
+    constexpr int S = HSFLOW_PRE_STRIP_ROWS;
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 4; // blockDim.x = 64: threadIdx.y is the wavefront
+    const int y0 = (blockIdx.y * blockDim.y + threadIdx.y) * S;
+    if (x0 >= W || y0 >= H) return;
+    const uint8_t *src = blockIdx.z ? srcB : srcA;
+    const long long stride = blockIdx.z ? strideB : strideA;
+    uint8_t *dst = blockIdx.z ? dstB : dstA;
+    const bool word = ((word_loads >> blockIdx.z) & 1u) != 0 && x0 + 4 <= W;
+    int xc[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) xc[k] = hspre::clamp_index(x0 + k, W);
+    const int xl = hspre::clamp_index(x0 - 1, W), xr = hspre::clamp_index(x0 + 4, W);
+
+    auto gray4 = [&](const uint8_t *row) -> uint32_t { // gray of columns x0 .. x0 + 3 (clamped), one byte each
+        if (word) {
+            if (!COLOUR) return *(const uint32_t *)(row + x0);
+            const uint32_t *p = (const uint32_t *)(row + 3 * x0);
+            const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
+            return hspre::gray_bgr(w0 & 0xFFu, (w0 >> 8) & 0xFFu, (w0 >> 16) & 0xFFu) |
+                   hspre::gray_bgr(w0 >> 24, w1 & 0xFFu, (w1 >> 8) & 0xFFu) << 8 |
+                   hspre::gray_bgr((w1 >> 16) & 0xFFu, w1 >> 24, w2 & 0xFFu) << 16 |
+                   hspre::gray_bgr((w2 >> 8) & 0xFFu, (w2 >> 16) & 0xFFu, w2 >> 24) << 24;
+        }
+        uint32_t w = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) w |= hspre::gray_at<COLOUR>(row, xc[k]) << (8 * k);
+        return w;
+    };
+
+    if (!BLUR) {
+#pragma unroll
+        for (int r = 0; r < S; r++) {
+            const int y = y0 + r;
+            if (y < H) {
+                const uint32_t w = gray4(src + (long long)y * stride);
+                *(uint32_t *)(dst + (long long)y * P + x0) = w; // row pitch P is a multiple of 64: in bounds
+            }
+        }
+        return;
+    }
+
+    uint32_t h[3][4]; // horizontal 3-sums of the last three source rows (slot j % 3; the loop is unrolled: registers)
+#pragma unroll
+    for (int j = 0; j < S + 2; j++) { // source rows y0 - 1 .. y0 + S
+        const int ys = y0 + j - 1;
+        if (j >= 2 && ys - 1 >= H) break; // nothing below the frame is stored
+        const uint8_t *row = src + (long long)hspre::clamp_index(ys, H) * stride;
+        const uint32_t w = gray4(row);
+        uint32_t g[6]; // columns x0 - 1 .. x0 + 4
+#pragma unroll
+        for (int k = 0; k < 4; k++) g[k + 1] = (w >> (8 * k)) & 0xFFu;
+        g[0] = hspre::gray_at<COLOUR>(row, xl);
+        g[5] = hspre::gray_at<COLOUR>(row, xr);
+#pragma unroll
+        for (int k = 0; k < 4; k++) h[j % 3][k] = g[k] + g[k + 1] + g[k + 2];
+        if (j >= 2) { // output row y0 + j - 2
+            const int y = ys - 1;
+            uint32_t out = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) out |= hspre::round_div9(h[0][k] + h[1][k] + h[2][k]) << (8 * k);
+            *(uint32_t *)(dst + (long long)y * P + x0) = out;
+        }
     }
 }
 

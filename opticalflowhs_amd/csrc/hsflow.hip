@@ -124,6 +124,7 @@ int hsflow_create(hsflow_ctx **out, int device, int width, int height, int n_pai
     std::memset(&c->info, 0, sizeof(c->info));
     c->info.struct_size = sizeof(hsflow_info);
     c->info.width = width; c->info.height = height; c->info.n_pairs = n_pairs; c->info.pitch = c->P;
+    c->pre_unfused = getenv("HSFLOW_PRE_UNFUSED") && atoi(getenv("HSFLOW_PRE_UNFUSED")) != 0;
     auto bail = [&](int code, const std::string &m) { g_create_error = m; hsflow_destroy(c); return code; };
 #define HS_TRY(call)                                                                              \
     do {                                                                                          \
@@ -313,16 +314,9 @@ int hsflow_push_frame_u8(hsflow_ctx *c, int pair, const uint8_t *next, size_t ns
 static int preprocess_frame(hsflow_ctx *c, uint8_t *dst, const uint8_t *host, size_t stride, bool colour, bool blur, int slot = 0,
                             bool sync = true)
 {
-    const size_t bgr_bytes = (size_t)c->W * 3 * c->H, gray_bytes = (size_t)c->plane;
-    const size_t one = bgr_bytes + 2 * gray_bytes, need = 2 * one;
-    if (c->scratch_bytes < need) {
-        HS_HIP(c, hipStreamSynchronize(c->stream)); // nothing in flight may still use the old area
-        hipFree(c->dScratch);
-        c->dScratch = nullptr; c->scratch_bytes = 0;
-        HS_HIP(c, hipMalloc(&c->dScratch, need));
-        c->scratch_bytes = need;
-    }
-    uint8_t *dBgr = (uint8_t *)c->dScratch + (size_t)slot * one, *dGray = dBgr + bgr_bytes;
+    uint8_t *dBgr = nullptr, *dGray = nullptr;
+    const int st = pre_scratch(c, slot, &dBgr, &dGray);
+    if (st) return st;
     const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4), block(64, 4);
     if (sync) HS_HIP(c, hipStreamSynchronize(c->stream));
     if (colour) {
@@ -395,6 +389,85 @@ int hsflow_set_frames_gray8_blur_async(hsflow_ctx *c, int pair, const uint8_t *p
     c->frames_set = true;
     c->coef_valid = false;
     return HSFLOW_OK;
+}
+
+// Frames that lie in device memory, in any HSFLOW_FRAMES_* layout: the whole pre-processing of the pair is ONE launch
+// (k_pre_pair) on the context's stream.
+int hsflow_set_frames_device_ex(hsflow_ctx *c, int pair, int format, const void *dprev, size_t ps, const void *dcurr, size_t cs)
+{
+    if (format == HSFLOW_FRAMES_GRAY8) return hsflow_set_frames_u8_device(c, pair, dprev, ps, dcurr, cs);
+    int st = check_ctx(c, pair);
+    if (st) return st;
+    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
+    if (!dprev || !dcurr) return fail(c, HSFLOW_E_ARG, "null frame pointer");
+    if (!hspre::format_known(format)) return fail(c, HSFLOW_E_ARG, "unknown frame format");
+    const size_t rowb = (size_t)c->W * (hspre::format_colour(format) ? 3 : 1);
+    if (ps < rowb || cs < rowb) return fail(c, HSFLOW_E_SIZE, hspre::format_colour(format) ? "colour frame stride smaller than 3*width" : "frame stride smaller than width");
+    if ((st = launch_pre(c, format, 2, dprev, ps, dcurr, cs, c->dA + pair * c->plane, c->dB + pair * c->plane))) return st;
+    c->frames_set = true;
+    c->coef_valid = false;
+    return HSFLOW_OK;
+}
+
+// The camera sequence (OpticalFlowOpenCV.cpp:92-93,118): prev := reblur_prev ? box_blur3(curr) : curr, then
+// curr := pre(format, next) -- two launches in stream order (one launch could not do both: the second write would race
+// the first read of the same plane), into the planes the cached graphs were captured with.  host: `next` is host memory,
+// uploaded into the context's scratch first; complete on return.
+static int push_frame_impl(hsflow_ctx *c, int pair, int format, const void *next, size_t ns, int reblur_prev, bool host)
+{
+    int st = check_ctx(c, pair);
+    if (st) return st;
+    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
+    if (!next) return fail(c, HSFLOW_E_ARG, "null frame pointer");
+    if (!hspre::format_known(format)) return fail(c, HSFLOW_E_ARG, "unknown frame format");
+    if (reblur_prev != 0 && reblur_prev != 1) return fail(c, HSFLOW_E_ARG, "reblur_prev must be 0 or 1");
+    const bool colour = hspre::format_colour(format);
+    const size_t rowb = (size_t)c->W * (colour ? 3 : 1);
+    if (ns < rowb) return fail(c, HSFLOW_E_SIZE, colour ? "colour frame stride smaller than 3*width" : "frame stride smaller than width");
+    if (!c->frames_set) return fail(c, HSFLOW_E_STATE, "push_frame needs a previous pair");
+    uint8_t *dPrev = c->dA + pair * c->plane, *dCurr = c->dB + pair * c->plane;
+    const void *src = next;
+    size_t sp = ns;
+    if (host && format != HSFLOW_FRAMES_GRAY8) { // (area 1: the unfused route stages a single frame through area 0)
+        uint8_t *dBgr = nullptr, *dGray = nullptr;
+        if ((st = pre_scratch(c, 1, &dBgr, &dGray))) return st;
+        src = colour ? dBgr : dGray;
+        sp = colour ? rowb : (size_t)c->P;
+        HS_HIP(c, hipStreamSynchronize(c->stream));
+        HS_HIP(c, hipMemcpy2D(const_cast<void *>(src), sp, next, ns, rowb, c->H, hipMemcpyHostToDevice));
+    }
+    if (reblur_prev) {
+        if ((st = launch_pre(c, HSFLOW_FRAMES_GRAY8_BLUR, 1, dCurr, (size_t)c->P, nullptr, 0, dPrev, nullptr, true))) return st;
+    } else {
+        HS_HIP(c, hipMemcpyAsync(dPrev, dCurr, (size_t)c->plane, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (format == HSFLOW_FRAMES_GRAY8) {
+        if (host) HS_HIP(c, hipStreamSynchronize(c->stream));
+        if ((st = copy_frame_in(c, dCurr, next, ns, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, host))) return st;
+    } else if ((st = launch_pre(c, format, 1, src, sp, nullptr, 0, dCurr, nullptr))) return st;
+    if (host) HS_HIP(c, hipStreamSynchronize(c->stream));
+    c->coef_valid = false;
+    return HSFLOW_OK;
+}
+
+int hsflow_push_frame_ex(hsflow_ctx *c, int pair, int format, const uint8_t *next, size_t stride, int reblur_prev)
+{
+    return push_frame_impl(c, pair, format, next, stride, reblur_prev, true);
+}
+
+int hsflow_push_frame_device_ex(hsflow_ctx *c, int pair, int format, const void *d_next, size_t stride, int reblur_prev)
+{
+    return push_frame_impl(c, pair, format, d_next, stride, reblur_prev, false);
+}
+
+int hsflow_preprocess_frame_host(int format, const uint8_t *src, size_t src_stride, int width, int height, uint8_t *dst, size_t dst_stride)
+{
+    switch (hspre::preprocess_host(format, src, src_stride, width, height, dst, dst_stride)) {
+    case 0: return HSFLOW_OK;
+    case 1: return fail(nullptr, HSFLOW_E_ARG, "hsflow_preprocess_frame_host: null pointer or unknown frame format");
+    case 2: return fail(nullptr, HSFLOW_E_SIZE, "hsflow_preprocess_frame_host: non-positive size or stride smaller than a row");
+    default: return fail(nullptr, HSFLOW_E_OOM, "hsflow_preprocess_frame_host: host allocation failed");
+    }
 }
 
 int hsflow_set_async_reduce(hsflow_ctx *c, int on)

@@ -254,6 +254,34 @@ int hsflow_pipeline_submit_device(hsflow_pipeline *pl, const void *d_prev, size_
     return HSFLOW_OK;
 }
 
+int hsflow_pipeline_submit_device_ex(hsflow_pipeline *pl, int format, const void *d_prev, size_t ps, const void *d_curr, size_t cs,
+                                     const hsflow_params *params, uint64_t *ticket)
+{
+    if (format == HSFLOW_FRAMES_GRAY8) return hsflow_pipeline_submit_device(pl, d_prev, ps, d_curr, cs, params, ticket);
+    if (!pl) return HSFLOW_E_ARG;
+    if (format < HSFLOW_FRAMES_GRAY8 || format > HSFLOW_FRAMES_BGR8_BLUR) return pfail(pl, HSFLOW_E_ARG, "unknown frame format");
+    if (!params) return pfail(pl, HSFLOW_E_ARG, "params is null");
+    hsflow_pipeline::Slot &s = pl->slots[pl->next % pl->slots.size()];
+    int st = finish_slot(pl, s); // the job that used this slot `depth` submissions ago
+    if (st) return st;
+    // the fused pre-processing launch stands where the copy kernel stands in a gray pair's chain; the solve then works
+    // from the slot's planes, like after a host submit
+    if ((st = hsflow_set_frames_device_ex(s.ctx, 0, format, d_prev, ps, d_curr, cs))) return ctx_fail(pl, s.ctx, st, "hsflow_set_frames_device_ex");
+    hsflow_params shaped;
+    const hsflow_params *use = params; // (a struct of another size is not copied: hsflow_solve_async refuses it)
+    if (params->struct_size == sizeof(hsflow_params)) { shaped = stream_shape(pl, *params); use = &shaped; }
+    if ((st = hsflow_solve_async(s.ctx, use))) {
+        hsflow_synchronize(s.ctx); // the pre-processing was queued: do not leave it reading caller memory
+        return ctx_fail(pl, s.ctx, st, "hsflow_solve_async");
+    }
+    s.busy = true;
+    s.ticket = pl->next;
+    s.u = s.v = nullptr; s.us = s.vs = 0; // the flow stays in the slot (hsflow_pipeline_flow_device)
+    if (ticket) *ticket = pl->next;
+    pl->next++;
+    return HSFLOW_OK;
+}
+
 int hsflow_pipeline_flow_device(hsflow_pipeline *pl, uint64_t ticket, const float **du, const float **dv, size_t *stride_bytes)
 {
     if (!pl) return HSFLOW_E_ARG;

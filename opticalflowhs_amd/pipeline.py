@@ -63,7 +63,7 @@ class PairPipeline(object):
         """Enqueues upload -> [pre-processing] -> solve -> download of one pair; returns its ticket.  The four
         arrays belong to the pipeline until `wait(ticket)` (or `drain()`) returned.
         frames: "gray" (u8, as is), "gray_blur" (3x3 box blur on the device), "bgr" / "bgr_blur" ((H, W, 3) u8)."""
-        fmt = {"gray": _lib.FRAMES_GRAY8, "gray_blur": _lib.FRAMES_GRAY8_BLUR, "bgr": _lib.FRAMES_BGR8, "bgr_blur": _lib.FRAMES_BGR8_BLUR}[frames]
+        fmt = _lib.FRAME_FORMATS[frames]
         colour = fmt >= _lib.FRAMES_BGR8
         for a in (prev, curr):
             want = (self.height, self.width, 3) if colour else (self.height, self.width)
@@ -86,20 +86,30 @@ class PairPipeline(object):
         self._held[t.value] = (prev, curr, u_out, v_out)
         return t.value
 
-    def submit_device(self, prev, curr, params=None, **kw):
+    def submit_device(self, prev, curr, params=None, frames="gray", **kw):
         """A pair that already lies in device memory (CUDA uint8 tensors of shape (height, width), unit column stride):
         the slot gets its own copy of the frames (from the solve's first launch where that can read the tensors in place,
         `copies_elided`) -> solve; the flow stays in the slot (`flow_device`).  The tensors are held
-        until the ticket has been waited for."""
+        until the ticket has been waited for.
+        frames: "gray" (as is), or "gray_blur", "bgr" / "bgr_blur" ((height, width, 3), packed pixels): the pre-processing
+        is then one launch ahead of the solve (`hsflow_pipeline_submit_device_ex`) and the slot holds its result."""
+        fmt = _lib.FRAME_FORMATS[frames]
+        colour = fmt >= _lib.FRAMES_BGR8
+        want = (self.height, self.width, 3) if colour else (self.height, self.width)
         for a in (prev, curr):
-            if not (hasattr(a, "is_cuda") and a.is_cuda) or str(a.dtype) != "torch.uint8" or tuple(a.shape) != (self.height, self.width) or a.stride(1) != 1:
-                raise ValueError("device frames must be CUDA uint8 tensors of shape (height, width) with unit column stride")
+            if not (hasattr(a, "is_cuda") and a.is_cuda) or str(a.dtype) != "torch.uint8" or tuple(a.shape) != want or a.stride(-1) != 1 or \
+                    (colour and a.stride(1) != 3):
+                raise ValueError("device frames must be CUDA uint8 tensors of shape %r with unit column stride (packed pixels)" % (want,))
         if params is None:
             kw.setdefault("term_type", TERM_ITER)
             params = make_params(**kw)
         t = ctypes.c_uint64()
-        self._check(self._lib.hsflow_pipeline_submit_device(self._h, ctypes.c_void_p(prev.data_ptr()), prev.stride(0), ctypes.c_void_p(curr.data_ptr()),
-                                                            curr.stride(0), ctypes.byref(params), ctypes.byref(t)))
+        if fmt == _lib.FRAMES_GRAY8:
+            self._check(self._lib.hsflow_pipeline_submit_device(self._h, ctypes.c_void_p(prev.data_ptr()), prev.stride(0), ctypes.c_void_p(curr.data_ptr()),
+                                                                curr.stride(0), ctypes.byref(params), ctypes.byref(t)))
+        else:
+            self._check(self._lib.hsflow_pipeline_submit_device_ex(self._h, fmt, ctypes.c_void_p(prev.data_ptr()), prev.stride(0),
+                                                                   ctypes.c_void_p(curr.data_ptr()), curr.stride(0), ctypes.byref(params), ctypes.byref(t)))
         self._held.pop(t.value - self.depth, None)
         self._held[t.value] = (prev, curr)
         return t.value

@@ -191,6 +191,36 @@ class HSFlow(object):
             raise ValueError("frame shape must be (height, width)")
         self._check(self._lib.hsflow_push_frame_u8(self._h, pair, _ptr(nxt), nxt.strides[0]))
 
+    def _device_frame(self, t, colour):
+        """(pointer, row stride in bytes) of a CUDA uint8 tensor of shape (H, W) or (H, W, 3) with unit innermost stride."""
+        want = (self.height, self.width, 3) if colour else (self.height, self.width)
+        if not _is_device_tensor(t) or str(t.dtype) != "torch.uint8" or tuple(t.shape) != want or t.stride(-1) != 1 or (colour and t.stride(1) != 3):
+            raise ValueError("device frames must be CUDA uint8 tensors of shape %r with packed pixels" % (want,))
+        return _ptr(t), t.stride(0)
+
+    def set_frames_device(self, prev, curr, frames="gray", pair=0):
+        """Frames that already lie in device memory, in any layout: CUDA uint8 tensors of shape (H, W) ("gray",
+        "gray_blur") or (H, W, 3) ("bgr", "bgr_blur") with unit innermost stride and any row stride.  The pre-processing
+        of the pair is one launch on the context's stream (`hsflow_set_frames_device_ex`); only enqueued."""
+        fmt = _lib.FRAME_FORMATS[frames]
+        (pa, sa), (pb, sb) = (self._device_frame(t, fmt >= _lib.FRAMES_BGR8) for t in (prev, curr))
+        self._check(self._lib.hsflow_set_frames_device_ex(self._h, pair, fmt, pa, sa, pb, sb))
+
+    def push_frame_ex(self, nxt, frames="gray", reblur_prev=False, pair=0):
+        """The camera sequence: the current frame becomes the previous one -- blurred once more with reblur_prev, which
+        with a "*_blur" layout is the reference's loop -- and `nxt` is pre-processed into the current one.  nxt: a numpy
+        array (uploaded; complete on return) or a CUDA tensor (only enqueued), shaped as for `set_frames_device`."""
+        fmt = _lib.FRAME_FORMATS[frames]
+        colour = fmt >= _lib.FRAMES_BGR8
+        if _is_device_tensor(nxt):
+            ptr, stride = self._device_frame(nxt, colour)
+            self._check(self._lib.hsflow_push_frame_device_ex(self._h, pair, fmt, ptr, stride, 1 if reblur_prev else 0))
+            return
+        nxt = np.ascontiguousarray(nxt, dtype=np.uint8)
+        if nxt.shape != ((self.height, self.width, 3) if colour else (self.height, self.width)):
+            raise ValueError("frame shape must be (height, width) or, for colour, (height, width, 3)")
+        self._check(self._lib.hsflow_push_frame_ex(self._h, pair, fmt, _ptr(nxt), nxt.strides[0], 1 if reblur_prev else 0))
+
     # -- solve ---------------------------------------------------------------------------
     def make_params(self, **kw):
         """hsflow_params with the defaults of hsflow_default_params; see `make_params` (module)."""
@@ -338,6 +368,23 @@ def compare_planes(a, b):
     if st:
         raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
     return d
+
+
+def preprocess_frame(img, frames):
+    """The pre-processing rule on the host (`hsflow_preprocess_frame_host`; no device needed): the (H, W) uint8 frame the
+    solver sees for `img` given as layout `frames` -- "gray", "gray_blur" ((H, W) uint8) or "bgr", "bgr_blur" ((H, W, 3))."""
+    lib = _lib.load()
+    fmt = _lib.FRAME_FORMATS[frames]
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != (3 if fmt >= _lib.FRAMES_BGR8 else 2) or (img.ndim == 3 and img.shape[2] != 3):
+        raise ValueError("expected a uint8 array of shape (H, W), or (H, W, 3) for colour")
+    if img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != 3):
+        img = np.ascontiguousarray(img)
+    out = np.empty(img.shape[:2], np.uint8)
+    st = lib.hsflow_preprocess_frame_host(fmt, _ptr(img), img.strides[0], img.shape[1], img.shape[0], _ptr(out), out.strides[0])
+    if st:
+        raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
+    return out
 
 
 def plan_query(width, height, n_pairs=1, params=None, **kw):
