@@ -111,7 +111,16 @@ typedef struct hsflow_params {
     int32_t term_type;    /* HSFLOW_TERM_ITER | HSFLOW_TERM_EPS                          */
     int32_t max_iter;     /* CvTermCriteria.max_iter                                     */
     double epsilon;       /* CvTermCriteria.epsilon (caller rounds through float if it
-                             wants cvTermCriteria()'s behaviour, cxtypes.h:912)          */
+                             wants cvTermCriteria()'s behaviour, cxtypes.h:912).  The rule
+                             is strict and decided in double over the whole range: a
+                             solve stops after the first sweep with (double)Eps < epsilon.
+                             With a sweep budget any value is taken: +inf or one above
+                             FLT_MAX stops after sweep 1; zero, a negative one or a NaN
+                             never stops and the budget runs out.  From about
+                             2^(127 - 2 fuse_steps) up, and for a NaN, an ITER|EPS solve
+                             measures every sweep and hsflow_solve_async returns with the
+                             solve complete.  Without a budget: finite and > 0, else
+                             HSFLOW_E_NOTERM                                              */
     int32_t use_previous; /* 0: u=v=0 first (reference behaviour); 1: continue from the
                              flow currently held by the context                          */
     int32_t kernel;       /* HSFLOW_KERNEL_*                                             */

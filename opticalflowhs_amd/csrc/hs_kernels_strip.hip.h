@@ -864,8 +864,10 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
         if constexpr (EPS != 1) asm volatile("" : "+s"(act), "+s"(actb), "+s"(actr));
         // (scaled state: this sweep takes the flow from scale 4^s to 4^(s+1))
         // eps_thr * 4^(s+1) by integer arithmetic on the exponent: scalar instructions only (v_ldexp + v_readfirstlane put
-        // a vector-to-scalar round trip into every sweep).  Exact for a normal eps_thr; eps_thr = 0 or a product beyond
-        // the float range merely makes the witness fail, and the exact pass decides (the host never sends a denormal).
+        // a vector-to-scalar round trip into every sweep).  Exact while eps_thr is normal and the product finite; past
+        // that the sum reads +inf for one sweep and then carries into the sign bit, where every lane would pass.  The host
+        // sends only a threshold that stays exact over all T sweeps (hs_stop_rule.h: never zero, never a denormal, exponent
+        // field + 2 T <= 254), and runs no witness launch where there is none.
         const float thr_s = __int_as_float(__float_as_int(eps_thr) + ((s + 1) << 24));
 #if HS_DIAG & 1 /* diagnostic build (wrong results): no LDS traffic, the strip's own edge rows stand in */
         const float4 hu4 = make_float4(uP[0].x, uP[0].y, uQ[0].x, uQ[0].y), hv4 = make_float4(vP[0].x, vP[0].y, vQ[0].x, vQ[0].y);

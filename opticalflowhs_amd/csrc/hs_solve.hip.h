@@ -746,14 +746,9 @@ int first_eps_hit(const unsigned *w, int n, double epsilon, float *last)
     return -1;
 }
 
-// The threshold of witness launches: the smallest float >= epsilon, so that "change >= threshold" implies "Eps >= epsilon".
-float witness_threshold(double epsilon)
-{
-    float thr = epsilon > 0 ? (float)epsilon : 0.f;
-    if ((double)thr < epsilon) thr = std::nextafterf(thr, INFINITY);
-    if (thr < FLT_MIN) thr = thr > 0.f ? FLT_MIN : 0.f; // the kernels scale it through its exponent bits
-    return thr;
-}
+// The threshold of witness launches, and whether launches of T sweeps can use it: hs_stop_rule.h.
+using hsstop::witness_threshold;
+using hsstop::witness_usable;
 
 // The witness pass of ITER|EPS: the budget runs at full speed, nothing on the host between launches.  All launches but
 // the last run the kernels' witness mode, which costs almost nothing over the ITER-only kernel and yields one number per
@@ -1264,6 +1259,15 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
     c->info.last_eps = 0.f;
     Profiler prof{c, p.profile != 0};
     if (!S.use_eps) return solve_fixed(c, S, prof, async);
+    // A threshold that S.T sweeps of scaling would carry out of the float range (epsilon from about 2^(127 - 2 T) up), or
+    // a NaN: the witness launches could prove nothing, or worse (hs_stop_rule.h).  No witness pass then: every sweep is
+    // measured, launch by launch, and the solve is complete when the call returns, also where it was asked for
+    // asynchronously -- nothing stays owed.  (S.T is the longest launch of the pass: a tail is shorter.)
+    if (S.witness && !witness_usable(p.epsilon, S.T)) {
+        S.witness = S.persist = false;
+        c->info.persistent = 0;
+        async = false;
+    }
     constexpr long long kSpecMax = 1 << 16; // speculative ITER|EPS: the whole budget in one go
     if (S.use_iter && p.max_iter > 0 && S.budget <= kSpecMax) return solve_iter_eps(c, S, prof, async);
     if (stops_per_pair(c)) // (no budget to speculate on: every pair through its own chunk loop, stall rule included)

@@ -28,6 +28,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "hs_stop_rule.h"
 #include "hs_context.hip.h"
 #include "hs_plan_launch.hip.h"
 #include "hs_runtime.hip.h"

@@ -12,6 +12,7 @@
 //                   trip of the reference (HSOpticalFlowOpenCL.cpp:483-501, 655-675) at the multi-GPU level.
 //                   (The one-process-per-GPU form with RCCL send/recv is opticalflowhs_amd/slab.py.)
 #include "../../include/hsflow.h"
+#include "hs_stop_rule.h"
 
 #include <hip/hip_runtime.h>
 
@@ -530,6 +531,13 @@ int hsflow_slab_solve(hsflow_slab *s, const hsflow_params *pp)
     if (pp->use_previous && use_eps && (st = copy_flows(s, &Slab::start_uv, true))) return st;
     int done = 0;
     bool measure = false; // every chunk from here on is measured sweep by sweep
+    // An epsilon whose witness threshold cannot be scaled over a chunk's sweeps (hs_stop_rule.h; a slab's launches are no
+    // longer than a chunk): no slab could vouch for anything, and a slab's context would settle such a solve by itself,
+    // on its own rows' Eps.  Measured from the first chunk on.
+    if (use_eps && !hsstop::witness_usable(pp->epsilon, std::min(s->halo, budget))) {
+        measure = true;
+        s->eps_measured = 1;
+    }
     std::vector<float> eps_s, eps_max;
     while (done < budget) {
         const int chunk = std::min(s->halo, budget - done);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised stress of the C ABI against the oracle (a one-off soak, not part of the test suite):
-random sizes, pairs per context, kernels and tuning knobs, ITER / ITER|EPS with random epsilon, warm
+random sizes, pairs per context, kernels and tuning knobs, ITER / ITER|EPS with random epsilon (every eighth case: one from the ends of the float range), warm
 starts, graphs, asynchronous solves.  usage: python tools/stress.py [cases] [seed]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,6 +11,9 @@ from opticalflowhs_amd import synth
 from oracle import hs_oracle
 
 ITER, EPS = 1, 2
+# the ends of the float range: above every change (one sweep), below every change or unordered (the whole budget)
+EPS_EXTREMES = [float("inf"), 1e39, float(np.finfo(np.float32).max), 2.0 ** 127, 2.0 ** 126, 2.0 ** 100, 2.0 ** 89, 1e30,
+                float(np.finfo(np.float32).tiny), 1e-40, 5e-324, 0.0, -1.0, float("nan")]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 bad = 0
@@ -30,6 +33,8 @@ for case in range(n_cases):
     lam = float(10.0 ** rng.uniform(-2.5, 1.5))
     use_eps = bool(rng.integers(0, 2))
     eps = float(10.0 ** rng.uniform(-7, -1))
+    if use_eps and case % 8 == 3:   # (no draw: the other cases stay what they were)
+        eps = EPS_EXTREMES[(case // 8) % len(EPS_EXTREMES)]
     kernel = int(rng.choice([hs.KERNEL_AUTO, hs.KERNEL_AUTO, hs.KERNEL_SIMPLE, hs.KERNEL_FUSED, hs.KERNEL_STRIP, hs.KERNEL_FOLD]))
     kw = dict(kernel=kernel)
     if kernel in (hs.KERNEL_FUSED, hs.KERNEL_STRIP, hs.KERNEL_FOLD) and rng.integers(0, 2):
