@@ -328,8 +328,6 @@ int hsflow_push_frame_u8(hsflow_ctx *ctx, int pair, const uint8_t *next, size_t 
  * context's planes -- no gray plane in between, every source byte read once plus one halo row per strip end.  Sources
  * whose base and stride are multiples of 4 are read a word at a time, others byte by byte; the bytes written are those
  * of hsflow_set_frames_bgr8 / hsflow_set_frames_gray8_blur from the same pixels (hsflow_preprocess_frame_host).
- * HSFLOW_PRE_UNFUSED=1 in the environment when the context is created: the kernels of the host-pointer entries instead,
- * two launches per frame through a gray scratch plane (A/B runs, and the fallback).
  * HSFLOW_E_ARG: null pointer, unknown format; HSFLOW_E_SIZE: a stride below the row's bytes. */
 #define HSFLOW_PRE_STRIP_ROWS 8 /* rows a lane of the fused pre-processing kernel walks (a design constant) */
 int hsflow_set_frames_device_ex(hsflow_ctx *ctx, int pair, int format, const void *d_prev, size_t prev_stride,
@@ -339,7 +337,7 @@ int hsflow_set_frames_device_ex(hsflow_ctx *ctx, int pair, int format, const voi
  * 118: cvSmooth works in place and the blurred new frame becomes the next old one, so from the second pair on the old
  * frame enters the solver blurred twice); reblur_prev = 0 with HSFLOW_FRAMES_GRAY8 is hsflow_push_frame_u8.  Two launches
  * in stream order into the planes the context has always had (cached graphs stay valid).  hsflow_push_frame_ex takes
- * `next` from host memory, uploads it into the context's scratch and returns when everything is complete;
+ * `next` from host memory, uploads it into the context's staging and returns when everything is complete;
  * hsflow_push_frame_device_ex takes it from device memory and only enqueues.
  * HSFLOW_E_ARG: null pointer, unknown format, reblur_prev not 0 or 1; HSFLOW_E_SIZE: stride below the row's bytes;
  * HSFLOW_E_STATE: no frames were set before. */

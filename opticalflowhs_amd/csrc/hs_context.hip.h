@@ -153,7 +153,7 @@ struct hsflow_ctx {
     int cu_share = 0;            // > 0: the planners count on this many CUs only (hsflow_set_cu_share); 0: the whole chip
     int num_cu = 0;              // compute units of the device (one workgroup of the persistent launch per CU)
     int max_grid_z = 65535;      // the device's grid limit in z: launches with one layer of workgroups per pair take at most this many
-    void *dScratch = nullptr;   // staging for colour frames / derivative read-back
+    void *dScratch = nullptr;   // staging for host frames / derivative read-back (scratch_reserve)
     // hsflow_render_flow[_device] (hs_render.hip.h), allocated by the first render: the priority plane (P x H words, zero
     // between renders), the picture hsflow_render_flow draws into before it copies it out (3*W x H bytes), and the
     // event behind that copy
@@ -177,7 +177,6 @@ struct hsflow_ctx {
     int cmp_cap = 0;            // records both hold
     hipEvent_t evVerify = nullptr;
     size_t scratch_bytes = 0;
-    bool pre_unfused = false;   // HSFLOW_PRE_UNFUSED=1 at creation: the device entries pre-process with k_bgr2gray / k_box_blur3
     int cur = 0;                // which of dU/dV holds the current flow
     // hsflow_solve_async_frames_device: the caller's frames, while the solve has not yet decided who copies them (`lazy`:
     // only inside that call).  Once it has decided that its first Jacobi launch reads them in place and leaves the copy in

@@ -49,27 +49,22 @@ hipError_t launch_frame_copy(hsflow_ctx *c, int pair, const void *dprev, size_t 
     return hipGetLastError();
 }
 
-// The context's staging for pre-processing: two areas (`slot` 0 / 1, so that both frames of a pair can be in flight), each a
-// packed BGR frame followed by two gray planes of pitch P.  Grows only; nothing in flight may still use the old one.
-int pre_scratch(hsflow_ctx *c, int slot, uint8_t **bgr, uint8_t **gray)
+// The context's one staging buffer (dScratch: host frames on their way to pre-processing, the derivative read-back): at
+// least `need` bytes.  Grows only; nothing in flight may still use the old one, so the stream is waited for first.
+int scratch_reserve(hsflow_ctx *c, size_t need)
 {
-    const size_t bgr_bytes = (size_t)c->W * 3 * c->H, gray_bytes = (size_t)c->plane;
-    const size_t one = bgr_bytes + 2 * gray_bytes, need = 2 * one;
-    if (c->scratch_bytes < need) {
-        HS_HIP(c, hipStreamSynchronize(c->stream));
-        hipFree(c->dScratch);
-        c->dScratch = nullptr; c->scratch_bytes = 0;
-        HS_HIP(c, hipMalloc(&c->dScratch, need));
-        c->scratch_bytes = need;
-    }
-    *bgr = (uint8_t *)c->dScratch + (size_t)slot * one;
-    *gray = *bgr + bgr_bytes;
+    if (c->scratch_bytes >= need) return HSFLOW_OK;
+    HS_HIP(c, hipStreamSynchronize(c->stream));
+    hipFree(c->dScratch);
+    c->dScratch = nullptr; c->scratch_bytes = 0;
+    HS_HIP(c, hipMalloc(&c->dScratch, need));
+    c->scratch_bytes = need;
     return HSFLOW_OK;
 }
 
-// dst planes (pitch P) = pre(format, src) for `frames` (1 or 2) frames that lie in device memory, on the context's stream:
-// ONE launch of k_pre_pair, whatever the format (HSFLOW_FRAMES_GRAY8 is a copy and not handled here).  Word loads per
-// source where its base and stride allow them.
+// dst planes (pitch P) = pre(format, src) for `frames` (1 or 2) frames that lie in device memory (a caller's, the staging
+// slots, or a plane of the context), on the context's stream: ONE launch of k_pre_pair, whatever the format
+// (HSFLOW_FRAMES_GRAY8 is a copy and not handled here).  Word loads per source where its base and stride allow them.
 hipError_t launch_pre_fused(hsflow_ctx *c, int format, int frames, const void *sA, size_t psA, const void *sB, size_t psB, uint8_t *dA, uint8_t *dB)
 {
     constexpr int S = HSFLOW_PRE_STRIP_ROWS;
@@ -89,38 +84,6 @@ hipError_t launch_pre_fused(hsflow_ctx *c, int format, int frames, const void *s
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
-}
-
-// The same through the two kernels the host-pointer entries use (HSFLOW_PRE_UNFUSED=1: the A/B switch and the fallback):
-// per frame BGR->gray into a gray scratch plane (a gray source: copied there, k_box_blur3 reads pitch P) and the blur
-// out of it -- two launches per frame.  own_plane: the source IS a plane of pitch P (the re-blur of a push): one launch.
-int launch_pre_unfused(hsflow_ctx *c, int format, int frames, const void *sA, size_t psA, const void *sB, size_t psB, uint8_t *dA, uint8_t *dB,
-                       bool own_plane = false)
-{
-    const bool colour = hspre::format_colour(format), blur = hspre::format_blur(format);
-    const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4), block(64, 4);
-    for (int f = 0; f < frames; f++) {
-        const uint8_t *src = (const uint8_t *)(f ? sB : sA);
-        const size_t ps = f ? psB : psA;
-        uint8_t *dst = f ? dB : dA, *bgr = nullptr, *gray = nullptr;
-        int st = own_plane ? HSFLOW_OK : pre_scratch(c, f, &bgr, &gray);
-        if (st) return st;
-        if (own_plane) gray = const_cast<uint8_t *>(src);
-        else if (colour) hipLaunchKernelGGL(hsk::k_bgr2gray, grid, block, 0, c->stream, src, (long long)ps, blur ? gray : dst, c->W, c->H, c->P);
-        else HS_HIP(c, hipMemcpy2DAsync(gray, c->P, src, ps, c->W, c->H, hipMemcpyDeviceToDevice, c->stream));
-        if (blur) hipLaunchKernelGGL(hsk::k_box_blur3, grid, block, 0, c->stream, gray, dst, c->W, c->H, c->P);
-        HS_HIP(c, hipGetLastError());
-    }
-    return HSFLOW_OK;
-}
-
-// dst = pre(format, src) for device-resident frames by whichever of the two the context runs.
-int launch_pre(hsflow_ctx *c, int format, int frames, const void *sA, size_t psA, const void *sB, size_t psB, uint8_t *dA, uint8_t *dB,
-               bool own_plane = false)
-{
-    if (c->pre_unfused) return launch_pre_unfused(c, format, frames, sA, psA, sB, psB, dA, dB, own_plane);
-    HS_HIP(c, launch_pre_fused(c, format, frames, sA, psA, sB, psB, dA, dB));
-    return HSFLOW_OK;
 }
 
 // Could the first Jacobi launch of a solve read these frames where they lie (hsk::FrameSrc)?  It reads a lane's four

@@ -125,7 +125,6 @@ int hsflow_create(hsflow_ctx **out, int device, int width, int height, int n_pai
     std::memset(&c->info, 0, sizeof(c->info));
     c->info.struct_size = sizeof(hsflow_info);
     c->info.width = width; c->info.height = height; c->info.n_pairs = n_pairs; c->info.pitch = c->P;
-    c->pre_unfused = getenv("HSFLOW_PRE_UNFUSED") && atoi(getenv("HSFLOW_PRE_UNFUSED")) != 0;
     auto bail = [&](int code, const std::string &m) { g_create_error = m; hsflow_destroy(c); return code; };
 #define HS_TRY(call)                                                                              \
     do {                                                                                          \
@@ -243,21 +242,6 @@ int hsflow_destroy(hsflow_ctx *c)
     return HSFLOW_OK;
 }
 
-int hsflow_set_frames_u8(hsflow_ctx *c, int pair, const uint8_t *prev, size_t ps, const uint8_t *curr, size_t cs)
-{
-    int st = check_ctx(c, pair);
-    if (st) return st;
-    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
-    if (!prev || !curr) return fail(c, HSFLOW_E_ARG, "null frame pointer");
-    if (ps < (size_t)c->W || cs < (size_t)c->W) return fail(c, HSFLOW_E_SIZE, "frame stride smaller than width");
-    HS_HIP(c, hipStreamSynchronize(c->stream));
-    if ((st = copy_frame_in(c, c->dA + pair * c->plane, prev, ps, hipMemcpyHostToDevice, true))) return st;
-    if ((st = copy_frame_in(c, c->dB + pair * c->plane, curr, cs, hipMemcpyHostToDevice, true))) return st;
-    c->frames_set = true;
-    c->coef_valid = false;
-    return HSFLOW_OK;
-}
-
 // One transfer of `rows` rows of `rowb` bytes between a pitched device plane and a host buffer on
 // ctx's stream.  Dense layouts on both sides take the 1-D path (a single SDMA copy).
 static hipError_t copy_rows_async(hsflow_ctx *c, void *dst, size_t dpitch, const void *src, size_t spitch, size_t rowb,
@@ -267,198 +251,168 @@ static hipError_t copy_rows_async(hsflow_ctx *c, void *dst, size_t dpitch, const
     return hipMemcpy2DAsync(dst, dpitch, src, spitch, rowb, rows, kind, c->stream);
 }
 
-int hsflow_set_frames_u8_async(hsflow_ctx *c, int pair, const uint8_t *prev, size_t ps, const uint8_t *curr, size_t cs)
+// One call of the frame-input entries below.
+struct FramesIn {
+    int format = HSFLOW_FRAMES_GRAY8; // HSFLOW_FRAMES_*
+    const void *src[2] = {nullptr, nullptr}; // a pair: prev, curr; a push: the next frame alone
+    size_t stride[2] = {0, 0};
+    bool host = true;   // the sources are host memory, else device memory on ctx's device
+    bool async = false; // only enqueued (host buffers belong to the context until hsflow_synchronize), else complete on return
+    bool push = false;  // the camera sequence instead of a pair: prev := reblur_prev ? box_blur3(curr) : curr, curr := pre(src[0])
+    int reblur_prev = 0;
+};
+
+// Host rows of a frame into device memory: blocking (the caller has drained the stream), or enqueued.
+static hipError_t upload_rows(hsflow_ctx *c, void *dst, size_t dpitch, const void *src, size_t spitch, size_t rowb, bool async)
+{
+    if (!async) return hipMemcpy2D(dst, dpitch, src, spitch, rowb, c->H, hipMemcpyHostToDevice);
+    return copy_rows_async(c, dst, dpitch, src, spitch, rowb, c->H, hipMemcpyHostToDevice);
+}
+
+// The staging of host frames: two areas of dScratch (`slot` 0 / 1, so that both frames of a pair can be in flight), each a
+// packed BGR frame followed by two gray planes of pitch P.
+static int stage_area(hsflow_ctx *c, int slot, uint8_t **bgr, uint8_t **gray)
+{
+    const size_t bgr_bytes = (size_t)c->W * 3 * c->H, one = bgr_bytes + 2 * (size_t)c->plane;
+    const int st = scratch_reserve(c, 2 * one);
+    *bgr = (uint8_t *)c->dScratch + (size_t)slot * one;
+    *gray = *bgr + bgr_bytes;
+    return st;
+}
+
+// Every way frames enter a context.  HSFLOW_FRAMES_GRAY8 is a copy into the planes.  The other formats: frames in device
+// memory, and a pushed host frame once it is staged, are ONE k_pre_pair launch (hs_kernels_pre.hip.h).  A host PAIR still
+// goes frame by frame through k_bgr2gray / k_box_blur3 and a gray plane of the staging: staging both frames as they are
+// and running the one launch on them gave the same bytes but a 1080p BGR host-buffer stream 12 % slower, for a reason
+// not found yet, so that route is held back.  A push (OpticalFlowOpenCV.cpp:92-93,118) is two launches
+// in stream order -- one could not do both: the second write would race the first read of the same plane -- into the
+// planes the cached graphs were captured with.
+static int frames_in(hsflow_ctx *c, int pair, const FramesIn &f)
 {
     int st = check_ctx(c, pair);
     if (st) return st;
     if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
-    if (!prev || !curr) return fail(c, HSFLOW_E_ARG, "null frame pointer");
-    if (ps < (size_t)c->W || cs < (size_t)c->W) return fail(c, HSFLOW_E_SIZE, "frame stride smaller than width");
-    HS_HIP(c, copy_rows_async(c, c->dA + pair * c->plane, c->P, prev, ps, c->W, c->H, hipMemcpyHostToDevice));
-    HS_HIP(c, copy_rows_async(c, c->dB + pair * c->plane, c->P, curr, cs, c->W, c->H, hipMemcpyHostToDevice));
-    c->frames_set = true;
+    const int n = f.push ? 1 : 2;
+    if (!f.src[0] || (n == 2 && !f.src[1])) return fail(c, HSFLOW_E_ARG, "null frame pointer");
+    if (!hspre::format_known(f.format)) return fail(c, HSFLOW_E_ARG, "unknown frame format");
+    if (f.reblur_prev != 0 && f.reblur_prev != 1) return fail(c, HSFLOW_E_ARG, "reblur_prev must be 0 or 1");
+    const bool colour = hspre::format_colour(f.format), plain = f.format == HSFLOW_FRAMES_GRAY8;
+    const size_t rowb = (size_t)c->W * (colour ? 3 : 1);
+    if (f.stride[0] < rowb || (n == 2 && f.stride[1] < rowb))
+        return fail(c, HSFLOW_E_SIZE, colour ? "colour frame stride smaller than 3*width" : "frame stride smaller than width");
+    if (f.push && !c->frames_set) return fail(c, HSFLOW_E_STATE, "push_frame needs a previous pair");
+    uint8_t *dPrev = c->dA + pair * c->plane, *dCurr = c->dB + pair * c->plane;
+    uint8_t *dst[2] = {f.push ? dCurr : dPrev, dCurr}; // where source i goes
+    const bool wait = f.host && !f.async;              // complete on return: blocking copies on a drained stream
+    const bool first_sync = wait && !(plain && f.push); // (a plain gray push waits once, behind its plane copy)
+    uint8_t *bgr[2] = {nullptr, nullptr}, *gray[2] = {nullptr, nullptr};
+    if (f.host && !plain)
+        for (int i = 0; i < 2; i++)
+            if ((st = stage_area(c, i, &bgr[i], &gray[i]))) return st;
+    if (first_sync) HS_HIP(c, hipStreamSynchronize(c->stream));
+    if (f.push && f.reblur_prev) HS_HIP(c, launch_pre_fused(c, HSFLOW_FRAMES_GRAY8_BLUR, 1, dCurr, (size_t)c->P, nullptr, 0, dPrev, nullptr));
+    else if (f.push) HS_HIP(c, hipMemcpyAsync(dPrev, dCurr, (size_t)c->plane, hipMemcpyDeviceToDevice, c->stream));
+    if (plain && f.host) { // host gray: straight into the planes
+        if (wait && f.push) HS_HIP(c, hipStreamSynchronize(c->stream)); // (the plane copy above reads dCurr)
+        for (int i = 0; i < n; i++) HS_HIP(c, upload_rows(c, dst[i], c->P, f.src[i], f.stride[i], rowb, f.async));
+    } else if (plain && f.push) {
+        HS_HIP(c, hipMemcpy2DAsync(dCurr, c->P, f.src[0], f.stride[0], rowb, c->H, hipMemcpyDeviceToDevice, c->stream));
+    } else if (plain) {
+        HS_HIP(c, launch_frame_copy(c, pair, f.src[0], f.stride[0], f.src[1], f.stride[1]));
+    } else if (!f.host) {
+        HS_HIP(c, launch_pre_fused(c, f.format, n, f.src[0], f.stride[0], f.src[1], f.stride[1], dst[0], dst[1]));
+    } else if (f.push) { // a host frame: staged in area 1 as it is, then the same launch
+        uint8_t *s = colour ? bgr[1] : gray[1];
+        const size_t sp = colour ? rowb : (size_t)c->P;
+        HS_HIP(c, upload_rows(c, s, sp, f.src[0], f.stride[0], rowb, f.async));
+        HS_HIP(c, launch_pre_fused(c, f.format, 1, s, sp, nullptr, 0, dCurr, nullptr));
+        HS_HIP(c, hipStreamSynchronize(c->stream));
+    } else { // a host pair: frame by frame through the two kernels (see above)
+        const bool blur = hspre::format_blur(f.format);
+        const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4), block(64, 4);
+        for (int i = 0; i < 2; i++) {
+            uint8_t *mid = blur ? gray[i] : dst[i]; // the gray frame before the blur
+            if (colour) {
+                HS_HIP(c, upload_rows(c, bgr[i], rowb, f.src[i], f.stride[i], rowb, f.async));
+                hipLaunchKernelGGL(hsk::k_bgr2gray, grid, block, 0, c->stream, bgr[i], (long long)rowb, mid, c->W, c->H, c->P);
+            } else HS_HIP(c, upload_rows(c, mid, c->P, f.src[i], f.stride[i], rowb, f.async));
+            if (blur) hipLaunchKernelGGL(hsk::k_box_blur3, grid, block, 0, c->stream, gray[i], dst[i], c->W, c->H, c->P);
+            HS_HIP(c, hipGetLastError());
+        }
+        if (wait) HS_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    if (!f.push) c->frames_set = true;
     c->coef_valid = false;
     return HSFLOW_OK;
+}
+
+static FramesIn pair_in(int format, const void *prev, size_t ps, const void *curr, size_t cs, bool host, bool async)
+{
+    FramesIn f;
+    f.format = format; f.src[0] = prev; f.src[1] = curr; f.stride[0] = ps; f.stride[1] = cs; f.host = host; f.async = async;
+    return f;
+}
+
+static FramesIn push_in(int format, const void *next, size_t ns, int reblur_prev, bool host)
+{
+    FramesIn f;
+    f.format = format; f.src[0] = next; f.stride[0] = ns; f.host = host; f.async = !host; f.push = true; f.reblur_prev = reblur_prev;
+    return f;
+}
+
+int hsflow_set_frames_u8(hsflow_ctx *c, int pair, const uint8_t *prev, size_t ps, const uint8_t *curr, size_t cs)
+{
+    return frames_in(c, pair, pair_in(HSFLOW_FRAMES_GRAY8, prev, ps, curr, cs, true, false));
+}
+
+int hsflow_set_frames_u8_async(hsflow_ctx *c, int pair, const uint8_t *prev, size_t ps, const uint8_t *curr, size_t cs)
+{
+    return frames_in(c, pair, pair_in(HSFLOW_FRAMES_GRAY8, prev, ps, curr, cs, true, true));
 }
 
 int hsflow_set_frames_u8_device(hsflow_ctx *c, int pair, const void *dprev, size_t ps, const void *dcurr, size_t cs)
 {
-    int st = check_ctx(c, pair);
-    if (st) return st;
-    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
-    if (!dprev || !dcurr) return fail(c, HSFLOW_E_ARG, "null frame pointer");
-    if (ps < (size_t)c->W || cs < (size_t)c->W) return fail(c, HSFLOW_E_SIZE, "frame stride smaller than width");
-    HS_HIP(c, launch_frame_copy(c, pair, dprev, ps, dcurr, cs));
-    c->frames_set = true;
-    c->coef_valid = false;
-    return HSFLOW_OK;
-}
-
-int hsflow_push_frame_u8(hsflow_ctx *c, int pair, const uint8_t *next, size_t ns)
-{
-    int st = check_ctx(c, pair);
-    if (st) return st;
-    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
-    if (!next) return fail(c, HSFLOW_E_ARG, "null frame pointer");
-    if (ns < (size_t)c->W) return fail(c, HSFLOW_E_SIZE, "frame stride smaller than width");
-    if (!c->frames_set) return fail(c, HSFLOW_E_STATE, "push_frame needs a previous pair");
-    HS_HIP(c, hipMemcpyAsync(c->dA + pair * c->plane, c->dB + pair * c->plane, (size_t)c->plane, hipMemcpyDeviceToDevice, c->stream));
-    HS_HIP(c, hipStreamSynchronize(c->stream));
-    if ((st = copy_frame_in(c, c->dB + pair * c->plane, next, ns, hipMemcpyHostToDevice, true))) return st;
-    c->coef_valid = false;
-    return HSFLOW_OK;
-}
-
-// Upload one host frame (colour or gray) into scratch, convert / blur on the device into dst.  `slot`
-// (0 / 1) picks one of two scratch areas, so that the two frames of a pair can be in flight together;
-// sync = false only enqueues (host buffer must stay valid until the stream has passed the copy).
-static int preprocess_frame(hsflow_ctx *c, uint8_t *dst, const uint8_t *host, size_t stride, bool colour, bool blur, int slot = 0,
-                            bool sync = true)
-{
-    uint8_t *dBgr = nullptr, *dGray = nullptr;
-    const int st = pre_scratch(c, slot, &dBgr, &dGray);
-    if (st) return st;
-    const dim3 grid((c->W + 255) / 256, (c->H + 3) / 4), block(64, 4);
-    if (sync) HS_HIP(c, hipStreamSynchronize(c->stream));
-    if (colour) {
-        if (sync) HS_HIP(c, hipMemcpy2D(dBgr, (size_t)c->W * 3, host, stride, (size_t)c->W * 3, c->H, hipMemcpyHostToDevice));
-        else HS_HIP(c, copy_rows_async(c, dBgr, (size_t)c->W * 3, host, stride, (size_t)c->W * 3, c->H, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(hsk::k_bgr2gray, grid, block, 0, c->stream, dBgr, (long long)c->W * 3, blur ? dGray : dst, c->W, c->H, c->P);
-    } else {
-        if (sync) HS_HIP(c, hipMemcpy2D(blur ? dGray : dst, c->P, host, stride, c->W, c->H, hipMemcpyHostToDevice));
-        else HS_HIP(c, copy_rows_async(c, blur ? dGray : dst, c->P, host, stride, c->W, c->H, hipMemcpyHostToDevice));
-    }
-    if (blur) hipLaunchKernelGGL(hsk::k_box_blur3, grid, block, 0, c->stream, dGray, dst, c->W, c->H, c->P);
-    HS_HIP(c, hipGetLastError());
-    if (sync) HS_HIP(c, hipStreamSynchronize(c->stream));
-    return HSFLOW_OK;
+    return frames_in(c, pair, pair_in(HSFLOW_FRAMES_GRAY8, dprev, ps, dcurr, cs, false, true));
 }
 
 int hsflow_set_frames_bgr8(hsflow_ctx *c, int pair, const uint8_t *prev, size_t ps, const uint8_t *curr, size_t cs, int blur3x3)
 {
-    int st = check_ctx(c, pair);
-    if (st) return st;
-    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
-    if (!prev || !curr) return fail(c, HSFLOW_E_ARG, "null frame pointer");
-    if (ps < (size_t)c->W * 3 || cs < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "colour frame stride smaller than 3*width");
-    if ((st = preprocess_frame(c, c->dA + pair * c->plane, prev, ps, true, blur3x3 != 0))) return st;
-    if ((st = preprocess_frame(c, c->dB + pair * c->plane, curr, cs, true, blur3x3 != 0))) return st;
-    c->frames_set = true;
-    c->coef_valid = false;
-    return HSFLOW_OK;
+    return frames_in(c, pair, pair_in(blur3x3 ? HSFLOW_FRAMES_BGR8_BLUR : HSFLOW_FRAMES_BGR8, prev, ps, curr, cs, true, false));
 }
 
 int hsflow_set_frames_gray8_blur(hsflow_ctx *c, int pair, const uint8_t *prev, size_t ps, const uint8_t *curr, size_t cs)
 {
-    int st = check_ctx(c, pair);
-    if (st) return st;
-    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
-    if (!prev || !curr) return fail(c, HSFLOW_E_ARG, "null frame pointer");
-    if (ps < (size_t)c->W || cs < (size_t)c->W) return fail(c, HSFLOW_E_SIZE, "frame stride smaller than width");
-    if ((st = preprocess_frame(c, c->dA + pair * c->plane, prev, ps, false, true))) return st;
-    if ((st = preprocess_frame(c, c->dB + pair * c->plane, curr, cs, false, true))) return st;
-    c->frames_set = true;
-    c->coef_valid = false;
-    return HSFLOW_OK;
+    return frames_in(c, pair, pair_in(HSFLOW_FRAMES_GRAY8_BLUR, prev, ps, curr, cs, true, false));
 }
 
-// Asynchronous forms: everything is only enqueued on ctx's stream (uploads into two scratch areas, then
-// the conversion / blur kernels); the host buffers belong to the context until hsflow_synchronize.
 int hsflow_set_frames_bgr8_async(hsflow_ctx *c, int pair, const uint8_t *prev, size_t ps, const uint8_t *curr, size_t cs, int blur3x3)
 {
-    int st = check_ctx(c, pair);
-    if (st) return st;
-    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
-    if (!prev || !curr) return fail(c, HSFLOW_E_ARG, "null frame pointer");
-    if (ps < (size_t)c->W * 3 || cs < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "colour frame stride smaller than 3*width");
-    if ((st = preprocess_frame(c, c->dA + pair * c->plane, prev, ps, true, blur3x3 != 0, 0, false))) return st;
-    if ((st = preprocess_frame(c, c->dB + pair * c->plane, curr, cs, true, blur3x3 != 0, 1, false))) return st;
-    c->frames_set = true;
-    c->coef_valid = false;
-    return HSFLOW_OK;
+    return frames_in(c, pair, pair_in(blur3x3 ? HSFLOW_FRAMES_BGR8_BLUR : HSFLOW_FRAMES_BGR8, prev, ps, curr, cs, true, true));
 }
 
 int hsflow_set_frames_gray8_blur_async(hsflow_ctx *c, int pair, const uint8_t *prev, size_t ps, const uint8_t *curr, size_t cs)
 {
-    int st = check_ctx(c, pair);
-    if (st) return st;
-    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
-    if (!prev || !curr) return fail(c, HSFLOW_E_ARG, "null frame pointer");
-    if (ps < (size_t)c->W || cs < (size_t)c->W) return fail(c, HSFLOW_E_SIZE, "frame stride smaller than width");
-    if ((st = preprocess_frame(c, c->dA + pair * c->plane, prev, ps, false, true, 0, false))) return st;
-    if ((st = preprocess_frame(c, c->dB + pair * c->plane, curr, cs, false, true, 1, false))) return st;
-    c->frames_set = true;
-    c->coef_valid = false;
-    return HSFLOW_OK;
+    return frames_in(c, pair, pair_in(HSFLOW_FRAMES_GRAY8_BLUR, prev, ps, curr, cs, true, true));
 }
 
-// Frames that lie in device memory, in any HSFLOW_FRAMES_* layout: the whole pre-processing of the pair is ONE launch
-// (k_pre_pair) on the context's stream.
 int hsflow_set_frames_device_ex(hsflow_ctx *c, int pair, int format, const void *dprev, size_t ps, const void *dcurr, size_t cs)
 {
-    if (format == HSFLOW_FRAMES_GRAY8) return hsflow_set_frames_u8_device(c, pair, dprev, ps, dcurr, cs);
-    int st = check_ctx(c, pair);
-    if (st) return st;
-    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
-    if (!dprev || !dcurr) return fail(c, HSFLOW_E_ARG, "null frame pointer");
-    if (!hspre::format_known(format)) return fail(c, HSFLOW_E_ARG, "unknown frame format");
-    const size_t rowb = (size_t)c->W * (hspre::format_colour(format) ? 3 : 1);
-    if (ps < rowb || cs < rowb) return fail(c, HSFLOW_E_SIZE, hspre::format_colour(format) ? "colour frame stride smaller than 3*width" : "frame stride smaller than width");
-    if ((st = launch_pre(c, format, 2, dprev, ps, dcurr, cs, c->dA + pair * c->plane, c->dB + pair * c->plane))) return st;
-    c->frames_set = true;
-    c->coef_valid = false;
-    return HSFLOW_OK;
+    return frames_in(c, pair, pair_in(format, dprev, ps, dcurr, cs, false, true));
 }
 
-// The camera sequence (OpticalFlowOpenCV.cpp:92-93,118): prev := reblur_prev ? box_blur3(curr) : curr, then
-// curr := pre(format, next) -- two launches in stream order (one launch could not do both: the second write would race
-// the first read of the same plane), into the planes the cached graphs were captured with.  host: `next` is host memory,
-// uploaded into the context's scratch first; complete on return.
-static int push_frame_impl(hsflow_ctx *c, int pair, int format, const void *next, size_t ns, int reblur_prev, bool host)
+int hsflow_push_frame_u8(hsflow_ctx *c, int pair, const uint8_t *next, size_t ns)
 {
-    int st = check_ctx(c, pair);
-    if (st) return st;
-    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
-    if (!next) return fail(c, HSFLOW_E_ARG, "null frame pointer");
-    if (!hspre::format_known(format)) return fail(c, HSFLOW_E_ARG, "unknown frame format");
-    if (reblur_prev != 0 && reblur_prev != 1) return fail(c, HSFLOW_E_ARG, "reblur_prev must be 0 or 1");
-    const bool colour = hspre::format_colour(format);
-    const size_t rowb = (size_t)c->W * (colour ? 3 : 1);
-    if (ns < rowb) return fail(c, HSFLOW_E_SIZE, colour ? "colour frame stride smaller than 3*width" : "frame stride smaller than width");
-    if (!c->frames_set) return fail(c, HSFLOW_E_STATE, "push_frame needs a previous pair");
-    uint8_t *dPrev = c->dA + pair * c->plane, *dCurr = c->dB + pair * c->plane;
-    const void *src = next;
-    size_t sp = ns;
-    if (host && format != HSFLOW_FRAMES_GRAY8) { // (area 1: the unfused route stages a single frame through area 0)
-        uint8_t *dBgr = nullptr, *dGray = nullptr;
-        if ((st = pre_scratch(c, 1, &dBgr, &dGray))) return st;
-        src = colour ? dBgr : dGray;
-        sp = colour ? rowb : (size_t)c->P;
-        HS_HIP(c, hipStreamSynchronize(c->stream));
-        HS_HIP(c, hipMemcpy2D(const_cast<void *>(src), sp, next, ns, rowb, c->H, hipMemcpyHostToDevice));
-    }
-    if (reblur_prev) {
-        if ((st = launch_pre(c, HSFLOW_FRAMES_GRAY8_BLUR, 1, dCurr, (size_t)c->P, nullptr, 0, dPrev, nullptr, true))) return st;
-    } else {
-        HS_HIP(c, hipMemcpyAsync(dPrev, dCurr, (size_t)c->plane, hipMemcpyDeviceToDevice, c->stream));
-    }
-    if (format == HSFLOW_FRAMES_GRAY8) {
-        if (host) HS_HIP(c, hipStreamSynchronize(c->stream));
-        if ((st = copy_frame_in(c, dCurr, next, ns, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, host))) return st;
-    } else if ((st = launch_pre(c, format, 1, src, sp, nullptr, 0, dCurr, nullptr))) return st;
-    if (host) HS_HIP(c, hipStreamSynchronize(c->stream));
-    c->coef_valid = false;
-    return HSFLOW_OK;
+    return frames_in(c, pair, push_in(HSFLOW_FRAMES_GRAY8, next, ns, 0, true));
 }
 
 int hsflow_push_frame_ex(hsflow_ctx *c, int pair, int format, const uint8_t *next, size_t stride, int reblur_prev)
 {
-    return push_frame_impl(c, pair, format, next, stride, reblur_prev, true);
+    return frames_in(c, pair, push_in(format, next, stride, reblur_prev, true));
 }
 
 int hsflow_push_frame_device_ex(hsflow_ctx *c, int pair, int format, const void *d_next, size_t stride, int reblur_prev)
 {
-    return push_frame_impl(c, pair, format, d_next, stride, reblur_prev, false);
+    return frames_in(c, pair, push_in(format, d_next, stride, reblur_prev, false));
 }
 
 int hsflow_preprocess_frame_host(int format, const uint8_t *src, size_t src_stride, int width, int height, uint8_t *dst, size_t dst_stride)
@@ -766,13 +720,7 @@ int hsflow_get_derivatives(hsflow_ctx *c, int pair, float *dx, float *dy, float 
     const size_t rowb = (size_t)c->W * 4;
     if ((stride & 3) || stride < rowb) return fail(c, HSFLOW_E_SIZE, "stride must be a multiple of 4 and >= 4*width");
     if (!c->coef_valid) return fail(c, HSFLOW_E_STATE, "no derivatives yet: call hsflow_solve first");
-    const size_t need = (size_t)c->W * c->H * 3 * sizeof(float);
-    if (c->scratch_bytes < need) {
-        hipFree(c->dScratch);
-        c->dScratch = nullptr; c->scratch_bytes = 0;
-        HS_HIP(c, hipMalloc(&c->dScratch, need));
-        c->scratch_bytes = need;
-    }
+    if ((st = scratch_reserve(c, (size_t)c->W * c->H * 3 * sizeof(float)))) return st;
     float *sx = (float *)c->dScratch, *sy = sx + (size_t)c->W * c->H, *stt = sy + (size_t)c->W * c->H;
     if (c->coef_mode == HSFLOW_MODE_CLASSIC) // (each mode packs its derivatives its own way)
         hipLaunchKernelGGL(hsk::k_unpack_deriv<true>, dim3((c->W + 255) / 256, c->H), dim3(256), 0, c->stream,

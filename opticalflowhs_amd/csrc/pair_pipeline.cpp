@@ -110,6 +110,39 @@ int finish_slot(hsflow_pipeline *pl, hsflow_pipeline::Slot &s)
     return HSFLOW_OK;
 }
 
+// What the three submit forms share.  open_job: the arguments every form checks, the slot whose turn it is -- free once
+// the job that used it `depth` submissions ago has finished -- and the params as the solve gets them (stream_shape).
+// close_job: the slot runs the job; u = v = nullptr: the flow stays in the slot (hsflow_pipeline_flow_device).
+struct Job {
+    hsflow_pipeline::Slot *s = nullptr;
+    hsflow_params shaped;
+    const hsflow_params *use = nullptr;
+};
+
+int open_job(hsflow_pipeline *pl, int format, const hsflow_params *params, bool flow_given, Job &j)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    if (format < HSFLOW_FRAMES_GRAY8 || format > HSFLOW_FRAMES_BGR8_BLUR) return pfail(pl, HSFLOW_E_ARG, "unknown frame format");
+    if (!params) return pfail(pl, HSFLOW_E_ARG, "params is null");
+    if (!flow_given) return pfail(pl, HSFLOW_E_ARG, "null flow pointer");
+    j.s = &pl->slots[pl->next % pl->slots.size()];
+    const int st = finish_slot(pl, *j.s);
+    if (st) return st;
+    j.use = params; // (a struct of another size is not copied: hsflow_solve_async refuses it)
+    if (params->struct_size == sizeof(hsflow_params)) { j.shaped = stream_shape(pl, *params); j.use = &j.shaped; }
+    return HSFLOW_OK;
+}
+
+int close_job(hsflow_pipeline *pl, Job &j, float *u, size_t us, float *v, size_t vs, uint64_t *ticket)
+{
+    j.s->busy = true;
+    j.s->ticket = pl->next;
+    j.s->u = u; j.s->v = v; j.s->us = us; j.s->vs = vs;
+    if (ticket) *ticket = pl->next;
+    pl->next++;
+    return HSFLOW_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -190,13 +223,10 @@ int hsflow_pipeline_submit(hsflow_pipeline *pl, const uint8_t *prev, size_t ps, 
 int hsflow_pipeline_submit_ex(hsflow_pipeline *pl, int format, const uint8_t *prev, size_t ps, const uint8_t *curr, size_t cs,
                               float *u, size_t us, float *v, size_t vs, const hsflow_params *params, uint64_t *ticket)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    if (format < HSFLOW_FRAMES_GRAY8 || format > HSFLOW_FRAMES_BGR8_BLUR) return pfail(pl, HSFLOW_E_ARG, "unknown frame format");
-    if (!params) return pfail(pl, HSFLOW_E_ARG, "params is null");
-    if (!u || !v) return pfail(pl, HSFLOW_E_ARG, "null flow pointer");
-    hsflow_pipeline::Slot &s = pl->slots[pl->next % pl->slots.size()];
-    int st = finish_slot(pl, s); // the job that used this slot `depth` submissions ago
+    Job j;
+    int st = open_job(pl, format, params, u && v, j);
     if (st) return st;
+    hsflow_pipeline::Slot &s = *j.s;
     switch (format) { // the reference CPU route's pre-processing (gray, 3x3 blur) can ride along on the device
     case HSFLOW_FRAMES_GRAY8: st = hsflow_set_frames_u8_async(s.ctx, 0, prev, ps, curr, cs); break;
     case HSFLOW_FRAMES_GRAY8_BLUR: st = hsflow_set_frames_gray8_blur_async(s.ctx, 0, prev, ps, curr, cs); break;
@@ -206,10 +236,7 @@ int hsflow_pipeline_submit_ex(hsflow_pipeline *pl, int format, const uint8_t *pr
         hsflow_synchronize(s.ctx); // one of the two uploads may have been queued already
         return ctx_fail(pl, s.ctx, st, "upload of the frames");
     }
-    hsflow_params shaped;
-    const hsflow_params *use = params; // (a struct of another size is not copied: hsflow_solve_async refuses it)
-    if (params->struct_size == sizeof(hsflow_params)) { shaped = stream_shape(pl, *params); use = &shaped; }
-    if ((st = hsflow_solve_async(s.ctx, use))) {
+    if ((st = hsflow_solve_async(s.ctx, j.use))) {
         hsflow_synchronize(s.ctx); // the uploads were queued: do not leave them reading caller memory
         return ctx_fail(pl, s.ctx, st, "hsflow_solve_async");
     }
@@ -221,65 +248,39 @@ int hsflow_pipeline_submit_ex(hsflow_pipeline *pl, int format, const uint8_t *pr
         hsflow_synchronize(s.ctx);
         return pfail(pl, HSFLOW_E_DEVICE, "hipEventRecord failed");
     }
-    s.busy = true;
-    s.ticket = pl->next;
-    s.u = u; s.v = v; s.us = us; s.vs = vs;
-    if (ticket) *ticket = pl->next;
-    pl->next++;
-    return HSFLOW_OK;
+    return close_job(pl, j, u, us, v, vs, ticket);
 }
 
 int hsflow_pipeline_submit_device(hsflow_pipeline *pl, const void *d_prev, size_t ps, const void *d_curr, size_t cs,
                                   const hsflow_params *params, uint64_t *ticket)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    if (!params) return pfail(pl, HSFLOW_E_ARG, "params is null");
-    hsflow_pipeline::Slot &s = pl->slots[pl->next % pl->slots.size()];
-    int st = finish_slot(pl, s); // the job that used this slot `depth` submissions ago
+    Job j;
+    int st = open_job(pl, HSFLOW_FRAMES_GRAY8, params, true, j);
     if (st) return st;
-    hsflow_params shaped;
-    const hsflow_params *use = params; // (a struct of another size is not copied: hsflow_solve_async refuses it)
-    if (params->struct_size == sizeof(hsflow_params)) { shaped = stream_shape(pl, *params); use = &shaped; }
     // frames and solve in one call: where the solve's first launch can read the caller's planes (strip kernel with the
     // derivative pass, word-aligned sources) it also leaves the slot's copy of them behind, and no copy kernel runs
-    if ((st = hsflow_solve_async_frames_device(s.ctx, d_prev, ps, d_curr, cs, use))) {
-        hsflow_synchronize(s.ctx); // whatever was queued: do not leave it reading caller memory
-        return ctx_fail(pl, s.ctx, st, "hsflow_solve_async_frames_device");
+    if ((st = hsflow_solve_async_frames_device(j.s->ctx, d_prev, ps, d_curr, cs, j.use))) {
+        hsflow_synchronize(j.s->ctx); // whatever was queued: do not leave it reading caller memory
+        return ctx_fail(pl, j.s->ctx, st, "hsflow_solve_async_frames_device");
     }
-    s.busy = true;
-    s.ticket = pl->next;
-    s.u = s.v = nullptr; s.us = s.vs = 0; // the flow stays in the slot (hsflow_pipeline_flow_device)
-    if (ticket) *ticket = pl->next;
-    pl->next++;
-    return HSFLOW_OK;
+    return close_job(pl, j, nullptr, 0, nullptr, 0, ticket);
 }
 
 int hsflow_pipeline_submit_device_ex(hsflow_pipeline *pl, int format, const void *d_prev, size_t ps, const void *d_curr, size_t cs,
                                      const hsflow_params *params, uint64_t *ticket)
 {
     if (format == HSFLOW_FRAMES_GRAY8) return hsflow_pipeline_submit_device(pl, d_prev, ps, d_curr, cs, params, ticket);
-    if (!pl) return HSFLOW_E_ARG;
-    if (format < HSFLOW_FRAMES_GRAY8 || format > HSFLOW_FRAMES_BGR8_BLUR) return pfail(pl, HSFLOW_E_ARG, "unknown frame format");
-    if (!params) return pfail(pl, HSFLOW_E_ARG, "params is null");
-    hsflow_pipeline::Slot &s = pl->slots[pl->next % pl->slots.size()];
-    int st = finish_slot(pl, s); // the job that used this slot `depth` submissions ago
+    Job j;
+    int st = open_job(pl, format, params, true, j);
     if (st) return st;
     // the fused pre-processing launch stands where the copy kernel stands in a gray pair's chain; the solve then works
     // from the slot's planes, like after a host submit
-    if ((st = hsflow_set_frames_device_ex(s.ctx, 0, format, d_prev, ps, d_curr, cs))) return ctx_fail(pl, s.ctx, st, "hsflow_set_frames_device_ex");
-    hsflow_params shaped;
-    const hsflow_params *use = params; // (a struct of another size is not copied: hsflow_solve_async refuses it)
-    if (params->struct_size == sizeof(hsflow_params)) { shaped = stream_shape(pl, *params); use = &shaped; }
-    if ((st = hsflow_solve_async(s.ctx, use))) {
-        hsflow_synchronize(s.ctx); // the pre-processing was queued: do not leave it reading caller memory
-        return ctx_fail(pl, s.ctx, st, "hsflow_solve_async");
+    if ((st = hsflow_set_frames_device_ex(j.s->ctx, 0, format, d_prev, ps, d_curr, cs))) return ctx_fail(pl, j.s->ctx, st, "hsflow_set_frames_device_ex");
+    if ((st = hsflow_solve_async(j.s->ctx, j.use))) {
+        hsflow_synchronize(j.s->ctx); // the pre-processing was queued: do not leave it reading caller memory
+        return ctx_fail(pl, j.s->ctx, st, "hsflow_solve_async");
     }
-    s.busy = true;
-    s.ticket = pl->next;
-    s.u = s.v = nullptr; s.us = s.vs = 0; // the flow stays in the slot (hsflow_pipeline_flow_device)
-    if (ticket) *ticket = pl->next;
-    pl->next++;
-    return HSFLOW_OK;
+    return close_job(pl, j, nullptr, 0, nullptr, 0, ticket);
 }
 
 int hsflow_pipeline_flow_device(hsflow_pipeline *pl, uint64_t ticket, const float **du, const float **dv, size_t *stride_bytes)

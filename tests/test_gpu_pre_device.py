@@ -1,10 +1,11 @@
-"""Device-resident frame pre-processing (ABI 0.9): the fused kernel behind hsflow_set_frames_device_ex against the CPU oracle
-and against the host-pointer entries (the old two kernels), the camera sequence of hsflow_push_frame[_device]_ex against
-the oracle run through the reference's loop, hsflow_pipeline_submit_device_ex against the host-buffer pipeline, and the
-CLI's camera route, which now pushes frames instead of reading the blurred one back."""
+"""Frame pre-processing on the device (ABI 0.9): the fused kernel behind hsflow_set_frames_device_ex against the CPU oracle,
+and the host-pointer entries (uploads into the context's staging, then k_bgr2gray / k_box_blur3) against the oracle too; the
+camera sequence of hsflow_push_frame[_device]_ex against the oracle run through the reference's loop,
+hsflow_pipeline_submit_device_ex against the host-buffer pipeline, and the CLI's camera route, which pushes frames instead
+of reading the blurred one back."""
+import ctypes
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -47,7 +48,7 @@ def strided_device(img, offset, stride):
 
 
 def host_route(ctx, a, b, frames):
-    """The same pixels through the host-pointer entries (k_bgr2gray / k_box_blur3)."""
+    """The same pixels through the host-pointer entries (uploaded into the staging, then k_bgr2gray / k_box_blur3)."""
     if frames == "gray_blur":
         ctx.set_frames_gray_blur(a, b)
     else:
@@ -55,9 +56,10 @@ def host_route(ctx, a, b, frames):
     return ctx.frames()
 
 
-def check_kernel_against_two_references(hs, oracle):
-    """Every shape of the CPU list x every format, the (alignment, stride) variant cycling through all sixteen; then all
-    sixteen on one shape that has a ragged last group and a strip seam."""
+def check_both_routes_against_the_oracle(hs, oracle):
+    """Device sources against the oracle, then host sources of the same pixels against the oracle and against the device
+    route.  Every shape of the CPU list x every format, the (alignment, stride) variant cycling through all sixteen; then
+    all sixteen on one shape that has a ragged last group and a strip seam."""
     S = hs.PRE_STRIP_ROWS
     rng = np.random.default_rng(17)
     case = 0
@@ -73,6 +75,7 @@ def check_kernel_against_two_references(hs, oracle):
         tag = (W, H, frames, off_a, off_b, extra_a, extra_b)
         assert np.array_equal(fa, oracle_pre(oracle, a, frames)) and np.array_equal(fb, oracle_pre(oracle, b, frames)), tag
         ha, hb = host_route(ctx, a, b, frames)
+        assert np.array_equal(ha, oracle_pre(oracle, a, frames)) and np.array_equal(hb, oracle_pre(oracle, b, frames)), tag
         assert np.array_equal(fa, ha) and np.array_equal(fb, hb), tag
 
     extras = [0, 1, 4, 3]   # strides 3W, 3W+1, 3W+4 (W, W+1, W+4 for gray) and +3
@@ -99,14 +102,136 @@ def check_kernel_against_two_references(hs, oracle):
 
 
 def test_fused_kernel_against_oracle_and_host_entries(hs, oracle, gpu_ok):
-    check_kernel_against_two_references(hs, oracle)
+    check_both_routes_against_the_oracle(hs, oracle)
 
 
-def test_unfused_switch_runs_the_same_checks_in_a_child(hs, oracle, gpu_ok):
-    """HSFLOW_PRE_UNFUSED=1 is read when a context is created: a fresh process runs the same comparison on the old kernels."""
-    env = dict(os.environ, HSFLOW_PRE_UNFUSED="1")
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "kernel-check"], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "kernel-check ok unfused=1" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+def strided_host(img, offset, stride):
+    """`img` as a view into a larger NumPy byte array: base `offset` bytes past its start, rows `stride` bytes apart, the
+    bytes between rows filled with a value of their own; the array ends with the last row.  Returns (rows, the array)."""
+    H, rowb = img.shape[0], int(np.prod(img.shape[1:]))
+    host = np.full(offset + (H - 1) * stride + rowb, 0xA5, np.uint8)
+    rows = np.lib.stride_tricks.as_strided(host[offset:], (H, rowb), (stride, 1))
+    rows[...] = img.reshape(H, rowb)
+    return rows, host
+
+
+@pytest.mark.parametrize("entry", ["sync", "async"])
+def test_host_sources_that_are_not_dense(hs, oracle, gpu_ok, entry):
+    """Host frames with padded rows and an odd base, straight through the C entries (the Python wrappers make rows dense):
+    a ragged last group, a strip seam and, at 257, more than one wavefront.  Frame a and frame b are different random
+    frames and each plane is compared with its own oracle frame, so a swap of the two staging areas, or a launch that
+    reads area 0 twice, fails here."""
+    S = hs.PRE_STRIP_ROWS
+    L = hs._lib.load()
+    rng = np.random.default_rng(23)
+    tail = "_async" if entry == "async" else ""
+    for W, H in ((5, S + 1), (257, S + 1)):
+        with hs.HSFlow(W, H, 1, own_stream=True) as ctx:
+            for frames in FORMATS:
+                colour = frames.startswith("bgr")
+                shape = (H, W, 3) if colour else (H, W)
+                rowb = W * (3 if colour else 1)
+                for extra_a, extra_b, off_a, off_b in ((1, 4, 1, 3), (4, 1, 3, 1)):
+                    a, b = rng.integers(0, 256, shape, dtype=np.uint8), rng.integers(0, 256, shape, dtype=np.uint8)
+                    (ra, keep_a), (rb, keep_b) = strided_host(a, off_a, rowb + extra_a), strided_host(b, off_b, rowb + extra_b)
+                    pa, pb = ctypes.c_void_p(ra.ctypes.data), ctypes.c_void_p(rb.ctypes.data)
+                    assert pa.value % 2 == 1 and pb.value % 2 == 1
+                    if colour:
+                        st = getattr(L, "hsflow_set_frames_bgr8" + tail)(ctx._h, 0, pa, rowb + extra_a, pb, rowb + extra_b, int(frames == "bgr_blur"))
+                    else:
+                        st = getattr(L, "hsflow_set_frames_gray8_blur" + tail)(ctx._h, 0, pa, rowb + extra_a, pb, rowb + extra_b)
+                    assert st == 0, (W, frames, st)
+                    ctx.synchronize()   # the asynchronous forms own keep_a / keep_b until here
+                    fa, fb = ctx.frames()
+                    tag = (W, H, frames, extra_a, extra_b)
+                    assert np.array_equal(fa, oracle_pre(oracle, a, frames)) and np.array_equal(fb, oracle_pre(oracle, b, frames)), tag
+                    del keep_a, keep_b
+
+
+@pytest.mark.parametrize("frames", ["bgr_blur", "gray_blur"])
+def test_staging_reused_in_stream_order(hs, oracle, gpu_ok, frames):
+    """One slot, so every pair goes through the same two staging areas: three different host pairs submitted one after
+    the other without a wait of the test's own (the pipeline itself waits for the slot's last job in every submit), then
+    three more with the slot's frames read after each.  Every flow is bit for bit that of a plain context given the
+    oracle's planes, every frames() the oracle's.  Reuse with the earlier launch still in flight: the next test."""
+    W, H = 264, 96
+    rng = np.random.default_rng(31)
+    shape = (H, W, 3) if frames.startswith("bgr") else (H, W)
+    pairs = [(rng.integers(0, 256, shape, dtype=np.uint8), rng.integers(0, 256, shape, dtype=np.uint8)) for _ in range(3)]
+    crit = dict(lam=0.2, max_iter=40, epsilon=EPS6, term_type=ITER | EPS)
+    want = []
+    with hs.HSFlow(W, H, 1, own_stream=True) as ctx:
+        for a, b in pairs:
+            oa, ob = oracle_pre(oracle, a, frames), oracle_pre(oracle, b, frames)
+            ctx.set_frames(oa, ob)
+            ctx.solve(**crit)
+            want.append((oa, ob) + ctx.flow())
+    with hs.PairPipeline(W, H, depth=1) as pl:
+        out = [(np.zeros((H, W), np.float32), np.zeros((H, W), np.float32)) for _ in range(6)]
+        tickets = [pl.submit(a, b, out[k][0], out[k][1], frames=frames, **crit) for k, (a, b) in enumerate(pairs)]
+        fa, fb = pl.frames(tickets[2])
+        assert np.array_equal(fa, want[2][0]) and np.array_equal(fb, want[2][1])
+        for k, (a, b) in enumerate(pairs):
+            t = pl.submit(a, b, out[3 + k][0], out[3 + k][1], frames=frames, **crit)
+            fa, fb = pl.frames(t)
+            assert np.array_equal(fa, want[k][0]) and np.array_equal(fb, want[k][1]), k
+        pl.drain()
+    for k in range(6):
+        assert np.array_equal(out[k][0], want[k % 3][2]) and np.array_equal(out[k][1], want[k % 3][3]), k
+
+
+def test_staging_reused_while_the_earlier_pair_is_in_flight(hs, oracle, gpu_ok):
+    """Two hsflow_set_frames_*_async calls on one context with nothing waited for in between, a 1080p BGR pair and then a
+    gray pair: the second pair's uploads land in the areas the first pair's launches read, behind them in stream order."""
+    W, H = 1920, 1080
+    L = hs._lib.load()
+    rng = np.random.default_rng(43)
+    a, b = rng.integers(0, 256, (H, W, 3), dtype=np.uint8), rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    g, h = rng.integers(0, 256, (H, W), dtype=np.uint8), rng.integers(0, 256, (H, W), dtype=np.uint8)
+    ptr = lambda x: ctypes.c_void_p(x.ctypes.data)
+    with hs.HSFlow(W, H, 2, own_stream=True) as ctx:
+        ctx.set_frames_bgr(a, b, pair=1)   # (the staging has its size: nothing below waits to grow it)
+        assert L.hsflow_set_frames_bgr8_async(ctx._h, 0, ptr(a), 3 * W, ptr(b), 3 * W, 1) == 0
+        assert L.hsflow_set_frames_gray8_blur_async(ctx._h, 1, ptr(g), W, ptr(h), W) == 0
+        ctx.synchronize()
+        fa, fb = ctx.frames(pair=0)
+        ga, gb = ctx.frames(pair=1)
+    assert np.array_equal(fa, oracle_pre(oracle, a, "bgr_blur")) and np.array_equal(fb, oracle_pre(oracle, b, "bgr_blur"))
+    assert np.array_equal(ga, oracle.box_blur3(g)) and np.array_equal(gb, oracle.box_blur3(h))
+
+
+def test_staging_shared_with_the_derivative_read_back(hs, oracle, gpu_ok):
+    """Frame staging and hsflow_get_derivatives use one grow-only buffer: the read-back grows it between two uploads."""
+    W, H = 260, 17
+    rng = np.random.default_rng(37)
+    a, b = rng.integers(0, 256, (H, W, 3), dtype=np.uint8), rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    g, h = rng.integers(0, 256, (H, W), dtype=np.uint8), rng.integers(0, 256, (H, W), dtype=np.uint8)
+    crit = dict(lam=0.2, max_iter=8, term_type=ITER)
+    with hs.HSFlow(W, H, 1, own_stream=True) as fresh:
+        fresh.set_frames(oracle_pre(oracle, a, "bgr_blur"), oracle_pre(oracle, b, "bgr_blur"))
+        fresh.solve(**crit)
+        want = fresh.derivatives()
+    with hs.HSFlow(W, H, 1, own_stream=True) as ctx:
+        ctx.set_frames_bgr(a, b)
+        ctx.solve(**crit)
+        got = ctx.derivatives()
+        ctx.set_frames_gray_blur(g, h)
+        fa, fb = ctx.frames()
+    assert np.array_equal(fa, oracle.box_blur3(g)) and np.array_equal(fb, oracle.box_blur3(h))
+    for x, y in zip(got, want):
+        assert np.array_equal(x, y)
+
+
+def test_push_from_host_where_every_column_is_a_border_column(hs, oracle, gpu_ok):
+    W, H = 5, 3
+    rng = np.random.default_rng(41)
+    a, b = rng.integers(0, 256, (H, W), dtype=np.uint8), rng.integers(0, 256, (H, W), dtype=np.uint8)
+    bgr = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    with hs.HSFlow(W, H, 1, own_stream=True) as ctx:
+        ctx.set_frames_gray_blur(a, b)
+        ctx.push_frame_ex(bgr, "bgr_blur", reblur_prev=True)
+        fa, fb = ctx.frames()
+    assert np.array_equal(fa, oracle.box_blur3(oracle.box_blur3(b))) and np.array_equal(fb, oracle.box_blur3(oracle.bgr2gray(bgr)))
 
 
 def test_pair_isolation(hs, oracle, gpu_ok):
@@ -194,7 +319,6 @@ def test_camera_sequence(hs, oracle, gpu_ok, where):
 
 
 def test_push_call_order_and_arguments(hs, oracle, gpu_ok):
-    import ctypes
     W, H = 160, 96
     frames = camera_frames()
     L = hs._lib.load()
@@ -338,7 +462,7 @@ def test_cli_camera_route_writes_the_oracle_loops_pictures(hs, oracle, gpu_ok, t
         write_pgm(str(cam / ("frame_%04d.pgm" % i)), f)
     env = dict(os.environ, LD_LIBRARY_PATH=os.path.join(ROOT, "opticalflowhs_amd") + ":" + os.environ.get("LD_LIBRARY_PATH", ""),
                HSFLOW_CAMERA_DIR=str(cam), HSFLOW_CAMERA_OUT=str(out))
-    for name in ("HSFLOW_RENDER_DEVICE", "HSFLOW_VERIFY", "HSFLOW_PRE_UNFUSED"):
+    for name in ("HSFLOW_RENDER_DEVICE", "HSFLOW_VERIFY"):
         env.pop(name, None)
     r = subprocess.run([cli, "-cv", "-cam", ".1", "12"], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "Avg time" in r.stdout, r.stdout + r.stderr
@@ -350,11 +474,3 @@ def test_cli_camera_route_writes_the_oracle_loops_pictures(hs, oracle, gpu_ok, t
         old = new_b
     assert not (out / ("flow_%04d.ppm" % len(frames))).exists()
 
-
-if __name__ == "__main__":   # the child of test_unfused_switch_runs_the_same_checks_in_a_child
-    assert sys.argv[1:] == ["kernel-check"]
-    import opticalflowhs_amd
-    from oracle import hs_oracle
-    hs_oracle.build()
-    check_kernel_against_two_references(opticalflowhs_amd, hs_oracle)
-    print("kernel-check ok unfused=%s" % os.environ.get("HSFLOW_PRE_UNFUSED", "0"))
