@@ -30,6 +30,8 @@
  *   hsflow_render_flow[_device] ......... the arrow drawing after the read-back: cvCircle + cvLine per grid point
  *                                          (OpticalFlowOpenCV.cpp:33-46, HSOpticalFlowOpenCL.cpp:759-769), from the
  *                                          flow where it lies -- no read-back
+ *   hsflow_render_flow_jpeg[_device] .... cvSaveImage(output, imgFlow) behind it (OpticalFlowOpenCV.cpp:47,
+ *                                          HSOpticalFlowOpenCL.cpp:771): the picture's JPEG file, encoded on the device
  *   hsflow_verify ....................... HSOpticalFlowOpenCL::verifyResults (HSOpticalFlowOpenCL.cpp:894), the hook of
  *                                          SDKUtil/include/SDKApplication.hpp that the reference left a stub
  *   hsflow_calc_optical_flow_hs_8u32f ... one-shot form with the argument list of OpenCV's
@@ -51,7 +53,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 9 /* 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 10 /* 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -466,6 +468,59 @@ int hsflow_render_flow(hsflow_ctx *ctx, int pair, const hsflow_render_params *rp
  * number and writes the first `capacity` of them to xy as x, y pairs.  -1: non-positive size or xy null. */
 int hsflow_render_line_pixels(int x0, int y0, int x1, int y1, int width, int height, int32_t *xy, int capacity);
 
+/* --- the picture's file (cvSaveImage) ------------------------------------------------------- */
+
+/* The reference delivers a file: runFromImg ends in cvSaveImage(output, imgFlow) (OpticalFlowOpenCV.cpp:47,
+ * HSOpticalFlowOpenCL.cpp:771), libjpeg with its defaults.  The file, exactly:
+ *   JFIF 1.01 baseline, the Annex K quantisation tables scaled by the quality (scale = q < 50 ? 5000 / q : 200 - 2 q,
+ *   (base * scale + 50) / 100 clamped to 1..255), libjpeg's 16-bit fixed-point RGB -> YCbCr, 4:2:0 chroma (2x2 box
+ *   average, rounding bias alternating 1, 2 along a row; the planes padded to whole MCUs by edge replication, the
+ *   DOWNSAMPLED chroma plane by repeating its last row), the "islow" forward DCT, the standard Huffman tables, luma
+ *   blocks outside the component's own block grid as dummy blocks (no AC, the DC of the block before), no restart
+ *   markers, the stream padded with 1-bits, 0x00 behind every 0xFF, FF D9.
+ * That is byte for byte what the drop-in CLI's writer (csrc/host/jpeg_encode.hpp) writes for an RGB picture, and with
+ * it what libjpeg-turbo writes at the same quality with 4:2:0 and what the reference's own output files hold.  The
+ * device forms compute it where the picture lies: of a 1080p picture (6.2 MB) only the file (tens of KB for an arrow
+ * picture) crosses PCIe.  The bytes do not depend on the order of execution and are the same on every run.
+ * quality: 1..100, otherwise HSFLOW_E_ARG; 95 is what cvSaveImage uses.  Gray pictures, other subsamplings, optimised
+ * Huffman tables and restart markers are not offered. */
+#define HSFLOW_JPEG_HEADER_BYTES 623 /* SOI, JFIF, two DQT, SOF0, four DHT, SOS: the same count for every picture */
+/* Bytes that always suffice: 625 + 416 * 6 * ceil(w/16) * ceil(h/16)  (1660 bits per block, every byte stuffed); 0 for a non-positive size. */
+size_t hsflow_jpeg_bound(int width, int height);
+/* The rule on the host, no device needed (like hsflow_preprocess_frame_host): rgb is width x height pixels of 3 bytes,
+ * rows `stride` bytes apart; the file goes to jpeg[0 .. capacity) and its size to *bytes.  Reads exactly the picture's
+ * pixels and writes nothing at or beyond jpeg + capacity.
+ * HSFLOW_E_ARG: null pointer (jpeg may be null when capacity is 0), quality outside 1..100; HSFLOW_E_SIZE: width or
+ * height outside 1..65535, stride < 3*width, or capacity below the file's size -- then *bytes still holds the size
+ * needed and the first `capacity` bytes are the file's; HSFLOW_E_OOM: no host memory for the coefficients. */
+int hsflow_jpeg_encode_host(const uint8_t *rgb, size_t stride, int width, int height, int quality,
+                            uint8_t *jpeg, size_t capacity, size_t *bytes);
+/* An RGB picture of the context's size in device memory -> JPEG bytes in device memory; only enqueued on ctx's stream
+ * (seven launches and a memset, nothing read back in between; complete after hsflow_synchronize / a wait for the
+ * stream).  d_bytes: a device word, 8-byte aligned, that receives the file's size.  Nothing at or beyond
+ * d_jpeg + capacity is written; with capacity below the file's size *d_bytes still holds the size needed -- this form
+ * cannot know and returns HSFLOW_OK: the caller compares.  With capacity >= hsflow_jpeg_bound that never happens.
+ * Touches no solver state.  The first encode of a context allocates its scratch (coefficients, bit lengths and offsets,
+ * the raw stream, per quality the tables and header: 18.0 MB at 1080p), kept until hsflow_destroy; contexts that never
+ * encode pay nothing, and the scratch does not count for HSFLOW_KERNEL_PERSIST's "only one alive" rule.
+ * HSFLOW_E_ARG: null pointer, d_bytes not 8-byte aligned, quality outside 1..100; HSFLOW_E_SIZE: stride < 3*width, a
+ * context wider or higher than 65535. */
+int hsflow_jpeg_encode_device(hsflow_ctx *ctx, const void *d_rgb, size_t stride, int quality,
+                              void *d_jpeg, size_t capacity, uint64_t *d_bytes /* device, 8-byte aligned */);
+/* hsflow_render_flow_device into the context's own picture + the encode, behind each other on the stream.  The
+ * ordering rules of hsflow_render_flow_device apply word for word: an ITER|EPS check that hsflow_solve_async still
+ * owes is settled first, the flow is read and never changed, and on a context with hsflow_set_async_reduce
+ * hsflow_wait_solve and hsflow_flow_view_device called after it wait for the stream.  Argument errors: those of
+ * hsflow_render_flow_device and of hsflow_jpeg_encode_device. */
+int hsflow_render_flow_jpeg_device(hsflow_ctx *ctx, int pair, const hsflow_render_params *rp, int quality,
+                                   void *d_jpeg, size_t capacity, uint64_t *d_bytes);
+/* The same into host memory, synchronous: only the file's bytes cross PCIe (size word first, then that many bytes).
+ * Complete on return; waits only for what this context enqueued.  HSFLOW_E_SIZE with capacity below the file's size:
+ * *bytes holds the size needed and jpeg is left alone.  Keeps the file on the device (at most min(capacity,
+ * hsflow_jpeg_bound) bytes, allocated on demand) and a page-locked size word until hsflow_destroy. */
+int hsflow_render_flow_jpeg(hsflow_ctx *ctx, int pair, const hsflow_render_params *rp, int quality,
+                            uint8_t *jpeg, size_t capacity, size_t *bytes);
+
 /* --- is it right?  (verifyResults) -------------------------------------------------------- */
 
 /* The reference's class has a verifyResults() like every SDK sample (SDKUtil/include/SDKApplication.hpp) and left it
@@ -648,6 +703,10 @@ int hsflow_pipeline_wait(hsflow_pipeline *pl, uint64_t ticket); /* u, v of that 
  * errors as hsflow_render_flow_device. */
 int hsflow_pipeline_render(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, uint8_t *rgb, size_t stride);
 int hsflow_pipeline_render_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, void *d_rgb, size_t stride);
+/* wait(ticket) + the JPEG file of that pair's picture (hsflow_render_flow_jpeg of its slot): complete on return.
+ * HSFLOW_E_STATE if the slot has been reused already; otherwise the errors of hsflow_render_flow_jpeg. */
+int hsflow_pipeline_render_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, int quality,
+                                uint8_t *jpeg, size_t capacity, size_t *bytes);
 /* wait(ticket) -- a pair whose early stop fired has been re-solved by then -- + hsflow_verify of that pair on its slot:
  * what the slot actually ran is verified, including a launch shape the pipeline chose itself (three or more lanes).
  * HSFLOW_E_STATE if the slot has been reused already. */

@@ -126,6 +126,11 @@ PROTOTYPES = {
     "hsflow_default_render_params": (None, [_rp, _i]),
     "hsflow_render_flow_device": (_i, [_vp, _i, _rp, _vp, _sz]),
     "hsflow_render_flow": (_i, [_vp, _i, _rp, _vp, _sz]),
+    "hsflow_jpeg_bound": (_sz, [_i, _i]),
+    "hsflow_jpeg_encode_host": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, ctypes.POINTER(_sz)]),
+    "hsflow_jpeg_encode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
+    "hsflow_render_flow_jpeg_device": (_i, [_vp, _i, _rp, _i, _vp, _sz, _vp]),
+    "hsflow_render_flow_jpeg": (_i, [_vp, _i, _rp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
     "hsflow_render_line_pixels": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i]),
     "hsflow_compare_planes_host": (_i, [_vp, _sz, _vp, _sz, _i, _i, _dp]),
     "hsflow_compare_flow_device": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _dp, _dp]),
@@ -153,6 +158,7 @@ PROTOTYPES = {
     "hsflow_pipeline_flow_device": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
     "hsflow_pipeline_wait": (_i, [_vp, ctypes.c_uint64]),
     "hsflow_pipeline_render": (_i, [_vp, ctypes.c_uint64, _rp, _vp, _sz]),
+    "hsflow_pipeline_render_jpeg": (_i, [_vp, ctypes.c_uint64, _rp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
     "hsflow_pipeline_render_device": (_i, [_vp, ctypes.c_uint64, _rp, _vp, _sz]),
     "hsflow_pipeline_info": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(HsflowInfo)]),
     "hsflow_pipeline_drain": (_i, [_vp]),

@@ -71,6 +71,39 @@ int draw_on_device(hsflow_ctx *ctx, int preset, int W, int H, pnm::Image &imgFlo
     return st == HSFLOW_OK ? SDK_SUCCESS : SDK_FAILURE;
 }
 
+// HSFLOW_JPEG_DEVICE=1 next to HSFLOW_RENDER_DEVICE=1, and an output name ending in .jpg / .jpeg: the file itself comes
+// from the device (hsflow_render_flow_jpeg) and is written as it is -- the picture never crosses, only its file.
+bool jpeg_on_device(const std::string &output)
+{
+    const char *e = getenv("HSFLOW_JPEG_DEVICE");
+    if (!render_on_device() || !e || atoi(e) == 0) return false;
+    auto ends = [&](const char *x) {
+        const size_t n = std::strlen(x);
+        if (output.size() < n) return false;
+        for (size_t i = 0; i < n; i++) {
+            const char c = output[output.size() - n + i];
+            if ((c >= 'A' && c <= 'Z' ? c + 32 : c) != x[i]) return false;
+        }
+        return true;
+    };
+    return ends(".jpg") || ends(".jpeg");
+}
+
+// The device route of the file: ctx's current flow drawn, encoded (quality 95, as cvSaveImage) and written to `output`.
+int save_jpeg_from_device(hsflow_ctx *ctx, int preset, int W, int H, const std::string &output)
+{
+    hsflow_render_params rp;
+    hsflow_default_render_params(&rp, preset);
+    std::vector<uint8_t> file(hsflow_jpeg_bound(W, H));
+    size_t n = 0;
+    const int st = hsflow_render_flow_jpeg(ctx, 0, &rp, 95, file.data(), file.size(), &n);
+    if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+    FILE *f = fopen(output.c_str(), "wb");
+    if (!f) return SDK_FAILURE;
+    const bool ok = fwrite(file.data(), 1, n, f) == n;
+    return fclose(f) == 0 && ok ? SDK_SUCCESS : SDK_FAILURE;
+}
+
 } // namespace
 
 HSOpticalFlowOpenCL::HSOpticalFlowOpenCL(const char *name, char *src_, char *in1, char *in2, char *out, float alp,
@@ -187,6 +220,7 @@ int HSOpticalFlowOpenCL::run()
         if (solvePair(g1, g2, false) != SDK_SUCCESS) return SDK_FAILURE;
         std::cout << "Avg time: " << lastMs << " [ms]" << std::endl; // :755
         const int verdict = verify_wanted() ? verifyResults() : SDK_SUCCESS;
+        if (jpeg_on_device(output)) return save_jpeg_from_device(ctx, HSFLOW_RENDER_CL, (int)width, (int)height, output) == SDK_SUCCESS ? verdict : SDK_FAILURE;
         pnm::Image imgFlow;
         if (drawFlow(imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
         if (!output.empty() && !pnm::save_image(output, imgFlow)) return SDK_FAILURE;
@@ -269,10 +303,13 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     hsflow_verify_report report;
     const int verdict = verify_wanted() ? verify_pair(ctx, W, report) : SDK_SUCCESS; // (the context goes away below)
     pnm::Image imgFlow;
-    if (on_device && draw_on_device(ctx, HSFLOW_RENDER_CV, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
+    const bool file_on_device = jpeg_on_device(output ? output : "");
+    if (file_on_device) {
+        if (save_jpeg_from_device(ctx, HSFLOW_RENDER_CV, W, H, output) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
+    } else if (on_device && draw_on_device(ctx, HSFLOW_RENDER_CV, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     hsflow_destroy(ctx);
     if (!on_device) draw_cv_flow(imgFlow, u, v, W, H);
-    pnm::save_image(output, imgFlow);
+    if (!file_on_device) pnm::save_image(output, imgFlow);
     std::cout << "Avg time: " << ms << " [ms]" << std::endl;
     return verdict;
 }

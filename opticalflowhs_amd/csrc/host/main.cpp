@@ -8,6 +8,8 @@
 // kept only when HSFLOW_PAUSE is set.
 // HSFLOW_RENDER_DEVICE=1: the arrow picture is drawn on the device (hsflow_render_flow) and the flow is not
 // downloaded; the files written are the same.
+// HSFLOW_JPEG_DEVICE=1 with it, and an output name ending in .jpg / .jpeg (the two -hd routes): the file is encoded on
+// the device too (hsflow_render_flow_jpeg) and written as it is; the same bytes.
 // HSFLOW_VERIFY=1: every solved pair is verified on the device (hsflow_verify: re-solved sweep by sweep, compared
 // there) before its context goes away; one "Passed!" / "Failed" line per pair on stdout, the pictures are written as
 // always, and the exit status is SDK_FAILURE if any pair failed.

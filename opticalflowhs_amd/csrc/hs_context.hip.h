@@ -161,6 +161,22 @@ struct hsflow_ctx {
     bool prio_dirty = false;    // a render failed between its two launches: clear the plane before the next one
     uint8_t *dRgb = nullptr;
     hipEvent_t evRender = nullptr;
+    // hsflow_jpeg_encode_device and the render-and-encode forms (hs_jpeg.hip.h), allocated by the first encode and kept:
+    // one block of device memory carved into the coefficients (128 B per block), the blocks' bit lengths and offsets, the
+    // raw stream (208 B per block), the chunks' 0xFF counts and offsets and a size word; the tables and header of every
+    // quality used so far; for the synchronous forms the file on the device and a page-locked size word
+    struct JpegScratch {
+        void *base = nullptr;
+        int16_t *coef = nullptr;
+        uint32_t *len = nullptr, *raw = nullptr, *ff = nullptr;
+        uint64_t *off = nullptr, *ffoff = nullptr, *size = nullptr;
+        long long nb = 0, nchunks = 0;
+        size_t raw_bytes = 0;
+        std::map<int, hsjpeg::Tables *> tables; // by quality, device memory
+        uint8_t *out = nullptr;
+        size_t out_bytes = 0;
+        uint64_t *hSize = nullptr;
+    } jpeg;
     // hsflow_verify / hsflow_compare_flow_device (hs_verify.hip.h), all allocated by the first call: the parameters of the
     // last solve asked for through the ABI and how it ended; the reference pass's own buffers, held as a second context
     // object that borrows this one's frames and stream (`shadow`; it is `borrowed`: not counted in g_live_ctx, and it frees

@@ -12,6 +12,7 @@
 #include "hs_kernels_classic_strip.hip.h"
 #include "hs_kernels_render.hip.h"
 #include "hs_kernels_verify.hip.h"
+#include "hs_kernels_jpeg.hip.h"
 
 #include <atomic>
 #include <chrono>
@@ -34,6 +35,8 @@
 #include "hs_runtime.hip.h"
 #include "hs_solve.hip.h"
 
+
+namespace { void jpeg_release(hsflow_ctx *c); } // hs_jpeg.hip.h
 
 extern "C" {
 
@@ -236,6 +239,7 @@ int hsflow_destroy(hsflow_ctx *c)
     hipFree(c->dScratch);
     hipFree(c->dPrio); hipFree(c->dRgb);
     if (c->evRender) hipEventDestroy(c->evRender);
+    jpeg_release(c);
     if (c->hEps) hipHostFree(c->hEps);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -845,3 +849,4 @@ void hsflow_release_cached(void)
 
 #include "hs_render.hip.h" // hsflow_render_flow[_device], hsflow_default_render_params
 #include "hs_verify.hip.h" // hsflow_verify, hsflow_compare_flow_device, hsflow_compare_planes_host
+#include "hs_jpeg.hip.h"   // hsflow_jpeg_bound, hsflow_jpeg_encode_host / _device, hsflow_render_flow_jpeg[_device]

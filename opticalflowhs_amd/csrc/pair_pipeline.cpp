@@ -318,6 +318,18 @@ int hsflow_pipeline_render(hsflow_pipeline *pl, uint64_t ticket, const hsflow_re
     return HSFLOW_OK;
 }
 
+int hsflow_pipeline_render_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, int quality, uint8_t *jpeg, size_t capacity,
+                                size_t *bytes)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    // (like hsflow_render_flow it waits for an event behind its own work only)
+    if ((st = hsflow_render_flow_jpeg(s->ctx, 0, rp, quality, jpeg, capacity, bytes))) return ctx_fail(pl, s->ctx, st, "hsflow_render_flow_jpeg");
+    return HSFLOW_OK;
+}
+
 int hsflow_pipeline_render_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, void *d_rgb, size_t stride)
 {
     if (!pl) return HSFLOW_E_ARG;

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HsflowError, HsflowInfo, HsflowVerifyReport, TERM_ITER
-from .solver import _is_device_tensor, _render_host, _render_target, make_params, make_render_params
+from .solver import _is_device_tensor, _render_host, _render_target, jpeg_bound, make_params, make_render_params
 
 
 def pinned_empty(shape, dtype):
@@ -141,6 +141,18 @@ class PairPipeline(object):
         self._check(self._lib.hsflow_pipeline_render(self._h, int(ticket), ctypes.byref(rp), ctypes.c_void_p(img.ctypes.data), img.strides[0]))
         self._held.pop(int(ticket), None)
         return img
+
+    def render_jpeg(self, ticket, route="cv", quality=95, params=None, **kw):
+        """wait(ticket) + the JPEG file of that pair's picture as `bytes` (`HSFlow.render_jpeg` on the slot's stream):
+        drawn and encoded on the device, complete on return.  Raises HsflowError (E_STATE) once `depth` more pairs have
+        been submitted."""
+        rp = params if params is not None else make_render_params(route, **kw)
+        buf = np.empty(jpeg_bound(self.width, self.height), np.uint8)
+        n = ctypes.c_size_t()
+        self._check(self._lib.hsflow_pipeline_render_jpeg(self._h, int(ticket), ctypes.byref(rp), int(quality), ctypes.c_void_p(buf.ctypes.data),
+                                                          buf.size, ctypes.byref(n)))
+        self._held.pop(int(ticket), None)
+        return buf[:n.value].tobytes()
 
     def verify(self, ticket):
         """wait(ticket) + `HSFlow.verify` of that pair on its slot (what the slot actually ran, the pipeline's own launch

@@ -309,6 +309,32 @@ class HSFlow(object):
         self._check(self._lib.hsflow_render_flow(self._h, pair, ctypes.byref(rp), _ptr(img), img.strides[0]))
         return img
 
+    def render_jpeg(self, route="cv", quality=95, pair=0, params=None, **kw):
+        """The JPEG file of the picture `render` draws, as `bytes`: drawn and encoded on the device
+        (`hsflow_render_flow_jpeg`), only the file crosses to the host.  quality 95 is what the reference's cvSaveImage
+        uses: the bytes are then the reference's own output file.  Complete on return."""
+        rp = params if params is not None else make_render_params(route, **kw)
+        buf = np.empty(jpeg_bound(self.width, self.height), np.uint8)
+        n = ctypes.c_size_t()
+        self._check(self._lib.hsflow_render_flow_jpeg(self._h, pair, ctypes.byref(rp), int(quality), _ptr(buf), buf.size, ctypes.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def encode_jpeg(self, rgb, quality=95):
+        """The baseline JPEG file (4:2:0, standard tables) of an RGB picture of the context's size that lies in device
+        memory -- a CUDA uint8 tensor of shape (H, W, 3) with packed pixels and any row stride -- encoded on the device
+        (`hsflow_jpeg_encode_device`) on the context's stream, as `bytes`.  Waits for the tensor's producer on torch's
+        current stream first and for the encode afterwards; only the file crosses to the host."""
+        import torch
+        if not _is_device_tensor(rgb):
+            raise ValueError("expected a CUDA uint8 tensor of shape (height, width, 3); for host arrays use the module's encode_jpeg")
+        ptr, stride = _render_target(rgb, self.height, self.width)
+        out = torch.empty(jpeg_bound(self.width, self.height), dtype=torch.uint8, device=rgb.device)
+        size = torch.zeros(1, dtype=torch.int64, device=rgb.device)
+        torch.cuda.current_stream(rgb.device).synchronize()
+        self._check(self._lib.hsflow_jpeg_encode_device(self._h, ptr, stride, int(quality), _ptr(out), out.numel(), _ptr(size)))
+        self.synchronize()
+        return out[:int(size.item())].cpu().numpy().tobytes()
+
     def verify(self, pair=-1):
         """Is the flow held now what a sweep-by-sweep solve of the frames held, with the parameters of the last solve,
         produces?  Re-solves on the device with the one-sweep kernel behind the stand-alone derivative kernel into
@@ -385,6 +411,28 @@ def preprocess_frame(img, frames):
     if st:
         raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
     return out
+
+
+def jpeg_bound(width, height):
+    """Bytes that always suffice for the JPEG file of a width x height picture (`hsflow_jpeg_bound`); 0 for a non-positive size."""
+    return int(_lib.load().hsflow_jpeg_bound(int(width), int(height)))
+
+
+def encode_jpeg(rgb, quality=95):
+    """The JPEG rule on the host (`hsflow_jpeg_encode_host`; no device needed): the file of an (H, W, 3) uint8 RGB array as
+    `bytes` -- baseline, 4:2:0, standard tables, byte for byte what the device encoder and the drop-in CLI write."""
+    lib = _lib.load()
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("expected a uint8 array of shape (H, W, 3)")
+    if rgb.strides[2] != 1 or rgb.strides[1] != 3 or rgb.strides[0] < 3 * rgb.shape[1]:
+        rgb = np.ascontiguousarray(rgb)
+    buf = np.empty(jpeg_bound(rgb.shape[1], rgb.shape[0]), np.uint8)
+    n = ctypes.c_size_t()
+    st = lib.hsflow_jpeg_encode_host(_ptr(rgb), rgb.strides[0], rgb.shape[1], rgb.shape[0], int(quality), _ptr(buf), buf.size, ctypes.byref(n))
+    if st:
+        raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
+    return buf[:n.value].tobytes()
 
 
 def plan_query(width, height, n_pairs=1, params=None, **kw):
