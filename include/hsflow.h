@@ -32,6 +32,11 @@
  *                                          flow where it lies -- no read-back
  *   hsflow_render_flow_jpeg[_device] .... cvSaveImage(output, imgFlow) behind it (OpticalFlowOpenCV.cpp:47,
  *                                          HSOpticalFlowOpenCL.cpp:771): the picture's JPEG file, encoded on the device
+ *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
+ *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
+ *                                          the pictures are decoded on the device
+ *   hsflow_push_frame_jpeg .............. the camera loop's cvQueryFrame (OpticalFlowOpenCV.cpp:85) for a camera that
+ *                                          delivers MJPEG
  *   hsflow_verify ....................... HSOpticalFlowOpenCL::verifyResults (HSOpticalFlowOpenCL.cpp:894), the hook of
  *                                          SDKUtil/include/SDKApplication.hpp that the reference left a stub
  *   hsflow_calc_optical_flow_hs_8u32f ... one-shot form with the argument list of OpenCV's
@@ -53,7 +58,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 10 /* 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 11 /* 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -63,6 +68,7 @@ extern "C" {
 #define HSFLOW_E_OOM 4     /* host or device allocation failed                     */
 #define HSFLOW_E_STATE 5   /* call order (solve before frames were set, ...)       */
 #define HSFLOW_E_NOTERM 6  /* termination rule that would never stop               */
+#define HSFLOW_E_DATA 7    /* a file's contents: unsupported kind, corrupt or truncated entropy-coded data */
 
 /* termination flags: values of CV_TERMCRIT_ITER / CV_TERMCRIT_EPS (cxtypes.h:894-896) */
 #define HSFLOW_TERM_ITER 1
@@ -520,6 +526,72 @@ int hsflow_render_flow_jpeg_device(hsflow_ctx *ctx, int pair, const hsflow_rende
  * hsflow_jpeg_bound) bytes, allocated on demand) and a page-locked size word until hsflow_destroy. */
 int hsflow_render_flow_jpeg(hsflow_ctx *ctx, int pair, const hsflow_render_params *rp, int quality,
                             uint8_t *jpeg, size_t capacity, size_t *bytes);
+
+/* --- the input files (cvLoadImage) ---------------------------------------------------------- */
+
+/* The reference reads its two frames with cvLoadImage(path, 1) (OpticalFlowOpenCV.cpp:15,18, HSOpticalFlowOpenCL.cpp:721,
+ * 732): libjpeg with its defaults -- baseline Huffman decoding, the "islow" inverse DCT, "fancy" triangle upsampling of
+ * the chroma planes (plain replication for planes at most 2 samples wide), the 16-bit fixed-point YCbCr -> RGB
+ * conversion -- into 3 bytes per pixel, B first.  The rule is csrc/hs_jpegd_rule.h, one header for the host form and the
+ * kernels; its pixels are those of the drop-in CLI's reader (csrc/host/jpeg_baseline.hpp, held to libjpeg-turbo by
+ * tests/test_jpeg.py) for every file both accept.
+ * Accepted: SOF0 / SOF1 with 8-bit samples, 1 or 3 components, luma sampling 1x1, 2x1 or 2x2 with 1x1 chroma, one
+ * interleaved scan, 8- and 16-bit quantisation tables, restart intervals.  Everything else is HSFLOW_E_DATA from the
+ * header alone: progressive, lossless, arithmetic and 12-bit files, other sampling factors, a second frame header, a
+ * missing table, an empty scan header, an entropy-coded segment of 256 MB or more.
+ * Stricter than that reader in the entropy-coded data: a decode that consumes a bit at or beyond the segment's end is
+ * an error (status word 2, "truncated"; the reader pads with zeros), and so is a code of no table, a DC category
+ * above 11, a zero run past coefficient 63, or a de-quantised coefficient beyond +-1151 -- what an 8x8 block of 8-bit
+ * samples can produce with an 8-bit quantiser, and what the 32-bit inverse DCT carries -- (status word 1, "corrupt").
+ * The device form decodes a file without restart intervals by self-synchronising speculation: the unstuffed segment is
+ * cut into subsequences of HSFLOW_JPEGD_SUBSEQ_BITS bits that are decoded at once from guessed states and repaired
+ * until every one starts where its predecessor ended; with restart intervals every interval is decoded on its own.
+ * The pixels depend on neither. */
+#define HSFLOW_JPEGD_SUBSEQ_BITS 1024 /* a multiple of 32; the environment variable of the same name overrides it per call, 32..4096 */
+#define HSFLOW_JPEG_ORDER_BGR 0 /* what cvLoadImage(..., 1) returns and HSFLOW_FRAMES_BGR8 takes */
+#define HSFLOW_JPEG_ORDER_RGB 1
+typedef struct hsflow_jpeg_info {
+    uint32_t struct_size; /* sizeof(hsflow_jpeg_info), set by the caller */
+    int32_t width, height, components; /* components: 1 or 3 */
+    int32_t h_samp, v_samp;            /* luma sampling factors; chroma is 1x1 */
+    int32_t restart_interval;          /* MCUs per restart interval, 0: none */
+    int32_t subseq_bits;               /* bits per subsequence a device decode of this file runs with now; 0 with restart intervals */
+    int64_t blocks;                    /* 8x8 blocks in the scan, MCU padding included */
+    uint64_t scan_offset, scan_bytes;  /* the entropy-coded segment within the file, up to the marker that ends it */
+} hsflow_jpeg_info;
+/* The header alone, on the host.  HSFLOW_E_ARG: null pointer, struct_size; HSFLOW_E_DATA: see above. */
+int hsflow_jpeg_read_header(const uint8_t *file, size_t bytes, hsflow_jpeg_info *info);
+/* The rule on the host, no device needed: pix receives width x height pixels of 3 bytes, rows `stride` apart, in
+ * `order`.  info may be null.  Writes exactly the picture's pixels, and none unless it returns HSFLOW_OK.
+ * HSFLOW_E_ARG: null file or pix, unknown order, struct_size; HSFLOW_E_SIZE: stride < 3*width; HSFLOW_E_DATA: the header
+ * or the entropy-coded data (hsflow_last_error(NULL) says which); HSFLOW_E_OOM. */
+int hsflow_jpeg_decode_host(const uint8_t *file, size_t bytes, int order, uint8_t *pix, size_t stride, hsflow_jpeg_info *info);
+/* A file in HOST memory -> its picture in device memory; only enqueued on ctx's stream (a copy of the entropy-coded
+ * segment and the tables from page-locked staging of the library's own -- the caller's buffer is free on return; two
+ * staging areas, so two decodes can be enqueued back to back and a third waits for the first one's copy --, three
+ * memsets and twelve launches without restart intervals, nine with; nothing read back in between).  The picture
+ * must have the context's size, else HSFLOW_E_SIZE.  HSFLOW_E_DATA is returned at once for what the header shows;
+ * d_status, a device word, receives what only the bit stream shows: 0 ok, 1 corrupt, 2 truncated (the pixels are then
+ * undefined, but nothing outside the picture's width x height x 3 bytes is written either way).
+ * Touches no solver state: an owed ITER|EPS check stays owed.  The first decode of a context allocates its scratch
+ * (coefficients, component planes, DC sums: 20.4 MB at 1080p; per file the segment, the clean stream and the
+ * subsequences' states, grown on demand behind a wait for the stream), kept until hsflow_destroy; contexts that never
+ * decode pay nothing, and the scratch does not count for HSFLOW_KERNEL_PERSIST's "only one alive" rule.
+ * HSFLOW_E_ARG: null pointer, unknown order, d_status not 4-byte aligned, HSFLOW_JPEGD_SUBSEQ_BITS in the environment
+ * not a multiple of 32 in 32..4096; HSFLOW_E_SIZE: stride < 3*width, a picture of another size. */
+int hsflow_jpeg_decode_device(hsflow_ctx *ctx, const uint8_t *file, size_t bytes, int order, void *d_pix, size_t stride,
+                              uint32_t *d_status /* device word: 0 ok, 1 corrupt, 2 truncated */);
+/* The same into host memory, synchronous; a non-zero status word becomes HSFLOW_E_DATA and pix is left alone.  The
+ * device-side picture has pix's alignment modulo 4 and its row padding modulo 4, so the stores are those the device form
+ * would use.  For checking. */
+int hsflow_jpeg_decode(hsflow_ctx *ctx, const uint8_t *file, size_t bytes, int order, uint8_t *pix, size_t stride);
+/* Both files into BGR pictures the context keeps on the device, then exactly hsflow_set_frames_device_ex(BGR8 or
+ * BGR8_BLUR) on them.  Synchronous like hsflow_set_frames_bgr8.  On HSFLOW_E_DATA (either file) and HSFLOW_E_SIZE the
+ * context's frames are unchanged.  Like every frame entry it settles an owed ITER|EPS check first. */
+int hsflow_set_frames_jpeg(hsflow_ctx *ctx, int pair, const uint8_t *prev, size_t prev_bytes, const uint8_t *curr, size_t curr_bytes,
+                           int blur3x3);
+/* The same in front of hsflow_push_frame_device_ex: the camera sequence fed with MJPEG frames. */
+int hsflow_push_frame_jpeg(hsflow_ctx *ctx, int pair, const uint8_t *next, size_t bytes, int blur3x3, int reblur_prev);
 
 /* --- is it right?  (verifyResults) -------------------------------------------------------- */
 

@@ -10,12 +10,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HSFLOW_LIB_PATH") or os.path.join(HERE, "libhsflow.so")  # override: diagnostic builds
 
 # status codes / enums of include/hsflow.h
-OK, E_ARG, E_SIZE, E_DEVICE, E_OOM, E_STATE, E_NOTERM = range(7)
+OK, E_ARG, E_SIZE, E_DEVICE, E_OOM, E_STATE, E_NOTERM, E_DATA = range(8)
 TERM_ITER, TERM_EPS = 1, 2
 MODE_CV, MODE_CLASSIC, MODE_CLASSIC_AS_SHIPPED = 0, 1, 2
 KERNEL_AUTO, KERNEL_SIMPLE, KERNEL_FUSED, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST = 0, 1, 2, 3, 4, 5
 FRAMES_GRAY8, FRAMES_GRAY8_BLUR, FRAMES_BGR8, FRAMES_BGR8_BLUR = 0, 1, 2, 3
 RENDER_CV, RENDER_CL = 0, 1
+JPEG_ORDER_BGR, JPEG_ORDER_RGB = 0, 1
+JPEGD_SUBSEQ_BITS = 1024  # HSFLOW_JPEGD_SUBSEQ_BITS
 FRAME_FORMATS = {"gray": FRAMES_GRAY8, "gray_blur": FRAMES_GRAY8_BLUR, "bgr": FRAMES_BGR8, "bgr_blur": FRAMES_BGR8_BLUR}
 
 
@@ -74,6 +76,15 @@ class HsflowPairResult(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
 
 
+class HsflowJpegInfo(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("components", ctypes.c_int32),
+                ("h_samp", ctypes.c_int32), ("v_samp", ctypes.c_int32), ("restart_interval", ctypes.c_int32), ("subseq_bits", ctypes.c_int32),
+                ("blocks", ctypes.c_int64), ("scan_offset", ctypes.c_uint64), ("scan_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
 VERIFY_TINY = 1e-30  # HSFLOW_VERIFY_TINY
 PAIR_STOP_SIMPLE_CHUNK = 32  # HSFLOW_PAIR_STOP_SIMPLE_CHUNK
 PRE_STRIP_ROWS = 8  # HSFLOW_PRE_STRIP_ROWS
@@ -83,6 +94,7 @@ _pp = ctypes.POINTER(HsflowParams)
 _rp = ctypes.POINTER(HsflowRenderParams)
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
+_ji = ctypes.POINTER(HsflowJpegInfo)
 
 # name -> (restype, argtypes).  tests/test_abi.py checks this table against include/hsflow.h.
 PROTOTYPES = {
@@ -131,6 +143,12 @@ PROTOTYPES = {
     "hsflow_jpeg_encode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "hsflow_render_flow_jpeg_device": (_i, [_vp, _i, _rp, _i, _vp, _sz, _vp]),
     "hsflow_render_flow_jpeg": (_i, [_vp, _i, _rp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
+    "hsflow_jpeg_read_header": (_i, [_vp, _sz, _ji]),
+    "hsflow_jpeg_decode_host": (_i, [_vp, _sz, _i, _vp, _sz, _ji]),
+    "hsflow_jpeg_decode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
+    "hsflow_jpeg_decode": (_i, [_vp, _vp, _sz, _i, _vp, _sz]),
+    "hsflow_set_frames_jpeg": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _i]),
+    "hsflow_push_frame_jpeg": (_i, [_vp, _i, _vp, _sz, _i, _i]),
     "hsflow_render_line_pixels": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i]),
     "hsflow_compare_planes_host": (_i, [_vp, _sz, _vp, _sz, _i, _i, _dp]),
     "hsflow_compare_flow_device": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _dp, _dp]),

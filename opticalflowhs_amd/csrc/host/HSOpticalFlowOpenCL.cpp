@@ -154,9 +154,9 @@ int HSOpticalFlowOpenCL::ensureContext(int w, int h)
     return SDK_SUCCESS;
 }
 
-int HSOpticalFlowOpenCL::solvePair(const pnm::Image &a, const pnm::Image &b, bool streaming)
+int HSOpticalFlowOpenCL::solvePair(const pnm::Image &a, const pnm::Image &b, bool streaming, bool frames_set)
 {
-    int st = streaming ? hsflow_push_frame_u8(ctx, 0, b.data.data(), b.width)
+    int st = frames_set ? HSFLOW_OK : streaming ? hsflow_push_frame_u8(ctx, 0, b.data.data(), b.width)
                        : hsflow_set_frames_u8(ctx, 0, a.data.data(), a.width, b.data.data(), b.width);
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
     hsflow_params p;
@@ -197,6 +197,39 @@ int HSOpticalFlowOpenCL::drawFlow(pnm::Image &imgFlow) const
     return SDK_SUCCESS;
 }
 
+// HSFLOW_JPEG_IN_DEVICE=1 on the two "-hd" routes: input files that are JPEG are handed to hsflow_set_frames_jpeg as
+// they are -- decoded on the device, only their entropy-coded bytes cross PCIe -- instead of jpegb::load and an upload
+// of 3 bytes per pixel.  PGM / PPM inputs, and everything without the switch, go the way they always went.
+static bool jpeg_in_device()
+{
+    const char *e = getenv("HSFLOW_JPEG_IN_DEVICE");
+    return e && e[0] == '1';
+}
+
+static bool read_jpeg_file(const std::string &path, std::vector<uint8_t> &buf)
+{
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    uint8_t tmp[65536];
+    size_t n;
+    buf.clear();
+    while ((n = fread(tmp, 1, sizeof tmp, f)) > 0) buf.insert(buf.end(), tmp, tmp + n);
+    fclose(f);
+    return buf.size() >= 2 && buf[0] == 0xFF && buf[1] == 0xD8;
+}
+
+// Both inputs as JPEG files whose headers the library accepts and that agree in size: that size, else false.
+static bool jpeg_pair(const std::string &in1, const std::string &in2, std::vector<uint8_t> &f1, std::vector<uint8_t> &f2, int &W, int &H)
+{
+    if (!jpeg_in_device() || !read_jpeg_file(in1, f1) || !read_jpeg_file(in2, f2)) return false;
+    hsflow_jpeg_info i1, i2;
+    i1.struct_size = i2.struct_size = sizeof(hsflow_jpeg_info);
+    if (hsflow_jpeg_read_header(f1.data(), f1.size(), &i1) != HSFLOW_OK || hsflow_jpeg_read_header(f2.data(), f2.size(), &i2) != HSFLOW_OK) return false;
+    if (i1.width != i2.width || i1.height != i2.height) return false;
+    W = i1.width; H = i1.height;
+    return true;
+}
+
 int HSOpticalFlowOpenCL::run()
 {
     if (!gpu) {
@@ -209,6 +242,17 @@ int HSOpticalFlowOpenCL::run()
     }
     if (src == "-hd") {
         pnm::Image c1, c2, g1, g2;
+        std::vector<uint8_t> f1, f2;
+        int jw = 0, jh = 0;
+        const bool from_files = jpeg_pair(input1, input2, f1, f2, jw, jh);
+        if (from_files) {
+            if (ensureContext(jw, jh) != SDK_SUCCESS) return SDK_FAILURE;
+            if (hsflow_set_frames_jpeg(ctx, 0, f1.data(), f1.size(), f2.data(), f2.size(), 0) != HSFLOW_OK) {
+                std::cout << hsflow_last_error(ctx) << std::endl;
+                return SDK_FAILURE;
+            }
+            if (solvePair(g1, g2, false, true) != SDK_SUCCESS) return SDK_FAILURE;
+        } else {
         if (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2)) {
             std::cout << "Input image error.\n";
             return -1; // HSOpticalFlowOpenCL.cpp:724,735
@@ -218,6 +262,7 @@ int HSOpticalFlowOpenCL::run()
         if (g1.width != g2.width || g1.height != g2.height) { std::cout << "Input image error.\n"; return -1; }
         if (ensureContext(g1.width, g1.height) != SDK_SUCCESS) return SDK_FAILURE;
         if (solvePair(g1, g2, false) != SDK_SUCCESS) return SDK_FAILURE;
+        }
         std::cout << "Avg time: " << lastMs << " [ms]" << std::endl; // :755
         const int verdict = verify_wanted() ? verifyResults() : SDK_SUCCESS;
         if (jpeg_on_device(output)) return save_jpeg_from_device(ctx, HSFLOW_RENDER_CL, (int)width, (int)height, output) == SDK_SUCCESS ? verdict : SDK_FAILURE;
@@ -273,16 +318,21 @@ static void draw_cv_flow(pnm::Image &imgFlow, const std::vector<float> &u, const
 int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, float lambda, int it)
 {
     pnm::Image c1, c2;
-    if (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2) || c1.width != c2.width || c1.height != c2.height) {
+    std::vector<uint8_t> f1, f2;
+    int jw = 0, jh = 0;
+    const bool from_files = jpeg_pair(input1, input2, f1, f2, jw, jh);
+    if (!from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2) || c1.width != c2.width || c1.height != c2.height)) {
         std::cout << "Input image error.\n";
         return -1;
     }
-    const int W = c1.width, H = c1.height;
+    const int W = from_files ? jw : c1.width, H = from_files ? jh : c1.height;
     hsflow_ctx *ctx = nullptr;
     if (hsflow_create(&ctx, 0, W, H, 1, nullptr, 1) != HSFLOW_OK) { std::cout << hsflow_last_error(nullptr) << std::endl; return 1; }
     int st;
     const double t0 = now_ms();
-    if (c1.channels == 3) { // PPM is RGB; the C ABI takes BGR like cvLoadImage delivers
+    if (from_files) { // cvLoadImage + cvCvtColor + cvSmooth, all on the device
+        st = hsflow_set_frames_jpeg(ctx, 0, f1.data(), f1.size(), f2.data(), f2.size(), 1);
+    } else if (c1.channels == 3) { // PPM is RGB; the C ABI takes BGR like cvLoadImage delivers
         std::vector<uint8_t> b1(c1.data), b2(c2.data);
         for (size_t i = 0; i < b1.size(); i += 3) { std::swap(b1[i], b1[i + 2]); std::swap(b2[i], b2[i + 2]); }
         st = hsflow_set_frames_bgr8(ctx, 0, b1.data(), (size_t)W * 3, b2.data(), (size_t)W * 3, 1); // gray + cvSmooth(CV_BLUR,3,3)

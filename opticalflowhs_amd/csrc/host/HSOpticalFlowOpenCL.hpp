@@ -50,7 +50,7 @@ class HSOpticalFlowOpenCL : public SDKSample {
     hsflow_verify_report report{}; // of the last verifyResults
 
     int ensureContext(int w, int h);
-    int solvePair(const pnm::Image &a, const pnm::Image &b, bool streaming);
+    int solvePair(const pnm::Image &a, const pnm::Image &b, bool streaming, bool frames_set = false);
     int drawFlow(pnm::Image &imgFlow) const; // host loop over u, v; HSFLOW_RENDER_DEVICE=1: hsflow_render_flow, no read-back
 
 public:

@@ -177,6 +177,29 @@ struct hsflow_ctx {
         size_t out_bytes = 0;
         uint64_t *hSize = nullptr;
     } jpeg;
+    // hsflow_jpeg_decode_device and the entries built on it (hs_jpegd.hip.h), allocated by the first decode and kept: one
+    // block of device memory sized by the context (coefficients 128 B per block, component planes, DC differences and sums,
+    // the restart intervals' starts), one sized by the longest file so far (tables and segment, the clean stream, per-chunk
+    // and per-subsequence words); two page-locked staging areas with the event behind each one's copy; for the synchronous
+    // forms a picture on the device (its first 256 bytes hold the status words), two BGR pictures, page-locked status words
+    struct JpegdScratch {
+        void *frame_base = nullptr, *file_base = nullptr;
+        size_t file_bytes = 0;
+        long long nb_cap = 0;
+        int16_t *coef = nullptr;
+        uint8_t *planes = nullptr;
+        uint32_t *diff = nullptr, *rstPos = nullptr;
+        uint64_t *dcsum = nullptr;
+        uint8_t *stage[2] = {nullptr, nullptr};
+        size_t stage_bytes[2] = {0, 0};
+        hipEvent_t evStage[2] = {nullptr, nullptr};
+        int next_slot = 0;
+        uint8_t *out = nullptr;
+        size_t out_bytes = 0;
+        uint8_t *bgr[2] = {nullptr, nullptr};
+        uint32_t *dStatus = nullptr, *hStatus = nullptr;
+        hipEvent_t evDone = nullptr;
+    } jpegd;
     // hsflow_verify / hsflow_compare_flow_device (hs_verify.hip.h), all allocated by the first call: the parameters of the
     // last solve asked for through the ABI and how it ended; the reference pass's own buffers, held as a second context
     // object that borrows this one's frames and stream (`shadow`; it is `borrowed`: not counted in g_live_ctx, and it frees

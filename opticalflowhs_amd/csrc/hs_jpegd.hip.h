@@ -1,0 +1,293 @@
+// hs_jpegd.hip.h -- part of libhsflow.so (one translation unit, see hsflow.hip): hsflow_jpeg_read_header,
+// hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg: the frames the reference's
+// runFromImg starts from (cvLoadImage, OpticalFlowOpenCV.cpp:15,18, HSOpticalFlowOpenCL.cpp:721,732), decoded on the
+// device from the files' entropy-coded bytes.  One copy, three memsets and nine or twelve launches on the context's
+// stream (hs_kernels_jpegd.hip.h); a context that never decodes allocates and launches nothing here.
+#pragma once
+
+namespace {
+
+void jpegd_release(hsflow_ctx *c)
+{
+    hsflow_ctx::JpegdScratch &j = c->jpegd;
+    hipFree(j.frame_base);
+    hipFree(j.file_base);
+    hipFree(j.out);
+    for (int i = 0; i < 2; i++) {
+        hipFree(j.bgr[i]);
+        if (j.stage[i]) hipHostFree(j.stage[i]);
+        if (j.evStage[i]) hipEventDestroy(j.evStage[i]);
+    }
+    if (j.hStatus) hipHostFree(j.hStatus);
+    if (j.evDone) hipEventDestroy(j.evDone);
+    c->jpegd = hsflow_ctx::JpegdScratch();
+}
+
+size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+// HSFLOW_JPEGD_SUBSEQ_BITS of this call: the environment's, else the header's.  0: the environment's value is unusable.
+int jpegd_subseq_bits()
+{
+    const char *e = getenv("HSFLOW_JPEGD_SUBSEQ_BITS");
+    if (!e || !*e) return HSFLOW_JPEGD_SUBSEQ_BITS;
+    char *rest = nullptr;
+    const long v = strtol(e, &rest, 10);
+    if (*rest || v < 32 || v > 4096 || v % 32) return 0;
+    return (int)v;
+}
+
+void jpegd_fill_info(const hsjpegd::Frame &f, hsflow_jpeg_info *info)
+{
+    info->width = f.W; info->height = f.H; info->components = f.ncomp; info->h_samp = f.hs; info->v_samp = f.vs;
+    info->restart_interval = f.ri;
+    info->subseq_bits = f.ri ? 0 : jpegd_subseq_bits();
+    info->blocks = f.nblocks; info->scan_offset = f.scan_offset; info->scan_bytes = f.scan_bytes;
+}
+
+// All of one decode, enqueued on c's stream.  The caller has checked every argument and parsed the header.
+int enqueue_jpegd(hsflow_ctx *c, const uint8_t *file, const hsjpegd::Frame &f, const hsjpegd::Tables &tab, int order, uint8_t *d_pix, size_t stride,
+                  uint32_t *d_status)
+{
+    hsflow_ctx::JpegdScratch &j = c->jpegd;
+    const int S = jpegd_subseq_bits();
+    if (!S) return fail(c, HSFLOW_E_ARG, "HSFLOW_JPEGD_SUBSEQ_BITS must be a multiple of 32 in 32 .. 4096");
+    // what the context's size bounds, once: 4:4:4 has the most blocks, 3 per 8x8 pixels of the picture padded to 16
+    if (!j.frame_base) {
+        const long long nb = 12ll * ((c->W + 15) / 16) * ((c->H + 15) / 16);
+        const size_t o_coef = 0, o_planes = o_coef + up256((size_t)nb * 128), o_diff = o_planes + up256((size_t)nb * 64), o_dcsum = o_diff + up256((size_t)nb * 4),
+                     o_rst = o_dcsum + up256(((size_t)nb + 1) * 8), total = o_rst + up256((size_t)nb * 4);
+        HS_HIP(c, hipMalloc(&j.frame_base, total));
+        uint8_t *p = (uint8_t *)j.frame_base;
+        j.coef = (int16_t *)(p + o_coef); j.planes = p + o_planes; j.diff = (uint32_t *)(p + o_diff); j.dcsum = (uint64_t *)(p + o_dcsum);
+        j.rstPos = (uint32_t *)(p + o_rst);
+        j.nb_cap = nb;
+    }
+    if (f.nblocks > j.nb_cap) return fail(c, HSFLOW_E_SIZE, "the file's block count exceeds the context's");
+    // what the file's length bounds: tables + segment (one copy), the clean stream, per chunk and per subsequence words
+    const uint32_t n = (uint32_t)f.scan_bytes, nchunks = (n + hsjpegd::kChunk - 1) / hsjpegd::kChunk;
+    const uint32_t nsubCap = (uint32_t)((((uint64_t)n * 8u + (uint32_t)S - 1u) / (uint32_t)S + hsk::kJpegdGroup - 1u) / hsk::kJpegdGroup * hsk::kJpegdGroup) + (n ? 0u : hsk::kJpegdGroup);
+    const size_t tab_bytes = up256(sizeof(hsjpegd::Tables)), in_bytes = tab_bytes + up256((size_t)n + 4);
+    const size_t o_in = 0, o_clean = o_in + in_bytes, o_cr = o_clean + up256((size_t)n + 16), o_cs = o_cr + up256((size_t)nchunks * 4 + 4),
+                 o_ro = o_cs + up256((size_t)nchunks * 4 + 4), o_so = o_ro + up256(((size_t)nchunks + 1) * 8), o_start = o_so + up256(((size_t)nchunks + 1) * 8),
+                 o_exit = o_start + up256((size_t)nsubCap * 8), o_cnt = o_exit + up256((size_t)nsubCap * 8), o_base = o_cnt + up256((size_t)nsubCap * 4),
+                 need = o_base + up256(((size_t)nsubCap + 1) * 8);
+    if (j.file_bytes < need) { // (what is in flight still reads the old one)
+        HS_HIP(c, hipStreamSynchronize(c->stream));
+        hipFree(j.file_base);
+        j.file_base = nullptr; j.file_bytes = 0;
+        HS_HIP(c, hipMalloc(&j.file_base, need));
+        j.file_bytes = need;
+    }
+    // staging: the older of the two areas, once the copy out of it is done
+    const int slot = j.next_slot;
+    j.next_slot ^= 1;
+    if (j.evStage[slot]) HS_HIP(c, hipEventSynchronize(j.evStage[slot]));
+    else HS_HIP(c, hipEventCreateWithFlags(&j.evStage[slot], hipEventDisableTiming));
+    if (j.stage_bytes[slot] < in_bytes) {
+        if (j.stage[slot]) hipHostFree(j.stage[slot]);
+        j.stage[slot] = nullptr; j.stage_bytes[slot] = 0;
+        HS_HIP(c, hipHostMalloc((void **)&j.stage[slot], in_bytes, hipHostMallocDefault));
+        j.stage_bytes[slot] = in_bytes;
+    }
+    uint8_t *h = j.stage[slot];
+    std::memcpy(h, &tab, sizeof tab);
+    std::memcpy(h + tab_bytes, file + f.scan_offset, n);
+    std::memset(h + tab_bytes + n, 0, in_bytes - tab_bytes - n);
+    uint8_t *p = (uint8_t *)j.file_base;
+    HS_HIP(c, hipMemcpyAsync(p + o_in, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HS_HIP(c, hipEventRecord(j.evStage[slot], c->stream));
+
+    hsk::JpegdArgs a;
+    a.f = f;
+    a.tab = (const hsjpegd::Tables *)(p + o_in);
+    a.scan = p + o_in + tab_bytes;
+    a.n = n; a.nchunks = nchunks; a.S = (uint32_t)S;
+    a.cntRem = (uint32_t *)(p + o_cr); a.cntRst = (uint32_t *)(p + o_cs);
+    a.remOff = (uint64_t *)(p + o_ro); a.rstOff = (uint64_t *)(p + o_so);
+    a.clean = (uint32_t *)(p + o_clean);
+    a.rstPos = j.rstPos;
+    const long long nmcu = (long long)f.mcux * f.mcuy;
+    a.nint = f.ri ? (uint32_t)((nmcu + f.ri - 1) / f.ri) : 0u;
+    a.start = (uint64_t *)(p + o_start); a.exit = (uint64_t *)(p + o_exit);
+    a.cnt = (uint32_t *)(p + o_cnt); a.base = (uint64_t *)(p + o_base);
+    a.nsubCap = nsubCap;
+    a.coef = j.coef; a.diff = j.diff; a.dcsum = j.dcsum; a.planes = j.planes;
+    a.status = d_status;
+
+    const unsigned gc = nchunks ? (nchunks + 255u) / 256u : 1u, gb = (unsigned)((f.nblocks + 255) / 256);
+    HS_HIP(c, hipMemsetAsync(d_status, 0, sizeof(uint32_t), c->stream));
+    HS_HIP(c, hipMemsetAsync(a.clean, 0, up256((size_t)n + 16), c->stream));
+    HS_HIP(c, hipMemsetAsync(a.coef, 0, (size_t)f.nblocks * 128, c->stream));
+    hipLaunchKernelGGL(hsk::k_jpegd_clean<0>, dim3(gc), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(hsk::k_jpeg_scan, dim3(1), dim3(hsk::kJpegScanLanes), 0, c->stream, a.cntRem, a.remOff, (long long)nchunks, (const uint64_t *)nullptr);
+    hipLaunchKernelGGL(hsk::k_jpeg_scan, dim3(1), dim3(hsk::kJpegScanLanes), 0, c->stream, a.cntRst, a.rstOff, (long long)nchunks, (const uint64_t *)nullptr);
+    hipLaunchKernelGGL(hsk::k_jpegd_clean<1>, dim3(gc), dim3(256), 0, c->stream, a);
+    if (!f.ri) {
+        const unsigned gs = nsubCap / hsk::kJpegdGroup;
+        hipLaunchKernelGGL(hsk::k_jpegd_sync, dim3(gs), dim3(hsk::kJpegdGroup), 0, c->stream, a);
+        hipLaunchKernelGGL(hsk::k_jpegd_repair, dim3(1), dim3(hsk::kJpegdRepairLanes), 0, c->stream, a);
+        hipLaunchKernelGGL(hsk::k_jpeg_scan, dim3(1), dim3(hsk::kJpegScanLanes), 0, c->stream, a.cnt, a.base, (long long)nsubCap, (const uint64_t *)nullptr);
+        hipLaunchKernelGGL(hsk::k_jpegd_write, dim3(gs), dim3(256), 0, c->stream, a);
+    } else {
+        hipLaunchKernelGGL(hsk::k_jpegd_write_rst, dim3((a.nint + 255u) / 256u), dim3(256), 0, c->stream, a);
+    }
+    hipLaunchKernelGGL(hsk::k_jpegd_dc_gather, dim3(gb), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(hsk::k_jpeg_scan, dim3(1), dim3(hsk::kJpegScanLanes), 0, c->stream, a.diff, a.dcsum, (long long)f.nblocks, (const uint64_t *)nullptr);
+    hipLaunchKernelGGL(hsk::k_jpegd_blocks, dim3((unsigned)((f.nblocks + 31) / 32)), dim3(256), 0, c->stream, a);
+    const int wide = (((uintptr_t)d_pix | stride) & 3u) == 0;
+    hipLaunchKernelGGL(hsk::k_jpegd_pixels, dim3((f.W + 255) / 256, (f.H + 3) / 4), dim3(64, 4), 0, c->stream, a, d_pix, (long long)stride,
+                       order == HSFLOW_JPEG_ORDER_RGB ? 1 : 0, wide);
+    HS_HIP(c, hipGetLastError());
+    return HSFLOW_OK;
+}
+
+// Header, checks and the enqueue for one file of the context's size.
+int jpegd_one(hsflow_ctx *c, const uint8_t *file, size_t bytes, int order, uint8_t *d_pix, size_t stride, uint32_t *d_status)
+{
+    if (!file) return fail(c, HSFLOW_E_ARG, "null file pointer");
+    if (order != HSFLOW_JPEG_ORDER_BGR && order != HSFLOW_JPEG_ORDER_RGB) return fail(c, HSFLOW_E_ARG, "unknown pixel order");
+    hsjpegd::Frame f;
+    std::unique_ptr<hsjpegd::Tables> t(new (std::nothrow) hsjpegd::Tables);
+    if (!t) return fail(c, HSFLOW_E_OOM, "host allocation failed");
+    const char *why = "";
+    if (hsjpegd::parse(file, bytes, f, *t, &why)) return fail(c, HSFLOW_E_DATA, std::string("JPEG file: ") + why);
+    if (f.W != c->W || f.H != c->H) return fail(c, HSFLOW_E_SIZE, "the picture does not have the context's size");
+    if (stride < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
+    return enqueue_jpegd(c, file, f, *t, order, d_pix, stride, d_status);
+}
+
+// The status words of the decodes enqueued so far into page-locked memory, waited for.
+int jpegd_wait_status(hsflow_ctx *c, int words)
+{
+    hsflow_ctx::JpegdScratch &j = c->jpegd;
+    if (!j.evDone) HS_HIP(c, hipEventCreateWithFlags(&j.evDone, hipEventDisableTiming));
+    HS_HIP(c, hipMemcpyAsync(j.hStatus, j.dStatus, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HS_HIP(c, hipEventRecord(j.evDone, c->stream));
+    HS_HIP(c, hipEventSynchronize(j.evDone));
+    for (int i = 0; i < words; i++)
+        if (j.hStatus[i]) return fail(c, HSFLOW_E_DATA, j.hStatus[i] == 2 ? "JPEG file: truncated entropy-coded data" : "JPEG file: corrupt entropy-coded data");
+    return HSFLOW_OK;
+}
+
+// The context's own status words (device and page-locked) and, with pictures != 0, its BGR pictures.
+int jpegd_own(hsflow_ctx *c, int pictures)
+{
+    hsflow_ctx::JpegdScratch &j = c->jpegd;
+    if (!j.hStatus) {
+        HS_HIP(c, hipHostMalloc((void **)&j.hStatus, 64, hipHostMallocDefault));
+        j.hStatus[0] = j.hStatus[1] = 0;
+    }
+    if (!j.out) { HS_HIP(c, hipMalloc((void **)&j.out, 256)); j.out_bytes = 256; } // its first 256 bytes hold the status words, the picture lies behind them
+    for (int i = 0; i < pictures; i++)
+        if (!j.bgr[i]) HS_HIP(c, hipMalloc((void **)&j.bgr[i], (size_t)c->W * 3 * c->H));
+    return HSFLOW_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int hsflow_jpeg_read_header(const uint8_t *file, size_t bytes, hsflow_jpeg_info *info)
+{
+    if (!file || !info) return fail(nullptr, HSFLOW_E_ARG, "hsflow_jpeg_read_header: null pointer");
+    if (info->struct_size != sizeof(hsflow_jpeg_info)) return fail(nullptr, HSFLOW_E_ARG, "hsflow_jpeg_read_header: struct_size mismatch");
+    hsjpegd::Frame f;
+    std::unique_ptr<hsjpegd::Tables> t(new (std::nothrow) hsjpegd::Tables);
+    if (!t) return fail(nullptr, HSFLOW_E_OOM, "hsflow_jpeg_read_header: host allocation failed");
+    const char *why = "";
+    if (hsjpegd::parse(file, bytes, f, *t, &why)) return fail(nullptr, HSFLOW_E_DATA, std::string("JPEG file: ") + why);
+    jpegd_fill_info(f, info);
+    return HSFLOW_OK;
+}
+
+int hsflow_jpeg_decode_host(const uint8_t *file, size_t bytes, int order, uint8_t *pix, size_t stride, hsflow_jpeg_info *info)
+{
+    if (!file || !pix) return fail(nullptr, HSFLOW_E_ARG, "hsflow_jpeg_decode_host: null pointer");
+    if (order != HSFLOW_JPEG_ORDER_BGR && order != HSFLOW_JPEG_ORDER_RGB) return fail(nullptr, HSFLOW_E_ARG, "hsflow_jpeg_decode_host: unknown pixel order");
+    if (info && info->struct_size != sizeof(hsflow_jpeg_info)) return fail(nullptr, HSFLOW_E_ARG, "hsflow_jpeg_decode_host: struct_size mismatch");
+    hsjpegd::Frame f;
+    const char *why = "";
+    int status = 0;
+    const int r = hsjpegd::decode_host(file, bytes, order == HSFLOW_JPEG_ORDER_RGB, pix, stride, &f, &status, &why);
+    if (info && (r == 0 || r == 2 || (r == 7 && status))) jpegd_fill_info(f, info);
+    switch (r) {
+    case 0: return HSFLOW_OK;
+    case 1: return fail(nullptr, HSFLOW_E_ARG, "hsflow_jpeg_decode_host: null pointer");
+    case 2: return fail(nullptr, HSFLOW_E_SIZE, "hsflow_jpeg_decode_host: stride smaller than 3*width");
+    case 7: return fail(nullptr, HSFLOW_E_DATA, std::string("JPEG file: ") + why);
+    default: return fail(nullptr, HSFLOW_E_OOM, "hsflow_jpeg_decode_host: host allocation failed");
+    }
+}
+
+int hsflow_jpeg_decode_device(hsflow_ctx *c, const uint8_t *file, size_t bytes, int order, void *d_pix, size_t stride, uint32_t *d_status)
+{
+    int st = check_ctx(c, 0);
+    if (st) return st;
+    if (!d_pix || !d_status) return fail(c, HSFLOW_E_ARG, "null picture or status pointer");
+    if ((uintptr_t)d_status & 3u) return fail(c, HSFLOW_E_ARG, "the status word must be 4-byte aligned");
+    return jpegd_one(c, file, bytes, order, (uint8_t *)d_pix, stride, d_status);
+}
+
+int hsflow_jpeg_decode(hsflow_ctx *c, const uint8_t *file, size_t bytes, int order, uint8_t *pix, size_t stride)
+{
+    int st = check_ctx(c, 0);
+    if (st) return st;
+    if (!pix) return fail(c, HSFLOW_E_ARG, "null picture pointer");
+    if ((st = jpegd_own(c, 0))) return st;
+    hsflow_ctx::JpegdScratch &j = c->jpegd;
+    const size_t rowb = (size_t)c->W * 3;
+    if (stride < rowb) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
+    // the picture on the device: pix's alignment and row padding modulo 4
+    const size_t dstride = rowb + ((stride - rowb) & 3u), off = 256 + ((uintptr_t)pix & 3u), want = off + dstride * (size_t)c->H;
+    if (j.out_bytes < want) { // (the synchronous forms leave nothing in flight that uses the old one)
+        HS_HIP(c, hipStreamSynchronize(c->stream));
+        hipFree(j.out);
+        j.out = nullptr; j.out_bytes = 0;
+        HS_HIP(c, hipMalloc((void **)&j.out, want));
+        j.out_bytes = want;
+    }
+    j.dStatus = (uint32_t *)j.out;
+    if ((st = jpegd_one(c, file, bytes, order, j.out + off, dstride, j.dStatus))) return st;
+    st = jpegd_wait_status(c, 1);
+    if (!st) {
+        HS_HIP(c, hipMemcpy2DAsync(pix, stride, j.out + off, dstride, rowb, c->H, hipMemcpyDeviceToHost, c->stream));
+        HS_HIP(c, hipEventRecord(j.evDone, c->stream));
+        HS_HIP(c, hipEventSynchronize(j.evDone));
+    }
+    return st;
+}
+
+int hsflow_set_frames_jpeg(hsflow_ctx *c, int pair, const uint8_t *prev, size_t prev_bytes, const uint8_t *curr, size_t curr_bytes, int blur3x3)
+{
+    int st = check_ctx(c, pair);
+    if (st) return st;
+    if (!prev || !curr) return fail(c, HSFLOW_E_ARG, "null file pointer");
+    if ((st = jpegd_own(c, 2))) return st;
+    hsflow_ctx::JpegdScratch &j = c->jpegd;
+    j.dStatus = (uint32_t *)j.out;
+    const size_t rowb = (size_t)c->W * 3;
+    if ((st = jpegd_one(c, prev, prev_bytes, HSFLOW_JPEG_ORDER_BGR, j.bgr[0], rowb, j.dStatus))) return st;
+    if ((st = jpegd_one(c, curr, curr_bytes, HSFLOW_JPEG_ORDER_BGR, j.bgr[1], rowb, j.dStatus + 1))) return st;
+    if ((st = jpegd_wait_status(c, 2))) return st;
+    if ((st = hsflow_set_frames_device_ex(c, pair, blur3x3 ? HSFLOW_FRAMES_BGR8_BLUR : HSFLOW_FRAMES_BGR8, j.bgr[0], rowb, j.bgr[1], rowb))) return st;
+    HS_HIP(c, hipStreamSynchronize(c->stream));
+    return HSFLOW_OK;
+}
+
+int hsflow_push_frame_jpeg(hsflow_ctx *c, int pair, const uint8_t *next, size_t bytes, int blur3x3, int reblur_prev)
+{
+    int st = check_ctx(c, pair);
+    if (st) return st;
+    if (!next) return fail(c, HSFLOW_E_ARG, "null file pointer");
+    if (reblur_prev != 0 && reblur_prev != 1) return fail(c, HSFLOW_E_ARG, "reblur_prev must be 0 or 1");
+    if (!c->frames_set) return fail(c, HSFLOW_E_STATE, "push_frame needs a previous pair");
+    if ((st = jpegd_own(c, 1))) return st;
+    hsflow_ctx::JpegdScratch &j = c->jpegd;
+    j.dStatus = (uint32_t *)j.out;
+    const size_t rowb = (size_t)c->W * 3;
+    if ((st = jpegd_one(c, next, bytes, HSFLOW_JPEG_ORDER_BGR, j.bgr[0], rowb, j.dStatus))) return st;
+    if ((st = jpegd_wait_status(c, 1))) return st;
+    return hsflow_push_frame_device_ex(c, pair, blur3x3 ? HSFLOW_FRAMES_BGR8_BLUR : HSFLOW_FRAMES_BGR8, j.bgr[0], rowb, reblur_prev);
+}
+
+} // extern "C"

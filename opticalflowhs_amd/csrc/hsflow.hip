@@ -13,6 +13,7 @@
 #include "hs_kernels_render.hip.h"
 #include "hs_kernels_verify.hip.h"
 #include "hs_kernels_jpeg.hip.h"
+#include "hs_kernels_jpegd.hip.h"
 
 #include <atomic>
 #include <chrono>
@@ -23,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <tuple>
@@ -36,7 +38,7 @@
 #include "hs_solve.hip.h"
 
 
-namespace { void jpeg_release(hsflow_ctx *c); } // hs_jpeg.hip.h
+namespace { void jpeg_release(hsflow_ctx *c); void jpegd_release(hsflow_ctx *c); } // hs_jpeg.hip.h, hs_jpegd.hip.h
 
 extern "C" {
 
@@ -105,6 +107,7 @@ const char *hsflow_status_string(int s)
     case HSFLOW_E_OOM: return "out of memory";
     case HSFLOW_E_STATE: return "invalid call order";
     case HSFLOW_E_NOTERM: return "termination criteria never met";
+    case HSFLOW_E_DATA: return "unsupported, corrupt or truncated file";
     default: return "unknown status";
     }
 }
@@ -240,6 +243,7 @@ int hsflow_destroy(hsflow_ctx *c)
     hipFree(c->dPrio); hipFree(c->dRgb);
     if (c->evRender) hipEventDestroy(c->evRender);
     jpeg_release(c);
+    jpegd_release(c);
     if (c->hEps) hipHostFree(c->hEps);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -850,3 +854,4 @@ void hsflow_release_cached(void)
 #include "hs_render.hip.h" // hsflow_render_flow[_device], hsflow_default_render_params
 #include "hs_verify.hip.h" // hsflow_verify, hsflow_compare_flow_device, hsflow_compare_planes_host
 #include "hs_jpeg.hip.h"   // hsflow_jpeg_bound, hsflow_jpeg_encode_host / _device, hsflow_render_flow_jpeg[_device]
+#include "hs_jpegd.hip.h"  // hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg

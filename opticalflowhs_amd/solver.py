@@ -335,6 +335,27 @@ class HSFlow(object):
         self.synchronize()
         return out[:int(size.item())].cpu().numpy().tobytes()
 
+    def jpeg_decode(self, data, order="rgb", out=None):
+        """The picture of a baseline JPEG file (`bytes`) of the context's size, decoded on the device
+        (`hsflow_jpeg_decode`): an (H, W, 3) uint8 array, R first ("rgb") or B first ("bgr").  out: a host array to decode
+        into (any row stride).  Complete on return; corrupt or truncated data raise `HsflowError` with status E_DATA."""
+        buf = np.frombuffer(data, np.uint8)
+        img = _render_host(out, self.height, self.width)
+        self._check(self._lib.hsflow_jpeg_decode(self._h, _ptr(buf), buf.size, _jpeg_order(order), _ptr(img), img.strides[0]))
+        return img
+
+    def set_frames_jpeg(self, prev, curr, blur=True, pair=0):
+        """Both frames as baseline JPEG files (`bytes`): decoded on the device, then cvCvtColor (+ cvSmooth with
+        blur=True) there (`hsflow_set_frames_jpeg`) -- only the files' entropy-coded bytes cross to the device."""
+        a, b = np.frombuffer(prev, np.uint8), np.frombuffer(curr, np.uint8)
+        self._check(self._lib.hsflow_set_frames_jpeg(self._h, pair, _ptr(a), a.size, _ptr(b), b.size, 1 if blur else 0))
+
+    def push_frame_jpeg(self, nxt, blur=True, reblur_prev=False, pair=0):
+        """The camera sequence fed with a JPEG frame (`hsflow_push_frame_jpeg`): as `push_frame_ex` with the frame decoded on
+        the device."""
+        a = np.frombuffer(nxt, np.uint8)
+        self._check(self._lib.hsflow_push_frame_jpeg(self._h, pair, _ptr(a), a.size, 1 if blur else 0, 1 if reblur_prev else 0))
+
     def verify(self, pair=-1):
         """Is the flow held now what a sweep-by-sweep solve of the frames held, with the parameters of the last solve,
         produces?  Re-solves on the device with the one-sweep kernel behind the stand-alone derivative kernel into
@@ -433,6 +454,39 @@ def encode_jpeg(rgb, quality=95):
     if st:
         raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
     return buf[:n.value].tobytes()
+
+
+def _jpeg_order(order):
+    if order not in ("rgb", "bgr"):
+        raise ValueError('order must be "rgb" or "bgr"')
+    return _lib.JPEG_ORDER_RGB if order == "rgb" else _lib.JPEG_ORDER_BGR
+
+
+def jpeg_read_header(data):
+    """What the header of a baseline JPEG file (`bytes`) says (`hsflow_jpeg_read_header`; no device needed): a dict of
+    width, height, components, h_samp, v_samp, restart_interval, subseq_bits, blocks, scan_offset, scan_bytes."""
+    lib = _lib.load()
+    buf = np.frombuffer(data, np.uint8)
+    info = _lib.HsflowJpegInfo()
+    info.struct_size = ctypes.sizeof(info)
+    st = lib.hsflow_jpeg_read_header(_ptr(buf), buf.size, ctypes.byref(info))
+    if st:
+        raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
+    return info.as_dict()
+
+
+def jpeg_decode_host(data, order="rgb"):
+    """The JPEG decoding rule on the host (`hsflow_jpeg_decode_host`; no device needed): the (H, W, 3) uint8 picture of a
+    baseline JPEG file given as `bytes`, R first ("rgb") or B first ("bgr") -- pixel for pixel what the device decoder,
+    the drop-in CLI's reader and libjpeg give.  A one-component file gives three equal channels."""
+    info = jpeg_read_header(data)
+    lib = _lib.load()
+    buf = np.frombuffer(data, np.uint8)
+    img = np.empty((info["height"], info["width"], 3), np.uint8)
+    st = lib.hsflow_jpeg_decode_host(_ptr(buf), buf.size, _jpeg_order(order), _ptr(img), img.strides[0], None)
+    if st:
+        raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
+    return img
 
 
 def plan_query(width, height, n_pairs=1, params=None, **kw):
