@@ -37,6 +37,11 @@
  *                                          the pictures are decoded on the device
  *   hsflow_push_frame_jpeg .............. the camera loop's cvQueryFrame (OpticalFlowOpenCV.cpp:85) for a camera that
  *                                          delivers MJPEG
+ *   hsflow_jpeg_decode_batch_device ..... cvLoadImage of many files at once (OpticalFlowOpenCV.cpp:15,18 for the disk
+ *                                          route, :76,83 for the camera loop's frames): one set of launches per batch
+ *   hsflow_set_sequence_jpeg ............ the same in front of a context of N pairs: N + 1 consecutive frames, each
+ *                                          decoded once (the camera loop's cvQueryFrame at :76,83, fed with files)
+ *   hsflow_pipeline_submit_jpeg ......... the disk route's two cvLoadImage (:15,18) in front of a pipeline slot
  *   hsflow_verify ....................... HSOpticalFlowOpenCL::verifyResults (HSOpticalFlowOpenCL.cpp:894), the hook of
  *                                          SDKUtil/include/SDKApplication.hpp that the reference left a stub
  *   hsflow_calc_optical_flow_hs_8u32f ... one-shot form with the argument list of OpenCV's
@@ -58,7 +63,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 11 /* 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 12 /* 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -593,6 +598,61 @@ int hsflow_set_frames_jpeg(hsflow_ctx *ctx, int pair, const uint8_t *prev, size_
 /* The same in front of hsflow_push_frame_device_ex: the camera sequence fed with MJPEG frames. */
 int hsflow_push_frame_jpeg(hsflow_ctx *ctx, int pair, const uint8_t *next, size_t bytes, int blur3x3, int reblur_prev);
 
+/* Many files by the same launches.  Files are independent, so n of them decoded side by side take about as long as
+ * the longest one: every decode kernel has a batched form whose grid carries the file as a further dimension and reads
+ * a per-file record from device memory (csrc/hs_kernels_jpegd.hip.h); the arithmetic is the single-file kernels' own.
+ * A batch larger than HSFLOW_JPEGD_BATCH_MAX is decoded in consecutive chunks of at most that many: per chunk one copy
+ * from page-locked staging (every file's tables and segment, the records), three memsets and eleven launches for files
+ * without restart intervals, eight for files with, twelve for a chunk that mixes the two.  The constant bounds
+ * the scratch: a 1080p file takes 19.8 MB (4:4:4; 10.0 MB at 4:2:0: coefficients, planes, DC sums by its own block
+ * count) plus about 2.4 times its entropy-coded bytes at the default HSFLOW_JPEGD_SUBSEQ_BITS (segment and clean
+ * stream 2, chunk words 0.19, 28 bytes per subsequence 0.22; at 32 bits per subsequence those 28 bytes make it about
+ * 9.2 times), so HSFLOW_JPEGD_BATCH_MAX times that at most (a batch of fewer files
+ * allocates for as many as it has), grown on demand
+ * behind a wait for the stream and kept until hsflow_destroy. */
+/* 32: the smallest of {4, 8, 16, 32} within 5 % of the best per-file time at 1080p (profiles/jpegd_batch_time.txt: 0.633,
+ * 0.345, 0.201, 0.145 ms per file against 2.31 ms alone).  32 x 11.2 MB = 358 MB of scratch for 1080p files of 500 KB at
+ * 4:2:0, about 670 MB at 4:4:4.  The environment variable of the same name overrides it per call, 1..32: that is how the
+ * candidates are measured (tools/jpegd_batch_time.py). */
+#define HSFLOW_JPEGD_BATCH_MAX 32
+/* n files in HOST memory, each of the context's picture size (what cvLoadImage does for OpticalFlowOpenCV.cpp:15,18 and
+ * the camera loop's frames, :76,83) -> n pictures in device memory at d_pix[0 .. n), rows `stride` bytes apart, in
+ * `order`; only enqueued on ctx's stream.  files, bytes and d_pix are host arrays of n entries; the files' buffers
+ * and the arrays are free on return.  Two calls can be enqueued back to back, and behind or in front of
+ * hsflow_jpeg_decode_device, with no synchronisation in between: staging is reused behind an event.
+ * Every header is parsed and every argument checked before anything is enqueued: on an error d_status, the pictures
+ * and the context are untouched, and hsflow_last_error names the file's index ("file 3: ...").  d_status[i], a device
+ * word, receives what only file i's bit stream shows (0 ok, 1 corrupt, 2 truncated); a bad file changes nothing for
+ * the others, and nothing outside any picture's width x height x 3 bytes is written.  A file's pixels are those of
+ * hsflow_jpeg_decode_device, whatever its position, its neighbours, n, the chunking or HSFLOW_JPEGD_SUBSEQ_BITS.
+ * Touches no solver state: an owed ITER|EPS check stays owed.
+ * HSFLOW_E_ARG: n < 1, a null list or entry, unknown order, d_status not 4-byte aligned, HSFLOW_JPEGD_SUBSEQ_BITS or
+ * HSFLOW_JPEGD_BATCH_MAX in the environment unusable; HSFLOW_E_DATA: a header; HSFLOW_E_SIZE: stride < 3*width, a picture of another size. */
+int hsflow_jpeg_decode_batch_device(hsflow_ctx *ctx, const uint8_t *const *files, const size_t *bytes, int n,
+                                    int order, void *const *d_pix, size_t stride, uint32_t *d_status /* n device words */);
+/* n_files >= 2 consecutive frames (the camera loop's cvQueryFrame, OpticalFlowOpenCV.cpp:76,83, fed with files) into
+ * the pairs first_pair .. first_pair + n_files - 2: pair k is (file k, file k + 1).  Every file is decoded once, as one
+ * batch, into BGR pictures the context keeps; each pair then gets exactly hsflow_set_frames_device_ex(BGR8 or
+ * BGR8_BLUR), so its planes are those of hsflow_set_frames_jpeg(ctx, first_pair + k, file k, file k + 1, blur3x3).
+ * Synchronous, and like every frame entry it settles an owed ITER|EPS check first.  All or nothing: on HSFLOW_E_DATA
+ * (any file, header or bit stream), HSFLOW_E_SIZE and HSFLOW_E_ARG (first_pair + n_files - 1 > n_pairs, n_files < 2,
+ * null entries) no pair's frames change.  The camera loop's double blur (reblur_prev) stays with
+ * hsflow_push_frame_jpeg. */
+int hsflow_set_sequence_jpeg(hsflow_ctx *ctx, int first_pair, const uint8_t *const *files, const size_t *bytes,
+                             int n_files, int blur3x3);
+/* hsflow_set_frames_jpeg without the wait, what hsflow_pipeline_submit_jpeg is made of: both headers are checked at
+ * once (HSFLOW_E_DATA / _SIZE / _ARG: nothing enqueued, the frames unchanged); then the two files are decoded as a batch
+ * of two into the context's BGR pictures, the two status words are copied to page-locked memory, and
+ * hsflow_set_frames_device_ex follows, all on ctx's stream.  hsflow_jpeg_async_status waits for that copy alone and
+ * returns HSFLOW_E_DATA if either bit stream was bad (the pair's planes and a solve enqueued behind them are then
+ * meaningless).  It answers once per hsflow_set_frames_jpeg_async, for the latest one: HSFLOW_E_STATE with no such call
+ * before or when that call's status has been asked for already.  The two words are the pair's own, on the device and on
+ * the host: hsflow_jpeg_decode, hsflow_set_frames_jpeg, hsflow_push_frame_jpeg and the batch entries in between do not
+ * change what it answers. */
+int hsflow_set_frames_jpeg_async(hsflow_ctx *ctx, int pair, const uint8_t *prev, size_t prev_bytes, const uint8_t *curr,
+                                 size_t curr_bytes, int blur3x3);
+int hsflow_jpeg_async_status(hsflow_ctx *ctx);
+
 /* --- is it right?  (verifyResults) -------------------------------------------------------- */
 
 /* The reference's class has a verifyResults() like every SDK sample (SDKUtil/include/SDKApplication.hpp) and left it
@@ -765,6 +825,18 @@ int hsflow_pipeline_submit_device(hsflow_pipeline *pl, const void *d_prev, size_
  * pre-processed planes, as after hsflow_pipeline_submit_ex.  The caller's buffers: as for hsflow_pipeline_submit_device. */
 int hsflow_pipeline_submit_device_ex(hsflow_pipeline *pl, int format, const void *d_prev, size_t prev_stride, const void *d_curr,
                                      size_t curr_stride, const hsflow_params *params, uint64_t *ticket);
+/* The same for a pair of JPEG FILES in host memory (the disk route's two cvLoadImage, OpticalFlowOpenCV.cpp:15,18; a
+ * camera that delivers MJPEG, :76,83): both files are decoded as a batch of two on the slot's stream into pictures the
+ * slot's context owns (hsflow_set_frames_jpeg_async); the pre-processing of hsflow_set_frames_device_ex and
+ * hsflow_solve_async follow on the same stream, and the flow stays in the slot as with hsflow_pipeline_submit_device.
+ * Never waits for the device except for a free slot.  The files' buffers are free on return.  What the headers show
+ * (HSFLOW_E_DATA, HSFLOW_E_SIZE) is returned here, and the slot stays free: no ticket is issued.  What only a bit stream
+ * shows is read when the ticket is waited for: hsflow_pipeline_wait, _flow_device, _info, _frames_u8, _verify and
+ * _render* of that ticket return HSFLOW_E_DATA; other tickets, earlier or later, on the same lane or not, are unaffected
+ * (the slot's reuse `depth` submissions later does not report it; hsflow_pipeline_drain does).  With
+ * hsflow_pipeline_render_jpeg of the ticket: files in, a file out, no picture crossing PCIe. */
+int hsflow_pipeline_submit_jpeg(hsflow_pipeline *pl, const uint8_t *prev, size_t prev_bytes, const uint8_t *curr,
+                                size_t curr_bytes, int blur3x3, const hsflow_params *params, uint64_t *ticket);
 /* wait(ticket) + where that pair's flow lies (hsflow_flow_view_device of its slot): valid until `depth` further
  * pairs have been submitted.  HSFLOW_E_STATE if the slot has been reused already. */
 int hsflow_pipeline_flow_device(hsflow_pipeline *pl, uint64_t ticket, const float **d_u, const float **d_v, size_t *stride_bytes);

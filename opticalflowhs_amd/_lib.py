@@ -18,6 +18,7 @@ FRAMES_GRAY8, FRAMES_GRAY8_BLUR, FRAMES_BGR8, FRAMES_BGR8_BLUR = 0, 1, 2, 3
 RENDER_CV, RENDER_CL = 0, 1
 JPEG_ORDER_BGR, JPEG_ORDER_RGB = 0, 1
 JPEGD_SUBSEQ_BITS = 1024  # HSFLOW_JPEGD_SUBSEQ_BITS
+JPEGD_BATCH_MAX = 32  # HSFLOW_JPEGD_BATCH_MAX
 FRAME_FORMATS = {"gray": FRAMES_GRAY8, "gray_blur": FRAMES_GRAY8_BLUR, "bgr": FRAMES_BGR8, "bgr_blur": FRAMES_BGR8_BLUR}
 
 
@@ -149,6 +150,10 @@ PROTOTYPES = {
     "hsflow_jpeg_decode": (_i, [_vp, _vp, _sz, _i, _vp, _sz]),
     "hsflow_set_frames_jpeg": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _i]),
     "hsflow_push_frame_jpeg": (_i, [_vp, _i, _vp, _sz, _i, _i]),
+    "hsflow_jpeg_decode_batch_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "hsflow_set_sequence_jpeg": (_i, [_vp, _i, _vp, _vp, _i, _i]),
+    "hsflow_set_frames_jpeg_async": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _i]),
+    "hsflow_jpeg_async_status": (_i, [_vp]),
     "hsflow_render_line_pixels": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i]),
     "hsflow_compare_planes_host": (_i, [_vp, _sz, _vp, _sz, _i, _i, _dp]),
     "hsflow_compare_flow_device": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _dp, _dp]),
@@ -173,6 +178,7 @@ PROTOTYPES = {
     "hsflow_pipeline_submit_ex": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _pp, ctypes.POINTER(ctypes.c_uint64)]),
     "hsflow_pipeline_submit_device": (_i, [_vp, _vp, _sz, _vp, _sz, _pp, ctypes.POINTER(ctypes.c_uint64)]),
     "hsflow_pipeline_submit_device_ex": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _pp, ctypes.POINTER(ctypes.c_uint64)]),
+    "hsflow_pipeline_submit_jpeg": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _pp, ctypes.POINTER(ctypes.c_uint64)]),
     "hsflow_pipeline_flow_device": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
     "hsflow_pipeline_wait": (_i, [_vp, ctypes.c_uint64]),
     "hsflow_pipeline_render": (_i, [_vp, ctypes.c_uint64, _rp, _vp, _sz]),

@@ -257,6 +257,19 @@ struct hsflow_ctx {
     std::map<GraphKey, GraphEntry> graphs;
     std::vector<PlanEntry> plan_cache; // prepare_solve's results by parameters; cleared when what they rest on changes
     std::vector<hipEvent_t> events;
+    // a batch of JPEG files (hs_jpegd.hip.h, hs_jpegd_batch_plan.h), allocated by the first batch call and kept: one
+    // allocation for a chunk's files; hsflow_set_sequence_jpeg's status words (the first 256-byte multiple) and pictures on
+    // the device, its status words in page-locked memory.  (Behind everything else: the solver's fields lie where they lay.)
+    struct JpegdBatchScratch {
+        void *batch_base = nullptr;
+        size_t batch_bytes = 0;
+        uint8_t *seq = nullptr;
+        size_t seq_bytes = 0;
+        uint32_t *hSeq = nullptr;
+        int hSeq_words = 0;
+        bool pair_status_owed = false; // hsflow_set_frames_jpeg_async's two words are on their way into jpegd.hStatus[2 .. 3],
+        hipEvent_t evPair = nullptr;   // this event behind their copy; hsflow_jpeg_async_status has not asked yet
+    } jpegd_batch;
 };
 
 namespace {

@@ -165,8 +165,9 @@ __device__ __forceinline__ long long jpeg_chunks_used(uint64_t raw_bits, long lo
     return used < (uint64_t)nchunks ? (long long)used : nchunks;
 }
 
-__global__ __launch_bounds__(kJpegScanLanes) void k_jpeg_scan(const uint32_t *__restrict__ in, uint64_t *__restrict__ out, long long n,
-                                                             const uint64_t *__restrict__ raw_bits)
+// (the body: k_jpeg_scan's and, one workgroup per file, k_jpegd_scan_batch's in hs_kernels_jpegd.hip.h)
+__device__ __forceinline__ void jpeg_scan_body(const uint32_t *__restrict__ in, uint64_t *__restrict__ out, long long n,
+                                               const uint64_t *__restrict__ raw_bits)
 {
     __shared__ uint32_t sWave[16], sExcl[17];
     if (raw_bits) n = jpeg_chunks_used(*raw_bits, n);
@@ -201,6 +202,12 @@ __global__ __launch_bounds__(kJpegScanLanes) void k_jpeg_scan(const uint32_t *__
         __syncthreads(); // sWave and sExcl are free again
     }
     if (t == 0) out[n] = carry;
+}
+
+__global__ __launch_bounds__(kJpegScanLanes) void k_jpeg_scan(const uint32_t *__restrict__ in, uint64_t *__restrict__ out, long long n,
+                                                             const uint64_t *__restrict__ raw_bits)
+{
+    jpeg_scan_body(in, out, n, raw_bits);
 }
 
 // A block's bits into the raw stream from bit `pos` on.  Stream bit i is bit 7 - i % 8 of byte i / 8; a word is

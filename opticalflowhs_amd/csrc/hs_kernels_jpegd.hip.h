@@ -25,6 +25,9 @@
 //                    row pass, + 128, clamp, 8 bytes per lane into the component planes padded to whole MCUs
 //   k_jpegd_pixels   one lane per four pixels: upsample, convert, three words (or twelve bytes) out
 // Huffman look-ups: the file's tables in look-up form (5.9 KB) are copied into LDS by every kernel that decodes symbols.
+// Every kernel's work for one file is a __device__ body; the __global__ entries above hand it their by-value arguments,
+// the *_batch entries at the end of this file a record read from device memory, the file picked by the grid's y or z:
+// n files by one set of launches (hsflow_jpeg_decode_batch_device), each workgroup with its own file's tables in LDS.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -69,9 +72,9 @@ __device__ __forceinline__ uint32_t jpegd_end_bits(const JpegdArgs &a) { return 
 
 // MODE 0: count what a chunk drops and the markers in it.  MODE 1: write its kept bytes and its intervals' starts.
 template <int MODE>
-__global__ __launch_bounds__(256) void k_jpegd_clean(JpegdArgs a)
+__device__ __forceinline__ void jpegd_clean_body(const JpegdArgs &a, const uint32_t bx)
 {
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t c = bx * 256u + threadIdx.x;
     if (c >= a.nchunks) return;
     const uint32_t i0 = c * (uint32_t)hsjpegd::kChunk;
     const uint8_t *scan = a.scan;
@@ -90,15 +93,21 @@ __global__ __launch_bounds__(256) void k_jpegd_clean(JpegdArgs a)
     if (MODE == 0) { a.cntRem[c] = dropped; a.cntRst[c] = markers; }
 }
 
+template <int MODE>
+__global__ __launch_bounds__(256) void k_jpegd_clean(JpegdArgs a)
+{
+    jpegd_clean_body<MODE>(a, blockIdx.x);
+}
+
 // Grid: nsubCap / 256 workgroups of 256.
-__global__ __launch_bounds__(kJpegdGroup) void k_jpegd_sync(JpegdArgs a)
+__device__ __forceinline__ void jpegd_sync_body(const JpegdArgs &a, const uint32_t bx)
 {
     __shared__ hsjpegd::Tables sTab;
     __shared__ uint64_t sExit[kJpegdGroup];
     jpegd_tables_to_lds(&sTab, a.tab);
     const uint32_t end = jpegd_end_bits(a), nsub = (end + a.S - 1u) / a.S;
     const int t = threadIdx.x;
-    const uint32_t i = blockIdx.x * (uint32_t)kJpegdGroup + t;
+    const uint32_t i = bx * (uint32_t)kJpegdGroup + t;
     const bool active = i < nsub;
     uint64_t st0 = hsjpegd::pack(hsjpegd::State{i * a.S, 0, 0}), ex = 0;
     uint32_t nb = 0;
@@ -125,8 +134,13 @@ __global__ __launch_bounds__(kJpegdGroup) void k_jpegd_sync(JpegdArgs a)
     a.cnt[i] = active ? nb : 0u;
 }
 
+__global__ __launch_bounds__(kJpegdGroup) void k_jpegd_sync(JpegdArgs a)
+{
+    jpegd_sync_body(a, blockIdx.x);
+}
+
 // Grid: ONE workgroup of kJpegdRepairLanes.
-__global__ __launch_bounds__(kJpegdRepairLanes) void k_jpegd_repair(JpegdArgs a)
+__device__ __forceinline__ void jpegd_repair_body(const JpegdArgs &a)
 {
     __shared__ hsjpegd::Tables sTab;
     jpegd_tables_to_lds(&sTab, a.tab);
@@ -152,13 +166,18 @@ __global__ __launch_bounds__(kJpegdRepairLanes) void k_jpegd_repair(JpegdArgs a)
     }
 }
 
+__global__ __launch_bounds__(kJpegdRepairLanes) void k_jpegd_repair(JpegdArgs a)
+{
+    jpegd_repair_body(a);
+}
+
 // Grid: nsubCap / 256 workgroups of 256.
-__global__ __launch_bounds__(256) void k_jpegd_write(JpegdArgs a)
+__device__ __forceinline__ void jpegd_write_body(const JpegdArgs &a, const uint32_t bx)
 {
     __shared__ hsjpegd::Tables sTab;
     jpegd_tables_to_lds(&sTab, a.tab);
     const uint32_t end = jpegd_end_bits(a), nsub = (end + a.S - 1u) / a.S;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t i = bx * 256u + threadIdx.x;
     if (i == 0 && nsub == 0) atomicMax(a.status, (uint32_t)hsjpegd::kStatusTruncated);
     if (i >= nsub) return;
     hsjpegd::State s = hsjpegd::unpack(a.start[i]);
@@ -168,12 +187,17 @@ __global__ __launch_bounds__(256) void k_jpegd_write(JpegdArgs a)
     if (st) atomicMax(a.status, (uint32_t)st);
 }
 
+__global__ __launch_bounds__(256) void k_jpegd_write(JpegdArgs a)
+{
+    jpegd_write_body(a, blockIdx.x);
+}
+
 // Grid: ceil(nint / 256) workgroups of 256.  (hsjpegd::entropy_host's loop body, one interval per lane.)
-__global__ __launch_bounds__(256) void k_jpegd_write_rst(JpegdArgs a)
+__device__ __forceinline__ void jpegd_write_rst_body(const JpegdArgs &a, const uint32_t bx)
 {
     __shared__ hsjpegd::Tables sTab;
     jpegd_tables_to_lds(&sTab, a.tab);
-    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t j = bx * 256u + threadIdx.x;
     if (j >= a.nint) return;
     const uint32_t end = jpegd_end_bits(a), nrst = (uint32_t)a.rstOff[a.nchunks];
     int st = 0;
@@ -188,6 +212,11 @@ __global__ __launch_bounds__(256) void k_jpegd_write_rst(JpegdArgs a)
         if (sink.block < b1) st = hsjpegd::kStatusTruncated;
     }
     if (st) atomicMax(a.status, (uint32_t)st);
+}
+
+__global__ __launch_bounds__(256) void k_jpegd_write_rst(JpegdArgs a)
+{
+    jpegd_write_rst_body(a, blockIdx.x);
 }
 
 // Block j of the component-after-component order: its component, MCU, place in the MCU and stream block.
@@ -205,19 +234,24 @@ __device__ __forceinline__ JpegdBlockAt jpegd_block_at(const hsjpegd::Frame &f, 
     return r;
 }
 
-__global__ __launch_bounds__(256) void k_jpegd_dc_gather(JpegdArgs a)
+__device__ __forceinline__ void jpegd_dc_gather_body(const JpegdArgs &a, const uint32_t bx)
 {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t j = (int64_t)bx * 256 + threadIdx.x;
     if (j >= a.f.nblocks) return;
     a.diff[j] = (uint32_t)(int32_t)a.coef[jpegd_block_at(a.f, j).B * 64];
 }
 
+__global__ __launch_bounds__(256) void k_jpegd_dc_gather(JpegdArgs a)
+{
+    jpegd_dc_gather_body(a, blockIdx.x);
+}
+
 // Grid: ceil(nblocks / 32) workgroups of 256: eight lanes per block.
-__global__ __launch_bounds__(256) void k_jpegd_blocks(JpegdArgs a)
+__device__ __forceinline__ void jpegd_blocks_body(const JpegdArgs &a, const uint32_t wg)
 {
     __shared__ int32_t sT[32][72];
     const int t = threadIdx.x, lb = t >> 3, r = t & 7;
-    const int64_t j = (int64_t)blockIdx.x * 32 + lb;
+    const int64_t j = (int64_t)wg * 32 + lb;
     const bool live = j < a.f.nblocks;
     JpegdBlockAt at{};
     int32_t d[8];
@@ -255,9 +289,14 @@ __global__ __launch_bounds__(256) void k_jpegd_blocks(JpegdArgs a)
     if (bad) atomicMax(a.status, (uint32_t)hsjpegd::kStatusCorrupt);
 }
 
+__global__ __launch_bounds__(256) void k_jpegd_blocks(JpegdArgs a)
+{
+    jpegd_blocks_body(a, blockIdx.x);
+}
+
 // pix: W x H pixels of 3 bytes, rows `stride` apart; rgb != 0: R first, else B first.  wide != 0: pix and stride are
 // multiples of 4.  Grid: (ceil(W / 256), ceil(H / 4)), block (64, 4).
-__global__ __launch_bounds__(256) void k_jpegd_pixels(JpegdArgs a, uint8_t *__restrict__ pix, long long stride, int rgb, int wide)
+__device__ __forceinline__ void jpegd_pixels_body(const JpegdArgs &a, uint8_t *__restrict__ pix, long long stride, int rgb, int wide)
 {
     const int x0 = 4 * (int)(blockIdx.x * 64 + threadIdx.x), y = (int)(blockIdx.y * 4 + threadIdx.y);
     if (x0 >= a.f.W || y >= a.f.H) return;
@@ -285,6 +324,97 @@ __global__ __launch_bounds__(256) void k_jpegd_pixels(JpegdArgs a, uint8_t *__re
         for (int i = 0; i < 12; i++)
             if (x0 + i / 3 < a.f.W) o[i] = (uint8_t)v[i];
     }
+}
+
+__global__ __launch_bounds__(256) void k_jpegd_pixels(JpegdArgs a, uint8_t *__restrict__ pix, long long stride, int rgb, int wide)
+{
+    jpegd_pixels_body(a, pix, stride, rgb, wide);
+}
+
+// ---- a batch of files by the same launches ---------------------------------------------------------------------------
+// One record per file in device memory; the file is the grid's y (pixels: z).  Every grid is sized for the batch's
+// largest file: a workgroup beyond its own file's extent, or of a file that takes the other route between clean and
+// dc_gather (restart intervals or not), reads its record and returns -- before any LDS, barrier or store.  The bodies
+// are the single-file kernels' own, so a file's pixels are theirs whatever lies beside it.
+struct JpegdBatchRec {
+    JpegdArgs a;
+    uint8_t *pix;      // where k_jpegd_pixels_batch puts this file's picture
+    long long stride;
+    int32_t rgb, wide;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_jpegd_clean_batch(const JpegdBatchRec *__restrict__ recs)
+{
+    const JpegdArgs a = recs[blockIdx.y].a;
+    if (blockIdx.x * 256u >= a.nchunks) return;
+    jpegd_clean_body<MODE>(a, blockIdx.x);
+}
+
+// Grid: (files, WHICH == 0 ? 2 : 1) workgroups of kJpegScanLanes.  WHICH 0: cntRem -> remOff (y = 0) and cntRst -> rstOff
+// (y = 1); 2: cnt -> base, files without restart intervals; 3: diff -> dcsum.
+template <int WHICH>
+__global__ __launch_bounds__(kJpegScanLanes) void k_jpegd_scan_batch(const JpegdBatchRec *__restrict__ recs)
+{
+    const JpegdArgs a = recs[blockIdx.x].a;
+    const uint32_t *in;
+    uint64_t *out;
+    long long n;
+    if (WHICH == 0) { in = blockIdx.y ? a.cntRst : a.cntRem; out = blockIdx.y ? a.rstOff : a.remOff; n = a.nchunks; }
+    else if (WHICH == 2) { if (a.f.ri) return; in = a.cnt; out = a.base; n = a.nsubCap; }
+    else { in = a.diff; out = a.dcsum; n = a.f.nblocks; }
+    jpeg_scan_body(in, out, n, nullptr);
+}
+
+__global__ __launch_bounds__(kJpegdGroup) void k_jpegd_sync_batch(const JpegdBatchRec *__restrict__ recs)
+{
+    const JpegdArgs a = recs[blockIdx.y].a;
+    if (a.f.ri || blockIdx.x * (uint32_t)kJpegdGroup >= a.nsubCap) return;
+    jpegd_sync_body(a, blockIdx.x);
+}
+
+// Grid: one workgroup of kJpegdRepairLanes per file.
+__global__ __launch_bounds__(kJpegdRepairLanes) void k_jpegd_repair_batch(const JpegdBatchRec *__restrict__ recs)
+{
+    const JpegdArgs a = recs[blockIdx.x].a;
+    if (a.f.ri) return;
+    jpegd_repair_body(a);
+}
+
+__global__ __launch_bounds__(256) void k_jpegd_write_batch(const JpegdBatchRec *__restrict__ recs)
+{
+    const JpegdArgs a = recs[blockIdx.y].a;
+    if (a.f.ri || blockIdx.x * 256u >= a.nsubCap) return;
+    jpegd_write_body(a, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void k_jpegd_write_rst_batch(const JpegdBatchRec *__restrict__ recs)
+{
+    const JpegdArgs a = recs[blockIdx.y].a;
+    if (!a.f.ri || blockIdx.x * 256u >= a.nint) return;
+    jpegd_write_rst_body(a, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void k_jpegd_dc_gather_batch(const JpegdBatchRec *__restrict__ recs)
+{
+    const JpegdArgs a = recs[blockIdx.y].a;
+    if ((int64_t)blockIdx.x * 256 >= a.f.nblocks) return;
+    jpegd_dc_gather_body(a, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void k_jpegd_blocks_batch(const JpegdBatchRec *__restrict__ recs)
+{
+    const JpegdArgs a = recs[blockIdx.y].a;
+    if ((int64_t)blockIdx.x * 32 >= a.f.nblocks) return;
+    jpegd_blocks_body(a, blockIdx.x);
+}
+
+// Grid: (ceil(W / 256), ceil(H / 4), files), block (64, 4).
+__global__ __launch_bounds__(256) void k_jpegd_pixels_batch(const JpegdBatchRec *__restrict__ recs)
+{
+    const JpegdBatchRec r = recs[blockIdx.z];
+    if ((int)(blockIdx.x * 256u) >= r.a.f.W || (int)(blockIdx.y * 4u) >= r.a.f.H) return;
+    jpegd_pixels_body(r.a, r.pix, r.stride, r.rgb, r.wide);
 }
 
 } // namespace hsk

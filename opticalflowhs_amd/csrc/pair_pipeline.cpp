@@ -27,6 +27,8 @@ struct hsflow_pipeline {
         uint64_t done_ticket = 0;
         hipStream_t stream = nullptr;     // the lane this slot works on (shared with the slots k +- lanes)
         hipEvent_t ev = nullptr;          // behind everything the running job enqueued: what finish_slot waits for
+        bool jpeg = false;                // the running job's frames are decoded files: their status words are owed
+        bool data_bad = false;            // the last job that finished here had a bad bit stream: its ticket answers HSFLOW_E_DATA
     };
     std::vector<Slot> slots;
     std::vector<hipStream_t> lanes;
@@ -85,6 +87,7 @@ int finish_slot(hsflow_pipeline *pl, hsflow_pipeline::Slot &s)
 {
     if (!s.busy) return HSFLOW_OK;
     s.busy = false; // also on failure: the job is over either way
+    s.data_bad = false;
     // Only THIS job is waited for -- the event behind what it enqueued -- not the jobs other slots have queued on the same
     // lane since; hsflow_wait_solve then settles the early-stop check of an ITER|EPS solve (its witness words were reduced
     // in-stream, before the event).
@@ -103,6 +106,12 @@ int finish_slot(hsflow_pipeline *pl, hsflow_pipeline::Slot &s)
     info.struct_size = sizeof(info);
     // (without last_eps: an asynchronous ITER|EPS solve measures it only on demand -- hsflow_pipeline_info)
     if ((st = hsflow_get_info_ex(s.ctx, &info, 0))) return ctx_fail(pl, s.ctx, st, "hsflow_get_info_ex");
+    if (s.jpeg && (st = hsflow_jpeg_async_status(s.ctx))) { // what only the bit streams showed (copied out ahead of the solve)
+        if (st != HSFLOW_E_DATA) return ctx_fail(pl, s.ctx, st, "hsflow_jpeg_async_status");
+        s.data_bad = true;
+        s.done = info; s.has_done = true; s.done_ticket = s.ticket;
+        return ctx_fail(pl, s.ctx, st, "hsflow_pipeline_submit_jpeg");
+    }
     if (info.eps_rerun && s.u) { // the solve was repeated exactly: what the queued download copied is stale
         if ((st = hsflow_get_flow(s.ctx, 0, s.u, s.us, s.v, s.vs))) return ctx_fail(pl, s.ctx, st, "hsflow_get_flow");
     }                            // (a device-resident job keeps its flow in the slot: nothing to copy again)
@@ -127,7 +136,7 @@ int open_job(hsflow_pipeline *pl, int format, const hsflow_params *params, bool 
     if (!flow_given) return pfail(pl, HSFLOW_E_ARG, "null flow pointer");
     j.s = &pl->slots[pl->next % pl->slots.size()];
     const int st = finish_slot(pl, *j.s);
-    if (st) return st;
+    if (st && !j.s->data_bad) return st; // (a bad file is its own ticket's error, not the next pair's)
     j.use = params; // (a struct of another size is not copied: hsflow_solve_async refuses it)
     if (params->struct_size == sizeof(hsflow_params)) { j.shaped = stream_shape(pl, *params); j.use = &j.shaped; }
     return HSFLOW_OK;
@@ -138,6 +147,7 @@ int close_job(hsflow_pipeline *pl, Job &j, float *u, size_t us, float *v, size_t
     j.s->busy = true;
     j.s->ticket = pl->next;
     j.s->u = u; j.s->v = v; j.s->us = us; j.s->vs = vs;
+    j.s->jpeg = false;
     if (ticket) *ticket = pl->next;
     pl->next++;
     return HSFLOW_OK;
@@ -283,6 +293,23 @@ int hsflow_pipeline_submit_device_ex(hsflow_pipeline *pl, int format, const void
     return close_job(pl, j, nullptr, 0, nullptr, 0, ticket);
 }
 
+int hsflow_pipeline_submit_jpeg(hsflow_pipeline *pl, const uint8_t *prev, size_t prev_bytes, const uint8_t *curr, size_t curr_bytes, int blur3x3,
+                                const hsflow_params *params, uint64_t *ticket)
+{
+    Job j;
+    int st = open_job(pl, blur3x3 ? HSFLOW_FRAMES_BGR8_BLUR : HSFLOW_FRAMES_BGR8, params, true, j);
+    if (st) return st;
+    // nothing is enqueued unless both headers are good, so the slot stays free on an error
+    if ((st = hsflow_set_frames_jpeg_async(j.s->ctx, 0, prev, prev_bytes, curr, curr_bytes, blur3x3))) return ctx_fail(pl, j.s->ctx, st, "hsflow_set_frames_jpeg_async");
+    if ((st = hsflow_solve_async(j.s->ctx, j.use))) {
+        hsflow_synchronize(j.s->ctx);
+        return ctx_fail(pl, j.s->ctx, st, "hsflow_solve_async");
+    }
+    st = close_job(pl, j, nullptr, 0, nullptr, 0, ticket);
+    j.s->jpeg = true;
+    return st;
+}
+
 int hsflow_pipeline_flow_device(hsflow_pipeline *pl, uint64_t ticket, const float **du, const float **dv, size_t *stride_bytes)
 {
     if (!pl) return HSFLOW_E_ARG;
@@ -371,7 +398,10 @@ int hsflow_pipeline_wait(hsflow_pipeline *pl, uint64_t ticket)
     if (ticket >= pl->next) return pfail(pl, HSFLOW_E_ARG, "ticket was never issued");
     hsflow_pipeline::Slot &s = pl->slots[ticket % pl->slots.size()];
     // a later job on the same slot means this one was already waited for inside submit()
-    if (!s.busy || s.ticket != ticket) return HSFLOW_OK;
+    if (!s.busy || s.ticket != ticket) {
+        if (!s.busy && s.has_done && s.done_ticket == ticket && s.data_bad) return pfail(pl, HSFLOW_E_DATA, "hsflow_pipeline_submit_jpeg: that pair's entropy-coded data was corrupt or truncated");
+        return HSFLOW_OK;
+    }
     return finish_slot(pl, s);
 }
 

@@ -114,6 +114,21 @@ class PairPipeline(object):
         self._held[t.value] = (prev, curr)
         return t.value
 
+    def submit_jpeg(self, prev, curr, blur=True, params=None, **kw):
+        """A pair of baseline JPEG files (`bytes`) of the pipeline's size: both decoded as a batch of two on the slot's
+        stream, cvCvtColor (+ cvSmooth with blur=True) and the solve behind them (`hsflow_pipeline_submit_jpeg`); the flow
+        stays in the slot (`flow_device`, `render_jpeg`).  Returns the ticket.  What the headers show raises at once
+        (no ticket); corrupt or truncated entropy-coded data raise E_DATA when the ticket is waited for."""
+        a, b = np.frombuffer(prev, np.uint8), np.frombuffer(curr, np.uint8)
+        if params is None:
+            kw.setdefault("term_type", TERM_ITER)
+            params = make_params(**kw)
+        t = ctypes.c_uint64()
+        self._check(self._lib.hsflow_pipeline_submit_jpeg(self._h, ctypes.c_void_p(a.ctypes.data), a.size, ctypes.c_void_p(b.ctypes.data), b.size,
+                                                          1 if blur else 0, ctypes.byref(params), ctypes.byref(t)))
+        self._held.pop(t.value - self.depth, None)
+        return t.value
+
     def flow_device(self, ticket, copy=True):
         """wait(ticket) + that pair's flow as two CUDA tensors of shape (height, width).  copy=False: views of the slot's
         own planes (row stride = the context's pitch), valid until `depth` more pairs have been submitted."""

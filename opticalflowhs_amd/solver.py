@@ -344,6 +344,32 @@ class HSFlow(object):
         self._check(self._lib.hsflow_jpeg_decode(self._h, _ptr(buf), buf.size, _jpeg_order(order), _ptr(img), img.strides[0]))
         return img
 
+    def jpeg_decode_batch(self, files, order="rgb", out=None):
+        """The pictures of n baseline JPEG files (`bytes`) of the context's size, decoded on the device by one set of
+        launches per `JPEGD_BATCH_MAX` files (`hsflow_jpeg_decode_batch_device`): a CUDA uint8 tensor (n, H, W, 3) -- `out`
+        (packed pixels, any row stride) or a new one -- and the list of the files' status words (0 ok, 1 corrupt,
+        2 truncated: that picture is then undefined, the others are not affected).  Complete on return."""
+        import torch
+        n = len(files)
+        if out is None:
+            out = torch.empty((n, self.height, self.width, 3), dtype=torch.uint8, device="cuda:%d" % self.device)
+        if not _is_device_tensor(out) or out.dim() != 4 or tuple(out.shape) != (n, self.height, self.width, 3) or out.stride(3) != 1 or out.stride(2) != 3:
+            raise ValueError("out must be a CUDA uint8 tensor of shape (n, height, width, 3) with packed pixels")
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=out.device)
+        ptrs, sizes, keep = _file_lists(files)
+        pix = (ctypes.c_void_p * max(n, 1))(*[out.data_ptr() + i * out.stride(0) for i in range(n)])
+        torch.cuda.current_stream(out.device).synchronize()
+        self._check(self._lib.hsflow_jpeg_decode_batch_device(self._h, ptrs, sizes, n, _jpeg_order(order), pix, out.stride(1), _ptr(status)))
+        torch.cuda.synchronize(out.device)  # (not `synchronize`: a decode touches no solver state, an owed check stays owed)
+        return out, [int(v) for v in status[:n].cpu().tolist()]
+
+    def set_sequence_jpeg(self, files, blur=True, first_pair=0):
+        """len(files) >= 2 consecutive frames as baseline JPEG files (`bytes`) into the pairs first_pair .. first_pair +
+        len(files) - 2, pair k = (file k, file k + 1): every file decoded once, as one batch, then `set_frames_jpeg`'s
+        pre-processing per pair (`hsflow_set_sequence_jpeg`).  All or nothing: on an error no pair's frames change."""
+        ptrs, sizes, keep = _file_lists(files)
+        self._check(self._lib.hsflow_set_sequence_jpeg(self._h, int(first_pair), ptrs, sizes, len(files), 1 if blur else 0))
+
     def set_frames_jpeg(self, prev, curr, blur=True, pair=0):
         """Both frames as baseline JPEG files (`bytes`): decoded on the device, then cvCvtColor (+ cvSmooth with
         blur=True) there (`hsflow_set_frames_jpeg`) -- only the files' entropy-coded bytes cross to the device."""
@@ -454,6 +480,15 @@ def encode_jpeg(rgb, quality=95):
     if st:
         raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
     return buf[:n.value].tobytes()
+
+
+def _file_lists(files):
+    """(pointer array, size array, what keeps them alive) for a list of `bytes`-like files."""
+    bufs = [np.frombuffer(f, np.uint8) for f in files]
+    n = max(len(bufs), 1)
+    ptrs = (ctypes.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    sizes = (ctypes.c_size_t * n)(*[b.size for b in bufs])
+    return ptrs, sizes, bufs
 
 
 def _jpeg_order(order):
