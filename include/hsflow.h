@@ -32,6 +32,10 @@
  *                                          flow where it lies -- no read-back
  *   hsflow_render_flow_jpeg[_device] .... cvSaveImage(output, imgFlow) behind it (OpticalFlowOpenCV.cpp:47,
  *                                          HSOpticalFlowOpenCL.cpp:771): the picture's JPEG file, encoded on the device
+ *   hsflow_render_flow_batch_device, hsflow_jpeg_encode_batch_device, hsflow_render_flow_jpeg_batch[_device]
+ *                                          the same drawing and cvSaveImage (OpticalFlowOpenCV.cpp:32-47,
+ *                                          HSOpticalFlowOpenCL.cpp:759-771) for every pair of a context at once: one set
+ *                                          of launches per batch, N files out without a round trip per pair
  *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
  *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
  *                                          the pictures are decoded on the device
@@ -63,7 +67,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 12 /* 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 13 /* 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -531,6 +535,63 @@ int hsflow_render_flow_jpeg_device(hsflow_ctx *ctx, int pair, const hsflow_rende
  * hsflow_jpeg_bound) bytes, allocated on demand) and a page-locked size word until hsflow_destroy. */
 int hsflow_render_flow_jpeg(hsflow_ctx *ctx, int pair, const hsflow_render_params *rp, int quality,
                             uint8_t *jpeg, size_t capacity, size_t *bytes);
+
+/* A BATCH of pictures (ABI 0.13): what the reference does once per run at the end of runFromImg -- the drawing and
+ * cvSaveImage (OpticalFlowOpenCV.cpp:32-47, HSOpticalFlowOpenCL.cpp:759-771) -- for n pictures of the context's size by
+ * ONE set of launches: every kernel of the single forms takes the picture from a further grid dimension and runs the same
+ * body (csrc/hs_kernels_render.hip.h, csrc/hs_kernels_jpeg.hip.h), what differs from picture to picture goes to the
+ * kernels by value, and picture i's scratch is slice i of one allocation (csrc/hs_jpeg_batch_plan.h).  A batch larger
+ * than HSFLOW_JPEG_BATCH_MAX runs in consecutive chunks of at most that many on the stream: per chunk one memset for the
+ * raw streams, at most one for the priority planes, two render launches and seven encode launches, whatever n is.
+ * Picture i's file is byte for byte that of hsflow_jpeg_encode_device / hsflow_render_flow_jpeg for the same picture or
+ * pair, whatever its position, its neighbours, n, the chunking or HSFLOW_JPEG_BATCH_MAX; nothing at or beyond
+ * d_jpeg[i] + capacity is written, and a picture whose file does not fit changes nothing for its neighbours.
+ * Memory: the batched scratch is separate from the single encode's, so single and batched calls can be enqueued back to
+ * back in any order without synchronisation.  It is allocated on demand for as many pictures as the largest chunk so
+ * far (grown behind a wait for the stream), kept until hsflow_destroy, and does not count for HSFLOW_KERNEL_PERSIST's
+ * "only one alive" rule; contexts that never batch pay nothing.  Per 1080p picture of a chunk: about 18 MB of scratch;
+ * for the render forms a priority plane (8.3 MB); for the render-and-encode forms the picture (6.2 MB); for the
+ * synchronous form the output slot (min(capacity, hsflow_jpeg_bound) bytes) -- so HSFLOW_JPEG_BATCH_MAX times that at most.
+ * Every argument is checked before anything is enqueued or allocated; on an error nothing is written and
+ * hsflow_last_error names the entry's index, where there is one. */
+/* 16: the smallest of {4, 8, 16, 32} within 5 % of the best per-file time of one synchronous call at 1080p, n = 32
+ * (profiles/jpeg_batch_time.txt, measured with the constant at 32: 0.0964, 0.0889, 0.0828, 0.0816 ms per file -- "best
+ * 0.0816; the smallest maximum within 5 % of it: 16"; the parent's hsflow_render_flow_jpeg: 0.212).  Small pictures would
+ * take more: at 600x480 a chunk of 32 costs 0.0160 ms per file against 0.0200 with 16 (and 0.143 one by one).  The kernels'
+ * argument blocks hold 32 pictures; to measure a larger candidate build with the constant raised (tools/jpeg_batch_time.py). */
+#define HSFLOW_JPEG_BATCH_MAX 16 /* pictures per set of launches; the environment variable of the same name overrides it per call, 1..HSFLOW_JPEG_BATCH_MAX */
+/* n RGB pictures of the context's size in device memory (rows `stride` bytes apart, any alignment, each its own) -> n
+ * files in device memory, file i into d_jpeg[i][0 .. capacity), its size into d_bytes[i]; only enqueued on ctx's stream
+ * (complete after hsflow_synchronize / a wait for the stream).  The lists are host arrays, free on return.  This form
+ * cannot know a file's size: with capacity below it d_bytes[i] still holds the size needed and the call has returned
+ * HSFLOW_OK, as hsflow_jpeg_encode_device.  Touches no solver state.
+ * HSFLOW_E_ARG: n < 1, a null list or entry, quality outside 1..100, d_bytes null or not 8-byte aligned,
+ * HSFLOW_JPEG_BATCH_MAX in the environment unusable; HSFLOW_E_SIZE: stride < 3*width, a context wider or higher than 65535. */
+int hsflow_jpeg_encode_batch_device(hsflow_ctx *ctx, const void *const *d_rgb, int n, size_t stride, int quality,
+                                    void *const *d_jpeg, size_t capacity, uint64_t *d_bytes /* n device words, 8-byte aligned */);
+/* The pictures of the pairs first_pair .. first_pair + n - 1 into device memory, pair first_pair + i into d_rgb[i]; only
+ * enqueued (two launches per chunk).  Pair i reads its own flow planes and owns a priority plane of its own: the context's
+ * plane grows to one per picture of a chunk.  The ordering rules of hsflow_render_flow_device apply word for word: an
+ * ITER|EPS check that hsflow_solve_async still owes is settled first, the flow is read and never changed, and on a
+ * context with hsflow_set_async_reduce hsflow_wait_solve and hsflow_flow_view_device called after it wait for the
+ * stream.  After a solve with hsflow_set_pair_termination pair i's picture is that of its own final flow.
+ * HSFLOW_E_ARG: n < 1, first_pair < 0 or first_pair + n > n_pairs, a null list or entry, render params as
+ * hsflow_render_flow_device, the environment value unusable; HSFLOW_E_SIZE: stride < 3*width. */
+int hsflow_render_flow_batch_device(hsflow_ctx *ctx, int first_pair, int n, const hsflow_render_params *rp,
+                                    void *const *d_rgb, size_t stride);
+/* hsflow_render_flow_batch_device into pictures the context keeps + hsflow_jpeg_encode_batch_device, behind each other
+ * on the stream; only enqueued.  The ordering rules and argument errors of both. */
+int hsflow_render_flow_jpeg_batch_device(hsflow_ctx *ctx, int first_pair, int n, const hsflow_render_params *rp, int quality,
+                                         void *const *d_jpeg, size_t capacity, uint64_t *d_bytes);
+/* The same into host memory, synchronous: per chunk the size words cross in ONE copy, then each file's bytes, with one
+ * wait each -- two host round trips per chunk where n hsflow_render_flow_jpeg calls take 2 n.  Complete on return; waits
+ * only for what this context enqueued; hsflow_wait_solve's marker speaks for the context again afterwards.
+ * HSFLOW_E_SIZE if any file exceeds capacity: bytes[i] then holds the size needed for EVERY i, a buffer whose file does
+ * not fit is left alone, and buffers whose files fit may have been written.  Keeps per-picture output slots of
+ * min(capacity, hsflow_jpeg_bound) bytes on the device and page-locked size words until hsflow_destroy.
+ * HSFLOW_E_ARG: as the device form, with jpeg / bytes null (bytes needs no alignment). */
+int hsflow_render_flow_jpeg_batch(hsflow_ctx *ctx, int first_pair, int n, const hsflow_render_params *rp, int quality,
+                                  uint8_t *const *jpeg, size_t capacity, size_t *bytes /* n */);
 
 /* --- the input files (cvLoadImage) ---------------------------------------------------------- */
 

@@ -19,6 +19,7 @@ RENDER_CV, RENDER_CL = 0, 1
 JPEG_ORDER_BGR, JPEG_ORDER_RGB = 0, 1
 JPEGD_SUBSEQ_BITS = 1024  # HSFLOW_JPEGD_SUBSEQ_BITS
 JPEGD_BATCH_MAX = 32  # HSFLOW_JPEGD_BATCH_MAX
+JPEG_BATCH_MAX = 16  # HSFLOW_JPEG_BATCH_MAX
 FRAME_FORMATS = {"gray": FRAMES_GRAY8, "gray_blur": FRAMES_GRAY8_BLUR, "bgr": FRAMES_BGR8, "bgr_blur": FRAMES_BGR8_BLUR}
 
 
@@ -144,6 +145,10 @@ PROTOTYPES = {
     "hsflow_jpeg_encode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "hsflow_render_flow_jpeg_device": (_i, [_vp, _i, _rp, _i, _vp, _sz, _vp]),
     "hsflow_render_flow_jpeg": (_i, [_vp, _i, _rp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
+    "hsflow_jpeg_encode_batch_device": (_i, [_vp, _vp, _i, _sz, _i, _vp, _sz, _vp]),
+    "hsflow_render_flow_batch_device": (_i, [_vp, _i, _i, _rp, _vp, _sz]),
+    "hsflow_render_flow_jpeg_batch_device": (_i, [_vp, _i, _i, _rp, _i, _vp, _sz, _vp]),
+    "hsflow_render_flow_jpeg_batch": (_i, [_vp, _i, _i, _rp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
     "hsflow_jpeg_read_header": (_i, [_vp, _sz, _ji]),
     "hsflow_jpeg_decode_host": (_i, [_vp, _sz, _i, _vp, _sz, _ji]),
     "hsflow_jpeg_decode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),

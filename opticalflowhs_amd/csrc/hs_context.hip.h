@@ -270,6 +270,22 @@ struct hsflow_ctx {
         bool pair_status_owed = false; // hsflow_set_frames_jpeg_async's two words are on their way into jpegd.hStatus[2 .. 3],
         hipEvent_t evPair = nullptr;   // this event behind their copy; hsflow_jpeg_async_status has not asked yet
     } jpegd_batch;
+    // a batch of pictures drawn and encoded by one set of launches per chunk (hs_render.hip.h, hs_jpeg.hip.h,
+    // hs_jpeg_batch_plan.h), allocated by the first batched call and kept: dPrio holds prio_planes priority planes (the
+    // single render uses the first); one allocation for the encode scratch of `pictures` slices, separate from the single
+    // encode's; for the render-and-encode forms `rgb_pictures` pictures on the device; for the synchronous form
+    // `out_pictures` output slots of `slot` bytes and the chunk's size words in page-locked memory
+    int prio_planes = 0;
+    struct JpegBatchScratch {
+        void *base = nullptr;
+        int pictures = 0;
+        uint8_t *rgb = nullptr;
+        int rgb_pictures = 0;
+        uint8_t *out = nullptr;
+        size_t slot = 0;
+        int out_pictures = 0;
+        uint64_t *hSize = nullptr;
+    } jpeg_batch;
 };
 
 namespace {

@@ -2,7 +2,12 @@
 // the file the reference's runFromImg ends in (cvSaveImage, OpticalFlowOpenCV.cpp:47, HSOpticalFlowOpenCL.cpp:771) from a
 // picture that never leaves the device.  Seven launches and one memset on the context's stream
 // (hs_kernels_jpeg.hip.h); a context that never encodes allocates and launches nothing here.
+// hsflow_jpeg_encode_batch_device, hsflow_render_flow_jpeg_batch[_device]: many pictures by one memset and one set of
+// launches per chunk of at most HSFLOW_JPEG_BATCH_MAX (what cvSaveImage does once per run, OpticalFlowOpenCV.cpp:32-47,
+// HSOpticalFlowOpenCL.cpp:759-771, for every pair of the context at once), scratch laid out by hs_jpeg_batch_plan.h.
 #pragma once
+
+#include "hs_jpeg_batch_plan.h"
 
 namespace {
 
@@ -13,6 +18,11 @@ void jpeg_release(hsflow_ctx *c)
     hipFree(c->jpeg.out);
     if (c->jpeg.hSize) hipHostFree(c->jpeg.hSize);
     c->jpeg = hsflow_ctx::JpegScratch();
+    hipFree(c->jpeg_batch.base);
+    hipFree(c->jpeg_batch.rgb);
+    hipFree(c->jpeg_batch.out);
+    if (c->jpeg_batch.hSize) hipHostFree(c->jpeg_batch.hSize);
+    c->jpeg_batch = hsflow_ctx::JpegBatchScratch();
 }
 
 int check_jpeg_args(hsflow_ctx *c, int quality, const void *d_jpeg, const void *d_bytes)
@@ -23,7 +33,25 @@ int check_jpeg_args(hsflow_ctx *c, int quality, const void *d_jpeg, const void *
     return HSFLOW_OK;
 }
 
-// The scratch of every encode of this context, one allocation, and the tables of `quality`.
+// The tables and header of `quality` on the device, filled once per quality (the size is the context's): a blocking
+// copy into memory nothing uses yet.
+int jpeg_tables(hsflow_ctx *c, int quality, hsjpeg::Tables **tab)
+{
+    hsflow_ctx::JpegScratch &j = c->jpeg;
+    auto it = j.tables.find(quality);
+    if (it == j.tables.end()) {
+        hsjpeg::Tables host, *dev = nullptr;
+        hsjpeg::build_tables(host, c->W, c->H, quality);
+        HS_HIP(c, hipMalloc((void **)&dev, sizeof(hsjpeg::Tables)));
+        const hipError_t e = hipMemcpy(dev, &host, sizeof(host), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { hipFree(dev); HS_HIP(c, e); }
+        it = j.tables.emplace(quality, dev).first;
+    }
+    *tab = it->second;
+    return HSFLOW_OK;
+}
+
+// The scratch of every single encode of this context, one allocation, and the tables of `quality`.
 int jpeg_prepare(hsflow_ctx *c, int quality, hsjpeg::Tables **tab)
 {
     hsflow_ctx::JpegScratch &j = c->jpeg;
@@ -41,17 +69,7 @@ int jpeg_prepare(hsflow_ctx *c, int quality, hsjpeg::Tables **tab)
         j.len = (uint32_t *)(p + o_len); j.ff = (uint32_t *)(p + o_ff); j.size = (uint64_t *)(p + o_size);
         j.nb = nb; j.nchunks = nchunks; j.raw_bytes = raw_bytes;
     }
-    auto it = j.tables.find(quality);
-    if (it == j.tables.end()) { // filled once per quality (the size is the context's); a blocking copy into memory nothing uses yet
-        hsjpeg::Tables host, *dev = nullptr;
-        hsjpeg::build_tables(host, c->W, c->H, quality);
-        HS_HIP(c, hipMalloc((void **)&dev, sizeof(hsjpeg::Tables)));
-        const hipError_t e = hipMemcpy(dev, &host, sizeof(host), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { hipFree(dev); HS_HIP(c, e); }
-        it = j.tables.emplace(quality, dev).first;
-    }
-    *tab = it->second;
-    return HSFLOW_OK;
+    return jpeg_tables(c, quality, tab);
 }
 
 // All launches of one encode, enqueued on c's stream.  The caller has checked every argument.  d_bytes == nullptr: the
@@ -90,6 +108,126 @@ int render_jpeg_begin(hsflow_ctx *c, int pair, const hsflow_render_params *rp, i
     if ((st = settle_pending(c))) return st;
     if (!c->dRgb) HS_HIP(c, hipMalloc((void **)&c->dRgb, (size_t)c->W * 3 * c->H));
     return HSFLOW_OK;
+}
+
+// ---- a batch of pictures ------------------------------------------------------------------------------------------------
+
+static_assert(hsjpeg_plan::kMaxBlockBytes == (size_t)hsjpeg::kMaxBlockBytes && hsjpeg_plan::kChunkBytes == (size_t)hsk::kJpegChunk,
+              "hs_jpeg_batch_plan.h restates two constants");
+static_assert(sizeof(hsk::JpegBatchPic) == 32, "one picture of a batch is 32 bytes of kernel arguments");
+
+// The batched scratch for a chunk of `pictures`.  Grown behind a wait for the stream: what is in flight still uses the
+// old one.
+int jpeg_batch_reserve(hsflow_ctx *c, int pictures)
+{
+    hsflow_ctx::JpegBatchScratch &b = c->jpeg_batch;
+    if (b.pictures >= pictures) return HSFLOW_OK;
+    HS_HIP(c, hipStreamSynchronize(c->stream));
+    hipFree(b.base);
+    b.base = nullptr; b.pictures = 0;
+    HS_HIP(c, hipMalloc(&b.base, hsjpeg_plan::layout(c->W, c->H, pictures).total));
+    b.pictures = pictures;
+    return HSFLOW_OK;
+}
+
+// The context's own pictures for a chunk of `pictures`: 3*W x H bytes each, 256-byte multiples apart.
+size_t jpeg_batch_rgb_span(const hsflow_ctx *c) { return hsjpeg_plan::up256((size_t)c->W * 3 * c->H); }
+
+int jpeg_batch_reserve_rgb(hsflow_ctx *c, int pictures)
+{
+    hsflow_ctx::JpegBatchScratch &b = c->jpeg_batch;
+    if (b.rgb_pictures >= pictures) return HSFLOW_OK;
+    HS_HIP(c, hipStreamSynchronize(c->stream));
+    hipFree(b.rgb);
+    b.rgb = nullptr; b.rgb_pictures = 0;
+    HS_HIP(c, hipMalloc((void **)&b.rgb, jpeg_batch_rgb_span(c) * (size_t)pictures));
+    b.rgb_pictures = pictures;
+    return HSFLOW_OK;
+}
+
+// The size words of a chunk inside the batched scratch (the synchronous form's; the device forms write the caller's).
+uint64_t *jpeg_batch_size_words(hsflow_ctx *c)
+{
+    return (uint64_t *)((uint8_t *)c->jpeg_batch.base + hsjpeg_plan::layout(c->W, c->H, c->jpeg_batch.pictures).o_size);
+}
+
+// One memset and all launches for a chunk of cnt pictures (cnt <= jpeg_batch.pictures), enqueued on c's stream; picture
+// i's size goes to d_bytes[i].  The caller has checked every argument.
+int enqueue_jpeg_chunk(hsflow_ctx *c, const hsjpeg::Tables *tab, const hsk::JpegBatchPics &pics, int cnt, size_t stride, uint64_t *d_bytes)
+{
+    const hsjpeg_plan::Layout l = hsjpeg_plan::layout(c->W, c->H, c->jpeg_batch.pictures);
+    uint8_t *p = (uint8_t *)c->jpeg_batch.base;
+    const hsk::JpegBatchScratch sc{p + l.o_coef, p + l.o_raw, p + l.o_off, p + l.o_ffoff, p + l.o_len, p + l.o_ff,
+                                   l.s.s_coef, l.s.s_raw, l.s.s_off, l.s.s_ffoff, l.s.s_len, l.s.s_ff};
+    const int MW = hsjpeg::mcus_x(c->W), MH = hsjpeg::mcus_y(c->H);
+    const long long nb = l.s.nb, nchunks = l.s.nchunks;
+    const unsigned gb = (unsigned)((nb + 255) / 256), gc = (unsigned)((nchunks + 255) / 256), np = (unsigned)cnt;
+    HS_HIP(c, hipMemsetAsync(sc.raw, 0, l.s.s_raw * (size_t)cnt, c->stream)); // the chunk's raw streams lie behind each other
+    hipLaunchKernelGGL(hsk::k_jpeg_blocks_batch, dim3((MW + hsk::kJpegStripMcus - 1) / hsk::kJpegStripMcus, MH, np), dim3(256), 0, c->stream, pics,
+                       (long long)stride, c->W, c->H, MW, tab, sc);
+    hipLaunchKernelGGL(hsk::k_jpeg_lengths_batch, dim3(gb, np), dim3(256), 0, c->stream, tab, sc, c->W, c->H, MW, nb);
+    hipLaunchKernelGGL(hsk::k_jpeg_scan_batch, dim3(np), dim3(hsk::kJpegScanLanes), 0, c->stream, sc, nb, nchunks, 0);
+    hipLaunchKernelGGL(hsk::k_jpeg_emit_batch, dim3(gb, np), dim3(256), 0, c->stream, tab, sc, c->W, c->H, MW, nb);
+    hipLaunchKernelGGL(hsk::k_jpeg_count_ff_batch, dim3(gc, np), dim3(256), 0, c->stream, sc, nb, nchunks);
+    hipLaunchKernelGGL(hsk::k_jpeg_scan_batch, dim3(np), dim3(hsk::kJpegScanLanes), 0, c->stream, sc, nb, nchunks, 1);
+    hipLaunchKernelGGL(hsk::k_jpeg_stuff_batch, dim3(gc, np), dim3(256), 0, c->stream, tab, sc, nb, nchunks, pics, d_bytes);
+    HS_HIP(c, hipGetLastError());
+    return HSFLOW_OK;
+}
+
+hsk::JpegBatchPic jpeg_batch_pic(const void *rgb, size_t stride, void *out, size_t capacity)
+{
+    return hsk::JpegBatchPic{(const uint8_t *)rgb, (uint8_t *)out, (unsigned long long)capacity, (((uintptr_t)rgb | stride) & 3u) == 0, 0};
+}
+
+// What the batched encodes check of the file side: quality, the lists, the context's size.
+int check_jpeg_batch_args(hsflow_ctx *c, int n, int quality, const void *const *list, const void *bytes)
+{
+    if (quality < 1 || quality > 100) return fail(c, HSFLOW_E_ARG, "jpeg quality must be 1 .. 100");
+    if (!list || !bytes) return fail(c, HSFLOW_E_ARG, "null jpeg list or size pointer");
+    for (int i = 0; i < n; i++)
+        if (!list[i]) return fail(c, HSFLOW_E_ARG, "picture " + std::to_string(i) + ": null jpeg pointer");
+    if (c->W > 65535 || c->H > 65535) return fail(c, HSFLOW_E_SIZE, "a JPEG picture has at most 65535 columns and rows");
+    return HSFLOW_OK;
+}
+
+// The checks the two batched render-and-encode forms share, then the owed ITER|EPS check settled and everything a chunk
+// needs on the device there.  *maxb: the chunk size of this call.
+int render_jpeg_batch_begin(hsflow_ctx *c, int first_pair, int n, const hsflow_render_params *rp, int quality, const void *const *jpeg, const void *bytes,
+                            bool aligned8, int *maxb, hsjpeg::Tables **tab)
+{
+    int st = check_ctx(c, 0);
+    if (st) return st;
+    if ((st = check_batch_pairs(c, first_pair, n))) return st;
+    if ((st = check_render_params(c, rp))) return st;
+    if ((st = check_jpeg_batch_args(c, n, quality, jpeg, bytes))) return st;
+    if (aligned8 && ((uintptr_t)bytes & 7u)) return fail(c, HSFLOW_E_ARG, "the size words must be 8-byte aligned");
+    if ((st = check_batch_max(c, maxb))) return st;
+    if ((st = settle_pending(c))) return st;
+    const int most = n < *maxb ? n : *maxb;
+    if ((st = jpeg_tables(c, quality, tab))) return st;
+    if ((st = render_batch_reserve(c, most))) return st;
+    if ((st = jpeg_batch_reserve_rgb(c, most))) return st;
+    return jpeg_batch_reserve(c, most);
+}
+
+// The pictures of cnt pairs from first_pair on into the context's own pictures, and their encodes into out[k] /
+// d_bytes[k], behind each other on the stream.
+int enqueue_render_jpeg_chunk(hsflow_ctx *c, int first_pair, int cnt, const hsflow_render_params &rp, const hsjpeg::Tables *tab, uint8_t *const *out,
+                              size_t capacity, uint64_t *d_bytes)
+{
+    const size_t rowb = (size_t)c->W * 3, span = jpeg_batch_rgb_span(c);
+    hsk::RenderBatchPics rpics{};
+    hsk::JpegBatchPics jpics{};
+    for (int k = 0; k < cnt; k++) {
+        uint8_t *pic = c->jpeg_batch.rgb + span * (size_t)k;
+        rpics.rgb[k] = pic;
+        jpics.p[k] = jpeg_batch_pic(pic, rowb, out[k], capacity);
+        if (jpics.p[k].wide) rpics.wide |= 1u << k;
+    }
+    int st = enqueue_render_chunk(c, first_pair, cnt, rp, rpics, rowb);
+    if (st) return st;
+    return enqueue_jpeg_chunk(c, tab, jpics, cnt, rowb, d_bytes);
 }
 
 } // namespace
@@ -161,6 +299,93 @@ int hsflow_render_flow_jpeg(hsflow_ctx *c, int pair, const hsflow_render_params 
     }
     c->last_marked = marked; // nothing of this call is in flight any more: the solve's marker speaks for the context again
     if (size > capacity) return fail(c, HSFLOW_E_SIZE, "capacity smaller than the file (hsflow_jpeg_bound always suffices)");
+    return check_persist(c);
+}
+
+int hsflow_jpeg_encode_batch_device(hsflow_ctx *c, const void *const *d_rgb, int n, size_t stride, int quality, void *const *d_jpeg, size_t capacity,
+                                    uint64_t *d_bytes)
+{
+    int st = check_ctx(c, 0), maxb = 0;
+    if (st) return st;
+    if (n < 1) return fail(c, HSFLOW_E_ARG, "a batch needs at least one picture");
+    if (!d_rgb) return fail(c, HSFLOW_E_ARG, "null picture list");
+    for (int i = 0; i < n; i++)
+        if (!d_rgb[i]) return fail(c, HSFLOW_E_ARG, "picture " + std::to_string(i) + ": null picture pointer");
+    if ((st = check_jpeg_batch_args(c, n, quality, d_jpeg, d_bytes))) return st;
+    if ((uintptr_t)d_bytes & 7u) return fail(c, HSFLOW_E_ARG, "the size words must be 8-byte aligned");
+    if (stride < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
+    if ((st = check_batch_max(c, &maxb))) return st;
+    hsjpeg::Tables *tab = nullptr;
+    if ((st = jpeg_tables(c, quality, &tab))) return st;
+    if ((st = jpeg_batch_reserve(c, n < maxb ? n : maxb))) return st;
+    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb)) {
+        hsk::JpegBatchPics pics{};
+        for (int k = 0; k < ch.count; k++) pics.p[k] = jpeg_batch_pic(d_rgb[ch.first + k], stride, d_jpeg[ch.first + k], capacity);
+        if ((st = enqueue_jpeg_chunk(c, tab, pics, ch.count, stride, d_bytes + ch.first))) return st;
+    }
+    return HSFLOW_OK;
+}
+
+int hsflow_render_flow_jpeg_batch_device(hsflow_ctx *c, int first_pair, int n, const hsflow_render_params *rp, int quality, void *const *d_jpeg,
+                                         size_t capacity, uint64_t *d_bytes)
+{
+    int maxb = 0;
+    hsjpeg::Tables *tab = nullptr;
+    int st = render_jpeg_batch_begin(c, first_pair, n, rp, quality, d_jpeg, d_bytes, true, &maxb, &tab);
+    if (st) return st;
+    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb))
+        if ((st = enqueue_render_jpeg_chunk(c, first_pair + ch.first, ch.count, *rp, tab, (uint8_t *const *)d_jpeg + ch.first, capacity, d_bytes + ch.first)))
+            return st;
+    return HSFLOW_OK;
+}
+
+int hsflow_render_flow_jpeg_batch(hsflow_ctx *c, int first_pair, int n, const hsflow_render_params *rp, int quality, uint8_t *const *jpeg, size_t capacity,
+                                  size_t *bytes)
+{
+    int maxb = 0;
+    hsjpeg::Tables *tab = nullptr;
+    int st = render_jpeg_batch_begin(c, first_pair, n, rp, quality, (const void *const *)jpeg, bytes, false, &maxb, &tab);
+    if (st) return st;
+    hsflow_ctx::JpegBatchScratch &b = c->jpeg_batch;
+    const int most = n < maxb ? n : maxb;
+    const size_t bound = hsjpeg::bound(c->W, c->H), cap = capacity < bound ? capacity : bound, slot = hsjpeg_plan::up256(cap ? cap : 1);
+    if (b.slot < slot || b.out_pictures < most) { // (the synchronous form leaves nothing in flight that writes the old ones)
+        const size_t s = b.slot > slot ? b.slot : slot;
+        const int pictures = b.out_pictures > most ? b.out_pictures : most;
+        hipFree(b.out);
+        b.out = nullptr; b.slot = 0; b.out_pictures = 0;
+        HS_HIP(c, hipMalloc((void **)&b.out, s * (size_t)pictures));
+        b.slot = s; b.out_pictures = pictures;
+    }
+    if (!b.hSize) HS_HIP(c, hipHostMalloc((void **)&b.hSize, sizeof(uint64_t) * hsk::kJpegBatchMax, hipHostMallocDefault));
+    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
+    const bool marked = c->last_marked;
+    bool fits = true;
+    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb)) {
+        uint8_t *out[hsk::kJpegBatchMax];
+        for (int k = 0; k < ch.count; k++) out[k] = b.out + b.slot * (size_t)k;
+        uint64_t *words = jpeg_batch_size_words(c);
+        if ((st = enqueue_render_jpeg_chunk(c, first_pair + ch.first, ch.count, *rp, tab, out, cap, words))) return st;
+        // the chunk's size words in one copy, then each file's bytes: only the files cross, and what THIS context enqueued
+        // is all that is waited for
+        HS_HIP(c, hipMemcpyAsync(b.hSize, words, sizeof(uint64_t) * (size_t)ch.count, hipMemcpyDeviceToHost, c->stream));
+        HS_HIP(c, hipEventRecord(c->evRender, c->stream));
+        HS_HIP(c, hipEventSynchronize(c->evRender));
+        bool any = false;
+        for (int k = 0; k < ch.count; k++) {
+            const uint64_t size = b.hSize[k];
+            bytes[ch.first + k] = (size_t)size;
+            if (size > capacity) { fits = false; continue; }
+            HS_HIP(c, hipMemcpyAsync(jpeg[ch.first + k], out[k], (size_t)size, hipMemcpyDeviceToHost, c->stream));
+            any = true;
+        }
+        if (any) {
+            HS_HIP(c, hipEventRecord(c->evRender, c->stream));
+            HS_HIP(c, hipEventSynchronize(c->evRender));
+        }
+    }
+    c->last_marked = marked; // nothing of this call is in flight any more: the solve's marker speaks for the context again
+    if (!fits) return fail(c, HSFLOW_E_SIZE, "capacity smaller than a file (hsflow_jpeg_bound always suffices)");
     return check_persist(c);
 }
 

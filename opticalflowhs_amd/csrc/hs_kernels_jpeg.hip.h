@@ -13,6 +13,10 @@
 //                    the last block's lane adds the 1-bits up to a whole byte
 //   k_jpeg_count_ff  one lane per 128-byte chunk of the raw stream: its 0xFF bytes
 //   k_jpeg_stuff     header + stuffed bytes + FF D9 + the total; nothing at or beyond `capacity` is written
+// Each kernel's work for one picture is a __device__ body.  The entries above call it with their by-value arguments;
+// the k_jpeg_*_batch entries take the picture from a further grid dimension and call the same body: picture i's scratch
+// is slice i of one allocation (JpegBatchScratch, laid out by hs_jpeg_batch_plan.h), and what differs from picture to
+// picture -- source, `wide`, output, capacity -- comes from an argument block by value (JpegBatchPics).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,6 +29,30 @@ constexpr int kJpegStripMcus = 8;   // MCUs per workgroup of k_jpeg_blocks
 constexpr int kJpegScanLanes = 1024;
 constexpr int kJpegScanPer = 4;     // consecutive entries per lane and tile of k_jpeg_scan
 constexpr int kJpegChunk = 128;     // bytes of raw stream per lane of the two stuffing kernels
+constexpr int kJpegBatchMax = 32;   // pictures per set of launches (HSFLOW_JPEG_BATCH_MAX is at most this)
+
+// One picture of a batch: 32 bytes.
+struct JpegBatchPic {
+    const uint8_t *rgb;          // the picture, rows `stride` bytes apart
+    uint8_t *out;                // its file
+    unsigned long long capacity; // bytes of `out`
+    int wide, pad;               // rgb and the stride are multiples of 4
+};
+struct JpegBatchPics {
+    JpegBatchPic p[kJpegBatchMax];
+};
+
+// The scratch of a chunk: the ranges' first slices and the bytes from one picture's slice to the next one's.
+struct JpegBatchScratch {
+    uint8_t *coef, *raw, *off, *ffoff, *len, *ff;
+    unsigned long long s_coef, s_raw, s_off, s_ffoff, s_len, s_ff;
+    __device__ __forceinline__ int16_t *coef_of(unsigned i) const { return (int16_t *)(coef + i * s_coef); }
+    __device__ __forceinline__ uint32_t *raw_of(unsigned i) const { return (uint32_t *)(raw + i * s_raw); }
+    __device__ __forceinline__ uint64_t *off_of(unsigned i) const { return (uint64_t *)(off + i * s_off); }
+    __device__ __forceinline__ uint64_t *ffoff_of(unsigned i) const { return (uint64_t *)(ffoff + i * s_ffoff); }
+    __device__ __forceinline__ uint32_t *len_of(unsigned i) const { return (uint32_t *)(len + i * s_len); }
+    __device__ __forceinline__ uint32_t *ff_of(unsigned i) const { return (uint32_t *)(ff + i * s_ff); }
+};
 
 // Four pixels x .. x + 3 of row `row` (already clamped to the picture); columns clamped to the picture.  wide: the row's
 // base and 3 * x are multiples of 4 and x + 4 <= W -- three aligned words.
@@ -48,8 +76,8 @@ __device__ __forceinline__ void jpeg_load4(const uint8_t *__restrict__ row, int 
 
 // rgb: W x H pixels, rows `stride` bytes apart.  coef: 64 int16 per block, block b = 6 * (my * MW + mx) + k.
 // Grid: (ceil(MW / 8), MH), 256 lanes.  wide != 0: rgb and stride are multiples of 4.
-__global__ __launch_bounds__(256) void k_jpeg_blocks(const uint8_t *__restrict__ rgb, long long stride, int W, int H, int MW,
-                                                     const hsjpeg::Tables *__restrict__ tab, int16_t *__restrict__ coef, int wide)
+__device__ __forceinline__ void jpeg_blocks_body(const uint8_t *__restrict__ rgb, long long stride, int W, int H, int MW,
+                                                 const hsjpeg::Tables *__restrict__ tab, int16_t *__restrict__ coef, int wide)
 {
     constexpr int S = kJpegStripMcus;
     __shared__ uint32_t sY[16][4 * S + 1];      // 16 rows of 128 luma samples, 4 to a word; the odd stride spreads the rows over the banks
@@ -141,9 +169,23 @@ __global__ __launch_bounds__(256) void k_jpeg_blocks(const uint8_t *__restrict__
     }
 }
 
+__global__ __launch_bounds__(256) void k_jpeg_blocks(const uint8_t *__restrict__ rgb, long long stride, int W, int H, int MW,
+                                                     const hsjpeg::Tables *__restrict__ tab, int16_t *__restrict__ coef, int wide)
+{
+    jpeg_blocks_body(rgb, stride, W, H, MW, tab, coef, wide);
+}
+
+// Grid: (ceil(MW / 8), MH, pictures).
+__global__ __launch_bounds__(256) void k_jpeg_blocks_batch(const JpegBatchPics pics, long long stride, int W, int H, int MW,
+                                                           const hsjpeg::Tables *__restrict__ tab, const JpegBatchScratch sc)
+{
+    const unsigned i = blockIdx.z;
+    jpeg_blocks_body(pics.p[i].rgb, stride, W, H, MW, tab, sc.coef_of(i), pics.p[i].wide);
+}
+
 // len[b]: the bits of block b, at most hsjpeg::kMaxBlockBits.
-__global__ __launch_bounds__(256) void k_jpeg_lengths(const hsjpeg::Tables *__restrict__ tab, const int16_t *__restrict__ coef, int W, int H, int MW,
-                                                      long long nb, uint32_t *__restrict__ len)
+__device__ __forceinline__ void jpeg_lengths_body(const hsjpeg::Tables *__restrict__ tab, const int16_t *__restrict__ coef, int W, int H, int MW,
+                                                  long long nb, uint32_t *__restrict__ len)
 {
     const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
     if (b >= nb) return;
@@ -153,6 +195,20 @@ __global__ __launch_bounds__(256) void k_jpeg_lengths(const hsjpeg::Tables *__re
     hsjpeg::CountSink sink;
     hsjpeg::block_bits(*tab, k < 4 ? 0 : 1, coef + b * 64, hsjpeg::block_dc(coef, W, H, MW, b), hsjpeg::block_pred(coef, W, H, MW, b), dummy, sink);
     len[b] = sink.bits;
+}
+
+__global__ __launch_bounds__(256) void k_jpeg_lengths(const hsjpeg::Tables *__restrict__ tab, const int16_t *__restrict__ coef, int W, int H, int MW,
+                                                      long long nb, uint32_t *__restrict__ len)
+{
+    jpeg_lengths_body(tab, coef, W, H, MW, nb, len);
+}
+
+// Grid: (ceil(nb / 256), pictures).
+__global__ __launch_bounds__(256) void k_jpeg_lengths_batch(const hsjpeg::Tables *__restrict__ tab, const JpegBatchScratch sc, int W, int H, int MW,
+                                                            long long nb)
+{
+    const unsigned i = blockIdx.y;
+    jpeg_lengths_body(tab, sc.coef_of(i), W, H, MW, nb, sc.len_of(i));
 }
 
 // out[i] = in[0] + ... + in[i - 1] for i = 0 .. n (n + 1 entries: out[n] is the total).  One workgroup of 1024 lanes:
@@ -210,6 +266,15 @@ __global__ __launch_bounds__(kJpegScanLanes) void k_jpeg_scan(const uint32_t *__
     jpeg_scan_body(in, out, n, raw_bits);
 }
 
+// One workgroup per picture (grid = pictures).  second == 0: the nb blocks' bit lengths into their offsets; otherwise
+// the nchunks chunks' 0xFF counts into their stuffing offsets, over the chunks the picture's raw stream reaches.
+__global__ __launch_bounds__(kJpegScanLanes) void k_jpeg_scan_batch(const JpegBatchScratch sc, long long nb, long long nchunks, int second)
+{
+    const unsigned i = blockIdx.x;
+    if (!second) jpeg_scan_body(sc.len_of(i), sc.off_of(i), nb, (const uint64_t *)nullptr);
+    else jpeg_scan_body(sc.ff_of(i), sc.ffoff_of(i), nchunks, sc.off_of(i) + nb);
+}
+
 // A block's bits into the raw stream from bit `pos` on.  Stream bit i is bit 7 - i % 8 of byte i / 8; a word is
 // assembled with its first stream bit on top and byte-swapped into memory order.  Words that hold bits of this block
 // alone are stored; the first word when the block starts inside it, and the last when it ends inside it, are OR-ed
@@ -250,8 +315,8 @@ struct JpegEmitSink {
 };
 
 // raw: the raw stream, zero before; off[b]: block b's bit offset, off[nb] the total.
-__global__ __launch_bounds__(256) void k_jpeg_emit(const hsjpeg::Tables *__restrict__ tab, const int16_t *__restrict__ coef, int W, int H, int MW,
-                                                   long long nb, const uint64_t *__restrict__ off, uint32_t *__restrict__ raw)
+__device__ __forceinline__ void jpeg_emit_body(const hsjpeg::Tables *__restrict__ tab, const int16_t *__restrict__ coef, int W, int H, int MW,
+                                               long long nb, const uint64_t *__restrict__ off, uint32_t *__restrict__ raw)
 {
     const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
     if (b >= nb) return;
@@ -267,6 +332,20 @@ __global__ __launch_bounds__(256) void k_jpeg_emit(const hsjpeg::Tables *__restr
     sink.finish();
 }
 
+__global__ __launch_bounds__(256) void k_jpeg_emit(const hsjpeg::Tables *__restrict__ tab, const int16_t *__restrict__ coef, int W, int H, int MW,
+                                                   long long nb, const uint64_t *__restrict__ off, uint32_t *__restrict__ raw)
+{
+    jpeg_emit_body(tab, coef, W, H, MW, nb, off, raw);
+}
+
+// Grid: (ceil(nb / 256), pictures).
+__global__ __launch_bounds__(256) void k_jpeg_emit_batch(const hsjpeg::Tables *__restrict__ tab, const JpegBatchScratch sc, int W, int H, int MW,
+                                                         long long nb)
+{
+    const unsigned i = blockIdx.y;
+    jpeg_emit_body(tab, sc.coef_of(i), W, H, MW, nb, sc.off_of(i), sc.raw_of(i));
+}
+
 __device__ __forceinline__ uint32_t jpeg_ff_in_word(uint32_t w)
 {
     uint32_t n = 0;
@@ -276,8 +355,8 @@ __device__ __forceinline__ uint32_t jpeg_ff_in_word(uint32_t w)
 }
 
 // cnt[c]: the 0xFF bytes of chunk c of the raw stream, for the chunks the stream reaches (it is zero behind its end).
-__global__ __launch_bounds__(256) void k_jpeg_count_ff(const uint32_t *__restrict__ raw, const uint64_t *__restrict__ raw_bits, long long nchunks,
-                                                       uint32_t *__restrict__ cnt)
+__device__ __forceinline__ void jpeg_count_ff_body(const uint32_t *__restrict__ raw, const uint64_t *__restrict__ raw_bits, long long nchunks,
+                                                   uint32_t *__restrict__ cnt)
 {
     const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
     if (c >= jpeg_chunks_used(*raw_bits, nchunks)) return;
@@ -291,11 +370,24 @@ __global__ __launch_bounds__(256) void k_jpeg_count_ff(const uint32_t *__restric
     cnt[c] = n;
 }
 
+__global__ __launch_bounds__(256) void k_jpeg_count_ff(const uint32_t *__restrict__ raw, const uint64_t *__restrict__ raw_bits, long long nchunks,
+                                                       uint32_t *__restrict__ cnt)
+{
+    jpeg_count_ff_body(raw, raw_bits, nchunks, cnt);
+}
+
+// Grid: (ceil(nchunks / 256), pictures).
+__global__ __launch_bounds__(256) void k_jpeg_count_ff_batch(const JpegBatchScratch sc, long long nb, long long nchunks)
+{
+    const unsigned i = blockIdx.y;
+    jpeg_count_ff_body(sc.raw_of(i), sc.off_of(i) + nb, nchunks, sc.ff_of(i));
+}
+
 // The file: header, the raw stream with 0x00 behind every 0xFF (chunk c's bytes start ffoff[c] later than unstuffed),
 // FF D9.  *total: the file's size, whatever `capacity`; bytes at or beyond capacity are not written.
-__global__ __launch_bounds__(256) void k_jpeg_stuff(const hsjpeg::Tables *__restrict__ tab, const uint32_t *__restrict__ raw, const uint64_t *__restrict__ raw_bits,
-                                                    const uint64_t *__restrict__ ffoff, long long nchunks, uint8_t *__restrict__ out,
-                                                    unsigned long long capacity, uint64_t *__restrict__ total)
+__device__ __forceinline__ void jpeg_stuff_body(const hsjpeg::Tables *__restrict__ tab, const uint32_t *__restrict__ raw, const uint64_t *__restrict__ raw_bits,
+                                                const uint64_t *__restrict__ ffoff, long long nchunks, uint8_t *__restrict__ out,
+                                                unsigned long long capacity, uint64_t *__restrict__ total)
 {
     const unsigned long long raw_bytes = (*raw_bits + 7u) / 8u;
     const long long used = jpeg_chunks_used(*raw_bits, nchunks);
@@ -330,6 +422,21 @@ __global__ __launch_bounds__(256) void k_jpeg_stuff(const hsjpeg::Tables *__rest
             src++;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_jpeg_stuff(const hsjpeg::Tables *__restrict__ tab, const uint32_t *__restrict__ raw, const uint64_t *__restrict__ raw_bits,
+                                                    const uint64_t *__restrict__ ffoff, long long nchunks, uint8_t *__restrict__ out,
+                                                    unsigned long long capacity, uint64_t *__restrict__ total)
+{
+    jpeg_stuff_body(tab, raw, raw_bits, ffoff, nchunks, out, capacity, total);
+}
+
+// Grid: (ceil(nchunks / 256), pictures).  total: the chunk's size words, picture i's is total[i].
+__global__ __launch_bounds__(256) void k_jpeg_stuff_batch(const hsjpeg::Tables *__restrict__ tab, const JpegBatchScratch sc, long long nb, long long nchunks,
+                                                          const JpegBatchPics pics, uint64_t *__restrict__ total)
+{
+    const unsigned i = blockIdx.y;
+    jpeg_stuff_body(tab, sc.raw_of(i), sc.off_of(i) + nb, sc.ffoff_of(i), nchunks, pics.p[i].out, pics.p[i].capacity, total + i);
 }
 
 } // namespace hsk

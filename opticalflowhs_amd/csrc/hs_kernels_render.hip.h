@@ -9,6 +9,9 @@
 //
 //   k_render_scatter: one lane per grid point; priorities into a uint32 plane (zero before).
 //   k_render_resolve: one pass over the plane: packed RGB out, zero written back -- no clear between renders.
+// Each kernel's work for one picture is a __device__ body; the entries above call it with their own arguments, and
+//   k_render_scatter_batch, k_render_resolve_batch take the pair from a further grid dimension: pair i reads its own
+//   flow planes and owns a priority plane of its own, and its picture's pointer comes from an argument block by value.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,9 +20,17 @@
 
 namespace hsk {
 
+constexpr int kRenderBatchMax = 32; // pictures per set of launches (HSFLOW_JPEG_BATCH_MAX is at most this)
+
+// What differs from picture to picture of a batched render, handed to the kernel by value.
+struct RenderBatchPics {
+    uint8_t *rgb[kRenderBatchMax];
+    uint32_t wide; // bit i: picture i's base and the stride are multiples of 4
+};
+
 // u, v: the flow planes of one pair (pitch P floats).  prio: width x height words, pitch PP.  n = gx * gy grid points.
-__global__ __launch_bounds__(256) void k_render_scatter(const float *__restrict__ u, const float *__restrict__ v, unsigned *__restrict__ prio,
-                                                        int W, int H, int P, int PP, int step, int gx, unsigned n, float thr, float scale)
+__device__ __forceinline__ void render_scatter_body(const float *__restrict__ u, const float *__restrict__ v, unsigned *__restrict__ prio,
+                                                    int W, int H, int P, int PP, int step, int gx, unsigned n, float thr, float scale)
 {
     const unsigned k = blockIdx.x * 256u + threadIdx.x;
     if (k >= n) return;
@@ -46,6 +57,22 @@ __global__ __launch_bounds__(256) void k_render_scatter(const float *__restrict_
     }
 }
 
+__global__ __launch_bounds__(256) void k_render_scatter(const float *__restrict__ u, const float *__restrict__ v, unsigned *__restrict__ prio,
+                                                        int W, int H, int P, int PP, int step, int gx, unsigned n, float thr, float scale)
+{
+    render_scatter_body(u, v, prio, W, H, P, PP, step, gx, n, thr, scale);
+}
+
+// Grid: (ceil(n / 256), pairs).  u, v: the planes of the first pair; pair i's lie i * plane floats, its priorities
+// i * plane words further.
+__global__ __launch_bounds__(256) void k_render_scatter_batch(const float *__restrict__ u, const float *__restrict__ v, unsigned *__restrict__ prio,
+                                                              long long plane, int W, int H, int P, int PP, int step, int gx, unsigned n, float thr,
+                                                              float scale)
+{
+    const long long o = (long long)blockIdx.y * plane;
+    render_scatter_body(u + o, v + o, prio + o, W, H, P, PP, step, gx, n, thr, scale);
+}
+
 __device__ __forceinline__ unsigned render_colour(unsigned p, unsigned dot, unsigned line)
 {
     return p == 0u ? 0u : ((p & 1u) ? dot : line);
@@ -54,8 +81,8 @@ __device__ __forceinline__ unsigned render_colour(unsigned p, unsigned dot, unsi
 // Each lane takes 4 pixels of a row: one 16-byte load of priorities, 12 bytes of picture.  dot / line: R | G << 8 | B << 16.
 // wide != 0: rgb and stride are multiples of 4, so the 12 bytes go out as three aligned words; the last pixels of a
 // row whose width is no multiple of 4, and every pixel otherwise, go out byte by byte -- nothing beyond 3*W is touched.
-__global__ __launch_bounds__(256) void k_render_resolve(unsigned *__restrict__ prio, uint8_t *__restrict__ rgb, long long stride, int W, int H,
-                                                        int PP, unsigned dot, unsigned line, int wide)
+__device__ __forceinline__ void render_resolve_body(unsigned *__restrict__ prio, uint8_t *__restrict__ rgb, long long stride, int W, int H,
+                                                    int PP, unsigned dot, unsigned line, int wide)
 {
     const int x0 = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (x0 >= W) return;
@@ -82,6 +109,20 @@ __global__ __launch_bounds__(256) void k_render_resolve(unsigned *__restrict__ p
                 }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_render_resolve(unsigned *__restrict__ prio, uint8_t *__restrict__ rgb, long long stride, int W, int H,
+                                                        int PP, unsigned dot, unsigned line, int wide)
+{
+    render_resolve_body(prio, rgb, stride, W, H, PP, dot, line, wide);
+}
+
+// Grid: (ceil(W / 1024), rows, pairs): pair i's priority plane into pics.rgb[i].
+__global__ __launch_bounds__(256) void k_render_resolve_batch(unsigned *__restrict__ prio, long long plane, const RenderBatchPics pics, long long stride,
+                                                              int W, int H, int PP, unsigned dot, unsigned line)
+{
+    const unsigned i = blockIdx.z;
+    render_resolve_body(prio + (long long)i * plane, pics.rgb[i], stride, W, H, PP, dot, line, (int)((pics.wide >> i) & 1u));
 }
 
 } // namespace hsk

@@ -1,7 +1,8 @@
 // hs_render.hip.h -- part of libhsflow.so (one translation unit, see hsflow.hip): hsflow_render_flow[_device], the
 // flow picture of the reference (OpticalFlowOpenCV.cpp:33-46, HSOpticalFlowOpenCL.cpp:759-769) drawn from the flow
 // where the solver left it.  Two launches on the context's stream (hs_kernels_render.hip.h); a context that never
-// renders allocates and launches nothing here.
+// renders allocates and launches nothing here.  hsflow_render_flow_batch_device: the pictures of consecutive pairs by
+// two launches per chunk of at most HSFLOW_JPEG_BATCH_MAX.
 #pragma once
 
 namespace {
@@ -21,10 +22,11 @@ int enqueue_render(hsflow_ctx *c, int pair, const hsflow_render_params &rp, uint
     const size_t words = (size_t)c->plane;
     if (!c->dPrio) {
         HS_HIP(c, hipMalloc((void **)&c->dPrio, words * sizeof(unsigned)));
+        c->prio_planes = 1;
         c->prio_dirty = true;
     }
-    if (c->prio_dirty) {
-        HS_HIP(c, hipMemsetAsync(c->dPrio, 0, words * sizeof(unsigned), c->stream));
+    if (c->prio_dirty) { // (every plane there is: a batched render may have left any of them dirty)
+        HS_HIP(c, hipMemsetAsync(c->dPrio, 0, words * sizeof(unsigned) * (size_t)c->prio_planes, c->stream));
         c->prio_dirty = false;
     }
     const int gx = (c->W + rp.step - 1) / rp.step, gy = (c->H + rp.step - 1) / rp.step;
@@ -43,6 +45,74 @@ int enqueue_render(hsflow_ctx *c, int pair, const hsflow_render_params &rp, uint
     // work that reads the flow planes now lies behind the marker of the last solve: hsflow_wait_solve and
     // hsflow_flow_view_device wait for the stream, not for that marker
     c->last_marked = false;
+    return HSFLOW_OK;
+}
+
+// HSFLOW_JPEG_BATCH_MAX of this call: the environment's (1 .. the header's, for measuring the candidates), else the
+// header's.  0: the environment's value is unusable.
+int jpeg_batch_max()
+{
+    static_assert(HSFLOW_JPEG_BATCH_MAX >= 1 && HSFLOW_JPEG_BATCH_MAX <= hsk::kRenderBatchMax && HSFLOW_JPEG_BATCH_MAX <= hsk::kJpegBatchMax,
+                  "the kernels' argument blocks hold at most 32 pictures");
+    const char *e = getenv("HSFLOW_JPEG_BATCH_MAX");
+    if (!e || !*e) return HSFLOW_JPEG_BATCH_MAX;
+    char *rest = nullptr;
+    const long v = strtol(e, &rest, 10);
+    if (*rest || v < 1 || v > HSFLOW_JPEG_BATCH_MAX) return 0;
+    return (int)v;
+}
+
+// The checks the batched entries share: the pairs ...
+int check_batch_pairs(hsflow_ctx *c, int first_pair, int n)
+{
+    if (n < 1) return fail(c, HSFLOW_E_ARG, "a batch needs at least one picture");
+    if (first_pair < 0 || (long long)first_pair + n > c->N) return fail(c, HSFLOW_E_ARG, "the batch's pairs exceed the context's");
+    return HSFLOW_OK;
+}
+
+// ... and the chunk size of this call into *maxb.
+int check_batch_max(hsflow_ctx *c, int *maxb)
+{
+    if (!(*maxb = jpeg_batch_max())) return fail(c, HSFLOW_E_ARG, "HSFLOW_JPEG_BATCH_MAX in the environment must be 1 .. " + std::to_string(HSFLOW_JPEG_BATCH_MAX));
+    return HSFLOW_OK;
+}
+
+// One priority plane per picture of a chunk of `planes`.  Grown behind a wait for the stream: what is in flight still uses
+// the old ones.
+int render_batch_reserve(hsflow_ctx *c, int planes)
+{
+    if (c->prio_planes >= planes) return HSFLOW_OK;
+    HS_HIP(c, hipStreamSynchronize(c->stream));
+    hipFree(c->dPrio);
+    c->dPrio = nullptr; c->prio_planes = 0;
+    HS_HIP(c, hipMalloc((void **)&c->dPrio, (size_t)c->plane * sizeof(unsigned) * (size_t)planes));
+    c->prio_planes = planes;
+    c->prio_dirty = true;
+    return HSFLOW_OK;
+}
+
+// Both launches for the pairs first_pair .. first_pair + cnt - 1 (cnt <= prio_planes), picture i into pics.rgb[i].  The
+// caller has checked every argument.
+int enqueue_render_chunk(hsflow_ctx *c, int first_pair, int cnt, const hsflow_render_params &rp, const hsk::RenderBatchPics &pics, size_t stride)
+{
+    const size_t words = (size_t)c->plane;
+    if (c->prio_dirty) {
+        HS_HIP(c, hipMemsetAsync(c->dPrio, 0, words * sizeof(unsigned) * (size_t)c->prio_planes, c->stream));
+        c->prio_dirty = false;
+    }
+    const int gx = (c->W + rp.step - 1) / rp.step, gy = (c->H + rp.step - 1) / rp.step;
+    const unsigned n = (unsigned)((long long)gx * gy);
+    const unsigned dot = rp.dot_rgb[0] | (unsigned)rp.dot_rgb[1] << 8 | (unsigned)rp.dot_rgb[2] << 16;
+    const unsigned line = rp.line_rgb[0] | (unsigned)rp.line_rgb[1] << 8 | (unsigned)rp.line_rgb[2] << 16;
+    c->prio_dirty = true; // until the resolve pass has been enqueued behind the scatter pass
+    hipLaunchKernelGGL(hsk::k_render_scatter_batch, dim3((n + 255u) / 256u, (unsigned)cnt), dim3(256), 0, c->stream, c->dU[c->cur] + first_pair * c->plane,
+                       c->dV[c->cur] + first_pair * c->plane, c->dPrio, c->plane, c->W, c->H, c->P, c->P, rp.step, gx, n, rp.threshold, rp.scale);
+    HS_HIP(c, hipGetLastError());
+    const dim3 grid((c->W + 1023) / 1024, c->H < 65535 ? c->H : 65535, (unsigned)cnt);
+    hipLaunchKernelGGL(hsk::k_render_resolve_batch, grid, dim3(256), 0, c->stream, c->dPrio, c->plane, pics, (long long)stride, c->W, c->H, c->P, dot, line);
+    HS_HIP(c, hipGetLastError());
+    c->prio_dirty = false;
+    c->last_marked = false; // (as enqueue_render: the flow planes are read behind the marker of the last solve)
     return HSFLOW_OK;
 }
 
@@ -73,6 +143,31 @@ int hsflow_render_flow_device(hsflow_ctx *c, int pair, const hsflow_render_param
     // the picture of a flow that a re-run would change is worth nothing: an owed ITER|EPS check is settled first
     if ((st = settle_pending(c))) return st;
     return enqueue_render(c, pair, *rp, (uint8_t *)d_rgb, stride);
+}
+
+int hsflow_render_flow_batch_device(hsflow_ctx *c, int first_pair, int n, const hsflow_render_params *rp, void *const *d_rgb, size_t stride)
+{
+    int st = check_ctx(c, 0), maxb = 0;
+    if (st) return st;
+    if ((st = check_batch_pairs(c, first_pair, n))) return st;
+    if ((st = check_render_params(c, rp))) return st;
+    if (!d_rgb) return fail(c, HSFLOW_E_ARG, "null picture list");
+    for (int i = 0; i < n; i++)
+        if (!d_rgb[i]) return fail(c, HSFLOW_E_ARG, "picture " + std::to_string(i) + ": null picture pointer");
+    if (stride < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
+    if ((st = check_batch_max(c, &maxb))) return st;
+    if ((st = settle_pending(c))) return st;
+    if ((st = render_batch_reserve(c, n < maxb ? n : maxb))) return st;
+    for (int first = 0; first < n; first += maxb) {
+        const int cnt = n - first < maxb ? n - first : maxb;
+        hsk::RenderBatchPics pics{};
+        for (int k = 0; k < cnt; k++) {
+            pics.rgb[k] = (uint8_t *)d_rgb[first + k];
+            if ((((uintptr_t)d_rgb[first + k] | stride) & 3u) == 0) pics.wide |= 1u << k;
+        }
+        if ((st = enqueue_render_chunk(c, first_pair + first, cnt, *rp, pics, stride))) return st;
+    }
+    return HSFLOW_OK;
 }
 
 int hsflow_render_flow(hsflow_ctx *c, int pair, const hsflow_render_params *rp, uint8_t *rgb, size_t stride)

@@ -335,6 +335,64 @@ class HSFlow(object):
         self.synchronize()
         return out[:int(size.item())].cpu().numpy().tobytes()
 
+    def encode_jpeg_batch(self, pictures, quality=95):
+        """`encode_jpeg` for a list of CUDA uint8 tensors of shape (H, W, 3) (packed pixels, one row stride for all, any
+        alignment each): one set of launches per `JPEG_BATCH_MAX` pictures (`hsflow_jpeg_encode_batch_device`).  Returns
+        the list of the files as `bytes`, each byte for byte what `encode_jpeg` gives for that picture."""
+        import torch
+        n = len(pictures)
+        if n < 1 or not all(_is_device_tensor(t) for t in pictures):
+            raise ValueError("expected a non-empty list of CUDA uint8 tensors of shape (height, width, 3)")
+        targets = [_render_target(t, self.height, self.width) for t in pictures]
+        if len(set(s for _, s in targets)) != 1:
+            raise ValueError("the pictures of a batch share one row stride")
+        dev = pictures[0].device
+        bound = jpeg_bound(self.width, self.height)
+        out = torch.empty((n, bound), dtype=torch.uint8, device=dev)
+        sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+        src = (ctypes.c_void_p * n)(*[p.value for p, _ in targets])
+        dst = (ctypes.c_void_p * n)(*[out.data_ptr() + i * bound for i in range(n)])
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._lib.hsflow_jpeg_encode_batch_device(self._h, src, n, targets[0][1], int(quality), dst, bound, _ptr(sizes)))
+        self.synchronize()
+        host = sizes.cpu().tolist()
+        return [out[i, :int(host[i])].cpu().numpy().tobytes() for i in range(n)]
+
+    def _batch_range(self, first_pair, n):
+        first_pair = int(first_pair)
+        return first_pair, self.n_pairs - first_pair if n is None else int(n)
+
+    def render_jpeg_batch(self, route="cv", quality=95, first_pair=0, n=None, params=None, **kw):
+        """`render_jpeg` for the pairs first_pair .. first_pair + n - 1 (n=None: all pairs from first_pair): drawn and
+        encoded on the device by one set of launches per `JPEG_BATCH_MAX` pairs (`hsflow_render_flow_jpeg_batch`); per
+        chunk the size words cross in one copy, then the files.  Returns the list of the files as `bytes`, each byte for
+        byte what `render_jpeg(pair=i)` gives.  Complete on return."""
+        rp = params if params is not None else make_render_params(route, **kw)
+        first_pair, n = self._batch_range(first_pair, n)
+        bound = jpeg_bound(self.width, self.height)
+        buf = np.empty((max(n, 1), bound), np.uint8)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[buf[i].ctypes.data for i in range(max(n, 1))])
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        self._check(self._lib.hsflow_render_flow_jpeg_batch(self._h, first_pair, n, ctypes.byref(rp), int(quality), ptrs, bound, sizes))
+        return [buf[i, :sizes[i]].tobytes() for i in range(n)]
+
+    def render_batch_device(self, out, route="cv", first_pair=0, n=None, params=None, **kw):
+        """`render` into caller tensors for the pairs first_pair .. first_pair + n - 1 (n=None: all pairs from first_pair)
+        by two launches per `JPEG_BATCH_MAX` pairs (`hsflow_render_flow_batch_device`).  out: a CUDA uint8 tensor
+        (n, H, W, 3) or a list of n tensors (H, W, 3), packed pixels, one row stride for all.  Only enqueued on the
+        context's stream (complete after `synchronize()`); returns `out`."""
+        rp = params if params is not None else make_render_params(route, **kw)
+        first_pair, n = self._batch_range(first_pair, n)
+        pictures = [out[i] for i in range(len(out))]
+        if len(pictures) != n or not all(_is_device_tensor(t) for t in pictures):
+            raise ValueError("out must hold one CUDA uint8 tensor of shape (height, width, 3) per pair")
+        targets = [_render_target(t, self.height, self.width) for t in pictures]
+        if len(set(s for _, s in targets)) > 1:
+            raise ValueError("the pictures of a batch share one row stride")
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[p.value for p, _ in targets])
+        self._check(self._lib.hsflow_render_flow_batch_device(self._h, first_pair, n, ctypes.byref(rp), ptrs, targets[0][1] if targets else 0))
+        return out
+
     def jpeg_decode(self, data, order="rgb", out=None):
         """The picture of a baseline JPEG file (`bytes`) of the context's size, decoded on the device
         (`hsflow_jpeg_decode`): an (H, W, 3) uint8 array, R first ("rgb") or B first ("bgr").  out: a host array to decode
