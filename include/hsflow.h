@@ -635,13 +635,15 @@ int hsflow_jpeg_decode_host(const uint8_t *file, size_t bytes, int order, uint8_
 /* A file in HOST memory -> its picture in device memory; only enqueued on ctx's stream (a copy of the entropy-coded
  * segment and the tables from page-locked staging of the library's own -- the caller's buffer is free on return; two
  * staging areas, so two decodes can be enqueued back to back and a third waits for the first one's copy --, three
- * memsets and twelve launches without restart intervals, nine with; nothing read back in between).  The picture
+ * memsets and, as a chunk of one file of the batched path below, eleven launches without restart intervals, eight with;
+ * nothing read back in between).  The picture
  * must have the context's size, else HSFLOW_E_SIZE.  HSFLOW_E_DATA is returned at once for what the header shows;
  * d_status, a device word, receives what only the bit stream shows: 0 ok, 1 corrupt, 2 truncated (the pixels are then
  * undefined, but nothing outside the picture's width x height x 3 bytes is written either way).
  * Touches no solver state: an owed ITER|EPS check stays owed.  The first decode of a context allocates its scratch
- * (coefficients, component planes, DC sums: 20.4 MB at 1080p; per file the segment, the clean stream and the
- * subsequences' states, grown on demand behind a wait for the stream), kept until hsflow_destroy; contexts that never
+ * (by the file's block count coefficients, component planes, DC sums: 19.8 MB for a 1080p file at 4:4:4; by its length
+ * the segment, the clean stream and the subsequences' states; grown on demand behind a wait for the stream, and the one
+ * allocation the batched entry grows), kept until hsflow_destroy; contexts that never
  * decode pay nothing, and the scratch does not count for HSFLOW_KERNEL_PERSIST's "only one alive" rule.
  * HSFLOW_E_ARG: null pointer, unknown order, d_status not 4-byte aligned, HSFLOW_JPEGD_SUBSEQ_BITS in the environment
  * not a multiple of 32 in 32..4096; HSFLOW_E_SIZE: stride < 3*width, a picture of another size. */
@@ -660,8 +662,8 @@ int hsflow_set_frames_jpeg(hsflow_ctx *ctx, int pair, const uint8_t *prev, size_
 int hsflow_push_frame_jpeg(hsflow_ctx *ctx, int pair, const uint8_t *next, size_t bytes, int blur3x3, int reblur_prev);
 
 /* Many files by the same launches.  Files are independent, so n of them decoded side by side take about as long as
- * the longest one: every decode kernel has a batched form whose grid carries the file as a further dimension and reads
- * a per-file record from device memory (csrc/hs_kernels_jpegd.hip.h); the arithmetic is the single-file kernels' own.
+ * the longest one: every decode kernel's grid carries the file as a further dimension and reads a per-file record from
+ * device memory (csrc/hs_kernels_jpegd.hip.h); hsflow_jpeg_decode_device above is a chunk of one through the same kernels.
  * A batch larger than HSFLOW_JPEGD_BATCH_MAX is decoded in consecutive chunks of at most that many: per chunk one copy
  * from page-locked staging (every file's tables and segment, the records), three memsets and eleven launches for files
  * without restart intervals, eight for files with, twelve for a chunk that mixes the two.  The constant bounds

@@ -177,19 +177,15 @@ struct hsflow_ctx {
         size_t out_bytes = 0;
         uint64_t *hSize = nullptr;
     } jpeg;
-    // hsflow_jpeg_decode_device and the entries built on it (hs_jpegd.hip.h), allocated by the first decode and kept: one
-    // block of device memory sized by the context (coefficients 128 B per block, component planes, DC differences and sums,
-    // the restart intervals' starts), one sized by the longest file so far (tables and segment, the clean stream, per-chunk
-    // and per-subsequence words); two page-locked staging areas with the event behind each one's copy; for the synchronous
-    // forms a picture on the device (its first 256 bytes hold the status words), two BGR pictures, page-locked status words
+    // hsflow_jpeg_decode_device, hsflow_jpeg_decode_batch_device and the entries built on them (hs_jpegd.hip.h), allocated
+    // by the first decode and kept: one block of device memory for a chunk's files, laid out by hs_jpegd_batch_plan.h (a
+    // single decode is a chunk of one) and grown to the largest chunk so far; two page-locked staging areas with the event
+    // behind each one's copy; for the synchronous forms a picture on the device (its first 256 bytes hold the status
+    // words), two BGR pictures, page-locked status words; hsflow_set_sequence_jpeg's status words (the first 256-byte
+    // multiple) and pictures on the device, its status words in page-locked memory
     struct JpegdScratch {
-        void *frame_base = nullptr, *file_base = nullptr;
-        size_t file_bytes = 0;
-        long long nb_cap = 0;
-        int16_t *coef = nullptr;
-        uint8_t *planes = nullptr;
-        uint32_t *diff = nullptr, *rstPos = nullptr;
-        uint64_t *dcsum = nullptr;
+        void *base = nullptr;
+        size_t bytes = 0;
         uint8_t *stage[2] = {nullptr, nullptr};
         size_t stage_bytes[2] = {0, 0};
         hipEvent_t evStage[2] = {nullptr, nullptr};
@@ -199,6 +195,12 @@ struct hsflow_ctx {
         uint8_t *bgr[2] = {nullptr, nullptr};
         uint32_t *dStatus = nullptr, *hStatus = nullptr;
         hipEvent_t evDone = nullptr;
+        uint8_t *seq = nullptr;
+        size_t seq_bytes = 0;
+        uint32_t *hSeq = nullptr;
+        int hSeq_words = 0;
+        bool pair_status_owed = false; // hsflow_set_frames_jpeg_async's two words are on their way into hStatus[2 .. 3],
+        hipEvent_t evPair = nullptr;   // this event behind their copy; hsflow_jpeg_async_status has not asked yet
     } jpegd;
     // hsflow_verify / hsflow_compare_flow_device (hs_verify.hip.h), all allocated by the first call: the parameters of the
     // last solve asked for through the ABI and how it ended; the reference pass's own buffers, held as a second context
@@ -257,19 +259,6 @@ struct hsflow_ctx {
     std::map<GraphKey, GraphEntry> graphs;
     std::vector<PlanEntry> plan_cache; // prepare_solve's results by parameters; cleared when what they rest on changes
     std::vector<hipEvent_t> events;
-    // a batch of JPEG files (hs_jpegd.hip.h, hs_jpegd_batch_plan.h), allocated by the first batch call and kept: one
-    // allocation for a chunk's files; hsflow_set_sequence_jpeg's status words (the first 256-byte multiple) and pictures on
-    // the device, its status words in page-locked memory.  (Behind everything else: the solver's fields lie where they lay.)
-    struct JpegdBatchScratch {
-        void *batch_base = nullptr;
-        size_t batch_bytes = 0;
-        uint8_t *seq = nullptr;
-        size_t seq_bytes = 0;
-        uint32_t *hSeq = nullptr;
-        int hSeq_words = 0;
-        bool pair_status_owed = false; // hsflow_set_frames_jpeg_async's two words are on their way into jpegd.hStatus[2 .. 3],
-        hipEvent_t evPair = nullptr;   // this event behind their copy; hsflow_jpeg_async_status has not asked yet
-    } jpegd_batch;
     // a batch of pictures drawn and encoded by one set of launches per chunk (hs_render.hip.h, hs_jpeg.hip.h,
     // hs_jpeg_batch_plan.h), allocated by the first batched call and kept: dPrio holds prio_planes priority planes (the
     // single render uses the first); one allocation for the encode scratch of `pictures` slices, separate from the single
@@ -349,5 +338,8 @@ int fail(hsflow_ctx *c, int code, const std::string &msg)
     } while (0)
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// A picture whose base and row stride are multiples of 4: the kernels move its rows as whole words (`wide`).
+int word_aligned(const void *p, size_t stride) { return (((uintptr_t)p | stride) & 3u) == 0; }
 
 } // namespace

@@ -82,7 +82,7 @@ int enqueue_jpeg(hsflow_ctx *c, const uint8_t *d_rgb, size_t stride, int quality
     hsflow_ctx::JpegScratch &j = c->jpeg;
     if (!d_bytes) d_bytes = j.size;
     const int MW = hsjpeg::mcus_x(c->W), MH = hsjpeg::mcus_y(c->H);
-    const int wide = (((uintptr_t)d_rgb | stride) & 3u) == 0;
+    const int wide = word_aligned(d_rgb, stride);
     const unsigned gb = (unsigned)((j.nb + 255) / 256), gc = (unsigned)((j.nchunks + 255) / 256);
     HS_HIP(c, hipMemsetAsync(j.raw, 0, j.raw_bytes, c->stream));
     hipLaunchKernelGGL(hsk::k_jpeg_blocks, dim3((MW + hsk::kJpegStripMcus - 1) / hsk::kJpegStripMcus, MH), dim3(256), 0, c->stream, d_rgb,
@@ -177,7 +177,7 @@ int enqueue_jpeg_chunk(hsflow_ctx *c, const hsjpeg::Tables *tab, const hsk::Jpeg
 
 hsk::JpegBatchPic jpeg_batch_pic(const void *rgb, size_t stride, void *out, size_t capacity)
 {
-    return hsk::JpegBatchPic{(const uint8_t *)rgb, (uint8_t *)out, (unsigned long long)capacity, (((uintptr_t)rgb | stride) & 3u) == 0, 0};
+    return hsk::JpegBatchPic{(const uint8_t *)rgb, (uint8_t *)out, (unsigned long long)capacity, word_aligned(rgb, stride), 0};
 }
 
 // What the batched encodes check of the file side: quality, the lists, the context's size.

@@ -1,10 +1,10 @@
 // hs_jpegd.hip.h -- part of libhsflow.so (one translation unit, see hsflow.hip): hsflow_jpeg_read_header,
-// hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg: the frames the reference's
-// runFromImg starts from (cvLoadImage, OpticalFlowOpenCV.cpp:15,18, HSOpticalFlowOpenCL.cpp:721,732), decoded on the
-// device from the files' entropy-coded bytes.  One copy, three memsets and nine or twelve launches on the context's
-// stream (hs_kernels_jpegd.hip.h); a context that never decodes allocates and launches nothing here.
-// hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async: many files by one set of
-// launches per chunk of at most HSFLOW_JPEGD_BATCH_MAX, laid out by hs_jpegd_batch_plan.h.
+// hsflow_jpeg_decode[_host|_device|_batch_device], hsflow_set_frames_jpeg[_async], hsflow_push_frame_jpeg,
+// hsflow_set_sequence_jpeg: the frames the reference's runFromImg starts from (cvLoadImage, OpticalFlowOpenCV.cpp:15,18,
+// HSOpticalFlowOpenCL.cpp:721,732), decoded on the device from the files' entropy-coded bytes.  One path: files are
+// decoded in chunks of at most HSFLOW_JPEGD_BATCH_MAX, laid out by hs_jpegd_batch_plan.h, each chunk by one copy, three
+// memsets and eight or eleven launches on the context's stream (hs_kernels_jpegd.hip.h); a single file is a chunk of
+// one.  A context that never decodes allocates and launches nothing here.
 #pragma once
 
 #include "hs_jpegd_batch_plan.h"
@@ -14,11 +14,9 @@ namespace {
 void jpegd_release(hsflow_ctx *c)
 {
     hsflow_ctx::JpegdScratch &j = c->jpegd;
-    hipFree(j.frame_base);
-    hipFree(j.file_base);
-    hipFree(c->jpegd_batch.batch_base);
-    hipFree(c->jpegd_batch.seq);
-    if (c->jpegd_batch.hSeq) hipHostFree(c->jpegd_batch.hSeq);
+    hipFree(j.base);
+    hipFree(j.seq);
+    if (j.hSeq) hipHostFree(j.hSeq);
     hipFree(j.out);
     for (int i = 0; i < 2; i++) {
         hipFree(j.bgr[i]);
@@ -27,12 +25,9 @@ void jpegd_release(hsflow_ctx *c)
     }
     if (j.hStatus) hipHostFree(j.hStatus);
     if (j.evDone) hipEventDestroy(j.evDone);
-    if (c->jpegd_batch.evPair) hipEventDestroy(c->jpegd_batch.evPair);
+    if (j.evPair) hipEventDestroy(j.evPair);
     c->jpegd = hsflow_ctx::JpegdScratch();
-    c->jpegd_batch = hsflow_ctx::JpegdBatchScratch();
 }
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 // HSFLOW_JPEGD_SUBSEQ_BITS of this call: the environment's, else the header's.  0: the environment's value is unusable.
 int jpegd_subseq_bits()
@@ -84,110 +79,6 @@ int jpegd_stage(hsflow_ctx *c, size_t bytes, int *slot_out)
     return HSFLOW_OK;
 }
 
-// All of one decode, enqueued on c's stream.  The caller has checked every argument and parsed the header.
-int enqueue_jpegd(hsflow_ctx *c, const uint8_t *file, const hsjpegd::Frame &f, const hsjpegd::Tables &tab, int order, uint8_t *d_pix, size_t stride,
-                  uint32_t *d_status)
-{
-    hsflow_ctx::JpegdScratch &j = c->jpegd;
-    const int S = jpegd_subseq_bits();
-    if (!S) return fail(c, HSFLOW_E_ARG, "HSFLOW_JPEGD_SUBSEQ_BITS must be a multiple of 32 in 32 .. 4096");
-    // what the context's size bounds, once: 4:4:4 has the most blocks, 3 per 8x8 pixels of the picture padded to 16
-    if (!j.frame_base) {
-        const long long nb = 12ll * ((c->W + 15) / 16) * ((c->H + 15) / 16);
-        const size_t o_coef = 0, o_planes = o_coef + up256((size_t)nb * 128), o_diff = o_planes + up256((size_t)nb * 64), o_dcsum = o_diff + up256((size_t)nb * 4),
-                     o_rst = o_dcsum + up256(((size_t)nb + 1) * 8), total = o_rst + up256((size_t)nb * 4);
-        HS_HIP(c, hipMalloc(&j.frame_base, total));
-        uint8_t *p = (uint8_t *)j.frame_base;
-        j.coef = (int16_t *)(p + o_coef); j.planes = p + o_planes; j.diff = (uint32_t *)(p + o_diff); j.dcsum = (uint64_t *)(p + o_dcsum);
-        j.rstPos = (uint32_t *)(p + o_rst);
-        j.nb_cap = nb;
-    }
-    if (f.nblocks > j.nb_cap) return fail(c, HSFLOW_E_SIZE, "the file's block count exceeds the context's");
-    // what the file's length bounds: tables + segment (one copy), the clean stream, per chunk and per subsequence words
-    const uint32_t n = (uint32_t)f.scan_bytes, nchunks = (n + hsjpegd::kChunk - 1) / hsjpegd::kChunk;
-    const uint32_t nsubCap = (uint32_t)((((uint64_t)n * 8u + (uint32_t)S - 1u) / (uint32_t)S + hsk::kJpegdGroup - 1u) / hsk::kJpegdGroup * hsk::kJpegdGroup) + (n ? 0u : hsk::kJpegdGroup);
-    const size_t tab_bytes = up256(sizeof(hsjpegd::Tables)), in_bytes = tab_bytes + up256((size_t)n + 4);
-    const size_t o_in = 0, o_clean = o_in + in_bytes, o_cr = o_clean + up256((size_t)n + 16), o_cs = o_cr + up256((size_t)nchunks * 4 + 4),
-                 o_ro = o_cs + up256((size_t)nchunks * 4 + 4), o_so = o_ro + up256(((size_t)nchunks + 1) * 8), o_start = o_so + up256(((size_t)nchunks + 1) * 8),
-                 o_exit = o_start + up256((size_t)nsubCap * 8), o_cnt = o_exit + up256((size_t)nsubCap * 8), o_base = o_cnt + up256((size_t)nsubCap * 4),
-                 need = o_base + up256(((size_t)nsubCap + 1) * 8);
-    if (j.file_bytes < need) { // (what is in flight still reads the old one)
-        HS_HIP(c, hipStreamSynchronize(c->stream));
-        hipFree(j.file_base);
-        j.file_base = nullptr; j.file_bytes = 0;
-        HS_HIP(c, hipMalloc(&j.file_base, need));
-        j.file_bytes = need;
-    }
-    int slot = 0;
-    const int sst = jpegd_stage(c, in_bytes, &slot);
-    if (sst) return sst;
-    uint8_t *h = j.stage[slot];
-    std::memcpy(h, &tab, sizeof tab);
-    std::memcpy(h + tab_bytes, file + f.scan_offset, n);
-    std::memset(h + tab_bytes + n, 0, in_bytes - tab_bytes - n);
-    uint8_t *p = (uint8_t *)j.file_base;
-    HS_HIP(c, hipMemcpyAsync(p + o_in, h, in_bytes, hipMemcpyHostToDevice, c->stream));
-    HS_HIP(c, hipEventRecord(j.evStage[slot], c->stream));
-
-    hsk::JpegdArgs a;
-    a.f = f;
-    a.tab = (const hsjpegd::Tables *)(p + o_in);
-    a.scan = p + o_in + tab_bytes;
-    a.n = n; a.nchunks = nchunks; a.S = (uint32_t)S;
-    a.cntRem = (uint32_t *)(p + o_cr); a.cntRst = (uint32_t *)(p + o_cs);
-    a.remOff = (uint64_t *)(p + o_ro); a.rstOff = (uint64_t *)(p + o_so);
-    a.clean = (uint32_t *)(p + o_clean);
-    a.rstPos = j.rstPos;
-    const long long nmcu = (long long)f.mcux * f.mcuy;
-    a.nint = f.ri ? (uint32_t)((nmcu + f.ri - 1) / f.ri) : 0u;
-    a.start = (uint64_t *)(p + o_start); a.exit = (uint64_t *)(p + o_exit);
-    a.cnt = (uint32_t *)(p + o_cnt); a.base = (uint64_t *)(p + o_base);
-    a.nsubCap = nsubCap;
-    a.coef = j.coef; a.diff = j.diff; a.dcsum = j.dcsum; a.planes = j.planes;
-    a.status = d_status;
-
-    const unsigned gc = nchunks ? (nchunks + 255u) / 256u : 1u, gb = (unsigned)((f.nblocks + 255) / 256);
-    HS_HIP(c, hipMemsetAsync(d_status, 0, sizeof(uint32_t), c->stream));
-    HS_HIP(c, hipMemsetAsync(a.clean, 0, up256((size_t)n + 16), c->stream));
-    HS_HIP(c, hipMemsetAsync(a.coef, 0, (size_t)f.nblocks * 128, c->stream));
-    hipLaunchKernelGGL(hsk::k_jpegd_clean<0>, dim3(gc), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(hsk::k_jpeg_scan, dim3(1), dim3(hsk::kJpegScanLanes), 0, c->stream, a.cntRem, a.remOff, (long long)nchunks, (const uint64_t *)nullptr);
-    hipLaunchKernelGGL(hsk::k_jpeg_scan, dim3(1), dim3(hsk::kJpegScanLanes), 0, c->stream, a.cntRst, a.rstOff, (long long)nchunks, (const uint64_t *)nullptr);
-    hipLaunchKernelGGL(hsk::k_jpegd_clean<1>, dim3(gc), dim3(256), 0, c->stream, a);
-    if (!f.ri) {
-        const unsigned gs = nsubCap / hsk::kJpegdGroup;
-        hipLaunchKernelGGL(hsk::k_jpegd_sync, dim3(gs), dim3(hsk::kJpegdGroup), 0, c->stream, a);
-        hipLaunchKernelGGL(hsk::k_jpegd_repair, dim3(1), dim3(hsk::kJpegdRepairLanes), 0, c->stream, a);
-        hipLaunchKernelGGL(hsk::k_jpeg_scan, dim3(1), dim3(hsk::kJpegScanLanes), 0, c->stream, a.cnt, a.base, (long long)nsubCap, (const uint64_t *)nullptr);
-        hipLaunchKernelGGL(hsk::k_jpegd_write, dim3(gs), dim3(256), 0, c->stream, a);
-    } else {
-        hipLaunchKernelGGL(hsk::k_jpegd_write_rst, dim3((a.nint + 255u) / 256u), dim3(256), 0, c->stream, a);
-    }
-    hipLaunchKernelGGL(hsk::k_jpegd_dc_gather, dim3(gb), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(hsk::k_jpeg_scan, dim3(1), dim3(hsk::kJpegScanLanes), 0, c->stream, a.diff, a.dcsum, (long long)f.nblocks, (const uint64_t *)nullptr);
-    hipLaunchKernelGGL(hsk::k_jpegd_blocks, dim3((unsigned)((f.nblocks + 31) / 32)), dim3(256), 0, c->stream, a);
-    const int wide = (((uintptr_t)d_pix | stride) & 3u) == 0;
-    hipLaunchKernelGGL(hsk::k_jpegd_pixels, dim3((f.W + 255) / 256, (f.H + 3) / 4), dim3(64, 4), 0, c->stream, a, d_pix, (long long)stride,
-                       order == HSFLOW_JPEG_ORDER_RGB ? 1 : 0, wide);
-    HS_HIP(c, hipGetLastError());
-    return HSFLOW_OK;
-}
-
-// Header, checks and the enqueue for one file of the context's size.
-int jpegd_one(hsflow_ctx *c, const uint8_t *file, size_t bytes, int order, uint8_t *d_pix, size_t stride, uint32_t *d_status)
-{
-    if (!file) return fail(c, HSFLOW_E_ARG, "null file pointer");
-    if (order != HSFLOW_JPEG_ORDER_BGR && order != HSFLOW_JPEG_ORDER_RGB) return fail(c, HSFLOW_E_ARG, "unknown pixel order");
-    hsjpegd::Frame f;
-    std::unique_ptr<hsjpegd::Tables> t(new (std::nothrow) hsjpegd::Tables);
-    if (!t) return fail(c, HSFLOW_E_OOM, "host allocation failed");
-    const char *why = "";
-    if (hsjpegd::parse(file, bytes, f, *t, &why)) return fail(c, HSFLOW_E_DATA, std::string("JPEG file: ") + why);
-    if (f.W != c->W || f.H != c->H) return fail(c, HSFLOW_E_SIZE, "the picture does not have the context's size");
-    if (stride < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
-    return enqueue_jpegd(c, file, f, *t, order, d_pix, stride, d_status);
-}
-
 // The status words of the decodes enqueued so far into page-locked memory, waited for.
 int jpegd_wait_status(hsflow_ctx *c, int words)
 {
@@ -215,7 +106,7 @@ int jpegd_own(hsflow_ctx *c, int pictures)
     return HSFLOW_OK;
 }
 
-// ---- a batch of files ---------------------------------------------------------------------------------------------------
+// ---- chunks of files: the one decode path ------------------------------------------------------------------------------
 
 // The headers of n files of the context's size, before anything is enqueued.  An error names the file's index.
 int jpegd_batch_parse(hsflow_ctx *c, const uint8_t *const *files, const size_t *bytes, int n, std::vector<hsjpegd::Frame> &fr,
@@ -237,27 +128,27 @@ int jpegd_batch_parse(hsflow_ctx *c, const uint8_t *const *files, const size_t *
     return HSFLOW_OK;
 }
 
-// All of a batch's decodes, enqueued on c's stream chunk after chunk: per chunk one copy, three memsets and one set of
-// launches (hs_kernels_jpegd.hip.h).  The caller has checked every argument and parsed every header.
-int enqueue_jpegd_batch(hsflow_ctx *c, const uint8_t *const *files, const std::vector<hsjpegd::Frame> &fr, const std::vector<hsjpegd::Tables> &tabs,
-                        int order, void *const *d_pix, size_t stride, uint32_t *d_status)
+// n files' decodes, enqueued on c's stream chunk after chunk of at most max_batch: per chunk one copy, three memsets and
+// one set of launches (hs_kernels_jpegd.hip.h).  The caller has checked every argument and parsed every header.
+int enqueue_jpegd_batch(hsflow_ctx *c, const uint8_t *const *files, const hsjpegd::Frame *fr, const hsjpegd::Tables *tabs, int n, int max_batch, int order,
+                        void *const *d_pix, size_t stride, uint32_t *d_status)
 {
     hsflow_ctx::JpegdScratch &j = c->jpegd;
-    const int n = (int)fr.size(), S = jpegd_subseq_bits();
+    const int S = jpegd_subseq_bits();
     hsjpegd_plan::Plan plan;
     try {
         std::vector<hsjpegd_plan::FileIn> in((size_t)n);
-        for (int i = 0; i < n; i++) in[(size_t)i] = hsjpegd_plan::FileIn{fr[(size_t)i].scan_bytes, fr[(size_t)i].nblocks, (int64_t)fr[(size_t)i].mcux * fr[(size_t)i].mcuy, fr[(size_t)i].ri};
-        plan = hsjpegd_plan::layout(in.data(), n, hsjpegd_plan::Params{sizeof(hsjpegd::Tables), sizeof(hsk::JpegdBatchRec), (uint32_t)S, jpegd_batch_max()});
+        for (int i = 0; i < n; i++) in[(size_t)i] = hsjpegd_plan::FileIn{fr[i].scan_bytes, fr[i].nblocks, (int64_t)fr[i].mcux * fr[i].mcuy, fr[i].ri};
+        plan = hsjpegd_plan::layout(in.data(), n, hsjpegd_plan::Params{sizeof(hsjpegd::Tables), sizeof(hsk::JpegdBatchRec), (uint32_t)S, max_batch});
     } catch (const std::bad_alloc &) { return fail(c, HSFLOW_E_OOM, "host allocation failed"); }
-    if (c->jpegd_batch.batch_bytes < plan.device_bytes) { // (what is in flight still reads the old one)
+    if (j.bytes < plan.device_bytes) { // (what is in flight still reads the old one)
         HS_HIP(c, hipStreamSynchronize(c->stream));
-        hipFree(c->jpegd_batch.batch_base);
-        c->jpegd_batch.batch_base = nullptr; c->jpegd_batch.batch_bytes = 0;
-        HS_HIP(c, hipMalloc(&c->jpegd_batch.batch_base, plan.device_bytes));
-        c->jpegd_batch.batch_bytes = plan.device_bytes;
+        hipFree(j.base);
+        j.base = nullptr; j.bytes = 0;
+        HS_HIP(c, hipMalloc(&j.base, plan.device_bytes));
+        j.bytes = plan.device_bytes;
     }
-    uint8_t *p = (uint8_t *)c->jpegd_batch.batch_base;
+    uint8_t *p = (uint8_t *)j.base;
     const int rgb = order == HSFLOW_JPEG_ORDER_RGB ? 1 : 0;
     for (const hsjpegd_plan::Chunk &ch : plan.chunks) {
         int slot = 0;
@@ -268,8 +159,8 @@ int enqueue_jpegd_batch(hsflow_ctx *c, const uint8_t *const *files, const std::v
         for (int k = 0; k < ch.count; k++) {
             const int i = ch.first + k;
             const hsjpegd_plan::FileOut &o = plan.files[(size_t)i];
-            const hsjpegd::Frame &f = fr[(size_t)i];
-            std::memcpy(h + o.o_tab, &tabs[(size_t)i], sizeof(hsjpegd::Tables));
+            const hsjpegd::Frame &f = fr[i];
+            std::memcpy(h + o.o_tab, &tabs[i], sizeof(hsjpegd::Tables));
             std::memcpy(h + o.o_scan, files[i] + f.scan_offset, o.n);
             std::memset(h + o.o_scan + o.n, 0, o.scan_span - o.n);
             hsk::JpegdBatchRec &r = recs[k];
@@ -291,7 +182,7 @@ int enqueue_jpegd_batch(hsflow_ctx *c, const uint8_t *const *files, const std::v
             r.pix = (uint8_t *)d_pix[i];
             r.stride = (long long)stride;
             r.rgb = rgb;
-            r.wide = (((uintptr_t)d_pix[i] | stride) & 3u) == 0;
+            r.wide = word_aligned(d_pix[i], stride);
         }
         HS_HIP(c, hipMemcpyAsync(p, h, ch.in_bytes, hipMemcpyHostToDevice, c->stream));
         HS_HIP(c, hipEventRecord(j.evStage[slot], c->stream));
@@ -332,7 +223,25 @@ int jpegd_batch(hsflow_ctx *c, const uint8_t *const *files, const size_t *bytes,
     if (st) return st;
     for (int i = 0; i < n; i++)
         if (!d_pix[i]) return fail(c, HSFLOW_E_ARG, "file " + std::to_string(i) + ": null picture pointer");
-    return enqueue_jpegd_batch(c, files, fr, tabs, order, d_pix, stride, d_status);
+    return enqueue_jpegd_batch(c, files, fr.data(), tabs.data(), n, jpegd_batch_max(), order, d_pix, stride, d_status);
+}
+
+// Header, checks and the enqueue for one file of the context's size: a chunk of one, which is never cut -- the batch
+// maximum does not enter.  Its messages name no position in a list.
+int jpegd_one(hsflow_ctx *c, const uint8_t *file, size_t bytes, int order, uint8_t *d_pix, size_t stride, uint32_t *d_status)
+{
+    if (!file) return fail(c, HSFLOW_E_ARG, "null file pointer");
+    if (order != HSFLOW_JPEG_ORDER_BGR && order != HSFLOW_JPEG_ORDER_RGB) return fail(c, HSFLOW_E_ARG, "unknown pixel order");
+    hsjpegd::Frame f;
+    std::unique_ptr<hsjpegd::Tables> t(new (std::nothrow) hsjpegd::Tables);
+    if (!t) return fail(c, HSFLOW_E_OOM, "host allocation failed");
+    const char *why = "";
+    if (hsjpegd::parse(file, bytes, f, *t, &why)) return fail(c, HSFLOW_E_DATA, std::string("JPEG file: ") + why);
+    if (f.W != c->W || f.H != c->H) return fail(c, HSFLOW_E_SIZE, "the picture does not have the context's size");
+    if (stride < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
+    if (!jpegd_subseq_bits()) return fail(c, HSFLOW_E_ARG, "HSFLOW_JPEGD_SUBSEQ_BITS must be a multiple of 32 in 32 .. 4096");
+    void *pix = d_pix;
+    return enqueue_jpegd_batch(c, &file, &f, t.get(), 1, 1, order, &pix, stride, d_status);
 }
 
 } // namespace
@@ -458,28 +367,28 @@ int hsflow_set_sequence_jpeg(hsflow_ctx *c, int first_pair, const uint8_t *const
     if (first_pair < 0 || (long long)first_pair + n_files - 1 > c->N) return fail(c, HSFLOW_E_ARG, "the sequence's pairs exceed the context's");
     if ((st = settle_pending(c))) return st; // (before the all-or-nothing part: an owed check belongs to the frames that are there)
     hsflow_ctx::JpegdScratch &j = c->jpegd;
-    const size_t rowb = (size_t)c->W * 3, pic = up256(rowb * (size_t)c->H), words = up256((size_t)n_files * 4), want = words + pic * (size_t)n_files;
-    if (c->jpegd_batch.seq_bytes < want) { // (synchronous: nothing in flight uses the old one)
+    const size_t rowb = (size_t)c->W * 3, pic = hsjpegd_plan::up256(rowb * (size_t)c->H), words = hsjpegd_plan::up256((size_t)n_files * 4), want = words + pic * (size_t)n_files;
+    if (j.seq_bytes < want) { // (synchronous: nothing in flight uses the old one)
         HS_HIP(c, hipStreamSynchronize(c->stream));
-        hipFree(c->jpegd_batch.seq);
-        c->jpegd_batch.seq = nullptr; c->jpegd_batch.seq_bytes = 0;
-        HS_HIP(c, hipMalloc((void **)&c->jpegd_batch.seq, want));
-        c->jpegd_batch.seq_bytes = want;
+        hipFree(j.seq);
+        j.seq = nullptr; j.seq_bytes = 0;
+        HS_HIP(c, hipMalloc((void **)&j.seq, want));
+        j.seq_bytes = want;
     }
-    if (c->jpegd_batch.hSeq_words < n_files) {
-        if (c->jpegd_batch.hSeq) hipHostFree(c->jpegd_batch.hSeq);
-        c->jpegd_batch.hSeq = nullptr; c->jpegd_batch.hSeq_words = 0;
-        HS_HIP(c, hipHostMalloc((void **)&c->jpegd_batch.hSeq, (size_t)n_files * 4, hipHostMallocDefault));
-        c->jpegd_batch.hSeq_words = n_files;
+    if (j.hSeq_words < n_files) {
+        if (j.hSeq) hipHostFree(j.hSeq);
+        j.hSeq = nullptr; j.hSeq_words = 0;
+        HS_HIP(c, hipHostMalloc((void **)&j.hSeq, (size_t)n_files * 4, hipHostMallocDefault));
+        j.hSeq_words = n_files;
     }
     std::vector<void *> pix((size_t)n_files);
-    for (int i = 0; i < n_files; i++) pix[(size_t)i] = c->jpegd_batch.seq + words + pic * (size_t)i;
-    if ((st = jpegd_batch(c, files, bytes, n_files, HSFLOW_JPEG_ORDER_BGR, pix.data(), rowb, (uint32_t *)c->jpegd_batch.seq))) return st;
-    HS_HIP(c, hipMemcpyAsync(c->jpegd_batch.hSeq, c->jpegd_batch.seq, (size_t)n_files * 4, hipMemcpyDeviceToHost, c->stream));
+    for (int i = 0; i < n_files; i++) pix[(size_t)i] = j.seq + words + pic * (size_t)i;
+    if ((st = jpegd_batch(c, files, bytes, n_files, HSFLOW_JPEG_ORDER_BGR, pix.data(), rowb, (uint32_t *)j.seq))) return st;
+    HS_HIP(c, hipMemcpyAsync(j.hSeq, j.seq, (size_t)n_files * 4, hipMemcpyDeviceToHost, c->stream));
     HS_HIP(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n_files; i++)
-        if (c->jpegd_batch.hSeq[i])
-            return fail(c, HSFLOW_E_DATA, "file " + std::to_string(i) + (c->jpegd_batch.hSeq[i] == 2 ? ": JPEG file: truncated entropy-coded data" : ": JPEG file: corrupt entropy-coded data"));
+        if (j.hSeq[i])
+            return fail(c, HSFLOW_E_DATA, "file " + std::to_string(i) + (j.hSeq[i] == 2 ? ": JPEG file: truncated entropy-coded data" : ": JPEG file: corrupt entropy-coded data"));
     for (int k = 0; k + 1 < n_files; k++)
         if ((st = hsflow_set_frames_device_ex(c, first_pair + k, blur3x3 ? HSFLOW_FRAMES_BGR8_BLUR : HSFLOW_FRAMES_BGR8, pix[(size_t)k], rowb, pix[(size_t)k + 1], rowb)))
             return st;
@@ -500,9 +409,9 @@ int hsflow_set_frames_jpeg_async(hsflow_ctx *c, int pair, const uint8_t *prev, s
     void *pix[2] = {j.bgr[0], j.bgr[1]};
     if ((st = jpegd_batch(c, files, bytes, 2, HSFLOW_JPEG_ORDER_BGR, pix, rowb, dPair))) return st;
     HS_HIP(c, hipMemcpyAsync(j.hStatus + 2, dPair, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (!c->jpegd_batch.evPair) HS_HIP(c, hipEventCreateWithFlags(&c->jpegd_batch.evPair, hipEventDisableTiming));
-    HS_HIP(c, hipEventRecord(c->jpegd_batch.evPair, c->stream));
-    c->jpegd_batch.pair_status_owed = true;
+    if (!j.evPair) HS_HIP(c, hipEventCreateWithFlags(&j.evPair, hipEventDisableTiming));
+    HS_HIP(c, hipEventRecord(j.evPair, c->stream));
+    j.pair_status_owed = true;
     return hsflow_set_frames_device_ex(c, pair, blur3x3 ? HSFLOW_FRAMES_BGR8_BLUR : HSFLOW_FRAMES_BGR8, j.bgr[0], rowb, j.bgr[1], rowb);
 }
 
@@ -511,9 +420,9 @@ int hsflow_jpeg_async_status(hsflow_ctx *c)
     int st = check_ctx(c, 0);
     if (st) return st;
     hsflow_ctx::JpegdScratch &j = c->jpegd;
-    if (!c->jpegd_batch.pair_status_owed) return fail(c, HSFLOW_E_STATE, "no hsflow_set_frames_jpeg_async whose status has not been asked for yet");
-    HS_HIP(c, hipEventSynchronize(c->jpegd_batch.evPair));
-    c->jpegd_batch.pair_status_owed = false; // one answer per call
+    if (!j.pair_status_owed) return fail(c, HSFLOW_E_STATE, "no hsflow_set_frames_jpeg_async whose status has not been asked for yet");
+    HS_HIP(c, hipEventSynchronize(j.evPair));
+    j.pair_status_owed = false; // one answer per call
     for (int i = 0; i < 2; i++)
         if (j.hStatus[2 + i])
             return fail(c, HSFLOW_E_DATA, "file " + std::to_string(i) + (j.hStatus[2 + i] == 2 ? ": JPEG file: truncated entropy-coded data" : ": JPEG file: corrupt entropy-coded data"));

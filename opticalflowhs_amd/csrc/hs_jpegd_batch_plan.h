@@ -1,6 +1,6 @@
 // hs_jpegd_batch_plan.h -- where everything of a batch of JPEG files lies in the context's one device allocation and
-// one staging area, how large the grids are, and how the batch is cut into chunks (hsflow_jpeg_decode_batch_device,
-// hs_jpegd.hip.h).  Plain C++, no HIP: tests/jpegd_batch_plan_main.cpp compiles it alone.
+// one staging area, how large the grids are, and how the batch is cut into chunks (enqueue_jpegd_batch, hs_jpegd.hip.h:
+// every decode, single or batched).  Plain C++, no HIP: tests/jpegd_batch_plan_main.cpp compiles it alone.
 //
 // A chunk is at most `max_batch` consecutive files, decoded by one set of launches.  Its allocation, from offset 0:
 //   [ input: per file the tables and the stuffed segment, then the chunk's records ]   one copy from staging
@@ -8,8 +8,7 @@
 //   [ the files' coefficient buffers ]                                                   one memset
 //   [ per file: chunk counts and offsets, subsequence states, planes, DC sums, restart positions ]
 // Every range starts at a multiple of 256 bytes.  Chunks follow each other on one stream, so every chunk starts at 0
-// again.  A file's ranges are sized by the formulas of the single-file path (enqueue_jpegd): with one file the input and
-// per-length sizes are that path's own.
+// again.  A single decode is the layout of one file with a maximum of 1: the batch maximum does not reach it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

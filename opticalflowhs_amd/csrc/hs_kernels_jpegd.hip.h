@@ -3,31 +3,32 @@
 // HSOpticalFlowOpenCL.cpp:721,732).  The arithmetic is hs_jpegd_rule.h's, shared with the host twin; this file is the
 // data movement around it.  Nothing crosses to the host between the first and the last launch, every grid is sized from
 // the header, no kernel waits on another workgroup, and the pixels do not depend on the order of execution:
-//   k_jpegd_clean<0> one lane per 128-byte chunk of the segment: the bytes byte_class drops, the RSTn markers
-//   k_jpeg_scan      (hs_kernels_jpeg.hip.h) twice: where a chunk's kept bytes go, which marker is its first
-//   k_jpegd_clean<1> the clean stream (zero behind its end), and the byte each restart interval starts at
+//   k_jpegd_clean_batch<0> one lane per 128-byte chunk of the segment: the bytes byte_class drops, the RSTn markers
+//   k_jpegd_scan_batch<0>  (jpeg_scan_body, hs_kernels_jpeg.hip.h) where a chunk's kept bytes go, which marker is its first
+//   k_jpegd_clean_batch<1> the clean stream (zero behind its end), and the byte each restart interval starts at
 // without restart intervals, the stream cut into subsequences of S bits, one lane each:
-//   k_jpegd_sync     256 subsequences per workgroup.  Round 0: every lane decodes from (its first bit, block 0, DC) to the
-//                    first symbol at or beyond its last bit and keeps its exit state in LDS; later rounds: a lane whose
+//   k_jpegd_sync_batch     256 subsequences per workgroup.  Round 0: every lane decodes from (its first bit, block 0, DC) to
+//                    the first symbol at or beyond its last bit and keeps its exit state in LDS; later rounds: a lane whose
 //                    predecessor's exit state is not what it started from starts again from that; until a round changes
 //                    nothing.  Afterwards a group is right if its first lane's start is.
-//   k_jpegd_repair   ONE workgroup, lane g for group g: from group g - 1's last exit state through its own subsequences
-//                    until it meets a stored start state it agrees with; rounds over __syncthreads until nothing changes.
-//                    Subsequence 0 starts from the true state, so round r leaves at least r + 1 groups right.
-//   k_jpeg_scan      the blocks that end in a subsequence -> the first block of each
-//   k_jpegd_write    one lane per subsequence from its now-true start state: coefficients into the zeroed int16 buffer,
-//                    DC as the difference; the only entropy pass that raises the status word
+//   k_jpegd_repair_batch   ONE workgroup per file, lane g for group g: from group g - 1's last exit state through its own
+//                    subsequences until it meets a stored start state it agrees with; rounds over __syncthreads until
+//                    nothing changes.  Subsequence 0 starts from the true state, so round r leaves at least r + 1 groups right.
+//   k_jpegd_scan_batch<2>  the blocks that end in a subsequence -> the first block of each
+//   k_jpegd_write_batch    one lane per subsequence from its now-true start state: coefficients into the zeroed int16
+//                    buffer, DC as the difference; the only entropy pass that raises the status word
 // with them:
-//   k_jpegd_write_rst one lane per interval: start bit, first block and DC reset are known
+//   k_jpegd_write_rst_batch one lane per interval: start bit, first block and DC reset are known
 // then for both:
-//   k_jpegd_dc_gather + k_jpeg_scan  the DC differences by component in stream order, their prefix sums (mod 2^32)
-//   k_jpegd_blocks   eight lanes per block: dequantise, column pass in registers, transpose through LDS (row stride 9),
+//   k_jpegd_dc_gather_batch + k_jpegd_scan_batch<3>  the DC differences by component in stream order, their prefix sums
+//                    (mod 2^32)
+//   k_jpegd_blocks_batch   eight lanes per block: dequantise, column pass in registers, transpose through LDS (row stride 9),
 //                    row pass, + 128, clamp, 8 bytes per lane into the component planes padded to whole MCUs
-//   k_jpegd_pixels   one lane per four pixels: upsample, convert, three words (or twelve bytes) out
+//   k_jpegd_pixels_batch   one lane per four pixels: upsample, convert, three words (or twelve bytes) out
 // Huffman look-ups: the file's tables in look-up form (5.9 KB) are copied into LDS by every kernel that decodes symbols.
-// Every kernel's work for one file is a __device__ body; the __global__ entries above hand it their by-value arguments,
-// the *_batch entries at the end of this file a record read from device memory, the file picked by the grid's y or z:
-// n files by one set of launches (hsflow_jpeg_decode_batch_device), each workgroup with its own file's tables in LDS.
+// Every kernel's work for one file is a __device__ body; the __global__ entries at the end of this file hand it a record
+// read from device memory, the file picked by the grid's y or z: the files of a chunk by one set of launches, each
+// workgroup with its own file's tables in LDS.  A single decode is a chunk of one file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,10 +37,10 @@
 
 namespace hsk {
 
-constexpr int kJpegdGroup = 256;      // subsequences per workgroup of k_jpegd_sync
+constexpr int kJpegdGroup = 256;      // subsequences per workgroup of k_jpegd_sync_batch
 constexpr int kJpegdRepairLanes = 1024;
 
-// What every kernel of one decode is handed by value.
+// What every kernel body is handed of one file.
 struct JpegdArgs {
     hsjpegd::Frame f;
     const hsjpegd::Tables *tab;
@@ -93,12 +94,6 @@ __device__ __forceinline__ void jpegd_clean_body(const JpegdArgs &a, const uint3
     if (MODE == 0) { a.cntRem[c] = dropped; a.cntRst[c] = markers; }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void k_jpegd_clean(JpegdArgs a)
-{
-    jpegd_clean_body<MODE>(a, blockIdx.x);
-}
-
 // Grid: nsubCap / 256 workgroups of 256.
 __device__ __forceinline__ void jpegd_sync_body(const JpegdArgs &a, const uint32_t bx)
 {
@@ -134,11 +129,6 @@ __device__ __forceinline__ void jpegd_sync_body(const JpegdArgs &a, const uint32
     a.cnt[i] = active ? nb : 0u;
 }
 
-__global__ __launch_bounds__(kJpegdGroup) void k_jpegd_sync(JpegdArgs a)
-{
-    jpegd_sync_body(a, blockIdx.x);
-}
-
 // Grid: ONE workgroup of kJpegdRepairLanes.
 __device__ __forceinline__ void jpegd_repair_body(const JpegdArgs &a)
 {
@@ -166,11 +156,6 @@ __device__ __forceinline__ void jpegd_repair_body(const JpegdArgs &a)
     }
 }
 
-__global__ __launch_bounds__(kJpegdRepairLanes) void k_jpegd_repair(JpegdArgs a)
-{
-    jpegd_repair_body(a);
-}
-
 // Grid: nsubCap / 256 workgroups of 256.
 __device__ __forceinline__ void jpegd_write_body(const JpegdArgs &a, const uint32_t bx)
 {
@@ -185,11 +170,6 @@ __device__ __forceinline__ void jpegd_write_body(const JpegdArgs &a, const uint3
     int st = hsjpegd::decode_stretch(sTab, a.f, a.clean, end, s, (i + 1u) * a.S, a.f.nblocks, sink);
     if (i == nsub - 1u && sink.block < a.f.nblocks) st = hsjpegd::kStatusTruncated;
     if (st) atomicMax(a.status, (uint32_t)st);
-}
-
-__global__ __launch_bounds__(256) void k_jpegd_write(JpegdArgs a)
-{
-    jpegd_write_body(a, blockIdx.x);
 }
 
 // Grid: ceil(nint / 256) workgroups of 256.  (hsjpegd::entropy_host's loop body, one interval per lane.)
@@ -214,11 +194,6 @@ __device__ __forceinline__ void jpegd_write_rst_body(const JpegdArgs &a, const u
     if (st) atomicMax(a.status, (uint32_t)st);
 }
 
-__global__ __launch_bounds__(256) void k_jpegd_write_rst(JpegdArgs a)
-{
-    jpegd_write_rst_body(a, blockIdx.x);
-}
-
 // Block j of the component-after-component order: its component, MCU, place in the MCU and stream block.
 struct JpegdBlockAt {
     int c, s, h, v;
@@ -239,11 +214,6 @@ __device__ __forceinline__ void jpegd_dc_gather_body(const JpegdArgs &a, const u
     const int64_t j = (int64_t)bx * 256 + threadIdx.x;
     if (j >= a.f.nblocks) return;
     a.diff[j] = (uint32_t)(int32_t)a.coef[jpegd_block_at(a.f, j).B * 64];
-}
-
-__global__ __launch_bounds__(256) void k_jpegd_dc_gather(JpegdArgs a)
-{
-    jpegd_dc_gather_body(a, blockIdx.x);
 }
 
 // Grid: ceil(nblocks / 32) workgroups of 256: eight lanes per block.
@@ -289,11 +259,6 @@ __device__ __forceinline__ void jpegd_blocks_body(const JpegdArgs &a, const uint
     if (bad) atomicMax(a.status, (uint32_t)hsjpegd::kStatusCorrupt);
 }
 
-__global__ __launch_bounds__(256) void k_jpegd_blocks(JpegdArgs a)
-{
-    jpegd_blocks_body(a, blockIdx.x);
-}
-
 // pix: W x H pixels of 3 bytes, rows `stride` apart; rgb != 0: R first, else B first.  wide != 0: pix and stride are
 // multiples of 4.  Grid: (ceil(W / 256), ceil(H / 4)), block (64, 4).
 __device__ __forceinline__ void jpegd_pixels_body(const JpegdArgs &a, uint8_t *__restrict__ pix, long long stride, int rgb, int wide)
@@ -326,16 +291,11 @@ __device__ __forceinline__ void jpegd_pixels_body(const JpegdArgs &a, uint8_t *_
     }
 }
 
-__global__ __launch_bounds__(256) void k_jpegd_pixels(JpegdArgs a, uint8_t *__restrict__ pix, long long stride, int rgb, int wide)
-{
-    jpegd_pixels_body(a, pix, stride, rgb, wide);
-}
-
-// ---- a batch of files by the same launches ---------------------------------------------------------------------------
-// One record per file in device memory; the file is the grid's y (pixels: z).  Every grid is sized for the batch's
+// ---- the entries: a chunk of files by the same launches ---------------------------------------------------------------
+// One record per file in device memory; the file is the grid's y (pixels: z).  Every grid is sized for the chunk's
 // largest file: a workgroup beyond its own file's extent, or of a file that takes the other route between clean and
-// dc_gather (restart intervals or not), reads its record and returns -- before any LDS, barrier or store.  The bodies
-// are the single-file kernels' own, so a file's pixels are theirs whatever lies beside it.
+// dc_gather (restart intervals or not), reads its record and returns -- before any LDS, barrier or store.  A body sees
+// its own file's record alone, so a file's pixels are the same whatever lies beside it.
 struct JpegdBatchRec {
     JpegdArgs a;
     uint8_t *pix;      // where k_jpegd_pixels_batch puts this file's picture

@@ -37,7 +37,7 @@ int enqueue_render(hsflow_ctx *c, int pair, const hsflow_render_params &rp, uint
     hipLaunchKernelGGL(hsk::k_render_scatter, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->dU[c->cur] + pair * c->plane,
                        c->dV[c->cur] + pair * c->plane, c->dPrio, c->W, c->H, c->P, c->P, rp.step, gx, n, rp.threshold, rp.scale);
     HS_HIP(c, hipGetLastError());
-    const int wide = (((uintptr_t)d_rgb | stride) & 3u) == 0;
+    const int wide = word_aligned(d_rgb, stride);
     const dim3 grid((c->W + 1023) / 1024, c->H < 65535 ? c->H : 65535);
     hipLaunchKernelGGL(hsk::k_render_resolve, grid, dim3(256), 0, c->stream, c->dPrio, d_rgb, (long long)stride, c->W, c->H, c->P, dot, line, wide);
     HS_HIP(c, hipGetLastError());
@@ -163,7 +163,7 @@ int hsflow_render_flow_batch_device(hsflow_ctx *c, int first_pair, int n, const 
         hsk::RenderBatchPics pics{};
         for (int k = 0; k < cnt; k++) {
             pics.rgb[k] = (uint8_t *)d_rgb[first + k];
-            if ((((uintptr_t)d_rgb[first + k] | stride) & 3u) == 0) pics.wide |= 1u << k;
+            if (word_aligned(d_rgb[first + k], stride)) pics.wide |= 1u << k;
         }
         if ((st = enqueue_render_chunk(c, first_pair + first, cnt, *rp, pics, stride))) return st;
     }

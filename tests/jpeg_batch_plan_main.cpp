@@ -103,6 +103,15 @@ int main(int argc, char **argv)
             if (check_layout(wh.first, wh.second, n)) return 1;                   // ... and the layout is sound for any count
             layouts += 2;
         }
+    for (const auto &wh : sizes) { // a batch of one with a maximum of 1: one slice, the one chunk (0, 1)
+        if (check_layout(wh.first, wh.second, 1)) return 1;
+        layouts++;
+    }
+    {
+        if (check_chunks(1, 1)) return 1;
+        const std::vector<Chunk> one = chunks(1, 1);
+        if (one.size() != 1 || one[0].first != 0 || one[0].count != 1) { std::printf("FAILED: chunks(1, 1)\n"); return 1; }
+    }
     for (int n = 1; n <= 3 * maxb; n++)
         for (int m = 1; m <= maxb; m++)
             if (check_chunks(n, m)) return 1;

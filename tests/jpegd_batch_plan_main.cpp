@@ -4,7 +4,8 @@
 //   every per-file range is 256-aligned, inside the chunk's total and disjoint from every other of its chunk;
 //   chunks cover the batch in order, none above the maximum;
 //   grid extents equal the per-file maxima;
-//   one file reproduces the sizes the single-file path (enqueue_jpegd, hs_jpegd.hip.h) computes.
+//   one file reproduces the sizes of the single-file formulas, written out below;
+//   one file with a maximum of 1 -- how hs_jpegd.hip.h lays out every single decode -- passes all of the above.
 #include "hs_jpegd_batch_plan.h"
 
 #include <algorithm>
@@ -46,7 +47,7 @@ static int check(const std::vector<FileIn> &in, uint32_t S, int maxb)
             const FileIn &fi = in[(size_t)(c.first + k)];
             const FileOut &f = pl.files[(size_t)(c.first + k)];
             const size_t nb = (size_t)fi.nblocks;
-            // today's formulas (enqueue_jpegd), written out
+            // the single-file formulas, written out
             const uint32_t nbytes = (uint32_t)fi.scan_bytes, nchunks = (nbytes + 127) / 128;
             const uint32_t nsubCap = (uint32_t)((((uint64_t)nbytes * 8u + S - 1u) / S + 255u) / 256u * 256u) + (nbytes ? 0u : 256u);
             const uint32_t nint = fi.restart_interval ? (uint32_t)((fi.nmcu + fi.restart_interval - 1) / fi.restart_interval) : 0u;
@@ -113,6 +114,10 @@ int main(int argc, char **argv)
     for (uint32_t S : Ss) {
         g_batch = batches++;
         if (check({file(0)}, S, maxb)) return 1;
+        for (uint64_t bytes : {0ull, 1ull, 127ull, 128ull, 700ull, 20000ull, 600000ull}) { // a single decode: n = 1, maximum 1
+            g_batch = batches++;
+            if (check({file(bytes)}, S, 1)) return 1;
+        }
         g_batch = batches++;
         if (check({file(700), file(0), file(1), file(0)}, S, maxb)) return 1;
         for (int n : {maxb, maxb + 1, 2 * maxb + 1}) {

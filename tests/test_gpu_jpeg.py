@@ -117,6 +117,7 @@ def test_capacity_on_the_device(hs, gpu_ok):
         assert f(ctx._h, tp, 3 * W, 95, op, bound, None) == E_ARG
         assert f(ctx._h, tp, 3 * W, 95, op, bound, ctypes.c_void_p(n.data_ptr() + 4)) == E_ARG          # not 8-byte aligned
         assert f(ctx._h, tp, 3 * W - 1, 95, op, bound, sp) == E_SIZE and b"stride" in L.hsflow_last_error(ctx._h)
+        assert b"picture 0" not in L.hsflow_last_error(ctx._h) and b"file 0" not in L.hsflow_last_error(ctx._h)
         rp = hs.make_render_params("cv")
         host = np.zeros(bound, np.uint8)
         hn = ctypes.c_size_t()
@@ -124,6 +125,8 @@ def test_capacity_on_the_device(hs, gpu_ok):
         assert g(ctx._h, 0, ctypes.byref(rp), 95, hp, bound, ctypes.byref(hn)) == OK and hn.value > 625
         need = hn.value
         assert g(ctx._h, 0, ctypes.byref(rp), 95, hp, need - 1, ctypes.byref(hn)) == E_SIZE and hn.value == need
+        msg = L.hsflow_last_error(ctx._h)
+        assert b"smaller than the file" in msg and b"picture 0" not in msg and b"file 0" not in msg, msg
         assert g(ctx._h, 0, ctypes.byref(rp), 95, hp, need, ctypes.byref(hn)) == OK and hn.value == need
         assert g(ctx._h, 0, ctypes.byref(rp), 0, hp, bound, ctypes.byref(hn)) == E_ARG
         assert g(ctx._h, 1, ctypes.byref(rp), 95, hp, bound, ctypes.byref(hn)) == E_ARG                  # bad pair
@@ -323,3 +326,51 @@ def test_render_jpeg_behind_an_asynchronous_solve(hs, gpu_ok):
         assert L.hsflow_wait_solve(ctx._h) == OK
         assert s.query(), "wait_solve returned while an encode was still in flight"
         assert out[:int(n.item())].cpu().numpy().tobytes() == want
+
+
+# ---- 8. the single entries and the batch maximum ------------------------------------------------------------------------
+
+def test_single_entries_ignore_the_batch_maximum(hs, gpu_ok, monkeypatch):
+    """A single picture is never cut into chunks: an unusable HSFLOW_JPEG_BATCH_MAX in the environment stops the batch
+    entries (E_ARG, naming the variable) and nothing else."""
+    import torch
+    L = hs._lib.load()
+    W, H = 17, 15
+    ENV_MAX = "HSFLOW_JPEG_BATCH_MAX"
+    arr = jpeg_pictures.picture("noise", W, H, 7 * W + H)
+    rng = np.random.default_rng(17)
+    u, v = (rng.uniform(-6, 6, (H, W)).astype(np.float32) for _ in range(2))
+    drawn = refpics.render(u, v, "cv")
+    assert (drawn != 0).any()
+    want_pic, want_drawn = hs.encode_jpeg(arr, 95), hs.encode_jpeg(drawn, 95)
+    bound = hs.jpeg_bound(W, H)
+    rp = hs.make_render_params("cv")
+    monkeypatch.setenv(ENV_MAX, "0")
+    with hs.HSFlow(W, H, own_stream=True) as ctx:
+        ud, vd = torch.from_numpy(u).cuda(), torch.from_numpy(v).cuda()
+        t = torch.from_numpy(np.ascontiguousarray(arr)).cuda()
+        out = torch.full((2, bound), 0xA5, dtype=torch.uint8, device="cuda")
+        n = torch.zeros(2, dtype=torch.int64, device="cuda")
+        pic = torch.zeros((H, W, 3), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        ctx.set_flow_rows_from(ud, vd, 0, H)
+        assert L.hsflow_jpeg_encode_device(ctx._h, ctypes.c_void_p(t.data_ptr()), 3 * W, 95, ctypes.c_void_p(out[0].data_ptr()), bound,
+                                           ctypes.c_void_p(n.data_ptr())) == OK
+        assert L.hsflow_render_flow_jpeg_device(ctx._h, 0, ctypes.byref(rp), 95, ctypes.c_void_p(out[1].data_ptr()), bound,
+                                                ctypes.c_void_p(n.data_ptr() + 8)) == OK
+        ctx.synchronize()
+        sizes = n.cpu().tolist()
+        assert out[0, :sizes[0]].cpu().numpy().tobytes() == want_pic and out[1, :sizes[1]].cpu().numpy().tobytes() == want_drawn
+        assert ctx.render_jpeg("cv") == want_drawn                                   # hsflow_render_flow_jpeg
+        assert np.array_equal(ctx.render("cv"), drawn)                               # hsflow_render_flow
+        # the batch entries: stopped by the variable, before anything is enqueued
+        src, dst = (ctypes.c_void_p * 1)(t.data_ptr()), (ctypes.c_void_p * 1)(out[0].data_ptr())
+        words, pics = ctypes.c_void_p(n.data_ptr()), (ctypes.c_void_p * 1)(pic.data_ptr())
+        host = np.zeros(bound, np.uint8)
+        hp, hn = (ctypes.c_void_p * 1)(host.ctypes.data), (ctypes.c_size_t * 1)()
+        for call in (lambda: L.hsflow_jpeg_encode_batch_device(ctx._h, src, 1, 3 * W, 95, dst, bound, words),
+                     lambda: L.hsflow_render_flow_batch_device(ctx._h, 0, 1, ctypes.byref(rp), pics, 3 * W),
+                     lambda: L.hsflow_render_flow_jpeg_batch_device(ctx._h, 0, 1, ctypes.byref(rp), 95, dst, bound, words),
+                     lambda: L.hsflow_render_flow_jpeg_batch(ctx._h, 0, 1, ctypes.byref(rp), 95, hp, bound, hn)):
+            assert call() == E_ARG
+            assert ENV_MAX.encode() in L.hsflow_last_error(ctx._h)

@@ -245,6 +245,40 @@ def test_back_to_back_without_synchronisation(hs, gpu_ok):
         assert ctx.encode_jpeg(done, 95) == hs.encode_jpeg(one, 95)
 
 
+def test_single_and_batch_share_one_scratch(hs, gpu_ok):
+    """On a fresh context, nothing waited for in between: a single encode, a batch of three (the batched scratch grown), a
+    single render-and-encode, a batch of two pairs.  Whatever scratch the two forms share or keep apart: a layout computed
+    for another number of pictures than an allocation holds would put one picture's ranges over another's."""
+    import torch
+    L = hs._lib.load()
+    W, H = 64, 48
+    one = jpeg_pictures.picture("noise", W, H, 99)
+    three = pictures(W, H, 3, seed0=70)
+    rng = np.random.default_rng(64)
+    flows = [tuple(rng.uniform(-9, 9, (H, W)).astype(np.float32) for _ in range(2)) for _ in range(2)]
+    drawn = [refpics.render(u, v, "cv") for u, v in flows]
+    assert all((d != 0).any() for d in drawn) and not np.array_equal(drawn[0], drawn[1])
+    done, _ = device_picture_at(one, 0, 3 * W)
+    d3 = [device_picture_at(a, 0, 3 * W) for a in three]
+    dev_flows = [tuple(torch.from_numpy(x).cuda() for x in uv) for uv in flows]
+    bound = hs.jpeg_bound(W, H)
+    rp = hs.make_render_params("cv")
+    with hs.HSFlow(W, H, 2, own_stream=True) as ctx:
+        for p, (u, v) in enumerate(dev_flows):
+            ctx.set_flow_rows_from(u, v, 0, H, pair=p)
+        s1, s3, r1, r2 = Slots(1, bound), Slots(3, bound), Slots(1, bound), Slots(2, bound)
+        ctx.synchronize()           # the flows are there; no encode or render has run on this context yet
+        assert L.hsflow_jpeg_encode_device(ctx._h, vp(done.data_ptr()), 3 * W, 95, s1.ptrs[0], bound, vp(s1.words.data_ptr())) == OK
+        assert encode_batch(L, ctx, [v for v, _ in d3], 3 * W, 95, s3) == OK
+        assert L.hsflow_render_flow_jpeg_device(ctx._h, 1, ctypes.byref(rp), 95, r1.ptrs[0], bound, vp(r1.words.data_ptr())) == OK
+        assert L.hsflow_render_flow_jpeg_batch_device(ctx._h, 0, 2, ctypes.byref(rp), 95, r2.ptrs, bound, vp(r2.words.data_ptr())) == OK
+        ctx.synchronize()
+        s1.check([hs.encode_jpeg(one, 95)])
+        s3.check([hs.encode_jpeg(a, 95) for a in three])
+        r1.check([hs.encode_jpeg(drawn[1], 95)])
+        r2.check([hs.encode_jpeg(d, 95) for d in drawn])
+
+
 # ---- 7. render batch --------------------------------------------------------------------------------------------------
 
 def view_pointers(hs, ctx, pair):

@@ -110,6 +110,37 @@ def test_many_groups_and_repair_rounds(hs, gpu_ok):
                 ctx.jpeg_decode(blob)
 
 
+@pytest.mark.parametrize("value", ["0", "99"])
+def test_single_entries_ignore_the_batch_maximum(hs, gpu_ok, monkeypatch, value):
+    """A single file is never cut into chunks: an unusable HSFLOW_JPEGD_BATCH_MAX in the environment stops the batch
+    entry (E_ARG) and nothing else."""
+    import torch
+    name = "c17x9_420_q75_noise"
+    blob = jc.data(name)
+    W, H = 17, 9
+    monkeypatch.setenv("HSFLOW_JPEGD_BATCH_MAX", value)
+    with hs.HSFlow(W, H, own_stream=True) as ctx:
+        for order in (RGB, BGR):
+            want = host_pixels(hs, blob, order).reshape(H, 3 * W)
+            st, rows, _ = decode_sync(hs, ctx, blob, order)
+            assert st == OK and np.array_equal(rows, want), (order, ctx._lib.hsflow_last_error(ctx._h))
+            st, word, rows, _ = decode_device(hs, ctx, blob, order)
+            assert st == OK and word == 0 and np.array_equal(rows, want), order
+        ctx.set_frames_jpeg(blob, blob, blur=False)
+        gray = hs.preprocess_frame(hs.jpeg_decode_host(blob, "bgr"), "bgr")
+        a, b = ctx.frames()
+        assert np.array_equal(a, gray) and np.array_equal(b, gray)
+        buf = np.frombuffer(blob, np.uint8)
+        pic = torch.full((H, 3 * W), 0xA5, dtype=torch.uint8, device="cuda")
+        word = torch.full((1,), 77, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        files, sizes, pix = (ctypes.c_void_p * 1)(buf.ctypes.data), (ctypes.c_size_t * 1)(buf.size), (ctypes.c_void_p * 1)(pic.data_ptr())
+        assert ctx._lib.hsflow_jpeg_decode_batch_device(ctx._h, files, sizes, 1, RGB, pix, 3 * W, ctypes.c_void_p(word.data_ptr())) == jc.E_ARG
+        assert b"HSFLOW_JPEGD_BATCH_MAX" in ctx._lib.hsflow_last_error(ctx._h)
+        torch.cuda.synchronize()
+        assert int(word.item()) == 77 and bool((pic == 0xA5).all().item())
+
+
 # ---- 2. the reference's inputs ------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("pic", ["city", "bunny"])
@@ -151,6 +182,11 @@ def test_1080p_twice_over_the_scratch_of_a_longer_file(hs, gpu_ok):
 
 # ---- 3. broken streams ----------------------------------------------------------------------------------------------------
 
+def no_index(ctx):
+    """The single entries' messages name no position in a list."""
+    msg = ctx._lib.hsflow_last_error(ctx._h)
+    return b"file 0" not in msg and b"picture 0" not in msg
+
 def test_broken_streams(hs, gpu_ok):
     name = "c64x48_420_q95_noise"
     blob = jc.data(name)
@@ -168,15 +204,16 @@ def test_broken_streams(hs, gpu_ok):
                 assert (rows[:-1, 192:] == 0xA5).all() and (flat[:1] == 0xA5).all() and (flat[1 + 47 * 197 + 192:] == 0xA5).all()
                 st, rows, flat = decode_sync(hs, ctx, cut, RGB)
                 assert st == E_DATA and (flat == 0xA5).all() and b"truncated" in ctx._lib.hsflow_last_error(ctx._h)
+                assert no_index(ctx)
         with pytest.raises(hs.HsflowError) as e:
             ctx.set_frames_jpeg(blob, cut)
-        assert e.value.status == E_DATA
+        assert e.value.status == E_DATA and no_index(ctx)
         with pytest.raises(hs.HsflowError) as e:
             ctx.set_frames_jpeg(blob[:off // 2], blob)
-        assert e.value.status == E_DATA
+        assert e.value.status == E_DATA and no_index(ctx)
         with pytest.raises(hs.HsflowError) as e:
             ctx.push_frame_jpeg(cut)
-        assert e.value.status == E_DATA
+        assert e.value.status == E_DATA and no_index(ctx)
         a, b = ctx.frames()
         assert np.array_equal(a, A) and np.array_equal(b, B)
         ctx.solve(lam=1.0, max_iter=30, term_type=ITER)
@@ -199,7 +236,7 @@ def test_broken_streams(hs, gpu_ok):
         assert st == OK and word == 1
         assert (flat[8 * 24:] == 0xA5).all()
         st, rows, flat = decode_sync(hs, ctx, bad, BGR)
-        assert st == E_DATA and (flat == 0xA5).all() and b"corrupt" in ctx._lib.hsflow_last_error(ctx._h)
+        assert st == E_DATA and (flat == 0xA5).all() and b"corrupt" in ctx._lib.hsflow_last_error(ctx._h) and no_index(ctx)
         assert np.array_equal(ctx.jpeg_decode(jc.data("g8x8_q75_smooth")), jc.pil_pixels("g8x8_q75_smooth"))     # and the context still decodes
 
 

@@ -1,6 +1,7 @@
 """A batch of JPEG files decoded by one set of launches (include/hsflow.h: hsflow_jpeg_decode_batch_device,
 hsflow_set_sequence_jpeg, hsflow_pipeline_submit_jpeg; the batched kernels of csrc/hs_kernels_jpegd.hip.h) against the
-single-file path: hsflow_jpeg_decode_device of each file alone, which tests/test_gpu_jpegd.py pins to the host rule.
+host rule (hsflow_jpeg_decode_host) applied to each file alone, which tests/test_jpegd_host.py pins to PIL and to the
+committed fixtures and tests/test_gpu_jpegd.py pins the single device decode to.
 Pictures are compared as bytes, every one of them, and so is every byte around them."""
 import contextlib
 import ctypes
@@ -60,21 +61,12 @@ _single = {}
 
 
 def single(hs, data, order):
-    """hsflow_jpeg_decode_device of the file alone into tight rows: (H, 3W) bytes.  Computed once per file and order."""
+    """The file alone by the host rule (hsflow_jpeg_decode_host) as tight rows: (H, 3W) bytes.  Computed once per file and
+    order.  (The single device decode is a batch of one: it cannot be the oracle of the batch.)"""
     key = (data, order)
     if key not in _single:
-        import torch
         W, H = size_of(hs, data)
-        buf = np.frombuffer(data, np.uint8)
-        with hs.HSFlow(W, H, own_stream=True) as ctx:
-            pic = torch.full((H, 3 * W), 0xA5, dtype=torch.uint8, device="cuda")
-            word = torch.full((1,), 77, dtype=torch.int32, device="cuda")
-            torch.cuda.synchronize()
-            st = ctx._lib.hsflow_jpeg_decode_device(ctx._h, ctypes.c_void_p(buf.ctypes.data), buf.size, order, ctypes.c_void_p(pic.data_ptr()), 3 * W,
-                                                    ctypes.c_void_p(word.data_ptr()))
-            torch.cuda.synchronize()
-            assert st == OK and int(word.item()) == 0
-            got = pic.cpu().numpy()
+        got = np.ascontiguousarray(hs.jpeg_decode_host(data, "rgb" if order == RGB else "bgr")).reshape(H, 3 * W)
         got.setflags(write=False)
         _single[key] = got
     return _single[key]
