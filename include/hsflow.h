@@ -45,6 +45,10 @@
  *                                          route, :76,83 for the camera loop's frames): one set of launches per batch
  *   hsflow_set_sequence_jpeg ............ the same in front of a context of N pairs: N + 1 consecutive frames, each
  *                                          decoded once (the camera loop's cvQueryFrame at :76,83, fed with files)
+ *   hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host
+ *                                          the camera loop's whole frame handling (OpticalFlowOpenCV.cpp:76-93,118: gray,
+ *                                          blur of old and new in place, imgOld = imgNew) for N + 1 frames into a context
+ *                                          of N pairs: every frame read once, one launch per HSFLOW_PRE_SEQ_MAX frames
  *   hsflow_pipeline_submit_jpeg ......... the disk route's two cvLoadImage (:15,18) in front of a pipeline slot
  *   hsflow_verify ....................... HSOpticalFlowOpenCL::verifyResults (HSOpticalFlowOpenCL.cpp:894), the hook of
  *                                          SDKUtil/include/SDKApplication.hpp that the reference left a stub
@@ -67,7 +71,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 13 /* 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 14 /* 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -365,6 +369,46 @@ int hsflow_push_frame_device_ex(hsflow_ctx *ctx, int pair, int format, const voi
  * HSFLOW_E_ARG: null pointer, unknown format; HSFLOW_E_SIZE: non-positive size, a stride below the row's bytes. */
 int hsflow_preprocess_frame_host(int format, const uint8_t *src, size_t src_stride, int width, int height,
                                  uint8_t *dst, size_t dst_stride);
+
+/* A SEQUENCE of frames into consecutive pairs (ABI 0.14): the reference's camera loop (OpticalFlowOpenCV.cpp:76-93,118:
+ * cvQueryFrame, gray, cvSmooth of old and new IN PLACE, solve, imgOld = imgNew) in a context of N pairs.  With the
+ * frames f_0 .. f_{n-1}, p_j = pre(format, f_j) and B(x) = HSFLOW_FRAMES_GRAY8_BLUR of the BYTES of x (x's own edge
+ * pixels repeated -- the blur of the stored plane, not a wider filter over f_j), pair first_pair + k, 0 <= k <= n - 2,
+ * receives
+ *     curr = p_{k+1}
+ *     prev = p_k      without HSFLOW_SEQ_REBLUR, or for k == 0 without HSFLOW_SEQ_REBLUR_FIRST
+ *     prev = B(p_k)   otherwise
+ * HSFLOW_SEQ_REBLUR with a *_BLUR format is the reference's loop from its start: from the second pair on the old frame
+ * enters the solver blurred twice.  HSFLOW_SEQ_REBLUR | HSFLOW_SEQ_REBLUR_FIRST is the same loop continued -- f_0 was
+ * the new frame of an earlier pair already -- so a long clip goes through a context in consecutive batches that share
+ * one frame.  The planes are exactly those the one-pair entries write: with flags 0
+ * hsflow_set_frames_device_ex(format, f_k, f_{k+1}); for a reblurred pair hsflow_set_frames_device_ex(format, f_k, f_k)
+ * followed by hsflow_push_frame_device_ex(format, f_{k+1}, 1) -- which cost a pair three launches and three reads of a
+ * frame.  Here every frame is read ONCE, by one launch per chunk of at most HSFLOW_PRE_SEQ_MAX frames (the frame is a
+ * grid dimension; frames are independent, so chunks need no overlap), and leaves p_j and / or B(p_j) in up to two
+ * planes; nothing in between exists outside registers.  Measured on an MI355X, 9 resident BGR frames into 8 pairs,
+ * BGR8_BLUR, HIP events around 200 repetitions (profiles/pre_sequence_time.txt; the frames stay cache-resident between
+ * repetitions): 1080p 3.3 us per pair with flags 0 against 9.8 us for 8 x hsflow_set_frames_device_ex on the parent
+ * commit, 4.9 us with HSFLOW_SEQ_REBLUR against 20.7 us for the one-pair calls above; 600x480 1.9 us against 6.7 us and
+ * 1.9 us against 16.1 us. */
+#define HSFLOW_SEQ_REBLUR 1       /* prev of every pair but the call's first is blurred once more        */
+#define HSFLOW_SEQ_REBLUR_FIRST 2 /* ... and the call's first pair too (only together with HSFLOW_SEQ_REBLUR) */
+#define HSFLOW_PRE_SEQ_MAX 32 /* frames per launch (four pointers each in the kernel's argument block); the environment variable of the same name overrides it per call, 1..HSFLOW_PRE_SEQ_MAX */
+/* d_frames: a host array of n_frames pointers to frames resident on ctx's device, all in `format` with rows `stride`
+ * bytes apart, any alignment; the array is free on return.  Only enqueues on ctx's stream, settles an owed ITER|EPS
+ * check first like every frame entry, and writes into the planes the context has always had (cached graphs stay
+ * valid).  Every argument is checked before anything is enqueued; on any error no pair's frames change.
+ * HSFLOW_E_ARG: a null list or entry, unknown format, n_frames < 2, first_pair < 0, first_pair + n_frames - 1 > n_pairs,
+ * flags not 0, 1 or 3, HSFLOW_PRE_SEQ_MAX in the environment unusable; HSFLOW_E_SIZE: a stride below the row's bytes. */
+int hsflow_set_sequence_device_ex(hsflow_ctx *ctx, int first_pair, int format, const void *const *d_frames,
+                                  int n_frames, size_t stride, int flags);
+/* The rule on the host, no device needed: frames are n_frames host frames, prev and curr n_frames - 1 planes each of
+ * width x height bytes with rows dst_stride apart (the planes of the call's pairs).  It walks a frame the way the
+ * kernel does (csrc/hs_pre_rule.h, one definition for both), so the composition of the two borders can be checked on
+ * a CPU.  Sources and planes must not overlap.  HSFLOW_E_ARG: null list or entry, unknown format or flags,
+ * n_frames < 2; HSFLOW_E_SIZE: non-positive size, a stride below the row's bytes. */
+int hsflow_preprocess_sequence_host(int format, int flags, const uint8_t *const *frames, int n_frames, size_t stride,
+                                    int width, int height, uint8_t *const *prev, uint8_t *const *curr, size_t dst_stride);
 
 /* --- solve -------------------------------------------------------------------------------- */
 
@@ -699,10 +743,17 @@ int hsflow_jpeg_decode_batch_device(hsflow_ctx *ctx, const uint8_t *const *files
  * BGR8_BLUR), so its planes are those of hsflow_set_frames_jpeg(ctx, first_pair + k, file k, file k + 1, blur3x3).
  * Synchronous, and like every frame entry it settles an owed ITER|EPS check first.  All or nothing: on HSFLOW_E_DATA
  * (any file, header or bit stream), HSFLOW_E_SIZE and HSFLOW_E_ARG (first_pair + n_files - 1 > n_pairs, n_files < 2,
- * null entries) no pair's frames change.  The camera loop's double blur (reblur_prev) stays with
- * hsflow_push_frame_jpeg. */
+ * null entries) no pair's frames change.  The same as hsflow_set_sequence_jpeg_ex with flags 0. */
 int hsflow_set_sequence_jpeg(hsflow_ctx *ctx, int first_pair, const uint8_t *const *files, const size_t *bytes,
                              int n_files, int blur3x3);
+/* The same with the camera loop's frame handling (ABI 0.14; OpticalFlowOpenCV.cpp:76-93,118 fed with files): the batched
+ * decode into the context's BGR pictures, then hsflow_set_sequence_device_ex(BGR8 or BGR8_BLUR, flags) -- ONE launch
+ * per HSFLOW_PRE_SEQ_MAX frames where there were n_files - 1, every picture read once.  flags: 0, HSFLOW_SEQ_REBLUR or
+ * HSFLOW_SEQ_REBLUR | HSFLOW_SEQ_REBLUR_FIRST; a reblurred pair's planes are those of hsflow_set_frames_jpeg(file k,
+ * file k) + hsflow_push_frame_jpeg(file k + 1, blur3x3, 1).  Synchronous and all or nothing as above; also HSFLOW_E_ARG
+ * for unknown flags. */
+int hsflow_set_sequence_jpeg_ex(hsflow_ctx *ctx, int first_pair, const uint8_t *const *files, const size_t *bytes,
+                                int n_files, int blur3x3, int flags);
 /* hsflow_set_frames_jpeg without the wait, what hsflow_pipeline_submit_jpeg is made of: both headers are checked at
  * once (HSFLOW_E_DATA / _SIZE / _ARG: nothing enqueued, the frames unchanged); then the two files are decoded as a batch
  * of two into the context's BGR pictures, the two status words are copied to page-locked memory, and

@@ -20,6 +20,8 @@ JPEG_ORDER_BGR, JPEG_ORDER_RGB = 0, 1
 JPEGD_SUBSEQ_BITS = 1024  # HSFLOW_JPEGD_SUBSEQ_BITS
 JPEGD_BATCH_MAX = 32  # HSFLOW_JPEGD_BATCH_MAX
 JPEG_BATCH_MAX = 16  # HSFLOW_JPEG_BATCH_MAX
+SEQ_REBLUR, SEQ_REBLUR_FIRST = 1, 2  # HSFLOW_SEQ_*
+PRE_SEQ_MAX = 32  # HSFLOW_PRE_SEQ_MAX
 FRAME_FORMATS = {"gray": FRAMES_GRAY8, "gray_blur": FRAMES_GRAY8_BLUR, "bgr": FRAMES_BGR8, "bgr_blur": FRAMES_BGR8_BLUR}
 
 
@@ -157,6 +159,9 @@ PROTOTYPES = {
     "hsflow_push_frame_jpeg": (_i, [_vp, _i, _vp, _sz, _i, _i]),
     "hsflow_jpeg_decode_batch_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "hsflow_set_sequence_jpeg": (_i, [_vp, _i, _vp, _vp, _i, _i]),
+    "hsflow_set_sequence_jpeg_ex": (_i, [_vp, _i, _vp, _vp, _i, _i, _i]),
+    "hsflow_set_sequence_device_ex": (_i, [_vp, _i, _i, _vp, _i, _sz, _i]),
+    "hsflow_preprocess_sequence_host": (_i, [_i, _i, _vp, _i, _sz, _i, _i, _vp, _vp, _sz]),
     "hsflow_set_frames_jpeg_async": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _i]),
     "hsflow_jpeg_async_status": (_i, [_vp]),
     "hsflow_render_line_pixels": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i]),

@@ -7,6 +7,8 @@
 #include <cstring>
 #include <iostream>
 
+#include <hip/hip_runtime_api.h> // the batched "-cv -cam" route uploads its frames itself: hipMalloc / hipMemcpy / hipFree
+
 namespace {
 
 double now_ms()
@@ -46,11 +48,11 @@ bool verify_wanted()
 }
 
 // hsflow_verify of ctx's pair and its line; SDK_SUCCESS iff the report says ok.
-int verify_pair(hsflow_ctx *ctx, int W, hsflow_verify_report &report)
+int verify_pair(hsflow_ctx *ctx, int W, hsflow_verify_report &report, int pair = 0)
 {
     std::memset(&report, 0, sizeof(report));
     report.struct_size = sizeof(report);
-    const int st = hsflow_verify(ctx, 0, &report);
+    const int st = hsflow_verify(ctx, pair, &report);
     if (st != HSFLOW_OK) {
         std::cout << "Failed: " << hsflow_last_error(ctx) << std::endl;
         return SDK_FAILURE;
@@ -60,13 +62,13 @@ int verify_pair(hsflow_ctx *ctx, int W, hsflow_verify_report &report)
 }
 
 // The device route of both drawings: the picture of ctx's current flow into imgFlow.
-int draw_on_device(hsflow_ctx *ctx, int preset, int W, int H, pnm::Image &imgFlow)
+int draw_on_device(hsflow_ctx *ctx, int preset, int W, int H, pnm::Image &imgFlow, int pair = 0)
 {
     imgFlow.width = W; imgFlow.height = H; imgFlow.channels = 3;
     imgFlow.data.resize((size_t)W * H * 3);
     hsflow_render_params rp;
     hsflow_default_render_params(&rp, preset);
-    const int st = hsflow_render_flow(ctx, 0, &rp, imgFlow.data.data(), (size_t)W * 3);
+    const int st = hsflow_render_flow(ctx, pair, &rp, imgFlow.data.data(), (size_t)W * 3);
     if (st != HSFLOW_OK) std::cout << hsflow_last_error(ctx) << std::endl;
     return st == HSFLOW_OK ? SDK_SUCCESS : SDK_FAILURE;
 }
@@ -370,8 +372,148 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
 // so from the second pair on the old frame enters the solver blurred TWICE.  The blurred frames never
 // leave the device: from the second pair on hsflow_push_frame_ex blurs the resident new frame once more into
 // the old one's plane and only the next gray frame is uploaded.
+// HSFLOW_CAMERA_BATCH=n (1 .. 256) on the "-cv -cam" route: the loop below in batches of n pairs.  0: not set; -1: unusable.
+static int camera_batch()
+{
+    const char *e = getenv("HSFLOW_CAMERA_BATCH");
+    if (!e || !*e) return 0;
+    char *rest = nullptr;
+    const long v = strtol(e, &rest, 10);
+    return *rest || v < 1 || v > 256 ? -1 : (int)v;
+}
+
+static bool ends_with_jpg(const std::string &s) { return s.size() >= 4 && s.compare(s.size() - 4, 4, ".jpg") == 0; }
+
+// The same loop with up to n + 1 frames read ahead: ONE hsflow_set_sequence_* call and ONE hsflow_solve per batch on a
+// context of n pairs whose pairs stop on their own Eps (hsflow_set_pair_termination), as the loop's calls of
+// cvCalcOpticalFlowHS do.  The first batch is the loop from its start (HSFLOW_SEQ_REBLUR: its first old frame is blurred
+// once, every later one twice); a later batch starts with the frame the one before ended with, which was a new frame
+// there (| HSFLOW_SEQ_REBLUR_FIRST).  A tail of m < n pairs gets a context of m pairs.  Gray frames are uploaded as they
+// are; with HSFLOW_JPEG_IN_DEVICE=1 and nothing but .jpg frames the files go to the device undecoded.  The flow_%04d.ppm
+// files are byte for byte those of the loop below.
+static int run_camera_batched(float lambda, int it, int nb)
+{
+    struct Frame {
+        pnm::Image gray;           // the gray frame, or
+        std::vector<uint8_t> file; // the JPEG file as it is
+    };
+    bool files = jpeg_in_device();
+    for (int i = 0; files; i++) { // every frame of the clip a .jpg?
+        const std::string name = camera_frame(i);
+        FILE *f = fopen(name.c_str(), "rb");
+        if (!f) { files = i > 0; break; }
+        fclose(f);
+        if (!ends_with_jpg(name)) files = false;
+    }
+    int W = 0, H = 0;
+    auto load = [&](int i, Frame &fr) { // false: the clip ends in front of frame i
+        int w = 0, h = 0;
+        if (files) {
+            hsflow_jpeg_info info;
+            info.struct_size = sizeof(info);
+            if (!read_jpeg_file(camera_frame(i), fr.file) || hsflow_jpeg_read_header(fr.file.data(), fr.file.size(), &info) != HSFLOW_OK) return false;
+            w = info.width; h = info.height;
+        } else {
+            pnm::Image frame;
+            if (!pnm::load_image(camera_frame(i), frame)) return false;
+            pnm::to_gray(frame, fr.gray); // cvCvtColor(imgTmp, img, CV_BGR2GRAY) :79,86
+            w = fr.gray.width; h = fr.gray.height;
+        }
+        if (i == 0) { W = w; H = h; }
+        return w == W && h == H;
+    };
+    std::vector<Frame> batch(1);
+    if (!load(0, batch[0])) { std::cout << "ERROR: capture is NULL \n"; return -1; }
+    hsflow_params p;
+    hsflow_default_params(&p); // ITER|EPS, eps (float)1e-6 :94
+    p.lambda = lambda;
+    p.max_iter = it;
+    const bool on_device = render_on_device();
+    std::vector<float> u, v;
+    if (!on_device) { u.resize((size_t)W * H); v.resize((size_t)W * H); }
+    hsflow_ctx *ctx = nullptr;
+    int ctx_pairs = 0;
+    void *dFrames = nullptr; // the batch's gray frames on the device, packed
+    size_t dBytes = 0;
+    const size_t frame_bytes = (size_t)W * H;
+    auto done = [&](int code) {
+        if (ctx) hsflow_destroy(ctx);
+        if (dFrames) (void)hipFree(dFrames);
+        return code;
+    };
+    double total = 0.0;
+    int count = 0, verdict = SDK_SUCCESS, flags = HSFLOW_SEQ_REBLUR;
+    for (bool more = true; more;) {
+        while ((int)batch.size() < nb + 1) {
+            Frame fr;
+            if (!load(count + (int)batch.size(), fr)) { more = false; break; }
+            batch.push_back(std::move(fr));
+        }
+        const int m = (int)batch.size() - 1;
+        if (m < 1) break;
+        if (m != ctx_pairs) {
+            if (ctx) hsflow_destroy(ctx);
+            ctx = nullptr;
+            if (hsflow_create(&ctx, 0, W, H, m, nullptr, 1) != HSFLOW_OK) { std::cout << hsflow_last_error(nullptr) << std::endl; return done(1); }
+            if (hsflow_set_pair_termination(ctx, 1) != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return done(1); }
+            ctx_pairs = m;
+        }
+        const double t0 = now_ms();
+        int st;
+        if (files) {
+            std::vector<const uint8_t *> ptrs;
+            std::vector<size_t> sizes;
+            for (const Frame &fr : batch) { ptrs.push_back(fr.file.data()); sizes.push_back(fr.file.size()); }
+            st = hsflow_set_sequence_jpeg_ex(ctx, 0, ptrs.data(), sizes.data(), m + 1, 1, flags);
+        } else {
+            if (dBytes < frame_bytes * (size_t)(m + 1)) {
+                if (dFrames) (void)hipFree(dFrames);
+                dFrames = nullptr; dBytes = 0;
+                if (hipMalloc(&dFrames, frame_bytes * (size_t)(m + 1)) != hipSuccess) { std::cout << "hipMalloc of the batch's frames failed" << std::endl; return done(1); }
+                dBytes = frame_bytes * (size_t)(m + 1);
+            }
+            std::vector<const void *> ptrs;
+            for (int j = 0; j <= m; j++) {
+                void *d = (uint8_t *)dFrames + frame_bytes * (size_t)j;
+                if (hipMemcpy(d, batch[(size_t)j].gray.data.data(), frame_bytes, hipMemcpyHostToDevice) != hipSuccess) { std::cout << "upload of a frame failed" << std::endl; return done(1); }
+                ptrs.push_back(d);
+            }
+            st = hsflow_set_sequence_device_ex(ctx, 0, HSFLOW_FRAMES_GRAY8_BLUR, ptrs.data(), m + 1, (size_t)W, flags); // :92-93,118 for every pair
+        }
+        if (st == HSFLOW_OK) st = hsflow_solve(ctx, &p);
+        if (st == HSFLOW_OK) st = hsflow_synchronize(ctx); // (the frames' buffer is written again by the next batch)
+        total += now_ms() - t0;
+        if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return done(1); }
+        for (int k = 0; k < m; k++) {
+            const int i = count + k + 1; // the pair's new frame
+            if (!on_device && hsflow_get_flow(ctx, k, u.data(), (size_t)W * 4, v.data(), (size_t)W * 4) != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return done(1); }
+            hsflow_verify_report report;
+            if (verify_wanted() && verify_pair(ctx, W, report, k) != SDK_SUCCESS) verdict = SDK_FAILURE;
+            if (getenv("HSFLOW_CAMERA_OUT")) {
+                pnm::Image imgFlow;
+                if (!on_device) draw_cv_flow(imgFlow, u, v, W, H);
+                else if (draw_on_device(ctx, HSFLOW_RENDER_CV, W, H, imgFlow, k) != SDK_SUCCESS) return done(1);
+                char name[64];
+                snprintf(name, sizeof(name), "/flow_%04d.ppm", i);
+                pnm::save_image(std::string(getenv("HSFLOW_CAMERA_OUT")) + name, imgFlow);
+            }
+        }
+        count += m;
+        Frame last = std::move(batch.back()); // imgOld = imgNew :118, across the batches
+        batch.clear();
+        batch.push_back(std::move(last));
+        flags = HSFLOW_SEQ_REBLUR | HSFLOW_SEQ_REBLUR_FIRST;
+    }
+    if (count) std::cout << "Avg time: " << total / count << " [ms]" << std::endl; // :122 (per frame)
+    return done(verdict);
+}
+
 int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
 {
+    if (const int nb = camera_batch()) {
+        if (nb < 0) { std::cout << "HSFLOW_CAMERA_BATCH must be 1 .. 256" << std::endl; return 1; }
+        return run_camera_batched(lambda, it, nb);
+    }
     pnm::Image frame, gold, gnew;
     if (!pnm::load_image(camera_frame(0), frame)) { std::cout << "ERROR: capture is NULL \n"; return -1; }
     pnm::to_gray(frame, gold);                                   // cvCvtColor(imgTmp, imgOld, CV_BGR2GRAY) :79

@@ -1,6 +1,6 @@
 // hs_jpegd.hip.h -- part of libhsflow.so (one translation unit, see hsflow.hip): hsflow_jpeg_read_header,
 // hsflow_jpeg_decode[_host|_device|_batch_device], hsflow_set_frames_jpeg[_async], hsflow_push_frame_jpeg,
-// hsflow_set_sequence_jpeg: the frames the reference's runFromImg starts from (cvLoadImage, OpticalFlowOpenCV.cpp:15,18,
+// hsflow_set_sequence_jpeg[_ex]: the frames the reference's runFromImg starts from (cvLoadImage, OpticalFlowOpenCV.cpp:15,18,
 // HSOpticalFlowOpenCL.cpp:721,732), decoded on the device from the files' entropy-coded bytes.  One path: files are
 // decoded in chunks of at most HSFLOW_JPEGD_BATCH_MAX, laid out by hs_jpegd_batch_plan.h, each chunk by one copy, three
 // memsets and eight or eleven launches on the context's stream (hs_kernels_jpegd.hip.h); a single file is a chunk of
@@ -361,10 +361,17 @@ int hsflow_jpeg_decode_batch_device(hsflow_ctx *c, const uint8_t *const *files, 
 
 int hsflow_set_sequence_jpeg(hsflow_ctx *c, int first_pair, const uint8_t *const *files, const size_t *bytes, int n_files, int blur3x3)
 {
+    return hsflow_set_sequence_jpeg_ex(c, first_pair, files, bytes, n_files, blur3x3, 0);
+}
+
+int hsflow_set_sequence_jpeg_ex(hsflow_ctx *c, int first_pair, const uint8_t *const *files, const size_t *bytes, int n_files, int blur3x3, int flags)
+{
     int st = check_ctx(c, 0);
     if (st) return st;
     if (n_files < 2) return fail(c, HSFLOW_E_ARG, "a sequence needs at least two files");
     if (first_pair < 0 || (long long)first_pair + n_files - 1 > c->N) return fail(c, HSFLOW_E_ARG, "the sequence's pairs exceed the context's");
+    if (!hspre::seq_flags_known(flags)) return fail(c, HSFLOW_E_ARG, "flags must be 0, HSFLOW_SEQ_REBLUR or HSFLOW_SEQ_REBLUR | HSFLOW_SEQ_REBLUR_FIRST");
+    if (!pre_seq_max()) return fail(c, HSFLOW_E_ARG, "HSFLOW_PRE_SEQ_MAX in the environment must be 1 .. " + std::to_string(HSFLOW_PRE_SEQ_MAX));
     if ((st = settle_pending(c))) return st; // (before the all-or-nothing part: an owed check belongs to the frames that are there)
     hsflow_ctx::JpegdScratch &j = c->jpegd;
     const size_t rowb = (size_t)c->W * 3, pic = hsjpegd_plan::up256(rowb * (size_t)c->H), words = hsjpegd_plan::up256((size_t)n_files * 4), want = words + pic * (size_t)n_files;
@@ -389,9 +396,8 @@ int hsflow_set_sequence_jpeg(hsflow_ctx *c, int first_pair, const uint8_t *const
     for (int i = 0; i < n_files; i++)
         if (j.hSeq[i])
             return fail(c, HSFLOW_E_DATA, "file " + std::to_string(i) + (j.hSeq[i] == 2 ? ": JPEG file: truncated entropy-coded data" : ": JPEG file: corrupt entropy-coded data"));
-    for (int k = 0; k + 1 < n_files; k++)
-        if ((st = hsflow_set_frames_device_ex(c, first_pair + k, blur3x3 ? HSFLOW_FRAMES_BGR8_BLUR : HSFLOW_FRAMES_BGR8, pix[(size_t)k], rowb, pix[(size_t)k + 1], rowb)))
-            return st;
+    // the pictures into the pairs: one launch per HSFLOW_PRE_SEQ_MAX of them, each read once
+    if ((st = hsflow_set_sequence_device_ex(c, first_pair, blur3x3 ? HSFLOW_FRAMES_BGR8_BLUR : HSFLOW_FRAMES_BGR8, pix.data(), n_files, rowb, flags))) return st;
     HS_HIP(c, hipStreamSynchronize(c->stream));
     return HSFLOW_OK;
 }

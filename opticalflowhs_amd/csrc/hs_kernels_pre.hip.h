@@ -163,4 +163,31 @@ __global__ __launch_bounds__(256) void k_pre_pair(const uint8_t *__restrict__ sr
     }
 }
 
+// A SEQUENCE of frames from device memory into consecutive pairs of the context in ONE launch per chunk of at most
+// kPreSeqMax frames (hsflow_set_sequence_device_ex; the reference's camera loop, OpticalFlowOpenCV.cpp:76-93,118, in a
+// context of N pairs).  blockIdx.z: the frame, as in the batched JPEG kernels; x, y and the lane shape are k_pre_pair's.
+// Frame j is read ONCE and leaves up to two results in up to two planes: p_j = pre(format, f_j) in curr of pair j - 1
+// and / or prev of pair j, and, where the loop's double blur is asked for, B(p_j) -- the blur of the rounded plane p_j
+// with p_j's own border repeated -- in prev of pair j.  The walk is hs_pre_rule.h's seq_strip, the host's too; no gray
+// or once-blurred plane exists outside registers.  The double blur keeps three rows of six sums and three rows of four
+// (30 words) and reads two halo rows and two halo columns on each side of a lane's strip.
+constexpr int kPreSeqMax = 32; // frames per launch: four pointers each, 1 KiB of the kernel's argument block
+
+struct PreSeqFrames { // what differs from frame to frame, handed to the kernel by value
+    const uint8_t *src[kPreSeqMax];
+    uint8_t *p0[kPreSeqMax], *p1[kPreSeqMax], *b[kPreSeqMax]; // hspre::SeqDst; null: not wanted
+    uint32_t words;                                           // bit i: frame i's base and the stride are multiples of 4
+};
+
+template <bool COLOUR, bool BLUR>
+__global__ __launch_bounds__(256) void k_pre_sequence(PreSeqFrames f, long long stride, int W, int H, int P)
+{
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 4; // blockDim.x = 64: threadIdx.y is the wavefront
+    const int y0 = (blockIdx.y * blockDim.y + threadIdx.y) * HSFLOW_PRE_STRIP_ROWS;
+    if (x0 >= W || y0 >= H) return;
+    const unsigned z = blockIdx.z;
+    const bool word = ((f.words >> z) & 1u) != 0 && x0 + 4 <= W;
+    hspre::seq_strip_any<COLOUR, BLUR, false>(f.src[z], (size_t)stride, W, H, x0, y0, word, f.p0[z], f.p1[z], f.b[z], (size_t)P);
+}
+
 } // namespace hsk

@@ -86,6 +86,50 @@ hipError_t launch_pre_fused(hsflow_ctx *c, int format, int frames, const void *s
     return hipGetLastError();
 }
 
+// HSFLOW_PRE_SEQ_MAX of this call: the environment's (1 .. the header's, for measuring and for testing the chunking), else
+// the header's; 0: unusable.
+int pre_seq_max()
+{
+    static_assert(HSFLOW_PRE_SEQ_MAX >= 1 && HSFLOW_PRE_SEQ_MAX <= hsk::kPreSeqMax, "a chunk of frames must fit k_pre_sequence's argument block");
+    const char *e = getenv("HSFLOW_PRE_SEQ_MAX");
+    if (!e || !*e) return HSFLOW_PRE_SEQ_MAX;
+    char *rest = nullptr;
+    const long v = strtol(e, &rest, 10);
+    if (*rest || v < 1 || v > HSFLOW_PRE_SEQ_MAX) return 0;
+    return (int)v;
+}
+
+// Frames f_0 .. f_{n-1} in device memory (rows `stride` apart) into the pairs first_pair .. first_pair + n - 2 by the
+// sequence rule of hs_pre_rule.h, on the context's stream: ONE launch of k_pre_sequence per chunk of at most `maxf`
+// frames, whatever the format (a frame's results depend on that frame alone, so a chunk boundary needs no overlap).
+hipError_t launch_pre_sequence(hsflow_ctx *c, int first_pair, int format, const void *const *frames, int n, size_t stride, int flags, int maxf)
+{
+    constexpr int S = HSFLOW_PRE_STRIP_ROWS;
+    for (int j0 = 0; j0 < n; j0 += maxf) {
+        const int m = std::min(maxf, n - j0);
+        hsk::PreSeqFrames f = {};
+        for (int i = 0; i < m; i++) {
+            const int j = j0 + i;
+            const hspre::SeqDst d = hspre::seq_dst(flags, j, n, j <= n - 2 ? c->dA + (size_t)(first_pair + j) * c->plane : nullptr,
+                                                   j >= 1 ? c->dB + (size_t)(first_pair + j - 1) * c->plane : nullptr);
+            f.src[i] = (const uint8_t *)frames[j];
+            f.p0[i] = d.p0; f.p1[i] = d.p1; f.b[i] = d.b;
+            if ((((uintptr_t)frames[j] | stride) & 3u) == 0) f.words |= 1u << i;
+        }
+        const dim3 grid((c->W + 255) / 256, ((c->H + S - 1) / S + 3) / 4, m), block(64, 4);
+        switch (format) {
+        case HSFLOW_FRAMES_GRAY8: hipLaunchKernelGGL((hsk::k_pre_sequence<false, false>), grid, block, 0, c->stream, f, (long long)stride, c->W, c->H, c->P); break;
+        case HSFLOW_FRAMES_GRAY8_BLUR: hipLaunchKernelGGL((hsk::k_pre_sequence<false, true>), grid, block, 0, c->stream, f, (long long)stride, c->W, c->H, c->P); break;
+        case HSFLOW_FRAMES_BGR8: hipLaunchKernelGGL((hsk::k_pre_sequence<true, false>), grid, block, 0, c->stream, f, (long long)stride, c->W, c->H, c->P); break;
+        case HSFLOW_FRAMES_BGR8_BLUR: hipLaunchKernelGGL((hsk::k_pre_sequence<true, true>), grid, block, 0, c->stream, f, (long long)stride, c->W, c->H, c->P); break;
+        default: return hipErrorInvalidValue;
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // Could the first Jacobi launch of a solve read these frames where they lie (hsk::FrameSrc)?  It reads a lane's four
 // columns as one word, so both planes must be word-aligned with pitches that keep every row so; one pair per context.
 // HSFLOW_KEEP_FRAME_COPY=1: never (A/B runs).  Whether the solve HAS such a launch it decides itself (resolve_lazy_frames).

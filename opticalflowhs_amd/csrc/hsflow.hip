@@ -433,6 +433,41 @@ int hsflow_preprocess_frame_host(int format, const uint8_t *src, size_t src_stri
     }
 }
 
+// The camera loop's frame handling for n_frames frames at once (OpticalFlowOpenCV.cpp:76-93,118): every argument is
+// checked, an owed check is settled against the frames that are there, and then the planes of the pairs receive the
+// results of one launch per chunk -- the planes the context has always had, so cached graphs stay valid.
+int hsflow_set_sequence_device_ex(hsflow_ctx *c, int first_pair, int format, const void *const *d_frames, int n_frames, size_t stride, int flags)
+{
+    int st = check_ctx(c, 0);
+    if (st) return st;
+    if (!d_frames) return fail(c, HSFLOW_E_ARG, "null frame list");
+    if (n_frames < 2) return fail(c, HSFLOW_E_ARG, "a sequence needs at least two frames");
+    if (first_pair < 0 || (long long)first_pair + n_frames - 1 > c->N) return fail(c, HSFLOW_E_ARG, "the sequence's pairs exceed the context's");
+    for (int j = 0; j < n_frames; j++)
+        if (!d_frames[j]) return fail(c, HSFLOW_E_ARG, "frame " + std::to_string(j) + ": null frame pointer");
+    if (!hspre::format_known(format)) return fail(c, HSFLOW_E_ARG, "unknown frame format");
+    if (!hspre::seq_flags_known(flags)) return fail(c, HSFLOW_E_ARG, "flags must be 0, HSFLOW_SEQ_REBLUR or HSFLOW_SEQ_REBLUR | HSFLOW_SEQ_REBLUR_FIRST");
+    const int maxf = pre_seq_max();
+    if (!maxf) return fail(c, HSFLOW_E_ARG, "HSFLOW_PRE_SEQ_MAX in the environment must be 1 .. " + std::to_string(HSFLOW_PRE_SEQ_MAX));
+    if (stride < (size_t)c->W * (hspre::format_colour(format) ? 3 : 1))
+        return fail(c, HSFLOW_E_SIZE, hspre::format_colour(format) ? "colour frame stride smaller than 3*width" : "frame stride smaller than width");
+    if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
+    HS_HIP(c, launch_pre_sequence(c, first_pair, format, d_frames, n_frames, stride, flags, maxf));
+    c->frames_set = true;
+    c->coef_valid = false;
+    return HSFLOW_OK;
+}
+
+int hsflow_preprocess_sequence_host(int format, int flags, const uint8_t *const *frames, int n_frames, size_t stride, int width, int height,
+                                    uint8_t *const *prev, uint8_t *const *curr, size_t dst_stride)
+{
+    switch (hspre::preprocess_sequence_host(format, flags, frames, n_frames, stride, width, height, prev, curr, dst_stride)) {
+    case 0: return HSFLOW_OK;
+    case 1: return fail(nullptr, HSFLOW_E_ARG, "hsflow_preprocess_sequence_host: null pointer, unknown frame format or flags, or fewer than two frames");
+    default: return fail(nullptr, HSFLOW_E_SIZE, "hsflow_preprocess_sequence_host: non-positive size or stride smaller than a row");
+    }
+}
+
 int hsflow_set_async_reduce(hsflow_ctx *c, int on)
 {
     int st = check_ctx(c, 0);

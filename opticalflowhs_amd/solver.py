@@ -206,6 +206,22 @@ class HSFlow(object):
         (pa, sa), (pb, sb) = (self._device_frame(t, fmt >= _lib.FRAMES_BGR8) for t in (prev, curr))
         self._check(self._lib.hsflow_set_frames_device_ex(self._h, pair, fmt, pa, sa, pb, sb))
 
+    def set_sequence_device(self, frames_list, frames="gray", reblur=False, reblur_first=False, first_pair=0):
+        """len(frames_list) >= 2 consecutive frames that lie in device memory (CUDA uint8 tensors as for
+        `set_frames_device`, one row stride for all) into the pairs first_pair .. first_pair + len - 2: pair k holds
+        (pre(frame k), pre(frame k + 1)); with reblur its previous frame is blurred once more -- the reference's camera
+        loop, which blurs old and new in place -- for every pair but the first, and with reblur_first for the first too
+        (the loop continued: frame 0 was the new frame of an earlier batch).  Every frame is read once, by one launch per
+        `PRE_SEQ_MAX` frames (`hsflow_set_sequence_device_ex`); only enqueued."""
+        fmt = _lib.FRAME_FORMATS[frames]
+        targets = [self._device_frame(t, fmt >= _lib.FRAMES_BGR8) for t in frames_list]
+        if len(set(s for _, s in targets)) > 1:
+            raise ValueError("the frames of a sequence share one row stride")
+        n = len(targets)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[p for p, _ in targets])
+        self._check(self._lib.hsflow_set_sequence_device_ex(self._h, int(first_pair), fmt, ptrs, n, targets[0][1] if n else 0,
+                                                            _seq_flags(reblur, reblur_first)))
+
     def push_frame_ex(self, nxt, frames="gray", reblur_prev=False, pair=0):
         """The camera sequence: the current frame becomes the previous one -- blurred once more with reblur_prev, which
         with a "*_blur" layout is the reference's loop -- and `nxt` is pre-processed into the current one.  nxt: a numpy
@@ -421,12 +437,15 @@ class HSFlow(object):
         torch.cuda.synchronize(out.device)  # (not `synchronize`: a decode touches no solver state, an owed check stays owed)
         return out, [int(v) for v in status[:n].cpu().tolist()]
 
-    def set_sequence_jpeg(self, files, blur=True, first_pair=0):
+    def set_sequence_jpeg(self, files, blur=True, first_pair=0, reblur=False, reblur_first=False):
         """len(files) >= 2 consecutive frames as baseline JPEG files (`bytes`) into the pairs first_pair .. first_pair +
         len(files) - 2, pair k = (file k, file k + 1): every file decoded once, as one batch, then `set_frames_jpeg`'s
-        pre-processing per pair (`hsflow_set_sequence_jpeg`).  All or nothing: on an error no pair's frames change."""
+        pre-processing of every pair by one launch (`hsflow_set_sequence_jpeg_ex`).  reblur, reblur_first: the camera
+        loop's double blur of the previous frame, as in `set_sequence_device`.  All or nothing: on an error no pair's
+        frames change."""
         ptrs, sizes, keep = _file_lists(files)
-        self._check(self._lib.hsflow_set_sequence_jpeg(self._h, int(first_pair), ptrs, sizes, len(files), 1 if blur else 0))
+        self._check(self._lib.hsflow_set_sequence_jpeg_ex(self._h, int(first_pair), ptrs, sizes, len(files), 1 if blur else 0,
+                                                          _seq_flags(reblur, reblur_first)))
 
     def set_frames_jpeg(self, prev, curr, blur=True, pair=0):
         """Both frames as baseline JPEG files (`bytes`): decoded on the device, then cvCvtColor (+ cvSmooth with
@@ -516,6 +535,37 @@ def preprocess_frame(img, frames):
     if st:
         raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
     return out
+
+
+def _seq_flags(reblur, reblur_first):
+    """HSFLOW_SEQ_* of the two keywords (reblur_first alone is passed on as it is: the library refuses it)."""
+    return (_lib.SEQ_REBLUR if reblur else 0) | (_lib.SEQ_REBLUR_FIRST if reblur_first else 0)
+
+
+def preprocess_sequence(frames_list, fmt, reblur=False, reblur_first=False):
+    """The sequence rule on the host (`hsflow_preprocess_sequence_host`; no device needed): for n >= 2 frames given in
+    layout `fmt` ("gray", "gray_blur": (H, W) uint8; "bgr", "bgr_blur": (H, W, 3)) the list of the n - 1 pairs'
+    (prev, curr) planes, what `HSFlow.set_sequence_device` leaves in `HSFlow.frames(k)`."""
+    lib = _lib.load()
+    f = _lib.FRAME_FORMATS[fmt]
+    colour = f >= _lib.FRAMES_BGR8
+    imgs = [np.asarray(a) for a in frames_list]
+    for a in imgs:
+        if a.dtype != np.uint8 or a.ndim != (3 if colour else 2) or (colour and a.shape[2] != 3) or a.shape != imgs[0].shape:
+            raise ValueError("expected uint8 arrays of one shape (H, W), or (H, W, 3) for colour")
+    if imgs and (len(set(a.strides for a in imgs)) > 1 or imgs[0].strides[-1] != 1 or (colour and imgs[0].strides[1] != 3)):
+        imgs = [np.ascontiguousarray(a) for a in imgs]
+    n = len(imgs)
+    H, W = imgs[0].shape[:2] if n else (0, 0)
+    prev = np.empty((max(n - 1, 1), H, W), np.uint8)
+    curr = np.empty((max(n - 1, 1), H, W), np.uint8)
+    src = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in imgs])
+    pp = (ctypes.c_void_p * max(n - 1, 1))(*[prev[k].ctypes.data for k in range(max(n - 1, 1))])
+    pc = (ctypes.c_void_p * max(n - 1, 1))(*[curr[k].ctypes.data for k in range(max(n - 1, 1))])
+    st = lib.hsflow_preprocess_sequence_host(f, _seq_flags(reblur, reblur_first), src, n, imgs[0].strides[0] if n else 0, W, H, pp, pc, W)
+    if st:
+        raise HsflowError(st, (lib.hsflow_last_error(None) or b"").decode())
+    return [(prev[k], curr[k]) for k in range(n - 1)]
 
 
 def jpeg_bound(width, height):
