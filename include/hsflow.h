@@ -71,7 +71,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 14 /* 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 15 /* 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -143,7 +143,18 @@ typedef struct hsflow_params {
                              solve complete.  Without a budget: finite and > 0, else
                              HSFLOW_E_NOTERM                                              */
     int32_t use_previous; /* 0: u=v=0 first (reference behaviour); 1: continue from the
-                             flow currently held by the context                          */
+                             flow currently held by the context: any floats, as the
+                             reference takes them.  Where a caller wrote that flow
+                             (hsflow_set_flow_device, the one-shot's velx / vely), or a
+                             solve with lambda > 1e20 or a classic solve left it, a strip /
+                             fold solve first measures the planes (one small launch, the
+                             host waits for one word -- hsflow_solve_async too) and shortens
+                             its launches so that no intermediate leaves the float range;
+                             info.fuse_steps reports the length taken.  Where the largest
+                             finite |value| m has m + n * 255 * sqrt(lambda) >= FLT_MAX / 64
+                             = 5.3e36 (n: max_iter, at most 2^20) HSFLOW_KERNEL_SIMPLE takes
+                             the solve, which is then complete when the call returns.  NaN / Inf spread one
+                             pixel per sweep, as in the reference, in every kernel       */
     int32_t kernel;       /* HSFLOW_KERNEL_*                                             */
     int32_t fuse_steps;   /* FUSED: iterations per launch, 0 = auto                      */
     int32_t tile_w;       /* FUSED: core tile width  (multiple of 4), 0 = auto           */
@@ -457,7 +468,17 @@ int hsflow_get_flow_async(hsflow_ctx *ctx, int pair, float *u, size_t u_stride, 
 /* Row range [row0, row0+nrows) of the flow to / from device memory, on ctx's stream (used for
  * the row-slab halo exchange).  set_ writes into the flow the next
  * use_previous=1 solve continues from.  Both settle an ITER|EPS check that hsflow_solve_async still
- * owes (they wait for the stream in that case); after an ITER-only solve they only enqueue. */
+ * owes (they wait for the stream in that case); after an ITER-only solve they only enqueue.
+ * Any float may be written.  After a set_ the context no longer knows how large its flow is: the next warm strip / fold
+ * solve measures the planes first (see hsflow_params.use_previous), and so does every later one unless that measurement
+ * found nothing above 1e15 (then the planes count as the solver's own again) or a solve with use_previous = 0 has made
+ * them anew.
+ * hsflow_set_flow_device_ex (ABI 0.15) is set_ with flags.  HSFLOW_FLOW_SOLVER_MADE: the caller vouches that the rows are
+ * flow that a CV solve of this library made from zero with the lambda of this context's solves -- a neighbouring row
+ * slab's halo rows, a copy of this context's own flow saved earlier.  The context then keeps what it knew about its
+ * planes: nothing is measured, a warm hsflow_solve_async enqueues and returns as it always did.  That is what the row-slab
+ * drivers (hsflow_slab_*, slab.py) pass.  Rows that are not what the flag says can overflow inside a strip launch. */
+#define HSFLOW_FLOW_SOLVER_MADE 1
 /* Where the context holds the current flow of `pair`, without a copy: device pointers to row 0 and the row
  * stride in bytes (rows are `width` floats; the pitch is that of hsflow_info).  Settles an ITER|EPS check that
  * hsflow_solve_async still owes and waits for the stream -- with hsflow_set_async_reduce, for the marker behind the last
@@ -470,6 +491,8 @@ int hsflow_get_flow_device(hsflow_ctx *ctx, int pair, int row0, int nrows, void 
                            size_t u_stride, void *d_v, size_t v_stride);
 int hsflow_set_flow_device(hsflow_ctx *ctx, int pair, int row0, int nrows, const void *d_u,
                            size_t u_stride, const void *d_v, size_t v_stride);
+int hsflow_set_flow_device_ex(hsflow_ctx *ctx, int pair, int row0, int nrows, const void *d_u,
+                              size_t u_stride, const void *d_v, size_t v_stride, int flags);
 /* Derivative planes of the last solve as fp32 (CV: Ix, Iy, It; CLASSIC: Ex, Ey, Et). */
 int hsflow_get_derivatives(hsflow_ctx *ctx, int pair, float *dx, float *dy, float *dt,
                            size_t stride);

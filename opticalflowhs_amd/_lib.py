@@ -137,6 +137,7 @@ PROTOTYPES = {
     "hsflow_flow_view_device": (_i, [_vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
     "hsflow_get_flow_device": (_i, [_vp, _i, _i, _i, _vp, _sz, _vp, _sz]),
     "hsflow_set_flow_device": (_i, [_vp, _i, _i, _i, _vp, _sz, _vp, _sz]),
+    "hsflow_set_flow_device_ex": (_i, [_vp, _i, _i, _i, _vp, _sz, _vp, _sz, _i]),
     "hsflow_get_derivatives": (_i, [_vp, _i, _vp, _vp, _vp, _sz]),
     "hsflow_get_frames_u8": (_i, [_vp, _i, _vp, _sz, _vp, _sz]),
     "hsflow_default_render_params": (None, [_rp, _i]),

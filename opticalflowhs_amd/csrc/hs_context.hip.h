@@ -83,6 +83,7 @@ struct SolveSetup {
 struct PlanKey {
     hsflow_params p;
     int async, exact;
+    int t_cap; // hsflow_ctx::t_cap the plan was made under
 };
 struct PlanEntry {
     PlanKey key;
@@ -114,6 +115,15 @@ struct hsflow_ctx {
     unsigned *dEpsTiles = nullptr; // per-sweep, per-workgroup Eps of the launches of one solve
     size_t epsTilesCap = 0;
     float *dUb = nullptr, *dVb = nullptr; // backup of the starting flow (ITER|EPS with use_previous)
+    // Caller-written flow (hs_solve.hip.h, "tame planes"): the flow planes are `tame` while this context's own CV solves
+    // with Ilambda >= 1e-20 made them, from zero or from tame planes -- what the strip kernels' scaled state counts on.  A
+    // write through hsflow_set_flow_device (without HSFLOW_FLOW_SOLVER_MADE) or the one-shot's upload, a solve with a
+    // smaller Ilambda and a classic solve clear the flag, a measurement that finds nothing above 1e15 sets it again; a warm
+    // strip / fold solve on planes that are not tame measures them first (dFlowMax: one word) and caps its launch length
+    // (t_cap: 0 none, else the most sweeps a strip / fold launch of the solve being planned may have).
+    bool flow_tame = true;
+    unsigned *dFlowMax = nullptr, *hFlowMax = nullptr; // (the word on the device, and page-locked for its way back)
+    int t_cap = 0;
     // the persistent launch (HSFLOW_KERNEL_PERSIST, hs_kernels_strip.hip.h): a third flow buffer (its phases alternate
     // between this one and the ping-pong buffer the result lands in; the starting flow stays intact), the tiles' phase
     // counters, the error word (page-locked, device-visible)

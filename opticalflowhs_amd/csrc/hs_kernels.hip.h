@@ -149,6 +149,26 @@ __device__ __forceinline__ float wave_sum16(float x)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 15));
 }
 
+// Largest |value| of the flow planes of a context (both planes, every pair: `rows` = pairs x height rows of pitch P), as
+// the bits of a non-negative float in *out (cleared by the host; unsigned order is float order there).  NaN and Inf are
+// left out: they are the same at every scale and turn whatever they meet into NaN or Inf at every scale alike.  For warm
+// starts from flow a caller wrote (measure_flow_absmax, hs_solve.hip.h); one lane per column.
+__global__ __launch_bounds__(256) void k_flow_absmax(const float *__restrict__ u, const float *__restrict__ v, int W, long long rows, int P,
+                                                     unsigned *__restrict__ out)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    unsigned m = 0u;
+    if (x < W)
+        for (long long y = blockIdx.y; y < rows; y += gridDim.y) {
+            const long long i = y * P + x;
+            const unsigned a = __float_as_uint(u[i]) & 0x7fffffffu, b = __float_as_uint(v[i]) & 0x7fffffffu;
+            m = max(m, max(a < 0x7f800000u ? a : 0u, b < 0x7f800000u ? b : 0u));
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+
 // ------------------------------------------------------------------------------------------
 // a1: derivative pass, CV mode.  One lane = 4 consecutive pixels of one row.
 //     reads 2 B/pixel (u8 A with a 3x3 neighbourhood from L1/L2, u8 B), writes 4 B/pixel.

@@ -42,10 +42,17 @@ struct ClassicStripGeom {
 // compiler's own correctly rounded sequence (v_div_scale, v_rcp, two refinement steps of the reciprocal, quotient,
 // two residual steps, v_div_fmas, v_div_fixup) with the three instructions that depend on the denominator alone hoisted
 // out of the sweep loop -- legal because the denominator alpha^2 + Ex^2 + Ey^2 is a normal number far from the ends of
-// the exponent range (the host admits 2^-40 <= alpha^2 <= 2^40 to these kernels), so v_div_scale never rescales IT; the
-// numerator keeps its v_div_scale (tiny numerators -- flow that has only just reached a static area -- are scaled by
-// 2^64 for the residuals and scaled back by v_div_fmas, as in the compiler's sequence).  Same instructions on the same
-// operands: the same bits (tests: bit-exact against oracle/hs_classic_oracle.c, which divides with `/`).
+// the exponent range (the host admits 2^-40 <= alpha^2 <= 2^40 to these kernels), so v_div_scale does not rescale IT on
+// its own account; the numerator keeps its v_div_scale (tiny numerators -- flow that has only just reached a static
+// area -- are scaled by 2^64 for the residuals and scaled back by v_div_fmas, as in the compiler's sequence).  Same
+// instructions on the same operands: the same bits (tests: bit-exact against oracle/hs_classic_oracle.c, which divides
+// with `/`).  One case needs care: a numerator whose exponent is 96 or more above the denominator's (flow from about
+// 1e31 upward, which only a caller can have written: tests/test_gpu_warm_flow.py).  There v_div_scale would rescale the
+// DENOMINATOR, which the hoisted reciprocal has not seen, and it raises the same flag as for a tiny numerator; v_div_fmas
+// then scaled a quotient that had never been scaled down, and every such lane overflowed.  The flag is therefore passed
+// on only where the numerator is a tiny one (|n| < 1; tiny ones lie below 2^-100): a huge numerator runs the sequence
+// unscaled, which rounds correctly as long as the quotient is a float at all (no residual can underflow there).  A
+// quotient beyond FLT_MAX comes out as NaN where `/` gives Inf -- flow that the next sweep turns into NaN either way.
 // It costs one more register per pixel: used by the shapes that have them (R = 2, 3 at 1024 threads, 4 at 768, 6 at 512).
 __device__ __forceinline__ float refined_rcp(float d)
 {
@@ -61,24 +68,10 @@ __device__ __forceinline__ float div_by(float n, float d, float r)
     const float e0 = __builtin_fmaf(-d, q0, ns);
     const float q1 = __builtin_fmaf(e0, r, q0);
     const float e1 = __builtin_fmaf(-d, q1, ns);
-    return __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e1, r, q1, scaled), d, n);
+    return __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e1, r, q1, scaled && __builtin_fabsf(n) < 1.0f), d, n); // (see above)
 }
 
-// Two quotients at once: the four multiply / fused multiply-add steps of div_by as packed instructions (v_pk_mul_f32,
-// v_pk_fma_f32 round each half exactly like their scalar forms).
 typedef float f2c __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2c div_by2(f2c n, f2c d, f2c r)
-{
-    bool sx, sy;
-    const f2c ns = f2c{__builtin_amdgcn_div_scalef(n.x, d.x, true, &sx), __builtin_amdgcn_div_scalef(n.y, d.y, true, &sy)};
-    const f2c q0 = ns * r;
-    const f2c e0 = __builtin_elementwise_fma(-d, q0, ns);
-    const f2c q1 = __builtin_elementwise_fma(e0, r, q0);
-    const f2c e1 = __builtin_elementwise_fma(-d, q1, ns);
-    return f2c{__builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e1.x, r.x, q1.x, sx), d.x, n.x),
-               __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e1.y, r.y, q1.y, sy), d.y, n.y)};
-}
-
 // The shapes without a register for the reciprocal divide with the complete sequence, two quotients at a time: the
 // compiler's own expansion of `/` (v_div_scale of both operands, v_rcp, two refinement steps, quotient, two residual
 // steps, v_div_fmas, v_div_fixup) with its six multiply / fused multiply-add steps packed.
@@ -94,6 +87,22 @@ __device__ __forceinline__ f2c div_full2(f2c n, f2c d)
     const f2c e0 = __builtin_elementwise_fma(-ds, q0, ns);
     const f2c q1 = __builtin_elementwise_fma(e0, r, q0);
     const f2c e1 = __builtin_elementwise_fma(-ds, q1, ns);
+    return f2c{__builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e1.x, r.x, q1.x, sx), d.x, n.x),
+               __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e1.y, r.y, q1.y, sy), d.y, n.y)};
+}
+
+// Two quotients at once: the four multiply / fused multiply-add steps of div_by as packed instructions (v_pk_mul_f32,
+// v_pk_fma_f32 round each half exactly like their scalar forms).
+__device__ __forceinline__ f2c div_by2(f2c n, f2c d, f2c r)
+{
+    bool sx, sy;
+    const f2c ns = f2c{__builtin_amdgcn_div_scalef(n.x, d.x, true, &sx), __builtin_amdgcn_div_scalef(n.y, d.y, true, &sy)};
+    const f2c q0 = ns * r;
+    const f2c e0 = __builtin_elementwise_fma(-d, q0, ns);
+    const f2c q1 = __builtin_elementwise_fma(e0, r, q0);
+    const f2c e1 = __builtin_elementwise_fma(-d, q1, ns);
+    sx = sx && __builtin_fabsf(n.x) < 1.0f; // (the flag counts only where the numerator was the one scaled, see above)
+    sy = sy && __builtin_fabsf(n.y) < 1.0f;
     return f2c{__builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e1.x, r.x, q1.x, sx), d.x, n.x),
                __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e1.y, r.y, q1.y, sy), d.y, n.y)};
 }

@@ -12,8 +12,12 @@
 // the average at the next scale and the multiplication by 0.25 disappears (the constant term ga is rescaled
 // instead: one packed multiply per pair of pixels where there were two).  Powers of 4 commute with every
 // rounding, so the result is bit-identical to the canonical arithmetic of update_cv<> -- except for values that
-// would be denormal there (below 1.2e-38), which keep their bits here.  T <= 24: 4^24 = 2.8e14, no overflow for
-// any flow a valid lambda allows.
+// would be denormal there (below 1.2e-38), which keep their bits here.  A launch has up to kMaxFuse = 32 sweeps, so the
+// state reaches 4^33 = 7.4e19 times the flow: no overflow for the flow the solver itself makes from zero while
+// lambda <= 1e20 (beyond that the host keeps launches to 8 sweeps), but the kernels do NOT bound the flow they are
+// handed.  For planes a caller wrote, or that a solve with a larger lambda left, the host measures the largest |value|
+// and caps the launch length (flow_launch_cap, hs_solve.hip.h); values from about 5e36 go to the one-sweep kernel.
+// NaN and Inf need no care: they spread through the scaled state exactly as through the canonical one.
 #ifndef HS_SWEEP_STAMPS
 #define HS_SWEEP_STAMPS 0
 #endif

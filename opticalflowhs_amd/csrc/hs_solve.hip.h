@@ -1131,8 +1131,12 @@ int prepare_solve(hsflow_ctx *c, const hsflow_params &p, bool async, SolveSetup 
         if (budget < T) T = (int)budget;
         // The strip kernels carry 4^k * u inside a launch (hs_kernels_strip.hip.h).  The largest flow and
         // constant term a pixel can have grow like sqrt(lambda); beyond lambda = 1e20 keep the launches
-        // short so that 4^(T+1) times those stays far inside the float range.
+        // short so that 4^(T+1) times those stays far inside the float range.  That bounds what the solver itself
+        // produces from zero flow, up to kMaxFuse sweeps per launch; it says nothing about flow a caller wrote or an
+        // earlier solve with a larger lambda left: a warm solve on such planes measures them and hands down the most
+        // sweeps a launch may have (c->t_cap, flow_launch_cap).
         if ((kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD) && coeff < 1e-20f) T = std::min(T, 8);
+        if ((kernel == HSFLOW_KERNEL_STRIP || kernel == HSFLOW_KERNEL_FOLD) && c->t_cap > 0) T = std::min(T, c->t_cap);
         if (!plan_sweeps(T, plan))
             return fail(c, HSFLOW_E_SIZE, "no feasible launch plan for the requested tile/threads/rows/fuse_steps");
         // the short last launch of a real sweep budget: planned here, once per parameter set like the full launch
@@ -1171,6 +1175,44 @@ int prepare_solve(hsflow_ctx *c, const hsflow_params &p, bool async, SolveSetup 
 }
 
 int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *took_over);
+
+// ---- tame planes: warm starts from flow the solver did not make ------------------------------------------------------
+// The largest finite |value| of the flow planes, every pair (NaN and Inf do not count: no scale changes them or what
+// they do to their neighbours).  One small launch, one word back, and the host waits for it: only on contexts whose
+// planes are not tame (hsflow_ctx::flow_tame).
+int measure_flow_absmax(hsflow_ctx *c, float &m)
+{
+    if (!c->dFlowMax) HS_HIP(c, hipMalloc((void **)&c->dFlowMax, sizeof(unsigned)));
+    if (!c->hFlowMax) HS_HIP(c, hipHostMalloc((void **)&c->hFlowMax, sizeof(unsigned), hipHostMallocDefault));
+    HS_HIP(c, hipMemsetAsync(c->dFlowMax, 0, sizeof(unsigned), c->stream));
+    const long long rows = (long long)c->N * c->H;
+    hipLaunchKernelGGL(hsk::k_flow_absmax, dim3((c->W + 255) / 256, (unsigned)std::min<long long>(rows, 256)), dim3(256), 0, c->stream,
+                       c->dU[c->cur], c->dV[c->cur], c->W, rows, c->P, c->dFlowMax);
+    HS_HIP(c, hipGetLastError());
+    HS_HIP(c, hipMemcpyAsync(c->hFlowMax, c->dFlowMax, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HS_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(&m, c->hFlowMax, sizeof(m));
+    return HSFLOW_OK;
+}
+
+// The most sweeps a strip / fold launch may have on planes whose largest |value| is m (0: not even one).
+// With N_k the largest Euclidean length of a pixel's (u, v) after k sweeps: the neighbour average does not lengthen it,
+// the update takes away part of its component along (Ix, Iy) and adds a constant no longer than |ga| <= 255 / sqrt(Ilambda)
+// (sweep_coefs: |It| <= 255, s <= 1 / sqrt(Ilambda)), so N_k <= sqrt(2) m + k g.  After k sweeps of a launch the kernel
+// holds 4^k * flow, and the largest numbers sweep k + 1 forms are the neighbour sum 4^(k+1) * average, the inner product q
+// of update_cv, at most 4^(k+1) * (N_k + g) as |al|, |be| <= 1, and sweep_diff's 4 * old - new, at most 2 * 4^(k+1) * N:
+// all below 4^(k+1) * 2 * (sqrt(2) m + (k + 1) g) < 4^(T+1) * 4 * (m + n g) / sqrt(2) over a launch of T sweeps in a solve
+// of n.  So 4^(T+1) * (m + n g) < FLT_MAX / 4 keeps every one of them finite with a factor sqrt(2) to spare for rounding.
+// (n: the sweep budget, at most 2^20 -- an EPS-only solve that long has its flow at a fixed point, not growing.)
+int flow_launch_cap(float m, float coeff, long long budget)
+{
+    if (!(m < INFINITY)) return 0;
+    const double g = 255.0 / std::sqrt((double)coeff);
+    const double bound = (double)m + (double)std::min<long long>(budget, 1LL << 20) * g;
+    int T = 0;
+    while (T < kMaxFuse && std::ldexp(bound, 2 * (T + 2)) < (double)FLT_MAX / 4) T++;
+    return T;
+}
 
 int solve_impl(hsflow_ctx *c, const hsflow_params *pp, bool async)
 {
@@ -1212,12 +1254,38 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
     c->sweeps_run = 0;
     if (!pp || pp->struct_size != sizeof(hsflow_params))
         return fail(c, HSFLOW_E_ARG, "params null or struct_size mismatch");
-    const hsflow_params &p = *pp;
+    bool measured_small = false; // the planes were measured and hold nothing the solver could not have made itself
+    hsflow_params tamed; // (this call's parameters with the one-sweep kernel in place of the caller's, where no strip launch fits)
     if (!c->frames_set) return fail(c, HSFLOW_E_STATE, "frames were not set");
-    if (p.mode == HSFLOW_MODE_CLASSIC || p.mode == HSFLOW_MODE_CLASSIC_AS_SHIPPED) {
+    if (pp->mode == HSFLOW_MODE_CLASSIC || pp->mode == HSFLOW_MODE_CLASSIC_AS_SHIPPED) {
         if ((st = resolve_lazy_frames(c, false))) return st; // (the classic kernels read the context's planes)
-        return solve_classic(c, p, async);
+        c->flow_tame = false; // (its flow is bounded by nothing the CV planner knows)
+        return solve_classic(c, *pp, async);
     }
+    // Tame planes.  A cold solve, and a warm one on tame planes, pass through here without a launch or a wait.
+    c->t_cap = 0;
+    if (pp->mode == HSFLOW_MODE_CV && pp->lambda > 0.f) { // (anything else is refused below)
+        const float coeff = std::max(1.0f / pp->lambda, FLT_MIN);
+        const bool strip_like = pp->kernel == HSFLOW_KERNEL_AUTO || pp->kernel == HSFLOW_KERNEL_STRIP || pp->kernel == HSFLOW_KERNEL_FOLD ||
+                                pp->kernel == HSFLOW_KERNEL_PERSIST;
+        if (pp->use_previous && !c->flow_tame && strip_like) {
+            float m = 0.f;
+            if ((st = measure_flow_absmax(c, m))) return st;
+            // Tame planes reach 65536 sweeps x 2.6e12 (the constant term at lambda = 1e20), about 1.7e17: planes with nothing
+            // finite above 1e15 are as good as the solver's own, and count as tame again once this solve is accepted
+            measured_small = m <= 1e15f;
+            const bool budgeted = (pp->term_type & HSFLOW_TERM_ITER) && pp->max_iter > 0;
+            c->t_cap = flow_launch_cap(m, coeff, budgeted ? pp->max_iter : (1LL << 40));
+            if (c->t_cap == 0) { // not one sweep of scaled state fits: the one-sweep kernel, which keeps the canonical scale;
+                tamed = *pp;     // complete when the call returns, also where it was asked for asynchronously
+                tamed.kernel = HSFLOW_KERNEL_SIMPLE;
+                tamed.fuse_steps = tamed.tile_w = tamed.tile_h = tamed.threads = tamed.strip_rows = 0;
+                pp = &tamed;
+                if (pp->term_type & HSFLOW_TERM_EPS) async = false;
+            }
+        }
+    }
+    const hsflow_params &p = *pp;
     if (p.mode != HSFLOW_MODE_CV) return fail(c, HSFLOW_E_ARG, "unknown mode");
     if (stops_per_pair(c) && (p.term_type & HSFLOW_TERM_EPS) && p.kernel == HSFLOW_KERNEL_PERSIST)
         return fail(c, HSFLOW_E_ARG, "HSFLOW_KERNEL_PERSIST with hsflow_set_pair_termination on a batch under EPS termination: the persistent "
@@ -1235,6 +1303,7 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
     key.p.use_previous = key.p.reuse_derivatives = key.p.use_graph = key.p.profile = 0; // (do not enter the plan)
     key.async = async ? 1 : 0;
     key.exact = c->force_exact ? 1 : 0;
+    key.t_cap = c->t_cap;
     const bool cacheable = p.kernel != HSFLOW_KERNEL_PERSIST && !getenv("HSFLOW_PERSIST_AUTO");
     const PlanEntry *hit = nullptr;
     if (cacheable)
@@ -1255,6 +1324,10 @@ int solve_impl_inner(hsflow_ctx *c, const hsflow_params *pp, bool async, bool *t
             c->plan_cache.push_back(PlanEntry{key, S, c->info});
         }
     }
+    // (the solve is accepted: from here on the planes are what it makes of them)
+    if (!p.use_previous) c->flow_tame = S.coeff >= 1e-20f;
+    else if (S.coeff < 1e-20f) c->flow_tame = false;
+    else if (measured_small) c->flow_tame = true;
     c->info.deriv_ms = c->info.jacobi_ms = c->info.solve_ms = 0.f;
     c->info.last_eps = 0.f;
     Profiler prof{c, p.profile != 0};

@@ -232,6 +232,8 @@ int hsflow_destroy(hsflow_ctx *c)
     hipFree(c->dEps);
     hipFree(c->dPairs);
     hipFree(c->dEpsTiles); hipFree(c->dUb); hipFree(c->dVb);
+    hipFree(c->dFlowMax);
+    if (c->hFlowMax) hipHostFree(c->hFlowMax);
     hipFree(c->dUp); hipFree(c->dVp); hipFree(c->dFlags);
     hipFree(c->dSeq);
     hipFree(c->dZero);
@@ -743,10 +745,17 @@ int hsflow_get_flow_device(hsflow_ctx *c, int pair, int row0, int nrows, void *d
 
 int hsflow_set_flow_device(hsflow_ctx *c, int pair, int row0, int nrows, const void *du, size_t us, const void *dv, size_t vs)
 {
+    return hsflow_set_flow_device_ex(c, pair, row0, nrows, du, us, dv, vs, 0);
+}
+
+int hsflow_set_flow_device_ex(hsflow_ctx *c, int pair, int row0, int nrows, const void *du, size_t us, const void *dv, size_t vs, int flags)
+{
     int st = flow_rows_args(c, pair, row0, nrows, du, us, dv, vs);
     if (st) return st;
+    if (flags & ~HSFLOW_FLOW_SOLVER_MADE) return fail(c, HSFLOW_E_ARG, "hsflow_set_flow_device_ex: unknown flag");
     if ((st = settle_pending(c))) return st; // an unverified asynchronous solve still needs the old inputs
     c->lastl.valid = false;                  // (its last_eps can no longer be measured: the flow is about to change)
+    if (!(flags & HSFLOW_FLOW_SOLVER_MADE)) c->flow_tame = false; // (the caller's values: the next warm strip / fold solve measures the planes)
     const size_t rowb = (size_t)c->W * 4;
     const long long off = pair * c->plane + (long long)row0 * c->P;
     HS_HIP(c, hipMemcpy2DAsync(c->dU[c->cur] + off, (size_t)c->P * 4, du, us, rowb, nrows, hipMemcpyDeviceToDevice, c->stream));
@@ -835,6 +844,7 @@ int hsflow_calc_optical_flow_hs_8u32f(const uint8_t *prev, const uint8_t *curr, 
         hipError_t e = hipMemcpy2D(c->dU[c->cur], (size_t)c->P * 4, velx, (size_t)vel_step, rowb, height, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy2D(c->dV[c->cur], (size_t)c->P * 4, vely, (size_t)vel_step, rowb, height, hipMemcpyHostToDevice);
         if (e != hipSuccess) st = HSFLOW_E_DEVICE;
+        c->flow_tame = false;
     }
     if (!st) st = hsflow_solve(c, &p);
     if (!st) st = hsflow_get_flow(c, 0, velx, (size_t)vel_step, vely, (size_t)vel_step);

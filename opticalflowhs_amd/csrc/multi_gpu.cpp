@@ -299,7 +299,7 @@ int move_rows(hsflow_slab *s, Slab &S, int src_row, float *send, hipEvent_t sent
     else SL_HIP(s, hipMemcpyAsync(recv, send, 2 * plane * sizeof(float), hipMemcpyDeviceToDevice, D.stream));
     SL_HIP(s, hipEventRecord(took, D.stream));
     took_valid = true;
-    SL_CTX(s, D, hsflow_set_flow_device(D.ctx, 0, dst_row, s->halo, recv, rowb, recv + plane, rowb));
+    SL_CTX(s, D, hsflow_set_flow_device_ex(D.ctx, 0, dst_row, s->halo, recv, rowb, recv + plane, rowb, HSFLOW_FLOW_SOLVER_MADE)); // (a neighbour's rows)
     return HSFLOW_OK;
 }
 
@@ -468,7 +468,7 @@ int copy_flows(hsflow_slab *s, float *Slab::*buf, bool save)
         if (!(sl.*buf)) SL_HIP(s, hipMalloc((void **)&(sl.*buf), 2 * plane * sizeof(float)));
         float *b = sl.*buf;
         if (save) SL_CTX(s, sl, hsflow_get_flow_device(sl.ctx, 0, 0, sl.local_h, b, rowb, b + plane, rowb));
-        else SL_CTX(s, sl, hsflow_set_flow_device(sl.ctx, 0, 0, sl.local_h, b, rowb, b + plane, rowb));
+        else SL_CTX(s, sl, hsflow_set_flow_device_ex(sl.ctx, 0, 0, sl.local_h, b, rowb, b + plane, rowb, HSFLOW_FLOW_SOLVER_MADE)); // (its own flow, saved above)
     }
     return HSFLOW_OK;
 }

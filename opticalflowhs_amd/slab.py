@@ -151,7 +151,7 @@ class HSFlowSlabBackend(object):
     def put_rows(self, row0, u, v):
         if not self.enqueue_only:
             self.torch.cuda.synchronize(self.device)  # the received rows were written on torch's stream
-        self.ctx.set_flow_rows_from(u, v, row0, u.shape[0])
+        self.ctx.set_flow_rows_from(u, v, row0, u.shape[0], solver_made=True)  # (a neighbour's rows, or this slab's own saved flow)
         if not self.enqueue_only:
             self.ctx.synchronize()
 

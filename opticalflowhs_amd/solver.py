@@ -307,9 +307,11 @@ class HSFlow(object):
         self._check(self._lib.hsflow_get_flow_device(self._h, pair, row0, nrows, _ptr(u_dev),
                                                      u_dev.stride(0) * 4, _ptr(v_dev), v_dev.stride(0) * 4))
 
-    def set_flow_rows_from(self, u_dev, v_dev, row0, nrows, pair=0):
-        self._check(self._lib.hsflow_set_flow_device(self._h, pair, row0, nrows, _ptr(u_dev),
-                                                     u_dev.stride(0) * 4, _ptr(v_dev), v_dev.stride(0) * 4))
+    def set_flow_rows_from(self, u_dev, v_dev, row0, nrows, pair=0, solver_made=False):
+        """solver_made: the rows are flow a CV solve made (a neighbour slab's halo rows, this context's own saved flow):
+        HSFLOW_FLOW_SOLVER_MADE, the next warm solve does not measure the planes."""
+        self._check(self._lib.hsflow_set_flow_device_ex(self._h, pair, row0, nrows, _ptr(u_dev), u_dev.stride(0) * 4, _ptr(v_dev),
+                                                        v_dev.stride(0) * 4, 1 if solver_made else 0))
 
     def render(self, route="cv", out=None, pair=0, params=None, **kw):
         """The reference's picture of the current flow of `pair`, drawn on the device (`make_render_params`: route, step,

@@ -62,7 +62,8 @@ def calc_optical_flow_hs(A, B, lam, max_iter, epsilon=1e-6, term_type=TERMCRIT_I
         if term_type & TERMCRIT_EPS:
             du = np.abs((u.astype(np.float64) - un.astype(np.float64)).astype(np.float32))
             dv = np.abs((v.astype(np.float64) - vn.astype(np.float64)).astype(np.float32))
-            eps = np.float32(max(du.max(), dv.max()))
+            # the reference's `if (t > Eps) Eps = t` never takes a NaN: the maximum over the changes that are numbers
+            eps = np.float32(np.fmax.reduce(np.concatenate((du.ravel(), dv.ravel(), np.zeros(1, np.float32)))))
         u, v = un, vn
         if (term_type & TERMCRIT_ITER) and it == max_iter:
             break
