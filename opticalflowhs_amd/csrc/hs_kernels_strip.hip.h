@@ -634,13 +634,18 @@ __device__ __forceinline__ void eps_tail(const int T, const int seen_n, const bo
 // after the loop, so that the loop keeps the registers of the witness kernel.  The last sweep is peeled off in the other
 // forms too (file header) except EPS == 1; TWO: two sweeps per loop trip (the folded kernel).  (T by reference: the
 // strip kernel's sweep reads the same variable, the phase's count; by value the R = 5 derivative kernels take a register more.)
-template <int EPS, bool TWO, class Sweep>
+// MARK_LAST: the tag of the copy behind the loop carries kSweepLast on top of its Eps mode, and a sweep that asks for the mark
+// reads its Eps mode as the tag masked with kSweepLast - 1 -- so no Eps mode may reach 16.  (Only the strip kernel asks: its
+// sweep keeps the interior cross sums apart in the loop's copy alone, a matter of its register allocation.)
+constexpr int kSweepLast = 16;
+template <int EPS, bool TWO, bool MARK_LAST = false, class Sweep>
 __device__ __forceinline__ void run_sweeps(const int &T, const Sweep &sweep)
 {
+    constexpr int kLast = MARK_LAST ? kSweepLast : 0; // (the strip kernel's sweep wants to know which copy it is)
     if constexpr (EPS == 3) {
 #pragma unroll 1
         for (int s = 0; s + 1 < T; s++) sweep(s, std::integral_constant<int, 2>{});
-        sweep(T - 1, std::integral_constant<int, 1>{});
+        sweep(T - 1, std::integral_constant<int, 1 + kLast>{});
     } else if constexpr (EPS != 1) {
         int s = 0;
         if constexpr (TWO) {
@@ -652,7 +657,7 @@ __device__ __forceinline__ void run_sweeps(const int &T, const Sweep &sweep)
         }
 #pragma unroll 1
         for (; s + 1 < T; s++) sweep(s, std::integral_constant<int, EPS>{});
-        sweep(T - 1, std::integral_constant<int, EPS>{});
+        sweep(T - 1, std::integral_constant<int, EPS + kLast>{});
     } else {
         const int n = T; // (a copy: against the reference the every-sweep strip loops come out 2 blocks and 2 branches larger)
 #pragma unroll 1
@@ -770,10 +775,11 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     // rows has both far below zero and never loses a row), so the mask is two 64-bit tables of ones shifted by s and met
     // in one word -- no compare per row.  The optimiser must not see through it (it turns the bits back into
     // one compare and branch per row and boundary): the mask passes through an empty asm, as the lane number does.
-#define HS_ACT(r) (((act >> (r)) & 1u) != 0u)
+#define HS_LIKELY(c) (PERSIST ? !!(c) : __builtin_expect(!!(c), 1))
+#define HS_ACT(r) HS_LIKELY(((act >> (r)) & 1u) != 0u)
 #define HS_ROW(r, PE, SC, SP)                                                                      \
     do {                                                                                           \
-        if (((actr >> (r)) & 1u) != 0u) {                                                          \
+        if (HS_LIKELY(((actr >> (r)) & 1u) != 0u)) {                                               \
             f2 ouP, ouQ, ovP, ovQ;                                                                 \
             if (EM == 1) { ouP = uP[r]; ouQ = uQ[r]; ovP = vP[r]; ovQ = vQ[r]; }                   \
             if (HS_DIAG & 8) uP[r] += SC.uP + SP.uP;                                               \
@@ -781,7 +787,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
             if (EM == 1) {                                                                         \
                 if ((epscore >> (r)) & 1u) { /* wave-uniform; lanes outside the core are masked once per sweep */ \
                     const f2 dUP = sweep_diff(ouP, uP[r]), dUQ = sweep_diff(ouQ, uQ[r]), dVP = sweep_diff(ovP, vP[r]), dVQ = sweep_diff(ovQ, vQ[r]); \
-                    if (!xedge) { /* workgroup-uniform: every column of the region is an image column */ \
+                    if (HS_LIKELY(!xedge)) { /* workgroup-uniform: every column of the region is an image column */ \
                         e = fmaxf(fmaxf(e, fabsf(dUP.x)), fabsf(dUP.y));                           \
                         e = fmaxf(fmaxf(e, fabsf(dUQ.x)), fabsf(dUQ.y));                           \
                         e = fmaxf(fmaxf(e, fabsf(dVP.x)), fabsf(dVP.y));                           \
@@ -800,7 +806,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     // cross sums of the boundary below register row A (row B underneath), needed while either row is still swept
 #define HS_CROSS(S, PE, A, B)                                                                      \
     do {                                                                                           \
-        if (((actb >> (A)) & 1u) != 0u) { /* B is A + 1 */                                         \
+        if (HS_LIKELY(((actb >> (A)) & 1u) != 0u)) { /* B is A + 1 */                              \
             if (HS_DIAG & 8) S.uP = uP[A] + uP[B];                                                 \
             else cross_rows<PE>(S, uP[A], uQ[A], vP[A], vQ[A], uP[B], uQ[B], vP[B], vQ[B]);        \
         }                                                                                          \
@@ -856,7 +862,8 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     // in the loop, but the straight-line body keeps more values alive and the ITER kernel then spills inside the loop:
     // ITER|EPS 0.1573 -> 0.1556 ms, ITER 0.1522 -> 0.1555 ms at 1080p / 100.)
     auto sweep = [&](const int s, auto em_tag) __attribute__((always_inline)) {
-        constexpr int EM = decltype(em_tag)::value;
+        constexpr int EM = decltype(em_tag)::value & (kSweepLast - 1);
+        constexpr bool IN_LOOP = (decltype(em_tag)::value & kSweepLast) == 0; // (not the copy of the sweep behind the loop)
 #if HS_DIAG & 4 /* diagnostic build: every row swept in every sweep (no trapezoid) */
         unsigned act = ~0u;
 #else
@@ -896,7 +903,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
         float e = 0.f;
         constexpr int EL = E0 ^ ((R - 1) & 1); // parity of the last register row
         Cross sA, s0, sK, sL; // above row 0, below row 0, above row R-1, below row R-1
-        const bool wturn = EM == 2 && wit_cnt == 0; // wave-uniform: this wavefront is the sweep's witness
+        const bool wturn = EM == 2 && (PERSIST ? wit_cnt == 0 : __builtin_expect(wit_cnt == 0, 0)); // wave-uniform: this wavefront is the sweep's witness
         float w0 = 0.f;
         if (wturn) w0 = uP[0].x; // witness: u at column x0 of register row 0 before the sweep
         // --- first row (the strip's upper edge)
@@ -928,9 +935,13 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
         // --- interior rows, top to bottom: each needs the cross sum above it (kept) and the one below (new)
         if (R >= 3) {
             Cross sp = s0;
+            // (one object per boundary: a single `sc` declared in the loop body is ONE variable to the optimiser, so the sum of
+            // a boundary no longer needed was the previous boundary's, kept alive by four v_mov_b64 ahead of the guard in
+            // every sweep of every wavefront; apart, an unneeded sum is simply undefined)
+            Cross scs[R], sc1;
 #pragma unroll
             for (int r = 1; r < R - 1; r++) {
-                Cross sc;
+                Cross &sc = IN_LOOP && EM != 1 ? scs[r] : sc1; // (only where it pays: apart, a measured sweep and the copy behind the loop spill more)
                 if (r == R - 2) sc = sK;
                 else {
                     const int rn = r + 1 < R ? r + 1 : r;
@@ -985,7 +996,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
         pt_load += t - pt0;
         pt0 = t;
     }
-    run_sweeps<EPS, false>(Tp, sweep);
+    run_sweeps<EPS, false, true>(Tp, sweep);
     unsigned *const eps_ph = PERSIST ? eps_out + (size_t)ph * eps_stride : eps_out; // PERSIST: one row of words per phase
     eps_tail<EPS, true>(Tp, seen_n, wit_rot, w, NW, lane_id, eps_lds, eps_out, eps_ph, eps_stride);
     if (stamps) st2 = __builtin_amdgcn_s_memtime();
@@ -1099,6 +1110,7 @@ __device__ __forceinline__ void strip_body(const uint32_t *__restrict__ coef,
     } // phases
 #undef HS_ROW
 #undef HS_ACT
+#undef HS_LIKELY
 #undef HS_CROSS
 #undef HS_PUBLISH
     if (stamps && threadIdx.x == 0) {

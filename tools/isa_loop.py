@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Instruction mix of the sweep loop of the strip / fold kernels, from a device assembly file
-(hipcc -S --cuda-device-only ...).   usage: tools/isa_loop.py file.s [substring of the mangled kernel name ...] [--dump] [--inner]
+(hipcc -S --cuda-device-only ...).   usage: tools/isa_loop.py file.s [substring of the mangled kernel name ...] [--dump] [--inner] [--hot]
 The sweep loop = the strongly connected component of the kernel's control-flow graph that holds the most
 v_pk_fma_f32 (every block counted once, i.e. all rows active).  The issue estimate prices packed and DPP
-instructions at 4.2 cycles and the other VALU instructions at 2.3 (profiles/r01_ubench_valu.txt)."""
+instructions at 4.2 cycles and the other VALU instructions at 2.3 (profiles/r01_ubench_valu.txt).
+--hot walks ONE trip of that loop as a wavefront does whose rows are all core rows: every trapezoid guard -- s_bitcmp0/1_b32
+followed by s_cbranch_scc0/1 -- is taken as "bit set"; of any other conditional branch inside the loop (the witness's turn)
+the side with fewer instructions up to the loop header is followed, and a branch that can leave the loop stays in it.  It
+prints the instructions executed, the taken branches, the scalar instructions (s_* without branches, waits, s_nop and
+s_barrier) and the v_mov count of that path."""
 import re
 import sys
 from collections import Counter
@@ -109,6 +114,66 @@ def classify(body):
     return c
 
 
+def hot_path(order, ins):
+    """One trip of the loop with every guard bit set, from its header (the first block of the loop in layout order) back
+    to it: (executed instructions, taken branches, conditional branches followed by the shorter side)."""
+    inside = set(order)
+    nxt = {b: order[i + 1] if i + 1 < len(order) else None for i, b in enumerate(order)}
+    header = order[0]
+
+    def walk(b, i, seen):
+        out, taken, guessed = [], 0, 0
+        while True:
+            if (b, i) in seen:
+                return None  # an inner cycle that never reaches the header: not a path of one trip
+            seen = seen | {(b, i)}
+            code = ins[b]
+            jump = None
+            while i < len(code):
+                x = code[i]
+                out.append(x)
+                i += 1
+                m = re.match(r's_(c?)branch(\w*)\s+(\.LBB\d+_\d+)', x)
+                if not m:
+                    continue
+                tgt, cond = m.group(3), m.group(2)
+                if not m.group(1):
+                    jump = tgt
+                    break
+                prev = next((y for y in reversed(out[:-1]) if y.startswith('s_') and not y.startswith(('s_waitcnt', 's_nop'))), '')
+                g = re.match(r's_bitcmp([01])_b32', prev)
+                if g and cond in ('_scc0', '_scc1'):  # a guard: bit set -> s_bitcmp1 gives scc = 1, s_bitcmp0 gives scc = 0
+                    if (g.group(1) == '1') == (cond == '_scc1'):
+                        jump = tgt
+                        break
+                    continue
+                fall_ok = i < len(code) or nxt[b] in inside  # (what follows the branch in this block, or the next block of the loop)
+                if tgt not in inside:
+                    continue  # would leave the loop: stay
+                if not fall_ok:
+                    jump = tgt
+                    break
+                a = ([], 0, 0) if tgt == header else walk(tgt, 0, seen)  # both sides stay in the loop: the shorter one (a side that leaves it later does not count)
+                c = walk(b, i, seen - {(b, i)}) if i < len(code) else walk(nxt[b], 0, seen)
+                if a is None and c is None:
+                    return None
+                if c is None or (a is not None and len(a[0]) < len(c[0])):
+                    return out + a[0], taken + 1 + a[1], guessed + 1 + a[2]
+                return out + c[0], taken + c[1], guessed + 1 + c[2]
+            if jump is not None:
+                taken += 1
+                b = jump
+            else:
+                b = nxt[b]
+            i = 0
+            if b == header:
+                return out, taken, guessed
+            if b is None or b not in inside:
+                return None
+
+    return walk(header, 0, frozenset())
+
+
 def main():
     lines = open(sys.argv[1]).read().split('\n')
     pats = [a for a in sys.argv[2:] if not a.startswith('--')]
@@ -145,6 +210,14 @@ def main():
         c = classify(body)
         est = 4.2 * (c['v_pk'] + c['dpp']) + 2.3 * (c['v_mov'] + c['v_other'])
         print('%s\n  loop: %d blocks, %d instr, VALU issue estimate %.0f cycles per wavefront-sweep  %s' % (name, len(best), len(body), est, dict(sorted(c.items()))))
+        if '--hot' in sys.argv:
+            h = hot_path(order, ins)
+            if h is None:
+                print('  hot path: no walk from the loop header back to it')
+            else:
+                hc = classify(h[0])
+                print('  hot path (all guards active): %d instr executed, %d taken branches, %d scalar, %d v_mov   (%d other conditional branches followed by their shorter side)'
+                      % (len(h[0]), h[1], hc['s_other'], hc['v_mov'], h[2]))
         if '--dump' in sys.argv:
             for n in order:
                 print(n + ':')
