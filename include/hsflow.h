@@ -127,8 +127,32 @@ typedef struct hsflow_ctx hsflow_ctx;
 typedef struct hsflow_params {
     uint32_t struct_size; /* = sizeof(hsflow_params); guards ABI growth                  */
     int32_t mode;         /* HSFLOW_MODE_*                                               */
-    float lambda;         /* CV mode: Lagrange multiplier of cvCalcOpticalFlowHS         */
-    float alpha;          /* CLASSIC mode: smoothness weight (Kernels.cl:85)             */
+    float lambda;         /* CV mode: Lagrange multiplier of cvCalcOpticalFlowHS.  Any positive
+                             finite float, denormals included (1 / lambda = Inf: the flow stays
+                             zero, as in the original); anything else is HSFLOW_E_ARG.  The
+                             kernels use max(fl32(1 / lambda), FLT_MIN), which changes nothing
+                             a pixel can see.  (The test suite holds every kernel, over this
+                             whole range, to 4x the original's own distance from an all-double
+                             iteration on its test frames: DESIGN.md 5; no guarantee beyond
+                             them.)  Beyond lambda = 1e20 strip / fold launches have at
+                             most 8 iterations (info.fuse_steps).  The three largest floats
+                             (lambda > 3.4028229e38, FLT_MAX among them) are where this library
+                             and the original part: there the original's alpha of a pixel with
+                             Ix = Iy = 0 is fl32(1 / 2^-128) = Inf, 0 * Inf is NaN and spreads
+                             one pixel per iteration; this library's coefficients of such a
+                             pixel are 0 and its flow stays finite, the flow the neighbouring
+                             lambda gives.  Kept on purpose                              */
+    float alpha;          /* CLASSIC mode: smoothness weight (Kernels.cl:85).  Any positive
+                             finite float; the update divides by fl32(alpha * alpha) + Ex^2 +
+                             Ey^2 as Kernels.cl does, so the flow is the reference's bit for
+                             bit, NaN included: where alpha^2 underflows to zero (alpha below
+                             about 2.6e-23) a flat pixel divides 0 / 0, and below
+                             alpha^2 = 255 / FLT_MAX = 7.5e-37 (alpha below about 8.7e-19) a
+                             flat pixel with a frame difference divides to Inf and 0 * Inf
+                             follows; alpha^2 = Inf (alpha above 1.8e19) gives zero flow.
+                             The strip kernel takes 2^-40 <= fl32(alpha * alpha) <= 2^40
+                             (2^-20 <= alpha <= 2^20) and is HSFLOW_E_ARG outside; AUTO then
+                             runs the LDS-tile kernel                                    */
     int32_t term_type;    /* HSFLOW_TERM_ITER | HSFLOW_TERM_EPS                          */
     int32_t max_iter;     /* CvTermCriteria.max_iter                                     */
     double epsilon;       /* CvTermCriteria.epsilon (caller rounds through float if it
