@@ -36,6 +36,10 @@
  *                                          the same drawing and cvSaveImage (OpticalFlowOpenCV.cpp:32-47,
  *                                          HSOpticalFlowOpenCL.cpp:759-771) for every pair of a context at once: one set
  *                                          of launches per batch, N files out without a round trip per pair
+ *   hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device]
+ *                                          no counterpart in the reference, whose only picture is the arrow plot: the
+ *                                          DENSE field as the Middlebury colour wheel, drawn (and encoded) where the flow
+ *                                          lies instead of a read-back of both fp32 planes
  *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
  *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
  *                                          the pictures are decoded on the device
@@ -71,7 +75,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 15 /* 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 16 /* 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -684,6 +688,100 @@ int hsflow_render_flow_jpeg_batch_device(hsflow_ctx *ctx, int first_pair, int n,
 int hsflow_render_flow_jpeg_batch(hsflow_ctx *ctx, int first_pair, int n, const hsflow_render_params *rp, int quality,
                                   uint8_t *const *jpeg, size_t capacity, size_t *bytes /* n */);
 
+/* --- the dense colour picture (ABI 0.16) ---------------------------------------------------- */
+
+/* The arrow picture samples one pixel in `step` squared, hides what lies below its threshold and needs a scale from the
+ * caller.  The picture everybody's tools draw from a DENSE flow field is the Middlebury colour wheel (Baker et al.'s
+ * colorcode.cpp; KITTI's and Sintel's tools and flow_to_image reproduce it): hue is the direction, saturation the
+ * magnitude, zero flow is white, unknown flow is black.  These entries draw it where the flow lies -- of a 1080p pair
+ * 6.2 MB of picture (or its file) cross PCIe where both flow planes are 16.6 MB.  The rule is csrc/hs_color_rule.h, one
+ * header for the kernels and the host form; device and host give the same bytes.  All arithmetic is fp32, every operation
+ * rounded on its own (fl), sqrt and / correctly rounded.
+ *   The wheel: 55 entries by Middlebury's integer arithmetic -- RY 15: (255, 255 i / 15, 0); YG 6: (255 - 255 i / 6, 255, 0);
+ *   GC 4: (0, 255, 255 i / 4); CB 11: (0, 255 - 255 i / 11, 255); BM 13: (255 i / 13, 0, 255); MR 6: (255, 0, 255 - 255 i / 6).
+ *   One pixel, a = u[y][x], b = v[y][x]:
+ *   1. unknown iff isnan(a) || isnan(b) || fabsf(a) > 1e9f || fabsf(b) > 1e9f: the pixel is (0, 0, 0) and does not count
+ *      for the scale;
+ *   2. r = sqrtf(fl(fl(a*a) + fl(b*b)));
+ *   3. the scale m: HSFLOW_COLOR_SCALE_AUTO -- the maximum of r over the picture's known pixels, 1 if that is 0;
+ *      HSFLOW_COLOR_SCALE_FIXED -- max_flow.  rad = fl(r / m);
+ *   4. theta = the rule's own atan2 of (-b, -a) with C's signed-zero conventions: t = fl(min(|y|, |x|) / max(|y|, |x|)) (0 when
+ *      both are 0), p = t P(t t) with a six-term polynomial P (max |p - atan t| = 1.8e-6 on [0, 1]; coefficients in the
+ *      rule header), |y| > |x|: p = fl(pi/2 - p); signbit(x): p = fl(pi - p); signbit(y): p = -p;
+ *   5. fk = fl(fl(fl(fl(theta / pi) + 1) * 0.5f) * 54), k0 = min((int)fk, 54), k1 = k0 == 54 ? 0 : k0 + 1, f = fl(fk - k0);
+ *   6. per channel: c0 = fl(wheel[k0] / 255.0f), c1 alike; col = fl(fl(fl(1 - f) * c0) + fl(f * c1)); rad <= 1:
+ *      col = fl(fl(1 - rad) + fl(rad * col)), otherwise col = fl(col * 0.75f); the byte is (int)fl(255.0f * col).
+ * Three departures from the Middlebury program: the RADIUS is normalised, after the square root, not the components before
+ * it -- in AUTO mode rad <= 1 then holds exactly and the pixel that sets the scale cannot fall into the "> 1" branch by
+ * rounding; the atan2 is the rule's own, no library's; and the saturation 1 - rad (1 - col) is formed as
+ * (1 - rad) + rad col, the same quantity but exact at both ends: zero flow is (255, 255, 255) and a pixel on the scale
+ * shows the wheel's own levels, where fl(1 - fl(1 - col)) would lose a level for every wheel level 1 .. 64 and every even
+ * one up to 126 (43 / 255 would come out as 42); the sum never exceeds 1.  Against the same formula in float64 every channel is within
+ * one level wherever rad is not within 2^-20 of 1 (tests/test_color_host.py).  The wheel's seam is Middlebury's: flow
+ * (m, +0) is (255, 0, 0), flow (m, -0) is (255, 0, 43).
+ * The picture is RGB, 3 bytes per pixel, rows `stride` bytes apart; the bytes of a row beyond 3*width are left alone.  The
+ * AUTO maximum is a maximum and the pixels are independent: the bytes do not depend on the order of execution.
+ * Time on an MI355X (profiles/color_time.txt, device events around 200 calls): a 1080p picture 0.010 ms with a
+ * fixed scale and 0.039 ms with the picture's own (the maximum pass, a memset and a second launch), 0.008 / 0.020 ms per
+ * picture in a batch of 8; 600x480: 0.004 .. 0.009 / 0.013 ms alone, 0.002 / 0.009 ms in a batch of 8; hsflow_render_flow_device of the same 1080p pair 0.015 ms, a
+ * device-to-device copy of 19 bytes per pixel 0.010 ms.  The kernel is bound by the rule's arithmetic (a square root and
+ * three correctly rounded divisions per pixel), not by memory. */
+#define HSFLOW_COLOR_SCALE_AUTO 0  /* the picture's own largest radius */
+#define HSFLOW_COLOR_SCALE_FIXED 1 /* max_flow                          */
+typedef struct hsflow_color_params {
+    uint32_t struct_size; /* = sizeof(hsflow_color_params)                         */
+    int32_t scale_mode;   /* HSFLOW_COLOR_SCALE_*                                  */
+    float max_flow;       /* FIXED: the scale, finite and > 0; AUTO: not looked at */
+    int32_t reserved;
+} hsflow_color_params;
+/* HSFLOW_COLOR_SCALE_AUTO. */
+void hsflow_default_color_params(hsflow_color_params *cp);
+/* The rule on the host, no device needed (like hsflow_preprocess_frame_host): u and v are width x height floats, rows
+ * u_stride / v_stride BYTES apart; *scale_used (may be null) receives m.
+ * HSFLOW_E_ARG: null pointer, wrong struct_size, unknown scale mode, max_flow not finite or not > 0; HSFLOW_E_SIZE:
+ * non-positive size, a flow stride below 4*width or no multiple of 4, stride < 3*width. */
+int hsflow_color_flow_host(const float *u, size_t u_stride, const float *v, size_t v_stride, int width, int height,
+                           const hsflow_color_params *cp, uint8_t *rgb, size_t stride, float *scale_used /* may be null */);
+/* The pictures of the pairs first_pair .. first_pair + n - 1 into device memory, pair first_pair + i into d_rgb[i] (any
+ * alignment, each its own); only enqueued on ctx's stream, in chunks of at most HSFLOW_JPEG_BATCH_MAX pictures (the
+ * environment variable of that name is honoured as for the arrow pictures): per chunk, AUTO: one memset of the chunk's
+ * scale words and two launches -- the maximum is formed on the device, as the bit pattern of the non-negative float by
+ * an integer atomicMax, and read there; no value goes through the host -- FIXED: one launch.  Picture i is byte for byte
+ * that of hsflow_color_flow_host of pair i's flow, whatever its position, its neighbours, n or the chunking.
+ * The ordering rules of hsflow_render_flow_device apply word for word: an ITER|EPS check that hsflow_solve_async still
+ * owes is settled first, the flow is read and never changed, pointers from hsflow_flow_view_device stay valid, and on a
+ * context with hsflow_set_async_reduce hsflow_wait_solve and hsflow_flow_view_device called after it wait for the stream.
+ * After a solve with hsflow_set_pair_termination pair i's picture is that of its own final flow.  The first colour call
+ * of a context allocates its scale words (128 bytes), kept until hsflow_destroy; they do not count for
+ * HSFLOW_KERNEL_PERSIST's "only one alive" rule, and contexts that never colour pay nothing.  Every argument is checked
+ * before anything is enqueued.
+ * HSFLOW_E_ARG: null pointer, list or entry, wrong struct_size, unknown scale mode, bad max_flow, n < 1, first_pair < 0 or
+ * first_pair + n > n_pairs, the environment value unusable; HSFLOW_E_SIZE: stride < 3*width. */
+int hsflow_color_flow_batch_device(hsflow_ctx *ctx, int first_pair, int n, const hsflow_color_params *cp,
+                                   void *const *d_rgb, size_t stride);
+/* A batch of one. */
+int hsflow_color_flow_device(hsflow_ctx *ctx, int pair, const hsflow_color_params *cp, void *d_rgb, size_t stride);
+/* The same into host memory, synchronous: drawn into the picture the context keeps on the device (the one
+ * hsflow_render_flow uses), copied to rgb, complete on return; *scale_used (may be null) receives m.  Waits only for what
+ * this context enqueued.  Page-locked destination for the full PCIe rate. */
+int hsflow_color_flow(hsflow_ctx *ctx, int pair, const hsflow_color_params *cp, uint8_t *rgb, size_t stride,
+                      float *scale_used /* may be null */);
+/* The colour picture + its file: hsflow_color_flow_batch_device into pictures the context keeps (those of
+ * hsflow_render_flow_jpeg_batch*) + hsflow_jpeg_encode_batch_device, behind each other on the stream.  Capacity, size
+ * words, errors and what crosses PCIe are exactly those of hsflow_render_flow_jpeg_batch_device / _batch; the single forms
+ * are batches of one, with the capacity and size semantics of hsflow_render_flow_jpeg_device / hsflow_render_flow_jpeg.
+ * File i is byte for byte hsflow_jpeg_encode_host of hsflow_color_flow_host's picture.  A dense picture makes a LARGE
+ * file -- several hundred KB at 1080p and quality 95 where an arrow picture has tens: hsflow_jpeg_bound is the capacity
+ * to pass. */
+int hsflow_color_flow_jpeg_batch_device(hsflow_ctx *ctx, int first_pair, int n, const hsflow_color_params *cp, int quality,
+                                        void *const *d_jpeg, size_t capacity, uint64_t *d_bytes);
+int hsflow_color_flow_jpeg_batch(hsflow_ctx *ctx, int first_pair, int n, const hsflow_color_params *cp, int quality,
+                                 uint8_t *const *jpeg, size_t capacity, size_t *bytes /* n */);
+int hsflow_color_flow_jpeg_device(hsflow_ctx *ctx, int pair, const hsflow_color_params *cp, int quality,
+                                  void *d_jpeg, size_t capacity, uint64_t *d_bytes);
+int hsflow_color_flow_jpeg(hsflow_ctx *ctx, int pair, const hsflow_color_params *cp, int quality,
+                           uint8_t *jpeg, size_t capacity, size_t *bytes);
+
 /* --- the input files (cvLoadImage) ---------------------------------------------------------- */
 
 /* The reference reads its two frames with cvLoadImage(path, 1) (OpticalFlowOpenCV.cpp:15,18, HSOpticalFlowOpenCL.cpp:721,
@@ -1008,6 +1106,13 @@ int hsflow_pipeline_wait(hsflow_pipeline *pl, uint64_t ticket); /* u, v of that 
  * errors as hsflow_render_flow_device. */
 int hsflow_pipeline_render(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, uint8_t *rgb, size_t stride);
 int hsflow_pipeline_render_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, void *d_rgb, size_t stride);
+/* The same three for the dense colour picture (hsflow_color_flow, hsflow_color_flow_device, hsflow_color_flow_jpeg of the
+ * ticket's slot): complete on return, HSFLOW_E_STATE if the slot has been reused already, otherwise their errors. */
+int hsflow_pipeline_color(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, uint8_t *rgb, size_t stride,
+                          float *scale_used /* may be null */);
+int hsflow_pipeline_color_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, void *d_rgb, size_t stride);
+int hsflow_pipeline_color_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, int quality,
+                               uint8_t *jpeg, size_t capacity, size_t *bytes);
 /* wait(ticket) + the JPEG file of that pair's picture (hsflow_render_flow_jpeg of its slot): complete on return.
  * HSFLOW_E_STATE if the slot has been reused already; otherwise the errors of hsflow_render_flow_jpeg. */
 int hsflow_pipeline_render_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, int quality,

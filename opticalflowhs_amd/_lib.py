@@ -16,6 +16,7 @@ MODE_CV, MODE_CLASSIC, MODE_CLASSIC_AS_SHIPPED = 0, 1, 2
 KERNEL_AUTO, KERNEL_SIMPLE, KERNEL_FUSED, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST = 0, 1, 2, 3, 4, 5
 FRAMES_GRAY8, FRAMES_GRAY8_BLUR, FRAMES_BGR8, FRAMES_BGR8_BLUR = 0, 1, 2, 3
 RENDER_CV, RENDER_CL = 0, 1
+COLOR_SCALE_AUTO, COLOR_SCALE_FIXED = 0, 1
 JPEG_ORDER_BGR, JPEG_ORDER_RGB = 0, 1
 JPEGD_SUBSEQ_BITS = 1024  # HSFLOW_JPEGD_SUBSEQ_BITS
 JPEGD_BATCH_MAX = 32  # HSFLOW_JPEGD_BATCH_MAX
@@ -54,6 +55,10 @@ class HsflowRenderParams(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("step", ctypes.c_int32),
                 ("threshold", ctypes.c_float), ("scale", ctypes.c_float),
                 ("dot_rgb", ctypes.c_uint8 * 3), ("line_rgb", ctypes.c_uint8 * 3), ("pad", ctypes.c_uint8 * 2)]
+
+
+class HsflowColorParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("scale_mode", ctypes.c_int32), ("max_flow", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
 class HsflowPlaneDiff(ctypes.Structure):
@@ -96,6 +101,8 @@ PRE_STRIP_ROWS = 8  # HSFLOW_PRE_STRIP_ROWS
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 _pp = ctypes.POINTER(HsflowParams)
 _rp = ctypes.POINTER(HsflowRenderParams)
+_cp = ctypes.POINTER(HsflowColorParams)
+_fp = ctypes.POINTER(ctypes.c_float)
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
 _ji = ctypes.POINTER(HsflowJpegInfo)
@@ -152,6 +159,15 @@ PROTOTYPES = {
     "hsflow_render_flow_batch_device": (_i, [_vp, _i, _i, _rp, _vp, _sz]),
     "hsflow_render_flow_jpeg_batch_device": (_i, [_vp, _i, _i, _rp, _i, _vp, _sz, _vp]),
     "hsflow_render_flow_jpeg_batch": (_i, [_vp, _i, _i, _rp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
+    "hsflow_default_color_params": (None, [_cp]),
+    "hsflow_color_flow_host": (_i, [_vp, _sz, _vp, _sz, _i, _i, _cp, _vp, _sz, _fp]),
+    "hsflow_color_flow_batch_device": (_i, [_vp, _i, _i, _cp, _vp, _sz]),
+    "hsflow_color_flow_device": (_i, [_vp, _i, _cp, _vp, _sz]),
+    "hsflow_color_flow": (_i, [_vp, _i, _cp, _vp, _sz, _fp]),
+    "hsflow_color_flow_jpeg_batch_device": (_i, [_vp, _i, _i, _cp, _i, _vp, _sz, _vp]),
+    "hsflow_color_flow_jpeg_batch": (_i, [_vp, _i, _i, _cp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
+    "hsflow_color_flow_jpeg_device": (_i, [_vp, _i, _cp, _i, _vp, _sz, _vp]),
+    "hsflow_color_flow_jpeg": (_i, [_vp, _i, _cp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
     "hsflow_jpeg_read_header": (_i, [_vp, _sz, _ji]),
     "hsflow_jpeg_decode_host": (_i, [_vp, _sz, _i, _vp, _sz, _ji]),
     "hsflow_jpeg_decode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
@@ -195,6 +211,9 @@ PROTOTYPES = {
     "hsflow_pipeline_render": (_i, [_vp, ctypes.c_uint64, _rp, _vp, _sz]),
     "hsflow_pipeline_render_jpeg": (_i, [_vp, ctypes.c_uint64, _rp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
     "hsflow_pipeline_render_device": (_i, [_vp, ctypes.c_uint64, _rp, _vp, _sz]),
+    "hsflow_pipeline_color": (_i, [_vp, ctypes.c_uint64, _cp, _vp, _sz, _fp]),
+    "hsflow_pipeline_color_jpeg": (_i, [_vp, ctypes.c_uint64, _cp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
+    "hsflow_pipeline_color_device": (_i, [_vp, ctypes.c_uint64, _cp, _vp, _sz]),
     "hsflow_pipeline_info": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(HsflowInfo)]),
     "hsflow_pipeline_drain": (_i, [_vp]),
     "hsflow_pipeline_depth": (_i, [_vp]),

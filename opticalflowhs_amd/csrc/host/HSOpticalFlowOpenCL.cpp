@@ -61,14 +61,55 @@ int verify_pair(hsflow_ctx *ctx, int W, hsflow_verify_report &report, int pair =
     return report.ok ? SDK_SUCCESS : SDK_FAILURE;
 }
 
-// The device route of both drawings: the picture of ctx's current flow into imgFlow.
+// HSFLOW_PICTURE=color: every route writes the dense colour picture (hsflow_color_flow*: the Middlebury wheel) instead
+// of the arrows; "arrows", or no variable, leaves everything as it was.  0: arrows, 1: colour, -1: unusable.
+int picture_kind()
+{
+    const char *e = getenv("HSFLOW_PICTURE");
+    if (!e || !*e || strcmp(e, "arrows") == 0) return 0;
+    return strcmp(e, "color") == 0 ? 1 : -1;
+}
+
+bool color_picture() { return picture_kind() == 1; }
+
+// HSFLOW_COLOR_MAX=<float>: the colour picture's scale is that flow (HSFLOW_COLOR_SCALE_FIXED); without it the picture's
+// own largest flow (AUTO).  false: the value is unusable.
+bool color_params(hsflow_color_params &cp)
+{
+    hsflow_default_color_params(&cp);
+    const char *e = getenv("HSFLOW_COLOR_MAX");
+    if (!e || !*e) return true;
+    char *rest = nullptr;
+    const float m = strtof(e, &rest);
+    if (*rest || !std::isfinite(m) || !(m > 0.f)) return false;
+    cp.scale_mode = HSFLOW_COLOR_SCALE_FIXED;
+    cp.max_flow = m;
+    return true;
+}
+
+// The host route of the colour picture: the rule on the host, applied to the flow that was read back.
+int color_on_host(pnm::Image &imgFlow, const std::vector<float> &u, const std::vector<float> &v, int W, int H)
+{
+    imgFlow.width = W; imgFlow.height = H; imgFlow.channels = 3;
+    imgFlow.data.resize((size_t)W * H * 3);
+    hsflow_color_params cp;
+    color_params(cp);
+    const int st = hsflow_color_flow_host(u.data(), (size_t)W * 4, v.data(), (size_t)W * 4, W, H, &cp, imgFlow.data.data(), (size_t)W * 3, nullptr);
+    if (st != HSFLOW_OK) std::cout << hsflow_last_error(nullptr) << std::endl;
+    return st == HSFLOW_OK ? SDK_SUCCESS : SDK_FAILURE;
+}
+
+// The device route of both drawings, and of the colour picture: the picture of ctx's current flow into imgFlow.
 int draw_on_device(hsflow_ctx *ctx, int preset, int W, int H, pnm::Image &imgFlow, int pair = 0)
 {
     imgFlow.width = W; imgFlow.height = H; imgFlow.channels = 3;
     imgFlow.data.resize((size_t)W * H * 3);
     hsflow_render_params rp;
     hsflow_default_render_params(&rp, preset);
-    const int st = hsflow_render_flow(ctx, pair, &rp, imgFlow.data.data(), (size_t)W * 3);
+    hsflow_color_params cp;
+    color_params(cp);
+    const int st = color_picture() ? hsflow_color_flow(ctx, pair, &cp, imgFlow.data.data(), (size_t)W * 3, nullptr)
+                                   : hsflow_render_flow(ctx, pair, &rp, imgFlow.data.data(), (size_t)W * 3);
     if (st != HSFLOW_OK) std::cout << hsflow_last_error(ctx) << std::endl;
     return st == HSFLOW_OK ? SDK_SUCCESS : SDK_FAILURE;
 }
@@ -96,9 +137,12 @@ int save_jpeg_from_device(hsflow_ctx *ctx, int preset, int W, int H, const std::
 {
     hsflow_render_params rp;
     hsflow_default_render_params(&rp, preset);
+    hsflow_color_params cp;
+    color_params(cp);
     std::vector<uint8_t> file(hsflow_jpeg_bound(W, H));
     size_t n = 0;
-    const int st = hsflow_render_flow_jpeg(ctx, 0, &rp, 95, file.data(), file.size(), &n);
+    const int st = color_picture() ? hsflow_color_flow_jpeg(ctx, 0, &cp, 95, file.data(), file.size(), &n)
+                                   : hsflow_render_flow_jpeg(ctx, 0, &rp, 95, file.data(), file.size(), &n);
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
     FILE *f = fopen(output.c_str(), "wb");
     if (!f) return SDK_FAILURE;
@@ -107,6 +151,14 @@ int save_jpeg_from_device(hsflow_ctx *ctx, int preset, int W, int H, const std::
 }
 
 } // namespace
+
+bool picture_choice_usable()
+{
+    hsflow_color_params cp;
+    if (picture_kind() < 0) { std::cout << "HSFLOW_PICTURE must be color or arrows" << std::endl; return false; }
+    if (!color_params(cp)) { std::cout << "HSFLOW_COLOR_MAX must be a finite number > 0" << std::endl; return false; }
+    return true;
+}
 
 HSOpticalFlowOpenCL::HSOpticalFlowOpenCL(const char *name, char *src_, char *in1, char *in2, char *out, float alp,
                                          int it, int gs, char *dType)
@@ -185,6 +237,7 @@ int HSOpticalFlowOpenCL::solvePair(const pnm::Image &a, const pnm::Image &b, boo
 int HSOpticalFlowOpenCL::drawFlow(pnm::Image &imgFlow) const
 {
     if (render_on_device()) return draw_on_device(ctx, HSFLOW_RENDER_CL, (int)width, (int)height, imgFlow);
+    if (color_picture()) return color_on_host(imgFlow, u, v, (int)width, (int)height);
     imgFlow.width = width; imgFlow.height = height; imgFlow.channels = 3;
     imgFlow.data.assign((size_t)width * height * 3, 0);
     const int step = 4;
@@ -302,9 +355,11 @@ int HSOpticalFlowOpenCL::run()
 
 // ---- GPU counterpart of OpticalFlowOpenCV (OpticalFlowHS/OpticalFlowOpenCV.cpp:7-52) --------------
 
-// arrows of the CPU route: 4-pixel grid, |.| > 1, half length (OpticalFlowOpenCV.cpp:33-46, :98-111)
+// arrows of the CPU route: 4-pixel grid, |.| > 1, half length (OpticalFlowOpenCV.cpp:33-46, :98-111); with
+// HSFLOW_PICTURE=color the dense colour picture instead
 static void draw_cv_flow(pnm::Image &imgFlow, const std::vector<float> &u, const std::vector<float> &v, int W, int H)
 {
+    if (color_picture()) { (void)color_on_host(imgFlow, u, v, W, H); return; } // (its arguments were checked at the start)
     imgFlow.width = W; imgFlow.height = H; imgFlow.channels = 3;
     imgFlow.data.assign((size_t)W * H * 3, 0);
     for (int y = 0; y < H; y += 4)

@@ -10,6 +10,10 @@
 // downloaded; the files written are the same.
 // HSFLOW_JPEG_DEVICE=1 with it, and an output name ending in .jpg / .jpeg (the two -hd routes): the file is encoded on
 // the device too (hsflow_render_flow_jpeg) and written as it is; the same bytes.
+// HSFLOW_PICTURE=color: every route writes the dense colour picture of the flow (the Middlebury wheel; include/hsflow.h,
+// hsflow_color_flow*) instead of the arrows -- by the host rule from the flow read back, with HSFLOW_RENDER_DEVICE=1 drawn
+// on the device, with HSFLOW_JPEG_DEVICE=1 encoded there too; the same bytes every way.  HSFLOW_COLOR_MAX=<float>: the
+// flow that is fully saturated (default: the picture's own largest).  An unusable value of either: a message, exit status 1.
 // HSFLOW_VERIFY=1: every solved pair is verified on the device (hsflow_verify: re-solved sweep by sweep, compared
 // there) before its context goes away; one "Passed!" / "Failed" line per pair on stdout, the pictures are written as
 // always, and the exit status is SDK_FAILURE if any pair failed.
@@ -49,6 +53,7 @@ int main(int argc, char *argv[])
         std::cout << "No parameters given.\n";
         return 0;
     }
+    if (!picture_choice_usable()) return 1;
     if (argc >= 3 && strcmp(argv[1], "-cl") == 0) {
         if (strcmp(argv[2], "-hd") == 0) {
             if (argc != 10) { std::cout << "Wrong argument list!\n"; return 0; }

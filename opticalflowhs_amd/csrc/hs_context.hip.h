@@ -171,6 +171,12 @@ struct hsflow_ctx {
     bool prio_dirty = false;    // a render failed between its two launches: clear the plane before the next one
     uint8_t *dRgb = nullptr;
     hipEvent_t evRender = nullptr;
+    // hsflow_color_flow* (hs_color.hip.h), allocated by the first colour picture: one scale word per picture of a chunk
+    // (the largest raw radius as a bit pattern, written and read on the device) and a page-locked word for the one the
+    // synchronous form hands to its caller.  The pictures the synchronous and JPEG forms draw into are dRgb and
+    // jpeg_batch.rgb, shared with the arrow drawing: everything of a context runs on one stream.
+    unsigned *dColorScale = nullptr;
+    unsigned *hColorScale = nullptr;
     // hsflow_jpeg_encode_device and the render-and-encode forms (hs_jpeg.hip.h), allocated by the first encode and kept:
     // one block of device memory carved into the coefficients (128 B per block), the blocks' bit lengths and offsets, the
     // raw stream (208 B per block), the chunks' 0xFF counts and offsets and a size word; the tables and header of every

@@ -191,29 +191,36 @@ int check_jpeg_batch_args(hsflow_ctx *c, int n, int quality, const void *const *
     return HSFLOW_OK;
 }
 
-// The checks the two batched render-and-encode forms share, then the owed ITER|EPS check settled and everything a chunk
+// What a batch draws in front of its encode: the reference's arrows (rp) or the colour picture (cp, hs_color.hip.h).
+struct Drawing {
+    bool color;
+    const hsflow_render_params *rp;
+    const hsflow_color_params *cp;
+};
+
+// The checks the batched draw-and-encode forms share, then the owed ITER|EPS check settled and everything a chunk
 // needs on the device there.  *maxb: the chunk size of this call.
-int render_jpeg_batch_begin(hsflow_ctx *c, int first_pair, int n, const hsflow_render_params *rp, int quality, const void *const *jpeg, const void *bytes,
+int render_jpeg_batch_begin(hsflow_ctx *c, int first_pair, int n, const Drawing &d, int quality, const void *const *jpeg, const void *bytes,
                             bool aligned8, int *maxb, hsjpeg::Tables **tab)
 {
     int st = check_ctx(c, 0);
     if (st) return st;
     if ((st = check_batch_pairs(c, first_pair, n))) return st;
-    if ((st = check_render_params(c, rp))) return st;
+    if ((st = d.color ? check_color_params(c, d.cp) : check_render_params(c, d.rp))) return st;
     if ((st = check_jpeg_batch_args(c, n, quality, jpeg, bytes))) return st;
     if (aligned8 && ((uintptr_t)bytes & 7u)) return fail(c, HSFLOW_E_ARG, "the size words must be 8-byte aligned");
     if ((st = check_batch_max(c, maxb))) return st;
     if ((st = settle_pending(c))) return st;
     const int most = n < *maxb ? n : *maxb;
     if ((st = jpeg_tables(c, quality, tab))) return st;
-    if ((st = render_batch_reserve(c, most))) return st;
+    if ((st = d.color ? color_reserve(c) : render_batch_reserve(c, most))) return st;
     if ((st = jpeg_batch_reserve_rgb(c, most))) return st;
     return jpeg_batch_reserve(c, most);
 }
 
 // The pictures of cnt pairs from first_pair on into the context's own pictures, and their encodes into out[k] /
 // d_bytes[k], behind each other on the stream.
-int enqueue_render_jpeg_chunk(hsflow_ctx *c, int first_pair, int cnt, const hsflow_render_params &rp, const hsjpeg::Tables *tab, uint8_t *const *out,
+int enqueue_render_jpeg_chunk(hsflow_ctx *c, int first_pair, int cnt, const Drawing &d, const hsjpeg::Tables *tab, uint8_t *const *out,
                               size_t capacity, uint64_t *d_bytes)
 {
     const size_t rowb = (size_t)c->W * 3, span = jpeg_batch_rgb_span(c);
@@ -225,9 +232,73 @@ int enqueue_render_jpeg_chunk(hsflow_ctx *c, int first_pair, int cnt, const hsfl
         jpics.p[k] = jpeg_batch_pic(pic, rowb, out[k], capacity);
         if (jpics.p[k].wide) rpics.wide |= 1u << k;
     }
-    int st = enqueue_render_chunk(c, first_pair, cnt, rp, rpics, rowb);
+    int st = d.color ? enqueue_color_chunk(c, first_pair, cnt, *d.cp, rpics, rowb) : enqueue_render_chunk(c, first_pair, cnt, *d.rp, rpics, rowb);
     if (st) return st;
     return enqueue_jpeg_chunk(c, tab, jpics, cnt, rowb, d_bytes);
+}
+
+// hsflow_render_flow_jpeg_batch_device and hsflow_color_flow_jpeg_batch_device: the pictures of a batch drawn into the
+// context's own and encoded behind each other on the stream, only enqueued.
+int draw_jpeg_batch_device(hsflow_ctx *c, int first_pair, int n, const Drawing &d, int quality, void *const *d_jpeg, size_t capacity, uint64_t *d_bytes)
+{
+    int maxb = 0;
+    hsjpeg::Tables *tab = nullptr;
+    int st = render_jpeg_batch_begin(c, first_pair, n, d, quality, d_jpeg, d_bytes, true, &maxb, &tab);
+    if (st) return st;
+    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb))
+        if ((st = enqueue_render_jpeg_chunk(c, first_pair + ch.first, ch.count, d, tab, (uint8_t *const *)d_jpeg + ch.first, capacity, d_bytes + ch.first)))
+            return st;
+    return HSFLOW_OK;
+}
+
+// hsflow_render_flow_jpeg_batch and hsflow_color_flow_jpeg_batch: the same into host memory, complete on return.
+int draw_jpeg_batch(hsflow_ctx *c, int first_pair, int n, const Drawing &d, int quality, uint8_t *const *jpeg, size_t capacity, size_t *bytes)
+{
+    int maxb = 0;
+    hsjpeg::Tables *tab = nullptr;
+    int st = render_jpeg_batch_begin(c, first_pair, n, d, quality, (const void *const *)jpeg, bytes, false, &maxb, &tab);
+    if (st) return st;
+    hsflow_ctx::JpegBatchScratch &b = c->jpeg_batch;
+    const int most = n < maxb ? n : maxb;
+    const size_t bound = hsjpeg::bound(c->W, c->H), cap = capacity < bound ? capacity : bound, slot = hsjpeg_plan::up256(cap ? cap : 1);
+    if (b.slot < slot || b.out_pictures < most) { // (the synchronous form leaves nothing in flight that writes the old ones)
+        const size_t s = b.slot > slot ? b.slot : slot;
+        const int pictures = b.out_pictures > most ? b.out_pictures : most;
+        hipFree(b.out);
+        b.out = nullptr; b.slot = 0; b.out_pictures = 0;
+        HS_HIP(c, hipMalloc((void **)&b.out, s * (size_t)pictures));
+        b.slot = s; b.out_pictures = pictures;
+    }
+    if (!b.hSize) HS_HIP(c, hipHostMalloc((void **)&b.hSize, sizeof(uint64_t) * hsk::kJpegBatchMax, hipHostMallocDefault));
+    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
+    const bool marked = c->last_marked;
+    bool fits = true;
+    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb)) {
+        uint8_t *out[hsk::kJpegBatchMax];
+        for (int k = 0; k < ch.count; k++) out[k] = b.out + b.slot * (size_t)k;
+        uint64_t *words = jpeg_batch_size_words(c);
+        if ((st = enqueue_render_jpeg_chunk(c, first_pair + ch.first, ch.count, d, tab, out, cap, words))) return st;
+        // the chunk's size words in one copy, then each file's bytes: only the files cross, and what THIS context enqueued
+        // is all that is waited for
+        HS_HIP(c, hipMemcpyAsync(b.hSize, words, sizeof(uint64_t) * (size_t)ch.count, hipMemcpyDeviceToHost, c->stream));
+        HS_HIP(c, hipEventRecord(c->evRender, c->stream));
+        HS_HIP(c, hipEventSynchronize(c->evRender));
+        bool any = false;
+        for (int k = 0; k < ch.count; k++) {
+            const uint64_t size = b.hSize[k];
+            bytes[ch.first + k] = (size_t)size;
+            if (size > capacity) { fits = false; continue; }
+            HS_HIP(c, hipMemcpyAsync(jpeg[ch.first + k], out[k], (size_t)size, hipMemcpyDeviceToHost, c->stream));
+            any = true;
+        }
+        if (any) {
+            HS_HIP(c, hipEventRecord(c->evRender, c->stream));
+            HS_HIP(c, hipEventSynchronize(c->evRender));
+        }
+    }
+    c->last_marked = marked; // nothing of this call is in flight any more: the solve's marker speaks for the context again
+    if (!fits) return fail(c, HSFLOW_E_SIZE, "capacity smaller than a file (hsflow_jpeg_bound always suffices)");
+    return check_persist(c);
 }
 
 } // namespace
@@ -329,64 +400,42 @@ int hsflow_jpeg_encode_batch_device(hsflow_ctx *c, const void *const *d_rgb, int
 int hsflow_render_flow_jpeg_batch_device(hsflow_ctx *c, int first_pair, int n, const hsflow_render_params *rp, int quality, void *const *d_jpeg,
                                          size_t capacity, uint64_t *d_bytes)
 {
-    int maxb = 0;
-    hsjpeg::Tables *tab = nullptr;
-    int st = render_jpeg_batch_begin(c, first_pair, n, rp, quality, d_jpeg, d_bytes, true, &maxb, &tab);
-    if (st) return st;
-    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb))
-        if ((st = enqueue_render_jpeg_chunk(c, first_pair + ch.first, ch.count, *rp, tab, (uint8_t *const *)d_jpeg + ch.first, capacity, d_bytes + ch.first)))
-            return st;
-    return HSFLOW_OK;
+    return draw_jpeg_batch_device(c, first_pair, n, Drawing{false, rp, nullptr}, quality, d_jpeg, capacity, d_bytes);
 }
 
 int hsflow_render_flow_jpeg_batch(hsflow_ctx *c, int first_pair, int n, const hsflow_render_params *rp, int quality, uint8_t *const *jpeg, size_t capacity,
                                   size_t *bytes)
 {
-    int maxb = 0;
-    hsjpeg::Tables *tab = nullptr;
-    int st = render_jpeg_batch_begin(c, first_pair, n, rp, quality, (const void *const *)jpeg, bytes, false, &maxb, &tab);
+    return draw_jpeg_batch(c, first_pair, n, Drawing{false, rp, nullptr}, quality, jpeg, capacity, bytes);
+}
+
+// The colour picture's files (hs_color.hip.h draws, the chain above encodes); the single forms are batches of one.
+int hsflow_color_flow_jpeg_batch_device(hsflow_ctx *c, int first_pair, int n, const hsflow_color_params *cp, int quality, void *const *d_jpeg,
+                                        size_t capacity, uint64_t *d_bytes)
+{
+    return draw_jpeg_batch_device(c, first_pair, n, Drawing{true, nullptr, cp}, quality, d_jpeg, capacity, d_bytes);
+}
+
+int hsflow_color_flow_jpeg_batch(hsflow_ctx *c, int first_pair, int n, const hsflow_color_params *cp, int quality, uint8_t *const *jpeg, size_t capacity,
+                                 size_t *bytes)
+{
+    return draw_jpeg_batch(c, first_pair, n, Drawing{true, nullptr, cp}, quality, jpeg, capacity, bytes);
+}
+
+int hsflow_color_flow_jpeg_device(hsflow_ctx *c, int pair, const hsflow_color_params *cp, int quality, void *d_jpeg, size_t capacity, uint64_t *d_bytes)
+{
+    int st = check_ctx(c, pair);
     if (st) return st;
-    hsflow_ctx::JpegBatchScratch &b = c->jpeg_batch;
-    const int most = n < maxb ? n : maxb;
-    const size_t bound = hsjpeg::bound(c->W, c->H), cap = capacity < bound ? capacity : bound, slot = hsjpeg_plan::up256(cap ? cap : 1);
-    if (b.slot < slot || b.out_pictures < most) { // (the synchronous form leaves nothing in flight that writes the old ones)
-        const size_t s = b.slot > slot ? b.slot : slot;
-        const int pictures = b.out_pictures > most ? b.out_pictures : most;
-        hipFree(b.out);
-        b.out = nullptr; b.slot = 0; b.out_pictures = 0;
-        HS_HIP(c, hipMalloc((void **)&b.out, s * (size_t)pictures));
-        b.slot = s; b.out_pictures = pictures;
-    }
-    if (!b.hSize) HS_HIP(c, hipHostMalloc((void **)&b.hSize, sizeof(uint64_t) * hsk::kJpegBatchMax, hipHostMallocDefault));
-    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
-    const bool marked = c->last_marked;
-    bool fits = true;
-    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb)) {
-        uint8_t *out[hsk::kJpegBatchMax];
-        for (int k = 0; k < ch.count; k++) out[k] = b.out + b.slot * (size_t)k;
-        uint64_t *words = jpeg_batch_size_words(c);
-        if ((st = enqueue_render_jpeg_chunk(c, first_pair + ch.first, ch.count, *rp, tab, out, cap, words))) return st;
-        // the chunk's size words in one copy, then each file's bytes: only the files cross, and what THIS context enqueued
-        // is all that is waited for
-        HS_HIP(c, hipMemcpyAsync(b.hSize, words, sizeof(uint64_t) * (size_t)ch.count, hipMemcpyDeviceToHost, c->stream));
-        HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-        HS_HIP(c, hipEventSynchronize(c->evRender));
-        bool any = false;
-        for (int k = 0; k < ch.count; k++) {
-            const uint64_t size = b.hSize[k];
-            bytes[ch.first + k] = (size_t)size;
-            if (size > capacity) { fits = false; continue; }
-            HS_HIP(c, hipMemcpyAsync(jpeg[ch.first + k], out[k], (size_t)size, hipMemcpyDeviceToHost, c->stream));
-            any = true;
-        }
-        if (any) {
-            HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-            HS_HIP(c, hipEventSynchronize(c->evRender));
-        }
-    }
-    c->last_marked = marked; // nothing of this call is in flight any more: the solve's marker speaks for the context again
-    if (!fits) return fail(c, HSFLOW_E_SIZE, "capacity smaller than a file (hsflow_jpeg_bound always suffices)");
-    return check_persist(c);
+    void *const list[1] = {d_jpeg};
+    return draw_jpeg_batch_device(c, pair, 1, Drawing{true, nullptr, cp}, quality, d_jpeg ? list : nullptr, capacity, d_bytes);
+}
+
+int hsflow_color_flow_jpeg(hsflow_ctx *c, int pair, const hsflow_color_params *cp, int quality, uint8_t *jpeg, size_t capacity, size_t *bytes)
+{
+    int st = check_ctx(c, pair);
+    if (st) return st;
+    uint8_t *const list[1] = {jpeg};
+    return draw_jpeg_batch(c, pair, 1, Drawing{true, nullptr, cp}, quality, jpeg ? list : nullptr, capacity, bytes);
 }
 
 } // extern "C"

@@ -11,6 +11,7 @@
 #include "hs_kernels_classic.hip.h"
 #include "hs_kernels_classic_strip.hip.h"
 #include "hs_kernels_render.hip.h"
+#include "hs_kernels_color.hip.h"
 #include "hs_kernels_verify.hip.h"
 #include "hs_kernels_jpeg.hip.h"
 #include "hs_kernels_jpegd.hip.h"
@@ -243,6 +244,8 @@ int hsflow_destroy(hsflow_ctx *c)
     hipFree(c->dStamps);
     hipFree(c->dScratch);
     hipFree(c->dPrio); hipFree(c->dRgb);
+    hipFree(c->dColorScale);
+    if (c->hColorScale) hipHostFree(c->hColorScale);
     if (c->evRender) hipEventDestroy(c->evRender);
     jpeg_release(c);
     jpegd_release(c);
@@ -897,6 +900,7 @@ void hsflow_release_cached(void)
 } // extern "C"
 
 #include "hs_render.hip.h" // hsflow_render_flow[_device], hsflow_default_render_params
+#include "hs_color.hip.h"  // hsflow_color_flow[_host|_device|_batch_device], hsflow_default_color_params
 #include "hs_verify.hip.h" // hsflow_verify, hsflow_compare_flow_device, hsflow_compare_planes_host
 #include "hs_jpeg.hip.h"   // hsflow_jpeg_bound, hsflow_jpeg_encode_host / _device, hsflow_render_flow_jpeg[_device]
 #include "hs_jpegd.hip.h"  // hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg

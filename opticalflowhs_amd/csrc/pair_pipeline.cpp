@@ -370,6 +370,41 @@ int hsflow_pipeline_render_device(hsflow_pipeline *pl, uint64_t ticket, const hs
     return HSFLOW_OK;
 }
 
+int hsflow_pipeline_color(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, uint8_t *rgb, size_t stride, float *scale_used)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    // (like hsflow_render_flow it waits for an event behind its own copy only)
+    if ((st = hsflow_color_flow(s->ctx, 0, cp, rgb, stride, scale_used))) return ctx_fail(pl, s->ctx, st, "hsflow_color_flow");
+    return HSFLOW_OK;
+}
+
+int hsflow_pipeline_color_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, int quality, uint8_t *jpeg, size_t capacity,
+                               size_t *bytes)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    if ((st = hsflow_color_flow_jpeg(s->ctx, 0, cp, quality, jpeg, capacity, bytes))) return ctx_fail(pl, s->ctx, st, "hsflow_color_flow_jpeg");
+    return HSFLOW_OK;
+}
+
+int hsflow_pipeline_color_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, void *d_rgb, size_t stride)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    if ((st = hsflow_color_flow_device(s->ctx, 0, cp, d_rgb, stride))) return ctx_fail(pl, s->ctx, st, "hsflow_color_flow_device");
+    // the slot is idle, so its event is free: behind the launches, and only they are waited for
+    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
+        return pfail(pl, HSFLOW_E_DEVICE, "waiting for the slot's colour picture failed");
+    return HSFLOW_OK;
+}
+
 int hsflow_pipeline_verify(hsflow_pipeline *pl, uint64_t ticket, hsflow_verify_report *report)
 {
     if (!pl) return HSFLOW_E_ARG;

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HsflowError, HsflowInfo, HsflowVerifyReport, TERM_ITER
-from .solver import _is_device_tensor, _render_host, _render_target, jpeg_bound, make_params, make_render_params
+from .solver import _is_device_tensor, _render_host, _render_target, jpeg_bound, make_color_params, make_params, make_render_params
 
 
 def pinned_empty(shape, dtype):
@@ -166,6 +166,38 @@ class PairPipeline(object):
         n = ctypes.c_size_t()
         self._check(self._lib.hsflow_pipeline_render_jpeg(self._h, int(ticket), ctypes.byref(rp), int(quality), ctypes.c_void_p(buf.ctypes.data),
                                                           buf.size, ctypes.byref(n)))
+        self._held.pop(int(ticket), None)
+        return buf[:n.value].tobytes()
+
+    def color(self, ticket, max_flow=None, out=None, params=None):
+        """wait(ticket) + the dense colour picture of that pair's flow, drawn on the device on the slot's stream
+        (`HSFlow.color`): an (H, W, 3) uint8 NumPy array, or into the CUDA uint8 tensor `out` (`color_device`); complete on
+        return either way.  Raises HsflowError (E_STATE) once `depth` more pairs have been submitted."""
+        if _is_device_tensor(out):
+            return self.color_device(ticket, out, max_flow=max_flow, params=params)
+        cp = params if params is not None else make_color_params(max_flow)
+        img = _render_host(out, self.height, self.width)
+        self._check(self._lib.hsflow_pipeline_color(self._h, int(ticket), ctypes.byref(cp), ctypes.c_void_p(img.ctypes.data), img.strides[0], None))
+        self._held.pop(int(ticket), None)
+        return img
+
+    def color_device(self, ticket, out, max_flow=None, params=None):
+        """`color` into the CUDA uint8 tensor `out` of shape (H, W, 3) (`hsflow_pipeline_color_device`); returns `out`."""
+        cp = params if params is not None else make_color_params(max_flow)
+        ptr, stride = _render_target(out, self.height, self.width)
+        self._check(self._lib.hsflow_pipeline_color_device(self._h, int(ticket), ctypes.byref(cp), ptr, stride))
+        self._held.pop(int(ticket), None)
+        return out
+
+    def color_jpeg(self, ticket, max_flow=None, quality=95, params=None):
+        """wait(ticket) + the JPEG file of that pair's colour picture as `bytes` (`HSFlow.color_jpeg` on the slot's
+        stream): drawn and encoded on the device, complete on return.  Raises HsflowError (E_STATE) once `depth` more
+        pairs have been submitted."""
+        cp = params if params is not None else make_color_params(max_flow)
+        buf = np.empty(jpeg_bound(self.width, self.height), np.uint8)
+        n = ctypes.c_size_t()
+        self._check(self._lib.hsflow_pipeline_color_jpeg(self._h, int(ticket), ctypes.byref(cp), int(quality), ctypes.c_void_p(buf.ctypes.data),
+                                                         buf.size, ctypes.byref(n)))
         self._held.pop(int(ticket), None)
         return buf[:n.value].tobytes()
 

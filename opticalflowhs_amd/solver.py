@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, HsflowColorParams, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -83,6 +83,17 @@ def make_render_params(route="cv", step=None, threshold=None, scale=None, dot_rg
                 raise ValueError("%s must be three bytes" % name)
             setattr(rp, name, (ctypes.c_uint8 * 3)(*[int(t) for t in val]))
     return rp
+
+
+def make_color_params(max_flow=None):
+    """hsflow_color_params of the dense colour picture (the Middlebury wheel): max_flow=None takes the scale from the
+    picture itself (HSFLOW_COLOR_SCALE_AUTO), a number fixes it (HSFLOW_COLOR_SCALE_FIXED; finite and > 0)."""
+    cp = HsflowColorParams()
+    _lib.load().hsflow_default_color_params(ctypes.byref(cp))
+    if max_flow is not None:
+        cp.scale_mode = COLOR_SCALE_FIXED
+        cp.max_flow = max_flow
+    return cp
 
 
 def _render_target(out, height, width):
@@ -337,6 +348,61 @@ class HSFlow(object):
         self._check(self._lib.hsflow_render_flow_jpeg(self._h, pair, ctypes.byref(rp), int(quality), _ptr(buf), buf.size, ctypes.byref(n)))
         return buf[:n.value].tobytes()
 
+    def color(self, max_flow=None, out=None, pair=0, params=None, return_scale=False):
+        """The dense colour picture of the current flow of `pair` (the Middlebury wheel: hue is direction, saturation
+        magnitude, zero flow white, unknown flow black), drawn on the device (`make_color_params`: max_flow=None scales by
+        the picture's own largest flow).  out=None or a host array: returns an (H, W, 3) uint8 NumPy array, complete on
+        return -- with return_scale=True the pair (picture, scale used).  out = a CUDA uint8 tensor of shape (H, W, 3):
+        only enqueued on the context's stream (complete after `synchronize()`), returns `out`."""
+        cp = params if params is not None else make_color_params(max_flow)
+        if _is_device_tensor(out):
+            ptr, stride = _render_target(out, self.height, self.width)
+            self._check(self._lib.hsflow_color_flow_device(self._h, pair, ctypes.byref(cp), ptr, stride))
+            return out
+        img = _render_host(out, self.height, self.width)
+        m = ctypes.c_float()
+        self._check(self._lib.hsflow_color_flow(self._h, pair, ctypes.byref(cp), _ptr(img), img.strides[0], ctypes.byref(m)))
+        return (img, m.value) if return_scale else img
+
+    def color_jpeg(self, max_flow=None, quality=95, pair=0, params=None):
+        """The JPEG file of the picture `color` draws, as `bytes`: drawn and encoded on the device
+        (`hsflow_color_flow_jpeg`), only the file crosses to the host.  Complete on return."""
+        cp = params if params is not None else make_color_params(max_flow)
+        buf = np.empty(jpeg_bound(self.width, self.height), np.uint8)
+        n = ctypes.c_size_t()
+        self._check(self._lib.hsflow_color_flow_jpeg(self._h, pair, ctypes.byref(cp), int(quality), _ptr(buf), buf.size, ctypes.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def color_jpeg_batch(self, max_flow=None, quality=95, first_pair=0, n=None, params=None):
+        """`color_jpeg` for the pairs first_pair .. first_pair + n - 1 (n=None: all pairs from first_pair) by one set of
+        launches per `JPEG_BATCH_MAX` pairs (`hsflow_color_flow_jpeg_batch`).  Returns the list of the files as `bytes`,
+        each byte for byte what `color_jpeg(pair=i)` gives.  Complete on return."""
+        cp = params if params is not None else make_color_params(max_flow)
+        first_pair, n = self._batch_range(first_pair, n)
+        bound = jpeg_bound(self.width, self.height)
+        buf = np.empty((max(n, 1), bound), np.uint8)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[buf[i].ctypes.data for i in range(max(n, 1))])
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        self._check(self._lib.hsflow_color_flow_jpeg_batch(self._h, first_pair, n, ctypes.byref(cp), int(quality), ptrs, bound, sizes))
+        return [buf[i, :sizes[i]].tobytes() for i in range(n)]
+
+    def color_batch_device(self, out, max_flow=None, first_pair=0, n=None, params=None):
+        """`color` into caller tensors for the pairs first_pair .. first_pair + n - 1 (n=None: all pairs from first_pair)
+        (`hsflow_color_flow_batch_device`).  out: a CUDA uint8 tensor (n, H, W, 3) or a list of n tensors (H, W, 3), packed
+        pixels, one row stride for all.  Only enqueued on the context's stream (complete after `synchronize()`); returns
+        `out`."""
+        cp = params if params is not None else make_color_params(max_flow)
+        first_pair, n = self._batch_range(first_pair, n)
+        pictures = [out[i] for i in range(len(out))]
+        if len(pictures) != n or not all(_is_device_tensor(t) for t in pictures):
+            raise ValueError("out must hold one CUDA uint8 tensor of shape (height, width, 3) per pair")
+        targets = [_render_target(t, self.height, self.width) for t in pictures]
+        if len(set(s for _, s in targets)) > 1:
+            raise ValueError("the pictures of a batch share one row stride")
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[p.value for p, _ in targets])
+        self._check(self._lib.hsflow_color_flow_batch_device(self._h, first_pair, n, ctypes.byref(cp), ptrs, targets[0][1] if targets else 0))
+        return out
+
     def encode_jpeg(self, rgb, quality=95):
         """The baseline JPEG file (4:2:0, standard tables) of an RGB picture of the context's size that lies in device
         memory -- a CUDA uint8 tensor of shape (H, W, 3) with packed pixels and any row stride -- encoded on the device
@@ -500,6 +566,23 @@ class HSFlow(object):
         i.struct_size = ctypes.sizeof(HsflowInfo)
         self._check(self._lib.hsflow_get_info(self._h, ctypes.byref(i)))
         return {name: getattr(i, name) for name, _ in HsflowInfo._fields_}
+
+
+def color_flow_host(u, v, max_flow=None, params=None, return_scale=False):
+    """The dense colour picture of a flow field by the rule on the host (`hsflow_color_flow_host`, no GPU work): u, v
+    float32 arrays of one shape (H, W).  Returns an (H, W, 3) uint8 array -- byte for byte what `HSFlow.color` draws from
+    the same flow -- or with return_scale=True the pair (picture, scale used)."""
+    cp = params if params is not None else make_color_params(max_flow)
+    u, v = np.ascontiguousarray(u, np.float32), np.ascontiguousarray(v, np.float32)
+    if u.ndim != 2 or u.shape != v.shape:
+        raise ValueError("u and v must be 2-D arrays of one shape")
+    img = np.empty(u.shape + (3,), np.uint8)
+    m = ctypes.c_float()
+    st = _lib.load().hsflow_color_flow_host(_ptr(u), u.strides[0], _ptr(v), v.strides[0], u.shape[1], u.shape[0], ctypes.byref(cp), _ptr(img),
+                                            img.strides[0], ctypes.byref(m))
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return (img, m.value) if return_scale else img
 
 
 def compare_planes(a, b):
