@@ -40,6 +40,10 @@
  *                                          no counterpart in the reference, whose only picture is the arrow plot: the
  *                                          DENSE field as the Middlebury colour wheel, drawn (and encoded) where the flow
  *                                          lies instead of a read-back of both fp32 planes
+ *   hsflow_warp[_host|_device|_batch_device]
+ *                                          no counterpart in the reference: the second frame warped backwards onto the
+ *                                          first by the solved flow, and the residual |warp(curr) - prev| as exact integer
+ *                                          sums, where the flow lies
  *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
  *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
  *                                          the pictures are decoded on the device
@@ -75,7 +79,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 16 /* 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 17 /* 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -782,6 +786,97 @@ int hsflow_color_flow_jpeg_device(hsflow_ctx *ctx, int pair, const hsflow_color_
 int hsflow_color_flow_jpeg(hsflow_ctx *ctx, int pair, const hsflow_color_params *cp, int quality,
                            uint8_t *jpeg, size_t capacity, size_t *bytes);
 
+/* --- a picture warped by the flow, and the residual (ABI 0.17) -------------------------------- */
+
+/* What every consumer of a dense field does next -- frame-rate conversion, stabilisation, de-noising -- is to warp the
+ * second frame backwards onto the first, and the residual that leaves, the sum of |warp(curr) - prev|, is the number that
+ * says how well a flow explains its pair where there is no ground truth.  These entries do both where the flow lies,
+ * without a read-back of both fp32 planes (16.6 MB for a 1080p pair).  No counterpart in the reference.  The rule is
+ * csrc/hs_warp_rule.h, one header for the kernel and the host form; device and host give the same bytes.  All arithmetic
+ * is fp32, every operation rounded on its own (fl).
+ * The direction is the solver's: It = B - A, so curr(x + u, y + v) ~ prev(x, y): the warped picture approximates PREV.
+ *   One pixel (x, y), a = u[y][x], b = v[y][x], src a u8 picture of C interleaved channels (C = 1 or 3), t the fraction of
+ *   the flow to apply:
+ *   1. unknown iff the colour picture's test says so (isnan(a) || isnan(b) || fabsf(a) > 1e9f || fabsf(b) > 1e9f): every
+ *      channel of the pixel is fill[c];
+ *   2. fx = fl((float)x + fl(a * t)), fy = fl((float)y + fl(b * t));
+ *   3. outside iff !(fx >= 0 && fx <= W-1 && fy >= 0 && fy <= H-1).  HSFLOW_WARP_BORDER_CONSTANT: the pixel is fill;
+ *      HSFLOW_WARP_BORDER_REPLICATE: fx and fy are clamped to those ranges and sampling goes on;
+ *   4. x0 = (int)floorf(fx), x1 = min(x0 + 1, W-1), ax = fl(fx - (float)x0); y0, y1 and ay alike;
+ *   5. per channel: top = fl(p00 + fl(ax * fl(p10 - p00))), bot alike from row y1, val = fl(top + fl(ay * fl(bot - top)));
+ *      the byte is min((int)fl(val + 0.5f), 255).
+ * So fx == W-1 exactly is inside with ax = 0; a component of 1e9 is known (and outside), the next float above it unknown;
+ * t = 0 gives src itself at every known pixel; a whole-number flow gives src shifted, exactly.  Against the same formula
+ * in float64 every byte is within one level (tests/test_warp_host.py).
+ * The statistics are exact integers and do not depend on the order of execution: inside / outside / unknown count the
+ * pixels (inside: known and not outside; the three sum to W*H); sad_warped is the sum of |warped_c - ref_c| over the
+ * inside pixels and all channels, sad_plain the sum of |src_c - ref_c| over the SAME pixels, so that the two compare;
+ * max_warped and max_plain are the largest single differences.  Without a reference picture the four are 0.
+ * dst must not overlap src or ref.  Rows of dst beyond C*width bytes are left alone.
+ * Time on an MI355X: profiles/warp_time.txt. */
+#define HSFLOW_WARP_BORDER_CONSTANT 0  /* a pixel that samples outside the picture is fill */
+#define HSFLOW_WARP_BORDER_REPLICATE 1 /* ... samples the nearest pixel of the picture    */
+typedef struct hsflow_warp_params {
+    uint32_t struct_size; /* = sizeof(hsflow_warp_params)       */
+    int32_t channels;     /* 1 or 3, interleaved                 */
+    int32_t border;       /* HSFLOW_WARP_BORDER_*                */
+    float t;              /* finite, |t| <= 1e6                  */
+    uint8_t fill[4];      /* fill[c] for channel c; [3] not used */
+} hsflow_warp_params;
+typedef struct hsflow_warp_stats { /* 64 bytes, the same on the device and on the host */
+    uint64_t inside, outside, unknown;
+    uint64_t sad_warped, sad_plain;
+    uint32_t max_warped, max_plain;
+    uint8_t reserved[16];
+} hsflow_warp_stats;
+/* channels 1, HSFLOW_WARP_BORDER_CONSTANT, t = 1, fill 0. */
+void hsflow_default_warp_params(hsflow_warp_params *wp);
+/* The rule on the host, no device needed: u and v are width x height floats, rows u_stride / v_stride BYTES apart; src,
+ * ref and dst are width x height pixels of wp->channels bytes.  ref == NULL: the SADs and maxima are 0.  dst == NULL:
+ * no picture is written (statistics only).
+ * HSFLOW_E_ARG: null u, v, src or wp, wrong struct_size, channels not 1 or 3, unknown border, t not finite or |t| > 1e6,
+ * neither dst nor stats, dst equal to src or ref; HSFLOW_E_SIZE: non-positive size, a flow stride below 4*width or no
+ * multiple of 4, a picture stride below channels*width. */
+int hsflow_warp_host(const float *u, size_t u_stride, const float *v, size_t v_stride, int width, int height,
+                     const hsflow_warp_params *wp, const uint8_t *src, size_t src_stride,
+                     const uint8_t *ref /* may be null */, size_t ref_stride, uint8_t *dst /* may be null */, size_t dst_stride,
+                     hsflow_warp_stats *stats /* may be null */);
+/* The pictures d_src[i] warped by the flow of pair first_pair + i into d_dst[i] (device memory, any alignment, each its
+ * own), the statistics against d_ref[i] into d_stats[i]; only enqueued on ctx's stream, in chunks of at most
+ * HSFLOW_JPEG_BATCH_MAX pictures (the environment variable of that name is honoured as for the other pictures): per chunk
+ * one launch, with statistics a memset of the chunk's records in front of it -- the counters are formed on the device by
+ * integer atomics, one per counter and workgroup.  Picture i and record i are those of hsflow_warp_host with pair
+ * first_pair + i's flow, whatever the position, the neighbours, n or the chunking.
+ * d_src == NULL: the context's own pre-processed curr planes (what hsflow_get_frames_u8 hands out); channels must then be
+ * 1, src_stride is not looked at, and d_ref == NULL then means its prev planes.  With caller pictures d_ref == NULL means
+ * no reference: the SADs and maxima are 0.  d_dst == NULL: a statistics-only pass that writes no picture.  d_stats ==
+ * NULL: no statistics.  The pictures may have any alignment; d_stats must be a multiple of 8 (the counters are 64-bit
+ * atomics).
+ * The ordering rules of hsflow_render_flow_device apply word for word: an ITER|EPS check that hsflow_solve_async still
+ * owes is settled first, the flow is read and never changed, and on a context with hsflow_set_async_reduce
+ * hsflow_wait_solve and hsflow_flow_view_device called after it wait for the stream.  After a solve with
+ * hsflow_set_pair_termination pair i is warped by its own final flow.  Nothing is allocated.  Every argument is checked
+ * before anything is enqueued.
+ * HSFLOW_E_ARG: null wp, a null entry of a list, wrong struct_size, channels not 1 or 3 (or 3 with the context's own
+ * frames), unknown border, bad t, neither d_dst nor d_stats, d_stats no multiple of 8, d_dst[i] equal to d_src[i] or d_ref[i], n < 1, first_pair < 0
+ * or first_pair + n > n_pairs, the environment value unusable; HSFLOW_E_SIZE: a stride below channels*width. */
+int hsflow_warp_batch_device(hsflow_ctx *ctx, int first_pair, int n, const hsflow_warp_params *wp,
+                             const void *const *d_src /* n, or NULL */, size_t src_stride,
+                             const void *const *d_ref /* n, or NULL */, size_t ref_stride,
+                             void *const *d_dst /* n, or NULL */, size_t dst_stride, hsflow_warp_stats *d_stats /* n on the device, or NULL */);
+/* A batch of one. */
+int hsflow_warp_device(hsflow_ctx *ctx, int pair, const hsflow_warp_params *wp, const void *d_src, size_t src_stride,
+                       const void *d_ref, size_t ref_stride, void *d_dst, size_t dst_stride, hsflow_warp_stats *d_stats);
+/* The same with pictures in host memory, synchronous: src and ref (where given) are copied to the device, the picture
+ * and the record come back, complete on return.  src == NULL: the context's own frames, as above.  Waits only for what
+ * this context enqueued -- except in a call that has to allocate: the staging pictures (one each for src, ref and dst,
+ * as needed) are allocated by the first call that needs them and again by a call with a larger picture (hipMalloc, and
+ * hipFree of the smaller one, which the runtime may hold until the device is idle, the other slots of a pipeline's lane
+ * included); they are kept until hsflow_destroy (hsflow_release_cached for the one-shot's context).  Contexts that never
+ * warp pay nothing. */
+int hsflow_warp(hsflow_ctx *ctx, int pair, const hsflow_warp_params *wp, const uint8_t *src, size_t src_stride,
+                const uint8_t *ref, size_t ref_stride, uint8_t *dst, size_t dst_stride, hsflow_warp_stats *stats);
+
 /* --- the input files (cvLoadImage) ---------------------------------------------------------- */
 
 /* The reference reads its two frames with cvLoadImage(path, 1) (OpticalFlowOpenCV.cpp:15,18, HSOpticalFlowOpenCL.cpp:721,
@@ -1113,6 +1208,12 @@ int hsflow_pipeline_color(hsflow_pipeline *pl, uint64_t ticket, const hsflow_col
 int hsflow_pipeline_color_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, void *d_rgb, size_t stride);
 int hsflow_pipeline_color_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, int quality,
                                uint8_t *jpeg, size_t capacity, size_t *bytes);
+/* wait(ticket) + hsflow_warp / hsflow_warp_device of the ticket's slot: complete on return, HSFLOW_E_STATE if the slot has
+ * been reused already, otherwise their errors. */
+int hsflow_pipeline_warp(hsflow_pipeline *pl, uint64_t ticket, const hsflow_warp_params *wp, const uint8_t *src, size_t src_stride,
+                         const uint8_t *ref, size_t ref_stride, uint8_t *dst, size_t dst_stride, hsflow_warp_stats *stats);
+int hsflow_pipeline_warp_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_warp_params *wp, const void *d_src, size_t src_stride,
+                                const void *d_ref, size_t ref_stride, void *d_dst, size_t dst_stride, hsflow_warp_stats *d_stats);
 /* wait(ticket) + the JPEG file of that pair's picture (hsflow_render_flow_jpeg of its slot): complete on return.
  * HSFLOW_E_STATE if the slot has been reused already; otherwise the errors of hsflow_render_flow_jpeg. */
 int hsflow_pipeline_render_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, int quality,

@@ -17,6 +17,7 @@ KERNEL_AUTO, KERNEL_SIMPLE, KERNEL_FUSED, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERS
 FRAMES_GRAY8, FRAMES_GRAY8_BLUR, FRAMES_BGR8, FRAMES_BGR8_BLUR = 0, 1, 2, 3
 RENDER_CV, RENDER_CL = 0, 1
 COLOR_SCALE_AUTO, COLOR_SCALE_FIXED = 0, 1
+WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE = 0, 1
 JPEG_ORDER_BGR, JPEG_ORDER_RGB = 0, 1
 JPEGD_SUBSEQ_BITS = 1024  # HSFLOW_JPEGD_SUBSEQ_BITS
 JPEGD_BATCH_MAX = 32  # HSFLOW_JPEGD_BATCH_MAX
@@ -61,6 +62,16 @@ class HsflowColorParams(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("scale_mode", ctypes.c_int32), ("max_flow", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class HsflowWarpParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("channels", ctypes.c_int32), ("border", ctypes.c_int32), ("t", ctypes.c_float),
+                ("fill", ctypes.c_uint8 * 4)]
+
+
+class HsflowWarpStats(ctypes.Structure):
+    _fields_ = [("inside", ctypes.c_uint64), ("outside", ctypes.c_uint64), ("unknown", ctypes.c_uint64), ("sad_warped", ctypes.c_uint64),
+                ("sad_plain", ctypes.c_uint64), ("max_warped", ctypes.c_uint32), ("max_plain", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 16)]
+
+
 class HsflowPlaneDiff(ctypes.Structure):
     _fields_ = [("differing", ctypes.c_uint64), ("failing", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64),
                 ("first_failing", ctypes.c_int64), ("max_abs_diff", ctypes.c_float), ("max_ulp", ctypes.c_uint32)]
@@ -103,6 +114,8 @@ _pp = ctypes.POINTER(HsflowParams)
 _rp = ctypes.POINTER(HsflowRenderParams)
 _cp = ctypes.POINTER(HsflowColorParams)
 _fp = ctypes.POINTER(ctypes.c_float)
+_wp = ctypes.POINTER(HsflowWarpParams)
+_ws = ctypes.POINTER(HsflowWarpStats)
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
 _ji = ctypes.POINTER(HsflowJpegInfo)
@@ -168,6 +181,11 @@ PROTOTYPES = {
     "hsflow_color_flow_jpeg_batch": (_i, [_vp, _i, _i, _cp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
     "hsflow_color_flow_jpeg_device": (_i, [_vp, _i, _cp, _i, _vp, _sz, _vp]),
     "hsflow_color_flow_jpeg": (_i, [_vp, _i, _cp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
+    "hsflow_default_warp_params": (None, [_wp]),
+    "hsflow_warp_host": (_i, [_vp, _sz, _vp, _sz, _i, _i, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _ws]),
+    "hsflow_warp_batch_device": (_i, [_vp, _i, _i, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_warp_device": (_i, [_vp, _i, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_warp": (_i, [_vp, _i, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _ws]),
     "hsflow_jpeg_read_header": (_i, [_vp, _sz, _ji]),
     "hsflow_jpeg_decode_host": (_i, [_vp, _sz, _i, _vp, _sz, _ji]),
     "hsflow_jpeg_decode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
@@ -214,6 +232,8 @@ PROTOTYPES = {
     "hsflow_pipeline_color": (_i, [_vp, ctypes.c_uint64, _cp, _vp, _sz, _fp]),
     "hsflow_pipeline_color_jpeg": (_i, [_vp, ctypes.c_uint64, _cp, _i, _vp, _sz, ctypes.POINTER(_sz)]),
     "hsflow_pipeline_color_device": (_i, [_vp, ctypes.c_uint64, _cp, _vp, _sz]),
+    "hsflow_pipeline_warp": (_i, [_vp, ctypes.c_uint64, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _ws]),
+    "hsflow_pipeline_warp_device": (_i, [_vp, ctypes.c_uint64, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_pipeline_info": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(HsflowInfo)]),
     "hsflow_pipeline_drain": (_i, [_vp]),
     "hsflow_pipeline_depth": (_i, [_vp]),

@@ -67,7 +67,7 @@ int picture_kind()
 {
     const char *e = getenv("HSFLOW_PICTURE");
     if (!e || !*e || strcmp(e, "arrows") == 0) return 0;
-    return strcmp(e, "color") == 0 ? 1 : -1;
+    return strcmp(e, "color") == 0 ? 1 : strcmp(e, "warp") == 0 ? 2 : -1;
 }
 
 bool color_picture() { return picture_kind() == 1; }
@@ -85,6 +85,45 @@ bool color_params(hsflow_color_params &cp)
     cp.scale_mode = HSFLOW_COLOR_SCALE_FIXED;
     cp.max_flow = m;
     return true;
+}
+
+// HSFLOW_PICTURE=warp on the two "-hd" routes: the file holds the motion-compensated second frame -- the second input as
+// loaded, colour and all, warped onto the first by the solved flow (hsflow_warp*) -- instead of a picture of the flow, and
+// one line on stdout tells the residual.  HSFLOW_WARP_T=<float>: the fraction of the flow to apply (default 1).
+// false: the value is unusable.
+bool warp_params(hsflow_warp_params &wp)
+{
+    hsflow_default_warp_params(&wp);
+    const char *e = getenv("HSFLOW_WARP_T");
+    if (!e || !*e) return true;
+    char *rest = nullptr;
+    const float t = strtof(e, &rest);
+    if (*rest || !std::isfinite(t) || !(std::fabs(t) <= 1e6f)) return false;
+    wp.t = t;
+    return true;
+}
+
+// With HSFLOW_RENDER_DEVICE=1 through hsflow_warp (the flow stays on the device), otherwise hsflow_warp_host on the flow
+// that was read back; the same bytes and the same line.
+int warp_picture(hsflow_ctx *ctx, const pnm::Image &first, const pnm::Image &second, const std::vector<float> &u, const std::vector<float> &v,
+                 pnm::Image &out)
+{
+    const int W = second.width, H = second.height, C = second.channels;
+    if (first.width != W || first.height != H || first.channels != C) { std::cout << "HSFLOW_PICTURE=warp: the two frames differ in kind" << std::endl; return SDK_FAILURE; }
+    out.width = W; out.height = H; out.channels = C;
+    out.data.resize((size_t)W * H * C);
+    hsflow_warp_params wp;
+    warp_params(wp);
+    wp.channels = C;
+    hsflow_warp_stats s;
+    const size_t rowb = (size_t)W * C;
+    const int st = render_on_device() ? hsflow_warp(ctx, 0, &wp, second.data.data(), rowb, first.data.data(), rowb, out.data.data(), rowb, &s)
+                                      : hsflow_warp_host(u.data(), (size_t)W * 4, v.data(), (size_t)W * 4, W, H, &wp, second.data.data(), rowb,
+                                                         first.data.data(), rowb, out.data.data(), rowb, &s);
+    if (st != HSFLOW_OK) { std::cout << hsflow_last_error(render_on_device() ? ctx : nullptr) << std::endl; return SDK_FAILURE; }
+    std::cout << "warp: inside " << s.inside << " outside " << s.outside << " unknown " << s.unknown << " sad_warped " << s.sad_warped << " sad_plain "
+              << s.sad_plain << std::endl;
+    return SDK_SUCCESS;
 }
 
 // The host route of the colour picture: the rule on the host, applied to the flow that was read back.
@@ -119,7 +158,7 @@ int draw_on_device(hsflow_ctx *ctx, int preset, int W, int H, pnm::Image &imgFlo
 bool jpeg_on_device(const std::string &output)
 {
     const char *e = getenv("HSFLOW_JPEG_DEVICE");
-    if (!render_on_device() || !e || atoi(e) == 0) return false;
+    if (!render_on_device() || !e || atoi(e) == 0 || warp_wanted()) return false; // (the warped frame is written by the host's encoder)
     auto ends = [&](const char *x) {
         const size_t n = std::strlen(x);
         if (output.size() < n) return false;
@@ -155,10 +194,14 @@ int save_jpeg_from_device(hsflow_ctx *ctx, int preset, int W, int H, const std::
 bool picture_choice_usable()
 {
     hsflow_color_params cp;
-    if (picture_kind() < 0) { std::cout << "HSFLOW_PICTURE must be color or arrows" << std::endl; return false; }
+    hsflow_warp_params wp;
+    if (picture_kind() < 0) { std::cout << "HSFLOW_PICTURE must be color, warp or arrows" << std::endl; return false; }
     if (!color_params(cp)) { std::cout << "HSFLOW_COLOR_MAX must be a finite number > 0" << std::endl; return false; }
+    if (!warp_params(wp)) { std::cout << "HSFLOW_WARP_T must be a finite number, at most 1e6 in magnitude" << std::endl; return false; }
     return true;
 }
+
+bool warp_wanted() { return picture_kind() == 2; }
 
 HSOpticalFlowOpenCL::HSOpticalFlowOpenCL(const char *name, char *src_, char *in1, char *in2, char *out, float alp,
                                          int it, int gs, char *dType)
@@ -322,7 +365,10 @@ int HSOpticalFlowOpenCL::run()
         const int verdict = verify_wanted() ? verifyResults() : SDK_SUCCESS;
         if (jpeg_on_device(output)) return save_jpeg_from_device(ctx, HSFLOW_RENDER_CL, (int)width, (int)height, output) == SDK_SUCCESS ? verdict : SDK_FAILURE;
         pnm::Image imgFlow;
-        if (drawFlow(imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
+        if (warp_wanted()) {
+            if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; return -1; }
+            if (warp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
+        } else if (drawFlow(imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
         if (!output.empty() && !pnm::save_image(output, imgFlow)) return SDK_FAILURE;
         return verdict;
     }
@@ -413,9 +459,12 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     const bool file_on_device = jpeg_on_device(output ? output : "");
     if (file_on_device) {
         if (save_jpeg_from_device(ctx, HSFLOW_RENDER_CV, W, H, output) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
+    } else if (warp_wanted()) {
+        if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; hsflow_destroy(ctx); return -1; }
+        if (warp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     } else if (on_device && draw_on_device(ctx, HSFLOW_RENDER_CV, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     hsflow_destroy(ctx);
-    if (!on_device) draw_cv_flow(imgFlow, u, v, W, H);
+    if (!on_device && !warp_wanted()) draw_cv_flow(imgFlow, u, v, W, H);
     if (!file_on_device) pnm::save_image(output, imgFlow);
     std::cout << "Avg time: " << ms << " [ms]" << std::endl;
     return verdict;

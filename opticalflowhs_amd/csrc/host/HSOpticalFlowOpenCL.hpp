@@ -75,6 +75,8 @@ public:
 // HSFLOW_PICTURE (color | arrows) and HSFLOW_COLOR_MAX (a finite float > 0) as every route will read them: false, after
 // a message on stdout, if either holds something else.
 bool picture_choice_usable();
+// HSFLOW_PICTURE=warp: the file is the motion-compensated second frame (the two "-hd" routes only).
+bool warp_wanted();
 
 // GPU counterpart of the reference's CPU route (OpticalFlowHS/OpticalFlowOpenCV.hpp:6-11):
 // gray -> 3x3 box blur -> Horn-Schunck(lambda, ITER|EPS, eps 1e-6) -> arrows, all but the file I/O

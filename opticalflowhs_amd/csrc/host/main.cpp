@@ -14,6 +14,11 @@
 // hsflow_color_flow*) instead of the arrows -- by the host rule from the flow read back, with HSFLOW_RENDER_DEVICE=1 drawn
 // on the device, with HSFLOW_JPEG_DEVICE=1 encoded there too; the same bytes every way.  HSFLOW_COLOR_MAX=<float>: the
 // flow that is fully saturated (default: the picture's own largest).  An unusable value of either: a message, exit status 1.
+// HSFLOW_PICTURE=warp (the two -hd routes): the file is the motion-compensated SECOND frame instead -- the second input as
+// loaded, warped onto the first by the solved flow (hsflow_warp*) -- and one line "warp: inside .. outside .. unknown ..
+// sad_warped .. sad_plain .." tells the residual; by hsflow_warp_host from the flow read back, with HSFLOW_RENDER_DEVICE=1
+// by hsflow_warp on the device; the same file and line.  HSFLOW_WARP_T=<float>: the fraction of the flow applied (default 1;
+// finite, at most 1e6 in magnitude, else a message and exit status 1).
 // HSFLOW_VERIFY=1: every solved pair is verified on the device (hsflow_verify: re-solved sweep by sweep, compared
 // there) before its context goes away; one "Passed!" / "Failed" line per pair on stdout, the pictures are written as
 // always, and the exit status is SDK_FAILURE if any pair failed.
@@ -54,6 +59,7 @@ int main(int argc, char *argv[])
         return 0;
     }
     if (!picture_choice_usable()) return 1;
+    if (warp_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=warp needs a pair of files (-hd)\n"; return 1; }
     if (argc >= 3 && strcmp(argv[1], "-cl") == 0) {
         if (strcmp(argv[2], "-hd") == 0) {
             if (argc != 10) { std::cout << "Wrong argument list!\n"; return 0; }

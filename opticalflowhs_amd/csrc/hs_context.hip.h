@@ -177,6 +177,15 @@ struct hsflow_ctx {
     // jpeg_batch.rgb, shared with the arrow drawing: everything of a context runs on one stream.
     unsigned *dColorScale = nullptr;
     unsigned *hColorScale = nullptr;
+    // hsflow_warp (hs_warp.hip.h), allocated by the first synchronous warp that needs them and grown to the largest
+    // picture so far: the caller's source and reference on the device, the warped picture before it is copied out, one
+    // statistics record on the device and one in page-locked memory.  The device forms take the caller's memory and
+    // allocate nothing.
+    struct WarpScratch {
+        uint8_t *src = nullptr, *ref = nullptr, *dst = nullptr;
+        size_t src_bytes = 0, ref_bytes = 0, dst_bytes = 0;
+        hsflow_warp_stats *dStats = nullptr, *hStats = nullptr;
+    } warp;
     // hsflow_jpeg_encode_device and the render-and-encode forms (hs_jpeg.hip.h), allocated by the first encode and kept:
     // one block of device memory carved into the coefficients (128 B per block), the blocks' bit lengths and offsets, the
     // raw stream (208 B per block), the chunks' 0xFF counts and offsets and a size word; the tables and header of every

@@ -405,6 +405,33 @@ int hsflow_pipeline_color_device(hsflow_pipeline *pl, uint64_t ticket, const hsf
     return HSFLOW_OK;
 }
 
+int hsflow_pipeline_warp(hsflow_pipeline *pl, uint64_t ticket, const hsflow_warp_params *wp, const uint8_t *src, size_t src_stride, const uint8_t *ref,
+                         size_t ref_stride, uint8_t *dst, size_t dst_stride, hsflow_warp_stats *stats)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    // (like hsflow_color_flow it waits for an event behind its own copies only)
+    if ((st = hsflow_warp(s->ctx, 0, wp, src, src_stride, ref, ref_stride, dst, dst_stride, stats))) return ctx_fail(pl, s->ctx, st, "hsflow_warp");
+    return HSFLOW_OK;
+}
+
+int hsflow_pipeline_warp_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_warp_params *wp, const void *d_src, size_t src_stride, const void *d_ref,
+                                size_t ref_stride, void *d_dst, size_t dst_stride, hsflow_warp_stats *d_stats)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    if ((st = hsflow_warp_device(s->ctx, 0, wp, d_src, src_stride, d_ref, ref_stride, d_dst, dst_stride, d_stats)))
+        return ctx_fail(pl, s->ctx, st, "hsflow_warp_device");
+    // the slot is idle, so its event is free: behind the launch, and only it is waited for
+    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
+        return pfail(pl, HSFLOW_E_DEVICE, "waiting for the slot's warp failed");
+    return HSFLOW_OK;
+}
+
 int hsflow_pipeline_verify(hsflow_pipeline *pl, uint64_t ticket, hsflow_verify_report *report)
 {
     if (!pl) return HSFLOW_E_ARG;

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HsflowError, HsflowInfo, HsflowVerifyReport, TERM_ITER
-from .solver import _is_device_tensor, _render_host, _render_target, jpeg_bound, make_color_params, make_params, make_render_params
+from .solver import _is_device_tensor, _render_host, _render_target, _warp_call, jpeg_bound, make_color_params, make_params, make_render_params
 
 
 def pinned_empty(shape, dtype):
@@ -46,7 +46,7 @@ class PairPipeline(object):
         want 2 lanes with 4 - 8 slots, hsflow_pipeline_create_lanes)."""
         self._lib = _lib.load()
         self._h = ctypes.c_void_p()
-        self.width, self.height = int(width), int(height)
+        self.width, self.height, self.device = int(width), int(height), int(device)
         st = self._lib.hsflow_pipeline_create_lanes(ctypes.byref(self._h), int(device), self.width, self.height, int(depth),
                                                     int(depth if lanes is None else lanes))
         if st:
@@ -200,6 +200,15 @@ class PairPipeline(object):
                                                          buf.size, ctypes.byref(n)))
         self._held.pop(int(ticket), None)
         return buf[:n.value].tobytes()
+
+    def warp(self, ticket, src=None, ref=None, out=None, t=1.0, border="constant", fill=0, return_stats=False, params=None, picture=True):
+        """wait(ticket) + `HSFlow.warp` of that pair on its slot, on the slot's stream: `src` (None: the pair's own second
+        frame, and ref=None then its first) warped backwards by the pair's flow; host pictures or CUDA tensors as there,
+        but complete on return either way.  Raises HsflowError (E_STATE) once `depth` more pairs have been submitted."""
+        device, args, out, stats = _warp_call(self.height, self.width, self.device, src, ref, out, params, t, border, fill, return_stats, picture)
+        self._check((self._lib.hsflow_pipeline_warp_device if device else self._lib.hsflow_pipeline_warp)(self._h, int(ticket), *args))
+        self._held.pop(int(ticket), None)
+        return (out, stats) if return_stats else out
 
     def verify(self, ticket):
         """wait(ticket) + `HSFlow.verify` of that pair on its slot (what the slot actually ran, the pipeline's own launch

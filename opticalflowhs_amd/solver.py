@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, HsflowColorParams, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -94,6 +94,84 @@ def make_color_params(max_flow=None):
         cp.scale_mode = COLOR_SCALE_FIXED
         cp.max_flow = max_flow
     return cp
+
+
+def make_warp_params(channels=1, t=1.0, border="constant", fill=0):
+    """hsflow_warp_params of a backward warp by the flow: `channels` 1 or 3 (interleaved), `t` the fraction of the flow to
+    apply (1: the second frame onto the first), `border` "constant" (a pixel that samples outside the picture, or whose
+    flow is unknown, is `fill`) or "replicate" (outside samples take the nearest pixel), `fill` one level or one per
+    channel."""
+    wp = HsflowWarpParams()
+    _lib.load().hsflow_default_warp_params(ctypes.byref(wp))
+    wp.channels = int(channels)
+    wp.t = t
+    if isinstance(border, str):
+        if border not in ("constant", "replicate"):
+            raise ValueError("border must be 'constant' or 'replicate'")
+        border = WARP_BORDER_REPLICATE if border == "replicate" else WARP_BORDER_CONSTANT
+    wp.border = int(border)
+    levels = [int(fill)] * 3 if np.isscalar(fill) else [int(f) for f in fill]
+    if len(levels) > 4 or any(not 0 <= f <= 255 for f in levels):
+        raise ValueError("fill must be at most 4 levels of 0 .. 255")
+    for k, f in enumerate(levels):
+        wp.fill[k] = f
+    return wp
+
+
+def _warp_image(img, height, width, what, device):
+    """(pointer, row stride in bytes, channels) of a picture for the warp entries: uint8, (H, W), (H, W, 1) or (H, W, 3),
+    packed pixels, any row stride; a NumPy array, or with device=True a CUDA tensor."""
+    shape = tuple(img.shape)
+    if device != _is_device_tensor(img) or (not device and not isinstance(img, np.ndarray)):
+        raise ValueError("%s must be %s" % (what, "a CUDA uint8 tensor" if device else "a uint8 NumPy array"))
+    channels = 1 if len(shape) == 2 else shape[2] if len(shape) == 3 else 0
+    if str(img.dtype) not in ("uint8", "torch.uint8") or shape[:2] != (height, width) or channels not in (1, 3):
+        raise ValueError("%s must be uint8 of shape (height, width), (height, width, 1) or (height, width, 3)" % what)
+    strides = tuple(img.stride()) if device else img.strides
+    if strides[1] != channels or (len(shape) == 3 and channels == 3 and strides[2] != 1):
+        raise ValueError("%s must have packed pixels" % what)
+    return _ptr(img), strides[0], channels
+
+
+def _warp_args(height, width, src, ref, out, device, params, t, border, fill):
+    """The pictures of one warp call as ((pointer, stride) of src, of ref, of out, params); absent pictures are (None, 0)."""
+    pics = [(_warp_image(x, height, width, what, device) if x is not None else (None, 0, None))
+            for x, what in ((src, "src"), (ref, "ref"), (out, "out"))]
+    given = set(c for _, _, c in pics if c is not None)
+    if len(given) > 1:
+        raise ValueError("src, ref and out must have the same number of channels")
+    channels = given.pop() if given else 1
+    if params is None:
+        params = make_warp_params(channels, t, border, fill)
+    elif given and params.channels != channels:
+        raise ValueError("params.channels does not match the pictures")
+    return tuple((p, s) for p, s, _ in pics) + (params,)
+
+
+def _warp_call(height, width, device_index, src, ref, out, params, t, border, fill, return_stats, picture):
+    """What `HSFlow.warp` and `PairPipeline.warp` share: decides between the host and the device form, allocates `out`
+    where a picture is wanted and none was given, and the statistics record.  Returns (device, the C call's arguments
+    from the params on, out, stats)."""
+    device = any(_is_device_tensor(x) for x in (src, ref, out))
+    if not picture:
+        out = None
+    elif out is None:
+        shape = tuple(src.shape) if src is not None else (height, width)
+        if device:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device="cuda:%d" % device_index)
+        else:
+            out = np.empty(shape, np.uint8)
+    (sp, ss), (rp, rs), (op, os_), wp = _warp_args(height, width, src, ref, out, device, params, t, border, fill)
+    stats, sref = None, None
+    if return_stats and device:
+        import torch
+        stats = torch.empty(ctypes.sizeof(HsflowWarpStats), dtype=torch.uint8, device="cuda:%d" % device_index)  # (the library clears it)
+        sref = _ptr(stats)
+    elif return_stats:
+        stats = HsflowWarpStats()
+        sref = ctypes.byref(stats)
+    return device, (ctypes.byref(wp), sp, ss, rp, rs, op, os_, sref), out, stats
 
 
 def _render_target(out, height, width):
@@ -403,6 +481,49 @@ class HSFlow(object):
         self._check(self._lib.hsflow_color_flow_batch_device(self._h, first_pair, n, ctypes.byref(cp), ptrs, targets[0][1] if targets else 0))
         return out
 
+    def warp(self, src=None, ref=None, out=None, pair=0, t=1.0, border="constant", fill=0, return_stats=False, params=None, picture=True):
+        """`src` warped backwards by the current flow of `pair` (`make_warp_params`; include/hsflow.h has the rule): with
+        t=1 the second frame of a pair onto the first.  src=None: the context's own pre-processed second frame, and ref=None
+        then means its first.  `ref`: the picture the residual is taken against.  Host pictures (NumPy uint8 (H, W) or
+        (H, W, 3)): synchronous, returns the warped picture, or with return_stats=True the pair (picture,
+        `HsflowWarpStats`).  CUDA tensors (src, ref, out all on the device, or src=None and `out` on the device): only
+        enqueued on the context's stream (complete after `synchronize()`); returns `out`, or with return_stats=True the
+        pair (out, a CUDA uint8 tensor of 64 bytes that `warp_stats_from` reads).  picture=False: statistics only, no
+        picture is written (returns None in its place)."""
+        device, args, out, stats = _warp_call(self.height, self.width, self.device, src, ref, out, params, t, border, fill, return_stats, picture)
+        self._check((self._lib.hsflow_warp_device if device else self._lib.hsflow_warp)(self._h, pair, *args))
+        return (out, stats) if return_stats else out
+
+    def warp_batch_device(self, out=None, src=None, ref=None, stats=None, first_pair=0, n=None, t=1.0, border="constant", fill=0, params=None):
+        """`warp` on the device for the pairs first_pair .. first_pair + n - 1 (n=None: all pairs from first_pair) by one
+        launch per `JPEG_BATCH_MAX` pairs (`hsflow_warp_batch_device`).  out, src, ref: each None, a CUDA uint8 tensor
+        (n, H, W[, C]) or a list of n tensors (H, W[, C]); one row stride per list.  src=None: the context's own second
+        frames (and ref=None then its first).  out=None: statistics only.  stats: None, or a CUDA uint8 tensor of n * 64
+        bytes that receives record i of pair first_pair + i (`warp_stats_from`).  Only enqueued on the context's stream
+        (complete after `synchronize()`); returns `out`."""
+        first_pair, n = self._batch_range(first_pair, n)
+        lists, strides, channels = [], [], set()
+        for x, what in ((src, "src"), (ref, "ref"), (out, "out")):
+            if x is None:
+                lists.append(None)
+                strides.append(0)
+                continue
+            items = [_warp_image(x[i], self.height, self.width, what, True) for i in range(len(x))]
+            if len(items) != n or len(set(st for _, st, _ in items)) > 1:
+                raise ValueError("%s must hold one picture per pair, all of one row stride" % what)
+            channels.update(c for _, _, c in items)
+            lists.append((ctypes.c_void_p * max(n, 1))(*[p.value for p, _, _ in items]))
+            strides.append(items[0][1] if items else 0)
+        if len(channels) > 1:
+            raise ValueError("src, ref and out must have the same number of channels")
+        wp = params if params is not None else make_warp_params(channels.pop() if channels else 1, t, border, fill)
+        if stats is not None and (not _is_device_tensor(stats) or str(stats.dtype) != "torch.uint8" or not stats.is_contiguous()
+                                  or stats.numel() < n * ctypes.sizeof(HsflowWarpStats)):
+            raise ValueError("stats must be a contiguous CUDA uint8 tensor of at least n * 64 bytes")
+        self._check(self._lib.hsflow_warp_batch_device(self._h, first_pair, n, ctypes.byref(wp), lists[0], strides[0], lists[1], strides[1],
+                                                       lists[2], strides[2], _ptr(stats) if stats is not None else None))
+        return out
+
     def encode_jpeg(self, rgb, quality=95):
         """The baseline JPEG file (4:2:0, standard tables) of an RGB picture of the context's size that lies in device
         memory -- a CUDA uint8 tensor of shape (H, W, 3) with packed pixels and any row stride -- encoded on the device
@@ -583,6 +704,39 @@ def color_flow_host(u, v, max_flow=None, params=None, return_scale=False):
     if st != _lib.OK:
         raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
     return (img, m.value) if return_scale else img
+
+
+def warp_stats_from(stats, n=1):
+    """The `HsflowWarpStats` records a device call left in the CUDA uint8 tensor `stats` (after `synchronize()`): one
+    record for n=1, else a list of n."""
+    raw = stats.cpu().numpy().tobytes()
+    size = ctypes.sizeof(HsflowWarpStats)
+    recs = [HsflowWarpStats.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(n)]
+    return recs[0] if n == 1 else recs
+
+
+def warp_host(u, v, src, ref=None, out=None, t=1.0, border="constant", fill=0, return_stats=False, params=None, picture=True):
+    """`src` warped backwards by the flow (u, v) by the rule on the host (`hsflow_warp_host`, no GPU work): u, v float32
+    arrays of one shape (H, W), src (and ref, out) uint8 (H, W) or (H, W, 3).  Returns the warped picture -- byte for byte
+    what `HSFlow.warp` gives from the same flow -- or with return_stats=True the pair (picture, `HsflowWarpStats`).
+    picture=False: statistics only (None in the picture's place)."""
+    u, v = (a if a.ndim == 2 and a.strides[1] == 4 and a.strides[0] % 4 == 0 else np.ascontiguousarray(a)  # (padded rows are taken as they are)
+            for a in (np.asarray(u, np.float32), np.asarray(v, np.float32)))
+    if u.ndim != 2 or u.shape != v.shape:
+        raise ValueError("u and v must be 2-D arrays of one shape")
+    if src is None:
+        raise ValueError("src is needed")
+    if picture and out is None:
+        out = np.empty(src.shape, np.uint8)
+    if not picture:
+        out = None
+    (sp, ss), (rp, rs), (op, os_), wp = _warp_args(u.shape[0], u.shape[1], src, ref, out, False, params, t, border, fill)
+    stats = HsflowWarpStats()
+    st = _lib.load().hsflow_warp_host(_ptr(u), u.strides[0], _ptr(v), v.strides[0], u.shape[1], u.shape[0], ctypes.byref(wp), sp, ss, rp, rs, op, os_,
+                                      ctypes.byref(stats) if return_stats else None)
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return (out, stats) if return_stats else out
 
 
 def compare_planes(a, b):
