@@ -44,6 +44,11 @@
  *                                          no counterpart in the reference: the second frame warped backwards onto the
  *                                          first by the solved flow, and the residual |warp(curr) - prev| as exact integer
  *                                          sums, where the flow lies
+ *   hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed
+ *                                          no counterpart in the reference: the forward-backward consistency of the
+ *                                          flows of (A, B) and (B, A), pixel by pixel -- a confidence mask, the squared
+ *                                          error and exact integer statistics -- where the flows lie; the reversed pair
+ *                                          from the frames that are already on the device
  *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
  *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
  *                                          the pictures are decoded on the device
@@ -79,7 +84,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 17 /* 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 18 /* 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -877,6 +882,118 @@ int hsflow_warp_device(hsflow_ctx *ctx, int pair, const hsflow_warp_params *wp, 
 int hsflow_warp(hsflow_ctx *ctx, int pair, const hsflow_warp_params *wp, const uint8_t *src, size_t src_stride,
                 const uint8_t *ref, size_t ref_stride, uint8_t *dst, size_t dst_stride, hsflow_warp_stats *stats);
 
+/* --- forward-backward consistency of two flows (ABI 0.18) ------------------------------------- */
+
+/* hsflow_warp* tell with one number how well a flow explains its pair; these entries tell, pixel by pixel, WHERE it is to
+ * be trusted.  A warped pixel in an occluded or mis-estimated region is a ghost, and Horn-Schunck smooths across motion
+ * boundaries, so every consumer of the warp wants this mask.  The remedy is the standard one (Sundaram, Brox and Keutzer
+ * 2010): solve A->B and B->A, follow the forward vector, read the backward flow there, and call the pixel consistent where
+ * the two cancel.  Done where the flows lie, without a read-back of four fp32 planes (33 MB for a 1080p pair).  No
+ * counterpart in the reference.  The rule is csrc/hs_fb_rule.h, one header for the kernel and the host form; device and
+ * host give the same bits.  All arithmetic is fp32, every operation rounded on its own (fl).
+ *   Forward flow (uf, vf) of a pair (A, B), backward flow (ub, vb) of the pair (B, A), both W x H.  One pixel (x, y),
+ *   a = uf[y][x], b = vf[y][x]:
+ *   1. UNKNOWN (3) iff the colour picture's test says so (isnan(a) || isnan(b) || fabsf(a) > 1e9f || fabsf(b) > 1e9f);
+ *   2. fx = fl((float)x + a), fy = fl((float)y + b); OUTSIDE (2) iff !(fx >= 0 && fx <= W-1 && fy >= 0 && fy <= H-1).
+ *      There is no border option: a target outside the frame has no backward flow;
+ *   3. x0 = (int)floorf(fx), x1 = min(x0 + 1, W-1), ax = fl(fx - (float)x0); y0, y1 and ay alike (the warp's taps with
+ *      t = 1).  If any of the four taps of (ub, vb) is not known by the test of 1.: UNKNOWN, even where its weight is 0;
+ *   4. c = the bilinear sample of ub in the warp's order: top = fl(p00 + fl(ax * fl(p10 - p00))), bot alike from row y1,
+ *      c = fl(top + fl(ay * fl(bot - top))); d alike from vb;
+ *   5. ex = fl(a + c), ey = fl(b + d), err2 = fl(fl(ex * ex) + fl(ey * ey));
+ *      mag2 = fl(fl(fl(a * a) + fl(b * b)) + fl(fl(c * c) + fl(d * d))); bound = fl(fl(alpha * mag2) + beta).
+ *      Known components are at most 1e9, so nothing overflows;
+ *   6. CONSISTENT (0) iff err2 <= bound, else INCONSISTENT (1).  Classes 0 and 1 are the "evaluated" pixels.
+ * So fx == W-1 exactly is inside; a forward component of 1e9 is OUTSIDE, the next float above it UNKNOWN; a whole-number
+ * forward flow with the exactly opposite backward flow is CONSISTENT with err2 == 0 even with alpha = beta = 0.  Against
+ * the same formula in float64 the classes agree (0 of 192 400 test pixels differed) and err2 is within 9.24e-5 of
+ * (err2 + 0.5) where the backward taps are ordinary flow (tests/test_fb_host.py).
+ * Outputs, each may be absent, but at least one must be asked for:
+ *   mask   a u8 plane, value[class] per pixel;
+ *   err2   an fp32 plane: err2 at evaluated pixels, the quiet NaN 0x7fc00000 elsewhere (the colour picture's test calls
+ *          those unknown).  The squared distance on purpose: no square root, so it stays bit-exact;
+ *   stats  exact integers that do not depend on the order of execution: the four class counts (they sum to W*H);
+ *          sum_err2_q, the sum over evaluated pixels of (uint32_t)min(fl(err2 * 256.0f), 65535.0f) -- the squared error in
+ *          1/256 px^2, saturated at 256 px^2, so that the mean squared error is sum_err2_q / (256 * evaluated);
+ *          max_err2_bits, the bit pattern of the largest err2 over evaluated pixels (non-negative floats order as unsigned
+ *          integers), 0 if there are none.
+ * Rows of mask beyond width bytes and of err2 beyond width floats are left alone.
+ * Time on an MI355X (profiles/fb_time.txt): mask + err2 + statistics of a 1080p pair in 0.052 ms with the
+ * solver's flows -- 2.75 x the time of a device-to-device copy of 37 bytes per pixel, which reads 37 and writes 37 (74 bytes
+ * of traffic beside the check's 32 read + 5 written), 634 x faster than reading four planes back and checking on the host
+ * (32.7 ms); 0.022 ms at 600x480 (6.0 x that copy, 468 x faster than the host route). */
+#define HSFLOW_FB_CONSISTENT 0
+#define HSFLOW_FB_INCONSISTENT 1
+#define HSFLOW_FB_OUTSIDE 2
+#define HSFLOW_FB_UNKNOWN 3
+typedef struct hsflow_fb_params {
+    uint32_t struct_size; /* = sizeof(hsflow_fb_params)            */
+    float alpha;          /* finite, 0 <= alpha <= 1e6               */
+    float beta;           /* finite, 0 <= beta <= 1e30               */
+    uint8_t value[4];     /* the mask's byte for class HSFLOW_FB_*   */
+} hsflow_fb_params;
+typedef struct hsflow_fb_stats { /* 64 bytes, the same on the device and on the host */
+    uint64_t consistent, inconsistent, outside, unknown;
+    uint64_t sum_err2_q;
+    uint32_t max_err2_bits;
+    uint8_t reserved[20];
+} hsflow_fb_stats;
+/* alpha 0.01, beta 0.5 (Sundaram, Brox and Keutzer 2010), value {255, 0, 0, 0}: a confidence mask.  NULL is ignored. */
+void hsflow_default_fb_params(hsflow_fb_params *fp);
+/* The rule on the host, no device needed: four planes of width x height floats, rows *_stride BYTES apart.  mask, err2
+ * and stats may each be null.
+ * HSFLOW_E_ARG: a null flow plane or fp, wrong struct_size, alpha or beta out of range, nothing asked for;
+ * HSFLOW_E_SIZE: a non-positive size, a float stride below 4*width or no multiple of 4, a mask stride below width. */
+int hsflow_fb_host(const float *uf, size_t uf_stride, const float *vf, size_t vf_stride, const float *ub, size_t ub_stride,
+                   const float *vb, size_t vb_stride, int width, int height, const hsflow_fb_params *fp,
+                   uint8_t *mask /* may be null */, size_t mask_stride, float *err2 /* may be null */, size_t err2_stride,
+                   hsflow_fb_stats *stats /* may be null */);
+/* Check i reads the flow of pair fwd_pairs[i] forwards and that of pair bwd_pairs[i] backwards (host arrays of n, free on
+ * return; any pair may appear any number of times) into d_mask[i], d_err2[i] and d_stats[i] (device memory); only enqueued
+ * on ctx's stream, in chunks of at most HSFLOW_JPEG_BATCH_MAX checks (the environment variable of that name is honoured
+ * as for the other pictures): per chunk one launch, with statistics a memset of the chunk's records in front of it -- the
+ * counters are formed on the device by integer atomics, one per counter and workgroup.  Output i is that of
+ * hsflow_fb_host with the two pairs' flows, whatever the position, the neighbours, n or the chunking.
+ * d_mask, d_err2, d_stats: each may be NULL, not all three.  The mask may have any alignment; d_err2[i] and err2_stride
+ * must be multiples of 4, d_stats a multiple of 8 (the counters are 64-bit atomics).
+ * The ordering rules of hsflow_warp_batch_device apply word for word: an ITER|EPS check that hsflow_solve_async still
+ * owes is settled first, the flow is read and never changed, and on a context with hsflow_set_async_reduce
+ * hsflow_wait_solve and hsflow_flow_view_device called after it wait for the stream.  After a solve with
+ * hsflow_set_pair_termination every pair's own final flow is read.  Nothing is allocated.  Every argument is checked
+ * before anything is enqueued.
+ * HSFLOW_E_ARG: null fp or pair list, a null entry of an output list, wrong struct_size, alpha or beta out of range,
+ * nothing asked for, a pair out of range, n < 1, d_err2[i] no multiple of 4, d_stats no multiple of 8, the environment
+ * value unusable; HSFLOW_E_SIZE: a mask stride below width, an err2 stride below 4*width or no multiple of 4. */
+int hsflow_fb_batch_device(hsflow_ctx *ctx, int n, const int *fwd_pairs, const int *bwd_pairs, const hsflow_fb_params *fp,
+                           void *const *d_mask /* n, or NULL */, size_t mask_stride, void *const *d_err2 /* n, or NULL */, size_t err2_stride,
+                           hsflow_fb_stats *d_stats /* n on the device, or NULL */);
+/* A batch of one. */
+int hsflow_fb_device(hsflow_ctx *ctx, int fwd_pair, int bwd_pair, const hsflow_fb_params *fp, void *d_mask, size_t mask_stride,
+                     void *d_err2, size_t err2_stride, hsflow_fb_stats *d_stats);
+/* The same with the backward flow from caller planes on ctx's device: width x height floats each, 4-byte aligned, rows
+ * b_stride bytes apart (a multiple of 4, at least 4*width) -- another context's hsflow_flow_view_device, or a flow from
+ * elsewhere.  The caller orders that producer before ctx's stream.  HSFLOW_E_ARG: a null or misaligned plane;
+ * HSFLOW_E_SIZE: a bad b_stride; else as above. */
+int hsflow_fb_planes_device(hsflow_ctx *ctx, int fwd_pair, const void *d_ub, const void *d_vb, size_t b_stride,
+                            const hsflow_fb_params *fp, void *d_mask, size_t mask_stride, void *d_err2, size_t err2_stride,
+                            hsflow_fb_stats *d_stats);
+/* The results in host memory, synchronous: complete on return.  Waits only for an event behind its own work, like
+ * hsflow_warp -- except in a call that has to allocate: the staging (a mask, an err2 plane, a record, as needed) is
+ * allocated by the first call that needs it and kept until hsflow_destroy (hsflow_release_cached for the one-shot's
+ * context).  Contexts that never check pay nothing. */
+int hsflow_fb(hsflow_ctx *ctx, int fwd_pair, int bwd_pair, const hsflow_fb_params *fp, uint8_t *mask, size_t mask_stride,
+              float *err2, size_t err2_stride, hsflow_fb_stats *stats);
+/* hsflow_fb with the backward flow from caller planes on ctx's device, as hsflow_fb_planes_device takes them. */
+int hsflow_fb_planes(hsflow_ctx *ctx, int fwd_pair, const void *d_ub, const void *d_vb, size_t b_stride, const hsflow_fb_params *fp,
+                     uint8_t *mask, size_t mask_stride, float *err2, size_t err2_stride, hsflow_fb_stats *stats);
+/* The reversed pair of a bidirectional solve: pair dst_pair receives prev = src_pair's pre-processed curr plane and
+ * curr = its prev plane, by device copies on ctx's stream, so the frames are uploaded and pre-processed once.  It goes
+ * the way of hsflow_set_frames_u8_device: an owed check is settled first, dst_pair's coefficients are rebuilt by its next
+ * solve, cached graphs stay valid.  "Frames were set" is one flag per context: the caller sees to it that src_pair itself
+ * has frames -- a source pair that never received any, while another pair did, is copied as it lies, without an error.
+ * HSFLOW_E_ARG: a bad pair, dst_pair == src_pair; HSFLOW_E_STATE: no frames were set in the context. */
+int hsflow_set_frames_reversed(hsflow_ctx *ctx, int dst_pair, int src_pair);
+
 /* --- the input files (cvLoadImage) ---------------------------------------------------------- */
 
 /* The reference reads its two frames with cvLoadImage(path, 1) (OpticalFlowOpenCV.cpp:15,18, HSOpticalFlowOpenCL.cpp:721,
@@ -1214,6 +1331,13 @@ int hsflow_pipeline_warp(hsflow_pipeline *pl, uint64_t ticket, const hsflow_warp
                          const uint8_t *ref, size_t ref_stride, uint8_t *dst, size_t dst_stride, hsflow_warp_stats *stats);
 int hsflow_pipeline_warp_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_warp_params *wp, const void *d_src, size_t src_stride,
                                 const void *d_ref, size_t ref_stride, void *d_dst, size_t dst_stride, hsflow_warp_stats *d_stats);
+/* wait(both tickets) + the forward-backward check of ticket_fwd's flow against ticket_bwd's (hsflow_fb_planes /
+ * hsflow_fb_planes_device on the forward slot, the backward slot's flow in place): complete on return, HSFLOW_E_STATE if
+ * either slot has been reused. */
+int hsflow_pipeline_fb(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket_bwd, const hsflow_fb_params *fp, uint8_t *mask, size_t mask_stride,
+                       float *err2, size_t err2_stride, hsflow_fb_stats *stats);
+int hsflow_pipeline_fb_device(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket_bwd, const hsflow_fb_params *fp, void *d_mask,
+                              size_t mask_stride, void *d_err2, size_t err2_stride, hsflow_fb_stats *d_stats);
 /* wait(ticket) + the JPEG file of that pair's picture (hsflow_render_flow_jpeg of its slot): complete on return.
  * HSFLOW_E_STATE if the slot has been reused already; otherwise the errors of hsflow_render_flow_jpeg. */
 int hsflow_pipeline_render_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, int quality,

@@ -18,6 +18,7 @@ FRAMES_GRAY8, FRAMES_GRAY8_BLUR, FRAMES_BGR8, FRAMES_BGR8_BLUR = 0, 1, 2, 3
 RENDER_CV, RENDER_CL = 0, 1
 COLOR_SCALE_AUTO, COLOR_SCALE_FIXED = 0, 1
 WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE = 0, 1
+FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE, FB_UNKNOWN = 0, 1, 2, 3
 JPEG_ORDER_BGR, JPEG_ORDER_RGB = 0, 1
 JPEGD_SUBSEQ_BITS = 1024  # HSFLOW_JPEGD_SUBSEQ_BITS
 JPEGD_BATCH_MAX = 32  # HSFLOW_JPEGD_BATCH_MAX
@@ -72,6 +73,15 @@ class HsflowWarpStats(ctypes.Structure):
                 ("sad_plain", ctypes.c_uint64), ("max_warped", ctypes.c_uint32), ("max_plain", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 16)]
 
 
+class HsflowFbParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("value", ctypes.c_uint8 * 4)]
+
+
+class HsflowFbStats(ctypes.Structure):
+    _fields_ = [("consistent", ctypes.c_uint64), ("inconsistent", ctypes.c_uint64), ("outside", ctypes.c_uint64), ("unknown", ctypes.c_uint64),
+                ("sum_err2_q", ctypes.c_uint64), ("max_err2_bits", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 20)]
+
+
 class HsflowPlaneDiff(ctypes.Structure):
     _fields_ = [("differing", ctypes.c_uint64), ("failing", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64),
                 ("first_failing", ctypes.c_int64), ("max_abs_diff", ctypes.c_float), ("max_ulp", ctypes.c_uint32)]
@@ -116,6 +126,9 @@ _cp = ctypes.POINTER(HsflowColorParams)
 _fp = ctypes.POINTER(ctypes.c_float)
 _wp = ctypes.POINTER(HsflowWarpParams)
 _ws = ctypes.POINTER(HsflowWarpStats)
+_bp = ctypes.POINTER(HsflowFbParams)
+_bs = ctypes.POINTER(HsflowFbStats)
+_ip = ctypes.POINTER(ctypes.c_int)
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
 _ji = ctypes.POINTER(HsflowJpegInfo)
@@ -186,6 +199,14 @@ PROTOTYPES = {
     "hsflow_warp_batch_device": (_i, [_vp, _i, _i, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_warp_device": (_i, [_vp, _i, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_warp": (_i, [_vp, _i, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _ws]),
+    "hsflow_default_fb_params": (None, [_bp]),
+    "hsflow_fb_host": (_i, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _bp, _vp, _sz, _vp, _sz, _bs]),
+    "hsflow_fb_batch_device": (_i, [_vp, _i, _ip, _ip, _bp, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_fb_device": (_i, [_vp, _i, _i, _bp, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_fb_planes_device": (_i, [_vp, _i, _vp, _vp, _sz, _bp, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_fb": (_i, [_vp, _i, _i, _bp, _vp, _sz, _vp, _sz, _bs]),
+    "hsflow_fb_planes": (_i, [_vp, _i, _vp, _vp, _sz, _bp, _vp, _sz, _vp, _sz, _bs]),
+    "hsflow_set_frames_reversed": (_i, [_vp, _i, _i]),
     "hsflow_jpeg_read_header": (_i, [_vp, _sz, _ji]),
     "hsflow_jpeg_decode_host": (_i, [_vp, _sz, _i, _vp, _sz, _ji]),
     "hsflow_jpeg_decode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
@@ -234,6 +255,8 @@ PROTOTYPES = {
     "hsflow_pipeline_color_device": (_i, [_vp, ctypes.c_uint64, _cp, _vp, _sz]),
     "hsflow_pipeline_warp": (_i, [_vp, ctypes.c_uint64, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _ws]),
     "hsflow_pipeline_warp_device": (_i, [_vp, ctypes.c_uint64, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_pipeline_fb": (_i, [_vp, ctypes.c_uint64, ctypes.c_uint64, _bp, _vp, _sz, _vp, _sz, _bs]),
+    "hsflow_pipeline_fb_device": (_i, [_vp, ctypes.c_uint64, ctypes.c_uint64, _bp, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_pipeline_info": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(HsflowInfo)]),
     "hsflow_pipeline_drain": (_i, [_vp]),
     "hsflow_pipeline_depth": (_i, [_vp]),

@@ -67,7 +67,7 @@ int picture_kind()
 {
     const char *e = getenv("HSFLOW_PICTURE");
     if (!e || !*e || strcmp(e, "arrows") == 0) return 0;
-    return strcmp(e, "color") == 0 ? 1 : strcmp(e, "warp") == 0 ? 2 : -1;
+    return strcmp(e, "color") == 0 ? 1 : strcmp(e, "warp") == 0 ? 2 : strcmp(e, "fb") == 0 ? 3 : -1;
 }
 
 bool color_picture() { return picture_kind() == 1; }
@@ -126,6 +126,58 @@ int warp_picture(hsflow_ctx *ctx, const pnm::Image &first, const pnm::Image &sec
     return SDK_SUCCESS;
 }
 
+// HSFLOW_PICTURE=fb on the two "-hd" routes: the context holds two pairs, the second the first one reversed
+// (hsflow_set_frames_reversed), both solved by the route's own parameters; the file holds the forward-backward
+// consistency mask of pair 0 against pair 1 (hsflow_fb*: 255 consistent, 0 elsewhere) as a gray picture, and one line on
+// stdout tells the statistics.  HSFLOW_FB_ALPHA / HSFLOW_FB_BETA=<float> override the defaults.  false: a value is
+// unusable, *which names its variable.
+bool fb_params(hsflow_fb_params &fp, const char **which)
+{
+    hsflow_default_fb_params(&fp);
+    const struct { const char *name; float *field; float top; } vars[2] = {{"HSFLOW_FB_ALPHA", &fp.alpha, 1e6f}, {"HSFLOW_FB_BETA", &fp.beta, 1e30f}};
+    for (const auto &var : vars) {
+        const char *e = getenv(var.name);
+        if (!e || !*e) continue;
+        char *rest = nullptr;
+        const float x = strtof(e, &rest);
+        if (*rest || !std::isfinite(x) || !(x >= 0.f && x <= var.top)) { *which = var.name; return false; }
+        *var.field = x;
+    }
+    return true;
+}
+
+// With HSFLOW_RENDER_DEVICE=1 through hsflow_fb (the flows stay on the device), otherwise hsflow_fb_host on the four
+// planes read back; the same bytes and the same line.
+int fb_picture(hsflow_ctx *ctx, int W, int H, pnm::Image &out)
+{
+    out.width = W; out.height = H; out.channels = 1;
+    out.data.resize((size_t)W * H);
+    hsflow_fb_params fp;
+    const char *which = nullptr;
+    fb_params(fp, &which);
+    hsflow_fb_stats s;
+    int st;
+    if (render_on_device()) {
+        st = hsflow_fb(ctx, 0, 1, &fp, out.data.data(), (size_t)W, nullptr, 0, &s);
+    } else {
+        std::vector<float> f[4];
+        for (auto &plane : f) plane.resize((size_t)W * H);
+        const size_t rowb = (size_t)W * 4;
+        st = hsflow_get_flow(ctx, 0, f[0].data(), rowb, f[1].data(), rowb);
+        if (st == HSFLOW_OK) st = hsflow_get_flow(ctx, 1, f[2].data(), rowb, f[3].data(), rowb);
+        if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+        st = hsflow_fb_host(f[0].data(), rowb, f[1].data(), rowb, f[2].data(), rowb, f[3].data(), rowb, W, H, &fp, out.data.data(), (size_t)W, nullptr, 0, &s);
+        if (st != HSFLOW_OK) { std::cout << hsflow_last_error(nullptr) << std::endl; return SDK_FAILURE; }
+    }
+    if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+    const uint64_t evaluated = s.consistent + s.inconsistent;
+    char mse[64];
+    snprintf(mse, sizeof(mse), "%.6f", evaluated ? (double)s.sum_err2_q / (256.0 * (double)evaluated) : 0.0);
+    std::cout << "fb: consistent " << s.consistent << " inconsistent " << s.inconsistent << " outside " << s.outside << " unknown " << s.unknown << " mse "
+              << mse << std::endl;
+    return SDK_SUCCESS;
+}
+
 // The host route of the colour picture: the rule on the host, applied to the flow that was read back.
 int color_on_host(pnm::Image &imgFlow, const std::vector<float> &u, const std::vector<float> &v, int W, int H)
 {
@@ -158,7 +210,7 @@ int draw_on_device(hsflow_ctx *ctx, int preset, int W, int H, pnm::Image &imgFlo
 bool jpeg_on_device(const std::string &output)
 {
     const char *e = getenv("HSFLOW_JPEG_DEVICE");
-    if (!render_on_device() || !e || atoi(e) == 0 || warp_wanted()) return false; // (the warped frame is written by the host's encoder)
+    if (!render_on_device() || !e || atoi(e) == 0 || warp_wanted() || fb_wanted()) return false; // (the warped frame and the mask are written by the host's encoder)
     auto ends = [&](const char *x) {
         const size_t n = std::strlen(x);
         if (output.size() < n) return false;
@@ -195,13 +247,18 @@ bool picture_choice_usable()
 {
     hsflow_color_params cp;
     hsflow_warp_params wp;
-    if (picture_kind() < 0) { std::cout << "HSFLOW_PICTURE must be color, warp or arrows" << std::endl; return false; }
+    hsflow_fb_params fp;
+    const char *which = nullptr;
+    if (picture_kind() < 0) { std::cout << "HSFLOW_PICTURE must be color, warp, fb or arrows" << std::endl; return false; }
+    if (!fb_params(fp, &which)) { std::cout << which << " must be a finite number >= 0 (alpha at most 1e6, beta at most 1e30)" << std::endl; return false; }
     if (!color_params(cp)) { std::cout << "HSFLOW_COLOR_MAX must be a finite number > 0" << std::endl; return false; }
     if (!warp_params(wp)) { std::cout << "HSFLOW_WARP_T must be a finite number, at most 1e6 in magnitude" << std::endl; return false; }
     return true;
 }
 
 bool warp_wanted() { return picture_kind() == 2; }
+
+bool fb_wanted() { return picture_kind() == 3; }
 
 HSOpticalFlowOpenCL::HSOpticalFlowOpenCL(const char *name, char *src_, char *in1, char *in2, char *out, float alp,
                                          int it, int gs, char *dType)
@@ -240,7 +297,7 @@ int HSOpticalFlowOpenCL::ensureContext(int w, int h)
 {
     if (ctx && (unsigned)w == width && (unsigned)h == height) return SDK_SUCCESS;
     cleanup();
-    if (hsflow_create(&ctx, 0, w, h, 1, nullptr, 1) != HSFLOW_OK) {
+    if (hsflow_create(&ctx, 0, w, h, fb_wanted() && src == "-hd" ? 2 : 1, nullptr, 1) != HSFLOW_OK) { // (HSFLOW_PICTURE=fb: the reversed pair beside it)
         std::cout << "hsflow_create: " << hsflow_last_error(nullptr) << std::endl;
         ctx = nullptr;
         return SDK_FAILURE;
@@ -255,6 +312,7 @@ int HSOpticalFlowOpenCL::solvePair(const pnm::Image &a, const pnm::Image &b, boo
 {
     int st = frames_set ? HSFLOW_OK : streaming ? hsflow_push_frame_u8(ctx, 0, b.data.data(), b.width)
                        : hsflow_set_frames_u8(ctx, 0, a.data.data(), a.width, b.data.data(), b.width);
+    if (st == HSFLOW_OK && fb_wanted() && src == "-hd") st = hsflow_set_frames_reversed(ctx, 1, 0);
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
     hsflow_params p;
     hsflow_default_params(&p);
@@ -368,6 +426,8 @@ int HSOpticalFlowOpenCL::run()
         if (warp_wanted()) {
             if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; return -1; }
             if (warp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
+        } else if (fb_wanted()) {
+            if (fb_picture(ctx, (int)width, (int)height, imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
         } else if (drawFlow(imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
         if (!output.empty() && !pnm::save_image(output, imgFlow)) return SDK_FAILURE;
         return verdict;
@@ -430,7 +490,7 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     }
     const int W = from_files ? jw : c1.width, H = from_files ? jh : c1.height;
     hsflow_ctx *ctx = nullptr;
-    if (hsflow_create(&ctx, 0, W, H, 1, nullptr, 1) != HSFLOW_OK) { std::cout << hsflow_last_error(nullptr) << std::endl; return 1; }
+    if (hsflow_create(&ctx, 0, W, H, fb_wanted() ? 2 : 1, nullptr, 1) != HSFLOW_OK) { std::cout << hsflow_last_error(nullptr) << std::endl; return 1; } // (fb: the reversed pair beside it)
     int st;
     const double t0 = now_ms();
     if (from_files) { // cvLoadImage + cvCvtColor + cvSmooth, all on the device
@@ -442,6 +502,7 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     } else {
         st = hsflow_set_frames_gray8_blur(ctx, 0, c1.data.data(), (size_t)W, c2.data.data(), (size_t)W);
     }
+    if (st == HSFLOW_OK && fb_wanted()) st = hsflow_set_frames_reversed(ctx, 1, 0);
     hsflow_params p;
     hsflow_default_params(&p);          // ITER|EPS, eps = (float)1e-6 as at OpticalFlowOpenCV.cpp:29
     p.lambda = lambda;
@@ -462,9 +523,11 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     } else if (warp_wanted()) {
         if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; hsflow_destroy(ctx); return -1; }
         if (warp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
+    } else if (fb_wanted()) {
+        if (fb_picture(ctx, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     } else if (on_device && draw_on_device(ctx, HSFLOW_RENDER_CV, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     hsflow_destroy(ctx);
-    if (!on_device && !warp_wanted()) draw_cv_flow(imgFlow, u, v, W, H);
+    if (!on_device && !warp_wanted() && !fb_wanted()) draw_cv_flow(imgFlow, u, v, W, H);
     if (!file_on_device) pnm::save_image(output, imgFlow);
     std::cout << "Avg time: " << ms << " [ms]" << std::endl;
     return verdict;

@@ -77,6 +77,9 @@ public:
 bool picture_choice_usable();
 // HSFLOW_PICTURE=warp: the file is the motion-compensated second frame (the two "-hd" routes only).
 bool warp_wanted();
+// HSFLOW_PICTURE=fb: the file is the forward-backward consistency mask of the pair against its reverse (the two "-hd"
+// routes only).
+bool fb_wanted();
 
 // GPU counterpart of the reference's CPU route (OpticalFlowHS/OpticalFlowOpenCV.hpp:6-11):
 // gray -> 3x3 box blur -> Horn-Schunck(lambda, ITER|EPS, eps 1e-6) -> arrows, all but the file I/O

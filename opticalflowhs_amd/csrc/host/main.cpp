@@ -19,6 +19,12 @@
 // sad_warped .. sad_plain .." tells the residual; by hsflow_warp_host from the flow read back, with HSFLOW_RENDER_DEVICE=1
 // by hsflow_warp on the device; the same file and line.  HSFLOW_WARP_T=<float>: the fraction of the flow applied (default 1;
 // finite, at most 1e6 in magnitude, else a message and exit status 1).
+// HSFLOW_PICTURE=fb (the two -hd routes): the pair is solved forwards and, from the same pre-processed frames, backwards
+// (hsflow_set_frames_reversed), and the file is the forward-backward consistency mask (hsflow_fb*: 255 where the two flows
+// cancel, 0 elsewhere) as a gray picture; one line "fb: consistent .. inconsistent .. outside .. unknown .. mse .." tells
+// the statistics; by hsflow_fb_host from the flows read back, with HSFLOW_RENDER_DEVICE=1 by hsflow_fb on the device; the
+// same file and line.  HSFLOW_FB_ALPHA / HSFLOW_FB_BETA=<float>: the bound's two terms (defaults 0.01 and 0.5; finite,
+// 0 .. 1e6 and 0 .. 1e30, else a message and exit status 1).
 // HSFLOW_VERIFY=1: every solved pair is verified on the device (hsflow_verify: re-solved sweep by sweep, compared
 // there) before its context goes away; one "Passed!" / "Failed" line per pair on stdout, the pictures are written as
 // always, and the exit status is SDK_FAILURE if any pair failed.
@@ -60,6 +66,7 @@ int main(int argc, char *argv[])
     }
     if (!picture_choice_usable()) return 1;
     if (warp_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=warp needs a pair of files (-hd)\n"; return 1; }
+    if (fb_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=fb needs a pair of files (-hd)\n"; return 1; }
     if (argc >= 3 && strcmp(argv[1], "-cl") == 0) {
         if (strcmp(argv[2], "-hd") == 0) {
             if (argc != 10) { std::cout << "Wrong argument list!\n"; return 0; }

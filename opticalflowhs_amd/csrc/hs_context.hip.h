@@ -186,6 +186,14 @@ struct hsflow_ctx {
         size_t src_bytes = 0, ref_bytes = 0, dst_bytes = 0;
         hsflow_warp_stats *dStats = nullptr, *hStats = nullptr;
     } warp;
+    // hsflow_fb / hsflow_fb_planes (hs_fb.hip.h), allocated by the first synchronous check that needs them: the mask and
+    // the err2 plane before they are copied out, one statistics record on the device and one in page-locked memory.  The
+    // device forms take the caller's memory and allocate nothing.
+    struct FbScratch {
+        uint8_t *mask = nullptr, *err2 = nullptr;
+        size_t mask_bytes = 0, err2_bytes = 0;
+        hsflow_fb_stats *dStats = nullptr, *hStats = nullptr;
+    } fb;
     // hsflow_jpeg_encode_device and the render-and-encode forms (hs_jpeg.hip.h), allocated by the first encode and kept:
     // one block of device memory carved into the coefficients (128 B per block), the blocks' bit lengths and offsets, the
     // raw stream (208 B per block), the chunks' 0xFF counts and offsets and a size word; the tables and header of every

@@ -432,6 +432,47 @@ int hsflow_pipeline_warp_device(hsflow_pipeline *pl, uint64_t ticket, const hsfl
     return HSFLOW_OK;
 }
 
+// Both slots of a forward-backward check and the backward slot's flow where it lies (final: the view waits for it).
+static int fb_slots(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket_bwd, hsflow_pipeline::Slot **f, const float **ub, const float **vb, size_t *bs)
+{
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *b = nullptr;
+    if (!(*f = slot_of_finished(pl, ticket_fwd, &st)) || !(b = slot_of_finished(pl, ticket_bwd, &st))) return st;
+    if ((st = hsflow_flow_view_device(b->ctx, 0, ub, vb, bs))) return ctx_fail(pl, b->ctx, st, "hsflow_flow_view_device");
+    return HSFLOW_OK;
+}
+
+int hsflow_pipeline_fb(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket_bwd, const hsflow_fb_params *fp, uint8_t *mask, size_t mask_stride,
+                       float *err2, size_t err2_stride, hsflow_fb_stats *stats)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    hsflow_pipeline::Slot *s = nullptr;
+    const float *ub = nullptr, *vb = nullptr;
+    size_t bs = 0;
+    int st = fb_slots(pl, ticket_fwd, ticket_bwd, &s, &ub, &vb, &bs);
+    if (st) return st;
+    // (like hsflow_warp it waits for an event behind its own copies only)
+    if ((st = hsflow_fb_planes(s->ctx, 0, ub, vb, bs, fp, mask, mask_stride, err2, err2_stride, stats))) return ctx_fail(pl, s->ctx, st, "hsflow_fb_planes");
+    return HSFLOW_OK;
+}
+
+int hsflow_pipeline_fb_device(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket_bwd, const hsflow_fb_params *fp, void *d_mask,
+                              size_t mask_stride, void *d_err2, size_t err2_stride, hsflow_fb_stats *d_stats)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    hsflow_pipeline::Slot *s = nullptr;
+    const float *ub = nullptr, *vb = nullptr;
+    size_t bs = 0;
+    int st = fb_slots(pl, ticket_fwd, ticket_bwd, &s, &ub, &vb, &bs);
+    if (st) return st;
+    if ((st = hsflow_fb_planes_device(s->ctx, 0, ub, vb, bs, fp, d_mask, mask_stride, d_err2, err2_stride, d_stats)))
+        return ctx_fail(pl, s->ctx, st, "hsflow_fb_planes_device");
+    // the forward slot is idle, so its event is free: behind the launch, and only it is waited for
+    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
+        return pfail(pl, HSFLOW_E_DEVICE, "waiting for the slot's check failed");
+    return HSFLOW_OK;
+}
+
 int hsflow_pipeline_verify(hsflow_pipeline *pl, uint64_t ticket, hsflow_verify_report *report)
 {
     if (!pl) return HSFLOW_E_ARG;

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HsflowError, HsflowInfo, HsflowVerifyReport, TERM_ITER
-from .solver import _is_device_tensor, _render_host, _render_target, _warp_call, jpeg_bound, make_color_params, make_params, make_render_params
+from .solver import _is_device_tensor, _render_host, _render_target, _warp_call, _fb_call, jpeg_bound, make_color_params, make_params, make_render_params
 
 
 def pinned_empty(shape, dtype):
@@ -209,6 +209,16 @@ class PairPipeline(object):
         self._check((self._lib.hsflow_pipeline_warp_device if device else self._lib.hsflow_pipeline_warp)(self._h, int(ticket), *args))
         self._held.pop(int(ticket), None)
         return (out, stats) if return_stats else out
+
+    def fb(self, ticket_fwd, ticket_bwd, mask=True, err2=False, stats=False, alpha=0.01, beta=0.5, values=(255, 0, 0, 0), params=None, device=False):
+        """wait(both tickets) + `HSFlow.fb` of ticket_fwd's flow against ticket_bwd's on the forward pair's slot: host planes
+        or CUDA tensors as there, but complete on return either way.  Returns (mask, err2, stats).  Raises HsflowError
+        (E_STATE) once either slot has been reused by a later pair."""
+        device, args, mask, err2, rec = _fb_call(self.height, self.width, self.device, mask, err2, stats, params, alpha, beta, values, device)
+        self._check((self._lib.hsflow_pipeline_fb_device if device else self._lib.hsflow_pipeline_fb)(self._h, int(ticket_fwd), int(ticket_bwd), *args))
+        self._held.pop(int(ticket_fwd), None)
+        self._held.pop(int(ticket_bwd), None)
+        return mask, err2, rec
 
     def verify(self, ticket):
         """wait(ticket) + `HSFlow.verify` of that pair on its slot (what the slot actually ran, the pipeline's own launch

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -172,6 +172,64 @@ def _warp_call(height, width, device_index, src, ref, out, params, t, border, fi
         stats = HsflowWarpStats()
         sref = ctypes.byref(stats)
     return device, (ctypes.byref(wp), sp, ss, rp, rs, op, os_, sref), out, stats
+
+
+def make_fb_params(alpha=0.01, beta=0.5, values=(255, 0, 0, 0)):
+    """hsflow_fb_params of a forward-backward check: a pixel is consistent where |f + b(x + f)|^2 <= alpha (|f|^2 + |b|^2) +
+    beta (alpha finite in 0 .. 1e6, beta in 0 .. 1e30); `values`: the mask's byte for the classes consistent,
+    inconsistent, outside, unknown."""
+    fp = HsflowFbParams()
+    _lib.load().hsflow_default_fb_params(ctypes.byref(fp))
+    fp.alpha, fp.beta = alpha, beta
+    levels = [int(x) for x in values]
+    if len(levels) != 4 or any(not 0 <= x <= 255 for x in levels):
+        raise ValueError("values must be 4 levels of 0 .. 255")
+    for k, x in enumerate(levels):
+        fp.value[k] = x
+    return fp
+
+
+def _fb_plane(x, height, width, dtype, what, device):
+    """(pointer, row stride in bytes) of an output plane of the check: (H, W) of `dtype`, elements packed, any row stride."""
+    if device != _is_device_tensor(x) or (not device and not isinstance(x, np.ndarray)):
+        raise ValueError("%s must be %s" % (what, "a CUDA tensor" if device else "a NumPy array"))
+    if str(x.dtype) not in (dtype, "torch." + dtype) or tuple(x.shape) != (height, width):
+        raise ValueError("%s must be %s of shape (height, width)" % (what, dtype))
+    size = 4 if dtype == "float32" else 1
+    strides = tuple(st * size for st in x.stride()) if device else x.strides
+    if strides[1] != size:
+        raise ValueError("%s must have packed elements" % what)
+    return _ptr(x), strides[0]
+
+
+def _fb_call(height, width, device_index, mask, err2, stats, params, alpha, beta, values, device):
+    """What `HSFlow.fb`, `PairPipeline.fb` and `fb_host` share: mask / err2 each False or None (absent), True (allocated
+    here) or the plane to fill; stats True or False.  Returns (device, the C call's arguments from the params on, mask,
+    err2, stats)."""
+    device = bool(device) or any(_is_device_tensor(x) for x in (mask, err2))
+    planes = []
+    for x, dtype in ((mask, "uint8"), (err2, "float32")):
+        if x is None or x is False:
+            x = None
+        elif x is True and device:
+            import torch
+            x = torch.empty((height, width), dtype=getattr(torch, dtype), device="cuda:%d" % device_index)
+        elif x is True:
+            x = np.empty((height, width), dtype)
+        planes.append(x)
+    mask, err2 = planes
+    mp, ms = _fb_plane(mask, height, width, "uint8", "mask", device) if mask is not None else (None, 0)
+    ep, es = _fb_plane(err2, height, width, "float32", "err2", device) if err2 is not None else (None, 0)
+    fp = params if params is not None else make_fb_params(alpha, beta, values)
+    rec, sref = None, None
+    if stats and device:
+        import torch
+        rec = torch.empty(ctypes.sizeof(HsflowFbStats), dtype=torch.uint8, device="cuda:%d" % device_index)  # (the library clears it)
+        sref = _ptr(rec)
+    elif stats:
+        rec = HsflowFbStats()
+        sref = ctypes.byref(rec)
+    return device, (ctypes.byref(fp), mp, ms, ep, es, sref), mask, err2, rec
 
 
 def _render_target(out, height, width):
@@ -524,6 +582,63 @@ class HSFlow(object):
                                                        lists[2], strides[2], _ptr(stats) if stats is not None else None))
         return out
 
+    def set_frames_reversed(self, dst_pair, src_pair):
+        """Pair `dst_pair` receives the pre-processed frames of `src_pair`, swapped (`hsflow_set_frames_reversed`): the
+        reversed pair of a bidirectional solve, by device copies on the context's stream."""
+        self._check(self._lib.hsflow_set_frames_reversed(self._h, int(dst_pair), int(src_pair)))
+
+    def fb(self, fwd_pair=0, bwd_pair=1, mask=True, err2=False, stats=False, alpha=0.01, beta=0.5, values=(255, 0, 0, 0), params=None, device=False):
+        """The forward-backward check of the flow of `fwd_pair` against that of `bwd_pair` (`make_fb_params`;
+        include/hsflow.h has the rule).  mask, err2: False (not wanted), True (allocated here) or the plane to fill -- uint8
+        and float32 of shape (H, W), any row stride; stats: True for the statistics.  Host planes: synchronous.  CUDA
+        tensors (or device=True for planes allocated here): only enqueued on the context's stream (complete after
+        `synchronize()`), the statistics then a CUDA uint8 tensor of 64 bytes that `fb_stats_from` reads.  Returns (mask,
+        err2, stats), None for what was not asked for."""
+        device, args, mask, err2, rec = _fb_call(self.height, self.width, self.device, mask, err2, stats, params, alpha, beta, values, device)
+        self._check((self._lib.hsflow_fb_device if device else self._lib.hsflow_fb)(self._h, int(fwd_pair), int(bwd_pair), *args))
+        return mask, err2, rec
+
+    def fb_planes(self, ub, vb, fwd_pair=0, mask=True, err2=False, stats=False, alpha=0.01, beta=0.5, values=(255, 0, 0, 0), params=None, device=False):
+        """`fb` with the backward flow from CUDA float32 tensors (H, W) of one row stride (`hsflow_fb_planes_device`,
+        `hsflow_fb_planes`): another context's flow, or a flow from elsewhere, ordered before this context's stream by the
+        caller."""
+        strides = set(tuple(x.stride()) for x in (ub, vb))
+        if (not all(_is_device_tensor(x) and str(x.dtype) == "torch.float32" and tuple(x.shape) == (self.height, self.width) for x in (ub, vb))
+                or len(strides) != 1 or ub.stride(1) != 1):
+            raise ValueError("ub and vb must be CUDA float32 tensors (height, width) of one row stride")
+        device, args, mask, err2, rec = _fb_call(self.height, self.width, self.device, mask, err2, stats, params, alpha, beta, values, device)
+        self._check((self._lib.hsflow_fb_planes_device if device else self._lib.hsflow_fb_planes)(self._h, int(fwd_pair), _ptr(ub), _ptr(vb),
+                                                                                                 ub.stride(0) * 4, *args))
+        return mask, err2, rec
+
+    def fb_batch_device(self, fwd_pairs, bwd_pairs, mask=None, err2=None, stats=None, alpha=0.01, beta=0.5, values=(255, 0, 0, 0), params=None):
+        """`fb` on the device for the checks (fwd_pairs[i], bwd_pairs[i]) by one launch per `JPEG_BATCH_MAX` checks
+        (`hsflow_fb_batch_device`).  mask, err2: each None, a CUDA tensor (n, H, W) or a list of n tensors (H, W), uint8 and
+        float32; one row stride per list.  stats: None, or a CUDA uint8 tensor of n * 64 bytes that receives record i of
+        check i (`fb_stats_from`).  Only enqueued on the context's stream (complete after `synchronize()`)."""
+        n = len(fwd_pairs)
+        if len(bwd_pairs) != n:
+            raise ValueError("fwd_pairs and bwd_pairs must have one length")
+        lists, strides = [], []
+        for x, dtype, what in ((mask, "uint8", "mask"), (err2, "float32", "err2")):
+            if x is None:
+                lists.append(None)
+                strides.append(0)
+                continue
+            items = [_fb_plane(x[i], self.height, self.width, dtype, what, True) for i in range(len(x))]
+            if len(items) != n or len(set(st for _, st in items)) > 1:
+                raise ValueError("%s must hold one plane per check, all of one row stride" % what)
+            lists.append((ctypes.c_void_p * max(n, 1))(*[p.value for p, _ in items]))
+            strides.append(items[0][1] if items else 0)
+        fp = params if params is not None else make_fb_params(alpha, beta, values)
+        if stats is not None and (not _is_device_tensor(stats) or str(stats.dtype) != "torch.uint8" or not stats.is_contiguous()
+                                  or stats.numel() < n * ctypes.sizeof(HsflowFbStats)):
+            raise ValueError("stats must be a contiguous CUDA uint8 tensor of at least n * 64 bytes")
+        ints = ctypes.c_int * max(n, 1)
+        self._check(self._lib.hsflow_fb_batch_device(self._h, n, ints(*[int(p) for p in fwd_pairs]), ints(*[int(p) for p in bwd_pairs]), ctypes.byref(fp),
+                                                     lists[0], strides[0], lists[1], strides[1], _ptr(stats) if stats is not None else None))
+        return mask, err2, stats
+
     def encode_jpeg(self, rgb, quality=95):
         """The baseline JPEG file (4:2:0, standard tables) of an RGB picture of the context's size that lies in device
         memory -- a CUDA uint8 tensor of shape (H, W, 3) with packed pixels and any row stride -- encoded on the device
@@ -737,6 +852,34 @@ def warp_host(u, v, src, ref=None, out=None, t=1.0, border="constant", fill=0, r
     if st != _lib.OK:
         raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
     return (out, stats) if return_stats else out
+
+
+def fb_stats_from(stats, n=1):
+    """The `HsflowFbStats` records a device call left in the CUDA uint8 tensor `stats` (after `synchronize()`): one record
+    for n=1, else a list of n."""
+    raw = stats.cpu().numpy().tobytes()
+    size = ctypes.sizeof(HsflowFbStats)
+    recs = [HsflowFbStats.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(n)]
+    return recs[0] if n == 1 else recs
+
+
+def fb_host(uf, vf, ub, vb, mask=True, err2=False, stats=False, alpha=0.01, beta=0.5, values=(255, 0, 0, 0), params=None):
+    """The forward-backward check by the rule on the host (`hsflow_fb_host`, no GPU work): four float32 arrays of one shape
+    (H, W), padded rows taken as they are.  mask, err2, stats as `HSFlow.fb` takes them.  Returns (mask, err2, stats) --
+    bit for bit what `HSFlow.fb` gives from the same flows."""
+    planes = [a if a.ndim == 2 and a.strides[1] == 4 and a.strides[0] % 4 == 0 else np.ascontiguousarray(a)
+              for a in (np.asarray(x, np.float32) for x in (uf, vf, ub, vb))]
+    if planes[0].ndim != 2 or any(a.shape != planes[0].shape for a in planes):
+        raise ValueError("uf, vf, ub and vb must be 2-D arrays of one shape")
+    H, W = planes[0].shape
+    _, args, mask, err2, rec = _fb_call(H, W, 0, mask, err2, stats, params, alpha, beta, values, False)
+    flows = []
+    for a in planes:
+        flows += [_ptr(a), a.strides[0]]
+    st = _lib.load().hsflow_fb_host(*(flows + [W, H] + list(args)))
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return mask, err2, rec
 
 
 def compare_planes(a, b):
