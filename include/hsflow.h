@@ -49,6 +49,9 @@
  *                                          flows of (A, B) and (B, A), pixel by pixel -- a confidence mask, the squared
  *                                          error and exact integer statistics -- where the flows lie; the reversed pair
  *                                          from the frames that are already on the device
+ *   hsflow_median[_host|_device|_batch_device|_planes_device|_apply]
+ *                                          no counterpart in the reference: the median filter of the flow and the filling
+ *                                          of untrusted pixels from their trusted neighbours, where the flow lies
  *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
  *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
  *                                          the pictures are decoded on the device
@@ -84,7 +87,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 18 /* 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 19 /* 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -994,6 +997,129 @@ int hsflow_fb_planes(hsflow_ctx *ctx, int fwd_pair, const void *d_ub, const void
  * HSFLOW_E_ARG: a bad pair, dst_pair == src_pair; HSFLOW_E_STATE: no frames were set in the context. */
 int hsflow_set_frames_reversed(hsflow_ctx *ctx, int dst_pair, int src_pair);
 
+/* --- median filter and hole filling of the flow (ABI 0.19) ------------------------------------ */
+
+/* hsflow_fb* end with a mask that says "this vector is not to be trusted"; these entries act on it.  Horn-Schunck smooths
+ * across motion boundaries and leaves outliers at occlusions, and the standard remedy has two parts: a median filter of
+ * the field (Sun, Roth and Black 2010) and filling the untrusted pixels from their trusted neighbours.  Done where the
+ * flow lies, without a read-back and an upload of both fp32 planes (16.6 MB each way for a 1080p pair).  No counterpart
+ * in the reference.  The rule is csrc/hs_median_rule.h, one header for the kernel and the host form; the median is a
+ * selection on integers, so device and host give the same bits.
+ *   Inputs: flow planes u, v (W x H fp32), an optional u8 state plane, radius r in {1, 2} (window 3x3 or 5x5), a mode and
+ *   min_votes in 1 .. (2r+1)^2.  One pass at the pixel p = (x, y), a = u[p], b = v[p]:
+ *   1. known(p) is the colour picture's test: !(isnan(a) || isnan(b) || fabsf(a) > 1e9f || fabsf(b) > 1e9f);
+ *   2. the input state s(p): 0 (INVALID) if !known(p) or the state byte is 0; 2 (FILLED) if the byte is 2; 1 (KEPT) for
+ *      any other non-zero byte, or when no state plane is given.  So the default mask of hsflow_fb (255 = consistent) can
+ *      be passed as it is;
+ *   3. the voters are the pixels q of the (2r+1)^2 window around p that lie inside the frame and have s(q) != 0.  The
+ *      window is clipped at the frame, not replicated; p itself votes if it is valid; n is the number of voters;
+ *   4. the median of a component is taken over the integer keys key(f) = bits(f) ^ ((bits(f) >> 31) ? 0xffffffff :
+ *      0x80000000), an order-preserving map in which -0.0 < +0.0: the voter key of rank (n - 1) >> 1 in ascending order
+ *      (the lower median), mapped back to its bits.  u and v are filtered independently, so the output vector need not
+ *      be any input vector;
+ *   5. HSFLOW_MEDIAN_FILTER: if n >= min_votes the output is the two medians and s_out = s if s != 0, else 2; otherwise
+ *      the output is the input bits and s_out = s;
+ *   6. HSFLOW_MEDIAN_FILL: if s != 0 the output is the input bits and s_out = s; if s == 0 and n >= min_votes the output
+ *      is the two medians and s_out = 2; otherwise the input bits (NaNs are copied bit for bit) and s_out = 0;
+ *   7. `passes` k >= 1: pass j + 1 reads pass j's output flow and output state.
+ * So a window of {-0.0, +0.0} gives -0.0; a component of 1e9 votes, the next float above it does not; the corner pixel
+ * of a 5x5 window has at most 9 voters; a hole pixel at Chebyshev depth d inside an otherwise valid field is filled, with
+ * min_votes 1, in pass ceil(d / r).
+ * Outputs, each may be absent, but at least one must be asked for:
+ *   the two flow planes, together or not at all;
+ *   the output state plane, bytes 0 UNFILLED, 1 KEPT, 2 FILLED -- a valid input state, so passes can be chained;
+ *   stats  exact integers about the LAST pass: kept, filled, unfilled count s_out (they sum to W*H); newly_filled counts
+ *          s == 0 -> s_out == 2 in that pass; changed counts the pixels whose output bits differ from that pass's input
+ *          bits in u or v.  The reserved bytes are zero.
+ * Rows of the outputs beyond width elements are left alone.  An output may not overlap an input.
+ * Time on an MI355X (profiles/median_time.txt), one pass over a 1080p pair's flow into caller planes:
+ * 0.016 ms with the 3x3 window and 0.050 ms with the 5x5 one (0.018 and 0.052 ms filling from the hsflow_fb mask), with
+ * the record 0.011 .. 0.013 ms more; hsflow_median_apply with four passes 0.076 and 0.196 ms.  That is 4.2 x and 13 x the
+ * time of a device-to-device copy of both planes (8 bytes per pixel read, 8 written): the selection, not the memory,
+ * bounds the pass.  Against the host route (hsflow_get_flow, hsflow_median_host, upload and hsflow_set_flow_device: 75.5
+ * and 244 ms) a pass is 4700 and 4900 times faster; at 600x480 0.006 and 0.015 ms, 1.7 x and 4.0 x the copy, 1300 and
+ * 2400 times faster than the host route. */
+#define HSFLOW_MEDIAN_FILTER 0
+#define HSFLOW_MEDIAN_FILL 1
+#define HSFLOW_MEDIAN_UNFILLED 0
+#define HSFLOW_MEDIAN_KEPT 1
+#define HSFLOW_MEDIAN_FILLED 2
+#define HSFLOW_MEDIAN_MAX_PASSES 64
+typedef struct hsflow_median_params {
+    uint32_t struct_size; /* = sizeof(hsflow_median_params)        */
+    int32_t radius;       /* 1 (3x3) or 2 (5x5)                      */
+    int32_t mode;         /* HSFLOW_MEDIAN_FILTER or HSFLOW_MEDIAN_FILL */
+    int32_t min_votes;    /* 1 .. (2 radius + 1)^2                   */
+} hsflow_median_params;
+typedef struct hsflow_median_stats { /* 64 bytes, the same on the device and on the host */
+    uint64_t kept, filled, unfilled;
+    uint64_t newly_filled;
+    uint64_t changed;
+    uint8_t reserved[24];
+} hsflow_median_stats;
+/* radius 1, HSFLOW_MEDIAN_FILTER, min_votes 1.  NULL is ignored. */
+void hsflow_default_median_params(hsflow_median_params *mp);
+/* The rule on the host, no device needed: `passes` passes (1 .. HSFLOW_MEDIAN_MAX_PASSES) over two planes of width x
+ * height floats, rows *_stride BYTES apart; state may be null (every known pixel is KEPT).  u_out / v_out (together),
+ * state_out and stats may each be null, not all.  With several passes the planes between them are the call's own.
+ * HSFLOW_E_ARG: a null flow plane or mp, wrong struct_size, radius not 1 or 2, an unknown mode, min_votes or passes out
+ * of range, nothing asked for, one flow output without the other, an output that overlaps (or is) an input;
+ * HSFLOW_E_SIZE: a non-positive size, a float stride below 4*width or no multiple of 4, a byte stride below width. */
+int hsflow_median_host(const float *u, size_t u_stride, const float *v, size_t v_stride, const uint8_t *state /* may be null */,
+                       size_t state_stride, int width, int height, const hsflow_median_params *mp, int passes,
+                       float *u_out /* may be null */, float *v_out /* may be null */, size_t out_stride,
+                       uint8_t *state_out /* may be null */, size_t state_out_stride, hsflow_median_stats *stats /* may be null */);
+/* ONE pass over the flows of the pairs first_pair .. first_pair + n - 1: field i reads the flow of pair first_pair + i
+ * and d_state[i] into d_u_out[i], d_v_out[i], d_state_out[i] and d_stats[i] (device memory; the lists are host arrays of
+ * n, free on return); only enqueued on ctx's stream, in chunks of at most HSFLOW_JPEG_BATCH_MAX fields (the environment
+ * variable of that name is honoured as for the pictures): per chunk one launch, with statistics a memset of the chunk's
+ * records in front of it -- the counters are formed on the device by integer atomics, one per counter and workgroup.
+ * Output i is that of hsflow_median_host with that pair's flow, whatever the position, the neighbours, n or the chunking.
+ * d_state, d_u_out + d_v_out, d_state_out, d_stats: each may be NULL, the outputs not all three.  The byte planes may
+ * have any alignment; d_u_out[i], d_v_out[i] and out_stride must be multiples of 4, d_stats a multiple of 8 (the counters
+ * are 64-bit atomics).
+ * The ordering rules of hsflow_fb_batch_device apply word for word: an ITER|EPS check that hsflow_solve_async still owes
+ * is settled first, the flow is read and never changed, and on a context with hsflow_set_async_reduce hsflow_wait_solve
+ * and hsflow_flow_view_device called after it wait for the stream.  After a solve with hsflow_set_pair_termination every
+ * pair's own final flow is read.  Nothing is allocated.  Every argument is checked before anything is enqueued.
+ * HSFLOW_E_ARG: null mp, a null entry of a list, wrong struct_size, radius, mode or min_votes out of range, nothing asked
+ * for, one flow output without the other, an output that overlaps an input of the batch, a pair out of range, n < 1, a
+ * flow output no multiple of 4, d_stats no multiple of 8, the environment value unusable; HSFLOW_E_SIZE: a byte stride
+ * below width, out_stride below 4*width or no multiple of 4. */
+int hsflow_median_batch_device(hsflow_ctx *ctx, int first_pair, int n, const hsflow_median_params *mp,
+                               const void *const *d_state /* n, or NULL */, size_t state_stride, void *const *d_u_out /* n, or NULL */,
+                               void *const *d_v_out /* n, or NULL */, size_t out_stride, void *const *d_state_out /* n, or NULL */,
+                               size_t state_out_stride, hsflow_median_stats *d_stats /* n on the device, or NULL */);
+/* A batch of one. */
+int hsflow_median_device(hsflow_ctx *ctx, int pair, const hsflow_median_params *mp, const void *d_state, size_t state_stride,
+                         void *d_u_out, void *d_v_out, size_t out_stride, void *d_state_out, size_t state_out_stride,
+                         hsflow_median_stats *d_stats);
+/* One pass over caller planes on ctx's device: width x height floats each, 4-byte aligned, rows in_stride bytes apart (a
+ * multiple of 4, at least 4*width).  The output state (0 / 1 / 2) is a valid input state, so a caller chains passes by
+ * calling again with the outputs as inputs and fresh outputs.  The caller orders the planes' producer before ctx's stream.
+ * HSFLOW_E_ARG: a null or misaligned plane; HSFLOW_E_SIZE: a bad in_stride; else as above. */
+int hsflow_median_planes_device(hsflow_ctx *ctx, const hsflow_median_params *mp, const void *d_u, const void *d_v, size_t in_stride,
+                                const void *d_state /* or NULL */, size_t state_stride, void *d_u_out, void *d_v_out, size_t out_stride,
+                                void *d_state_out, size_t state_out_stride, hsflow_median_stats *d_stats);
+/* `passes` passes (1 .. HSFLOW_MEDIAN_MAX_PASSES) whose result REPLACES the pair's flow in the context, so every later
+ * picture, warp, check and use_previous = 1 solve reads it.  Only enqueued.  d_state (or NULL), d_state_out (or NULL, the
+ * last pass's state) and d_stats (or NULL, the last pass's record) are device memory as above.  The flow goes to and fro
+ * between the pair's planes and a scratch of one pair of fp32 planes, the states between two byte planes; the first call
+ * that needs them allocates them, and they are kept until hsflow_destroy (hsflow_release_cached for the one-shot's
+ * context).  Contexts that never filter pay nothing.  For the context's knowledge of its planes it goes the way of
+ * hsflow_set_flow_device: an owed check is settled first, the planes count as the caller's (the next warm strip / fold
+ * solve measures them), cached graphs stay valid, and hsflow_flow_view_device called after it waits for the stream.
+ * HSFLOW_E_ARG: as hsflow_median_device, passes out of range, d_state_out overlapping d_state or the pair's planes. */
+int hsflow_median_apply(hsflow_ctx *ctx, int pair, const hsflow_median_params *mp, int passes, const void *d_state /* or NULL */,
+                        size_t state_stride, void *d_state_out /* or NULL */, size_t state_out_stride, hsflow_median_stats *d_stats /* or NULL */);
+/* `passes` passes over the pair's flow with everything in host memory, synchronous: complete on return.  It does not
+ * change the context's flow.  Waits only for an event behind its own work, like hsflow_fb -- except in a call that has
+ * to allocate: the staging (up to two pairs of fp32 planes, two byte planes, a record) is shared with hsflow_median_apply
+ * and kept like it. */
+int hsflow_median(hsflow_ctx *ctx, int pair, const hsflow_median_params *mp, int passes, const uint8_t *state /* or NULL */,
+                  size_t state_stride, float *u /* or NULL */, float *v /* or NULL */, size_t out_stride, uint8_t *state_out /* or NULL */,
+                  size_t state_out_stride, hsflow_median_stats *stats /* or NULL */);
+
 /* --- the input files (cvLoadImage) ---------------------------------------------------------- */
 
 /* The reference reads its two frames with cvLoadImage(path, 1) (OpticalFlowOpenCV.cpp:15,18, HSOpticalFlowOpenCL.cpp:721,
@@ -1338,6 +1464,13 @@ int hsflow_pipeline_fb(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket
                        float *err2, size_t err2_stride, hsflow_fb_stats *stats);
 int hsflow_pipeline_fb_device(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket_bwd, const hsflow_fb_params *fp, void *d_mask,
                               size_t mask_stride, void *d_err2, size_t err2_stride, hsflow_fb_stats *d_stats);
+/* wait(ticket) + hsflow_median of that pair's flow on its slot (host memory, the slot's flow unchanged) and
+ * hsflow_median_apply (the slot's flow replaced; device memory): both complete on return, HSFLOW_E_STATE if the slot has
+ * been reused. */
+int hsflow_pipeline_median(hsflow_pipeline *pl, uint64_t ticket, const hsflow_median_params *mp, int passes, const uint8_t *state, size_t state_stride,
+                           float *u, float *v, size_t out_stride, uint8_t *state_out, size_t state_out_stride, hsflow_median_stats *stats);
+int hsflow_pipeline_median_apply(hsflow_pipeline *pl, uint64_t ticket, const hsflow_median_params *mp, int passes, const void *d_state,
+                                 size_t state_stride, void *d_state_out, size_t state_out_stride, hsflow_median_stats *d_stats);
 /* wait(ticket) + the JPEG file of that pair's picture (hsflow_render_flow_jpeg of its slot): complete on return.
  * HSFLOW_E_STATE if the slot has been reused already; otherwise the errors of hsflow_render_flow_jpeg. */
 int hsflow_pipeline_render_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, int quality,

@@ -19,6 +19,9 @@ RENDER_CV, RENDER_CL = 0, 1
 COLOR_SCALE_AUTO, COLOR_SCALE_FIXED = 0, 1
 WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE = 0, 1
 FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE, FB_UNKNOWN = 0, 1, 2, 3
+MEDIAN_FILTER, MEDIAN_FILL = 0, 1
+MEDIAN_UNFILLED, MEDIAN_KEPT, MEDIAN_FILLED = 0, 1, 2
+MEDIAN_MAX_PASSES = 64  # HSFLOW_MEDIAN_MAX_PASSES
 JPEG_ORDER_BGR, JPEG_ORDER_RGB = 0, 1
 JPEGD_SUBSEQ_BITS = 1024  # HSFLOW_JPEGD_SUBSEQ_BITS
 JPEGD_BATCH_MAX = 32  # HSFLOW_JPEGD_BATCH_MAX
@@ -82,6 +85,15 @@ class HsflowFbStats(ctypes.Structure):
                 ("sum_err2_q", ctypes.c_uint64), ("max_err2_bits", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 20)]
 
 
+class HsflowMedianParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("radius", ctypes.c_int32), ("mode", ctypes.c_int32), ("min_votes", ctypes.c_int32)]
+
+
+class HsflowMedianStats(ctypes.Structure):
+    _fields_ = [("kept", ctypes.c_uint64), ("filled", ctypes.c_uint64), ("unfilled", ctypes.c_uint64), ("newly_filled", ctypes.c_uint64),
+                ("changed", ctypes.c_uint64), ("reserved", ctypes.c_uint8 * 24)]
+
+
 class HsflowPlaneDiff(ctypes.Structure):
     _fields_ = [("differing", ctypes.c_uint64), ("failing", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64),
                 ("first_failing", ctypes.c_int64), ("max_abs_diff", ctypes.c_float), ("max_ulp", ctypes.c_uint32)]
@@ -129,6 +141,8 @@ _ws = ctypes.POINTER(HsflowWarpStats)
 _bp = ctypes.POINTER(HsflowFbParams)
 _bs = ctypes.POINTER(HsflowFbStats)
 _ip = ctypes.POINTER(ctypes.c_int)
+_mp = ctypes.POINTER(HsflowMedianParams)
+_ms = ctypes.POINTER(HsflowMedianStats)
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
 _ji = ctypes.POINTER(HsflowJpegInfo)
@@ -207,6 +221,13 @@ PROTOTYPES = {
     "hsflow_fb": (_i, [_vp, _i, _i, _bp, _vp, _sz, _vp, _sz, _bs]),
     "hsflow_fb_planes": (_i, [_vp, _i, _vp, _vp, _sz, _bp, _vp, _sz, _vp, _sz, _bs]),
     "hsflow_set_frames_reversed": (_i, [_vp, _i, _i]),
+    "hsflow_default_median_params": (None, [_mp]),
+    "hsflow_median_host": (_i, [_vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _mp, _i, _vp, _vp, _sz, _vp, _sz, _ms]),
+    "hsflow_median_batch_device": (_i, [_vp, _i, _i, _mp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_median_device": (_i, [_vp, _i, _mp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_median_planes_device": (_i, [_vp, _mp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_median_apply": (_i, [_vp, _i, _mp, _i, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_median": (_i, [_vp, _i, _mp, _i, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _ms]),
     "hsflow_jpeg_read_header": (_i, [_vp, _sz, _ji]),
     "hsflow_jpeg_decode_host": (_i, [_vp, _sz, _i, _vp, _sz, _ji]),
     "hsflow_jpeg_decode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
@@ -257,6 +278,8 @@ PROTOTYPES = {
     "hsflow_pipeline_warp_device": (_i, [_vp, ctypes.c_uint64, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_pipeline_fb": (_i, [_vp, ctypes.c_uint64, ctypes.c_uint64, _bp, _vp, _sz, _vp, _sz, _bs]),
     "hsflow_pipeline_fb_device": (_i, [_vp, ctypes.c_uint64, ctypes.c_uint64, _bp, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_pipeline_median": (_i, [_vp, ctypes.c_uint64, _mp, _i, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _ms]),
+    "hsflow_pipeline_median_apply": (_i, [_vp, ctypes.c_uint64, _mp, _i, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_pipeline_info": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(HsflowInfo)]),
     "hsflow_pipeline_drain": (_i, [_vp]),
     "hsflow_pipeline_depth": (_i, [_vp]),

@@ -178,6 +178,72 @@ int fb_picture(hsflow_ctx *ctx, int W, int H, pnm::Image &out)
     return SDK_SUCCESS;
 }
 
+// HSFLOW_MEDIAN=<radius>[,<passes>[,fill]] on the two "-hd" routes: the pair's flow is median-filtered in place
+// (hsflow_median_apply: radius 1 or 2, passes 1 .. 64, default 1) before the picture is drawn.  With "fill" the context
+// holds the reversed pair as for HSFLOW_PICTURE=fb, the hsflow_fb mask (HSFLOW_FB_ALPHA / HSFLOW_FB_BETA) is the state,
+// only the untrusted pixels of the forward flow are replaced, and one line on stdout tells the record.
+// 0: not set, 1: usable, -1: unusable.
+int median_choice(int &radius, int &passes, bool &fill)
+{
+    radius = 1; passes = 1; fill = false;
+    const char *e = getenv("HSFLOW_MEDIAN");
+    if (!e || !*e) return 0;
+    char *rest = nullptr;
+    const long r = strtol(e, &rest, 10);
+    if (rest == e || (r != 1 && r != 2)) return -1;
+    radius = (int)r;
+    if (!*rest) return 1;
+    if (*rest != ',') return -1;
+    const char *q = rest + 1;
+    const long k = strtol(q, &rest, 10);
+    if (rest == q || k < 1 || k > HSFLOW_MEDIAN_MAX_PASSES) return -1;
+    passes = (int)k;
+    if (!*rest) return 1;
+    if (strcmp(rest, ",fill") != 0) return -1;
+    fill = true;
+    return 1;
+}
+
+// The filter of pair 0's flow in place; u, v (host copies of the flow, or null) are read again behind it.
+int median_step(hsflow_ctx *ctx, int W, int H, std::vector<float> *u, std::vector<float> *v)
+{
+    int radius, passes;
+    bool fill;
+    if (median_choice(radius, passes, fill) != 1) return SDK_SUCCESS;
+    hsflow_median_params mp;
+    hsflow_default_median_params(&mp);
+    mp.radius = radius;
+    int st;
+    if (!fill) {
+        st = hsflow_median_apply(ctx, 0, &mp, passes, nullptr, 0, nullptr, 0, nullptr);
+    } else {
+        mp.mode = HSFLOW_MEDIAN_FILL;
+        hsflow_fb_params fp;
+        const char *which = nullptr;
+        fb_params(fp, &which);
+        void *dMask = nullptr, *dStats = nullptr;
+        hsflow_median_stats s;
+        if (hipMalloc(&dMask, (size_t)W * H) != hipSuccess || hipMalloc(&dStats, sizeof(s)) != hipSuccess) {
+            (void)hipFree(dMask);
+            std::cout << "hipMalloc of the median's state failed" << std::endl;
+            return SDK_FAILURE;
+        }
+        st = hsflow_fb_device(ctx, 0, 1, &fp, dMask, (size_t)W, nullptr, 0, nullptr);
+        if (st == HSFLOW_OK) st = hsflow_median_apply(ctx, 0, &mp, passes, dMask, (size_t)W, nullptr, 0, (hsflow_median_stats *)dStats);
+        if (st == HSFLOW_OK) st = hsflow_synchronize(ctx);
+        const bool copied = st == HSFLOW_OK && hipMemcpy(&s, dStats, sizeof(s), hipMemcpyDeviceToHost) == hipSuccess;
+        (void)hipFree(dMask);
+        (void)hipFree(dStats);
+        if (st == HSFLOW_OK && !copied) { std::cout << "reading the median's record failed" << std::endl; return SDK_FAILURE; }
+        if (st == HSFLOW_OK)
+            std::cout << "median: kept " << s.kept << " filled " << s.filled << " unfilled " << s.unfilled << " newly_filled " << s.newly_filled << " changed "
+                      << s.changed << std::endl;
+    }
+    if (st == HSFLOW_OK && u && v && !u->empty()) st = hsflow_get_flow(ctx, 0, u->data(), (size_t)W * 4, v->data(), (size_t)W * 4);
+    if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+    return SDK_SUCCESS;
+}
+
 // The host route of the colour picture: the rule on the host, applied to the flow that was read back.
 int color_on_host(pnm::Image &imgFlow, const std::vector<float> &u, const std::vector<float> &v, int W, int H)
 {
@@ -253,7 +319,25 @@ bool picture_choice_usable()
     if (!fb_params(fp, &which)) { std::cout << which << " must be a finite number >= 0 (alpha at most 1e6, beta at most 1e30)" << std::endl; return false; }
     if (!color_params(cp)) { std::cout << "HSFLOW_COLOR_MAX must be a finite number > 0" << std::endl; return false; }
     if (!warp_params(wp)) { std::cout << "HSFLOW_WARP_T must be a finite number, at most 1e6 in magnitude" << std::endl; return false; }
+    int radius, passes;
+    bool fill;
+    if (median_choice(radius, passes, fill) < 0) { std::cout << "HSFLOW_MEDIAN must be <radius 1 or 2>[,<passes 1 .. 64>[,fill]]" << std::endl; return false; }
     return true;
+}
+
+bool median_wanted()
+{
+    int radius, passes;
+    bool fill;
+    return median_choice(radius, passes, fill) == 1;
+}
+
+// HSFLOW_MEDIAN=..,fill needs the reversed pair beside the pair, as HSFLOW_PICTURE=fb does.
+static bool reversed_pair_wanted()
+{
+    int radius, passes;
+    bool fill;
+    return fb_wanted() || (median_choice(radius, passes, fill) == 1 && fill);
 }
 
 bool warp_wanted() { return picture_kind() == 2; }
@@ -297,7 +381,7 @@ int HSOpticalFlowOpenCL::ensureContext(int w, int h)
 {
     if (ctx && (unsigned)w == width && (unsigned)h == height) return SDK_SUCCESS;
     cleanup();
-    if (hsflow_create(&ctx, 0, w, h, fb_wanted() && src == "-hd" ? 2 : 1, nullptr, 1) != HSFLOW_OK) { // (HSFLOW_PICTURE=fb: the reversed pair beside it)
+    if (hsflow_create(&ctx, 0, w, h, reversed_pair_wanted() && src == "-hd" ? 2 : 1, nullptr, 1) != HSFLOW_OK) { // (HSFLOW_PICTURE=fb, HSFLOW_MEDIAN=..,fill: the reversed pair beside it)
         std::cout << "hsflow_create: " << hsflow_last_error(nullptr) << std::endl;
         ctx = nullptr;
         return SDK_FAILURE;
@@ -312,7 +396,7 @@ int HSOpticalFlowOpenCL::solvePair(const pnm::Image &a, const pnm::Image &b, boo
 {
     int st = frames_set ? HSFLOW_OK : streaming ? hsflow_push_frame_u8(ctx, 0, b.data.data(), b.width)
                        : hsflow_set_frames_u8(ctx, 0, a.data.data(), a.width, b.data.data(), b.width);
-    if (st == HSFLOW_OK && fb_wanted() && src == "-hd") st = hsflow_set_frames_reversed(ctx, 1, 0);
+    if (st == HSFLOW_OK && reversed_pair_wanted() && src == "-hd") st = hsflow_set_frames_reversed(ctx, 1, 0);
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
     hsflow_params p;
     hsflow_default_params(&p);
@@ -421,6 +505,7 @@ int HSOpticalFlowOpenCL::run()
         }
         std::cout << "Avg time: " << lastMs << " [ms]" << std::endl; // :755
         const int verdict = verify_wanted() ? verifyResults() : SDK_SUCCESS;
+        if (median_step(ctx, (int)width, (int)height, render_on_device() ? nullptr : &u, render_on_device() ? nullptr : &v) != SDK_SUCCESS) return SDK_FAILURE;
         if (jpeg_on_device(output)) return save_jpeg_from_device(ctx, HSFLOW_RENDER_CL, (int)width, (int)height, output) == SDK_SUCCESS ? verdict : SDK_FAILURE;
         pnm::Image imgFlow;
         if (warp_wanted()) {
@@ -490,7 +575,7 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     }
     const int W = from_files ? jw : c1.width, H = from_files ? jh : c1.height;
     hsflow_ctx *ctx = nullptr;
-    if (hsflow_create(&ctx, 0, W, H, fb_wanted() ? 2 : 1, nullptr, 1) != HSFLOW_OK) { std::cout << hsflow_last_error(nullptr) << std::endl; return 1; } // (fb: the reversed pair beside it)
+    if (hsflow_create(&ctx, 0, W, H, reversed_pair_wanted() ? 2 : 1, nullptr, 1) != HSFLOW_OK) { std::cout << hsflow_last_error(nullptr) << std::endl; return 1; } // (fb, median fill: the reversed pair beside it)
     int st;
     const double t0 = now_ms();
     if (from_files) { // cvLoadImage + cvCvtColor + cvSmooth, all on the device
@@ -502,7 +587,7 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     } else {
         st = hsflow_set_frames_gray8_blur(ctx, 0, c1.data.data(), (size_t)W, c2.data.data(), (size_t)W);
     }
-    if (st == HSFLOW_OK && fb_wanted()) st = hsflow_set_frames_reversed(ctx, 1, 0);
+    if (st == HSFLOW_OK && reversed_pair_wanted()) st = hsflow_set_frames_reversed(ctx, 1, 0);
     hsflow_params p;
     hsflow_default_params(&p);          // ITER|EPS, eps = (float)1e-6 as at OpticalFlowOpenCV.cpp:29
     p.lambda = lambda;
@@ -516,6 +601,7 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; hsflow_destroy(ctx); return 1; }
     hsflow_verify_report report;
     const int verdict = verify_wanted() ? verify_pair(ctx, W, report) : SDK_SUCCESS; // (the context goes away below)
+    if (median_step(ctx, W, H, on_device ? nullptr : &u, on_device ? nullptr : &v) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     pnm::Image imgFlow;
     const bool file_on_device = jpeg_on_device(output ? output : "");
     if (file_on_device) {

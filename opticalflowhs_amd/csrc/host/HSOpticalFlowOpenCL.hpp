@@ -80,6 +80,9 @@ bool warp_wanted();
 // HSFLOW_PICTURE=fb: the file is the forward-backward consistency mask of the pair against its reverse (the two "-hd"
 // routes only).
 bool fb_wanted();
+// HSFLOW_MEDIAN=<radius>[,<passes>[,fill]]: the flow is median-filtered, or its untrusted pixels filled, in place before
+// the picture is drawn (the two "-hd" routes only).
+bool median_wanted();
 
 // GPU counterpart of the reference's CPU route (OpticalFlowHS/OpticalFlowOpenCV.hpp:6-11):
 // gray -> 3x3 box blur -> Horn-Schunck(lambda, ITER|EPS, eps 1e-6) -> arrows, all but the file I/O

@@ -25,6 +25,12 @@
 // the statistics; by hsflow_fb_host from the flows read back, with HSFLOW_RENDER_DEVICE=1 by hsflow_fb on the device; the
 // same file and line.  HSFLOW_FB_ALPHA / HSFLOW_FB_BETA=<float>: the bound's two terms (defaults 0.01 and 0.5; finite,
 // 0 .. 1e6 and 0 .. 1e30, else a message and exit status 1).
+// HSFLOW_MEDIAN=<radius>[,<passes>[,fill]] (the two -hd routes): the solved flow is median-filtered in place on the device
+// (hsflow_median_apply; radius 1 or 2, passes 1 .. 64) before the picture that HSFLOW_PICTURE asks for is drawn.  With
+// "fill" the pair is also solved backwards as for HSFLOW_PICTURE=fb, the hsflow_fb mask (HSFLOW_FB_ALPHA / HSFLOW_FB_BETA)
+// is the state, only the untrusted pixels are replaced by the median of their trusted neighbours, and one line "median:
+// kept .. filled .. unfilled .. newly_filled .. changed .." tells the record of the last pass.  A bad value: a message
+// and exit status 1.
 // HSFLOW_VERIFY=1: every solved pair is verified on the device (hsflow_verify: re-solved sweep by sweep, compared
 // there) before its context goes away; one "Passed!" / "Failed" line per pair on stdout, the pictures are written as
 // always, and the exit status is SDK_FAILURE if any pair failed.
@@ -67,6 +73,7 @@ int main(int argc, char *argv[])
     if (!picture_choice_usable()) return 1;
     if (warp_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=warp needs a pair of files (-hd)\n"; return 1; }
     if (fb_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=fb needs a pair of files (-hd)\n"; return 1; }
+    if (median_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_MEDIAN needs a pair of files (-hd)\n"; return 1; }
     if (argc >= 3 && strcmp(argv[1], "-cl") == 0) {
         if (strcmp(argv[2], "-hd") == 0) {
             if (argc != 10) { std::cout << "Wrong argument list!\n"; return 0; }

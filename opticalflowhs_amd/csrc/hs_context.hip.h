@@ -308,6 +308,15 @@ struct hsflow_ctx {
         int out_pictures = 0;
         uint64_t *hSize = nullptr;
     } jpeg_batch;
+    // hsflow_median_apply / hsflow_median (hs_median.hip.h), each piece allocated by the first call that needs it and kept:
+    // packed fp32 plane pairs between the passes (apply: one; the synchronous form with several passes: two), two state
+    // planes, one statistics record on the device and one in page-locked memory.  The device forms take the caller's
+    // memory and allocate nothing.  (Last in the context: every other member stays where it was.)
+    struct MedianScratch {
+        float *u[2] = {nullptr, nullptr}, *v[2] = {nullptr, nullptr};
+        uint8_t *s[2] = {nullptr, nullptr};
+        hsflow_median_stats *dStats = nullptr, *hStats = nullptr;
+    } median;
 };
 
 namespace {

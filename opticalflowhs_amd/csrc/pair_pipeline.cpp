@@ -473,6 +473,33 @@ int hsflow_pipeline_fb_device(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t
     return HSFLOW_OK;
 }
 
+int hsflow_pipeline_median(hsflow_pipeline *pl, uint64_t ticket, const hsflow_median_params *mp, int passes, const uint8_t *state, size_t state_stride,
+                           float *u, float *v, size_t out_stride, uint8_t *state_out, size_t state_out_stride, hsflow_median_stats *stats)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    // (like hsflow_fb it waits for an event behind its own copies only)
+    if ((st = hsflow_median(s->ctx, 0, mp, passes, state, state_stride, u, v, out_stride, state_out, state_out_stride, stats))) return ctx_fail(pl, s->ctx, st, "hsflow_median");
+    return HSFLOW_OK;
+}
+
+int hsflow_pipeline_median_apply(hsflow_pipeline *pl, uint64_t ticket, const hsflow_median_params *mp, int passes, const void *d_state,
+                                 size_t state_stride, void *d_state_out, size_t state_out_stride, hsflow_median_stats *d_stats)
+{
+    if (!pl) return HSFLOW_E_ARG;
+    int st = HSFLOW_OK;
+    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
+    if (!s) return st;
+    if ((st = hsflow_median_apply(s->ctx, 0, mp, passes, d_state, state_stride, d_state_out, state_out_stride, d_stats)))
+        return ctx_fail(pl, s->ctx, st, "hsflow_median_apply");
+    // the slot is idle, so its event is free: behind the launches, and only they are waited for
+    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
+        return pfail(pl, HSFLOW_E_DEVICE, "waiting for the slot's median failed");
+    return HSFLOW_OK;
+}
+
 int hsflow_pipeline_verify(hsflow_pipeline *pl, uint64_t ticket, hsflow_verify_report *report)
 {
     if (!pl) return HSFLOW_E_ARG;

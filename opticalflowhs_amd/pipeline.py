@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HsflowError, HsflowInfo, HsflowVerifyReport, TERM_ITER
-from .solver import _is_device_tensor, _render_host, _render_target, _warp_call, _fb_call, jpeg_bound, make_color_params, make_params, make_render_params
+from .solver import _is_device_tensor, _render_host, _render_target, _warp_call, _fb_call, _median_call, jpeg_bound, make_color_params, make_params, make_render_params
 
 
 def pinned_empty(shape, dtype):
@@ -219,6 +219,25 @@ class PairPipeline(object):
         self._held.pop(int(ticket_fwd), None)
         self._held.pop(int(ticket_bwd), None)
         return mask, err2, rec
+
+    def median(self, ticket, state=None, flow=True, state_out=False, stats=False, radius=1, mode="filter", min_votes=1, passes=1, params=None):
+        """wait(ticket) + the host form of `HSFlow.median` of that pair's flow on its slot (NumPy planes, the slot's flow
+        unchanged): complete on return.  Returns (u_out, v_out, state_out, stats).  Raises HsflowError (E_STATE) once the
+        slot has been reused by a later pair."""
+        mp, (sp, ss), (up, vp, os_), (sop, sos), sref, u_out, v_out, state_out, rec = _median_call(
+            self.height, self.width, self.device, state, flow, state_out, stats, params, radius, mode, min_votes, False)
+        self._check(self._lib.hsflow_pipeline_median(self._h, int(ticket), ctypes.byref(mp), int(passes), sp, ss, up, vp, os_, sop, sos, sref))
+        self._held.pop(int(ticket), None)
+        return u_out, v_out, state_out, rec
+
+    def median_apply(self, ticket, state=None, passes=1, state_out=False, stats=False, radius=1, mode="filter", min_votes=1, params=None):
+        """wait(ticket) + `HSFlow.median_apply` on that pair's slot: the slot's flow is replaced (CUDA tensors as there),
+        complete on return.  Returns (state_out, stats)."""
+        mp, (sp, ss), _, (sop, sos), sref, _, _, state_out, rec = _median_call(
+            self.height, self.width, self.device, state, None, state_out, stats, params, radius, mode, min_votes, True)
+        self._check(self._lib.hsflow_pipeline_median_apply(self._h, int(ticket), ctypes.byref(mp), int(passes), sp, ss, sop, sos, sref))
+        self._held.pop(int(ticket), None)
+        return state_out, rec
 
     def verify(self, ticket):
         """wait(ticket) + `HSFlow.verify` of that pair on its slot (what the slot actually ran, the pipeline's own launch

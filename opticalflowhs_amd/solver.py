@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowMedianParams, HsflowMedianStats, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -230,6 +230,59 @@ def _fb_call(height, width, device_index, mask, err2, stats, params, alpha, beta
         rec = HsflowFbStats()
         sref = ctypes.byref(rec)
     return device, (ctypes.byref(fp), mp, ms, ep, es, sref), mask, err2, rec
+
+
+def make_median_params(radius=1, mode="filter", min_votes=1):
+    """hsflow_median_params: radius 1 (3x3) or 2 (5x5); mode "filter" (every pixel becomes its window's median) or "fill"
+    (only pixels whose state is 0 are replaced), or the MEDIAN_* constant; min_votes 1 .. (2 radius + 1)^2, the voters a
+    window needs.  include/hsflow.h has the rule."""
+    mp = HsflowMedianParams()
+    _lib.load().hsflow_default_median_params(ctypes.byref(mp))
+    if isinstance(mode, str):
+        if mode not in ("filter", "fill"):
+            raise ValueError("mode must be 'filter' or 'fill'")
+        mode = MEDIAN_FILL if mode == "fill" else MEDIAN_FILTER
+    mp.radius, mp.mode, mp.min_votes = int(radius), int(mode), int(min_votes)
+    return mp
+
+
+def _median_call(height, width, device_index, state, flow, state_out, stats, params, radius, mode, min_votes, device):
+    """What the median entries share.  state: None or the u8 plane (H, W); flow: False / None (absent), True (allocated
+    here) or the pair (u_out, v_out) of float32 planes of one row stride; state_out: False / None, True or the u8 plane;
+    stats: True or False.  Returns (mp, (state pointer, stride), (u pointer, v pointer, stride), (state_out pointer,
+    stride), record pointer, u_out, v_out, state_out, record)."""
+    def fresh(dtype):
+        if device:
+            import torch
+            return torch.empty((height, width), dtype=getattr(torch, dtype), device="cuda:%d" % device_index)
+        return np.empty((height, width), dtype)
+    sp, ss = _fb_plane(state, height, width, "uint8", "state", device) if state is not None else (None, 0)
+    u_out = v_out = None
+    up = vp = None
+    os_ = 0
+    if flow is True:
+        u_out, v_out = fresh("float32"), fresh("float32")
+    elif flow is not None and flow is not False:
+        u_out, v_out = flow
+    if u_out is not None:
+        (up, os_), (vp, vs) = _fb_plane(u_out, height, width, "float32", "u_out", device), _fb_plane(v_out, height, width, "float32", "v_out", device)
+        if vs != os_:
+            raise ValueError("u_out and v_out must have one row stride")
+    if state_out is True:
+        state_out = fresh("uint8")
+    elif state_out is False:
+        state_out = None
+    sop, sos = _fb_plane(state_out, height, width, "uint8", "state_out", device) if state_out is not None else (None, 0)
+    mp = params if params is not None else make_median_params(radius, mode, min_votes)
+    rec, sref = None, None
+    if stats and device:
+        import torch
+        rec = torch.empty(ctypes.sizeof(HsflowMedianStats), dtype=torch.uint8, device="cuda:%d" % device_index)  # (the library clears it)
+        sref = _ptr(rec)
+    elif stats:
+        rec = HsflowMedianStats()
+        sref = ctypes.byref(rec)
+    return mp, (sp, ss), (up, vp, os_), (sop, sos), sref, u_out, v_out, state_out, rec
 
 
 def _render_target(out, height, width):
@@ -639,6 +692,76 @@ class HSFlow(object):
                                                      lists[0], strides[0], lists[1], strides[1], _ptr(stats) if stats is not None else None))
         return mask, err2, stats
 
+    def median(self, pair=0, state=None, flow=True, state_out=False, stats=False, radius=1, mode="filter", min_votes=1, passes=1, params=None, device=False):
+        """The median filter / hole filling of the flow of `pair` (`make_median_params`; include/hsflow.h has the rule); the
+        context's flow is not changed.  state: None or the u8 plane (H, W) of input states (0 invalid, 2 filled, else kept:
+        the default mask of `fb` as it is); flow: False, True (allocated here) or the pair (u_out, v_out) to fill;
+        state_out: False, True or the plane to fill; stats: True for the record of the last pass.  Host planes:
+        synchronous, `passes` passes (`hsflow_median`).  CUDA tensors (or device=True): one pass, only enqueued on the
+        context's stream (`hsflow_median_device`, complete after `synchronize()`), the record then a CUDA uint8 tensor
+        of 64 bytes that `median_stats_from` reads.  Returns (u_out, v_out, state_out, stats), None for what was not
+        asked for."""
+        planes = [state, state_out] + (list(flow) if isinstance(flow, (tuple, list)) else [])
+        device = bool(device) or any(_is_device_tensor(x) for x in planes)
+        mp, (sp, ss), (up, vp, os_), (sop, sos), sref, u_out, v_out, state_out, rec = _median_call(
+            self.height, self.width, self.device, state, flow, state_out, stats, params, radius, mode, min_votes, device)
+        if device:
+            if int(passes) != 1:
+                raise ValueError("the device form runs one pass: chain `median_planes_device`, or use `median_apply`")
+            self._check(self._lib.hsflow_median_device(self._h, int(pair), ctypes.byref(mp), sp, ss, up, vp, os_, sop, sos, sref))
+        else:
+            self._check(self._lib.hsflow_median(self._h, int(pair), ctypes.byref(mp), int(passes), sp, ss, up, vp, os_, sop, sos, sref))
+        return u_out, v_out, state_out, rec
+
+    def median_apply(self, pair=0, state=None, passes=1, state_out=False, stats=False, radius=1, mode="filter", min_votes=1, params=None):
+        """`passes` passes of the median whose result REPLACES the flow of `pair` in the context (`hsflow_median_apply`):
+        every later picture, warp, check and `use_previous` solve reads it.  state, state_out: CUDA uint8 tensors (H, W) as
+        `median` takes them; only enqueued on the context's stream.  Returns (state_out, stats) of the last pass."""
+        mp, (sp, ss), _, (sop, sos), sref, _, _, state_out, rec = _median_call(
+            self.height, self.width, self.device, state, None, state_out, stats, params, radius, mode, min_votes, True)
+        self._check(self._lib.hsflow_median_apply(self._h, int(pair), ctypes.byref(mp), int(passes), sp, ss, sop, sos, sref))
+        return state_out, rec
+
+    def median_planes_device(self, u, v, state=None, flow=True, state_out=False, stats=False, radius=1, mode="filter", min_votes=1, params=None):
+        """One pass of the median over CUDA float32 tensors (H, W) of one row stride (`hsflow_median_planes_device`), only
+        enqueued on the context's stream; the output state is a valid input state, so passes are chained by calling again
+        with the outputs.  Returns (u_out, v_out, state_out, stats) as `median` does."""
+        strides = set(tuple(x.stride()) for x in (u, v))
+        if (not all(_is_device_tensor(x) and str(x.dtype) == "torch.float32" and tuple(x.shape) == (self.height, self.width) for x in (u, v))
+                or len(strides) != 1 or u.stride(1) != 1):
+            raise ValueError("u and v must be CUDA float32 tensors (height, width) of one row stride")
+        mp, (sp, ss), (up, vp, os_), (sop, sos), sref, u_out, v_out, state_out, rec = _median_call(
+            self.height, self.width, self.device, state, flow, state_out, stats, params, radius, mode, min_votes, True)
+        self._check(self._lib.hsflow_median_planes_device(self._h, ctypes.byref(mp), _ptr(u), _ptr(v), u.stride(0) * 4, sp, ss, up, vp, os_, sop, sos, sref))
+        return u_out, v_out, state_out, rec
+
+    def median_batch_device(self, first_pair, n, state=None, u_out=None, v_out=None, state_out=None, stats=None, radius=1, mode="filter", min_votes=1, params=None):
+        """One pass of the median over the flows of the pairs first_pair .. first_pair + n - 1 by one launch per
+        `JPEG_BATCH_MAX` fields (`hsflow_median_batch_device`).  state, u_out, v_out, state_out: each None, a CUDA tensor
+        (n, H, W) or a list of n tensors (H, W), uint8 / float32; one row stride per list, u_out and v_out one between them.
+        stats: None, or a CUDA uint8 tensor of n * 64 bytes that receives record i of field i (`median_stats_from`).
+        Only enqueued on the context's stream (complete after `synchronize()`)."""
+        lists, strides = [], []
+        for x, dtype, what in ((state, "uint8", "state"), (u_out, "float32", "u_out"), (v_out, "float32", "v_out"), (state_out, "uint8", "state_out")):
+            if x is None:
+                lists.append(None)
+                strides.append(0)
+                continue
+            items = [_fb_plane(x[i], self.height, self.width, dtype, what, True) for i in range(len(x))]
+            if len(items) != n or len(set(st for _, st in items)) > 1:
+                raise ValueError("%s must hold one plane per field, all of one row stride" % what)
+            lists.append((ctypes.c_void_p * max(n, 1))(*[p.value for p, _ in items]))
+            strides.append(items[0][1] if items else 0)
+        if u_out is not None and v_out is not None and strides[1] != strides[2]:
+            raise ValueError("u_out and v_out must have one row stride")
+        mp = params if params is not None else make_median_params(radius, mode, min_votes)
+        if stats is not None and (not _is_device_tensor(stats) or str(stats.dtype) != "torch.uint8" or not stats.is_contiguous()
+                                  or stats.numel() < n * ctypes.sizeof(HsflowMedianStats)):
+            raise ValueError("stats must be a contiguous CUDA uint8 tensor of at least n * 64 bytes")
+        self._check(self._lib.hsflow_median_batch_device(self._h, int(first_pair), int(n), ctypes.byref(mp), lists[0], strides[0], lists[1], lists[2],
+                                                         strides[1] or strides[2], lists[3], strides[3], _ptr(stats) if stats is not None else None))
+        return u_out, v_out, state_out, stats
+
     def encode_jpeg(self, rgb, quality=95):
         """The baseline JPEG file (4:2:0, standard tables) of an RGB picture of the context's size that lies in device
         memory -- a CUDA uint8 tensor of shape (H, W, 3) with packed pixels and any row stride -- encoded on the device
@@ -880,6 +1003,33 @@ def fb_host(uf, vf, ub, vb, mask=True, err2=False, stats=False, alpha=0.01, beta
     if st != _lib.OK:
         raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
     return mask, err2, rec
+
+
+def median_stats_from(stats, n=1):
+    """The `HsflowMedianStats` records a device call left in the CUDA uint8 tensor `stats` (after `synchronize()`): one
+    record for n=1, else a list of n."""
+    raw = stats.cpu().numpy().tobytes()
+    size = ctypes.sizeof(HsflowMedianStats)
+    recs = [HsflowMedianStats.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(n)]
+    return recs[0] if n == 1 else recs
+
+
+def median_host(u, v, state=None, flow=True, state_out=False, stats=False, radius=1, mode="filter", min_votes=1, passes=1, params=None):
+    """The median filter / hole filling by the rule on the host (`hsflow_median_host`, no GPU work): two float32 arrays of
+    one shape (H, W), padded rows taken as they are; state, flow, state_out, stats as `HSFlow.median` takes them.
+    Returns (u_out, v_out, state_out, stats) -- bit for bit what the device forms give from the same planes."""
+    planes = [a if a.ndim == 2 and a.strides[1] == 4 and a.strides[0] % 4 == 0 else np.ascontiguousarray(a)
+              for a in (np.asarray(x, np.float32) for x in (u, v))]
+    if planes[0].ndim != 2 or planes[1].shape != planes[0].shape:
+        raise ValueError("u and v must be 2-D arrays of one shape")
+    H, W = planes[0].shape
+    mp, (sp, ss), (up, vp, os_), (sop, sos), sref, u_out, v_out, state_out, rec = _median_call(
+        H, W, 0, state, flow, state_out, stats, params, radius, mode, min_votes, False)
+    st = _lib.load().hsflow_median_host(_ptr(planes[0]), planes[0].strides[0], _ptr(planes[1]), planes[1].strides[0], sp, ss, W, H, ctypes.byref(mp),
+                                        int(passes), up, vp, os_, sop, sos, sref)
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return u_out, v_out, state_out, rec
 
 
 def compare_planes(a, b):
