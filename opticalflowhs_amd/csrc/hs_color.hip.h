@@ -38,7 +38,7 @@ int enqueue_color_chunk(hsflow_ctx *c, int first_pair, int cnt, const hsflow_col
     hipLaunchKernelGGL(hsk::k_color_batch, grid, dim3(256), 0, c->stream, u, v, c->plane, pics, (long long)stride, c->W, c->H, c->P,
                        fixed ? (const unsigned *)nullptr : c->dColorScale, fixed ? cp.max_flow : 0.f);
     HS_HIP(c, hipGetLastError());
-    c->last_marked = false; // (as enqueue_render: the flow planes are read behind the marker of the last solve)
+    c->last_marked = false; // (hs_postops.hip.h, rule 2: the flow planes are read behind the marker of the last solve)
     return HSFLOW_OK;
 }
 
@@ -79,18 +79,15 @@ int hsflow_color_flow_batch_device(hsflow_ctx *c, int first_pair, int n, const h
     for (int i = 0; i < n; i++)
         if (!d_rgb[i]) return fail(c, HSFLOW_E_ARG, "picture " + std::to_string(i) + ": null picture pointer");
     if (stride < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
-    if ((st = check_batch_max(c, &maxb))) return st;
-    // the picture of a flow that a re-run would change is worth nothing: an owed ITER|EPS check is settled first
-    if ((st = settle_pending(c))) return st;
+    if ((st = batch_device_begin(c, nullptr, &maxb))) return st;
     if ((st = color_reserve(c))) return st;
-    for (int first = 0; first < n; first += maxb) {
-        const int cnt = n - first < maxb ? n - first : maxb;
+    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb)) {
         hsk::RenderBatchPics pics{};
-        for (int k = 0; k < cnt; k++) {
-            pics.rgb[k] = (uint8_t *)d_rgb[first + k];
-            if (word_aligned(d_rgb[first + k], stride)) pics.wide |= 1u << k;
+        for (int k = 0; k < ch.count; k++) {
+            pics.rgb[k] = (uint8_t *)d_rgb[ch.first + k];
+            if (word_aligned(d_rgb[ch.first + k], stride)) pics.wide |= 1u << k;
         }
-        if ((st = enqueue_color_chunk(c, first_pair + first, cnt, *cp, pics, stride))) return st;
+        if ((st = enqueue_color_chunk(c, first_pair + ch.first, ch.count, *cp, pics, stride))) return st;
     }
     return HSFLOW_OK;
 }
@@ -116,19 +113,18 @@ int hsflow_color_flow(hsflow_ctx *c, int pair, const hsflow_color_params *cp, ui
     if ((st = color_reserve(c))) return st;
     if (!c->dRgb) HS_HIP(c, hipMalloc((void **)&c->dRgb, rowb * c->H));
     if (!c->hColorScale) HS_HIP(c, hipHostMalloc((void **)&c->hColorScale, 64, hipHostMallocDefault));
-    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
-    const bool marked = c->last_marked, fixed = cp->scale_mode == HSFLOW_COLOR_SCALE_FIXED;
+    bool marked = false;
+    if ((st = sync_begin(c, &marked))) return st;
+    const bool fixed = cp->scale_mode == HSFLOW_COLOR_SCALE_FIXED;
     hsk::RenderBatchPics pics{};
     pics.rgb[0] = c->dRgb;
     pics.wide = (uint32_t)word_aligned(c->dRgb, rowb);
     if ((st = enqueue_color_chunk(c, pair, 1, *cp, pics, rowb))) return st;
     HS_HIP(c, copy_rows_async(c, rgb, stride, c->dRgb, rowb, rowb, c->H, hipMemcpyDeviceToHost));
     if (scale_used && !fixed) HS_HIP(c, hipMemcpyAsync(c->hColorScale, c->dColorScale, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    // only what THIS context enqueued is waited for (the slots of a pair pipeline share streams)
-    HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-    HS_HIP(c, hipEventSynchronize(c->evRender));
+    if ((st = sync_wait(c))) return st;
     if (scale_used) *scale_used = fixed ? cp->max_flow : hscolor::auto_scale(*c->hColorScale);
-    c->last_marked = marked; // nothing of the picture is in flight any more: the solve's marker speaks for the context again
+    sync_restore(c, marked);
     return check_persist(c);
 }
 

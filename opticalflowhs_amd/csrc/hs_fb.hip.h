@@ -57,14 +57,9 @@ int enqueue_fb_chunk(hsflow_ctx *c, int cnt, const hsflow_fb_params &fp, const h
                      void *d_stats)
 {
     hsk::FbStatsWords *stats = (hsk::FbStatsWords *)d_stats;
-    // With statistics every workgroup ends in atomics on its check's one record, which the memory side serialises: up to
-    // 8 rows per workgroup while two workgroups per compute unit remain (as enqueue_warp_chunk).
-    const long long gx = (c->W + 1023) / 1024, cus = c->num_cu > 0 ? c->num_cu : 256;
-    long long per = stats ? gx * c->H * cnt / (2 * cus) : 1;
-    per = per < 1 ? 1 : per > 8 ? 8 : per;
-    const long long gy = (c->H + per - 1) / per;
-    const dim3 grid((unsigned)gx, (unsigned)(gy < 65535 ? gy : 65535), (unsigned)cnt);
-    if (stats) HS_HIP(c, hipMemsetAsync(stats, 0, sizeof(hsk::FbStatsWords) * (size_t)cnt, c->stream));
+    dim3 grid;
+    const int st = stats_grid(c, (c->W + 1023) / 1024, c->H, cnt, stats, &grid);
+    if (st) return st;
     if (with_err2) {
         if (stats) launch_fb<true, true>(c, grid, chk, bs, ms, es, fp, stats);
         else launch_fb<true, false>(c, grid, chk, bs, ms, es, fp, stats);
@@ -73,30 +68,11 @@ int enqueue_fb_chunk(hsflow_ctx *c, int cnt, const hsflow_fb_params &fp, const h
         else launch_fb<false, false>(c, grid, chk, bs, ms, es, fp, stats);
     }
     HS_HIP(c, hipGetLastError());
-    c->last_marked = false; // (as enqueue_render: the flow planes are read behind the marker of the last solve)
+    c->last_marked = false; // (hs_postops.hip.h, rule 2: the flow planes are read behind the marker of the last solve)
     return HSFLOW_OK;
 }
 
 int fb_wide16(const void *p, size_t stride) { return (((uintptr_t)p | stride) & 15u) == 0; }
-
-// One staging plane of the synchronous form, grown to the largest so far (as warp_stage).
-int fb_stage(hsflow_ctx *c, uint8_t **p, size_t *have, size_t bytes)
-{
-    if (*have >= bytes) return HSFLOW_OK;
-    if (*p && c->evRender) HS_HIP(c, hipEventSynchronize(c->evRender));
-    hipFree(*p);
-    *p = nullptr; *have = 0;
-    HS_HIP(c, hipMalloc((void **)p, bytes));
-    *have = bytes;
-    return HSFLOW_OK;
-}
-
-void fb_release(hsflow_ctx *c)
-{
-    hipFree(c->fb.mask); hipFree(c->fb.err2); hipFree(c->fb.dStats);
-    if (c->fb.hStats) hipHostFree(c->fb.hStats);
-    c->fb = hsflow_ctx::FbScratch();
-}
 
 // The synchronous form: pair fwd_pair forwards against pair bwd_pair of the context, or with bwd_pair < 0 against the
 // backward planes ub / vb (device memory, rows bs bytes apart); the results to host memory.  The caller has checked the
@@ -114,12 +90,11 @@ int fb_to_host(hsflow_ctx *c, int fwd_pair, int bwd_pair, const float *ub, const
     }
     const size_t mrow = (size_t)c->W, erow = (size_t)c->W * 4;
     hsflow_ctx::FbScratch &f = c->fb;
-    if (mask && (st = fb_stage(c, &f.mask, &f.mask_bytes, mrow * c->H))) return st;
-    if (err2 && (st = fb_stage(c, &f.err2, &f.err2_bytes, erow * c->H))) return st;
-    if (stats && !f.dStats) HS_HIP(c, hipMalloc((void **)&f.dStats, sizeof(hsflow_fb_stats)));
-    if (stats && !f.hStats) HS_HIP(c, hipHostMalloc((void **)&f.hStats, sizeof(hsflow_fb_stats), hipHostMallocDefault));
-    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
-    const bool marked = c->last_marked;
+    if (mask && (st = stage_reserve(c, &f.mask, &f.mask_bytes, mrow * c->H))) return st;
+    if (err2 && (st = stage_reserve(c, &f.err2, &f.err2_bytes, erow * c->H))) return st;
+    if (stats && (st = stats_reserve(c, (void **)&f.dStats, (void **)&f.hStats))) return st;
+    bool marked = false;
+    if ((st = sync_begin(c, &marked))) return st;
     hsk::FbBatchChecks chk{};
     chk.uf[0] = c->dU[c->cur] + fwd_pair * c->plane; chk.vf[0] = c->dV[c->cur] + fwd_pair * c->plane;
     chk.ub[0] = ub; chk.vb[0] = vb;
@@ -130,13 +105,8 @@ int fb_to_host(hsflow_ctx *c, int fwd_pair, int bwd_pair, const float *ub, const
     if ((st = enqueue_fb_chunk(c, 1, *fp, chk, err2 != nullptr, bs, mrow, erow, stats ? f.dStats : nullptr))) return st;
     if (mask) HS_HIP(c, copy_rows_async(c, mask, mask_stride, f.mask, mrow, mrow, c->H, hipMemcpyDeviceToHost));
     if (err2) HS_HIP(c, copy_rows_async(c, err2, err2_stride, f.err2, erow, erow, c->H, hipMemcpyDeviceToHost));
-    if (stats) HS_HIP(c, hipMemcpyAsync(f.hStats, f.dStats, sizeof(hsflow_fb_stats), hipMemcpyDeviceToHost, c->stream));
-    // only what THIS context enqueued is waited for (the slots of a pair pipeline share streams)
-    HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-    HS_HIP(c, hipEventSynchronize(c->evRender));
-    if (stats) *stats = *f.hStats;
-    c->last_marked = marked; // nothing of the check is in flight any more: the solve's marker speaks for the context again
-    return check_persist(c);
+    if (stats && (st = stats_copy_back(c, f.hStats, f.dStats))) return st;
+    return sync_finish(c, marked, stats, f.hStats);
 }
 
 // What the device forms share.  bwd_pairs: the backward flow is that of the context's pairs; else ub / vb / bs for every
@@ -155,26 +125,23 @@ int fb_on_device(hsflow_ctx *c, int n, const int *fwd_pairs, const int *bwd_pair
         if ((d_mask && !d_mask[i]) || (d_err2 && !d_err2[i])) return fail(c, HSFLOW_E_ARG, "check " + std::to_string(i) + ": null output pointer");
         if (d_err2 && ((uintptr_t)d_err2[i] & 3u)) return fail(c, HSFLOW_E_ARG, "check " + std::to_string(i) + ": err2 must be 4-byte aligned");
     }
-    if (((uintptr_t)d_stats & 7u) != 0) return fail(c, HSFLOW_E_ARG, "the statistics records must be 8-byte aligned");
-    if ((st = check_batch_max(c, &maxb))) return st;
-    // a check of a flow that a re-run would change is worth nothing: an owed ITER|EPS check is settled first
-    if ((st = settle_pending(c))) return st;
+    if ((st = batch_device_begin(c, d_stats, &maxb))) return st;
     const float *U = c->dU[c->cur], *V = c->dV[c->cur];
-    for (int first = 0; first < n; first += maxb) {
-        const int cnt = n - first < maxb ? n - first : maxb;
+    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb)) {
         hsk::FbBatchChecks chk{};
-        for (int k = 0; k < cnt; k++) {
-            const long long fwd = fwd_pairs[first + k];
+        for (int k = 0; k < ch.count; k++) {
+            const int i = ch.first + k;
+            const long long fwd = fwd_pairs[i];
             chk.uf[k] = U + fwd * c->plane; chk.vf[k] = V + fwd * c->plane;
-            chk.ub[k] = bwd_pairs ? U + (long long)bwd_pairs[first + k] * c->plane : ub;
-            chk.vb[k] = bwd_pairs ? V + (long long)bwd_pairs[first + k] * c->plane : vb;
-            chk.mask[k] = d_mask ? (uint8_t *)d_mask[first + k] : nullptr;
-            chk.err2[k] = d_err2 ? (float *)d_err2[first + k] : nullptr;
-            if (d_mask && word_aligned(d_mask[first + k], mask_stride)) chk.wide_mask |= 1u << k;
-            if (d_err2 && fb_wide16(d_err2[first + k], err2_stride)) chk.wide_err2 |= 1u << k;
+            chk.ub[k] = bwd_pairs ? U + (long long)bwd_pairs[i] * c->plane : ub;
+            chk.vb[k] = bwd_pairs ? V + (long long)bwd_pairs[i] * c->plane : vb;
+            chk.mask[k] = d_mask ? (uint8_t *)d_mask[i] : nullptr;
+            chk.err2[k] = d_err2 ? (float *)d_err2[i] : nullptr;
+            if (d_mask && word_aligned(d_mask[i], mask_stride)) chk.wide_mask |= 1u << k;
+            if (d_err2 && fb_wide16(d_err2[i], err2_stride)) chk.wide_err2 |= 1u << k;
         }
-        if ((st = enqueue_fb_chunk(c, cnt, *fp, chk, d_err2 != nullptr, bwd_pairs ? (size_t)c->P * 4 : bs, mask_stride, err2_stride,
-                                   d_stats ? d_stats + first : nullptr)))
+        if ((st = enqueue_fb_chunk(c, ch.count, *fp, chk, d_err2 != nullptr, bwd_pairs ? (size_t)c->P * 4 : bs, mask_stride, err2_stride,
+                                   d_stats ? d_stats + ch.first : nullptr)))
             return st;
     }
     return HSFLOW_OK;

@@ -209,8 +209,7 @@ int render_jpeg_batch_begin(hsflow_ctx *c, int first_pair, int n, const Drawing 
     if ((st = d.color ? check_color_params(c, d.cp) : check_render_params(c, d.rp))) return st;
     if ((st = check_jpeg_batch_args(c, n, quality, jpeg, bytes))) return st;
     if (aligned8 && ((uintptr_t)bytes & 7u)) return fail(c, HSFLOW_E_ARG, "the size words must be 8-byte aligned");
-    if ((st = check_batch_max(c, maxb))) return st;
-    if ((st = settle_pending(c))) return st;
+    if ((st = batch_device_begin(c, nullptr, maxb))) return st;
     const int most = n < *maxb ? n : *maxb;
     if ((st = jpeg_tables(c, quality, tab))) return st;
     if ((st = d.color ? color_reserve(c) : render_batch_reserve(c, most))) return st;
@@ -270,9 +269,8 @@ int draw_jpeg_batch(hsflow_ctx *c, int first_pair, int n, const Drawing &d, int 
         b.slot = s; b.out_pictures = pictures;
     }
     if (!b.hSize) HS_HIP(c, hipHostMalloc((void **)&b.hSize, sizeof(uint64_t) * hsk::kJpegBatchMax, hipHostMallocDefault));
-    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
-    const bool marked = c->last_marked;
-    bool fits = true;
+    bool marked = false, fits = true;
+    if ((st = sync_begin(c, &marked))) return st;
     for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb)) {
         uint8_t *out[hsk::kJpegBatchMax];
         for (int k = 0; k < ch.count; k++) out[k] = b.out + b.slot * (size_t)k;
@@ -281,8 +279,7 @@ int draw_jpeg_batch(hsflow_ctx *c, int first_pair, int n, const Drawing &d, int 
         // the chunk's size words in one copy, then each file's bytes: only the files cross, and what THIS context enqueued
         // is all that is waited for
         HS_HIP(c, hipMemcpyAsync(b.hSize, words, sizeof(uint64_t) * (size_t)ch.count, hipMemcpyDeviceToHost, c->stream));
-        HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-        HS_HIP(c, hipEventSynchronize(c->evRender));
+        if ((st = sync_wait(c))) return st;
         bool any = false;
         for (int k = 0; k < ch.count; k++) {
             const uint64_t size = b.hSize[k];
@@ -291,12 +288,9 @@ int draw_jpeg_batch(hsflow_ctx *c, int first_pair, int n, const Drawing &d, int 
             HS_HIP(c, hipMemcpyAsync(jpeg[ch.first + k], out[k], (size_t)size, hipMemcpyDeviceToHost, c->stream));
             any = true;
         }
-        if (any) {
-            HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-            HS_HIP(c, hipEventSynchronize(c->evRender));
-        }
+        if (any && (st = sync_wait(c))) return st;
     }
-    c->last_marked = marked; // nothing of this call is in flight any more: the solve's marker speaks for the context again
+    sync_restore(c, marked);
     if (!fits) return fail(c, HSFLOW_E_SIZE, "capacity smaller than a file (hsflow_jpeg_bound always suffices)");
     return check_persist(c);
 }
@@ -345,32 +339,24 @@ int hsflow_render_flow_jpeg(hsflow_ctx *c, int pair, const hsflow_render_params 
     if (st) return st;
     hsflow_ctx::JpegScratch &j = c->jpeg;
     const size_t bound = hsjpeg::bound(c->W, c->H), want = capacity < bound ? (capacity ? capacity : 1) : bound;
-    if (j.out_bytes < want) { // (the synchronous forms leave nothing in flight that reads the old one)
-        hipFree(j.out);
-        j.out = nullptr; j.out_bytes = 0;
-        HS_HIP(c, hipMalloc((void **)&j.out, want));
-        j.out_bytes = want;
-    }
+    if ((st = stage_reserve(c, &j.out, &j.out_bytes, want))) return st;
     if (!j.hSize) HS_HIP(c, hipHostMalloc((void **)&j.hSize, 64, hipHostMallocDefault));
-    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
-    const bool marked = c->last_marked;
+    bool marked = false;
+    if ((st = sync_begin(c, &marked))) return st;
     const size_t rowb = (size_t)c->W * 3, cap = capacity < bound ? capacity : bound;
     if ((st = enqueue_render(c, pair, *rp, c->dRgb, rowb))) return st;
     if ((st = enqueue_jpeg(c, c->dRgb, rowb, quality, j.out, cap, nullptr))) return st;
-    // the size word first, then that many bytes: only the file crosses; what THIS context enqueued is all that is waited for
+    // the size word first, then that many bytes: only the file crosses
     HS_HIP(c, hipMemcpyAsync(j.hSize, j.size, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-    HS_HIP(c, hipEventSynchronize(c->evRender));
+    if ((st = sync_wait(c))) return st;
     const uint64_t size = *j.hSize;
     *bytes = (size_t)size;
-    if (size <= capacity) {
-        HS_HIP(c, hipMemcpyAsync(jpeg, j.out, (size_t)size, hipMemcpyDeviceToHost, c->stream));
-        HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-        HS_HIP(c, hipEventSynchronize(c->evRender));
+    if (size > capacity) {
+        sync_restore(c, marked);
+        return fail(c, HSFLOW_E_SIZE, "capacity smaller than the file (hsflow_jpeg_bound always suffices)");
     }
-    c->last_marked = marked; // nothing of this call is in flight any more: the solve's marker speaks for the context again
-    if (size > capacity) return fail(c, HSFLOW_E_SIZE, "capacity smaller than the file (hsflow_jpeg_bound always suffices)");
-    return check_persist(c);
+    HS_HIP(c, hipMemcpyAsync(jpeg, j.out, (size_t)size, hipMemcpyDeviceToHost, c->stream));
+    return sync_finish(c, marked);
 }
 
 int hsflow_jpeg_encode_batch_device(hsflow_ctx *c, const void *const *d_rgb, int n, size_t stride, int quality, void *const *d_jpeg, size_t capacity,

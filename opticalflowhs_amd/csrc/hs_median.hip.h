@@ -62,18 +62,12 @@ int enqueue_median_chunk(hsflow_ctx *c, int cnt, const hsflow_median_params &mp,
                          void *d_stats)
 {
     hsk::MedianStatsWords *stats = (hsk::MedianStatsWords *)d_stats;
-    // With statistics every workgroup ends in atomics on its field's one record, which the memory side serialises: up to
-    // 8 tiles per workgroup while two workgroups per compute unit remain (as enqueue_fb_chunk).
-    const long long gx = (c->W + hsk::kMedTileX - 1) / hsk::kMedTileX, tiles_y = (c->H + hsk::kMedTileY - 1) / hsk::kMedTileY;
-    const long long cus = c->num_cu > 0 ? c->num_cu : 256;
-    long long per = stats ? gx * tiles_y * cnt / (2 * cus) : 1;
-    per = per < 1 ? 1 : per > 8 ? 8 : per;
-    const long long gy = (tiles_y + per - 1) / per;
-    const dim3 grid((unsigned)gx, (unsigned)(gy < 65535 ? gy : 65535), (unsigned)cnt);
-    if (stats) HS_HIP(c, hipMemsetAsync(stats, 0, sizeof(hsk::MedianStatsWords) * (size_t)cnt, c->stream));
+    dim3 grid;
+    const int st = stats_grid(c, (c->W + hsk::kMedTileX - 1) / hsk::kMedTileX, (c->H + hsk::kMedTileY - 1) / hsk::kMedTileY, cnt, stats, &grid);
+    if (st) return st;
     HS_HIP(c, hsk::launch_median_batch(mp.radius, mp.mode == HSFLOW_MEDIAN_FILL, grid, c->stream, f, (long long)is, (long long)ss, (long long)os, (long long)sos, c->W,
                                        c->H, mp.min_votes, stats));
-    c->last_marked = false; // (as enqueue_render: the flow planes are read behind the marker of the last solve)
+    c->last_marked = false; // (hs_postops.hip.h, rule 2: the flow planes are read behind the marker of the last solve)
     return HSFLOW_OK;
 }
 
@@ -88,18 +82,7 @@ int median_reserve(hsflow_ctx *c, int flow_pairs, int byte_planes, bool stats)
     }
     for (int k = 0; k < byte_planes; k++)
         if (!m.s[k]) HS_HIP(c, hipMalloc((void **)&m.s[k], bbytes));
-    if (stats && !m.dStats) HS_HIP(c, hipMalloc((void **)&m.dStats, sizeof(hsflow_median_stats)));
-    if (stats && !m.hStats) HS_HIP(c, hipHostMalloc((void **)&m.hStats, sizeof(hsflow_median_stats), hipHostMallocDefault));
-    return HSFLOW_OK;
-}
-
-void median_release(hsflow_ctx *c)
-{
-    hsflow_ctx::MedianScratch &m = c->median;
-    for (int k = 0; k < 2; k++) { hipFree(m.u[k]); hipFree(m.v[k]); hipFree(m.s[k]); }
-    hipFree(m.dStats);
-    if (m.hStats) hipHostFree(m.hStats);
-    c->median = hsflow_ctx::MedianScratch();
+    return stats ? stats_reserve(c, (void **)&m.dStats, (void **)&m.hStats) : HSFLOW_OK;
 }
 
 // `passes` passes from the planes (u, v, rows is bytes apart) and the state (or NULL) through the scratch; the scratch is
@@ -146,6 +129,7 @@ int median_on_device(hsflow_ctx *c, int first_pair, int n, const float *u, const
         if (d_u_out && (((uintptr_t)d_u_out[i] | (uintptr_t)d_v_out[i]) & 3u))
             return fail(c, HSFLOW_E_ARG, "field " + std::to_string(i) + ": the output flow planes must be 4-byte aligned");
     }
+    // (the alignment here, not in batch_device_begin: it is checked ahead of the overlaps)
     if (((uintptr_t)d_stats & 7u) != 0) return fail(c, HSFLOW_E_ARG, "the statistics records must be 8-byte aligned");
     // every output of the batch against every input of the batch (the pairs' planes in both buffers of the ping-pong)
     for (int i = 0; i < n; i++) {
@@ -165,23 +149,22 @@ int median_on_device(hsflow_ctx *c, int first_pair, int n, const float *u, const
             }
         }
     }
-    if ((st = check_batch_max(c, &maxb))) return st;
-    // a filter of a flow that a re-run would change is worth nothing: an owed ITER|EPS check is settled first
-    if ((st = settle_pending(c))) return st;
+    if ((st = batch_device_begin(c, nullptr, &maxb))) return st;
     const float *U = c->dU[c->cur], *V = c->dV[c->cur];
-    for (int first = 0; first < n; first += maxb) {
-        const int cnt = n - first < maxb ? n - first : maxb;
+    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb)) {
         hsk::MedianBatchFields f{};
-        for (int k = 0; k < cnt; k++) {
-            const long long pair = first_pair + first + k;
+        for (int k = 0; k < ch.count; k++) {
+            const int i = ch.first + k;
+            const long long pair = first_pair + i;
             f.u[k] = pairs ? U + pair * c->plane : u;
             f.v[k] = pairs ? V + pair * c->plane : v;
-            f.state[k] = d_state ? (const uint8_t *)d_state[first + k] : nullptr;
-            f.u_out[k] = d_u_out ? (float *)d_u_out[first + k] : nullptr;
-            f.v_out[k] = d_v_out ? (float *)d_v_out[first + k] : nullptr;
-            f.state_out[k] = d_state_out ? (uint8_t *)d_state_out[first + k] : nullptr;
+            f.state[k] = d_state ? (const uint8_t *)d_state[i] : nullptr;
+            f.u_out[k] = d_u_out ? (float *)d_u_out[i] : nullptr;
+            f.v_out[k] = d_v_out ? (float *)d_v_out[i] : nullptr;
+            f.state_out[k] = d_state_out ? (uint8_t *)d_state_out[i] : nullptr;
         }
-        if ((st = enqueue_median_chunk(c, cnt, *mp, f, pairs ? (size_t)c->P * 4 : is, state_stride, out_stride, state_out_stride, d_stats ? d_stats + first : nullptr)))
+        if ((st = enqueue_median_chunk(c, ch.count, *mp, f, pairs ? (size_t)c->P * 4 : is, state_stride, out_stride, state_out_stride,
+                                       d_stats ? d_stats + ch.first : nullptr)))
             return st;
     }
     return HSFLOW_OK;
@@ -351,8 +334,8 @@ int hsflow_median(hsflow_ctx *c, int pair, const hsflow_median_params *mp, int p
     const bool need_flow = u != nullptr || passes > 1, need_bytes = state != nullptr || state_out != nullptr || passes > 1;
     hsflow_ctx::MedianScratch &m = c->median;
     if ((st = median_reserve(c, need_flow ? (passes > 1 ? 2 : 1) : 0, need_bytes ? 2 : 0, stats != nullptr))) return st;
-    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
-    const bool marked = c->last_marked;
+    bool marked = false;
+    if ((st = sync_begin(c, &marked))) return st;
     if (state) HS_HIP(c, copy_rows_async(c, m.s[0], brow, state, state_stride, brow, c->H, hipMemcpyHostToDevice));
     const bool last_flow = u != nullptr;
     auto flow_dst = [&](int j, float **uo, float **vo, size_t *os) {
@@ -370,13 +353,8 @@ int hsflow_median(hsflow_ctx *c, int pair, const hsflow_median_params *mp, int p
         HS_HIP(c, copy_rows_async(c, v, out_stride, m.v[(passes & 1) ^ 1], frow, frow, c->H, hipMemcpyDeviceToHost));
     }
     if (state_out) HS_HIP(c, copy_rows_async(c, state_out, state_out_stride, last_state, brow, brow, c->H, hipMemcpyDeviceToHost));
-    if (stats) HS_HIP(c, hipMemcpyAsync(m.hStats, m.dStats, sizeof(hsflow_median_stats), hipMemcpyDeviceToHost, c->stream));
-    // only what THIS context enqueued is waited for (the slots of a pair pipeline share streams)
-    HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-    HS_HIP(c, hipEventSynchronize(c->evRender));
-    if (stats) *stats = *m.hStats;
-    c->last_marked = marked; // nothing of the filter is in flight any more: the solve's marker speaks for the context again
-    return check_persist(c);
+    if (stats && (st = stats_copy_back(c, m.hStats, m.dStats))) return st;
+    return sync_finish(c, marked, stats, m.hStats);
 }
 
 } // extern "C"

@@ -42,38 +42,7 @@ int enqueue_render(hsflow_ctx *c, int pair, const hsflow_render_params &rp, uint
     hipLaunchKernelGGL(hsk::k_render_resolve, grid, dim3(256), 0, c->stream, c->dPrio, d_rgb, (long long)stride, c->W, c->H, c->P, dot, line, wide);
     HS_HIP(c, hipGetLastError());
     c->prio_dirty = false;
-    // work that reads the flow planes now lies behind the marker of the last solve: hsflow_wait_solve and
-    // hsflow_flow_view_device wait for the stream, not for that marker
-    c->last_marked = false;
-    return HSFLOW_OK;
-}
-
-// HSFLOW_JPEG_BATCH_MAX of this call: the environment's (1 .. the header's, for measuring the candidates), else the
-// header's.  0: the environment's value is unusable.
-int jpeg_batch_max()
-{
-    static_assert(HSFLOW_JPEG_BATCH_MAX >= 1 && HSFLOW_JPEG_BATCH_MAX <= hsk::kRenderBatchMax && HSFLOW_JPEG_BATCH_MAX <= hsk::kJpegBatchMax,
-                  "the kernels' argument blocks hold at most 32 pictures");
-    const char *e = getenv("HSFLOW_JPEG_BATCH_MAX");
-    if (!e || !*e) return HSFLOW_JPEG_BATCH_MAX;
-    char *rest = nullptr;
-    const long v = strtol(e, &rest, 10);
-    if (*rest || v < 1 || v > HSFLOW_JPEG_BATCH_MAX) return 0;
-    return (int)v;
-}
-
-// The checks the batched entries share: the pairs ...
-int check_batch_pairs(hsflow_ctx *c, int first_pair, int n)
-{
-    if (n < 1) return fail(c, HSFLOW_E_ARG, "a batch needs at least one picture");
-    if (first_pair < 0 || (long long)first_pair + n > c->N) return fail(c, HSFLOW_E_ARG, "the batch's pairs exceed the context's");
-    return HSFLOW_OK;
-}
-
-// ... and the chunk size of this call into *maxb.
-int check_batch_max(hsflow_ctx *c, int *maxb)
-{
-    if (!(*maxb = jpeg_batch_max())) return fail(c, HSFLOW_E_ARG, "HSFLOW_JPEG_BATCH_MAX in the environment must be 1 .. " + std::to_string(HSFLOW_JPEG_BATCH_MAX));
+    c->last_marked = false; // (hs_postops.hip.h, rule 2: the flow planes are read behind the marker of the last solve)
     return HSFLOW_OK;
 }
 
@@ -112,7 +81,7 @@ int enqueue_render_chunk(hsflow_ctx *c, int first_pair, int cnt, const hsflow_re
     hipLaunchKernelGGL(hsk::k_render_resolve_batch, grid, dim3(256), 0, c->stream, c->dPrio, c->plane, pics, (long long)stride, c->W, c->H, c->P, dot, line);
     HS_HIP(c, hipGetLastError());
     c->prio_dirty = false;
-    c->last_marked = false; // (as enqueue_render: the flow planes are read behind the marker of the last solve)
+    c->last_marked = false; // (hs_postops.hip.h, rule 2: the flow planes are read behind the marker of the last solve)
     return HSFLOW_OK;
 }
 
@@ -140,8 +109,7 @@ int hsflow_render_flow_device(hsflow_ctx *c, int pair, const hsflow_render_param
     if ((st = check_render_params(c, rp))) return st;
     if (!d_rgb) return fail(c, HSFLOW_E_ARG, "null picture pointer");
     if (stride < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
-    // the picture of a flow that a re-run would change is worth nothing: an owed ITER|EPS check is settled first
-    if ((st = settle_pending(c))) return st;
+    if ((st = settle_pending(c))) return st; // (hs_postops.hip.h, rule 1)
     return enqueue_render(c, pair, *rp, (uint8_t *)d_rgb, stride);
 }
 
@@ -155,17 +123,15 @@ int hsflow_render_flow_batch_device(hsflow_ctx *c, int first_pair, int n, const 
     for (int i = 0; i < n; i++)
         if (!d_rgb[i]) return fail(c, HSFLOW_E_ARG, "picture " + std::to_string(i) + ": null picture pointer");
     if (stride < (size_t)c->W * 3) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
-    if ((st = check_batch_max(c, &maxb))) return st;
-    if ((st = settle_pending(c))) return st;
+    if ((st = batch_device_begin(c, nullptr, &maxb))) return st;
     if ((st = render_batch_reserve(c, n < maxb ? n : maxb))) return st;
-    for (int first = 0; first < n; first += maxb) {
-        const int cnt = n - first < maxb ? n - first : maxb;
+    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb)) {
         hsk::RenderBatchPics pics{};
-        for (int k = 0; k < cnt; k++) {
-            pics.rgb[k] = (uint8_t *)d_rgb[first + k];
-            if (word_aligned(d_rgb[first + k], stride)) pics.wide |= 1u << k;
+        for (int k = 0; k < ch.count; k++) {
+            pics.rgb[k] = (uint8_t *)d_rgb[ch.first + k];
+            if (word_aligned(d_rgb[ch.first + k], stride)) pics.wide |= 1u << k;
         }
-        if ((st = enqueue_render_chunk(c, first_pair + first, cnt, *rp, pics, stride))) return st;
+        if ((st = enqueue_render_chunk(c, first_pair + ch.first, ch.count, *rp, pics, stride))) return st;
     }
     return HSFLOW_OK;
 }
@@ -180,15 +146,11 @@ int hsflow_render_flow(hsflow_ctx *c, int pair, const hsflow_render_params *rp, 
     if (stride < rowb) return fail(c, HSFLOW_E_SIZE, "picture stride smaller than 3*width");
     if ((st = settle_pending(c))) return st;
     if (!c->dRgb) HS_HIP(c, hipMalloc((void **)&c->dRgb, rowb * c->H));
-    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
-    const bool marked = c->last_marked;
+    bool marked = false;
+    if ((st = sync_begin(c, &marked))) return st;
     if ((st = enqueue_render(c, pair, *rp, c->dRgb, rowb))) return st;
     HS_HIP(c, copy_rows_async(c, rgb, stride, c->dRgb, rowb, rowb, c->H, hipMemcpyDeviceToHost));
-    // only what THIS context enqueued is waited for (the slots of a pair pipeline share streams)
-    HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-    HS_HIP(c, hipEventSynchronize(c->evRender));
-    c->last_marked = marked; // nothing of the render is in flight any more: the solve's marker speaks for the context again
-    return check_persist(c);
+    return sync_finish(c, marked);
 }
 
 int hsflow_render_line_pixels(int x0, int y0, int x1, int y1, int width, int height, int32_t *xy, int capacity)

@@ -56,14 +56,9 @@ int enqueue_warp_chunk(hsflow_ctx *c, int first_pair, int cnt, const hsflow_warp
 {
     const float *u = c->dU[c->cur] + first_pair * c->plane, *v = c->dV[c->cur] + first_pair * c->plane;
     hsk::WarpStatsWords *stats = (hsk::WarpStatsWords *)d_stats;
-    // With statistics every workgroup ends in atomics on its picture's one record, which the memory side serialises: up to
-    // 8 rows per workgroup while two workgroups per compute unit remain (hs_kernels_warp.hip.h).
-    const long long gx = (c->W + 1023) / 1024, cus = c->num_cu > 0 ? c->num_cu : 256;
-    long long per = stats ? gx * c->H * cnt / (2 * cus) : 1;
-    per = per < 1 ? 1 : per > 8 ? 8 : per;
-    const long long gy = (c->H + per - 1) / per;
-    const dim3 grid((unsigned)gx, (unsigned)(gy < 65535 ? gy : 65535), (unsigned)cnt);
-    if (stats) HS_HIP(c, hipMemsetAsync(stats, 0, sizeof(hsk::WarpStatsWords) * (size_t)cnt, c->stream));
+    dim3 grid;
+    const int st = stats_grid(c, (c->W + 1023) / 1024, c->H, cnt, stats, &grid);
+    if (st) return st;
     if (wp.channels == 1) {
         if (stats) launch_warp<1, true>(c, grid, u, v, pics, ss, rs, ds, wp, stats);
         else launch_warp<1, false>(c, grid, u, v, pics, ss, rs, ds, wp, stats);
@@ -72,30 +67,8 @@ int enqueue_warp_chunk(hsflow_ctx *c, int first_pair, int cnt, const hsflow_warp
         else launch_warp<3, false>(c, grid, u, v, pics, ss, rs, ds, wp, stats);
     }
     HS_HIP(c, hipGetLastError());
-    c->last_marked = false; // (as enqueue_render: the flow planes are read behind the marker of the last solve)
+    c->last_marked = false; // (hs_postops.hip.h, rule 2: the flow planes are read behind the marker of the last solve)
     return HSFLOW_OK;
-}
-
-// One staging picture of the synchronous form, grown to the largest picture so far.  Only hsflow_warp uses the staging, and
-// it returns behind its own event, so the old picture is idle; that event is waited for once more -- the context's own
-// work, not the stream, which a pipeline's slots share.  (After a call that failed between its launch and its wait the
-// picture may still be in use: hipFree holds until the device is idle.)
-int warp_stage(hsflow_ctx *c, uint8_t **p, size_t *have, size_t bytes)
-{
-    if (*have >= bytes) return HSFLOW_OK;
-    if (*p && c->evRender) HS_HIP(c, hipEventSynchronize(c->evRender));
-    hipFree(*p);
-    *p = nullptr; *have = 0;
-    HS_HIP(c, hipMalloc((void **)p, bytes));
-    *have = bytes;
-    return HSFLOW_OK;
-}
-
-void warp_release(hsflow_ctx *c)
-{
-    hipFree(c->warp.src); hipFree(c->warp.ref); hipFree(c->warp.dst); hipFree(c->warp.dStats);
-    if (c->warp.hStats) hipHostFree(c->warp.hStats);
-    c->warp = hsflow_ctx::WarpScratch();
 }
 
 } // namespace
@@ -155,23 +128,19 @@ int hsflow_warp_batch_device(hsflow_ctx *c, int first_pair, int n, const hsflow_
         if (d_dst && ((d_src && d_dst[i] == d_src[i]) || (d_ref && d_dst[i] == d_ref[i])))
             return fail(c, HSFLOW_E_ARG, "picture " + std::to_string(i) + ": the destination is the source or the reference");
     }
-    if (((uintptr_t)d_stats & 7u) != 0) return fail(c, HSFLOW_E_ARG, "the statistics records must be 8-byte aligned");
-    if ((st = check_batch_max(c, &maxb))) return st;
-    // the warp by a flow that a re-run would change is worth nothing: an owed ITER|EPS check is settled first
-    if ((st = settle_pending(c))) return st;
+    if ((st = batch_device_begin(c, d_stats, &maxb))) return st;
     if (own && (st = resolve_lazy_frames(c, false))) return st;
     const size_t ss = own ? (size_t)c->P : src_stride, rs = d_ref ? ref_stride : (size_t)c->P;
-    for (int first = 0; first < n; first += maxb) {
-        const int cnt = n - first < maxb ? n - first : maxb;
+    for (const hsjpeg_plan::Chunk &ch : hsjpeg_plan::chunks(n, maxb)) {
         hsk::WarpBatchPics pics{};
-        for (int k = 0; k < cnt; k++) {
-            const long long pair = first_pair + first + k;
-            pics.src[k] = own ? c->dB + pair * c->plane : (const uint8_t *)d_src[first + k];
-            pics.ref[k] = d_ref ? (const uint8_t *)d_ref[first + k] : own ? c->dA + pair * c->plane : nullptr;
-            pics.dst[k] = d_dst ? (uint8_t *)d_dst[first + k] : nullptr;
-            if (d_dst && word_aligned(d_dst[first + k], dst_stride)) pics.wide |= 1u << k;
+        for (int k = 0; k < ch.count; k++) {
+            const long long pair = first_pair + ch.first + k;
+            pics.src[k] = own ? c->dB + pair * c->plane : (const uint8_t *)d_src[ch.first + k];
+            pics.ref[k] = d_ref ? (const uint8_t *)d_ref[ch.first + k] : own ? c->dA + pair * c->plane : nullptr;
+            pics.dst[k] = d_dst ? (uint8_t *)d_dst[ch.first + k] : nullptr;
+            if (d_dst && word_aligned(d_dst[ch.first + k], dst_stride)) pics.wide |= 1u << k;
         }
-        if ((st = enqueue_warp_chunk(c, first_pair + first, cnt, *wp, pics, ss, rs, dst_stride, d_stats ? d_stats + first : nullptr))) return st;
+        if ((st = enqueue_warp_chunk(c, first_pair + ch.first, ch.count, *wp, pics, ss, rs, dst_stride, d_stats ? d_stats + ch.first : nullptr))) return st;
     }
     return HSFLOW_OK;
 }
@@ -202,13 +171,12 @@ int hsflow_warp(hsflow_ctx *c, int pair, const hsflow_warp_params *wp, const uin
     if (own && (st = resolve_lazy_frames(c, false))) return st;
     const size_t rowb = (size_t)c->W * (size_t)wp->channels, bytes = rowb * c->H;
     hsflow_ctx::WarpScratch &w = c->warp;
-    if (src && (st = warp_stage(c, &w.src, &w.src_bytes, bytes))) return st;
-    if (ref && (st = warp_stage(c, &w.ref, &w.ref_bytes, bytes))) return st;
-    if (dst && (st = warp_stage(c, &w.dst, &w.dst_bytes, bytes))) return st;
-    if (stats && !w.dStats) HS_HIP(c, hipMalloc((void **)&w.dStats, sizeof(hsflow_warp_stats)));
-    if (stats && !w.hStats) HS_HIP(c, hipHostMalloc((void **)&w.hStats, sizeof(hsflow_warp_stats), hipHostMallocDefault));
-    if (!c->evRender) HS_HIP(c, hipEventCreateWithFlags(&c->evRender, hipEventDisableTiming));
-    const bool marked = c->last_marked;
+    if (src && (st = stage_reserve(c, &w.src, &w.src_bytes, bytes))) return st;
+    if (ref && (st = stage_reserve(c, &w.ref, &w.ref_bytes, bytes))) return st;
+    if (dst && (st = stage_reserve(c, &w.dst, &w.dst_bytes, bytes))) return st;
+    if (stats && (st = stats_reserve(c, (void **)&w.dStats, (void **)&w.hStats))) return st;
+    bool marked = false;
+    if ((st = sync_begin(c, &marked))) return st;
     if (src) HS_HIP(c, copy_rows_async(c, w.src, rowb, src, src_stride, rowb, c->H, hipMemcpyHostToDevice));
     if (ref) HS_HIP(c, copy_rows_async(c, w.ref, rowb, ref, ref_stride, rowb, c->H, hipMemcpyHostToDevice));
     hsk::WarpBatchPics pics{};
@@ -218,13 +186,8 @@ int hsflow_warp(hsflow_ctx *c, int pair, const hsflow_warp_params *wp, const uin
     pics.wide = dst ? (uint32_t)word_aligned(w.dst, rowb) : 0u;
     if ((st = enqueue_warp_chunk(c, pair, 1, *wp, pics, own ? (size_t)c->P : rowb, ref ? rowb : (size_t)c->P, rowb, stats ? w.dStats : nullptr))) return st;
     if (dst) HS_HIP(c, copy_rows_async(c, dst, dst_stride, w.dst, rowb, rowb, c->H, hipMemcpyDeviceToHost));
-    if (stats) HS_HIP(c, hipMemcpyAsync(w.hStats, w.dStats, sizeof(hsflow_warp_stats), hipMemcpyDeviceToHost, c->stream));
-    // only what THIS context enqueued is waited for (the slots of a pair pipeline share streams)
-    HS_HIP(c, hipEventRecord(c->evRender, c->stream));
-    HS_HIP(c, hipEventSynchronize(c->evRender));
-    if (stats) *stats = *w.hStats;
-    c->last_marked = marked; // nothing of the warp is in flight any more: the solve's marker speaks for the context again
-    return check_persist(c);
+    if (stats && (st = stats_copy_back(c, w.hStats, w.dStats))) return st;
+    return sync_finish(c, marked, stats, w.hStats);
 }
 
 } // extern "C"

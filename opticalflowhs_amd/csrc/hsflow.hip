@@ -42,7 +42,7 @@
 #include "hs_solve.hip.h"
 
 
-namespace { void jpeg_release(hsflow_ctx *c); void jpegd_release(hsflow_ctx *c); void warp_release(hsflow_ctx *c); void fb_release(hsflow_ctx *c); void median_release(hsflow_ctx *c); } // hs_jpeg.hip.h, hs_jpegd.hip.h, hs_warp.hip.h, hs_fb.hip.h, hs_median.hip.h
+namespace { void jpeg_release(hsflow_ctx *c); void jpegd_release(hsflow_ctx *c); void postops_release(hsflow_ctx *c); } // hs_jpeg.hip.h, hs_jpegd.hip.h, hs_postops.hip.h
 
 extern "C" {
 
@@ -249,9 +249,7 @@ int hsflow_destroy(hsflow_ctx *c)
     hipFree(c->dPrio); hipFree(c->dRgb);
     hipFree(c->dColorScale);
     if (c->hColorScale) hipHostFree(c->hColorScale);
-    warp_release(c);
-    fb_release(c);
-    median_release(c);
+    postops_release(c);
     if (c->evRender) hipEventDestroy(c->evRender);
     jpeg_release(c);
     jpegd_release(c);
@@ -905,6 +903,7 @@ void hsflow_release_cached(void)
 
 } // extern "C"
 
+#include "hs_postops.hip.h" // what the operators on a solved flow share: the synchronous bracket, staging, statistics, batches
 #include "hs_render.hip.h" // hsflow_render_flow[_device], hsflow_default_render_params
 #include "hs_color.hip.h"  // hsflow_color_flow[_host|_device|_batch_device], hsflow_default_color_params
 #include "hs_warp.hip.h"   // hsflow_warp[_host|_device|_batch_device], hsflow_default_warp_params

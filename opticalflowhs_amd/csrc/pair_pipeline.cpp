@@ -310,156 +310,132 @@ int hsflow_pipeline_submit_jpeg(hsflow_pipeline *pl, const uint8_t *prev, size_t
     return st;
 }
 
+// What every entry on a finished pair opens with: wait(ticket) -- a null pipeline is its HSFLOW_E_ARG -- then the slot that
+// still holds that pair into *s.
+static int slot_of_finished(hsflow_pipeline *pl, uint64_t ticket, hsflow_pipeline::Slot **s)
+{
+    const int st = hsflow_pipeline_wait(pl, ticket);
+    if (st) return st;
+    hsflow_pipeline::Slot &slot = pl->slots[ticket % pl->slots.size()];
+    if (slot.busy || !slot.has_done || slot.done_ticket != ticket) return pfail(pl, HSFLOW_E_STATE, "the slot of that ticket has been reused by a later pair");
+    *s = &slot;
+    return HSFLOW_OK;
+}
+
+// What the call `what` on the slot's context returned: HSFLOW_OK, or its error forwarded.
+static int ctx_status(hsflow_pipeline *pl, hsflow_pipeline::Slot *s, int st, const char *what)
+{
+    return st ? ctx_fail(pl, s->ctx, st, what) : HSFLOW_OK;
+}
+
+// What a device form closes with.  The slot is idle, so its event is free: behind what the call enqueued, and only that is
+// waited for, not what other slots have queued on the lane.  (The synchronous forms of the context need none of this: they
+// wait for an event behind their own work themselves.)
+static int wait_on_slot(hsflow_pipeline *pl, hsflow_pipeline::Slot *s, const char *what)
+{
+    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
+        return pfail(pl, HSFLOW_E_DEVICE, std::string("waiting for the slot's ") + what + " failed");
+    return HSFLOW_OK;
+}
+
 int hsflow_pipeline_flow_device(hsflow_pipeline *pl, uint64_t ticket, const float **du, const float **dv, size_t *stride_bytes)
 {
     if (!pl) return HSFLOW_E_ARG;
     if (!du || !dv || !stride_bytes) return pfail(pl, HSFLOW_E_ARG, "null out pointer");
-    int st = hsflow_pipeline_wait(pl, ticket);
-    if (st) return st;
-    hsflow_pipeline::Slot &s = pl->slots[ticket % pl->slots.size()];
-    if (s.busy || !s.has_done || s.done_ticket != ticket) return pfail(pl, HSFLOW_E_STATE, "the slot of that ticket has been reused by a later pair");
-    if ((st = hsflow_flow_view_device(s.ctx, 0, du, dv, stride_bytes))) return ctx_fail(pl, s.ctx, st, "hsflow_flow_view_device");
-    return HSFLOW_OK;
-}
-
-// wait(ticket), then the slot that still holds that pair (nullptr and the error set otherwise)
-static hsflow_pipeline::Slot *slot_of_finished(hsflow_pipeline *pl, uint64_t ticket, int *st)
-{
-    if ((*st = hsflow_pipeline_wait(pl, ticket))) return nullptr;
-    hsflow_pipeline::Slot &s = pl->slots[ticket % pl->slots.size()];
-    if (s.busy || !s.has_done || s.done_ticket != ticket) {
-        *st = pfail(pl, HSFLOW_E_STATE, "the slot of that ticket has been reused by a later pair");
-        return nullptr;
-    }
-    return &s;
+    hsflow_pipeline::Slot *s = nullptr;
+    const int st = slot_of_finished(pl, ticket, &s);
+    return st ? st : ctx_status(pl, s, hsflow_flow_view_device(s->ctx, 0, du, dv, stride_bytes), "hsflow_flow_view_device");
 }
 
 int hsflow_pipeline_render(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, uint8_t *rgb, size_t stride)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
-    // (hsflow_render_flow waits for an event behind its own copy, not for what other slots have queued on the lane)
-    if ((st = hsflow_render_flow(s->ctx, 0, rp, rgb, stride))) return ctx_fail(pl, s->ctx, st, "hsflow_render_flow");
-    return HSFLOW_OK;
+    hsflow_pipeline::Slot *s = nullptr;
+    const int st = slot_of_finished(pl, ticket, &s);
+    return st ? st : ctx_status(pl, s, hsflow_render_flow(s->ctx, 0, rp, rgb, stride), "hsflow_render_flow");
 }
 
 int hsflow_pipeline_render_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, int quality, uint8_t *jpeg, size_t capacity,
                                 size_t *bytes)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
-    // (like hsflow_render_flow it waits for an event behind its own work only)
-    if ((st = hsflow_render_flow_jpeg(s->ctx, 0, rp, quality, jpeg, capacity, bytes))) return ctx_fail(pl, s->ctx, st, "hsflow_render_flow_jpeg");
-    return HSFLOW_OK;
+    hsflow_pipeline::Slot *s = nullptr;
+    const int st = slot_of_finished(pl, ticket, &s);
+    return st ? st : ctx_status(pl, s, hsflow_render_flow_jpeg(s->ctx, 0, rp, quality, jpeg, capacity, bytes), "hsflow_render_flow_jpeg");
 }
 
 int hsflow_pipeline_render_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, void *d_rgb, size_t stride)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
+    hsflow_pipeline::Slot *s = nullptr;
+    int st = slot_of_finished(pl, ticket, &s);
+    if (st) return st;
     if ((st = hsflow_render_flow_device(s->ctx, 0, rp, d_rgb, stride))) return ctx_fail(pl, s->ctx, st, "hsflow_render_flow_device");
-    // the slot is idle, so its event is free: behind the two launches, and only they are waited for
-    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
-        return pfail(pl, HSFLOW_E_DEVICE, "waiting for the slot's render failed");
-    return HSFLOW_OK;
+    return wait_on_slot(pl, s, "render");
 }
 
 int hsflow_pipeline_color(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, uint8_t *rgb, size_t stride, float *scale_used)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
-    // (like hsflow_render_flow it waits for an event behind its own copy only)
-    if ((st = hsflow_color_flow(s->ctx, 0, cp, rgb, stride, scale_used))) return ctx_fail(pl, s->ctx, st, "hsflow_color_flow");
-    return HSFLOW_OK;
+    hsflow_pipeline::Slot *s = nullptr;
+    const int st = slot_of_finished(pl, ticket, &s);
+    return st ? st : ctx_status(pl, s, hsflow_color_flow(s->ctx, 0, cp, rgb, stride, scale_used), "hsflow_color_flow");
 }
 
 int hsflow_pipeline_color_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, int quality, uint8_t *jpeg, size_t capacity,
                                size_t *bytes)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
-    if ((st = hsflow_color_flow_jpeg(s->ctx, 0, cp, quality, jpeg, capacity, bytes))) return ctx_fail(pl, s->ctx, st, "hsflow_color_flow_jpeg");
-    return HSFLOW_OK;
+    hsflow_pipeline::Slot *s = nullptr;
+    const int st = slot_of_finished(pl, ticket, &s);
+    return st ? st : ctx_status(pl, s, hsflow_color_flow_jpeg(s->ctx, 0, cp, quality, jpeg, capacity, bytes), "hsflow_color_flow_jpeg");
 }
 
 int hsflow_pipeline_color_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_color_params *cp, void *d_rgb, size_t stride)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
+    hsflow_pipeline::Slot *s = nullptr;
+    int st = slot_of_finished(pl, ticket, &s);
+    if (st) return st;
     if ((st = hsflow_color_flow_device(s->ctx, 0, cp, d_rgb, stride))) return ctx_fail(pl, s->ctx, st, "hsflow_color_flow_device");
-    // the slot is idle, so its event is free: behind the launches, and only they are waited for
-    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
-        return pfail(pl, HSFLOW_E_DEVICE, "waiting for the slot's colour picture failed");
-    return HSFLOW_OK;
+    return wait_on_slot(pl, s, "colour picture");
 }
 
 int hsflow_pipeline_warp(hsflow_pipeline *pl, uint64_t ticket, const hsflow_warp_params *wp, const uint8_t *src, size_t src_stride, const uint8_t *ref,
                          size_t ref_stride, uint8_t *dst, size_t dst_stride, hsflow_warp_stats *stats)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
-    // (like hsflow_color_flow it waits for an event behind its own copies only)
-    if ((st = hsflow_warp(s->ctx, 0, wp, src, src_stride, ref, ref_stride, dst, dst_stride, stats))) return ctx_fail(pl, s->ctx, st, "hsflow_warp");
-    return HSFLOW_OK;
+    hsflow_pipeline::Slot *s = nullptr;
+    const int st = slot_of_finished(pl, ticket, &s);
+    return st ? st : ctx_status(pl, s, hsflow_warp(s->ctx, 0, wp, src, src_stride, ref, ref_stride, dst, dst_stride, stats), "hsflow_warp");
 }
 
 int hsflow_pipeline_warp_device(hsflow_pipeline *pl, uint64_t ticket, const hsflow_warp_params *wp, const void *d_src, size_t src_stride, const void *d_ref,
                                 size_t ref_stride, void *d_dst, size_t dst_stride, hsflow_warp_stats *d_stats)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
+    hsflow_pipeline::Slot *s = nullptr;
+    int st = slot_of_finished(pl, ticket, &s);
+    if (st) return st;
     if ((st = hsflow_warp_device(s->ctx, 0, wp, d_src, src_stride, d_ref, ref_stride, d_dst, dst_stride, d_stats)))
         return ctx_fail(pl, s->ctx, st, "hsflow_warp_device");
-    // the slot is idle, so its event is free: behind the launch, and only it is waited for
-    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
-        return pfail(pl, HSFLOW_E_DEVICE, "waiting for the slot's warp failed");
-    return HSFLOW_OK;
+    return wait_on_slot(pl, s, "warp");
 }
 
 // Both slots of a forward-backward check and the backward slot's flow where it lies (final: the view waits for it).
 static int fb_slots(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket_bwd, hsflow_pipeline::Slot **f, const float **ub, const float **vb, size_t *bs)
 {
-    int st = HSFLOW_OK;
     hsflow_pipeline::Slot *b = nullptr;
-    if (!(*f = slot_of_finished(pl, ticket_fwd, &st)) || !(b = slot_of_finished(pl, ticket_bwd, &st))) return st;
-    if ((st = hsflow_flow_view_device(b->ctx, 0, ub, vb, bs))) return ctx_fail(pl, b->ctx, st, "hsflow_flow_view_device");
-    return HSFLOW_OK;
+    int st = slot_of_finished(pl, ticket_fwd, f);
+    if (st || (st = slot_of_finished(pl, ticket_bwd, &b))) return st;
+    return ctx_status(pl, b, hsflow_flow_view_device(b->ctx, 0, ub, vb, bs), "hsflow_flow_view_device");
 }
 
 int hsflow_pipeline_fb(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket_bwd, const hsflow_fb_params *fp, uint8_t *mask, size_t mask_stride,
                        float *err2, size_t err2_stride, hsflow_fb_stats *stats)
 {
-    if (!pl) return HSFLOW_E_ARG;
     hsflow_pipeline::Slot *s = nullptr;
     const float *ub = nullptr, *vb = nullptr;
     size_t bs = 0;
-    int st = fb_slots(pl, ticket_fwd, ticket_bwd, &s, &ub, &vb, &bs);
-    if (st) return st;
-    // (like hsflow_warp it waits for an event behind its own copies only)
-    if ((st = hsflow_fb_planes(s->ctx, 0, ub, vb, bs, fp, mask, mask_stride, err2, err2_stride, stats))) return ctx_fail(pl, s->ctx, st, "hsflow_fb_planes");
-    return HSFLOW_OK;
+    const int st = fb_slots(pl, ticket_fwd, ticket_bwd, &s, &ub, &vb, &bs);
+    return st ? st : ctx_status(pl, s, hsflow_fb_planes(s->ctx, 0, ub, vb, bs, fp, mask, mask_stride, err2, err2_stride, stats), "hsflow_fb_planes");
 }
 
 int hsflow_pipeline_fb_device(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket_bwd, const hsflow_fb_params *fp, void *d_mask,
                               size_t mask_stride, void *d_err2, size_t err2_stride, hsflow_fb_stats *d_stats)
 {
-    if (!pl) return HSFLOW_E_ARG;
     hsflow_pipeline::Slot *s = nullptr;
     const float *ub = nullptr, *vb = nullptr;
     size_t bs = 0;
@@ -467,59 +443,43 @@ int hsflow_pipeline_fb_device(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t
     if (st) return st;
     if ((st = hsflow_fb_planes_device(s->ctx, 0, ub, vb, bs, fp, d_mask, mask_stride, d_err2, err2_stride, d_stats)))
         return ctx_fail(pl, s->ctx, st, "hsflow_fb_planes_device");
-    // the forward slot is idle, so its event is free: behind the launch, and only it is waited for
-    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
-        return pfail(pl, HSFLOW_E_DEVICE, "waiting for the slot's check failed");
-    return HSFLOW_OK;
+    return wait_on_slot(pl, s, "check"); // (the forward slot's event)
 }
 
 int hsflow_pipeline_median(hsflow_pipeline *pl, uint64_t ticket, const hsflow_median_params *mp, int passes, const uint8_t *state, size_t state_stride,
                            float *u, float *v, size_t out_stride, uint8_t *state_out, size_t state_out_stride, hsflow_median_stats *stats)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
-    // (like hsflow_fb it waits for an event behind its own copies only)
-    if ((st = hsflow_median(s->ctx, 0, mp, passes, state, state_stride, u, v, out_stride, state_out, state_out_stride, stats))) return ctx_fail(pl, s->ctx, st, "hsflow_median");
-    return HSFLOW_OK;
+    hsflow_pipeline::Slot *s = nullptr;
+    const int st = slot_of_finished(pl, ticket, &s);
+    return st ? st : ctx_status(pl, s, hsflow_median(s->ctx, 0, mp, passes, state, state_stride, u, v, out_stride, state_out, state_out_stride, stats), "hsflow_median");
 }
 
 int hsflow_pipeline_median_apply(hsflow_pipeline *pl, uint64_t ticket, const hsflow_median_params *mp, int passes, const void *d_state,
                                  size_t state_stride, void *d_state_out, size_t state_out_stride, hsflow_median_stats *d_stats)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
+    hsflow_pipeline::Slot *s = nullptr;
+    int st = slot_of_finished(pl, ticket, &s);
+    if (st) return st;
     if ((st = hsflow_median_apply(s->ctx, 0, mp, passes, d_state, state_stride, d_state_out, state_out_stride, d_stats)))
         return ctx_fail(pl, s->ctx, st, "hsflow_median_apply");
-    // the slot is idle, so its event is free: behind the launches, and only they are waited for
-    if (hipSetDevice(pl->device) != hipSuccess || hipEventRecord(s->ev, s->stream) != hipSuccess || hipEventSynchronize(s->ev) != hipSuccess)
-        return pfail(pl, HSFLOW_E_DEVICE, "waiting for the slot's median failed");
-    return HSFLOW_OK;
+    return wait_on_slot(pl, s, "median");
 }
 
 int hsflow_pipeline_verify(hsflow_pipeline *pl, uint64_t ticket, hsflow_verify_report *report)
 {
     if (!pl) return HSFLOW_E_ARG;
     if (!report || report->struct_size != sizeof(hsflow_verify_report)) return pfail(pl, HSFLOW_E_ARG, "report null or struct_size mismatch");
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
+    hsflow_pipeline::Slot *s = nullptr;
+    const int st = slot_of_finished(pl, ticket, &s);
     // the slot's context remembers what it ran -- the pipeline's own launch shape included (stream_shape)
-    if ((st = hsflow_verify(s->ctx, 0, report))) return ctx_fail(pl, s->ctx, st, "hsflow_verify");
-    return HSFLOW_OK;
+    return st ? st : ctx_status(pl, s, hsflow_verify(s->ctx, 0, report), "hsflow_verify");
 }
 
 int hsflow_pipeline_frames_u8(hsflow_pipeline *pl, uint64_t ticket, uint8_t *prev, size_t ps, uint8_t *curr, size_t cs)
 {
-    if (!pl) return HSFLOW_E_ARG;
-    int st = HSFLOW_OK;
-    hsflow_pipeline::Slot *s = slot_of_finished(pl, ticket, &st);
-    if (!s) return st;
-    if ((st = hsflow_get_frames_u8(s->ctx, 0, prev, ps, curr, cs))) return ctx_fail(pl, s->ctx, st, "hsflow_get_frames_u8");
-    return HSFLOW_OK;
+    hsflow_pipeline::Slot *s = nullptr;
+    const int st = slot_of_finished(pl, ticket, &s);
+    return st ? st : ctx_status(pl, s, hsflow_get_frames_u8(s->ctx, 0, prev, ps, curr, cs), "hsflow_get_frames_u8");
 }
 
 int hsflow_pipeline_wait(hsflow_pipeline *pl, uint64_t ticket)

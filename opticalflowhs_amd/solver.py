@@ -148,6 +148,40 @@ def _warp_args(height, width, src, ref, out, device, params, t, border, fill):
     return tuple((p, s) for p, s, _ in pics) + (params,)
 
 
+def _stats_record(cls, want, device, device_index):
+    """(record, pointer) of one statistics record of `cls` (64 bytes) where `want`, else (None, None): on the device a CUDA
+    uint8 tensor, else the ctypes record."""
+    if not want:
+        return None, None
+    if device:
+        import torch
+        rec = torch.empty(ctypes.sizeof(cls), dtype=torch.uint8, device="cuda:%d" % device_index)  # (the library clears it)
+        return rec, _ptr(rec)
+    rec = cls()
+    return rec, ctypes.byref(rec)
+
+
+def _check_stats_tensor(stats, n, cls):
+    """The pointer of a device batch's statistics: None, or of a contiguous CUDA uint8 tensor that holds n records of `cls`."""
+    if stats is None:
+        return None
+    if not _is_device_tensor(stats) or str(stats.dtype) != "torch.uint8" or not stats.is_contiguous() or stats.numel() < n * ctypes.sizeof(cls):
+        raise ValueError("stats must be a contiguous CUDA uint8 tensor of at least n * 64 bytes")
+    return _ptr(stats)
+
+
+def _plane_lists(items, n, what, unit, read):
+    """One list of a device batch as (pointer array, the one row stride, what `read` gave): items None (absent: (None, 0,
+    [])), a tensor (n, ...) or a list of n tensors; read(x): (pointer, row stride, ...) of one of them; `what` and `unit`
+    word the error."""
+    if items is None:
+        return None, 0, []
+    got = [read(items[i]) for i in range(len(items))]
+    if len(got) != n or len(set(g[1] for g in got)) > 1:
+        raise ValueError("%s must hold one %s, all of one row stride" % (what, unit))
+    return (ctypes.c_void_p * max(n, 1))(*[g[0].value for g in got]), got[0][1] if got else 0, got
+
+
 def _warp_call(height, width, device_index, src, ref, out, params, t, border, fill, return_stats, picture):
     """What `HSFlow.warp` and `PairPipeline.warp` share: decides between the host and the device form, allocates `out`
     where a picture is wanted and none was given, and the statistics record.  Returns (device, the C call's arguments
@@ -163,14 +197,7 @@ def _warp_call(height, width, device_index, src, ref, out, params, t, border, fi
         else:
             out = np.empty(shape, np.uint8)
     (sp, ss), (rp, rs), (op, os_), wp = _warp_args(height, width, src, ref, out, device, params, t, border, fill)
-    stats, sref = None, None
-    if return_stats and device:
-        import torch
-        stats = torch.empty(ctypes.sizeof(HsflowWarpStats), dtype=torch.uint8, device="cuda:%d" % device_index)  # (the library clears it)
-        sref = _ptr(stats)
-    elif return_stats:
-        stats = HsflowWarpStats()
-        sref = ctypes.byref(stats)
+    stats, sref = _stats_record(HsflowWarpStats, return_stats, device, device_index)
     return device, (ctypes.byref(wp), sp, ss, rp, rs, op, os_, sref), out, stats
 
 
@@ -189,8 +216,8 @@ def make_fb_params(alpha=0.01, beta=0.5, values=(255, 0, 0, 0)):
     return fp
 
 
-def _fb_plane(x, height, width, dtype, what, device):
-    """(pointer, row stride in bytes) of an output plane of the check: (H, W) of `dtype`, elements packed, any row stride."""
+def _plane(x, height, width, dtype, what, device):
+    """(pointer, row stride in bytes) of a plane of the check or the median: (H, W) of `dtype`, elements packed, any row stride."""
     if device != _is_device_tensor(x) or (not device and not isinstance(x, np.ndarray)):
         raise ValueError("%s must be %s" % (what, "a CUDA tensor" if device else "a NumPy array"))
     if str(x.dtype) not in (dtype, "torch." + dtype) or tuple(x.shape) != (height, width):
@@ -218,17 +245,10 @@ def _fb_call(height, width, device_index, mask, err2, stats, params, alpha, beta
             x = np.empty((height, width), dtype)
         planes.append(x)
     mask, err2 = planes
-    mp, ms = _fb_plane(mask, height, width, "uint8", "mask", device) if mask is not None else (None, 0)
-    ep, es = _fb_plane(err2, height, width, "float32", "err2", device) if err2 is not None else (None, 0)
+    mp, ms = _plane(mask, height, width, "uint8", "mask", device) if mask is not None else (None, 0)
+    ep, es = _plane(err2, height, width, "float32", "err2", device) if err2 is not None else (None, 0)
     fp = params if params is not None else make_fb_params(alpha, beta, values)
-    rec, sref = None, None
-    if stats and device:
-        import torch
-        rec = torch.empty(ctypes.sizeof(HsflowFbStats), dtype=torch.uint8, device="cuda:%d" % device_index)  # (the library clears it)
-        sref = _ptr(rec)
-    elif stats:
-        rec = HsflowFbStats()
-        sref = ctypes.byref(rec)
+    rec, sref = _stats_record(HsflowFbStats, stats, device, device_index)
     return device, (ctypes.byref(fp), mp, ms, ep, es, sref), mask, err2, rec
 
 
@@ -256,7 +276,7 @@ def _median_call(height, width, device_index, state, flow, state_out, stats, par
             import torch
             return torch.empty((height, width), dtype=getattr(torch, dtype), device="cuda:%d" % device_index)
         return np.empty((height, width), dtype)
-    sp, ss = _fb_plane(state, height, width, "uint8", "state", device) if state is not None else (None, 0)
+    sp, ss = _plane(state, height, width, "uint8", "state", device) if state is not None else (None, 0)
     u_out = v_out = None
     up = vp = None
     os_ = 0
@@ -265,23 +285,16 @@ def _median_call(height, width, device_index, state, flow, state_out, stats, par
     elif flow is not None and flow is not False:
         u_out, v_out = flow
     if u_out is not None:
-        (up, os_), (vp, vs) = _fb_plane(u_out, height, width, "float32", "u_out", device), _fb_plane(v_out, height, width, "float32", "v_out", device)
+        (up, os_), (vp, vs) = _plane(u_out, height, width, "float32", "u_out", device), _plane(v_out, height, width, "float32", "v_out", device)
         if vs != os_:
             raise ValueError("u_out and v_out must have one row stride")
     if state_out is True:
         state_out = fresh("uint8")
     elif state_out is False:
         state_out = None
-    sop, sos = _fb_plane(state_out, height, width, "uint8", "state_out", device) if state_out is not None else (None, 0)
+    sop, sos = _plane(state_out, height, width, "uint8", "state_out", device) if state_out is not None else (None, 0)
     mp = params if params is not None else make_median_params(radius, mode, min_votes)
-    rec, sref = None, None
-    if stats and device:
-        import torch
-        rec = torch.empty(ctypes.sizeof(HsflowMedianStats), dtype=torch.uint8, device="cuda:%d" % device_index)  # (the library clears it)
-        sref = _ptr(rec)
-    elif stats:
-        rec = HsflowMedianStats()
-        sref = ctypes.byref(rec)
+    rec, sref = _stats_record(HsflowMedianStats, stats, device, device_index)
     return mp, (sp, ss), (up, vp, os_), (sop, sos), sref, u_out, v_out, state_out, rec
 
 
@@ -613,26 +626,15 @@ class HSFlow(object):
         bytes that receives record i of pair first_pair + i (`warp_stats_from`).  Only enqueued on the context's stream
         (complete after `synchronize()`); returns `out`."""
         first_pair, n = self._batch_range(first_pair, n)
-        lists, strides, channels = [], [], set()
-        for x, what in ((src, "src"), (ref, "ref"), (out, "out")):
-            if x is None:
-                lists.append(None)
-                strides.append(0)
-                continue
-            items = [_warp_image(x[i], self.height, self.width, what, True) for i in range(len(x))]
-            if len(items) != n or len(set(st for _, st, _ in items)) > 1:
-                raise ValueError("%s must hold one picture per pair, all of one row stride" % what)
-            channels.update(c for _, _, c in items)
-            lists.append((ctypes.c_void_p * max(n, 1))(*[p.value for p, _, _ in items]))
-            strides.append(items[0][1] if items else 0)
+        (sl, ss, s_), (rl, rs, r_), (ol, os_, o_) = [
+            _plane_lists(x, n, what, "picture per pair", lambda img, what=what: _warp_image(img, self.height, self.width, what, True))
+            for x, what in ((src, "src"), (ref, "ref"), (out, "out"))]
+        channels = set(c for _, _, c in s_ + r_ + o_)
         if len(channels) > 1:
             raise ValueError("src, ref and out must have the same number of channels")
         wp = params if params is not None else make_warp_params(channels.pop() if channels else 1, t, border, fill)
-        if stats is not None and (not _is_device_tensor(stats) or str(stats.dtype) != "torch.uint8" or not stats.is_contiguous()
-                                  or stats.numel() < n * ctypes.sizeof(HsflowWarpStats)):
-            raise ValueError("stats must be a contiguous CUDA uint8 tensor of at least n * 64 bytes")
-        self._check(self._lib.hsflow_warp_batch_device(self._h, first_pair, n, ctypes.byref(wp), lists[0], strides[0], lists[1], strides[1],
-                                                       lists[2], strides[2], _ptr(stats) if stats is not None else None))
+        sref = _check_stats_tensor(stats, n, HsflowWarpStats)
+        self._check(self._lib.hsflow_warp_batch_device(self._h, first_pair, n, ctypes.byref(wp), sl, ss, rl, rs, ol, os_, sref))
         return out
 
     def set_frames_reversed(self, dst_pair, src_pair):
@@ -672,24 +674,14 @@ class HSFlow(object):
         n = len(fwd_pairs)
         if len(bwd_pairs) != n:
             raise ValueError("fwd_pairs and bwd_pairs must have one length")
-        lists, strides = [], []
-        for x, dtype, what in ((mask, "uint8", "mask"), (err2, "float32", "err2")):
-            if x is None:
-                lists.append(None)
-                strides.append(0)
-                continue
-            items = [_fb_plane(x[i], self.height, self.width, dtype, what, True) for i in range(len(x))]
-            if len(items) != n or len(set(st for _, st in items)) > 1:
-                raise ValueError("%s must hold one plane per check, all of one row stride" % what)
-            lists.append((ctypes.c_void_p * max(n, 1))(*[p.value for p, _ in items]))
-            strides.append(items[0][1] if items else 0)
+        (ml, ms, _), (el, es, _) = [
+            _plane_lists(x, n, what, "plane per check", lambda p, dtype=dtype, what=what: _plane(p, self.height, self.width, dtype, what, True))
+            for x, dtype, what in ((mask, "uint8", "mask"), (err2, "float32", "err2"))]
         fp = params if params is not None else make_fb_params(alpha, beta, values)
-        if stats is not None and (not _is_device_tensor(stats) or str(stats.dtype) != "torch.uint8" or not stats.is_contiguous()
-                                  or stats.numel() < n * ctypes.sizeof(HsflowFbStats)):
-            raise ValueError("stats must be a contiguous CUDA uint8 tensor of at least n * 64 bytes")
+        sref = _check_stats_tensor(stats, n, HsflowFbStats)
         ints = ctypes.c_int * max(n, 1)
         self._check(self._lib.hsflow_fb_batch_device(self._h, n, ints(*[int(p) for p in fwd_pairs]), ints(*[int(p) for p in bwd_pairs]), ctypes.byref(fp),
-                                                     lists[0], strides[0], lists[1], strides[1], _ptr(stats) if stats is not None else None))
+                                                     ml, ms, el, es, sref))
         return mask, err2, stats
 
     def median(self, pair=0, state=None, flow=True, state_out=False, stats=False, radius=1, mode="filter", min_votes=1, passes=1, params=None, device=False):
@@ -741,25 +733,14 @@ class HSFlow(object):
         (n, H, W) or a list of n tensors (H, W), uint8 / float32; one row stride per list, u_out and v_out one between them.
         stats: None, or a CUDA uint8 tensor of n * 64 bytes that receives record i of field i (`median_stats_from`).
         Only enqueued on the context's stream (complete after `synchronize()`)."""
-        lists, strides = [], []
-        for x, dtype, what in ((state, "uint8", "state"), (u_out, "float32", "u_out"), (v_out, "float32", "v_out"), (state_out, "uint8", "state_out")):
-            if x is None:
-                lists.append(None)
-                strides.append(0)
-                continue
-            items = [_fb_plane(x[i], self.height, self.width, dtype, what, True) for i in range(len(x))]
-            if len(items) != n or len(set(st for _, st in items)) > 1:
-                raise ValueError("%s must hold one plane per field, all of one row stride" % what)
-            lists.append((ctypes.c_void_p * max(n, 1))(*[p.value for p, _ in items]))
-            strides.append(items[0][1] if items else 0)
-        if u_out is not None and v_out is not None and strides[1] != strides[2]:
+        (sl, ss, _), (ul, us, _), (vl, vs, _), (ol, os_, _) = [
+            _plane_lists(x, n, what, "plane per field", lambda p, dtype=dtype, what=what: _plane(p, self.height, self.width, dtype, what, True))
+            for x, dtype, what in ((state, "uint8", "state"), (u_out, "float32", "u_out"), (v_out, "float32", "v_out"), (state_out, "uint8", "state_out"))]
+        if u_out is not None and v_out is not None and us != vs:
             raise ValueError("u_out and v_out must have one row stride")
         mp = params if params is not None else make_median_params(radius, mode, min_votes)
-        if stats is not None and (not _is_device_tensor(stats) or str(stats.dtype) != "torch.uint8" or not stats.is_contiguous()
-                                  or stats.numel() < n * ctypes.sizeof(HsflowMedianStats)):
-            raise ValueError("stats must be a contiguous CUDA uint8 tensor of at least n * 64 bytes")
-        self._check(self._lib.hsflow_median_batch_device(self._h, int(first_pair), int(n), ctypes.byref(mp), lists[0], strides[0], lists[1], lists[2],
-                                                         strides[1] or strides[2], lists[3], strides[3], _ptr(stats) if stats is not None else None))
+        sref = _check_stats_tensor(stats, n, HsflowMedianStats)
+        self._check(self._lib.hsflow_median_batch_device(self._h, int(first_pair), int(n), ctypes.byref(mp), sl, ss, ul, vl, us or vs, ol, os_, sref))
         return u_out, v_out, state_out, stats
 
     def encode_jpeg(self, rgb, quality=95):
