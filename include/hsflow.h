@@ -52,6 +52,10 @@
  *   hsflow_median[_host|_device|_batch_device|_planes_device|_apply]
  *                                          no counterpart in the reference: the median filter of the flow and the filling
  *                                          of untrusted pixels from their trusted neighbours, where the flow lies
+ *   hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device
+ *                                          no counterpart in the reference: the frame at time t between the two frames of
+ *                                          a pair (frame-rate conversion) -- the forward flow projected to t, holes
+ *                                          filled, both frames fetched and blended with occlusion -- where the flow lies
  *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
  *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
  *                                          the pictures are decoded on the device
@@ -87,7 +91,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 19 /* 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 20 /* 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -1120,6 +1124,141 @@ int hsflow_median(hsflow_ctx *ctx, int pair, const hsflow_median_params *mp, int
                   size_t state_stride, float *u /* or NULL */, float *v /* or NULL */, size_t out_stride, uint8_t *state_out /* or NULL */,
                   size_t state_out_stride, hsflow_median_stats *stats /* or NULL */);
 
+/* --- the frame at time t between the two frames of a pair (ABI 0.20) --------------------------- */
+
+/* Frame-rate conversion, the consumer that hsflow_warp* name: the picture at time t, 0 <= t <= 1, between the two frames
+ * of a pair (A, B) = (prev, curr), by the interpolation algorithm of Baker et al. ("A Database and Evaluation Methodology
+ * for Optical Flow", IJCV 2011, section 3.3.2), the paper the colour wheel follows.  hsflow_warp with a fractional t reads
+ * the vector at the pixel the picture is drawn at, not the vector that ARRIVES there, takes one frame only and knows
+ * nothing of occlusion; this operator projects the forward flow to time t, fills the holes, fetches both frames along
+ * the projected vector and blends them, or takes one frame alone where the other does not see the point.  Nothing of it
+ * is in the reference.  The rule is csrc/hs_interp_rule.h, one header for the kernels and the host form.  All arithmetic
+ * is fp32, every operation rounded on its own (fl); the integer parts are exact; device and host give the same bits.
+ * Inputs: the forward flow (u, v), W x H fp32; the pictures prev and curr of C in {1, 3} interleaved u8 channels;
+ * optional u8 planes vis_prev (on A's grid) and vis_curr (on B's grid), non-zero = "this pixel is visible in the other
+ * frame" -- the default masks of hsflow_fb of (fwd, bwd) and of (bwd, fwd) can be passed as they are; t; the fill's
+ * radius, min_votes and passes.
+ *   P, projection.  The source pixel p = (x, y), a = u[p], b = v[p]:
+ *   1. !known(a, b) (the colour picture's test): p contributes nothing and is counted `unknown`;
+ *   2. the cost of p: the warp's taps of (a, b) at t = 1 with HSFLOW_WARP_BORDER_CONSTANT; not inside: 1023; else the sum
+ *      over the channels of |prev_c[p] - the warp's bilinear byte of curr_c| (0 .. 765): the photo-consistency of (a, b);
+ *   3. hx = fl(fl((float)x + fl(a * t)) + 0.5f), hy alike.  If !(hx >= 0 && hx < (float)W && hy >= 0 && hy < (float)H), on
+ *      the floats, p is counted `left`; else its cell is q = ((int)floorf(hx), (int)floorf(hy));
+ *   4. key = (uint64)cost << 32 | (uint32)(y * W + x); a cell keeps the MINIMUM key of all sources that land on it -- the
+ *      lowest cost, at equal cost the lower source index -- whatever the order of arrival;
+ *   5. a cell with a key receives the bits of (u, v) of that key's source and state 1; an empty cell is a hole: +0.0,
+ *      +0.0, state 0.  `holes` counts the empty cells, `collisions` is (sources that landed) - (cells hit).
+ *   F, fill.  fill_passes passes (0 .. HSFLOW_MEDIAN_MAX_PASSES) of HSFLOW_MEDIAN_FILL with fill_radius and fill_min_votes
+ *      over (ut, vt, state): a hole at Chebyshev distance d from the nearest hit cell is filled in pass ceil(d / radius)
+ *      (min_votes 1) and gets state 2.  `unfilled` counts the state-0 cells afterwards; their vector is still +0.0, so
+ *      such a pixel is a plain cross-fade.
+ *   B, blend.  The output pixel (x, y) with the filled vector (a, b), wA = fl(1.0f - t), wB = t:
+ *   1. tA = the warp's taps of (a, b) at the fraction -t, tB = at the fraction wA, both with HSFLOW_WARP_BORDER_REPLICATE;
+ *      inA / inB: the warp's class is inside;
+ *   2. per channel fa = the bilinear value of prev at tA in the warp's order but UNROUNDED -- top = fl(p00 + fl(ax * fl(p10
+ *      - p00))), bot alike, fa = fl(top + fl(ay * fl(bot - top))) -- and fb alike from curr at tB: one rounding per
+ *      output byte (with the taps rounded to bytes first, the rounding noise alone makes low-contrast frames worse than
+ *      a cross-fade);
+ *   3. the nearest tap of a side is (ax >= 0.5f ? x1 : x0, ay >= 0.5f ? y1 : y0);
+ *   4. class.  inA && inB: occA iff vis_prev is given and its byte at tA's nearest tap is 0, occB alike with vis_curr at
+ *      tB; occA && !occB: HSFLOW_INTERP_PREV_ONLY; occB && !occA: HSFLOW_INTERP_CURR_ONLY; else HSFLOW_INTERP_BLENDED.
+ *      Only inA: PREV_ONLY.  Only inB: CURR_ONLY.  Neither: HSFLOW_INTERP_CLAMPED, the blend of the two clamped samples;
+ *   5. BLENDED / CLAMPED: m = fl(fl(wA * fa) + fl(wB * fb)); PREV_ONLY: m = fa; CURR_ONLY: m = fb;
+ *      byte = min((int)fl(m + 0.5f), 255).
+ * Without vis planes t = 0 gives prev and t = 1 gives curr byte for byte, whatever the flow; a constant whole-number flow
+ * (dx, dy) with t dx and t dy whole gives in the interior the exact mix of the two shifted pictures.  There is no fill
+ * colour and no border option: every pixel gets a plausible value.  Against the same formula of step B in float64 every
+ * byte is within one level (tests/test_interp_host.py).
+ * hsflow_interp_stats: blended + prev_only + curr_only + clamped = W*H; sad is the sum of |byte - ref| over all pixels
+ * and channels against an optional reference picture (the interpolation error of the Middlebury benchmark), max_diff the
+ * largest single difference, both 0 without one; hit cells + holes = W*H; landed + left + unknown = W*H.  The entries
+ * that stop after F leave the first five and max_diff 0. */
+#define HSFLOW_INTERP_BLENDED 0
+#define HSFLOW_INTERP_PREV_ONLY 1
+#define HSFLOW_INTERP_CURR_ONLY 2
+#define HSFLOW_INTERP_CLAMPED 3
+#define HSFLOW_INTERP_BATCH_MAX 8 /* times per set of launches; HSFLOW_INTERP_BATCH_MAX=<1..8> in the environment: fewer */
+typedef struct hsflow_interp_params {
+    uint32_t struct_size;   /* = sizeof(hsflow_interp_params)                 */
+    int32_t channels;       /* 1 or 3, interleaved                            */
+    int32_t fill_radius;    /* 1 or 2                                         */
+    int32_t fill_min_votes; /* 1 .. (2 fill_radius + 1)^2                     */
+    int32_t fill_passes;    /* 0 .. HSFLOW_MEDIAN_MAX_PASSES                  */
+} hsflow_interp_params;
+typedef struct hsflow_interp_stats { /* 64 bytes, the same on the device and on the host */
+    uint64_t blended, prev_only, curr_only, clamped;
+    uint64_t sad;
+    uint32_t holes, unfilled, collisions, left, unknown, max_diff;
+} hsflow_interp_stats;
+/* channels 1, fill_radius 1, fill_min_votes 1, fill_passes 4.  NULL is ignored. */
+void hsflow_default_interp_params(hsflow_interp_params *ip);
+/* Steps P and F on the host, no device needed: the flow at time t as two fp32 planes (together or not at all, rows
+ * out_stride bytes apart), the state plane (0 unfilled, 1 hit, 2 filled) and the record, at least one of them.  With
+ * t = 1 this is the flow on B's grid -- what a camera loop hands to the next pair (hsflow_set_flow_device and
+ * use_previous).  Writes 4*width bytes of every output flow row, width bytes of every state row and nothing else.
+ * HSFLOW_E_ARG: a null input, params, t outside [0, 1] or not finite, nothing asked for; HSFLOW_E_SIZE: a stride. */
+int hsflow_project_flow_host(const float *u, size_t u_stride, const float *v, size_t v_stride, int width, int height, float t,
+                             const hsflow_interp_params *ip, const uint8_t *prev, size_t prev_stride, const uint8_t *curr, size_t curr_stride,
+                             float *u_out /* may be null */, float *v_out /* may be null */, size_t out_stride, uint8_t *state_out /* may be null */,
+                             size_t state_out_stride, hsflow_interp_stats *stats /* may be null */);
+/* The whole rule on the host, no device needed.  vis_prev, vis_curr, ref, dst, cls and stats may each be null, but one of
+ * dst, cls (the class plane, one byte HSFLOW_INTERP_* per pixel) and stats must be asked for.  Writes channels*width
+ * bytes of every row of dst, width bytes of every row of cls and nothing else.  HSFLOW_E_ARG / HSFLOW_E_SIZE as
+ * hsflow_interp_batch_device. */
+int hsflow_interp_host(const float *u, size_t u_stride, const float *v, size_t v_stride, int width, int height, float t,
+                       const hsflow_interp_params *ip, const uint8_t *prev, size_t prev_stride, const uint8_t *curr, size_t curr_stride,
+                       const uint8_t *vis_prev, size_t vis_prev_stride, const uint8_t *vis_curr, size_t vis_curr_stride, const uint8_t *ref,
+                       size_t ref_stride, uint8_t *dst, size_t dst_stride, uint8_t *cls, size_t cls_stride, hsflow_interp_stats *stats);
+/* n intermediate frames of ONE pair (slow motion) at the times t[0 .. n) (host memory, read during the call) from the
+ * pair's flow where it lies: per chunk of at most HSFLOW_INTERP_BATCH_MAX times one memset of the key planes, the splat
+ * (one 64-bit atomicMin per landed source), the resolve, fill_passes launches of the median kernel in FILL mode and the
+ * blend; the time is the launches' batch axis.  Picture i, class plane i and record i are those of hsflow_interp_host
+ * with t[i], whatever n and the chunking.  Everything is device memory on the context's device, any alignment (word
+ * stores where base and stride are multiples of 4); d_stats: n records, 8-byte aligned.  d_prev == NULL: the context's
+ * own pre-processed frames of the pair (d_curr must be NULL too, channels 1).  d_ref[i]: the true frame at t[i], for
+ * sad / max_diff.  Only enqueued on the context's stream; the ordering rules of hsflow_warp_batch_device apply word for
+ * word (an owed ITER|EPS check is settled first; hsflow_wait_solve afterwards waits for this work too).  The flow is not
+ * changed.  Scratch: 26 bytes per pixel of pitch x height and time of the chunk (keys, two pairs of fp32 planes and two
+ * state planes for the fill's ping-pong), allocated by the first call for min(n, chunk) times, grown on demand and kept
+ * until hsflow_destroy: contexts that never interpolate pay nothing.  A call that has to allocate or grow the scratch
+ * (the first one, and the first with more times per chunk than any before) is not "only enqueued": freeing the old
+ * block waits until the whole device is idle, earlier chunks of this context and other streams' work included.  Call
+ * once with the largest n (up to the chunk size) ahead of a latency-critical loop.  Every argument is checked before anything is
+ * enqueued.  HSFLOW_E_ARG: null params or list entry, struct_size, channels, a t outside [0, 1] or not finite, fill
+ * parameters out of range, neither pictures nor class planes nor records asked for, misaligned records, a destination
+ * equal to an input, d_curr without d_prev or the reverse, the chunk size in the environment; HSFLOW_E_SIZE: a stride
+ * below the row's bytes.
+ * Time on an MI355X (profiles/interp_time.txt), BGR pictures of a 1080p pair: one time 0.183 ms, with
+ * reference and statistics 0.228 ms, eight times in one call 1.25 ms (0.156 each); 600x480: 0.058 ms, eight 0.198 ms.
+ * That is 19 x a device-to-device copy of the bytes moved and 7 x two hsflow_warp_device calls, and 1400 x faster than
+ * the host route (hsflow_get_flow + hsflow_interp_host, 263 ms).  Kernel by kernel at 1080p, one time, from a kernel
+ * trace: the key planes' memset 0.009, splat 0.047 (1 channel: 0.044), resolve 0.032 (with statistics 0.035), each of
+ * the four fill passes 0.0195, blend 0.023 (with reference and statistics 0.048) ms; eight times: 0.368, 0.264, 0.112 per
+ * pass and 0.146 ms; 600x480: 0.0081, 0.0055, 0.0087 per pass and 0.0073 ms.  The splat is bound by its 64-bit minima:
+ * the same gather without them (hsflow_warp's kernel) takes 0.013 ms, the 2.07 M atomics about 0.033 ms (45 G per
+ * second), and a launch of eight times takes eight times as long. */
+int hsflow_interp_batch_device(hsflow_ctx *ctx, int pair, int n, const float *t, const hsflow_interp_params *ip, const void *d_prev,
+                               size_t prev_stride, const void *d_curr, size_t curr_stride, const void *d_vis_prev /* or NULL */,
+                               size_t vis_prev_stride, const void *d_vis_curr /* or NULL */, size_t vis_curr_stride,
+                               const void *const *d_ref /* n, or NULL */, size_t ref_stride, void *const *d_dst /* n, or NULL */, size_t dst_stride,
+                               void *const *d_cls /* n, or NULL */, size_t cls_stride, hsflow_interp_stats *d_stats /* n on the device, or NULL */);
+/* A batch of one. */
+int hsflow_interp_device(hsflow_ctx *ctx, int pair, float t, const hsflow_interp_params *ip, const void *d_prev, size_t prev_stride,
+                         const void *d_curr, size_t curr_stride, const void *d_vis_prev, size_t vis_prev_stride, const void *d_vis_curr,
+                         size_t vis_curr_stride, const void *d_ref, size_t ref_stride, void *d_dst, size_t dst_stride, void *d_cls, size_t cls_stride,
+                         hsflow_interp_stats *d_stats);
+/* One time with everything in host memory, synchronous: complete on return.  prev == NULL: the context's own frames.
+ * Waits only for an event behind its own work, like hsflow_warp -- except in a call that has to allocate its staging. */
+int hsflow_interp(hsflow_ctx *ctx, int pair, float t, const hsflow_interp_params *ip, const uint8_t *prev, size_t prev_stride, const uint8_t *curr,
+                  size_t curr_stride, const uint8_t *vis_prev, size_t vis_prev_stride, const uint8_t *vis_curr, size_t vis_curr_stride,
+                  const uint8_t *ref, size_t ref_stride, uint8_t *dst, size_t dst_stride, uint8_t *cls, size_t cls_stride, hsflow_interp_stats *stats);
+/* Steps P and F of the pair's flow on the device: what hsflow_project_flow_host gives from that flow, into device memory
+ * (fp32 planes 4-byte aligned, out_stride a multiple of 4).  Only enqueued, like hsflow_interp_device; the outputs may
+ * not be the pair's own planes.  d_prev == NULL: the context's own frames. */
+int hsflow_project_flow_device(hsflow_ctx *ctx, int pair, float t, const hsflow_interp_params *ip, const void *d_prev, size_t prev_stride,
+                               const void *d_curr, size_t curr_stride, void *d_u_out /* or NULL */, void *d_v_out /* or NULL */, size_t out_stride,
+                               void *d_state_out /* or NULL */, size_t state_out_stride, hsflow_interp_stats *d_stats /* or NULL */);
+
 /* --- the input files (cvLoadImage) ---------------------------------------------------------- */
 
 /* The reference reads its two frames with cvLoadImage(path, 1) (OpticalFlowOpenCV.cpp:15,18, HSOpticalFlowOpenCL.cpp:721,
@@ -1471,6 +1610,16 @@ int hsflow_pipeline_median(hsflow_pipeline *pl, uint64_t ticket, const hsflow_me
                            float *u, float *v, size_t out_stride, uint8_t *state_out, size_t state_out_stride, hsflow_median_stats *stats);
 int hsflow_pipeline_median_apply(hsflow_pipeline *pl, uint64_t ticket, const hsflow_median_params *mp, int passes, const void *d_state,
                                  size_t state_stride, void *d_state_out, size_t state_out_stride, hsflow_median_stats *d_stats);
+/* wait(ticket) + hsflow_interp / hsflow_interp_device of the ticket's slot (the ticket's pair is the FORWARD pair): complete
+ * on return, HSFLOW_E_STATE if the slot has been reused. */
+int hsflow_pipeline_interp(hsflow_pipeline *pl, uint64_t ticket, float t, const hsflow_interp_params *ip, const uint8_t *prev, size_t prev_stride,
+                           const uint8_t *curr, size_t curr_stride, const uint8_t *vis_prev, size_t vis_prev_stride, const uint8_t *vis_curr,
+                           size_t vis_curr_stride, const uint8_t *ref, size_t ref_stride, uint8_t *dst, size_t dst_stride, uint8_t *cls,
+                           size_t cls_stride, hsflow_interp_stats *stats);
+int hsflow_pipeline_interp_device(hsflow_pipeline *pl, uint64_t ticket, float t, const hsflow_interp_params *ip, const void *d_prev, size_t prev_stride,
+                                  const void *d_curr, size_t curr_stride, const void *d_vis_prev, size_t vis_prev_stride, const void *d_vis_curr,
+                                  size_t vis_curr_stride, const void *d_ref, size_t ref_stride, void *d_dst, size_t dst_stride, void *d_cls,
+                                  size_t cls_stride, hsflow_interp_stats *d_stats);
 /* wait(ticket) + the JPEG file of that pair's picture (hsflow_render_flow_jpeg of its slot): complete on return.
  * HSFLOW_E_STATE if the slot has been reused already; otherwise the errors of hsflow_render_flow_jpeg. */
 int hsflow_pipeline_render_jpeg(hsflow_pipeline *pl, uint64_t ticket, const hsflow_render_params *rp, int quality,

@@ -22,6 +22,8 @@ FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE, FB_UNKNOWN = 0, 1, 2, 3
 MEDIAN_FILTER, MEDIAN_FILL = 0, 1
 MEDIAN_UNFILLED, MEDIAN_KEPT, MEDIAN_FILLED = 0, 1, 2
 MEDIAN_MAX_PASSES = 64  # HSFLOW_MEDIAN_MAX_PASSES
+INTERP_BLENDED, INTERP_PREV_ONLY, INTERP_CURR_ONLY, INTERP_CLAMPED = 0, 1, 2, 3
+INTERP_BATCH_MAX = 8  # HSFLOW_INTERP_BATCH_MAX
 JPEG_ORDER_BGR, JPEG_ORDER_RGB = 0, 1
 JPEGD_SUBSEQ_BITS = 1024  # HSFLOW_JPEGD_SUBSEQ_BITS
 JPEGD_BATCH_MAX = 32  # HSFLOW_JPEGD_BATCH_MAX
@@ -94,6 +96,20 @@ class HsflowMedianStats(ctypes.Structure):
                 ("changed", ctypes.c_uint64), ("reserved", ctypes.c_uint8 * 24)]
 
 
+class HsflowInterpParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("channels", ctypes.c_int32), ("fill_radius", ctypes.c_int32), ("fill_min_votes", ctypes.c_int32),
+                ("fill_passes", ctypes.c_int32)]
+
+
+class HsflowInterpStats(ctypes.Structure):
+    _fields_ = [("blended", ctypes.c_uint64), ("prev_only", ctypes.c_uint64), ("curr_only", ctypes.c_uint64), ("clamped", ctypes.c_uint64),
+                ("sad", ctypes.c_uint64), ("holes", ctypes.c_uint32), ("unfilled", ctypes.c_uint32), ("collisions", ctypes.c_uint32),
+                ("left", ctypes.c_uint32), ("unknown", ctypes.c_uint32), ("max_diff", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class HsflowPlaneDiff(ctypes.Structure):
     _fields_ = [("differing", ctypes.c_uint64), ("failing", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64),
                 ("first_failing", ctypes.c_int64), ("max_abs_diff", ctypes.c_float), ("max_ulp", ctypes.c_uint32)]
@@ -143,6 +159,9 @@ _bs = ctypes.POINTER(HsflowFbStats)
 _ip = ctypes.POINTER(ctypes.c_int)
 _mp = ctypes.POINTER(HsflowMedianParams)
 _ms = ctypes.POINTER(HsflowMedianStats)
+_np = ctypes.POINTER(HsflowInterpParams)
+_ns = ctypes.POINTER(HsflowInterpStats)
+_f = ctypes.c_float
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
 _ji = ctypes.POINTER(HsflowJpegInfo)
@@ -228,6 +247,13 @@ PROTOTYPES = {
     "hsflow_median_planes_device": (_i, [_vp, _mp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_median_apply": (_i, [_vp, _i, _mp, _i, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_median": (_i, [_vp, _i, _mp, _i, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _ms]),
+    "hsflow_default_interp_params": (None, [_np]),
+    "hsflow_project_flow_host": (_i, [_vp, _sz, _vp, _sz, _i, _i, _f, _np, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _ns]),
+    "hsflow_interp_host": (_i, [_vp, _sz, _vp, _sz, _i, _i, _f, _np, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _ns]),
+    "hsflow_interp_batch_device": (_i, [_vp, _i, _i, _fp, _np, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_interp_device": (_i, [_vp, _i, _f, _np, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_interp": (_i, [_vp, _i, _f, _np, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _ns]),
+    "hsflow_project_flow_device": (_i, [_vp, _i, _f, _np, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_jpeg_read_header": (_i, [_vp, _sz, _ji]),
     "hsflow_jpeg_decode_host": (_i, [_vp, _sz, _i, _vp, _sz, _ji]),
     "hsflow_jpeg_decode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),
@@ -280,6 +306,8 @@ PROTOTYPES = {
     "hsflow_pipeline_fb_device": (_i, [_vp, ctypes.c_uint64, ctypes.c_uint64, _bp, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_pipeline_median": (_i, [_vp, ctypes.c_uint64, _mp, _i, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _ms]),
     "hsflow_pipeline_median_apply": (_i, [_vp, ctypes.c_uint64, _mp, _i, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_pipeline_interp": (_i, [_vp, ctypes.c_uint64, _f, _np, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _ns]),
+    "hsflow_pipeline_interp_device": (_i, [_vp, ctypes.c_uint64, _f, _np, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_pipeline_info": (_i, [_vp, ctypes.c_uint64, ctypes.POINTER(HsflowInfo)]),
     "hsflow_pipeline_drain": (_i, [_vp]),
     "hsflow_pipeline_depth": (_i, [_vp]),

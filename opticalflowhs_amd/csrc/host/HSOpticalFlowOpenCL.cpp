@@ -67,7 +67,7 @@ int picture_kind()
 {
     const char *e = getenv("HSFLOW_PICTURE");
     if (!e || !*e || strcmp(e, "arrows") == 0) return 0;
-    return strcmp(e, "color") == 0 ? 1 : strcmp(e, "warp") == 0 ? 2 : strcmp(e, "fb") == 0 ? 3 : -1;
+    return strcmp(e, "color") == 0 ? 1 : strcmp(e, "warp") == 0 ? 2 : strcmp(e, "fb") == 0 ? 3 : strcmp(e, "interp") == 0 ? 4 : -1;
 }
 
 bool color_picture() { return picture_kind() == 1; }
@@ -178,6 +178,76 @@ int fb_picture(hsflow_ctx *ctx, int W, int H, pnm::Image &out)
     return SDK_SUCCESS;
 }
 
+// HSFLOW_PICTURE=interp on the two "-hd" routes: the file holds the frame at time t between the two input files, in their
+// own channels (hsflow_interp*: the forward flow projected to t, holes filled, both frames fetched and blended), and one
+// line on stdout tells the record.  HSFLOW_INTERP_T=<float in 0 .. 1> (default 0.5).  HSFLOW_INTERP_FB=1: the context
+// holds the reversed pair as for HSFLOW_PICTURE=fb, and the masks of both checks (HSFLOW_FB_ALPHA / HSFLOW_FB_BETA) go
+// in as vis_prev / vis_curr.  false: the value is unusable.
+bool interp_time(float &t)
+{
+    t = 0.5f;
+    const char *e = getenv("HSFLOW_INTERP_T");
+    if (!e || !*e) return true;
+    char *rest = nullptr;
+    const float x = strtof(e, &rest);
+    if (*rest || !std::isfinite(x) || !(x >= 0.f && x <= 1.f)) return false;
+    t = x;
+    return true;
+}
+
+bool interp_fb()
+{
+    const char *e = getenv("HSFLOW_INTERP_FB");
+    return e && e[0] == '1';
+}
+
+// With HSFLOW_RENDER_DEVICE=1 through hsflow_interp (and hsflow_fb: the flows stay on the device), otherwise
+// hsflow_interp_host (and hsflow_fb_host) on the flows read back; the same bytes and the same line.
+int interp_picture(hsflow_ctx *ctx, const pnm::Image &first, const pnm::Image &second, const std::vector<float> &u, const std::vector<float> &v,
+                   pnm::Image &out)
+{
+    const int W = second.width, H = second.height, C = second.channels;
+    if (first.width != W || first.height != H || first.channels != C) { std::cout << "HSFLOW_PICTURE=interp: the two frames differ in kind" << std::endl; return SDK_FAILURE; }
+    out.width = W; out.height = H; out.channels = C;
+    out.data.resize((size_t)W * H * C);
+    float t;
+    interp_time(t);
+    hsflow_interp_params ip;
+    hsflow_default_interp_params(&ip);
+    ip.channels = C;
+    hsflow_interp_stats s;
+    const size_t rowb = (size_t)W * C, frow = (size_t)W * 4;
+    const bool device = render_on_device(), fb = interp_fb();
+    std::vector<uint8_t> vis[2];
+    int st = HSFLOW_OK;
+    if (fb) {
+        hsflow_fb_params fp;
+        const char *which = nullptr;
+        fb_params(fp, &which);
+        for (auto &m : vis) m.resize((size_t)W * H);
+        if (device) {
+            st = hsflow_fb(ctx, 0, 1, &fp, vis[0].data(), (size_t)W, nullptr, 0, nullptr);
+            if (st == HSFLOW_OK) st = hsflow_fb(ctx, 1, 0, &fp, vis[1].data(), (size_t)W, nullptr, 0, nullptr);
+            if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+        } else {
+            std::vector<float> ub((size_t)W * H), vb((size_t)W * H);
+            if (hsflow_get_flow(ctx, 1, ub.data(), frow, vb.data(), frow) != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+            st = hsflow_fb_host(u.data(), frow, v.data(), frow, ub.data(), frow, vb.data(), frow, W, H, &fp, vis[0].data(), (size_t)W, nullptr, 0, nullptr);
+            if (st == HSFLOW_OK) st = hsflow_fb_host(ub.data(), frow, vb.data(), frow, u.data(), frow, v.data(), frow, W, H, &fp, vis[1].data(), (size_t)W, nullptr, 0, nullptr);
+            if (st != HSFLOW_OK) { std::cout << hsflow_last_error(nullptr) << std::endl; return SDK_FAILURE; }
+        }
+    }
+    const uint8_t *vp = fb ? vis[0].data() : nullptr, *vc = fb ? vis[1].data() : nullptr;
+    st = device ? hsflow_interp(ctx, 0, t, &ip, first.data.data(), rowb, second.data.data(), rowb, vp, (size_t)W, vc, (size_t)W, nullptr, 0, out.data.data(), rowb,
+                                nullptr, 0, &s)
+                : hsflow_interp_host(u.data(), frow, v.data(), frow, W, H, t, &ip, first.data.data(), rowb, second.data.data(), rowb, vp, (size_t)W, vc, (size_t)W,
+                                     nullptr, 0, out.data.data(), rowb, nullptr, 0, &s);
+    if (st != HSFLOW_OK) { std::cout << hsflow_last_error(device ? ctx : nullptr) << std::endl; return SDK_FAILURE; }
+    std::cout << "interp: t " << t << " blended " << s.blended << " prev_only " << s.prev_only << " curr_only " << s.curr_only << " clamped " << s.clamped
+              << " holes " << s.holes << " unfilled " << s.unfilled << " collisions " << s.collisions << " left " << s.left << " unknown " << s.unknown << std::endl;
+    return SDK_SUCCESS;
+}
+
 // HSFLOW_MEDIAN=<radius>[,<passes>[,fill]] on the two "-hd" routes: the pair's flow is median-filtered in place
 // (hsflow_median_apply: radius 1 or 2, passes 1 .. 64, default 1) before the picture is drawn.  With "fill" the context
 // holds the reversed pair as for HSFLOW_PICTURE=fb, the hsflow_fb mask (HSFLOW_FB_ALPHA / HSFLOW_FB_BETA) is the state,
@@ -276,7 +346,7 @@ int draw_on_device(hsflow_ctx *ctx, int preset, int W, int H, pnm::Image &imgFlo
 bool jpeg_on_device(const std::string &output)
 {
     const char *e = getenv("HSFLOW_JPEG_DEVICE");
-    if (!render_on_device() || !e || atoi(e) == 0 || warp_wanted() || fb_wanted()) return false; // (the warped frame and the mask are written by the host's encoder)
+    if (!render_on_device() || !e || atoi(e) == 0 || warp_wanted() || fb_wanted() || interp_wanted()) return false; // (the warped frame, the mask and the intermediate frame are written by the host's encoder)
     auto ends = [&](const char *x) {
         const size_t n = std::strlen(x);
         if (output.size() < n) return false;
@@ -315,10 +385,12 @@ bool picture_choice_usable()
     hsflow_warp_params wp;
     hsflow_fb_params fp;
     const char *which = nullptr;
-    if (picture_kind() < 0) { std::cout << "HSFLOW_PICTURE must be color, warp, fb or arrows" << std::endl; return false; }
+    if (picture_kind() < 0) { std::cout << "HSFLOW_PICTURE must be color, warp, fb, interp or arrows" << std::endl; return false; }
     if (!fb_params(fp, &which)) { std::cout << which << " must be a finite number >= 0 (alpha at most 1e6, beta at most 1e30)" << std::endl; return false; }
     if (!color_params(cp)) { std::cout << "HSFLOW_COLOR_MAX must be a finite number > 0" << std::endl; return false; }
     if (!warp_params(wp)) { std::cout << "HSFLOW_WARP_T must be a finite number, at most 1e6 in magnitude" << std::endl; return false; }
+    float t;
+    if (!interp_time(t)) { std::cout << "HSFLOW_INTERP_T must be a number in 0 .. 1" << std::endl; return false; }
     int radius, passes;
     bool fill;
     if (median_choice(radius, passes, fill) < 0) { std::cout << "HSFLOW_MEDIAN must be <radius 1 or 2>[,<passes 1 .. 64>[,fill]]" << std::endl; return false; }
@@ -332,17 +404,20 @@ bool median_wanted()
     return median_choice(radius, passes, fill) == 1;
 }
 
-// HSFLOW_MEDIAN=..,fill needs the reversed pair beside the pair, as HSFLOW_PICTURE=fb does.
+// HSFLOW_MEDIAN=..,fill and HSFLOW_PICTURE=interp with HSFLOW_INTERP_FB=1 need the reversed pair beside the pair, as
+// HSFLOW_PICTURE=fb does.
 static bool reversed_pair_wanted()
 {
     int radius, passes;
     bool fill;
-    return fb_wanted() || (median_choice(radius, passes, fill) == 1 && fill);
+    return fb_wanted() || (interp_wanted() && interp_fb()) || (median_choice(radius, passes, fill) == 1 && fill);
 }
 
 bool warp_wanted() { return picture_kind() == 2; }
 
 bool fb_wanted() { return picture_kind() == 3; }
+
+bool interp_wanted() { return picture_kind() == 4; }
 
 HSOpticalFlowOpenCL::HSOpticalFlowOpenCL(const char *name, char *src_, char *in1, char *in2, char *out, float alp,
                                          int it, int gs, char *dType)
@@ -511,6 +586,9 @@ int HSOpticalFlowOpenCL::run()
         if (warp_wanted()) {
             if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; return -1; }
             if (warp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
+        } else if (interp_wanted()) {
+            if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; return -1; }
+            if (interp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
         } else if (fb_wanted()) {
             if (fb_picture(ctx, (int)width, (int)height, imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
         } else if (drawFlow(imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
@@ -609,11 +687,14 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     } else if (warp_wanted()) {
         if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; hsflow_destroy(ctx); return -1; }
         if (warp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
+    } else if (interp_wanted()) {
+        if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; hsflow_destroy(ctx); return -1; }
+        if (interp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     } else if (fb_wanted()) {
         if (fb_picture(ctx, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     } else if (on_device && draw_on_device(ctx, HSFLOW_RENDER_CV, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     hsflow_destroy(ctx);
-    if (!on_device && !warp_wanted() && !fb_wanted()) draw_cv_flow(imgFlow, u, v, W, H);
+    if (!on_device && !warp_wanted() && !fb_wanted() && !interp_wanted()) draw_cv_flow(imgFlow, u, v, W, H);
     if (!file_on_device) pnm::save_image(output, imgFlow);
     std::cout << "Avg time: " << ms << " [ms]" << std::endl;
     return verdict;

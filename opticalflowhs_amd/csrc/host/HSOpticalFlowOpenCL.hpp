@@ -80,6 +80,9 @@ bool warp_wanted();
 // HSFLOW_PICTURE=fb: the file is the forward-backward consistency mask of the pair against its reverse (the two "-hd"
 // routes only).
 bool fb_wanted();
+// HSFLOW_PICTURE=interp: the file is the frame at time HSFLOW_INTERP_T between the two input files (the two "-hd" routes
+// only).
+bool interp_wanted();
 // HSFLOW_MEDIAN=<radius>[,<passes>[,fill]]: the flow is median-filtered, or its untrusted pixels filled, in place before
 // the picture is drawn (the two "-hd" routes only).
 bool median_wanted();

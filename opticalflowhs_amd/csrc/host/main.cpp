@@ -25,6 +25,13 @@
 // the statistics; by hsflow_fb_host from the flows read back, with HSFLOW_RENDER_DEVICE=1 by hsflow_fb on the device; the
 // same file and line.  HSFLOW_FB_ALPHA / HSFLOW_FB_BETA=<float>: the bound's two terms (defaults 0.01 and 0.5; finite,
 // 0 .. 1e6 and 0 .. 1e30, else a message and exit status 1).
+// HSFLOW_PICTURE=interp (the two -hd routes): the file is the frame at time t between the two input files, in their own
+// channels (hsflow_interp*: the forward flow projected to t, its holes filled, both frames fetched along it and blended);
+// one line "interp: t .. blended .. prev_only .. curr_only .. clamped .. holes .. unfilled .. collisions .. left .. unknown
+// .." tells the record; by hsflow_interp_host from the flow read back, with HSFLOW_RENDER_DEVICE=1 by hsflow_interp on the
+// device; the same file and line.  HSFLOW_INTERP_T=<float in 0 .. 1> (default 0.5; else a message and exit status 1).
+// HSFLOW_INTERP_FB=1: the pair is also solved backwards as for HSFLOW_PICTURE=fb, and the masks of both checks go in as
+// the visibility planes.
 // HSFLOW_MEDIAN=<radius>[,<passes>[,fill]] (the two -hd routes): the solved flow is median-filtered in place on the device
 // (hsflow_median_apply; radius 1 or 2, passes 1 .. 64) before the picture that HSFLOW_PICTURE asks for is drawn.  With
 // "fill" the pair is also solved backwards as for HSFLOW_PICTURE=fb, the hsflow_fb mask (HSFLOW_FB_ALPHA / HSFLOW_FB_BETA)
@@ -73,6 +80,7 @@ int main(int argc, char *argv[])
     if (!picture_choice_usable()) return 1;
     if (warp_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=warp needs a pair of files (-hd)\n"; return 1; }
     if (fb_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=fb needs a pair of files (-hd)\n"; return 1; }
+    if (interp_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=interp needs a pair of files (-hd)\n"; return 1; }
     if (median_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_MEDIAN needs a pair of files (-hd)\n"; return 1; }
     if (argc >= 3 && strcmp(argv[1], "-cl") == 0) {
         if (strcmp(argv[2], "-hd") == 0) {

@@ -317,6 +317,17 @@ struct hsflow_ctx {
         uint8_t *s[2] = {nullptr, nullptr};
         hsflow_median_stats *dStats = nullptr, *hStats = nullptr;
     } median;
+    // hsflow_interp* / hsflow_project_flow_device (hs_interp.hip.h): one block for `times` times of a chunk -- per time the
+    // key plane, two pairs of fp32 planes and two state planes of pitch x height, then the fill's records -- allocated by
+    // the first call, grown on demand and kept; for the synchronous form the caller's pictures on the device (prev, curr,
+    // vis_prev, vis_curr, ref, dst, cls), one statistics record on the device and one in page-locked memory.
+    struct InterpScratch {
+        void *base = nullptr;
+        int times = 0;
+        uint8_t *stage[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        size_t stage_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
+        hsflow_interp_stats *dStats = nullptr, *hStats = nullptr;
+    } interp;
 };
 
 namespace {

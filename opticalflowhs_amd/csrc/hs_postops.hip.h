@@ -1,6 +1,6 @@
 // hs_postops.hip.h -- part of libhsflow.so (one translation unit, see hsflow.hip): what the operators on a solved flow
-// share on the host side -- the arrow and colour pictures, their JPEG forms, warp, forward-backward check and median
-// (hs_render / hs_color / hs_jpeg / hs_warp / hs_fb / hs_median.hip.h).  Three ordering rules hold for all of them
+// share on the host side -- the arrow and colour pictures, their JPEG forms, warp, forward-backward check, median and
+// interpolation (hs_render / hs_color / hs_jpeg / hs_warp / hs_fb / hs_median / hs_interp.hip.h).  Three ordering rules hold for all of them
 // (DESIGN.md 4.15), and this is their one home:
 //   1. an owed ITER|EPS check is settled before c->cur is named: a re-run may end in the other buffer of the ping-pong, and
 //      a result from a flow that a re-run would change is worth nothing (batch_device_begin; the synchronous forms call
@@ -38,7 +38,7 @@ int sync_wait(hsflow_ctx *c)
 // Behind the call's last wait: nothing of it is in flight any more, the solve's marker speaks for the context again.
 void sync_restore(hsflow_ctx *c, bool marked) { c->last_marked = marked; }
 
-constexpr size_t kStatsBytes = 64; // hsflow_warp_stats, hsflow_fb_stats, hsflow_median_stats: each asserts it
+constexpr size_t kStatsBytes = 64; // hsflow_warp_stats, hsflow_fb_stats, hsflow_median_stats, hsflow_interp_stats: each asserts it
 
 // The last wait, then the statistics record from page-locked memory (h) to the caller (record; NULL: none was asked for).
 int sync_finish(hsflow_ctx *c, bool marked, void *record = nullptr, const void *h = nullptr)
@@ -145,7 +145,7 @@ int batch_device_begin(hsflow_ctx *c, const void *d_stats, int *maxb)
     return settle_pending(c);
 }
 
-// The synchronous forms' scratch of warp, check and median (hsflow_destroy).
+// The scratch of warp, check, median and interpolation (hsflow_destroy).
 void postops_release(hsflow_ctx *c)
 {
     hipFree(c->warp.src); hipFree(c->warp.ref); hipFree(c->warp.dst);
@@ -157,6 +157,10 @@ void postops_release(hsflow_ctx *c)
     for (int k = 0; k < 2; k++) { hipFree(c->median.u[k]); hipFree(c->median.v[k]); hipFree(c->median.s[k]); }
     stats_release(c->median.dStats, c->median.hStats);
     c->median = hsflow_ctx::MedianScratch();
+    hipFree(c->interp.base);
+    for (uint8_t *p : c->interp.stage) hipFree(p);
+    stats_release(c->interp.dStats, c->interp.hStats);
+    c->interp = hsflow_ctx::InterpScratch();
 }
 
 } // namespace

@@ -15,6 +15,7 @@
 #include "hs_kernels_warp.hip.h"
 #include "hs_kernels_fb.hip.h"
 #include "hs_kernels_median.hip.h"
+#include "hs_kernels_interp.hip.h"
 #include "hs_kernels_verify.hip.h"
 #include "hs_kernels_jpeg.hip.h"
 #include "hs_kernels_jpegd.hip.h"
@@ -909,6 +910,7 @@ void hsflow_release_cached(void)
 #include "hs_warp.hip.h"   // hsflow_warp[_host|_device|_batch_device], hsflow_default_warp_params
 #include "hs_fb.hip.h"     // hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_default_fb_params
 #include "hs_median.hip.h" // hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_default_median_params
+#include "hs_interp.hip.h" // hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host / _device, hsflow_default_interp_params
 #include "hs_verify.hip.h" // hsflow_verify, hsflow_compare_flow_device, hsflow_compare_planes_host
 #include "hs_jpeg.hip.h"   // hsflow_jpeg_bound, hsflow_jpeg_encode_host / _device, hsflow_render_flow_jpeg[_device]
 #include "hs_jpegd.hip.h"  // hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg

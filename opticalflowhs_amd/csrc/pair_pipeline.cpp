@@ -414,6 +414,34 @@ int hsflow_pipeline_warp_device(hsflow_pipeline *pl, uint64_t ticket, const hsfl
     return wait_on_slot(pl, s, "warp");
 }
 
+int hsflow_pipeline_interp(hsflow_pipeline *pl, uint64_t ticket, float t, const hsflow_interp_params *ip, const uint8_t *prev, size_t prev_stride,
+                           const uint8_t *curr, size_t curr_stride, const uint8_t *vis_prev, size_t vis_prev_stride, const uint8_t *vis_curr,
+                           size_t vis_curr_stride, const uint8_t *ref, size_t ref_stride, uint8_t *dst, size_t dst_stride, uint8_t *cls, size_t cls_stride,
+                           hsflow_interp_stats *stats)
+{
+    hsflow_pipeline::Slot *s = nullptr;
+    const int st = slot_of_finished(pl, ticket, &s);
+    return st ? st
+              : ctx_status(pl, s,
+                           hsflow_interp(s->ctx, 0, t, ip, prev, prev_stride, curr, curr_stride, vis_prev, vis_prev_stride, vis_curr, vis_curr_stride, ref,
+                                         ref_stride, dst, dst_stride, cls, cls_stride, stats),
+                           "hsflow_interp");
+}
+
+int hsflow_pipeline_interp_device(hsflow_pipeline *pl, uint64_t ticket, float t, const hsflow_interp_params *ip, const void *d_prev, size_t prev_stride,
+                                  const void *d_curr, size_t curr_stride, const void *d_vis_prev, size_t vis_prev_stride, const void *d_vis_curr,
+                                  size_t vis_curr_stride, const void *d_ref, size_t ref_stride, void *d_dst, size_t dst_stride, void *d_cls, size_t cls_stride,
+                                  hsflow_interp_stats *d_stats)
+{
+    hsflow_pipeline::Slot *s = nullptr;
+    int st = slot_of_finished(pl, ticket, &s);
+    if (st) return st;
+    if ((st = hsflow_interp_device(s->ctx, 0, t, ip, d_prev, prev_stride, d_curr, curr_stride, d_vis_prev, vis_prev_stride, d_vis_curr, vis_curr_stride, d_ref,
+                                   ref_stride, d_dst, dst_stride, d_cls, cls_stride, d_stats)))
+        return ctx_fail(pl, s->ctx, st, "hsflow_interp_device");
+    return wait_on_slot(pl, s, "interpolation");
+}
+
 // Both slots of a forward-backward check and the backward slot's flow where it lies (final: the view waits for it).
 static int fb_slots(hsflow_pipeline *pl, uint64_t ticket_fwd, uint64_t ticket_bwd, hsflow_pipeline::Slot **f, const float **ub, const float **vb, size_t *bs)
 {

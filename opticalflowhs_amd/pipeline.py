@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HsflowError, HsflowInfo, HsflowVerifyReport, TERM_ITER
-from .solver import _is_device_tensor, _render_host, _render_target, _warp_call, _fb_call, _median_call, jpeg_bound, make_color_params, make_params, make_render_params
+from .solver import _is_device_tensor, _render_host, _render_target, _warp_call, _fb_call, _median_call, _interp_call, jpeg_bound, make_color_params, make_params, make_render_params
 
 
 def pinned_empty(shape, dtype):
@@ -209,6 +209,16 @@ class PairPipeline(object):
         self._check((self._lib.hsflow_pipeline_warp_device if device else self._lib.hsflow_pipeline_warp)(self._h, int(ticket), *args))
         self._held.pop(int(ticket), None)
         return (out, stats) if return_stats else out
+
+    def interp(self, ticket, t=0.5, prev=None, curr=None, vis_prev=None, vis_curr=None, ref=None, out=True, classes=False, stats=False, params=None):
+        """wait(ticket) + `HSFlow.interp` of that pair on its slot: the frame at time `t` between the pair's two frames
+        (prev, curr both None: the slot's own pre-processed frames) from the pair's flow; host pictures or CUDA tensors as
+        there, but complete on return either way.  Returns (out, classes, stats).  Raises HsflowError (E_STATE) once the
+        slot has been reused by a later pair."""
+        device, args, out, classes, rec = _interp_call(self.height, self.width, self.device, prev, curr, vis_prev, vis_curr, ref, out, classes, stats, params, False)
+        self._check((self._lib.hsflow_pipeline_interp_device if device else self._lib.hsflow_pipeline_interp)(self._h, int(ticket), float(t), *args))
+        self._held.pop(int(ticket), None)
+        return out, classes, rec
 
     def fb(self, ticket_fwd, ticket_bwd, mask=True, err2=False, stats=False, alpha=0.01, beta=0.5, values=(255, 0, 0, 0), params=None, device=False):
         """wait(both tickets) + `HSFlow.fb` of ticket_fwd's flow against ticket_bwd's on the forward pair's slot: host planes

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowMedianParams, HsflowMedianStats, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -199,6 +199,85 @@ def _warp_call(height, width, device_index, src, ref, out, params, t, border, fi
     (sp, ss), (rp, rs), (op, os_), wp = _warp_args(height, width, src, ref, out, device, params, t, border, fill)
     stats, sref = _stats_record(HsflowWarpStats, return_stats, device, device_index)
     return device, (ctypes.byref(wp), sp, ss, rp, rs, op, os_, sref), out, stats
+
+
+def make_interp_params(channels=1, fill_radius=1, fill_min_votes=1, fill_passes=4):
+    """hsflow_interp_params of the frame between the two frames of a pair: `channels` 1 or 3 (interleaved), and the hole
+    filling of the projected flow -- `fill_passes` passes (0 .. MEDIAN_MAX_PASSES) of the median rule in FILL mode with
+    `fill_radius` (1 or 2) and `fill_min_votes`."""
+    ip = HsflowInterpParams()
+    _lib.load().hsflow_default_interp_params(ctypes.byref(ip))
+    ip.channels, ip.fill_radius, ip.fill_min_votes, ip.fill_passes = int(channels), int(fill_radius), int(fill_min_votes), int(fill_passes)
+    return ip
+
+
+def _interp_call(height, width, device_index, prev, curr, vis_prev, vis_curr, ref, out, classes, stats, params, device):
+    """What `HSFlow.interp`, `PairPipeline.interp` and `interp_host` share.  out / classes: False or None (absent), True
+    (allocated here) or the array to fill; stats True or False.  Returns (device, the C call's arguments from the params
+    on, out, classes, stats)."""
+    if (prev is None) != (curr is None):
+        raise ValueError("prev and curr are given together or not at all")
+    device = bool(device) or any(_is_device_tensor(x) for x in (prev, curr, vis_prev, vis_curr, ref, out, classes))
+    pshape = tuple(prev.shape) if prev is not None else (height, width)
+    made = []
+    for x, shape in ((out, pshape), (classes, (height, width))):
+        if x is None or x is False:
+            x = None
+        elif x is True and device:
+            import torch
+            x = torch.empty(shape, dtype=torch.uint8, device="cuda:%d" % device_index)
+        elif x is True:
+            x = np.empty(shape, np.uint8)
+        made.append(x)
+    out, classes = made
+    pics = [(_warp_image(x, height, width, what, device) if x is not None else (None, 0, None))
+            for x, what in ((prev, "prev"), (curr, "curr"), (ref, "ref"), (out, "out"))]
+    given = set(c for _, _, c in pics if c is not None)
+    if len(given) > 1:
+        raise ValueError("prev, curr, ref and out must have the same number of channels")
+    channels = given.pop() if given else 1
+    if params is None:
+        params = make_interp_params(channels)
+    elif given and params.channels != channels:
+        raise ValueError("params.channels does not match the pictures")
+    planes = [(_plane(x, height, width, "uint8", what, device) if x is not None else (None, 0))
+              for x, what in ((vis_prev, "vis_prev"), (vis_curr, "vis_curr"), (classes, "classes"))]
+    rec, sref = _stats_record(HsflowInterpStats, stats, device, device_index)
+    (pp, ps, _), (cp, cs, _), (rp, rs, _), (op, os_, _) = pics
+    (vpp, vps), (vcp, vcs), (kp, ks) = planes
+    return device, (ctypes.byref(params), pp, ps, cp, cs, vpp, vps, vcp, vcs, rp, rs, op, os_, kp, ks, sref), out, classes, rec
+
+
+def _project_call(height, width, device_index, prev, curr, flow, state, stats, params, device):
+    """What `HSFlow.project_flow` and `project_flow_host` share; flow / state: False, True or (for flow) a pair (u, v) of
+    planes, (for state) the plane to fill.  Returns (the C call's arguments from the params on, u, v, state, stats)."""
+    if (prev is None) != (curr is None):
+        raise ValueError("prev and curr are given together or not at all")
+    pics = [(_warp_image(x, height, width, what, device) if x is not None else (None, 0, None)) for x, what in ((prev, "prev"), (curr, "curr"))]
+    given = set(c for _, _, c in pics if c is not None)
+    if len(given) > 1:
+        raise ValueError("prev and curr must have the same number of channels")
+    if params is None:
+        params = make_interp_params(given.pop() if given else 1)
+
+    def new(dtype):
+        if device:
+            import torch
+            return torch.empty((height, width), dtype=getattr(torch, dtype), device="cuda:%d" % device_index)
+        return np.empty((height, width), dtype)
+    u = v = None
+    if flow is True:
+        u, v = new("float32"), new("float32")
+    elif flow:
+        u, v = flow
+    state = new("uint8") if state is True else (None if state is None or state is False else state)
+    (up, us), (vp, vs) = [(_plane(x, height, width, "float32", "flow output", device) if x is not None else (None, 0)) for x in (u, v)]
+    if u is not None and us != vs:
+        raise ValueError("the two flow outputs share one row stride")
+    sp, ss = _plane(state, height, width, "uint8", "state", device) if state is not None else (None, 0)
+    rec, sref = _stats_record(HsflowInterpStats, stats, device, device_index)
+    (pp, ps, _), (cp, cs, _) = pics
+    return (ctypes.byref(params), pp, ps, cp, cs, up, vp, us, sp, ss, sref), u, v, state, rec
 
 
 def make_fb_params(alpha=0.01, beta=0.5, values=(255, 0, 0, 0)):
@@ -637,6 +716,52 @@ class HSFlow(object):
         self._check(self._lib.hsflow_warp_batch_device(self._h, first_pair, n, ctypes.byref(wp), sl, ss, rl, rs, ol, os_, sref))
         return out
 
+    def interp(self, t=0.5, prev=None, curr=None, vis_prev=None, vis_curr=None, ref=None, out=True, classes=False, stats=False, pair=0, params=None):
+        """The frame at time `t` (0 .. 1) between the two frames of `pair` from its current flow (`make_interp_params`;
+        include/hsflow.h has the rule).  prev, curr: the two pictures, uint8 (H, W) or (H, W, 3); both None: the context's
+        own pre-processed frames.  vis_prev, vis_curr: optional uint8 (H, W) visibility planes (the masks of `fb`).  ref:
+        the true frame, for the record's sad.  out, classes: False, True (allocated) or the array to fill; stats: bool.
+        Host arrays: synchronous.  CUDA tensors: only enqueued on the context's stream (complete after `synchronize()`),
+        the record then a CUDA uint8 tensor of 64 bytes that `interp_stats_from` reads.  Returns (out, classes, stats)."""
+        device, args, out, classes, rec = _interp_call(self.height, self.width, self.device, prev, curr, vis_prev, vis_curr, ref, out, classes, stats, params, False)
+        self._check((self._lib.hsflow_interp_device if device else self._lib.hsflow_interp)(self._h, pair, float(t), *args))
+        return out, classes, rec
+
+    def interp_batch_device(self, times, out=None, prev=None, curr=None, vis_prev=None, vis_curr=None, ref=None, classes=None, stats=None, pair=0, params=None):
+        """`interp` on the device for the n = len(times) times of ONE pair by one set of launches per `INTERP_BATCH_MAX`
+        times (`hsflow_interp_batch_device`).  out, ref: None, a CUDA uint8 tensor (n, H, W[, C]) or a list of n; classes:
+        None or (n, H, W); prev, curr, vis_prev, vis_curr: as `interp` takes them, on the device; stats: None or a CUDA
+        uint8 tensor of n * 64 bytes (`interp_stats_from`).  Only enqueued; returns `out`."""
+        tt = [float(x) for x in times]
+        n = len(tt)
+        (rl, rs, r_), (ol, os_, o_) = [
+            _plane_lists(x, n, what, "picture per time", lambda img, what=what: _warp_image(img, self.height, self.width, what, True))
+            for x, what in ((ref, "ref"), (out, "out"))]
+        kl, ks, _ = _plane_lists(classes, n, "classes", "plane per time", lambda x: _plane(x, self.height, self.width, "uint8", "classes", True))
+        pics = [(_warp_image(x, self.height, self.width, what, True) if x is not None else (None, 0, None)) for x, what in ((prev, "prev"), (curr, "curr"))]
+        channels = set(c for _, _, c in r_ + o_) | set(c for _, _, c in pics if c is not None)
+        if len(channels) > 1:
+            raise ValueError("prev, curr, ref and out must have the same number of channels")
+        ip = params if params is not None else make_interp_params(channels.pop() if channels else 1)
+        (vpp, vps), (vcp, vcs) = [(_plane(x, self.height, self.width, "uint8", what, True) if x is not None else (None, 0))
+                                  for x, what in ((vis_prev, "vis_prev"), (vis_curr, "vis_curr"))]
+        sref = _check_stats_tensor(stats, n, HsflowInterpStats)
+        (pp, ps, _), (cp, cs, _) = pics
+        self._check(self._lib.hsflow_interp_batch_device(self._h, pair, n, (ctypes.c_float * max(n, 1))(*tt), ctypes.byref(ip), pp, ps, cp, cs, vpp, vps, vcp, vcs,
+                                                         rl, rs, ol, os_, kl, ks, sref))
+        return out
+
+    def project_flow(self, t=1.0, prev=None, curr=None, flow=True, state=False, stats=False, pair=0, params=None):
+        """The flow of `pair` projected to time `t` and hole-filled, on the device (`hsflow_project_flow_device`): with
+        t=1 the flow on the second frame's grid, what a camera loop hands to the next pair (`set_flow`, use_previous).
+        prev, curr: CUDA uint8 pictures, or both None: the context's own frames.  flow: True (two CUDA float32 (H, W)
+        tensors are allocated), False, or a pair of them; state: True, False or a CUDA uint8 (H, W) tensor (0 unfilled,
+        1 hit, 2 filled); stats: bool (a CUDA uint8 tensor of 64 bytes, `interp_stats_from`).  Only enqueued on the
+        context's stream.  Returns (u, v, state, stats)."""
+        args, u, v, state, rec = _project_call(self.height, self.width, self.device, prev, curr, flow, state, stats, params, True)
+        self._check(self._lib.hsflow_project_flow_device(self._h, pair, float(t), *args))
+        return u, v, state, rec
+
     def set_frames_reversed(self, dst_pair, src_pair):
         """Pair `dst_pair` receives the pre-processed frames of `src_pair`, swapped (`hsflow_set_frames_reversed`): the
         reversed pair of a bidirectional solve, by device copies on the context's stream."""
@@ -1011,6 +1136,48 @@ def median_host(u, v, state=None, flow=True, state_out=False, stats=False, radiu
     if st != _lib.OK:
         raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
     return u_out, v_out, state_out, rec
+
+
+def interp_stats_from(stats, n=1):
+    """The `HsflowInterpStats` records a device call left in the CUDA uint8 tensor `stats` (after `synchronize()`): one
+    record for n=1, else a list of n."""
+    raw = stats.cpu().numpy().tobytes()
+    size = ctypes.sizeof(HsflowInterpStats)
+    recs = [HsflowInterpStats.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(n)]
+    return recs[0] if n == 1 else recs
+
+
+def _host_flow(u, v):
+    u, v = (a if a.ndim == 2 and a.strides[1] == 4 and a.strides[0] % 4 == 0 else np.ascontiguousarray(a)  # (padded rows are taken as they are)
+            for a in (np.asarray(u, np.float32), np.asarray(v, np.float32)))
+    if u.ndim != 2 or u.shape != v.shape:
+        raise ValueError("u and v must be 2-D arrays of one shape")
+    return u, v
+
+
+def interp_host(u, v, prev, curr, t=0.5, vis_prev=None, vis_curr=None, ref=None, out=True, classes=False, stats=False, params=None):
+    """The frame at time `t` between `prev` and `curr` from the forward flow (u, v) by the rule on the host
+    (`hsflow_interp_host`, no GPU work); arguments as `HSFlow.interp` takes them.  Returns (out, classes, stats) -- bit for
+    bit what the device forms give from the same flow."""
+    u, v = _host_flow(u, v)
+    H, W = u.shape
+    _, args, out, classes, rec = _interp_call(H, W, 0, prev, curr, vis_prev, vis_curr, ref, out, classes, stats, params, False)
+    st = _lib.load().hsflow_interp_host(_ptr(u), u.strides[0], _ptr(v), v.strides[0], W, H, float(t), *args)
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return out, classes, rec
+
+
+def project_flow_host(u, v, prev, curr, t=1.0, flow=True, state=False, stats=False, params=None):
+    """The forward flow (u, v) projected to time `t` and hole-filled by the rule on the host (`hsflow_project_flow_host`);
+    arguments as `HSFlow.project_flow` takes them, NumPy arrays.  Returns (u, v, state, stats)."""
+    u, v = _host_flow(u, v)
+    H, W = u.shape
+    args, uo, vo, state, rec = _project_call(H, W, 0, prev, curr, flow, state, stats, params, False)
+    st = _lib.load().hsflow_project_flow_host(_ptr(u), u.strides[0], _ptr(v), v.strides[0], W, H, float(t), *args)
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return uo, vo, state, rec
 
 
 def compare_planes(a, b):
