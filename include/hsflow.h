@@ -91,7 +91,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 20 /* 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 21 /* 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -1687,6 +1687,102 @@ int hsflow_slab_eps_measured(hsflow_slab *s);                       /* 1: no sla
 int hsflow_slab_create_overlapped(hsflow_slab **out, const int *devices, int ndev, int width, int height, int halo);
 int hsflow_slab_get_flow(hsflow_slab *s, float *u, size_t u_stride, float *v, size_t v_stride);
 const char *hsflow_slab_last_error(hsflow_slab *s); /* s may be NULL: create() error */
+
+/* --- coarse-to-fine solves: a pyramid over the solver ---------------------------------------- */
+
+/* Horn-Schunck linearises the brightness equation, so one solve finds motions of about a pixel.  hsflow_solve_pyramid
+ * solves at several scales, coarsest first, and at every further step warps the second frame by the flow so far and solves
+ * for the INCREMENT.  Every solve is an ordinary hsflow_solve of the level's frames from zero flow with the caller's
+ * hsflow_params; each solve regularises the increment only (DESIGN.md 4.17 names that limit).  For a context of W x H:
+ *   Levels   level 0 is the context; level l+1 is ceil(W_l / 2) x ceil(H_l / 2).  levels = 0 (auto): as many levels as keep
+ *            min(W_l, H_l) >= min_size, at most HSFLOW_PYRAMID_MAX_LEVELS, level 0 always.  levels = 1 .. 8: as given; a
+ *            level of 1 x 1 pixels cannot be halved: HSFLOW_E_SIZE.
+ *   down     prev_l and curr_l, l >= 1, from level l-1, for u8 planes of W x H:
+ *              dst(x, y) = (sum_{i,j=-2..2} k_i k_j src(clamp(2x+i, 0, W-1), clamp(2y+j, 0, H-1)) + 128) >> 8, k = (1, 4, 6, 4, 1):
+ *            exact integers (hsflow_pyramid_down_host is the same rule on the host).
+ *   prolong  a coarse plane c of Wc x Hc floats to a fine one of W x H, Wc = ceil(W/2), Hc = ceil(H/2), all fp32, every
+ *            operation rounded on its own:
+ *              h(x, r)   = c(x>>1, r) for even x;  fl(fl(c(k, r) + c(min(k+1, Wc-1), r)) * 0.5f), k = x>>1, for odd x
+ *              g(x, y)   = h(x, y>>1) for even y;  fl(fl(h(x, r) + h(x, min(r+1, Hc-1))) * 0.5f), r = y>>1, for odd y
+ *              dst(x, y) = fl(2 * g(x, y))
+ *            Even positions copy; a NaN or an Inf beside them stays where it is (hsflow_pyramid_prolong_host).
+ *   Steps, coarsest level first, `warps` steps per level:
+ *     - the first step of the coarsest level: total = solve(prev, curr) from zero.  No addition and no warp: with
+ *       levels = 1, warps = 1, median_radius = 0 the call is hsflow_solve bit for bit, -0.0 included.
+ *     - every further step: the base flow (u0, v0) is prolong(total of level l+1) for the first step of a level, the
+ *       level's total so far for a later one; w = the warp rule of hsflow_warp on curr_l with (u0, v0), one channel, t = 1,
+ *       HSFLOW_WARP_BORDER_REPLICATE, where an unknown pixel (NaN, or a magnitude above 1e9) takes curr_l's own byte at
+ *       (x, y); (du, dv) = solve(prev_l, w) from zero; total = fl(u0 + du), fl(v0 + dv).
+ *     - median_radius 1 or 2: every total, the coarsest level's and the last one included, takes one pass of the median
+ *       rule (hsflow_median_host: that radius, HSFLOW_MEDIAN_FILTER, min_votes 1, no state plane) as soon as it is formed.
+ *   Afterwards the total of level 0 is the context's flow: hsflow_get_flow*, hsflow_flow_view_device, render, colour, warp,
+ *   fb, median, interp and a later use_previous = 1 solve see it as they see any flow.  The context's frames are the
+ *   caller's (the second frame is put back when the call's work has run); the context treats them as changed -- a following
+ *   solve with reuse_derivatives = 1 recomputes the derivatives -- and treats its flow as caller-written, the way
+ *   hsflow_set_flow_device leaves it.  hsflow_get_info reports the finest level's last solve; hsflow_verify returns
+ *   HSFLOW_E_STATE until the next plain solve.
+ * The call covers all pairs of the context.  The level contexts (levels >= 1) and their planes are created by the first call
+ * and kept until hsflow_destroy; they are made anew when the plan changes; they share the context's device, stream and CU
+ * share.  A context that never calls it pays nothing.  With ITER termination the call only enqueues (like
+ * hsflow_solve_async); with HSFLOW_TERM_EPS in term_type every solve is settled before its flow is read: ONE HOST WAIT PER
+ * STEP.  Not covered: pair-pipeline tickets, hsflow_multi_* and slabs. */
+#define HSFLOW_PYRAMID_MAX_LEVELS 8
+#define HSFLOW_PYRAMID_MAX_WARPS 8
+typedef struct hsflow_pyramid_params {
+    uint32_t struct_size;  /* = sizeof(hsflow_pyramid_params) */
+    int32_t levels;        /* 0: auto (min_size decides); 1 .. HSFLOW_PYRAMID_MAX_LEVELS: as given */
+    int32_t min_size;      /* auto: the smaller side of the coarsest level is at least this (>= 1) */
+    int32_t warps;         /* steps per level, 1 .. HSFLOW_PYRAMID_MAX_WARPS */
+    int32_t median_radius; /* 0: none; 1, 2: a 3x3 / 5x5 median of every total */
+} hsflow_pyramid_params;
+/* levels 0, min_size 32, warps 1, median_radius 0.  NULL is ignored.  (Measured with the CPU oracle: a coarsest level of
+ * 20 x 16 raised the error of a (9, 6) px shift on 320 x 256 from 0.24 to 1.27 px; hence 32.) */
+void hsflow_default_pyramid_params(hsflow_pyramid_params *pp);
+/* The plan of a width x height context, no device needed: *levels, and widths[l], heights[l] for l < *levels (arrays of
+ * HSFLOW_PYRAMID_MAX_LEVELS entries, the rest zero; either may be NULL).  HSFLOW_E_ARG: pp NULL or its struct_size wrong,
+ * levels outside 0 .. 8, min_size < 1, warps outside 1 .. 8, median_radius outside 0 .. 2, levels NULL.  HSFLOW_E_SIZE:
+ * width or height < 1, or explicit levels beyond a level of 1 x 1. */
+int hsflow_pyramid_plan(int width, int height, const hsflow_pyramid_params *pp, int *levels, int *widths, int *heights);
+/* `down` on the host: src is width x height bytes, dst receives ceil(width/2) bytes in each of ceil(height/2) rows and
+ * nothing else.  Strides in bytes.  HSFLOW_E_ARG: a NULL plane; HSFLOW_E_SIZE: width or height < 1, a stride smaller than
+ * its row. */
+int hsflow_pyramid_down_host(const uint8_t *src, size_t src_stride, int width, int height, uint8_t *dst, size_t dst_stride);
+/* `prolong` on the host: width x height is the FINE size, coarse holds ceil(width/2) x ceil(height/2) floats.  Strides in
+ * bytes, multiples of 4.  HSFLOW_E_ARG: a NULL plane; HSFLOW_E_SIZE: width or height < 1, a stride smaller than its row or
+ * no multiple of 4. */
+int hsflow_pyramid_prolong_host(const float *coarse, size_t coarse_stride, int width, int height, float *dst, size_t dst_stride);
+/* The pyramid solve of every pair of the context (above).
+ *   HSFLOW_E_ARG    params NULL or its struct_size wrong; pp as for hsflow_pyramid_plan; a mode other than HSFLOW_MODE_CV;
+ *                   use_previous set; profile = 1; HSFLOW_KERNEL_PERSIST; whatever hsflow_solve refuses in params
+ *   HSFLOW_E_SIZE   explicit levels beyond a level of 1 x 1; more pairs than half the device's grid limit in z
+ *   HSFLOW_E_STATE  frames not set; a row origin (hsflow_set_row_origin) or an Eps row window (hsflow_set_eps_rows) other
+ *                   than the default; hsflow_set_pair_termination on, with EPS in term_type and more than one pair
+ *   HSFLOW_E_NOTERM as hsflow_solve, from any level;  HSFLOW_E_OOM / HSFLOW_E_DEVICE: the level contexts, or a HIP call
+ * A refusal leaves the context's flow as it was.  A failure inside a level leaves the flow unspecified and the frames the
+ * caller's. */
+int hsflow_solve_pyramid(hsflow_ctx *ctx, const hsflow_params *params, const hsflow_pyramid_params *pp);
+/* What the last pyramid solve did. */
+typedef struct hsflow_pyramid_info {
+    uint32_t struct_size; /* = sizeof(hsflow_pyramid_info), set by the caller */
+    int32_t levels, warps, median_radius;
+    int32_t width[HSFLOW_PYRAMID_MAX_LEVELS], height[HSFLOW_PYRAMID_MAX_LEVELS];
+    int32_t sweeps[HSFLOW_PYRAMID_MAX_LEVELS][HSFLOW_PYRAMID_MAX_WARPS]; /* [level][step]: sweeps of that solve (ITER: max_iter; with EPS: where it stopped) */
+    int32_t solves;          /* levels * warps */
+    int32_t down_launches;   /* k_pyr_down: levels - 1 */
+    int32_t step_launches;   /* k_pyr_step: solves - 1 */
+    int32_t total_launches;  /* k_pyr_total */
+    int32_t median_launches; /* the median kernel, on behalf of the pyramid */
+    int32_t reserved[3];
+} hsflow_pyramid_info;
+/* HSFLOW_E_ARG: out NULL or its struct_size wrong; HSFLOW_E_STATE: no pyramid solve has succeeded on this context. */
+int hsflow_get_pyramid_info(hsflow_ctx *ctx, hsflow_pyramid_info *out);
+/* Synchronous copy-out of one level after the last pyramid solve: its frames (curr is the ORIGINAL curr_l, not the warped
+ * one) and its total flow, for one pair.  Each pointer may be NULL; strides in bytes (flow: multiples of 4).  This is what
+ * lets a caller say which level went wrong.  HSFLOW_E_ARG: level or pair out of range; HSFLOW_E_SIZE: a stride smaller than
+ * the level's row; HSFLOW_E_STATE: the context's last solve was not a successful pyramid solve.  (Level 0's planes are the
+ * context's own: what changed them since shows.) */
+int hsflow_pyramid_get_level(hsflow_ctx *ctx, int level, int pair, uint8_t *prev, size_t prev_stride, uint8_t *curr, size_t curr_stride, float *u,
+                             size_t u_stride, float *v, size_t v_stride);
 
 /* Planner introspection, no device needed: the kernel, sweeps per launch, tile shape, workgroup size,
  * tiles per launch, LDS bytes and launch count hsflow_solve would use for a context of this size with

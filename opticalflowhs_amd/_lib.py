@@ -24,6 +24,7 @@ MEDIAN_UNFILLED, MEDIAN_KEPT, MEDIAN_FILLED = 0, 1, 2
 MEDIAN_MAX_PASSES = 64  # HSFLOW_MEDIAN_MAX_PASSES
 INTERP_BLENDED, INTERP_PREV_ONLY, INTERP_CURR_ONLY, INTERP_CLAMPED = 0, 1, 2, 3
 INTERP_BATCH_MAX = 8  # HSFLOW_INTERP_BATCH_MAX
+PYRAMID_MAX_LEVELS, PYRAMID_MAX_WARPS = 8, 8  # HSFLOW_PYRAMID_MAX_LEVELS, HSFLOW_PYRAMID_MAX_WARPS
 JPEG_ORDER_BGR, JPEG_ORDER_RGB = 0, 1
 JPEGD_SUBSEQ_BITS = 1024  # HSFLOW_JPEGD_SUBSEQ_BITS
 JPEGD_BATCH_MAX = 32  # HSFLOW_JPEGD_BATCH_MAX
@@ -110,6 +111,18 @@ class HsflowInterpStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class HsflowPyramidParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("levels", ctypes.c_int32), ("min_size", ctypes.c_int32), ("warps", ctypes.c_int32),
+                ("median_radius", ctypes.c_int32)]
+
+
+class HsflowPyramidInfo(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("levels", ctypes.c_int32), ("warps", ctypes.c_int32), ("median_radius", ctypes.c_int32),
+                ("width", ctypes.c_int32 * PYRAMID_MAX_LEVELS), ("height", ctypes.c_int32 * PYRAMID_MAX_LEVELS),
+                ("sweeps", (ctypes.c_int32 * PYRAMID_MAX_WARPS) * PYRAMID_MAX_LEVELS), ("solves", ctypes.c_int32), ("down_launches", ctypes.c_int32),
+                ("step_launches", ctypes.c_int32), ("total_launches", ctypes.c_int32), ("median_launches", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
 class HsflowPlaneDiff(ctypes.Structure):
     _fields_ = [("differing", ctypes.c_uint64), ("failing", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64),
                 ("first_failing", ctypes.c_int64), ("max_abs_diff", ctypes.c_float), ("max_ulp", ctypes.c_uint32)]
@@ -161,6 +174,7 @@ _mp = ctypes.POINTER(HsflowMedianParams)
 _ms = ctypes.POINTER(HsflowMedianStats)
 _np = ctypes.POINTER(HsflowInterpParams)
 _ns = ctypes.POINTER(HsflowInterpStats)
+_yp = ctypes.POINTER(HsflowPyramidParams)
 _f = ctypes.c_float
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
@@ -254,6 +268,13 @@ PROTOTYPES = {
     "hsflow_interp_device": (_i, [_vp, _i, _f, _np, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_interp": (_i, [_vp, _i, _f, _np, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _ns]),
     "hsflow_project_flow_device": (_i, [_vp, _i, _f, _np, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_default_pyramid_params": (None, [_yp]),
+    "hsflow_pyramid_plan": (_i, [_i, _i, _yp, _ip, _ip, _ip]),
+    "hsflow_pyramid_down_host": (_i, [_vp, _sz, _i, _i, _vp, _sz]),
+    "hsflow_pyramid_prolong_host": (_i, [_vp, _sz, _i, _i, _vp, _sz]),
+    "hsflow_solve_pyramid": (_i, [_vp, _pp, _yp]),
+    "hsflow_get_pyramid_info": (_i, [_vp, ctypes.POINTER(HsflowPyramidInfo)]),
+    "hsflow_pyramid_get_level": (_i, [_vp, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
     "hsflow_jpeg_read_header": (_i, [_vp, _sz, _ji]),
     "hsflow_jpeg_decode_host": (_i, [_vp, _sz, _i, _vp, _sz, _ji]),
     "hsflow_jpeg_decode_device": (_i, [_vp, _vp, _sz, _i, _vp, _sz, _vp]),

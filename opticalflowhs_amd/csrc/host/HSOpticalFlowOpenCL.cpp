@@ -274,6 +274,38 @@ int median_choice(int &radius, int &passes, bool &fill)
     return 1;
 }
 
+// HSFLOW_PYRAMID=<levels 1 .. 8 | auto>[,<warps 1 .. 8>[,<median radius 0 .. 2>]] on the "-cv -hd" routes: the solve is the
+// coarse-to-fine solve (hsflow_solve_pyramid) with the route's parameters at every level; whatever HSFLOW_PICTURE and
+// HSFLOW_MEDIAN ask for works on its flow.  0: not set, 1: usable, -1: unusable.
+int pyramid_choice(hsflow_pyramid_params &pp)
+{
+    hsflow_default_pyramid_params(&pp);
+    const char *e = getenv("HSFLOW_PYRAMID");
+    if (!e || !*e) return 0;
+    const char *q = e;
+    char *rest = nullptr;
+    if (strncmp(q, "auto", 4) == 0) {
+        rest = const_cast<char *>(q) + 4;
+    } else {
+        const long l = strtol(q, &rest, 10);
+        if (rest == q || l < 1 || l > HSFLOW_PYRAMID_MAX_LEVELS) return -1;
+        pp.levels = (int)l;
+    }
+    if (!*rest) return 1;
+    if (*rest != ',') return -1;
+    q = rest + 1;
+    const long w = strtol(q, &rest, 10);
+    if (rest == q || w < 1 || w > HSFLOW_PYRAMID_MAX_WARPS) return -1;
+    pp.warps = (int)w;
+    if (!*rest) return 1;
+    if (*rest != ',') return -1;
+    q = rest + 1;
+    const long r = strtol(q, &rest, 10);
+    if (rest == q || *rest || r < 0 || r > 2) return -1;
+    pp.median_radius = (int)r;
+    return 1;
+}
+
 // The filter of pair 0's flow in place; u, v (host copies of the flow, or null) are read again behind it.
 int median_step(hsflow_ctx *ctx, int W, int H, std::vector<float> *u, std::vector<float> *v)
 {
@@ -394,7 +426,15 @@ bool picture_choice_usable()
     int radius, passes;
     bool fill;
     if (median_choice(radius, passes, fill) < 0) { std::cout << "HSFLOW_MEDIAN must be <radius 1 or 2>[,<passes 1 .. 64>[,fill]]" << std::endl; return false; }
+    hsflow_pyramid_params pp;
+    if (pyramid_choice(pp) < 0) { std::cout << "HSFLOW_PYRAMID must be <levels 1 .. 8 or auto>[,<warps 1 .. 8>[,<median radius 0, 1 or 2>]]" << std::endl; return false; }
     return true;
+}
+
+bool pyramid_wanted()
+{
+    hsflow_pyramid_params pp;
+    return pyramid_choice(pp) == 1;
 }
 
 bool median_wanted()
@@ -673,7 +713,9 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     const bool on_device = render_on_device();
     std::vector<float> u, v;
     if (!on_device) { u.resize((size_t)W * H); v.resize((size_t)W * H); }
-    if (st == HSFLOW_OK) st = hsflow_solve(ctx, &p);
+    hsflow_pyramid_params pyr;
+    const bool pyramid = pyramid_choice(pyr) == 1; // HSFLOW_PYRAMID: the coarse-to-fine solve in the solve's place
+    if (st == HSFLOW_OK) st = pyramid ? hsflow_solve_pyramid(ctx, &p, &pyr) : hsflow_solve(ctx, &p);
     if (st == HSFLOW_OK && !on_device) st = hsflow_get_flow(ctx, 0, u.data(), (size_t)W * 4, v.data(), (size_t)W * 4);
     const double ms = now_ms() - t0;
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; hsflow_destroy(ctx); return 1; }

@@ -86,6 +86,8 @@ bool interp_wanted();
 // HSFLOW_MEDIAN=<radius>[,<passes>[,fill]]: the flow is median-filtered, or its untrusted pixels filled, in place before
 // the picture is drawn (the two "-hd" routes only).
 bool median_wanted();
+// HSFLOW_PYRAMID=<levels|auto>[,<warps>[,<median radius>]]: the solve is hsflow_solve_pyramid (the "-cv -hd" routes only).
+bool pyramid_wanted();
 
 // GPU counterpart of the reference's CPU route (OpticalFlowHS/OpticalFlowOpenCV.hpp:6-11):
 // gray -> 3x3 box blur -> Horn-Schunck(lambda, ITER|EPS, eps 1e-6) -> arrows, all but the file I/O

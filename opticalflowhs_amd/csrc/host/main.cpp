@@ -38,6 +38,11 @@
 // is the state, only the untrusted pixels are replaced by the median of their trusted neighbours, and one line "median:
 // kept .. filled .. unfilled .. newly_filled .. changed .." tells the record of the last pass.  A bad value: a message
 // and exit status 1.
+// HSFLOW_PYRAMID=<levels 1 .. 8 | auto>[,<warps 1 .. 8>[,<median radius 0 .. 2>]] (-cv -hd, from PPM / PGM or from JPEG files):
+// the solve becomes the coarse-to-fine solve (hsflow_solve_pyramid: every level solved with the route's lambda and
+// iteration count), for motions of many pixels; every HSFLOW_PICTURE and HSFLOW_MEDIAN behind it works on its flow.  On
+// -cam and on -cl, and for a bad value: a message and exit status 1.  (HSFLOW_VERIFY=1 reports "Failed" for it: a pyramid's
+// flow is no single solve to re-run.)
 // HSFLOW_VERIFY=1: every solved pair is verified on the device (hsflow_verify: re-solved sweep by sweep, compared
 // there) before its context goes away; one "Passed!" / "Failed" line per pair on stdout, the pictures are written as
 // always, and the exit status is SDK_FAILURE if any pair failed.
@@ -82,6 +87,7 @@ int main(int argc, char *argv[])
     if (fb_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=fb needs a pair of files (-hd)\n"; return 1; }
     if (interp_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=interp needs a pair of files (-hd)\n"; return 1; }
     if (median_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_MEDIAN needs a pair of files (-hd)\n"; return 1; }
+    if (pyramid_wanted() && argc >= 3 && (strcmp(argv[2], "-cam") == 0 || strcmp(argv[1], "-cl") == 0)) { std::cout << "HSFLOW_PYRAMID needs the CV route on a pair of files (-cv -hd)\n"; return 1; }
     if (argc >= 3 && strcmp(argv[1], "-cl") == 0) {
         if (strcmp(argv[2], "-hd") == 0) {
             if (argc != 10) { std::cout << "Wrong argument list!\n"; return 0; }

@@ -93,6 +93,8 @@ struct PlanEntry {
 
 } // namespace
 
+struct HsPyramid; // hs_pyramid.hip.h
+
 struct hsflow_ctx {
     int device = 0;
     int W = 0, H = 0, N = 0, P = 0;
@@ -241,7 +243,7 @@ struct hsflow_ctx {
     // neither the frames nor the stream); the comparison records on the device and in page-locked memory; the event behind
     // their copy
     hsflow_params vparams;
-    int vstate = 0;             // 0: no solve yet, 1: the last solve succeeded, 2: it failed
+    int vstate = 0;             // 0: no solve yet, 1: the last solve succeeded, 2: it failed, 3: it was a pyramid solve (hs_pyramid.hip.h)
     int last_status = 0;        // ... and what it returned (hsflow_get_pair_result on a batch that stops as one)
     bool v_per_pair = false;    // ... and whether its pairs stopped each on its own
     int v_org = 0, v_eps_row0 = 0, v_eps_rows = 0; // row origin and Eps rows that solve ran with
@@ -328,6 +330,9 @@ struct hsflow_ctx {
         size_t stage_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
         hsflow_interp_stats *dStats = nullptr, *hStats = nullptr;
     } interp;
+    // hsflow_solve_pyramid (hs_pyramid.hip.h): the level contexts and planes of the last plan, allocated by the first
+    // pyramid solve and kept.  NULL on a context that never ran one.
+    HsPyramid *pyr = nullptr;
 };
 
 namespace {

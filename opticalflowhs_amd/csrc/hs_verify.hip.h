@@ -200,6 +200,7 @@ int hsflow_verify(hsflow_ctx *c, int pair, hsflow_verify_report *report)
     }
     if (c->vstate == 0) return fail(c, HSFLOW_E_STATE, "hsflow_verify: no solve yet on this context");
     if (c->vstate == 2) return fail(c, HSFLOW_E_STATE, "hsflow_verify: the last solve failed (or ended in HSFLOW_E_NOTERM): there is nothing to verify");
+    if (c->vstate == 3) return fail(c, HSFLOW_E_STATE, "hsflow_verify: the last solve was a pyramid solve: the flow held is no single solve of the context's frames");
     if (c->vparams.use_previous)
         return fail(c, HSFLOW_E_STATE, "hsflow_verify: the last solve continued from an earlier flow (use_previous = 1); that starting flow is gone, "
                                        "warm starts cannot be verified");

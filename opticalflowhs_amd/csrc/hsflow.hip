@@ -16,6 +16,7 @@
 #include "hs_kernels_fb.hip.h"
 #include "hs_kernels_median.hip.h"
 #include "hs_kernels_interp.hip.h"
+#include "hs_kernels_pyramid.hip.h"
 #include "hs_kernels_verify.hip.h"
 #include "hs_kernels_jpeg.hip.h"
 #include "hs_kernels_jpegd.hip.h"
@@ -43,7 +44,7 @@
 #include "hs_solve.hip.h"
 
 
-namespace { void jpeg_release(hsflow_ctx *c); void jpegd_release(hsflow_ctx *c); void postops_release(hsflow_ctx *c); } // hs_jpeg.hip.h, hs_jpegd.hip.h, hs_postops.hip.h
+namespace { void jpeg_release(hsflow_ctx *c); void jpegd_release(hsflow_ctx *c); void postops_release(hsflow_ctx *c); void pyramid_release(hsflow_ctx *c); } // hs_jpeg.hip.h, hs_jpegd.hip.h, hs_postops.hip.h, hs_pyramid.hip.h
 
 extern "C" {
 
@@ -222,6 +223,7 @@ int hsflow_destroy(hsflow_ctx *c)
     hipSetDevice(c->device);
     if (c->stream || !c->own_stream) hipStreamSynchronize(c->stream);
     if (c->shadow) { hsflow_destroy(c->shadow); c->shadow = nullptr; } // hsflow_verify's scratch
+    pyramid_release(c);                                                 // hsflow_solve_pyramid's level contexts
     if (c->borrowed) c->dA = c->dB = nullptr;                           // (the owner's frames)
     hipFree(c->dCmp);
     if (c->hCmp) hipHostFree(c->hCmp);
@@ -911,6 +913,7 @@ void hsflow_release_cached(void)
 #include "hs_fb.hip.h"     // hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_default_fb_params
 #include "hs_median.hip.h" // hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_default_median_params
 #include "hs_interp.hip.h" // hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host / _device, hsflow_default_interp_params
+#include "hs_pyramid.hip.h" // hsflow_solve_pyramid, hsflow_pyramid_plan / _down_host / _prolong_host / _get_level, hsflow_get_pyramid_info, hsflow_default_pyramid_params
 #include "hs_verify.hip.h" // hsflow_verify, hsflow_compare_flow_device, hsflow_compare_planes_host
 #include "hs_jpeg.hip.h"   // hsflow_jpeg_bound, hsflow_jpeg_encode_host / _device, hsflow_render_flow_jpeg[_device]
 #include "hs_jpegd.hip.h"  // hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg

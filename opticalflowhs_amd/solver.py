@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -345,6 +345,18 @@ def make_median_params(radius=1, mode="filter", min_votes=1):
     return mp
 
 
+def make_pyramid_params(levels=0, min_size=32, warps=1, median_radius=0):
+    """hsflow_pyramid_params: levels 0 ("auto": as many as keep the smaller side >= min_size, at most 8) or 1 .. 8 as given;
+    warps 1 .. 8 steps per level; median_radius 0 (none), 1 or 2: a 3x3 / 5x5 median of every total.  include/hsflow.h has
+    the scheme."""
+    pp = HsflowPyramidParams()
+    _lib.load().hsflow_default_pyramid_params(ctypes.byref(pp))
+    if levels == "auto":
+        levels = 0
+    pp.levels, pp.min_size, pp.warps, pp.median_radius = int(levels), int(min_size), int(warps), int(median_radius)
+    return pp
+
+
 def _median_call(height, width, device_index, state, flow, state_out, stats, params, radius, mode, min_votes, device):
     """What the median entries share.  state: None or the u8 plane (H, W); flow: False / None (absent), True (allocated
     here) or the pair (u_out, v_out) of float32 planes of one row stride; state_out: False / None, True or the u8 plane;
@@ -542,6 +554,43 @@ class HSFlow(object):
     def solve_async(self, params=None, **kw):
         p = params if params is not None else self.make_params(**kw)
         self._check(self._lib.hsflow_solve_async(self._h, ctypes.byref(p)))
+
+    def solve_pyramid(self, params=None, levels=0, min_size=32, warps=1, median_radius=0, pyramid=None, **kw):
+        """The coarse-to-fine solve of every pair (`hsflow_solve_pyramid`): the frames halved level by level, the coarsest
+        level solved from zero, and at every further step the second frame warped by the flow so far and the increment
+        solved for, every solve with `params` (or make_params(**kw)).  levels, min_size, warps, median_radius as
+        `make_pyramid_params` takes them (or pyramid: an HsflowPyramidParams).  The flow of level 0 is then the context's
+        flow.  With ITER termination only enqueued.  Returns `pyramid_info()`."""
+        p = params if params is not None else self.make_params(**kw)
+        pp = pyramid if pyramid is not None else make_pyramid_params(levels, min_size, warps, median_radius)
+        self._check(self._lib.hsflow_solve_pyramid(self._h, ctypes.byref(p), ctypes.byref(pp)))
+        return self.pyramid_info()
+
+    def pyramid_info(self):
+        """What the last pyramid solve did: levels, warps, median_radius, sizes [(width, height)] per level, sweeps
+        [level][step], solves, and the launches of the pyramid's kernels."""
+        i = HsflowPyramidInfo()
+        i.struct_size = ctypes.sizeof(HsflowPyramidInfo)
+        self._check(self._lib.hsflow_get_pyramid_info(self._h, ctypes.byref(i)))
+        n = i.levels
+        return {"levels": n, "warps": i.warps, "median_radius": i.median_radius, "sizes": [(i.width[l], i.height[l]) for l in range(n)],
+                "sweeps": [[i.sweeps[l][k] for k in range(i.warps)] for l in range(n)], "solves": i.solves, "down_launches": i.down_launches,
+                "step_launches": i.step_launches, "total_launches": i.total_launches, "median_launches": i.median_launches}
+
+    def pyramid_level(self, level, pair=0):
+        """One level after the last pyramid solve: (prev, curr, u, v) of that level's size -- its frames (curr as `down` made
+        it, not the warped one) and its total flow.  Complete on return."""
+        i = HsflowPyramidInfo()
+        i.struct_size = ctypes.sizeof(HsflowPyramidInfo)
+        self._check(self._lib.hsflow_get_pyramid_info(self._h, ctypes.byref(i)))
+        if not 0 <= level < i.levels:
+            raise ValueError("level out of range")
+        w, h = i.width[level], i.height[level]
+        a, b = np.empty((h, w), np.uint8), np.empty((h, w), np.uint8)
+        u, v = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+        self._check(self._lib.hsflow_pyramid_get_level(self._h, int(level), int(pair), _ptr(a), a.strides[0], _ptr(b), b.strides[0], _ptr(u), u.strides[0],
+                                                       _ptr(v), v.strides[0]))
+        return a, b, u, v
 
     def set_eps_rows(self, first_row, rows):
         """Only the changes of rows [first_row, first_row + rows) count for Eps / the witness (rows <= 0: the whole frame)."""
@@ -1136,6 +1185,60 @@ def median_host(u, v, state=None, flow=True, state_out=False, stats=False, radiu
     if st != _lib.OK:
         raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
     return u_out, v_out, state_out, rec
+
+
+def _host_check(st):
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+
+
+def pyramid_plan(width, height, levels=0, min_size=32, warps=1, median_radius=0, params=None):
+    """The level sizes `HSFlow.solve_pyramid` would use for a width x height context (`hsflow_pyramid_plan`, no GPU work): a
+    list of (width, height), level 0 first."""
+    pp = params if params is not None else make_pyramid_params(levels, min_size, warps, median_radius)
+    n = ctypes.c_int(0)
+    ws, hs_ = (ctypes.c_int * _lib.PYRAMID_MAX_LEVELS)(), (ctypes.c_int * _lib.PYRAMID_MAX_LEVELS)()
+    _host_check(_lib.load().hsflow_pyramid_plan(int(width), int(height), ctypes.byref(pp), ctypes.byref(n), ws, hs_))
+    return [(ws[l], hs_[l]) for l in range(n.value)]
+
+
+def _rows_as_they_are(a, dtype):
+    a = np.asarray(a, dtype)
+    item = np.dtype(dtype).itemsize
+    return a if a.ndim == 2 and a.strides[1] == item and a.strides[0] % item == 0 and a.strides[0] >= a.shape[1] * item else np.ascontiguousarray(a)
+
+
+def pyramid_down_host(img, out=None):
+    """A uint8 frame (H, W) at half the size, (ceil(H/2), ceil(W/2)), by the pyramid's rule on the host
+    (`hsflow_pyramid_down_host`, no GPU work); padded rows are taken as they are.  out: a uint8 array of that shape (its
+    row stride is used), else a new one."""
+    img = _rows_as_they_are(img, np.uint8)
+    if img.ndim != 2:
+        raise ValueError("img must be a 2-D uint8 array")
+    H, W = img.shape
+    if out is None:
+        out = np.empty(((H + 1) // 2, (W + 1) // 2), np.uint8)
+    if out.dtype != np.uint8 or out.shape != ((H + 1) // 2, (W + 1) // 2) or (out.shape[1] > 1 and out.strides[1] != 1):
+        raise ValueError("out must be a uint8 array of shape (ceil(H/2), ceil(W/2)) with dense rows")
+    _host_check(_lib.load().hsflow_pyramid_down_host(_ptr(img), img.strides[0] if H > 1 else max(img.strides[0], W), W, H, _ptr(out),
+                                                     out.strides[0] if out.shape[0] > 1 else max(out.strides[0], out.shape[1])))
+    return out
+
+
+def pyramid_prolong_host(coarse, width, height, out=None):
+    """A coarse float32 plane (ceil(height/2), ceil(width/2)) at the fine size (height, width), doubled, by the pyramid's
+    rule on the host (`hsflow_pyramid_prolong_host`, no GPU work); padded rows are taken as they are."""
+    coarse = _rows_as_they_are(coarse, np.float32)
+    width, height = int(width), int(height)
+    if coarse.ndim != 2 or coarse.shape != ((height + 1) // 2, (width + 1) // 2):
+        raise ValueError("coarse must be a 2-D float32 array of shape (ceil(height/2), ceil(width/2))")
+    if out is None:
+        out = np.empty((height, width), np.float32)
+    if out.dtype != np.float32 or out.shape != (height, width) or (width > 1 and out.strides[1] != 4):
+        raise ValueError("out must be a float32 array of shape (height, width) with dense rows")
+    _host_check(_lib.load().hsflow_pyramid_prolong_host(_ptr(coarse), coarse.strides[0] if coarse.shape[0] > 1 else max(coarse.strides[0], 4 * coarse.shape[1]),
+                                                        width, height, _ptr(out), out.strides[0] if height > 1 else max(out.strides[0], 4 * width)))
+    return out
 
 
 def interp_stats_from(stats, n=1):
