@@ -56,6 +56,10 @@
  *                                          no counterpart in the reference: the frame at time t between the two frames of
  *                                          a pair (frame-rate conversion) -- the forward flow projected to t, holes
  *                                          filled, both frames fetched and blended with occlusion -- where the flow lies
+ *   hsflow_chain_flow[_host|_device], hsflow_chain_planes_device, hsflow_track_points[_host|_device]
+ *                                          no counterpart in the reference: pixels and points followed through the flows
+ *                                          of a whole sequence of pairs -- the accumulated flow from the first frame to
+ *                                          the last, point tracks -- where the flows lie
  *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
  *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
  *                                          the pictures are decoded on the device
@@ -91,7 +95,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 21 /* 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 22 /* 0.22: hsflow_chain_flow[_host|_device], hsflow_chain_planes_device, hsflow_track_points[_host|_device], hsflow_default_chain_params, hsflow_chain_params, hsflow_chain_stats, HSFLOW_CHAIN_*; 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -1258,6 +1262,128 @@ int hsflow_interp(hsflow_ctx *ctx, int pair, float t, const hsflow_interp_params
 int hsflow_project_flow_device(hsflow_ctx *ctx, int pair, float t, const hsflow_interp_params *ip, const void *d_prev, size_t prev_stride,
                                const void *d_curr, size_t curr_stride, void *d_u_out /* or NULL */, void *d_v_out /* or NULL */, size_t out_stride,
                                void *d_state_out /* or NULL */, size_t state_out_stride, hsflow_interp_stats *d_stats /* or NULL */);
+
+/* --- pixels and points followed through a sequence of flows (ABI 0.22) -------------------------- */
+
+/* A context holds a whole sequence (hsflow_set_sequence_*: N + 1 frames in N pairs), and every operator above works on
+ * one pair.  These entries say where a pixel of frame 0 is in frame n: long-range correspondence, accumulated camera
+ * motion, point tracks.  Composition is not the sum of the planes -- the vector of pair k is read where the pixel has
+ * ARRIVED in frame k (on a field that rotates by 0.02 rad per pair, 96x64, eight pairs, 8 x flow is off by up to 0.60 px,
+ * the chain by 1.1e-6 px).  Done where the flows lie, in ONE launch with the trajectory in registers, without a read-back
+ * of 2 n fp32 planes.  No counterpart in the reference.  The rule is csrc/hs_chain_rule.h, one header for the kernels and
+ * the host forms; device and host give the same bits.  All arithmetic is fp32, every operation rounded on its own (fl).
+ *   Flow planes (u_k, v_k), k = 0 .. n-1, all W x H, n = 1 .. HSFLOW_CHAIN_MAX_PAIRS.  Optional state planes s_k (u8,
+ *   non-zero = trusted: the default mask of hsflow_fb as it is; a NULL list or a NULL entry: no test for that plane).
+ *   One step, advance(a, b, x, y, k), where (a, b) is what was accumulated and (x, y) where it started:
+ *   1. UNKNOWN (3) iff the colour picture's test says so of (a, b) (NaN, or a magnitude above 1e9);
+ *   2. fx = fl((float)x + a), fy = fl((float)y + b); LEFT (1) iff !(fx >= 0 && fx <= W-1 && fy >= 0 && fy <= H-1);
+ *   3. x0 = (int)floorf(fx), x1 = min(x0 + 1, W-1), ax = fl(fx - (float)x0); y0, y1, ay alike (the warp's taps with t = 1).
+ *      UNKNOWN iff any of the four taps of (u_k, v_k) is not known, even where its weight is 0;
+ *   4. UNTRUSTED (2) iff plane k has a state plane and any of its four taps is zero;
+ *   5. c = the bilinear sample of u_k in the warp's order (hsflow_fb, step 4), d of v_k; a' = fl(a + c), b' = fl(b + d);
+ *      UNKNOWN iff (a', b') is not known, else ALIVE (0) with (a', b').
+ *   Dense chain, pixel (x, y): WITHOUT start planes the start is (u_0, v_0)[y][x] verbatim -- no sampling, no addition, so
+ *   n = 1 is a copy, -0.0 included -- UNKNOWN if not known, else UNTRUSTED if s_0[y][x] == 0, and the pixel advances through
+ *   planes 1 .. n-1.  WITH start planes (U0, V0) the start is (U0, V0)[y][x], UNKNOWN if not known, no state is tested at
+ *   the start, and the pixel advances through all of 0 .. n-1.  The first class other than ALIVE is final; the walk ends.
+ *   Outputs, each may be absent, but at least one must be asked for; U and V together or not at all:
+ *     U, V    fp32 planes: the accumulated flow from frame 0 to frame n; the quiet NaN 0x7fc00000 in both where the pixel
+ *             is not ALIVE.  The last plane's vector may point outside the frame: only "known" is asked of the result, so
+ *             an ALIVE pixel is known to the colour picture;
+ *     status  a u8 plane, value[class]; with the default {255, 0, 0, 0} it is a state plane for hsflow_median* and
+ *             hsflow_interp* as it is;
+ *     age     a u8 plane: the number of planes of this call the pixel passed (n iff ALIVE; the verbatim start is plane 0);
+ *     stats   exact integers that do not depend on the order of execution: cls[4], the class counts (they sum to W*H);
+ *             sum_age; max_mag2_bits, the bit pattern of the largest fl(fl(U*U) + fl(V*V)) over ALIVE, 0 if there are none.
+ *   A longer chain continues from the U, V of the call before through the start planes: 32 + k planes in two calls are,
+ *   bit for bit, what one walk through all of them gives at every pixel that is ALIVE after the first call.  Pixels lost
+ *   in the first call carry the NaN and come back UNKNOWN from the second, whatever their class was.
+ *   Points: a point is a position (px, py) in frame 0, two floats.  UNKNOWN if not known; else it advances through ALL n
+ *   planes with advance(px, py, 0, 0, k), so what accumulates is the position.  Row j of the track (m points of two floats)
+ *   is the position after j planes for j <= age and the NaN bits beyond; row 0 is the start as given.  last: the position
+ *   after n planes, the NaN bits unless ALIVE.  For points max_mag2_bits is the squared distance from the start,
+ *   fl(fl(dx*dx) + fl(dy*dy)) with dx = fl(px_n - px_0), over ALIVE.  m = 1 .. 2^24.
+ * Rows of U and V beyond width floats and of status and age beyond width bytes are left alone.
+ * Not covered: the tickets of a pair pipeline, hsflow_multi_* and slabs.  A pipeline user takes the
+ * hsflow_pipeline_flow_device pointers after hsflow_pipeline_wait and calls hsflow_chain_planes_device on a context of
+ * their own.
+ * Time on an MI355X (profiles/chain_time.txt): U and V through 8 pairs of 1080p flows in 0.105 ms (0.147 ms
+ * with status and statistics) -- 0.62 x the seven mask-only hsflow_fb_planes_device launches that do the same gathers,
+ * 27 x a device-to-device copy of two planes, 2200 x faster than reading the pairs back and chaining on the host (236 ms);
+ * 32 pairs in 0.626 ms; 0.023 ms for 8 pairs at 600x480.  262 144 points with full tracks through 8 pairs in 0.026 ms. */
+#define HSFLOW_CHAIN_MAX_PAIRS 32
+#define HSFLOW_CHAIN_ALIVE 0
+#define HSFLOW_CHAIN_LEFT 1
+#define HSFLOW_CHAIN_UNTRUSTED 2
+#define HSFLOW_CHAIN_UNKNOWN 3
+typedef struct hsflow_chain_params {
+    uint32_t struct_size; /* = sizeof(hsflow_chain_params)              */
+    uint8_t value[4];     /* the status byte for class HSFLOW_CHAIN_*    */
+    int32_t reserved[2];  /* 0                                           */
+} hsflow_chain_params;
+typedef struct hsflow_chain_stats { /* 64 bytes, the same on the device and on the host */
+    uint64_t cls[4], sum_age;
+    uint32_t max_mag2_bits;
+    uint8_t reserved[20];
+} hsflow_chain_stats;
+/* value {255, 0, 0, 0}: a confidence mask.  NULL is ignored. */
+void hsflow_default_chain_params(hsflow_chain_params *cp);
+/* The rule on the host, no device needed: u, v: n planes each of width x height floats, rows flow_stride BYTES apart (one
+ * stride for all); state: NULL or n entries, each NULL or a plane of rows state_stride bytes apart; U0, V0: the start
+ * planes (rows start_stride bytes apart) or both NULL.  U, V, status, age and stats may each be null.
+ * HSFLOW_E_ARG: null cp, wrong struct_size, n out of 1 .. 32, a null list or list entry of u or v, a flow plane that is not
+ * 4-byte aligned, one start plane without the other, one of U and V without the other, nothing asked for, an output that
+ * overlaps an input plane; HSFLOW_E_SIZE: a non-positive size, a float stride below 4*width or no multiple of 4, a byte
+ * stride below width. */
+int hsflow_chain_flow_host(int n, const float *const *u, const float *const *v, size_t flow_stride, const uint8_t *const *state /* may be null */,
+                           size_t state_stride, int width, int height, const float *U0 /* may be null */, const float *V0, size_t start_stride,
+                           const hsflow_chain_params *cp, float *U /* may be null */, float *V, size_t out_stride, uint8_t *status /* may be null */,
+                           size_t status_stride, uint8_t *age /* may be null */, size_t age_stride, hsflow_chain_stats *stats /* may be null */);
+/* Points by the rule on the host: xy[m][2] in; track[n + 1][m][2], last[m][2], status[m], age[m] and stats may each be
+ * null, not all.  Errors as above, and HSFLOW_E_ARG: m out of 1 .. 2^24, null xy, a float array that is not 4-byte aligned. */
+int hsflow_track_points_host(int n, const float *const *u, const float *const *v, size_t flow_stride, const uint8_t *const *state /* may be null */,
+                             size_t state_stride, int width, int height, const hsflow_chain_params *cp, const float *xy, int m, float *track, float *last,
+                             uint8_t *status, uint8_t *age, hsflow_chain_stats *stats);
+/* The dense chain of n planes anywhere on ctx's device, of the context's width and height: d_u, d_v (and d_state) are
+ * host arrays of n device pointers, free on return.  Only enqueued on ctx's stream: one launch, with statistics a memset
+ * of the record in front of it.  The outputs are those of hsflow_chain_flow_host from the same planes.  The flow planes,
+ * the start planes, d_U and d_V are 4-byte aligned and their strides multiples of 4 (16-byte alignment of base and stride
+ * lets the kernel move 16 bytes at a time); status and age may have any alignment; d_stats a multiple of 8 (the counters
+ * are 64-bit atomics).  The caller orders the producers of the planes before ctx's stream.
+ * The ordering rules of hsflow_fb_batch_device apply word for word: an ITER|EPS check that hsflow_solve_async still owes
+ * is settled first, and on a context with hsflow_set_async_reduce hsflow_wait_solve and hsflow_flow_view_device called
+ * after it wait for the stream.  Nothing is allocated.  Every argument is checked before anything is enqueued.
+ * HSFLOW_E_ARG and HSFLOW_E_SIZE as hsflow_chain_flow_host, and HSFLOW_E_ARG: d_stats no multiple of 8. */
+int hsflow_chain_planes_device(hsflow_ctx *ctx, int n, const void *const *d_u, const void *const *d_v, size_t flow_stride,
+                               const void *const *d_state /* n or NULL; a NULL entry: no test for that plane */, size_t state_stride,
+                               const void *d_U0, const void *d_V0, size_t start_stride /* or NULL, NULL */, const hsflow_chain_params *cp, void *d_U,
+                               void *d_V, size_t out_stride, void *d_status, size_t status_stride, void *d_age, size_t age_stride,
+                               hsflow_chain_stats *d_stats);
+/* The same through the context's own flows: plane k is the flow of pair pairs[k] (a host array of n, free on return; any
+ * pair may appear any number of times).  The flow is read and never changed; after a solve with
+ * hsflow_set_pair_termination every pair contributes its own final flow.  The outputs may not lie in the context's flow
+ * planes.  HSFLOW_E_ARG also: null pairs, a pair out of range. */
+int hsflow_chain_flow_device(hsflow_ctx *ctx, const int *pairs, int n, const void *const *d_state, size_t state_stride, const void *d_U0,
+                             const void *d_V0, size_t start_stride, const hsflow_chain_params *cp, void *d_U, void *d_V, size_t out_stride,
+                             void *d_status, size_t status_stride, void *d_age, size_t age_stride, hsflow_chain_stats *d_stats);
+/* The same with state planes and start planes from host memory and the results in host memory, synchronous: complete on
+ * return.  Waits only for an event behind its own work, like hsflow_fb -- except in a call that has to allocate: the
+ * staging is allocated by the first call that needs a piece, grown to the largest so far and kept until hsflow_destroy
+ * (hsflow_release_cached for the one-shot's context).  Contexts that never chain pay nothing. */
+int hsflow_chain_flow(hsflow_ctx *ctx, const int *pairs, int n, const uint8_t *const *state, size_t state_stride, const float *U0, const float *V0,
+                      size_t start_stride, const hsflow_chain_params *cp, float *U, float *V, size_t out_stride, uint8_t *status, size_t status_stride,
+                      uint8_t *age, size_t age_stride, hsflow_chain_stats *stats);
+/* m points through the context's own flows, everything in device memory: d_xy[m][2] in; d_track[n + 1][m][2], d_last[m][2],
+ * d_status[m], d_age[m], d_stats each may be NULL, not all.  One launch, one lane per point; the float arrays are 4-byte
+ * aligned (8-byte alignment lets the kernel move a point at a time).  Ordering, allocation and errors as
+ * hsflow_chain_flow_device, and HSFLOW_E_ARG: m out of 1 .. 2^24, null d_xy, a misaligned float array, an output that
+ * overlaps the points, a state plane or the context's flow. */
+int hsflow_track_points_device(hsflow_ctx *ctx, const int *pairs, int n, const void *const *d_state, size_t state_stride,
+                               const hsflow_chain_params *cp, const float *d_xy, int m, float *d_track, float *d_last, uint8_t *d_status,
+                               uint8_t *d_age, hsflow_chain_stats *d_stats);
+/* The same from and to host memory, synchronous like hsflow_chain_flow. */
+int hsflow_track_points(hsflow_ctx *ctx, const int *pairs, int n, const uint8_t *const *state, size_t state_stride, const hsflow_chain_params *cp,
+                        const float *xy, int m, float *track, float *last, uint8_t *status, uint8_t *age, hsflow_chain_stats *stats);
 
 /* --- the input files (cvLoadImage) ---------------------------------------------------------- */
 

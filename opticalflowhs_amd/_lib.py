@@ -19,6 +19,8 @@ RENDER_CV, RENDER_CL = 0, 1
 COLOR_SCALE_AUTO, COLOR_SCALE_FIXED = 0, 1
 WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE = 0, 1
 FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE, FB_UNKNOWN = 0, 1, 2, 3
+CHAIN_ALIVE, CHAIN_LEFT, CHAIN_UNTRUSTED, CHAIN_UNKNOWN = 0, 1, 2, 3  # HSFLOW_CHAIN_*
+CHAIN_MAX_PAIRS = 32  # HSFLOW_CHAIN_MAX_PAIRS
 MEDIAN_FILTER, MEDIAN_FILL = 0, 1
 MEDIAN_UNFILLED, MEDIAN_KEPT, MEDIAN_FILLED = 0, 1, 2
 MEDIAN_MAX_PASSES = 64  # HSFLOW_MEDIAN_MAX_PASSES
@@ -86,6 +88,17 @@ class HsflowFbParams(ctypes.Structure):
 class HsflowFbStats(ctypes.Structure):
     _fields_ = [("consistent", ctypes.c_uint64), ("inconsistent", ctypes.c_uint64), ("outside", ctypes.c_uint64), ("unknown", ctypes.c_uint64),
                 ("sum_err2_q", ctypes.c_uint64), ("max_err2_bits", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 20)]
+
+
+class HsflowChainParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("value", ctypes.c_uint8 * 4), ("reserved", ctypes.c_int32 * 2)]
+
+
+class HsflowChainStats(ctypes.Structure):
+    _fields_ = [("cls", ctypes.c_uint64 * 4), ("sum_age", ctypes.c_uint64), ("max_mag2_bits", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 20)]
+
+
+assert ctypes.sizeof(HsflowChainParams) == 16 and ctypes.sizeof(HsflowChainStats) == 64
 
 
 class HsflowMedianParams(ctypes.Structure):
@@ -175,6 +188,8 @@ _ms = ctypes.POINTER(HsflowMedianStats)
 _np = ctypes.POINTER(HsflowInterpParams)
 _ns = ctypes.POINTER(HsflowInterpStats)
 _yp = ctypes.POINTER(HsflowPyramidParams)
+_hp = ctypes.POINTER(HsflowChainParams)
+_hs = ctypes.POINTER(HsflowChainStats)
 _f = ctypes.c_float
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
@@ -269,6 +284,14 @@ PROTOTYPES = {
     "hsflow_interp": (_i, [_vp, _i, _f, _np, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _ns]),
     "hsflow_project_flow_device": (_i, [_vp, _i, _f, _np, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
     "hsflow_default_pyramid_params": (None, [_yp]),
+    "hsflow_default_chain_params": (None, [_hp]),
+    "hsflow_chain_flow_host": (_i, [_i, _vp, _vp, _sz, _vp, _sz, _i, _i, _vp, _vp, _sz, _hp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _hs]),
+    "hsflow_track_points_host": (_i, [_i, _vp, _vp, _sz, _vp, _sz, _i, _i, _hp, _vp, _i, _vp, _vp, _vp, _vp, _hs]),
+    "hsflow_chain_planes_device": (_i, [_vp, _i, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _hp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_chain_flow_device": (_i, [_vp, _ip, _i, _vp, _sz, _vp, _vp, _sz, _hp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_chain_flow": (_i, [_vp, _ip, _i, _vp, _sz, _vp, _vp, _sz, _hp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _hs]),
+    "hsflow_track_points_device": (_i, [_vp, _ip, _i, _vp, _sz, _hp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "hsflow_track_points": (_i, [_vp, _ip, _i, _vp, _sz, _hp, _vp, _i, _vp, _vp, _vp, _vp, _hs]),
     "hsflow_pyramid_plan": (_i, [_i, _i, _yp, _ip, _ip, _ip]),
     "hsflow_pyramid_down_host": (_i, [_vp, _sz, _i, _i, _vp, _sz]),
     "hsflow_pyramid_prolong_host": (_i, [_vp, _sz, _i, _i, _vp, _sz]),

@@ -758,6 +758,37 @@ static int camera_batch()
     return *rest || v < 1 || v > 256 ? -1 : (int)v;
 }
 
+// HSFLOW_CAMERA_CHAIN=1 on the batched "-cv -cam" route: beside the flow_%04d.ppm files every batch writes chain_%04d.ppm
+// (numbered like the flow picture of its last pair), the colour picture (AUTO scale) of the flow from the batch's first frame
+// to its last -- every pixel followed through the batch's flows (hsflow_chain_flow).  0: not set (or "0"); -1: unusable.
+static int camera_chain()
+{
+    const char *e = getenv("HSFLOW_CAMERA_CHAIN");
+    if (!e || !*e || strcmp(e, "0") == 0) return 0;
+    return strcmp(e, "1") == 0 ? 1 : -1;
+}
+
+// The chained flow of ctx's m pairs into U, V (W x H, packed): HSFLOW_CHAIN_MAX_PAIRS pairs per call, a longer batch
+// continues from the call before through the start planes.
+static int chain_batch(hsflow_ctx *ctx, int m, int W, int H, std::vector<float> &U, std::vector<float> &V)
+{
+    hsflow_chain_params cp;
+    hsflow_default_chain_params(&cp);
+    const size_t px = (size_t)W * H, row = (size_t)W * 4;
+    std::vector<float> U0, V0;
+    U.resize(px); V.resize(px);
+    for (int first = 0; first < m; first += HSFLOW_CHAIN_MAX_PAIRS) {
+        const int n = m - first < HSFLOW_CHAIN_MAX_PAIRS ? m - first : HSFLOW_CHAIN_MAX_PAIRS;
+        int pairs[HSFLOW_CHAIN_MAX_PAIRS];
+        for (int k = 0; k < n; k++) pairs[k] = first + k;
+        if (first) { U0.swap(U); V0.swap(V); U.resize(px); V.resize(px); }
+        const int st = hsflow_chain_flow(ctx, pairs, n, nullptr, 0, first ? U0.data() : nullptr, first ? V0.data() : nullptr, row, &cp, U.data(), V.data(), row,
+                                         nullptr, 0, nullptr, 0, nullptr);
+        if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+    }
+    return SDK_SUCCESS;
+}
+
 static bool ends_with_jpg(const std::string &s) { return s.size() >= 4 && s.compare(s.size() - 4, 4, ".jpg") == 0; }
 
 // The same loop with up to n + 1 frames read ahead: ONE hsflow_set_sequence_* call and ONE hsflow_solve per batch on a
@@ -767,7 +798,7 @@ static bool ends_with_jpg(const std::string &s) { return s.size() >= 4 && s.comp
 // there (| HSFLOW_SEQ_REBLUR_FIRST).  A tail of m < n pairs gets a context of m pairs.  Gray frames are uploaded as they
 // are; with HSFLOW_JPEG_IN_DEVICE=1 and nothing but .jpg frames the files go to the device undecoded.  The flow_%04d.ppm
 // files are byte for byte those of the loop below.
-static int run_camera_batched(float lambda, int it, int nb)
+static int run_camera_batched(float lambda, int it, int nb, bool chain)
 {
     struct Frame {
         pnm::Image gray;           // the gray frame, or
@@ -874,6 +905,22 @@ static int run_camera_batched(float lambda, int it, int nb)
                 pnm::save_image(std::string(getenv("HSFLOW_CAMERA_OUT")) + name, imgFlow);
             }
         }
+        if (chain && getenv("HSFLOW_CAMERA_OUT")) {
+            std::vector<float> cu, cv;
+            if (chain_batch(ctx, m, W, H, cu, cv) != SDK_SUCCESS) return done(1);
+            pnm::Image imgChain;
+            imgChain.width = W; imgChain.height = H; imgChain.channels = 3;
+            imgChain.data.resize((size_t)W * H * 3);
+            hsflow_color_params cp;
+            hsflow_default_color_params(&cp); // (AUTO: the picture's own largest flow)
+            if (hsflow_color_flow_host(cu.data(), (size_t)W * 4, cv.data(), (size_t)W * 4, W, H, &cp, imgChain.data.data(), (size_t)W * 3, nullptr) != HSFLOW_OK) {
+                std::cout << hsflow_last_error(nullptr) << std::endl;
+                return done(1);
+            }
+            char name[64];
+            snprintf(name, sizeof(name), "/chain_%04d.ppm", count + m);
+            pnm::save_image(std::string(getenv("HSFLOW_CAMERA_OUT")) + name, imgChain);
+        }
         count += m;
         Frame last = std::move(batch.back()); // imgOld = imgNew :118, across the batches
         batch.clear();
@@ -886,10 +933,13 @@ static int run_camera_batched(float lambda, int it, int nb)
 
 int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
 {
+    const int chain = camera_chain();
+    if (chain < 0) { std::cout << "HSFLOW_CAMERA_CHAIN must be 0 or 1" << std::endl; return 1; }
     if (const int nb = camera_batch()) {
         if (nb < 0) { std::cout << "HSFLOW_CAMERA_BATCH must be 1 .. 256" << std::endl; return 1; }
-        return run_camera_batched(lambda, it, nb);
+        return run_camera_batched(lambda, it, nb, chain == 1);
     }
+    if (chain) { std::cout << "HSFLOW_CAMERA_CHAIN needs HSFLOW_CAMERA_BATCH=1 .. 256" << std::endl; return 1; }
     pnm::Image frame, gold, gnew;
     if (!pnm::load_image(camera_frame(0), frame)) { std::cout << "ERROR: capture is NULL \n"; return -1; }
     pnm::to_gray(frame, gold);                                   // cvCvtColor(imgTmp, imgOld, CV_BGR2GRAY) :79

@@ -333,6 +333,15 @@ struct hsflow_ctx {
     // hsflow_solve_pyramid (hs_pyramid.hip.h): the level contexts and planes of the last plan, allocated by the first
     // pyramid solve and kept.  NULL on a context that never ran one.
     HsPyramid *pyr = nullptr;
+    // hsflow_chain_flow / hsflow_track_points (hs_chain.hip.h): the staging of the synchronous forms -- the callers' state
+    // planes, start planes or points on the device and the results before they are copied out, each slot allocated by the
+    // first call that needs it and grown to the largest so far -- one statistics record on the device and one in page-locked
+    // memory.  The device forms take the caller's memory and allocate nothing.
+    struct ChainScratch {
+        uint8_t *stage[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        size_t stage_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
+        hsflow_chain_stats *dStats = nullptr, *hStats = nullptr;
+    } chain;
 };
 
 namespace {

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowChainParams, HsflowChainStats, CHAIN_MAX_PAIRS, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -329,6 +329,74 @@ def _fb_call(height, width, device_index, mask, err2, stats, params, alpha, beta
     fp = params if params is not None else make_fb_params(alpha, beta, values)
     rec, sref = _stats_record(HsflowFbStats, stats, device, device_index)
     return device, (ctypes.byref(fp), mp, ms, ep, es, sref), mask, err2, rec
+
+
+def make_chain_params(values=(255, 0, 0, 0)):
+    """hsflow_chain_params of a chain: `values` is the status byte for the classes alive, left, untrusted, unknown."""
+    cp = HsflowChainParams()
+    _lib.load().hsflow_default_chain_params(ctypes.byref(cp))
+    levels = [int(x) for x in values]
+    if len(levels) != 4 or any(not 0 <= x <= 255 for x in levels):
+        raise ValueError("values must be 4 levels of 0 .. 255")
+    for k, x in enumerate(levels):
+        cp.value[k] = x
+    return cp
+
+
+def _chain_list(planes, n, height, width, dtype, what, device, holes=False):
+    """(pointer array, the one row stride) of the n planes of a chain, (None, 0) for None; holes: entries may be None."""
+    if planes is None:
+        return None, 0
+    if len(planes) != n:
+        raise ValueError("%s must hold one plane per pair of the chain" % what)
+    got = [(None, 0) if (x is None and holes) else _plane(x, height, width, dtype, what, device) for x in planes]
+    strides = set(g[1] for g, x in zip(got, planes) if x is not None)
+    if len(strides) > 1:
+        raise ValueError("the planes of %s share one row stride" % what)
+    return (ctypes.c_void_p * n)(*[g[0].value if g[0] is not None else None for g in got]), (strides.pop() if strides else 0)
+
+
+def _chain_device(device, *groups):
+    """device=True, or any plane in `groups` (planes, None / True / False, or sequences of them) is a CUDA tensor."""
+    def walk(x):
+        if isinstance(x, (list, tuple)):
+            return any(walk(y) for y in x)
+        return _is_device_tensor(x)
+    return bool(device) or walk(groups)
+
+
+def _chain_call(height, width, device_index, n, state, start, flow, status, age, stats, params, device):
+    """What the dense chain entries share from the state list on: (the C call's arguments, U, V, status, age, stats)."""
+    def fresh(dtype):
+        if device:
+            import torch
+            return torch.empty((height, width), dtype=getattr(torch, dtype), device="cuda:%d" % device_index)
+        return np.empty((height, width), dtype)
+    sl, ss = _chain_list(state, n, height, width, "uint8", "state", device, holes=True)
+    U0p = V0p = None
+    s0s = 0
+    if start is not None:
+        (U0p, s0s), (V0p, vs) = [_plane(x, height, width, "float32", "start", device) for x in start]
+        if s0s != vs:
+            raise ValueError("the two start planes share one row stride")
+    U = V = Up = Vp = None
+    os_ = 0
+    if flow is True:
+        U, V = fresh("float32"), fresh("float32")
+    elif flow:
+        U, V = flow
+    if U is not None:
+        (Up, os_), (Vp, vs) = [_plane(x, height, width, "float32", "flow output", device) for x in (U, V)]
+        if os_ != vs:
+            raise ValueError("the two flow outputs share one row stride")
+    outs = []
+    for x, what in ((status, "status"), (age, "age")):
+        x = fresh("uint8") if x is True else (None if x is None or x is False else x)
+        outs.append((x,) + (_plane(x, height, width, "uint8", what, device) if x is not None else (None, 0)))
+    (status, stp, sts), (age, agp, ags) = outs
+    cp = params if params is not None else make_chain_params()
+    rec, sref = _stats_record(HsflowChainStats, stats, device, device_index)
+    return (sl, ss, U0p, V0p, s0s, ctypes.byref(cp), Up, Vp, os_, stp, sts, agp, ags, sref), U, V, status, age, rec
 
 
 def make_median_params(radius=1, mode="filter", min_votes=1):
@@ -858,6 +926,75 @@ class HSFlow(object):
                                                      ml, ms, el, es, sref))
         return mask, err2, stats
 
+    def _chain_pairs(self, pairs):
+        pairs = list(range(self.n_pairs)) if pairs is None else [int(p) for p in pairs]
+        if not 1 <= len(pairs) <= CHAIN_MAX_PAIRS:
+            raise ValueError("a chain takes 1 .. %d pairs; a longer one continues through `start`" % CHAIN_MAX_PAIRS)
+        return pairs, (ctypes.c_int * len(pairs))(*pairs)
+
+    def chain_flow(self, pairs=None, state=None, start=None, flow=True, status=False, age=False, stats=False, params=None, device=False):
+        """The flow from the first frame of the sequence to the last: every pixel followed through the flows of `pairs`
+        (None: all pairs of the context in order; at most 32, repeats allowed) by `hsflow_chain_flow[_device]`;
+        include/hsflow.h has the rule.  state: None or a list with one entry per pair, each None or a u8 plane (H, W), non-zero
+        = trusted (the masks of `fb`); start: None or the pair (U0, V0) a call before left -- a longer chain in two calls;
+        flow: False, True (allocated here) or the pair (U, V) to fill; status, age: False, True or the u8 plane; stats: True
+        for the statistics.  Host planes: synchronous.  CUDA tensors (or device=True): only enqueued on the context's stream,
+        the statistics then a CUDA uint8 tensor of 64 bytes that `chain_stats_from` reads.  Returns (U, V, status, age,
+        stats), None for what was not asked for."""
+        pairs, ints = self._chain_pairs(pairs)
+        device = _chain_device(device, state, start, flow, status, age)
+        args, U, V, status, age, rec = _chain_call(self.height, self.width, self.device, len(pairs), state, start, flow, status, age, stats, params, device)
+        self._check((self._lib.hsflow_chain_flow_device if device else self._lib.hsflow_chain_flow)(self._h, ints, len(pairs), *args))
+        return U, V, status, age, rec
+
+    def chain_planes_device(self, u, v, state=None, start=None, flow=True, status=False, age=False, stats=False, params=None):
+        """`chain_flow` on the device through caller planes (`hsflow_chain_planes_device`): u, v lists of n CUDA float32
+        tensors (H, W) of one row stride -- other contexts' `flow_view_device`, or flows from elsewhere, ordered before this
+        context's stream by the caller.  Only enqueued."""
+        n = len(u)
+        if len(v) != n or not 1 <= n <= CHAIN_MAX_PAIRS:
+            raise ValueError("u and v hold one plane each per pair, 1 .. %d pairs" % CHAIN_MAX_PAIRS)
+        (ul, us), (vl, vs) = [_chain_list(x, n, self.height, self.width, "float32", "flow", True) for x in (u, v)]
+        if us != vs:
+            raise ValueError("all flow planes share one row stride")
+        args, U, V, status, age, rec = _chain_call(self.height, self.width, self.device, n, state, start, flow, status, age, stats, params, True)
+        self._check(self._lib.hsflow_chain_planes_device(self._h, n, ul, vl, us, *args))
+        return U, V, status, age, rec
+
+    def track_points(self, xy, pairs=None, state=None, track=False, status=False, age=False, stats=False, device=False, params=None):
+        """The points xy -- float32 (m, 2), positions (x, y) in the first frame -- followed through the flows of `pairs`
+        (`hsflow_track_points[_device]`).  track: True for the positions after 0 .. n pairs as float32 (n + 1, m, 2), the NaN
+        bits from the step at which a point was lost; status, age: True for the u8 arrays (m,); stats: True for the
+        statistics.  A NumPy xy: synchronous; a CUDA tensor (or device=True with one): only enqueued.  Returns (last, track,
+        status, age, stats) with last the float32 (m, 2) positions in the last frame, NaN for lost points."""
+        pairs, ints = self._chain_pairs(pairs)
+        n = len(pairs)
+        device = _chain_device(device, xy, state)
+        if device != _is_device_tensor(xy) or (not device and not isinstance(xy, np.ndarray)):
+            raise ValueError("xy must be %s" % ("a CUDA tensor" if device else "a NumPy array"))
+        if str(xy.dtype) not in ("float32", "torch.float32") or xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] < 1:
+            raise ValueError("xy must be float32 of shape (m, 2)")
+        if not (xy.is_contiguous() if device else xy.flags.c_contiguous):
+            raise ValueError("xy must be contiguous")
+        m = int(xy.shape[0])
+
+        def fresh(shape, dtype):
+            if device:
+                import torch
+                return torch.empty(shape, dtype=getattr(torch, dtype), device="cuda:%d" % self.device)
+            return np.empty(shape, dtype)
+        sl, ss = _chain_list(state, n, self.height, self.width, "uint8", "state", device, holes=True)
+        last = fresh((m, 2), "float32")
+        track = fresh((n + 1, m, 2), "float32") if track else None
+        status = fresh((m,), "uint8") if status else None
+        age = fresh((m,), "uint8") if age else None
+        cp = params if params is not None else make_chain_params()
+        rec, sref = _stats_record(HsflowChainStats, stats, device, self.device)
+        opt = lambda x: _ptr(x) if x is not None else None
+        self._check((self._lib.hsflow_track_points_device if device else self._lib.hsflow_track_points)(
+            self._h, ints, n, sl, ss, ctypes.byref(cp), _ptr(xy), m, opt(track), _ptr(last), opt(status), opt(age), sref))
+        return last, track, status, age, rec
+
     def median(self, pair=0, state=None, flow=True, state_out=False, stats=False, radius=1, mode="filter", min_votes=1, passes=1, params=None, device=False):
         """The median filter / hole filling of the flow of `pair` (`make_median_params`; include/hsflow.h has the rule); the
         context's flow is not changed.  state: None or the u8 plane (H, W) of input states (0 invalid, 2 filled, else kept:
@@ -1158,6 +1295,61 @@ def fb_host(uf, vf, ub, vb, mask=True, err2=False, stats=False, alpha=0.01, beta
     if st != _lib.OK:
         raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
     return mask, err2, rec
+
+
+def chain_stats_from(stats):
+    """The `HsflowChainStats` record a device call left in the CUDA uint8 tensor `stats` (after `synchronize()`)."""
+    return HsflowChainStats.from_buffer_copy(stats.cpu().numpy().tobytes()[:ctypes.sizeof(HsflowChainStats)])
+
+
+def _chain_host_planes(u, v):
+    """The flow planes of a host chain as float32 arrays of one shape and ONE row stride (copied where they are not)."""
+    if len(u) != len(v) or not 1 <= len(u) <= CHAIN_MAX_PAIRS:
+        raise ValueError("u and v hold one plane each per pair, 1 .. %d pairs" % CHAIN_MAX_PAIRS)
+    planes = [np.asarray(x, np.float32) for x in list(u) + list(v)]
+    if planes[0].ndim != 2 or any(a.shape != planes[0].shape for a in planes):
+        raise ValueError("the flow planes must be 2-D arrays of one shape")
+    if any(a.strides[1] != 4 or a.strides[0] % 4 or a.strides[0] != planes[0].strides[0] for a in planes):
+        planes = [np.ascontiguousarray(a) for a in planes]
+    n = len(u)
+    ptrs = lambda part: (ctypes.c_void_p * n)(*[a.ctypes.data for a in part])
+    return planes, n, ptrs(planes[:n]), ptrs(planes[n:]), planes[0].strides[0]
+
+
+def chain_flow_host(u, v, state=None, start=None, flow=True, status=False, age=False, stats=False, params=None):
+    """The dense chain by the rule on the host (`hsflow_chain_flow_host`, no GPU work): u, v lists of n float32 arrays of
+    one shape (H, W); state, start, flow, status, age, stats as `HSFlow.chain_flow` takes them.  Returns (U, V, status, age,
+    stats) -- bit for bit what `HSFlow.chain_flow` gives from the same flows."""
+    planes, n, ul, vl, fs = _chain_host_planes(u, v)
+    H, W = planes[0].shape
+    args, U, V, status, age, rec = _chain_call(H, W, 0, n, state, start, flow, status, age, stats, params, False)
+    st = _lib.load().hsflow_chain_flow_host(n, ul, vl, fs, args[0], args[1], W, H, *args[2:])
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return U, V, status, age, rec
+
+
+def track_points_host(u, v, xy, state=None, track=False, status=False, age=False, stats=False, params=None):
+    """Points by the rule on the host (`hsflow_track_points_host`, no GPU work); arguments and result as
+    `HSFlow.track_points`: (last, track, status, age, stats)."""
+    planes, n, ul, vl, fs = _chain_host_planes(u, v)
+    H, W = planes[0].shape
+    xy = np.ascontiguousarray(xy, np.float32)
+    if xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] < 1:
+        raise ValueError("xy must be float32 of shape (m, 2)")
+    m = xy.shape[0]
+    sl, ss = _chain_list(state, n, H, W, "uint8", "state", False, holes=True)
+    last = np.empty((m, 2), np.float32)
+    track = np.empty((n + 1, m, 2), np.float32) if track else None
+    status = np.empty((m,), np.uint8) if status else None
+    age = np.empty((m,), np.uint8) if age else None
+    cp = params if params is not None else make_chain_params()
+    rec, sref = _stats_record(HsflowChainStats, stats, False, 0)
+    opt = lambda x: _ptr(x) if x is not None else None
+    st = _lib.load().hsflow_track_points_host(n, ul, vl, fs, sl, ss, W, H, ctypes.byref(cp), _ptr(xy), m, opt(track), _ptr(last), opt(status), opt(age), sref)
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return last, track, status, age, rec
 
 
 def median_stats_from(stats, n=1):
