@@ -95,7 +95,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 22 /* 0.22: hsflow_chain_flow[_host|_device], hsflow_chain_planes_device, hsflow_track_points[_host|_device], hsflow_default_chain_params, hsflow_chain_params, hsflow_chain_stats, HSFLOW_CHAIN_*; 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 23 /* 0.23: hsflow_gmotion_fit[_host|_device|_batch_device|_planes_device], hsflow_gmotion_warp[_host|_device], hsflow_gmotion_compose_host, hsflow_gmotion_invert_host, hsflow_default_gmotion_params, hsflow_gmotion_params, hsflow_gmotion_result, HSFLOW_GMOTION_*; 0.22: hsflow_chain_flow[_host|_device], hsflow_chain_planes_device, hsflow_track_points[_host|_device], hsflow_default_chain_params, hsflow_chain_params, hsflow_chain_stats, HSFLOW_CHAIN_*; 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -1384,6 +1384,133 @@ int hsflow_track_points_device(hsflow_ctx *ctx, const int *pairs, int n, const v
 /* The same from and to host memory, synchronous like hsflow_chain_flow. */
 int hsflow_track_points(hsflow_ctx *ctx, const int *pairs, int n, const uint8_t *const *state, size_t state_stride, const hsflow_chain_params *cp,
                         const float *xy, int m, float *track, float *last, uint8_t *status, uint8_t *age, hsflow_chain_stats *stats);
+
+/* --- camera motion from the flow (0.23) ------------------------------------------------------ */
+
+/* The single global motion that explains a flow field -- the camera's -- fitted where the flow lies, by a trimmed least
+ * squares; with it a mask of the pixels that follow it (or of those that do not: the moving foreground), the flow
+ * relative to the camera, and a picture warped by the model alone (stabilisation).  No counterpart in the reference.  The
+ * rule is csrc/hs_gmotion_rule.h, one header for the kernels and the host forms; device and host give the same bits.
+ *   Model.  p[6], fp32; with X = x - (W-1)/2, Y = y - (H-1)/2:
+ *     mu = fl(fl(p0 + fl(p1 * X)) + fl(p2 * Y)),  mv = fl(fl(p3 + fl(p4 * X)) + fl(p5 * Y))
+ *   TRANSLATION: p1 = p2 = p4 = p5 = 0; SIMILARITY: p1 = p5, p2 = -p4; AFFINE: all six.
+ *   Classes of a pixel with flow (a, b), the first that applies:
+ *     UNKNOWN (3)    the colour picture's test says so (NaN, a magnitude above 1e9), or |a| or |b| above 2048 px;
+ *     UNTRUSTED (2)  a state plane is given and its byte is 0;
+ *     OUTLIER (1) / INLIER (0) by r2 = fl(fl(ru * ru) + fl(rv * rv)) <= T, ru = fl(a - mu), rv = fl(b - mv); equality is an
+ *                    inlier.
+ *   Fit.  `passes` passes (1 .. 8): pass 0 takes every pixel that is neither UNKNOWN nor UNTRUSTED, pass j >= 1 the inliers
+ *   under the model of pass j-1 and the threshold T_j.  Every pass sums exact integers (the flow quantised to 1/256 px,
+ *   ties to even; doubled centred coordinates), so the order of accumulation cannot matter; from the twelve sums the
+ *   model follows in double precision by one fixed sequence of + - * / and is rounded to fp32.
+ *   Threshold.  FIXED: T_j = fl(inlier_px * inlier_px).  AUTO: T_j = max(min_thr2, fl(scale2 * E)), E the upper edge of the
+ *   bin that holds the median of r2 under the model of pass j-1 in an exact histogram of four bins per octave over all
+ *   pixels that are neither UNKNOWN nor UNTRUSTED; one more read of the flow per pass.
+ *   Degenerate sets -- fewer than 3 (AFFINE) or 2 (SIMILARITY) pixels, all on one row, one column or one line -- fall back
+ *   AFFINE -> SIMILARITY -> TRANSLATION -> the zero model (no pixel); the result's flags then carry
+ *   HSFLOW_GMOTION_FLAG_FALLBACK, and HSFLOW_GMOTION_USED(flags) is the kind that was fitted by the last pass.
+ *   Outputs under the model of the last pass and the threshold after it, each may be absent, at least one asked for:
+ *     result  64 bytes: p[6], the threshold, flags, cls[4] (the class counts; they sum to W*H);
+ *     mask    a u8 plane, value[class]; the default {255, 0, 0, 0} is a state plane for hsflow_median*, hsflow_interp* and
+ *             hsflow_chain_* as it is, {0, 255, 0, 0} the moving foreground;
+ *     res_u, res_v  fp32 planes fl(a - mu), fl(b - mv): the motion relative to the camera, ready for hsflow_color_flow*; the
+ *             quiet NaN 0x7fc00000 in both where the pixel is UNKNOWN, and in place of any NaN.  Both or neither.
+ *   Rows of the mask beyond width bytes and of the residual planes beyond width floats are left alone.
+ *   Frames wider or higher than HSFLOW_GMOTION_MAX_SIDE are refused (HSFLOW_E_SIZE): up to there no sum can overflow.
+ *   Warp by a model: dst(x, y) is src sampled by the rule of hsflow_warp with (a, b) = (mu, mv)(x, y) and the warp's t,
+ *   border and fill; statistics as hsflow_warp_stats.  No flow plane is read.  channels 1 or 3, as hsflow_warp.
+ *   Compose and invert work on positions: a model maps the centred position (X, Y) to (X + mu, Y + mv).
+ * Time on an MI355X (profiles/gmotion_time.txt): one 1080p pair, AFFINE, FIXED, in 0.028 ms with one pass and
+ * 0.060 ms with three (AUTO 0.054 / 0.144 ms); mask and residual planes add 0.002 ms; 8 pairs in one batch 0.130 ms for
+ * three passes; 15 x a device-to-device copy of both planes, 392 x faster than reading the flow back and fitting on the
+ * host (23.4 ms).  A 1080p BGR picture warped by a model in 0.0125 ms, 0.92 x hsflow_warp_device. */
+#define HSFLOW_GMOTION_TRANSLATION 0
+#define HSFLOW_GMOTION_SIMILARITY 1
+#define HSFLOW_GMOTION_AFFINE 2
+#define HSFLOW_GMOTION_ZERO 3 /* only as HSFLOW_GMOTION_USED: no pixel to fit */
+#define HSFLOW_GMOTION_THRESHOLD_FIXED 0
+#define HSFLOW_GMOTION_THRESHOLD_AUTO 1
+#define HSFLOW_GMOTION_INLIER 0
+#define HSFLOW_GMOTION_OUTLIER 1
+#define HSFLOW_GMOTION_UNTRUSTED 2
+#define HSFLOW_GMOTION_UNKNOWN 3
+#define HSFLOW_GMOTION_MAX_PASSES 8
+#define HSFLOW_GMOTION_MAX_SIDE 16384
+#define HSFLOW_GMOTION_FLAG_FALLBACK 1u
+#define HSFLOW_GMOTION_USED(flags) (((flags) >> 8) & 3u)
+typedef struct hsflow_gmotion_params {
+    uint32_t struct_size;   /* = sizeof(hsflow_gmotion_params)                      */
+    int32_t model;          /* HSFLOW_GMOTION_TRANSLATION / _SIMILARITY / _AFFINE      */
+    int32_t passes;         /* 1 .. HSFLOW_GMOTION_MAX_PASSES                          */
+    int32_t threshold_mode; /* HSFLOW_GMOTION_THRESHOLD_FIXED / _AUTO                  */
+    float inlier_px;        /* FIXED: finite, > 0, its square finite and > 0           */
+    float scale2;           /* AUTO: in (0, 1e6]                                       */
+    float min_thr2;         /* AUTO: finite, > 0                                       */
+    uint8_t value[4];       /* the mask's byte for class HSFLOW_GMOTION_INLIER ...     */
+    int32_t reserved[2];    /* 0                                                       */
+} hsflow_gmotion_params;
+typedef struct hsflow_gmotion_result { /* 64 bytes, the same on the device and on the host */
+    float p[6];
+    float threshold; /* the T the outputs were classified under */
+    uint32_t flags;  /* HSFLOW_GMOTION_FLAG_FALLBACK | kind used << 8 */
+    uint64_t cls[4];
+} hsflow_gmotion_result;
+/* AFFINE, 3 passes, FIXED with inlier_px 1, scale2 6, min_thr2 1/16, value {255, 0, 0, 0}.  NULL is ignored. */
+void hsflow_default_gmotion_params(hsflow_gmotion_params *gp);
+/* The rule on the host, no device needed: u, v of width x height floats, rows flow_stride BYTES apart; state NULL or a u8
+ * plane.  mask, res_u / res_v and result may each be null, not all.
+ * HSFLOW_E_ARG: null gp, wrong struct_size, unknown model or threshold mode, passes out of 1 .. 8, reserved not 0, a
+ * threshold field of the chosen mode that is not finite or not positive, a null or not 4-byte aligned flow plane, one
+ * residual plane without the other, nothing asked for, an output that overlaps an input;  HSFLOW_E_SIZE: a non-positive
+ * size, a side above 16384, a float stride below 4*width or no multiple of 4, a byte stride below width. */
+int hsflow_gmotion_fit_host(const float *u, const float *v, size_t flow_stride, const uint8_t *state /* may be null */, size_t state_stride, int width,
+                            int height, const hsflow_gmotion_params *gp, uint8_t *mask /* may be null */, size_t mask_stride, float *res_u /* may be null */,
+                            float *res_v, size_t res_stride, hsflow_gmotion_result *result /* may be null */);
+/* Planes anywhere on ctx's device, of the context's width and height -- the U and V of hsflow_chain_planes_device, the
+ * pointers of hsflow_pipeline_flow_device.  Only enqueued on ctx's stream: per pass one accumulation and one solve launch
+ * (AUTO: a histogram and a second solve launch more), then one launch for the outputs; no memset in between.  The outputs
+ * are those of hsflow_gmotion_fit_host from the same planes.  Flow and residual planes are 4-byte aligned, their strides
+ * multiples of 4 (16-byte alignment of base and stride lets the kernels move 16 bytes at a time); byte planes may have any
+ * alignment; d_result a multiple of 8 (the counts are 64-bit atomics).  The caller orders the producers of the planes
+ * before ctx's stream.  The ordering rules of hsflow_fb_batch_device apply word for word.  The kernels' records (1152
+ * bytes per field of the largest batch so far) are allocated by the first call and kept until hsflow_destroy.  Every
+ * argument is checked before anything is enqueued.  Errors as the host form, and HSFLOW_E_ARG: d_result no multiple of 8. */
+int hsflow_gmotion_fit_planes_device(hsflow_ctx *ctx, const void *d_u, const void *d_v, size_t flow_stride, const void *d_state, size_t state_stride,
+                                     const hsflow_gmotion_params *gp, void *d_mask, size_t mask_stride, void *d_res_u, void *d_res_v, size_t res_stride,
+                                     hsflow_gmotion_result *d_result);
+/* The flows of the pairs first_pair .. first_pair + n - 1 of the context by ONE set of launches (32 pairs per set).  d_state,
+ * d_mask, d_res_u, d_res_v: NULL, or host arrays of n device pointers, free on return, whose entries may be NULL (no
+ * state test / no such output for that pair); d_results: NULL or n records.  The flow is read and never changed; no output
+ * may lie in the context's flow planes.  HSFLOW_E_ARG also: n < 1, first_pair < 0, first_pair + n > n_pairs. */
+int hsflow_gmotion_fit_batch_device(hsflow_ctx *ctx, int first_pair, int n, const void *const *d_state, size_t state_stride,
+                                    const hsflow_gmotion_params *gp, void *const *d_mask, size_t mask_stride, void *const *d_res_u, void *const *d_res_v,
+                                    size_t res_stride, hsflow_gmotion_result *d_results);
+/* A batch of one. */
+int hsflow_gmotion_fit_device(hsflow_ctx *ctx, int pair, const void *d_state, size_t state_stride, const hsflow_gmotion_params *gp, void *d_mask,
+                              size_t mask_stride, void *d_res_u, void *d_res_v, size_t res_stride, hsflow_gmotion_result *d_result);
+/* The same with the state plane from host memory and the outputs in host memory, synchronous: complete on return.  Waits
+ * only for an event behind its own work, like hsflow_fb; the staging is allocated by the first call that needs a piece,
+ * grown and kept until hsflow_destroy. */
+int hsflow_gmotion_fit(hsflow_ctx *ctx, int pair, const uint8_t *state, size_t state_stride, const hsflow_gmotion_params *gp, uint8_t *mask,
+                       size_t mask_stride, float *res_u, float *res_v, size_t res_stride, hsflow_gmotion_result *result);
+/* A picture warped by the model (six floats in host memory) on the host: wp, src, ref, dst and stats as hsflow_warp_host.
+ * HSFLOW_E_ARG: a null model or source, a parameter that is not finite, and as hsflow_warp_host; HSFLOW_E_SIZE: a
+ * non-positive size, a side above 16384, a stride below channels*width. */
+int hsflow_gmotion_warp_host(const float *model, int width, int height, const hsflow_warp_params *wp, const uint8_t *src, size_t src_stride,
+                             const uint8_t *ref /* may be null */, size_t ref_stride, uint8_t *dst /* may be null */, size_t dst_stride,
+                             hsflow_warp_stats *stats /* may be null */);
+/* The same on pictures in device memory, of the context's size; only enqueued (one launch, with statistics a memset of the
+ * record in front of it); d_stats a multiple of 8.  Ordering as hsflow_warp_device. */
+int hsflow_gmotion_warp_device(hsflow_ctx *ctx, const float *model, const hsflow_warp_params *wp, const void *d_src, size_t src_stride, const void *d_ref,
+                               size_t ref_stride, void *d_dst, size_t dst_stride, hsflow_warp_stats *d_stats);
+/* The same from and to host memory, synchronous like hsflow_warp. */
+int hsflow_gmotion_warp(hsflow_ctx *ctx, const float *model, const hsflow_warp_params *wp, const uint8_t *src, size_t src_stride, const uint8_t *ref,
+                        size_t ref_stride, uint8_t *dst, size_t dst_stride, hsflow_warp_stats *stats);
+/* out = "first m1, then m2" on positions; in double, rounded to fp32.  out may be m1 or m2.  HSFLOW_E_ARG: a null
+ * pointer, a parameter that is not finite. */
+int hsflow_gmotion_compose_host(const float *m1, const float *m2, float *out);
+/* out = the inverse map of m.  HSFLOW_E_ARG also: the linear part I + [[p1, p2], [p4, p5]] is singular. */
+int hsflow_gmotion_invert_host(const float *m, float *out);
 
 /* --- the input files (cvLoadImage) ---------------------------------------------------------- */
 

@@ -21,6 +21,10 @@ WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE = 0, 1
 FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE, FB_UNKNOWN = 0, 1, 2, 3
 CHAIN_ALIVE, CHAIN_LEFT, CHAIN_UNTRUSTED, CHAIN_UNKNOWN = 0, 1, 2, 3  # HSFLOW_CHAIN_*
 CHAIN_MAX_PAIRS = 32  # HSFLOW_CHAIN_MAX_PAIRS
+GMOTION_TRANSLATION, GMOTION_SIMILARITY, GMOTION_AFFINE, GMOTION_ZERO = 0, 1, 2, 3  # HSFLOW_GMOTION_*
+GMOTION_THRESHOLD_FIXED, GMOTION_THRESHOLD_AUTO = 0, 1
+GMOTION_INLIER, GMOTION_OUTLIER, GMOTION_UNTRUSTED, GMOTION_UNKNOWN = 0, 1, 2, 3
+GMOTION_MAX_PASSES, GMOTION_MAX_SIDE, GMOTION_FLAG_FALLBACK = 8, 16384, 1
 MEDIAN_FILTER, MEDIAN_FILL = 0, 1
 MEDIAN_UNFILLED, MEDIAN_KEPT, MEDIAN_FILLED = 0, 1, 2
 MEDIAN_MAX_PASSES = 64  # HSFLOW_MEDIAN_MAX_PASSES
@@ -99,6 +103,23 @@ class HsflowChainStats(ctypes.Structure):
 
 
 assert ctypes.sizeof(HsflowChainParams) == 16 and ctypes.sizeof(HsflowChainStats) == 64
+
+
+class HsflowGmotionParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("model", ctypes.c_int32), ("passes", ctypes.c_int32), ("threshold_mode", ctypes.c_int32),
+                ("inlier_px", ctypes.c_float), ("scale2", ctypes.c_float), ("min_thr2", ctypes.c_float), ("value", ctypes.c_uint8 * 4),
+                ("reserved", ctypes.c_int32 * 2)]
+
+
+class HsflowGmotionResult(ctypes.Structure):
+    _fields_ = [("p", ctypes.c_float * 6), ("threshold", ctypes.c_float), ("flags", ctypes.c_uint32), ("cls", ctypes.c_uint64 * 4)]
+
+    def as_dict(self):
+        return {"p": [float(x) for x in self.p], "threshold": float(self.threshold), "flags": int(self.flags),
+                "fallback": bool(self.flags & GMOTION_FLAG_FALLBACK), "used": (int(self.flags) >> 8) & 3, "cls": [int(x) for x in self.cls]}
+
+
+assert ctypes.sizeof(HsflowGmotionParams) == 40 and ctypes.sizeof(HsflowGmotionResult) == 64
 
 
 class HsflowMedianParams(ctypes.Structure):
@@ -190,6 +211,8 @@ _ns = ctypes.POINTER(HsflowInterpStats)
 _yp = ctypes.POINTER(HsflowPyramidParams)
 _hp = ctypes.POINTER(HsflowChainParams)
 _hs = ctypes.POINTER(HsflowChainStats)
+_gp = ctypes.POINTER(HsflowGmotionParams)
+_gr = ctypes.POINTER(HsflowGmotionResult)
 _f = ctypes.c_float
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
@@ -292,6 +315,17 @@ PROTOTYPES = {
     "hsflow_chain_flow": (_i, [_vp, _ip, _i, _vp, _sz, _vp, _vp, _sz, _hp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _hs]),
     "hsflow_track_points_device": (_i, [_vp, _ip, _i, _vp, _sz, _hp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "hsflow_track_points": (_i, [_vp, _ip, _i, _vp, _sz, _hp, _vp, _i, _vp, _vp, _vp, _vp, _hs]),
+    "hsflow_default_gmotion_params": (None, [_gp]),
+    "hsflow_gmotion_fit_host": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _gp, _vp, _sz, _vp, _vp, _sz, _gr]),
+    "hsflow_gmotion_fit_planes_device": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _gp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "hsflow_gmotion_fit_batch_device": (_i, [_vp, _i, _i, _vp, _sz, _gp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "hsflow_gmotion_fit_device": (_i, [_vp, _i, _vp, _sz, _gp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "hsflow_gmotion_fit": (_i, [_vp, _i, _vp, _sz, _gp, _vp, _sz, _vp, _vp, _sz, _gr]),
+    "hsflow_gmotion_warp_host": (_i, [_fp, _i, _i, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _ws]),
+    "hsflow_gmotion_warp_device": (_i, [_vp, _fp, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "hsflow_gmotion_warp": (_i, [_vp, _fp, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _ws]),
+    "hsflow_gmotion_compose_host": (_i, [_fp, _fp, _fp]),
+    "hsflow_gmotion_invert_host": (_i, [_fp, _fp]),
     "hsflow_pyramid_plan": (_i, [_i, _i, _yp, _ip, _ip, _ip]),
     "hsflow_pyramid_down_host": (_i, [_vp, _sz, _i, _i, _vp, _sz]),
     "hsflow_pyramid_prolong_host": (_i, [_vp, _sz, _i, _i, _vp, _sz]),

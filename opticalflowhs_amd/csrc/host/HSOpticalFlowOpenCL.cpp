@@ -67,7 +67,7 @@ int picture_kind()
 {
     const char *e = getenv("HSFLOW_PICTURE");
     if (!e || !*e || strcmp(e, "arrows") == 0) return 0;
-    return strcmp(e, "color") == 0 ? 1 : strcmp(e, "warp") == 0 ? 2 : strcmp(e, "fb") == 0 ? 3 : strcmp(e, "interp") == 0 ? 4 : -1;
+    return strcmp(e, "color") == 0 ? 1 : strcmp(e, "warp") == 0 ? 2 : strcmp(e, "fb") == 0 ? 3 : strcmp(e, "interp") == 0 ? 4 : strcmp(e, "stab") == 0 ? 5 : -1;
 }
 
 bool color_picture() { return picture_kind() == 1; }
@@ -123,6 +123,74 @@ int warp_picture(hsflow_ctx *ctx, const pnm::Image &first, const pnm::Image &sec
     if (st != HSFLOW_OK) { std::cout << hsflow_last_error(render_on_device() ? ctx : nullptr) << std::endl; return SDK_FAILURE; }
     std::cout << "warp: inside " << s.inside << " outside " << s.outside << " unknown " << s.unknown << " sad_warped " << s.sad_warped << " sad_plain "
               << s.sad_plain << std::endl;
+    return SDK_SUCCESS;
+}
+
+// HSFLOW_PICTURE=stab on the two "-hd" routes: the file holds the second input warped onto the first by the ONE global motion
+// fitted to the solved flow (hsflow_gmotion_fit*, hsflow_gmotion_warp*) -- the stabilised frame -- not by the dense flow,
+// and one line on stdout tells the model's six parameters and the inliers' share.
+// HSFLOW_GMOTION=<translation|similarity|affine>[,<passes>[,<px>|auto]] selects the fit (default affine,3,1).
+// false: the value is unusable.
+bool gmotion_choice(hsflow_gmotion_params &gp)
+{
+    hsflow_default_gmotion_params(&gp);
+    const char *e = getenv("HSFLOW_GMOTION");
+    if (!e || !*e) return true;
+    const std::string text(e);
+    const size_t c1 = text.find(','), c2 = c1 == std::string::npos ? c1 : text.find(',', c1 + 1);
+    const std::string kind = text.substr(0, c1);
+    if (kind == "translation") gp.model = HSFLOW_GMOTION_TRANSLATION;
+    else if (kind == "similarity") gp.model = HSFLOW_GMOTION_SIMILARITY;
+    else if (kind == "affine") gp.model = HSFLOW_GMOTION_AFFINE;
+    else return false;
+    if (c1 == std::string::npos) return true;
+    const std::string passes = text.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+    char *rest = nullptr;
+    const long n = strtol(passes.c_str(), &rest, 10);
+    if (passes.empty() || *rest || n < 1 || n > HSFLOW_GMOTION_MAX_PASSES) return false;
+    gp.passes = (int)n;
+    if (c2 == std::string::npos) return true;
+    const std::string thr = text.substr(c2 + 1);
+    if (thr == "auto") { gp.threshold_mode = HSFLOW_GMOTION_THRESHOLD_AUTO; return true; }
+    const float px = strtof(thr.c_str(), &rest);
+    if (thr.empty() || *rest || !std::isfinite(px) || !(px > 0.f)) return false;
+    gp.inlier_px = px;
+    return true;
+}
+
+// "<what>: model p0 .. p5 inliers <share of the frame>": the line of HSFLOW_PICTURE=stab and of the chained camera route.
+static std::string gmotion_line(const char *what, const hsflow_gmotion_result &r, int W, int H)
+{
+    char line[256];
+    snprintf(line, sizeof(line), "%s: model %.9g %.9g %.9g %.9g %.9g %.9g inliers %.4f", what, r.p[0], r.p[1], r.p[2], r.p[3], r.p[4], r.p[5],
+             (double)r.cls[0] / ((double)W * H));
+    return line;
+}
+
+// With HSFLOW_RENDER_DEVICE=1 through hsflow_gmotion_fit and hsflow_gmotion_warp (the flow stays on the device), otherwise
+// the host rules on the flow that was read back; the same bytes and the same line.
+int stab_picture(hsflow_ctx *ctx, const pnm::Image &first, const pnm::Image &second, const std::vector<float> &u, const std::vector<float> &v,
+                 pnm::Image &out)
+{
+    const int W = second.width, H = second.height, C = second.channels;
+    if (first.width != W || first.height != H || first.channels != C) { std::cout << "HSFLOW_PICTURE=stab: the two frames differ in kind" << std::endl; return SDK_FAILURE; }
+    out.width = W; out.height = H; out.channels = C;
+    out.data.resize((size_t)W * H * C);
+    hsflow_gmotion_params gp;
+    gmotion_choice(gp);
+    hsflow_warp_params wp;
+    hsflow_default_warp_params(&wp);
+    wp.channels = C;
+    hsflow_gmotion_result r;
+    const size_t rowb = (size_t)W * C;
+    const bool dev = render_on_device();
+    int st = dev ? hsflow_gmotion_fit(ctx, 0, nullptr, 0, &gp, nullptr, 0, nullptr, nullptr, 0, &r)
+                 : hsflow_gmotion_fit_host(u.data(), v.data(), (size_t)W * 4, nullptr, 0, W, H, &gp, nullptr, 0, nullptr, nullptr, 0, &r);
+    if (st == HSFLOW_OK)
+        st = dev ? hsflow_gmotion_warp(ctx, r.p, &wp, second.data.data(), rowb, nullptr, 0, out.data.data(), rowb, nullptr)
+                 : hsflow_gmotion_warp_host(r.p, W, H, &wp, second.data.data(), rowb, nullptr, 0, out.data.data(), rowb, nullptr);
+    if (st != HSFLOW_OK) { std::cout << hsflow_last_error(dev ? ctx : nullptr) << std::endl; return SDK_FAILURE; }
+    std::cout << gmotion_line("stab", r, W, H) << std::endl;
     return SDK_SUCCESS;
 }
 
@@ -378,7 +446,7 @@ int draw_on_device(hsflow_ctx *ctx, int preset, int W, int H, pnm::Image &imgFlo
 bool jpeg_on_device(const std::string &output)
 {
     const char *e = getenv("HSFLOW_JPEG_DEVICE");
-    if (!render_on_device() || !e || atoi(e) == 0 || warp_wanted() || fb_wanted() || interp_wanted()) return false; // (the warped frame, the mask and the intermediate frame are written by the host's encoder)
+    if (!render_on_device() || !e || atoi(e) == 0 || warp_wanted() || fb_wanted() || interp_wanted() || stab_wanted()) return false; // (the warped frame, the mask and the intermediate frame are written by the host's encoder)
     auto ends = [&](const char *x) {
         const size_t n = std::strlen(x);
         if (output.size() < n) return false;
@@ -417,10 +485,12 @@ bool picture_choice_usable()
     hsflow_warp_params wp;
     hsflow_fb_params fp;
     const char *which = nullptr;
-    if (picture_kind() < 0) { std::cout << "HSFLOW_PICTURE must be color, warp, fb, interp or arrows" << std::endl; return false; }
+    if (picture_kind() < 0) { std::cout << "HSFLOW_PICTURE must be color, warp, fb, interp, stab or arrows" << std::endl; return false; }
     if (!fb_params(fp, &which)) { std::cout << which << " must be a finite number >= 0 (alpha at most 1e6, beta at most 1e30)" << std::endl; return false; }
     if (!color_params(cp)) { std::cout << "HSFLOW_COLOR_MAX must be a finite number > 0" << std::endl; return false; }
     if (!warp_params(wp)) { std::cout << "HSFLOW_WARP_T must be a finite number, at most 1e6 in magnitude" << std::endl; return false; }
+    hsflow_gmotion_params gmp;
+    if (!gmotion_choice(gmp)) { std::cout << "HSFLOW_GMOTION must be translation, similarity or affine[,<passes 1..8>[,<px>|auto]]" << std::endl; return false; }
     float t;
     if (!interp_time(t)) { std::cout << "HSFLOW_INTERP_T must be a number in 0 .. 1" << std::endl; return false; }
     int radius, passes;
@@ -454,6 +524,7 @@ static bool reversed_pair_wanted()
 }
 
 bool warp_wanted() { return picture_kind() == 2; }
+bool stab_wanted() { return picture_kind() == 5; }
 
 bool fb_wanted() { return picture_kind() == 3; }
 
@@ -626,6 +697,9 @@ int HSOpticalFlowOpenCL::run()
         if (warp_wanted()) {
             if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; return -1; }
             if (warp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
+        } else if (stab_wanted()) {
+            if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; return -1; }
+            if (stab_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
         } else if (interp_wanted()) {
             if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; return -1; }
             if (interp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) return SDK_FAILURE;
@@ -729,6 +803,9 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     } else if (warp_wanted()) {
         if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; hsflow_destroy(ctx); return -1; }
         if (warp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
+    } else if (stab_wanted()) {
+        if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; hsflow_destroy(ctx); return -1; }
+        if (stab_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     } else if (interp_wanted()) {
         if (from_files && (!pnm::load_image(input1, c1) || !pnm::load_image(input2, c2))) { std::cout << "Input image error.\n"; hsflow_destroy(ctx); return -1; }
         if (interp_picture(ctx, c1, c2, u, v, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
@@ -736,7 +813,7 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
         if (fb_picture(ctx, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     } else if (on_device && draw_on_device(ctx, HSFLOW_RENDER_CV, W, H, imgFlow) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     hsflow_destroy(ctx);
-    if (!on_device && !warp_wanted() && !fb_wanted() && !interp_wanted()) draw_cv_flow(imgFlow, u, v, W, H);
+    if (!on_device && !warp_wanted() && !fb_wanted() && !interp_wanted() && !stab_wanted()) draw_cv_flow(imgFlow, u, v, W, H);
     if (!file_on_device) pnm::save_image(output, imgFlow);
     std::cout << "Avg time: " << ms << " [ms]" << std::endl;
     return verdict;
@@ -760,7 +837,9 @@ static int camera_batch()
 
 // HSFLOW_CAMERA_CHAIN=1 on the batched "-cv -cam" route: beside the flow_%04d.ppm files every batch writes chain_%04d.ppm
 // (numbered like the flow picture of its last pair), the colour picture (AUTO scale) of the flow from the batch's first frame
-// to its last -- every pixel followed through the batch's flows (hsflow_chain_flow).  0: not set (or "0"); -1: unusable.
+// to its last -- every pixel followed through the batch's flows (hsflow_chain_flow) -- and prints one line
+// "chain %04d: model p0 .. p5 inliers <share>", the global motion fitted to that flow (hsflow_gmotion_fit_host; HSFLOW_GMOTION
+// selects the fit).  0: not set (or "0"); -1: unusable.
 static int camera_chain()
 {
     const char *e = getenv("HSFLOW_CAMERA_CHAIN");
@@ -920,6 +999,17 @@ static int run_camera_batched(float lambda, int it, int nb, bool chain)
             char name[64];
             snprintf(name, sizeof(name), "/chain_%04d.ppm", count + m);
             pnm::save_image(std::string(getenv("HSFLOW_CAMERA_OUT")) + name, imgChain);
+            // the camera's motion over the batch: the model of the accumulated flow (HSFLOW_GMOTION selects the fit); the
+            // pixels the chain lost carry NaN and are UNKNOWN to the fit
+            hsflow_gmotion_params gp;
+            gmotion_choice(gp);
+            hsflow_gmotion_result r;
+            if (hsflow_gmotion_fit_host(cu.data(), cv.data(), (size_t)W * 4, nullptr, 0, W, H, &gp, nullptr, 0, nullptr, nullptr, 0, &r) != HSFLOW_OK) {
+                std::cout << hsflow_last_error(nullptr) << std::endl;
+                return done(1);
+            }
+            snprintf(name, sizeof(name), "chain %04d", count + m);
+            std::cout << gmotion_line(name, r, W, H) << std::endl;
         }
         count += m;
         Frame last = std::move(batch.back()); // imgOld = imgNew :118, across the batches

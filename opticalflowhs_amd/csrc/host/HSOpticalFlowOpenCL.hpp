@@ -77,6 +77,8 @@ public:
 bool picture_choice_usable();
 // HSFLOW_PICTURE=warp: the file is the motion-compensated second frame (the two "-hd" routes only).
 bool warp_wanted();
+// HSFLOW_PICTURE=stab: the file is the second frame warped by the fitted global motion (the two "-hd" routes only).
+bool stab_wanted();
 // HSFLOW_PICTURE=fb: the file is the forward-backward consistency mask of the pair against its reverse (the two "-hd"
 // routes only).
 bool fb_wanted();

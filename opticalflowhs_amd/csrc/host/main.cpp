@@ -19,6 +19,9 @@
 // sad_warped .. sad_plain .." tells the residual; by hsflow_warp_host from the flow read back, with HSFLOW_RENDER_DEVICE=1
 // by hsflow_warp on the device; the same file and line.  HSFLOW_WARP_T=<float>: the fraction of the flow applied (default 1;
 // finite, at most 1e6 in magnitude, else a message and exit status 1).
+// HSFLOW_PICTURE=stab (the two -hd routes): the file is the second input warped onto the first by the ONE global motion fitted
+// to the solved flow (hsflow_gmotion_fit*, hsflow_gmotion_warp*), not by the dense flow; one line tells the model and the
+// inliers' share.  HSFLOW_GMOTION=<translation|similarity|affine>[,<passes>[,<px>|auto]] selects the fit.
 // HSFLOW_PICTURE=fb (the two -hd routes): the pair is solved forwards and, from the same pre-processed frames, backwards
 // (hsflow_set_frames_reversed), and the file is the forward-backward consistency mask (hsflow_fb*: 255 where the two flows
 // cancel, 0 elsewhere) as a gray picture; one line "fb: consistent .. inconsistent .. outside .. unknown .. mse .." tells
@@ -84,6 +87,7 @@ int main(int argc, char *argv[])
     }
     if (!picture_choice_usable()) return 1;
     if (warp_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=warp needs a pair of files (-hd)\n"; return 1; }
+    if (stab_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=stab needs a pair of files (-hd)\n"; return 1; }
     if (fb_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=fb needs a pair of files (-hd)\n"; return 1; }
     if (interp_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_PICTURE=interp needs a pair of files (-hd)\n"; return 1; }
     if (median_wanted() && argc >= 3 && strcmp(argv[2], "-cam") == 0) { std::cout << "HSFLOW_MEDIAN needs a pair of files (-hd)\n"; return 1; }

@@ -342,6 +342,20 @@ struct hsflow_ctx {
         size_t stage_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
         hsflow_chain_stats *dStats = nullptr, *hStats = nullptr;
     } chain;
+    // hsflow_gmotion_* (hs_gmotion.hip.h): the kernels' records (hsk::GmScratch, one per field of the largest batch so far;
+    // zero sums and histograms between calls, `dirty` while a call's launches may have been cut short), allocated by the
+    // first call and grown; the staging of the synchronous forms -- 0 state, 1 mask, 2 / 3 the residual planes, 4 / 5 / 6
+    // source, reference and destination of the model warp -- and one result and one warp statistics record on the device
+    // and in page-locked memory.
+    struct GmotionScratch {
+        void *scr = nullptr;
+        int cap = 0;
+        bool dirty = false;
+        uint8_t *stage[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        size_t stage_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
+        hsflow_gmotion_result *dRes = nullptr, *hRes = nullptr;
+        hsflow_warp_stats *dStats = nullptr, *hStats = nullptr;
+    } gmotion;
 };
 
 namespace {

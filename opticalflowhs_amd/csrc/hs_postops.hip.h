@@ -89,16 +89,22 @@ void stats_release(void *d, void *h)
 }
 
 // The grid of a chunk's launch: cnt pictures of units_x x units_y units each (columns of 1024 pixels x rows, or tiles x
-// tiles), and with statistics (d_stats: the chunk's first record, or NULL) the memset of the chunk's records in front of
-// the launch.  With statistics every workgroup ends in atomics on its picture's one record, which the memory side
-// serialises: up to 8 rows or tiles per workgroup while two workgroups per compute unit remain (hs_kernels_warp.hip.h).
-int stats_grid(hsflow_ctx *c, long long units_x, long long units_y, int cnt, void *d_stats, dim3 *grid)
+// tiles).  With statistics every workgroup ends in atomics on its picture's one record, which the memory side serialises:
+// up to 8 rows or tiles per workgroup while two workgroups per compute unit remain (hs_kernels_warp.hip.h).
+void stats_rows(hsflow_ctx *c, long long units_x, long long units_y, int cnt, bool stats, dim3 *grid)
 {
     const long long cus = c->num_cu > 0 ? c->num_cu : 256;
-    long long per = d_stats ? units_x * units_y * cnt / (2 * cus) : 1;
+    long long per = stats ? units_x * units_y * cnt / (2 * cus) : 1;
     per = per < 1 ? 1 : per > 8 ? 8 : per;
     const long long gy = (units_y + per - 1) / per;
     *grid = dim3((unsigned)units_x, (unsigned)(gy < 65535 ? gy : 65535), (unsigned)cnt);
+}
+
+// The same, and with statistics (d_stats: the chunk's first record, or NULL) the memset of the chunk's records in front of
+// the launch.
+int stats_grid(hsflow_ctx *c, long long units_x, long long units_y, int cnt, void *d_stats, dim3 *grid)
+{
+    stats_rows(c, units_x, units_y, cnt, d_stats != nullptr, grid);
     if (d_stats) HS_HIP(c, hipMemsetAsync(d_stats, 0, kStatsBytes * (size_t)cnt, c->stream));
     return HSFLOW_OK;
 }

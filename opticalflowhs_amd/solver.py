@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowChainParams, HsflowChainStats, CHAIN_MAX_PAIRS, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (HsflowGmotionParams, HsflowGmotionResult, GMOTION_TRANSLATION, GMOTION_SIMILARITY, GMOTION_AFFINE, GMOTION_THRESHOLD_FIXED, GMOTION_THRESHOLD_AUTO, COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowChainParams, HsflowChainStats, CHAIN_MAX_PAIRS, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -329,6 +329,69 @@ def _fb_call(height, width, device_index, mask, err2, stats, params, alpha, beta
     fp = params if params is not None else make_fb_params(alpha, beta, values)
     rec, sref = _stats_record(HsflowFbStats, stats, device, device_index)
     return device, (ctypes.byref(fp), mp, ms, ep, es, sref), mask, err2, rec
+
+
+def make_gmotion_params(model="affine", passes=3, threshold="fixed", inlier_px=1.0, scale2=6.0, min_thr2=0.0625, values=(255, 0, 0, 0)):
+    """hsflow_gmotion_params of a global-motion fit: `model` "translation", "similarity" or "affine" (or the GMOTION_*
+    constant); `passes` 1 .. 8 of the trimmed least squares; `threshold` "fixed" (a pixel is an inlier within `inlier_px`
+    of the model) or "auto" (the squared threshold is `scale2` times the median squared residual, at least `min_thr2`);
+    `values`: the mask's byte for the classes inlier, outlier, untrusted, unknown.  include/hsflow.h has the rule."""
+    gp = HsflowGmotionParams()
+    _lib.load().hsflow_default_gmotion_params(ctypes.byref(gp))
+    if isinstance(model, str):
+        kinds = {"translation": GMOTION_TRANSLATION, "similarity": GMOTION_SIMILARITY, "affine": GMOTION_AFFINE}
+        if model not in kinds:
+            raise ValueError("model must be 'translation', 'similarity' or 'affine'")
+        model = kinds[model]
+    if isinstance(threshold, str):
+        if threshold not in ("fixed", "auto"):
+            raise ValueError("threshold must be 'fixed' or 'auto'")
+        threshold = GMOTION_THRESHOLD_AUTO if threshold == "auto" else GMOTION_THRESHOLD_FIXED
+    gp.model, gp.passes, gp.threshold_mode = int(model), int(passes), int(threshold)
+    gp.inlier_px, gp.scale2, gp.min_thr2 = inlier_px, scale2, min_thr2
+    levels = [int(x) for x in values]
+    if len(levels) != 4 or any(not 0 <= x <= 255 for x in levels):
+        raise ValueError("values must be 4 levels of 0 .. 255")
+    for k, x in enumerate(levels):
+        gp.value[k] = x
+    return gp
+
+
+def _gmotion_call(height, width, device_index, state, mask, residual, result, params, device):
+    """What the global-motion fits share from the state plane on.  state: None or the u8 plane; mask: False / None, True
+    (allocated here) or the u8 plane; residual: False / None, True or the pair (res_u, res_v) of float32 planes of one row
+    stride; result: True or False.  Returns (the C call's arguments, record, mask, res_u, res_v)."""
+    def fresh(dtype):
+        if device:
+            import torch
+            return torch.empty((height, width), dtype=getattr(torch, dtype), device="cuda:%d" % device_index)
+        return np.empty((height, width), dtype)
+    sp, ss = _plane(state, height, width, "uint8", "state", device) if state is not None else (None, 0)
+    mask = fresh("uint8") if mask is True else (None if mask is None or mask is False else mask)
+    mp, ms = _plane(mask, height, width, "uint8", "mask", device) if mask is not None else (None, 0)
+    ru = rv = up = vp = None
+    rs = 0
+    if residual is True:
+        ru, rv = fresh("float32"), fresh("float32")
+    elif residual is not None and residual is not False:
+        ru, rv = residual
+    if ru is not None:
+        (up, rs), (vp, vs) = [_plane(x, height, width, "float32", "residual", device) for x in (ru, rv)]
+        if rs != vs:
+            raise ValueError("the two residual planes share one row stride")
+    gp = params if params is not None else make_gmotion_params()
+    rec, rref = _stats_record(HsflowGmotionResult, result, device, device_index)
+    return (sp, ss, ctypes.byref(gp), mp, ms, up, vp, rs, rref), rec, mask, ru, rv
+
+
+def _gmotion_model(model):
+    """Six floats of a model -- a sequence, an array or an `HsflowGmotionResult` -- as a ctypes array."""
+    if isinstance(model, HsflowGmotionResult):
+        model = list(model.p)
+    vals = [float(x) for x in np.asarray(model, np.float32).reshape(-1)]
+    if len(vals) != 6:
+        raise ValueError("a model has six parameters")
+    return (ctypes.c_float * 6)(*vals)
 
 
 def make_chain_params(values=(255, 0, 0, 0)):
@@ -926,6 +989,67 @@ class HSFlow(object):
                                                      ml, ms, el, es, sref))
         return mask, err2, stats
 
+    def global_motion(self, pair=0, state=None, mask=False, residual=False, result=True, params=None, device=False):
+        """The global motion that explains the current flow of `pair` -- the camera's -- by `hsflow_gmotion_fit[_device]`
+        (`make_gmotion_params`; include/hsflow.h has the rule).  state: None or a u8 plane (H, W), non-zero = trusted (the
+        mask of `fb`); mask: False, True (allocated here) or the u8 plane to fill with the class bytes; residual: False, True
+        or the pair (res_u, res_v): the flow relative to the model.  Host planes: synchronous, the result an
+        `HsflowGmotionResult`.  CUDA tensors (or device=True): only enqueued on the context's stream, the result then a
+        CUDA uint8 tensor of 64 bytes that `gmotion_result_from` reads.  Returns (result, mask, res_u, res_v), None for
+        what was not asked for."""
+        device = _chain_device(device, state, mask, residual)
+        args, rec, mask, ru, rv = _gmotion_call(self.height, self.width, self.device, state, mask, residual, result, params, device)
+        self._check((self._lib.hsflow_gmotion_fit_device if device else self._lib.hsflow_gmotion_fit)(self._h, int(pair), *args))
+        return rec, mask, ru, rv
+
+    def global_motion_planes_device(self, u, v, state=None, mask=False, residual=False, result=True, params=None):
+        """`global_motion` on the device of caller planes u, v (CUDA float32 (H, W), one row stride) -- the U and V of
+        `chain_flow(device=True)`, another context's `flow_view_device` (`hsflow_gmotion_fit_planes_device`).  Only enqueued."""
+        (up, us), (vp, vs) = [_plane(x, self.height, self.width, "float32", "flow", True) for x in (u, v)]
+        if us != vs:
+            raise ValueError("the two flow planes share one row stride")
+        args, rec, mask, ru, rv = _gmotion_call(self.height, self.width, self.device, state, mask, residual, result, params, True)
+        self._check(self._lib.hsflow_gmotion_fit_planes_device(self._h, up, vp, us, *args))
+        return rec, mask, ru, rv
+
+    def global_motion_batch_device(self, first_pair=0, n=None, state=None, mask=None, res_u=None, res_v=None, results=None, params=None):
+        """`global_motion` on the device for the pairs first_pair .. first_pair + n - 1 (n=None: all pairs from first_pair)
+        by one set of launches (`hsflow_gmotion_fit_batch_device`).  state, mask, res_u, res_v: None, or lists of n entries,
+        each None or a CUDA plane (H, W); one row stride per list.  results: None, or a CUDA uint8 tensor of n * 64 bytes
+        (`gmotion_result_from`).  Only enqueued."""
+        first_pair, n = self._batch_range(first_pair, n)
+        H, W = self.height, self.width
+        (sl, ss), (ml, ms) = [_chain_list(x, n, H, W, "uint8", what, True, holes=True) for x, what in ((state, "state"), (mask, "mask"))]
+        (ul, us), (vl, vs) = [_chain_list(x, n, H, W, "float32", "residual", True, holes=True) for x in (res_u, res_v)]
+        if us != vs:
+            raise ValueError("the residual planes share one row stride")
+        gp = params if params is not None else make_gmotion_params()
+        self._check(self._lib.hsflow_gmotion_fit_batch_device(self._h, first_pair, n, sl, ss, ctypes.byref(gp), ml, ms, ul, vl, us,
+                                                               _check_stats_tensor(results, n, HsflowGmotionResult)))
+        return results
+
+    def gmotion_warp(self, model, src, ref=None, out=None, t=1.0, border="constant", fill=0, return_stats=False, params=None, picture=True):
+        """`src` warped backwards by the motion `model` (six floats or an `HsflowGmotionResult`) alone, no flow plane read
+        (`hsflow_gmotion_warp[_device]`); everything else as `warp` takes and returns it."""
+        if src is None:
+            raise ValueError("src is needed")
+        device, args, out, stats = _warp_call(self.height, self.width, self.device, src, ref, out, params, t, border, fill, return_stats, picture)
+        self._check((self._lib.hsflow_gmotion_warp_device if device else self._lib.hsflow_gmotion_warp)(self._h, _gmotion_model(model), *args))
+        return (out, stats) if return_stats else out
+
+    def stabilize(self, src, pair=0, state=None, params=None, t=1.0, border="constant", fill=0, return_model=False):
+        """`src` (the second frame of `pair`, any channels `warp` takes) warped onto the first frame by the fitted global
+        motion of the pair's flow, not by the dense flow: `global_motion` for the model (64 bytes read back), then
+        `gmotion_warp`.  A CUDA `src` stays on the device.  Returns the picture, or with return_model=True (picture,
+        `HsflowGmotionResult`)."""
+        device = _is_device_tensor(src)
+        rec, _, _, _ = self.global_motion(pair=pair, state=state, params=params, device=device)
+        if device:
+            self.synchronize()
+            rec = gmotion_result_from(rec)
+        out = self.gmotion_warp(rec, src, t=t, border=border, fill=fill)
+        return (out, rec) if return_model else out
+
     def _chain_pairs(self, pairs):
         pairs = list(range(self.n_pairs)) if pairs is None else [int(p) for p in pairs]
         if not 1 <= len(pairs) <= CHAIN_MAX_PAIRS:
@@ -1295,6 +1419,68 @@ def fb_host(uf, vf, ub, vb, mask=True, err2=False, stats=False, alpha=0.01, beta
     if st != _lib.OK:
         raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
     return mask, err2, rec
+
+
+def gmotion_result_from(results, n=1):
+    """The `HsflowGmotionResult` records a device call left in the CUDA uint8 tensor `results` (after `synchronize()`):
+    one record for n=1, else a list of n."""
+    raw = results.cpu().numpy().tobytes()
+    size = ctypes.sizeof(HsflowGmotionResult)
+    recs = [HsflowGmotionResult.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(n)]
+    return recs[0] if n == 1 else recs
+
+
+def global_motion_host(u, v, state=None, mask=False, residual=False, result=True, params=None):
+    """The global-motion fit by the rule on the host (`hsflow_gmotion_fit_host`, no GPU work): u, v float32 arrays of one
+    shape (H, W), padded rows taken as they are; state, mask, residual, result as `HSFlow.global_motion` takes them.
+    Returns (result, mask, res_u, res_v) -- bit for bit what `HSFlow.global_motion` gives from the same flow."""
+    u, v = (np.asarray(a, np.float32) for a in (u, v))
+    if u.ndim != 2 or u.shape != v.shape:
+        raise ValueError("u and v must be 2-D arrays of one shape")
+    if any(a.strides[1] != 4 or a.strides[0] % 4 for a in (u, v)) or u.strides[0] != v.strides[0]:
+        u, v = np.ascontiguousarray(u), np.ascontiguousarray(v)
+    H, W = u.shape
+    args, rec, mask, ru, rv = _gmotion_call(H, W, 0, state, mask, residual, result, params, False)
+    st = _lib.load().hsflow_gmotion_fit_host(_ptr(u), _ptr(v), u.strides[0], args[0], args[1], W, H, *args[2:])
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return rec, mask, ru, rv
+
+
+def gmotion_warp_host(model, src, ref=None, out=None, t=1.0, border="constant", fill=0, return_stats=False, params=None, picture=True):
+    """`src` warped backwards by the motion `model` by the rule on the host (`hsflow_gmotion_warp_host`, no GPU work); the
+    pictures and the result as `warp_host`."""
+    if src is None:
+        raise ValueError("src is needed")
+    if picture and out is None:
+        out = np.empty(src.shape, np.uint8)
+    if not picture:
+        out = None
+    H, W = src.shape[:2]
+    (sp, ss), (rp, rs), (op, os_), wp = _warp_args(H, W, src, ref, out, False, params, t, border, fill)
+    stats = HsflowWarpStats()
+    st = _lib.load().hsflow_gmotion_warp_host(_gmotion_model(model), W, H, ctypes.byref(wp), sp, ss, rp, rs, op, os_, ctypes.byref(stats) if return_stats else None)
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return (out, stats) if return_stats else out
+
+
+def gmotion_compose(m1, m2):
+    """The model of "first m1, then m2" on positions (`hsflow_gmotion_compose_host`): float32 (6,)."""
+    out = (ctypes.c_float * 6)()
+    st = _lib.load().hsflow_gmotion_compose_host(_gmotion_model(m1), _gmotion_model(m2), out)
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return np.array(out[:], np.float32)
+
+
+def gmotion_invert(m):
+    """The model of the inverse map (`hsflow_gmotion_invert_host`): float32 (6,); a singular linear part raises."""
+    out = (ctypes.c_float * 6)()
+    st = _lib.load().hsflow_gmotion_invert_host(_gmotion_model(m), out)
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return np.array(out[:], np.float32)
 
 
 def chain_stats_from(stats):
