@@ -60,6 +60,11 @@
  *                                          no counterpart in the reference: pixels and points followed through the flows
  *                                          of a whole sequence of pairs -- the accumulated flow from the first frame to
  *                                          the last, point tracks -- where the flows lie
+ *   hsflow_regions[_host|_device|_batch_device|_planes_device]
+ *                                          no counterpart in the reference: the moving objects of a pair -- the connected
+ *                                          regions of a foreground mask (hsflow_gmotion_fit's, hsflow_fb's), optionally cut
+ *                                          where neighbours move differently, each with its size, box, centroid and mean
+ *                                          motion -- labelled where mask and flow lie; only the records cross PCIe
  *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
  *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
  *                                          the pictures are decoded on the device
@@ -95,7 +100,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 23 /* 0.23: hsflow_gmotion_fit[_host|_device|_batch_device|_planes_device], hsflow_gmotion_warp[_host|_device], hsflow_gmotion_compose_host, hsflow_gmotion_invert_host, hsflow_default_gmotion_params, hsflow_gmotion_params, hsflow_gmotion_result, HSFLOW_GMOTION_*; 0.22: hsflow_chain_flow[_host|_device], hsflow_chain_planes_device, hsflow_track_points[_host|_device], hsflow_default_chain_params, hsflow_chain_params, hsflow_chain_stats, HSFLOW_CHAIN_*; 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 24 /* 0.24: hsflow_regions[_host|_device|_batch_device|_planes_device], hsflow_default_regions_params, hsflow_regions_params, hsflow_regions_record, hsflow_regions_result, HSFLOW_REGIONS_*; 0.23: hsflow_gmotion_fit[_host|_device|_batch_device|_planes_device], hsflow_gmotion_warp[_host|_device], hsflow_gmotion_compose_host, hsflow_gmotion_invert_host, hsflow_default_gmotion_params, hsflow_gmotion_params, hsflow_gmotion_result, HSFLOW_GMOTION_*; 0.22: hsflow_chain_flow[_host|_device], hsflow_chain_planes_device, hsflow_track_points[_host|_device], hsflow_default_chain_params, hsflow_chain_params, hsflow_chain_stats, HSFLOW_CHAIN_*; 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -1511,6 +1516,104 @@ int hsflow_gmotion_warp(hsflow_ctx *ctx, const float *model, const hsflow_warp_p
 int hsflow_gmotion_compose_host(const float *m1, const float *m2, float *out);
 /* out = the inverse map of m.  HSFLOW_E_ARG also: the linear part I + [[p1, p2], [p4, p5]] is singular. */
 int hsflow_gmotion_invert_host(const float *m, float *out);
+
+/* --- moving objects from the flow: connected regions (0.24) ---------------------------------- */
+
+/* What moves in the scene, as a list: the connected regions of a foreground mask -- hsflow_gmotion_fit's mask with value
+ * {0, 255, 0, 0}, hsflow_fb's mask, a status plane of hsflow_chain_* -- labelled where mask and flow lie, each region with
+ * its size, box, centroid sums and motion sums, so that a tracker, a region-of-interest encoder or an alarm reads a few
+ * records instead of the mask and both flow planes.  No counterpart in the reference.  The rule is
+ * csrc/hs_regions_rule.h, one header for the kernels and the host form; device and host give the same bits.
+ *   Foreground.  A pixel whose mask byte lies in fg_lo .. fg_hi inclusive (defaults 1 .. 255); with no mask every pixel.
+ *   Connectivity.  4 or 8.
+ *   Join.  join_px == 0: two adjacent foreground pixels are always joined.  join_px > 0 (needs flow): only when both
+ *   flows are known by hsflow_gmotion_fit's test (no NaN, no magnitude above 1e9, |a| and |b| at most 2048) and
+ *     fl(fl(du * du) + fl(dv * dv)) <= fl(join_px * join_px),  du = fl(ua - ub), dv = fl(va - vb);
+ *   equality joins; the test gives the same bits from either end.  A foreground pixel with unknown flow is then a region of
+ *   its own.
+ *   Regions.  The connected components of that graph; a region's root is the smallest y * W + x among its pixels.
+ *   Numbering.  Regions of fewer than min_area (>= 1) pixels are dropped: label 0, as background, and no number.  The kept
+ *   ones are numbered 1, 2, ... in ascending order of their roots.
+ *   Outputs, each may be absent, at least one asked for:
+ *     labels   an int32 plane, stride a multiple of 4; bytes of a row beyond 4 * width are left alone;
+ *     records  `capacity` records of 64 bytes; record k-1 belongs to region k for k <= capacity, records from
+ *              min(n_regions, capacity) on are left alone; regions above the capacity are still numbered in labels.
+ *              sum_x / area, sum_y / area is the centroid; n_flow counts the region's pixels whose flow is known (0 with
+ *              no flow planes), sum_qu, sum_qv are their flow quantised as the fit does, rint(fl(a * 256)) with ties to
+ *              even, so the mean motion is sum / (256 * n_flow);
+ *     result   64 bytes: n_regions, n_written = min(n_regions, capacity), n_dropped (regions below min_area), flags
+ *              (HSFLOW_REGIONS_FLAG_OVERFLOW: n_regions > capacity), fg_px, dropped_px, unknown_flow_px (foreground
+ *              pixels whose flow is unknown; 0 with no flow planes), largest_area and largest_label (a tie goes to the
+ *              smaller label; 0, 0 with no region).  capacity counts whether or not a record array is given.
+ *   Every sum is an exact integer, so the order of accumulation cannot matter.  Frames wider or higher than
+ *   HSFLOW_REGIONS_MAX_SIDE are refused (HSFLOW_E_SIZE): up to there no sum can overflow (the rule header has the proof).
+ * Time on an MI355X (profiles/regions_time.txt), one 1080p pair, labels, 64 records and the header: the
+ * fit's foreground mask of the benchmark's pair (8767 regions) in 0.241 ms, 8 pairs in one batch 0.885 ms; a random mask at
+ * the percolation threshold (60210 regions) 1.39 ms; the full mask (ONE region) 4.12 ms, of which 3.4 ms are the records'
+ * atomics, every wavefront on one record; 34 x a device-to-device copy of mask and label plane; reading mask and flow back
+ * and labelling on the host takes 9.2 ms, 31.6 ms and 49.5 ms for the three masks, 38 x, 23 x and 12 x the device's time. */
+#define HSFLOW_REGIONS_MAX_SIDE 16384
+#define HSFLOW_REGIONS_FLAG_OVERFLOW 1u
+typedef struct hsflow_regions_params {
+    uint32_t struct_size; /* = sizeof(hsflow_regions_params)      */
+    int32_t connectivity; /* 4 or 8                               */
+    int32_t fg_lo, fg_hi; /* 0 <= fg_lo <= fg_hi <= 255           */
+    uint32_t min_area;    /* >= 1                                 */
+    float join_px;        /* finite, >= 0, its square finite      */
+    int32_t reserved[2];  /* 0                                    */
+} hsflow_regions_params;
+typedef struct hsflow_regions_record { /* 64 bytes, the same on the device and on the host */
+    uint32_t root, area;     /* the smallest y * W + x of the region; its pixels */
+    uint16_t x0, y0, x1, y1; /* the box, inclusive */
+    uint64_t sum_x, sum_y;
+    uint32_t n_flow, reserved0;
+    int64_t sum_qu, sum_qv;
+    uint64_t reserved1;
+} hsflow_regions_record;
+typedef struct hsflow_regions_result { /* 64 bytes, the same on the device and on the host */
+    uint32_t n_regions, n_written, n_dropped, flags;
+    uint64_t fg_px, dropped_px, unknown_flow_px;
+    uint32_t largest_area, largest_label;
+    uint64_t reserved[2];
+} hsflow_regions_result;
+/* connectivity 8, foreground 1 .. 255, min_area 1, join_px 0.  NULL is ignored. */
+void hsflow_default_regions_params(hsflow_regions_params *rp);
+/* The rule on the host, no device needed: mask NULL or a u8 plane of width x height, rows mask_stride bytes apart; u, v
+ * both NULL or fp32 planes, rows flow_stride BYTES apart.  labels, records and result may each be null, not all.
+ * HSFLOW_E_ARG: null rp, wrong struct_size, reserved not 0, connectivity neither 4 nor 8, fg_lo > fg_hi or outside
+ * 0 .. 255, min_area 0, join_px negative, not finite or with a square that is not finite or is 0 while join_px is not,
+ * join_px > 0 without flow planes, one flow plane without the other, a flow or label plane that is not 4-byte aligned,
+ * records or result not 8-byte aligned, nothing asked for, an output that overlaps an input or another output;
+ * HSFLOW_E_SIZE: a non-positive size, a side above 16384, a mask stride below width, a flow or labels stride below
+ * 4*width or no multiple of 4, a capacity above 2^30. */
+int hsflow_regions_host(const uint8_t *mask /* may be null */, size_t mask_stride, const float *u /* may be null */, const float *v, size_t flow_stride,
+                        int width, int height, const hsflow_regions_params *rp, int32_t *labels /* may be null */, size_t labels_stride,
+                        hsflow_regions_record *records /* may be null */, uint32_t capacity, hsflow_regions_result *result /* may be null */);
+/* Planes anywhere on ctx's device, of the context's width and height.  Only enqueued on ctx's stream: a fixed sequence of
+ * eight launches (seven for a frame that is one tile of 64 x 16) that does not depend on the data, no memset, no wait on
+ * the host and none between workgroups.  The outputs are those of hsflow_regions_host from the same planes.  d_records and
+ * d_result are multiples of 8 (64-bit atomics).  The caller orders the producers of the planes before ctx's stream.  The
+ * ordering rules of hsflow_fb_batch_device apply word for word.  The scratch -- per field of the largest set of launches
+ * so far two planes of 4 * width * height bytes and 4 bytes per 256 pixels of a row -- is allocated by the first call,
+ * grown and kept until hsflow_destroy.  Every argument is checked before anything is enqueued.  Errors as the host form. */
+int hsflow_regions_planes_device(hsflow_ctx *ctx, const void *d_mask, size_t mask_stride, const void *d_u, const void *d_v, size_t flow_stride,
+                                 const hsflow_regions_params *rp, void *d_labels, size_t labels_stride, hsflow_regions_record *d_records, uint32_t capacity,
+                                 hsflow_regions_result *d_result);
+/* The pairs first_pair .. first_pair + n - 1 of the context, each with the context's own flow of that pair, by ONE set of
+ * launches (8 pairs per set).  d_mask, d_labels, d_records: NULL, or host arrays of n device pointers, free on return,
+ * whose entries may be NULL (every pixel foreground / no such output for that pair); every record array has `capacity`
+ * records; d_results: NULL or n headers.  The flow is read and never changed; no output may lie in the context's flow
+ * planes.  HSFLOW_E_ARG also: n < 1, first_pair < 0, first_pair + n > n_pairs. */
+int hsflow_regions_batch_device(hsflow_ctx *ctx, int first_pair, int n, const void *const *d_mask, size_t mask_stride, const hsflow_regions_params *rp,
+                                void *const *d_labels, size_t labels_stride, void *const *d_records, uint32_t capacity, hsflow_regions_result *d_results);
+/* A batch of one. */
+int hsflow_regions_device(hsflow_ctx *ctx, int pair, const void *d_mask, size_t mask_stride, const hsflow_regions_params *rp, void *d_labels,
+                          size_t labels_stride, hsflow_regions_record *d_records, uint32_t capacity, hsflow_regions_result *d_result);
+/* The same with the mask from host memory and the outputs in host memory, synchronous: complete on return.  Waits only for
+ * events behind its own work, like hsflow_gmotion_fit; only the n_written records cross.  The staging is allocated by the
+ * first call that needs a piece, grown and kept until hsflow_destroy. */
+int hsflow_regions(hsflow_ctx *ctx, int pair, const uint8_t *mask, size_t mask_stride, const hsflow_regions_params *rp, int32_t *labels, size_t labels_stride,
+                   hsflow_regions_record *records, uint32_t capacity, hsflow_regions_result *result);
 
 /* --- the input files (cvLoadImage) ---------------------------------------------------------- */
 

@@ -25,6 +25,7 @@ GMOTION_TRANSLATION, GMOTION_SIMILARITY, GMOTION_AFFINE, GMOTION_ZERO = 0, 1, 2,
 GMOTION_THRESHOLD_FIXED, GMOTION_THRESHOLD_AUTO = 0, 1
 GMOTION_INLIER, GMOTION_OUTLIER, GMOTION_UNTRUSTED, GMOTION_UNKNOWN = 0, 1, 2, 3
 GMOTION_MAX_PASSES, GMOTION_MAX_SIDE, GMOTION_FLAG_FALLBACK = 8, 16384, 1
+REGIONS_MAX_SIDE, REGIONS_FLAG_OVERFLOW = 16384, 1  # HSFLOW_REGIONS_*
 MEDIAN_FILTER, MEDIAN_FILL = 0, 1
 MEDIAN_UNFILLED, MEDIAN_KEPT, MEDIAN_FILLED = 0, 1, 2
 MEDIAN_MAX_PASSES = 64  # HSFLOW_MEDIAN_MAX_PASSES
@@ -122,6 +123,34 @@ class HsflowGmotionResult(ctypes.Structure):
 assert ctypes.sizeof(HsflowGmotionParams) == 40 and ctypes.sizeof(HsflowGmotionResult) == 64
 
 
+class HsflowRegionsParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("connectivity", ctypes.c_int32), ("fg_lo", ctypes.c_int32), ("fg_hi", ctypes.c_int32),
+                ("min_area", ctypes.c_uint32), ("join_px", ctypes.c_float), ("reserved", ctypes.c_int32 * 2)]
+
+
+class HsflowRegionsRecord(ctypes.Structure):
+    _fields_ = [("root", ctypes.c_uint32), ("area", ctypes.c_uint32), ("x0", ctypes.c_uint16), ("y0", ctypes.c_uint16), ("x1", ctypes.c_uint16),
+                ("y1", ctypes.c_uint16), ("sum_x", ctypes.c_uint64), ("sum_y", ctypes.c_uint64), ("n_flow", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),
+                ("sum_qu", ctypes.c_int64), ("sum_qv", ctypes.c_int64), ("reserved1", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class HsflowRegionsResult(ctypes.Structure):
+    _fields_ = [("n_regions", ctypes.c_uint32), ("n_written", ctypes.c_uint32), ("n_dropped", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("fg_px", ctypes.c_uint64), ("dropped_px", ctypes.c_uint64), ("unknown_flow_px", ctypes.c_uint64), ("largest_area", ctypes.c_uint32),
+                ("largest_label", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 2)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+        d["overflow"] = bool(self.flags & REGIONS_FLAG_OVERFLOW)
+        return d
+
+
+assert ctypes.sizeof(HsflowRegionsParams) == 32 and ctypes.sizeof(HsflowRegionsRecord) == 64 and ctypes.sizeof(HsflowRegionsResult) == 64
+
+
 class HsflowMedianParams(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("radius", ctypes.c_int32), ("mode", ctypes.c_int32), ("min_votes", ctypes.c_int32)]
 
@@ -213,6 +242,8 @@ _hp = ctypes.POINTER(HsflowChainParams)
 _hs = ctypes.POINTER(HsflowChainStats)
 _gp = ctypes.POINTER(HsflowGmotionParams)
 _gr = ctypes.POINTER(HsflowGmotionResult)
+_rgp = ctypes.POINTER(HsflowRegionsParams)
+_rgr = ctypes.POINTER(HsflowRegionsResult)
 _f = ctypes.c_float
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
@@ -326,6 +357,12 @@ PROTOTYPES = {
     "hsflow_gmotion_warp": (_i, [_vp, _fp, _wp, _vp, _sz, _vp, _sz, _vp, _sz, _ws]),
     "hsflow_gmotion_compose_host": (_i, [_fp, _fp, _fp]),
     "hsflow_gmotion_invert_host": (_i, [_fp, _fp]),
+    "hsflow_default_regions_params": (None, [_rgp]),
+    "hsflow_regions_host": (_i, [_vp, _sz, _vp, _vp, _sz, _i, _i, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _rgr]),
+    "hsflow_regions_planes_device": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _vp]),
+    "hsflow_regions_batch_device": (_i, [_vp, _i, _i, _vp, _sz, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _vp]),
+    "hsflow_regions_device": (_i, [_vp, _i, _vp, _sz, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _vp]),
+    "hsflow_regions": (_i, [_vp, _i, _vp, _sz, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _rgr]),
     "hsflow_pyramid_plan": (_i, [_i, _i, _yp, _ip, _ip, _ip]),
     "hsflow_pyramid_down_host": (_i, [_vp, _sz, _i, _i, _vp, _sz]),
     "hsflow_pyramid_prolong_host": (_i, [_vp, _sz, _i, _i, _vp, _sz]),

@@ -414,6 +414,90 @@ int median_step(hsflow_ctx *ctx, int W, int H, std::vector<float> *u, std::vecto
     return SDK_SUCCESS;
 }
 
+// HSFLOW_REGIONS=<min_area>[,<4|8>[,<join_px>]] on the two "-hd" routes: behind the solve (and HSFLOW_MEDIAN / HSFLOW_PYRAMID)
+// the flow is fitted with the HSFLOW_GMOTION choice and mask values {0, 255, 0, 0} -- the pixels that do not follow the
+// camera -- and that mask is labelled (hsflow_regions*): one line "regions: kept .. dropped .. foreground .. largest .." and
+// at most 16 lines "region k: area .. box x0 y0 x1 y1 centre cx cy motion mu mv".  The picture is unchanged.
+// 0: not set, 1: usable, -1: unusable.
+constexpr uint32_t kRegionLines = 16;
+
+int regions_choice(hsflow_regions_params &rp)
+{
+    hsflow_default_regions_params(&rp);
+    const char *e = getenv("HSFLOW_REGIONS");
+    if (!e || !*e) return 0;
+    char *rest = nullptr;
+    const long a = strtol(e, &rest, 10);
+    if (rest == e || a < 1 || a > (1L << 30)) return -1;
+    rp.min_area = (uint32_t)a;
+    if (!*rest) return 1;
+    if (*rest != ',') return -1;
+    const char *q = rest + 1;
+    const long c = strtol(q, &rest, 10);
+    if (rest == q || (c != 4 && c != 8)) return -1;
+    rp.connectivity = (int)c;
+    if (!*rest) return 1;
+    if (*rest != ',') return -1;
+    q = rest + 1;
+    const float j = strtof(q, &rest);
+    if (rest == q || *rest || !std::isfinite(j) || !(j >= 0.f) || !std::isfinite(j * j) || (j > 0.f && !(j * j > 0.f))) return -1;
+    rp.join_px = j;
+    return 1;
+}
+
+// With HSFLOW_RENDER_DEVICE=1 through hsflow_gmotion_fit_device and hsflow_regions_device (mask and flow stay on the device,
+// the records alone are read back), otherwise the host rules on the flow that was read back (u, v); the same lines.
+int regions_step(hsflow_ctx *ctx, int W, int H, const std::vector<float> *u, const std::vector<float> *v)
+{
+    hsflow_regions_params rp;
+    if (regions_choice(rp) != 1) return SDK_SUCCESS;
+    hsflow_gmotion_params gp;
+    gmotion_choice(gp);
+    gp.value[0] = 0; gp.value[1] = 255; gp.value[2] = 0; gp.value[3] = 0;
+    std::vector<hsflow_regions_record> recs(kRegionLines);
+    hsflow_regions_result r;
+    int st;
+    if (render_on_device()) {
+        void *dMask = nullptr, *dOut = nullptr; // dOut: the result header, then the records
+        const size_t out_bytes = sizeof(r) + sizeof(hsflow_regions_record) * kRegionLines;
+        if (hipMalloc(&dMask, (size_t)W * H) != hipSuccess || hipMalloc(&dOut, out_bytes) != hipSuccess) {
+            (void)hipFree(dMask);
+            std::cout << "hipMalloc of the regions' mask failed" << std::endl;
+            return SDK_FAILURE;
+        }
+        std::vector<uint8_t> back(out_bytes);
+        st = hsflow_gmotion_fit_device(ctx, 0, nullptr, 0, &gp, dMask, (size_t)W, nullptr, nullptr, 0, nullptr);
+        if (st == HSFLOW_OK)
+            st = hsflow_regions_device(ctx, 0, dMask, (size_t)W, &rp, nullptr, 0, (hsflow_regions_record *)((uint8_t *)dOut + sizeof(r)), kRegionLines,
+                                       (hsflow_regions_result *)dOut);
+        if (st == HSFLOW_OK) st = hsflow_synchronize(ctx);
+        const bool copied = st == HSFLOW_OK && hipMemcpy(back.data(), dOut, out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+        (void)hipFree(dMask);
+        (void)hipFree(dOut);
+        if (st == HSFLOW_OK && !copied) { std::cout << "reading the regions' records failed" << std::endl; return SDK_FAILURE; }
+        if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+        memcpy(&r, back.data(), sizeof(r));
+        memcpy(recs.data(), back.data() + sizeof(r), sizeof(hsflow_regions_record) * kRegionLines);
+    } else {
+        if (!u || !v || u->size() != (size_t)W * H) { std::cout << "HSFLOW_REGIONS: no flow in host memory" << std::endl; return SDK_FAILURE; }
+        std::vector<uint8_t> mask((size_t)W * H);
+        st = hsflow_gmotion_fit_host(u->data(), v->data(), (size_t)W * 4, nullptr, 0, W, H, &gp, mask.data(), (size_t)W, nullptr, nullptr, 0, nullptr);
+        if (st == HSFLOW_OK)
+            st = hsflow_regions_host(mask.data(), (size_t)W, u->data(), v->data(), (size_t)W * 4, W, H, &rp, nullptr, 0, recs.data(), kRegionLines, &r);
+        if (st != HSFLOW_OK) { std::cout << hsflow_last_error(nullptr) << std::endl; return SDK_FAILURE; }
+    }
+    std::cout << "regions: kept " << r.n_regions << " dropped " << r.n_dropped << " foreground " << r.fg_px << " largest " << r.largest_area << std::endl;
+    for (uint32_t k = 0; k < r.n_written; k++) {
+        const hsflow_regions_record &q = recs[k];
+        const double nf = q.n_flow ? 256.0 * (double)q.n_flow : 1.0;
+        char line[256];
+        snprintf(line, sizeof(line), "region %u: area %u box %u %u %u %u centre %.2f %.2f motion %.3f %.3f", k + 1, q.area, (unsigned)q.x0, (unsigned)q.y0,
+                 (unsigned)q.x1, (unsigned)q.y1, (double)q.sum_x / q.area, (double)q.sum_y / q.area, (double)q.sum_qu / nf, (double)q.sum_qv / nf);
+        std::cout << line << std::endl;
+    }
+    return SDK_SUCCESS;
+}
+
 // The host route of the colour picture: the rule on the host, applied to the flow that was read back.
 int color_on_host(pnm::Image &imgFlow, const std::vector<float> &u, const std::vector<float> &v, int W, int H)
 {
@@ -498,6 +582,8 @@ bool picture_choice_usable()
     if (median_choice(radius, passes, fill) < 0) { std::cout << "HSFLOW_MEDIAN must be <radius 1 or 2>[,<passes 1 .. 64>[,fill]]" << std::endl; return false; }
     hsflow_pyramid_params pp;
     if (pyramid_choice(pp) < 0) { std::cout << "HSFLOW_PYRAMID must be <levels 1 .. 8 or auto>[,<warps 1 .. 8>[,<median radius 0, 1 or 2>]]" << std::endl; return false; }
+    hsflow_regions_params rgp;
+    if (regions_choice(rgp) < 0) { std::cout << "HSFLOW_REGIONS must be <min_area 1 .. 2^30>[,<4 or 8>[,<join_px, a finite number >= 0>]]" << std::endl; return false; }
     return true;
 }
 
@@ -692,6 +778,7 @@ int HSOpticalFlowOpenCL::run()
         std::cout << "Avg time: " << lastMs << " [ms]" << std::endl; // :755
         const int verdict = verify_wanted() ? verifyResults() : SDK_SUCCESS;
         if (median_step(ctx, (int)width, (int)height, render_on_device() ? nullptr : &u, render_on_device() ? nullptr : &v) != SDK_SUCCESS) return SDK_FAILURE;
+        if (regions_step(ctx, (int)width, (int)height, render_on_device() ? nullptr : &u, render_on_device() ? nullptr : &v) != SDK_SUCCESS) return SDK_FAILURE;
         if (jpeg_on_device(output)) return save_jpeg_from_device(ctx, HSFLOW_RENDER_CL, (int)width, (int)height, output) == SDK_SUCCESS ? verdict : SDK_FAILURE;
         pnm::Image imgFlow;
         if (warp_wanted()) {
@@ -796,6 +883,7 @@ int OpticalFlowOpenCV::runFromImg(char *input1, char *input2, char *output, floa
     hsflow_verify_report report;
     const int verdict = verify_wanted() ? verify_pair(ctx, W, report) : SDK_SUCCESS; // (the context goes away below)
     if (median_step(ctx, W, H, on_device ? nullptr : &u, on_device ? nullptr : &v) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
+    if (regions_step(ctx, W, H, on_device ? nullptr : &u, on_device ? nullptr : &v) != SDK_SUCCESS) { hsflow_destroy(ctx); return 1; }
     pnm::Image imgFlow;
     const bool file_on_device = jpeg_on_device(output ? output : "");
     if (file_on_device) {

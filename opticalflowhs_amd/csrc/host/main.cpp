@@ -22,6 +22,12 @@
 // HSFLOW_PICTURE=stab (the two -hd routes): the file is the second input warped onto the first by the ONE global motion fitted
 // to the solved flow (hsflow_gmotion_fit*, hsflow_gmotion_warp*), not by the dense flow; one line tells the model and the
 // inliers' share.  HSFLOW_GMOTION=<translation|similarity|affine>[,<passes>[,<px>|auto]] selects the fit.
+// HSFLOW_REGIONS=<min_area>[,<4|8>[,<join_px>]] (the two -hd routes): behind the solve (and HSFLOW_MEDIAN / HSFLOW_PYRAMID) the
+// flow is fitted with the HSFLOW_GMOTION choice, the pixels that do not follow the camera are labelled (hsflow_regions*), and
+// one line "regions: kept .. dropped .. foreground .. largest .." and at most 16 lines "region k: area .. box x0 y0 x1 y1
+// centre cx cy motion mu mv" tell what moves; by the host rules from the flow read back, with HSFLOW_RENDER_DEVICE=1 on the
+// device with only the records read back; the same lines, the picture is unchanged (an unusable value: a message and exit
+// status 1).
 // HSFLOW_PICTURE=fb (the two -hd routes): the pair is solved forwards and, from the same pre-processed frames, backwards
 // (hsflow_set_frames_reversed), and the file is the forward-backward consistency mask (hsflow_fb*: 255 where the two flows
 // cancel, 0 elsewhere) as a gray picture; one line "fb: consistent .. inconsistent .. outside .. unknown .. mse .." tells

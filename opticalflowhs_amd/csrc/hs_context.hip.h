@@ -356,6 +356,17 @@ struct hsflow_ctx {
         hsflow_gmotion_result *dRes = nullptr, *hRes = nullptr;
         hsflow_warp_stats *dStats = nullptr, *hStats = nullptr;
     } gmotion;
+    // hsflow_regions* (hs_regions.hip.h): the kernels' scratch (per field of the largest chunk so far a parent and an area
+    // plane of W * H words and one count word per 256 pixels of a row, then the hsk::RgAcc records; a call reads no word it
+    // has not written itself, so nothing is cleared), allocated by the first call and grown; the staging of the synchronous
+    // form -- 0 mask, 1 labels, 2 records -- and one result header on the device and in page-locked memory.
+    struct RegionsScratch {
+        void *scr = nullptr;
+        size_t bytes = 0;
+        uint8_t *stage[3] = {nullptr, nullptr, nullptr};
+        size_t stage_bytes[3] = {0, 0, 0};
+        hsflow_regions_result *dRes = nullptr, *hRes = nullptr;
+    } regions;
 };
 
 namespace {

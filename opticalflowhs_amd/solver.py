@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (HsflowGmotionParams, HsflowGmotionResult, GMOTION_TRANSLATION, GMOTION_SIMILARITY, GMOTION_AFFINE, GMOTION_THRESHOLD_FIXED, GMOTION_THRESHOLD_AUTO, COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowChainParams, HsflowChainStats, CHAIN_MAX_PAIRS, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (HsflowRegionsParams, HsflowRegionsRecord, HsflowRegionsResult, HsflowGmotionParams, HsflowGmotionResult, GMOTION_TRANSLATION, GMOTION_SIMILARITY, GMOTION_AFFINE, GMOTION_THRESHOLD_FIXED, GMOTION_THRESHOLD_AUTO, COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowChainParams, HsflowChainStats, CHAIN_MAX_PAIRS, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -392,6 +392,63 @@ def _gmotion_model(model):
     if len(vals) != 6:
         raise ValueError("a model has six parameters")
     return (ctypes.c_float * 6)(*vals)
+
+
+def make_regions_params(connectivity=8, min_area=1, join_px=0.0, fg=(1, 255)):
+    """hsflow_regions_params of a labelling: `connectivity` 4 or 8; regions of fewer than `min_area` pixels are dropped;
+    `join_px` 0 joins every two adjacent foreground pixels, above 0 only those whose flows differ by at most that many
+    pixels (needs flow); `fg`: the range (lo, hi) of mask bytes that are foreground.  include/hsflow.h has the rule."""
+    rp = HsflowRegionsParams()
+    _lib.load().hsflow_default_regions_params(ctypes.byref(rp))
+    rp.connectivity, rp.min_area, rp.join_px = int(connectivity), int(min_area), join_px
+    rp.fg_lo, rp.fg_hi = int(fg[0]), int(fg[1])
+    return rp
+
+
+def _regions_call(height, width, device_index, mask, labels, records, capacity, result, params, device):
+    """What the labelling entries share from the mask on.  mask: None or the u8 plane; labels: False / None, True
+    (allocated here) or the int32 plane; records: False / None, True (`capacity` of them allocated here: on the host a
+    ctypes array of `HsflowRegionsRecord`, on the device a CUDA uint8 tensor of capacity * 64 bytes) or such an array;
+    result: True or False.  Returns (the C call's arguments, result, labels, records)."""
+    capacity = int(capacity)
+    mp, ms = _plane(mask, height, width, "uint8", "mask", device) if mask is not None else (None, 0)
+    if labels is True:
+        if device:
+            import torch
+            labels = torch.empty((height, width), dtype=torch.int32, device="cuda:%d" % device_index)
+        else:
+            labels = np.empty((height, width), np.int32)
+    elif labels is None or labels is False:
+        labels = None
+    lp, ls = (None, 0)
+    if labels is not None:
+        if device != _is_device_tensor(labels) or str(labels.dtype) not in ("int32", "torch.int32") or tuple(labels.shape) != (height, width):
+            raise ValueError("labels must be int32 of shape (height, width), %s" % ("a CUDA tensor" if device else "a NumPy array"))
+        strides = tuple(st * 4 for st in labels.stride()) if device else labels.strides
+        if strides[1] != 4:
+            raise ValueError("labels must have packed elements")
+        lp, ls = _ptr(labels), strides[0]
+    rp_ = None
+    if records is True:
+        if device:
+            import torch
+            records = torch.empty(max(capacity, 1) * 64, dtype=torch.uint8, device="cuda:%d" % device_index)
+        else:
+            records = (HsflowRegionsRecord * max(capacity, 1))()
+    elif records is None or records is False:
+        records = None
+    if records is not None:
+        if device:
+            if not _is_device_tensor(records) or str(records.dtype) != "torch.uint8" or not records.is_contiguous() or records.numel() < capacity * 64:
+                raise ValueError("records must be a contiguous CUDA uint8 tensor of at least capacity * 64 bytes")
+            rp_ = _ptr(records)
+        else:
+            if ctypes.sizeof(records) < capacity * 64:
+                raise ValueError("records must hold at least capacity records")
+            rp_ = ctypes.cast(records, ctypes.c_void_p)
+    prm = params if params is not None else make_regions_params()
+    rec, rref = _stats_record(HsflowRegionsResult, result, device, device_index)
+    return (mp, ms, ctypes.byref(prm), lp, ls, rp_, capacity, rref), rec, labels, records
 
 
 def make_chain_params(values=(255, 0, 0, 0)):
@@ -1028,6 +1085,58 @@ class HSFlow(object):
                                                                _check_stats_tensor(results, n, HsflowGmotionResult)))
         return results
 
+    def regions(self, pair=0, mask=None, labels=False, records=True, capacity=64, result=True, params=None, device=False):
+        """The moving objects of `pair`: the connected regions of the foreground `mask` (None: every pixel; a u8 plane (H,
+        W), e.g. the mask of `global_motion` with values (0, 255, 0, 0)) with the pair's current flow, by
+        `hsflow_regions[_device]` (`make_regions_params`; include/hsflow.h has the rule).  labels: False, True or the int32
+        plane to fill; records: False, True (`capacity` records allocated here) or the array; result: True or False.  Host
+        planes: synchronous, the result an `HsflowRegionsResult`, the records a ctypes array of `HsflowRegionsRecord` of
+        which the first `n_written` are valid.  CUDA tensors (or device=True): only enqueued on the context's stream, result
+        and records then CUDA uint8 tensors that `regions_result_from` / `regions_records_from` read.  Returns (result,
+        labels, records), None for what was not asked for."""
+        device = _chain_device(device, mask, labels, records if not isinstance(records, ctypes.Array) else None)
+        args, rec, labels, records = _regions_call(self.height, self.width, self.device, mask, labels, records, capacity, result, params, device)
+        self._check((self._lib.hsflow_regions_device if device else self._lib.hsflow_regions)(self._h, int(pair), *args))
+        return rec, labels, records
+
+    def regions_planes_device(self, mask=None, u=None, v=None, labels=False, records=True, capacity=64, result=True, params=None):
+        """`regions` on the device of caller planes: mask None or a CUDA u8 plane, u, v None or CUDA float32 planes (H, W)
+        of one row stride (`hsflow_regions_planes_device`).  Only enqueued."""
+        if (u is None) != (v is None):
+            raise ValueError("u and v are given together or not at all")
+        up = vp = None
+        us = 0
+        if u is not None:
+            (up, us), (vp, vs) = [_plane(x, self.height, self.width, "float32", "flow", True) for x in (u, v)]
+            if us != vs:
+                raise ValueError("the two flow planes share one row stride")
+        args, rec, labels, records = _regions_call(self.height, self.width, self.device, mask, labels, records, capacity, result, params, True)
+        self._check(self._lib.hsflow_regions_planes_device(self._h, args[0], args[1], up, vp, us, *args[2:]))
+        return rec, labels, records
+
+    def regions_batch_device(self, first_pair=0, n=None, mask=None, labels=None, records=None, capacity=64, results=None, params=None):
+        """`regions` on the device for the pairs first_pair .. first_pair + n - 1 (n=None: all pairs from first_pair) by
+        one set of launches (`hsflow_regions_batch_device`), each with its own flow.  mask, labels: None, or lists of n
+        entries, each None or a CUDA plane (H, W); one row stride per list.  records: None, or a list of n entries, each
+        None or a contiguous CUDA uint8 tensor of capacity * 64 bytes.  results: None, or a CUDA uint8 tensor of n * 64
+        bytes (`regions_result_from`).  Only enqueued."""
+        first_pair, n = self._batch_range(first_pair, n)
+        H, W = self.height, self.width
+        ml, ms = _chain_list(mask, n, H, W, "uint8", "mask", True, holes=True)
+        ll, ls = _chain_list(labels, n, H, W, "int32", "labels", True, holes=True)
+        rl = None
+        if records is not None:
+            if len(records) != n:
+                raise ValueError("records must hold one entry per pair")
+            for r in records:
+                if r is not None and (not _is_device_tensor(r) or str(r.dtype) != "torch.uint8" or not r.is_contiguous() or r.numel() < int(capacity) * 64):
+                    raise ValueError("a record array must be a contiguous CUDA uint8 tensor of at least capacity * 64 bytes")
+            rl = (ctypes.c_void_p * n)(*[r.data_ptr() if r is not None else None for r in records])
+        prm = params if params is not None else make_regions_params()
+        self._check(self._lib.hsflow_regions_batch_device(self._h, first_pair, n, ml, ms, ctypes.byref(prm), ll, ls, rl, int(capacity),
+                                                           _check_stats_tensor(results, n, HsflowRegionsResult)))
+        return results
+
     def gmotion_warp(self, model, src, ref=None, out=None, t=1.0, border="constant", fill=0, return_stats=False, params=None, picture=True):
         """`src` warped backwards by the motion `model` (six floats or an `HsflowGmotionResult`) alone, no flow plane read
         (`hsflow_gmotion_warp[_device]`); everything else as `warp` takes and returns it."""
@@ -1428,6 +1537,53 @@ def gmotion_result_from(results, n=1):
     size = ctypes.sizeof(HsflowGmotionResult)
     recs = [HsflowGmotionResult.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(n)]
     return recs[0] if n == 1 else recs
+
+
+def regions_result_from(results, n=1):
+    """The `HsflowRegionsResult` headers a device call left in the CUDA uint8 tensor `results` (after `synchronize()`):
+    one for n=1, else a list of n."""
+    raw = results.cpu().numpy().tobytes()
+    size = ctypes.sizeof(HsflowRegionsResult)
+    recs = [HsflowRegionsResult.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(n)]
+    return recs[0] if n == 1 else recs
+
+
+def regions_records_from(records, n):
+    """The first n `HsflowRegionsRecord` of a record array: a CUDA uint8 tensor (after `synchronize()`) or the ctypes
+    array of the host forms; a list."""
+    raw = records.cpu().numpy().tobytes() if _is_device_tensor(records) else bytes(records)
+    return [HsflowRegionsRecord.from_buffer_copy(raw[i * 64:(i + 1) * 64]) for i in range(n)]
+
+
+def regions_host(mask=None, u=None, v=None, labels=False, records=True, capacity=64, result=True, params=None, shape=None):
+    """The labelling by the rule on the host (`hsflow_regions_host`, no GPU work): mask None or a u8 array (H, W), u, v
+    None or float32 arrays (H, W), padded rows taken as they are; with neither mask nor flow `shape` = (H, W) is needed.
+    labels, records, capacity, result as `HSFlow.regions` takes them.  Returns (result, labels, records) -- bit for bit
+    what the device forms give from the same planes."""
+    if (u is None) != (v is None):
+        raise ValueError("u and v are given together or not at all")
+    if u is not None:
+        u, v = (np.asarray(a, np.float32) for a in (u, v))
+        if u.ndim != 2 or u.shape != v.shape:
+            raise ValueError("u and v must be 2-D arrays of one shape")
+        if any(a.strides[1] != 4 or a.strides[0] % 4 for a in (u, v)) or u.strides[0] != v.strides[0]:
+            u, v = np.ascontiguousarray(u), np.ascontiguousarray(v)
+    if mask is not None:
+        H, W = mask.shape
+    elif u is not None:
+        H, W = u.shape
+    elif shape is not None:
+        H, W = shape
+    else:
+        raise ValueError("with neither mask nor flow the shape is needed")
+    if u is not None and u.shape != (H, W):
+        raise ValueError("mask and flow must have one shape")
+    args, rec, labels, records = _regions_call(H, W, 0, mask, labels, records, capacity, result, params, False)
+    st = _lib.load().hsflow_regions_host(args[0], args[1], _ptr(u) if u is not None else None, _ptr(v) if v is not None else None,
+                                         u.strides[0] if u is not None else 0, W, H, *args[2:])
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return rec, labels, records
 
 
 def global_motion_host(u, v, state=None, mask=False, residual=False, result=True, params=None):
