@@ -65,6 +65,10 @@
  *                                          regions of a foreground mask (hsflow_gmotion_fit's, hsflow_fb's), optionally cut
  *                                          where neighbours move differently, each with its size, box, centroid and mean
  *                                          motion -- labelled where mask and flow lie; only the records cross PCIe
+ *   hsflow_link_regions[_host|_device|_batch_device|_planes_device], hsflow_link_tracks_host
+ *                                          no counterpart in the reference: the regions of consecutive pairs linked by
+ *                                          the flow -- how many pixels of region a arrive in region b of the next frame --
+ *                                          where labels and flow lie, and object ids over the sequence from those records
  *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
  *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
  *                                          the pictures are decoded on the device
@@ -100,7 +104,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 24 /* 0.24: hsflow_regions[_host|_device|_batch_device|_planes_device], hsflow_default_regions_params, hsflow_regions_params, hsflow_regions_record, hsflow_regions_result, HSFLOW_REGIONS_*; 0.23: hsflow_gmotion_fit[_host|_device|_batch_device|_planes_device], hsflow_gmotion_warp[_host|_device], hsflow_gmotion_compose_host, hsflow_gmotion_invert_host, hsflow_default_gmotion_params, hsflow_gmotion_params, hsflow_gmotion_result, HSFLOW_GMOTION_*; 0.22: hsflow_chain_flow[_host|_device], hsflow_chain_planes_device, hsflow_track_points[_host|_device], hsflow_default_chain_params, hsflow_chain_params, hsflow_chain_stats, HSFLOW_CHAIN_*; 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 25 /* 0.25: hsflow_link_regions[_host|_device|_batch_device|_planes_device], hsflow_link_tracks_host, hsflow_default_link_params, hsflow_link_params, hsflow_link_record, hsflow_link_side, hsflow_link_result, HSFLOW_LINK_*; 0.24: hsflow_regions[_host|_device|_batch_device|_planes_device], hsflow_default_regions_params, hsflow_regions_params, hsflow_regions_record, hsflow_regions_result, HSFLOW_REGIONS_*; 0.23: hsflow_gmotion_fit[_host|_device|_batch_device|_planes_device], hsflow_gmotion_warp[_host|_device], hsflow_gmotion_compose_host, hsflow_gmotion_invert_host, hsflow_default_gmotion_params, hsflow_gmotion_params, hsflow_gmotion_result, HSFLOW_GMOTION_*; 0.22: hsflow_chain_flow[_host|_device], hsflow_chain_planes_device, hsflow_track_points[_host|_device], hsflow_default_chain_params, hsflow_chain_params, hsflow_chain_stats, HSFLOW_CHAIN_*; 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -1614,6 +1618,111 @@ int hsflow_regions_device(hsflow_ctx *ctx, int pair, const void *d_mask, size_t 
  * first call that needs a piece, grown and kept until hsflow_destroy. */
 int hsflow_regions(hsflow_ctx *ctx, int pair, const uint8_t *mask, size_t mask_stride, const hsflow_regions_params *rp, int32_t *labels, size_t labels_stride,
                    hsflow_regions_record *records, uint32_t capacity, hsflow_regions_result *result);
+
+/* --- moving objects through a sequence: regions linked across pairs (0.25) ------------------- */
+
+/* Which region of frame k + 1 is which region of frame k: every labelled pixel of frame k is followed along the flow of the
+ * pair k -> k + 1 and counted where it arrives, so that a tracker reads a few hundred bytes per pair instead of two label
+ * planes and a flow field.  No counterpart in the reference.  The rule is csrc/hs_link_rule.h, one header for the kernels
+ * and the host form; device and host give the same bytes.
+ *   Inputs of a step.  Two int32 label planes A (frame k) and B (frame k + 1) of width x height -- hsflow_regions*'s or any
+ *   other; a value <= 0 is background -- the flow (u, v) of the pair, and two caps cap_a, cap_b >= 1 with
+ *   cap_a * cap_b <= HSFLOW_LINK_MAX_CELLS.
+ *   Pixel (x, y) with a = A[y][x] > 0:
+ *     a > cap_a: it counts into the header's over_a_px and does nothing else;
+ *     it lands where hsflow_interp's projection at t = 1 puts it: hx = fl(fl((float)x + u) + 0.5f), hy alike, the pixel
+ *     (floor hx, floor hy) -- the same function, so the half-pixel tie is the interpolation operator's, bit for bit;
+ *     a flow that is not known (NaN, a magnitude above 1e9) or a landing outside the frame: it counts into gone_px of a;
+ *     b = B at the landing pixel; b <= 0 or b > cap_b: it counts into unmatched_px of a; else it is ONE VOTE for (a, b).
+ *   Outputs, each may be absent, at least one asked for:
+ *     links    link_capacity records of 16 bytes, one per cell (a, b) with px > 0 votes, in ascending order of (a, b);
+ *              records from min(n_links, link_capacity) on are left alone;
+ *     side_a   cap_a records of 32 bytes, all written; record a-1: px, the pixels of label a (= gone_px + unmatched_px + the
+ *              votes of row a); n_links, the non-zero cells of the row; best, the b of the largest cell (a tie goes to the
+ *              smaller b; 0 with no vote) and best_px, its votes; gone_px, unmatched_px;
+ *     side_b   cap_b records of the same struct over the columns: px the arrivals, best the a that sends most (a tie to the
+ *              smaller a), gone_px = unmatched_px = 0;
+ *     result   64 bytes: n_links, n_written = min(n_links, link_capacity), flags (HSFLOW_LINK_FLAG_OVERFLOW:
+ *              n_links > link_capacity), n_mutual (the pairs with best(a) == b and best(b) == a), and the totals voted_px,
+ *              gone_px, unmatched_px, over_a_px.  link_capacity counts whether or not a link array is given.  A link array with
+ *              link_capacity 0 is no output: alone it is "nothing asked for".
+ *   Every quantity is an exact integer count, so the order of arrival cannot matter.
+ * Time on an MI355X (profiles/link_time.txt), one 1080p step with 256 links, both sides and the header:
+ * both planes ONE region, every pixel voting, 0.051 ms at caps 64; the label planes of the benchmark pair's fit mask 0.042
+ * ms at caps 64 and 0.057 ms at caps 256 (of its 8767 regions only those within the caps vote; the rest returns after the
+ * label), 8 such steps in one batch 0.086 ms; random labels at caps 4096 x 4096 0.57 ms; 5 x a device-to-device copy of
+ * two label planes.  Reading the planes and the flow back and linking on the host takes 9 .. 15 ms, 21 .. 30 ms and 95 ..
+ * 120 ms for the three: two to three orders of magnitude more. */
+#define HSFLOW_LINK_MAX_CELLS (1u << 24)
+#define HSFLOW_LINK_FLAG_OVERFLOW 1u
+typedef struct hsflow_link_params {
+    uint32_t struct_size; /* = sizeof(hsflow_link_params)                              */
+    uint32_t cap_a;       /* >= 1: labels of A above it count into over_a_px           */
+    uint32_t cap_b;       /* >= 1: labels of B above it are unmatched; cap_a * cap_b <= HSFLOW_LINK_MAX_CELLS */
+    uint32_t reserved;    /* 0                                                         */
+} hsflow_link_params;
+typedef struct hsflow_link_record { /* 16 bytes, the same on the device and on the host */
+    uint32_t a, b, px, reserved;
+} hsflow_link_record;
+typedef struct hsflow_link_side { /* 32 bytes, the same on the device and on the host */
+    uint32_t px, n_links, best, best_px, gone_px, unmatched_px, reserved[2];
+} hsflow_link_side;
+typedef struct hsflow_link_result { /* 64 bytes, the same on the device and on the host */
+    uint32_t n_links, n_written, flags, n_mutual;
+    uint64_t voted_px, gone_px, unmatched_px, over_a_px;
+    uint64_t reserved[2];
+} hsflow_link_result;
+/* cap_a 64, cap_b 64.  NULL is ignored. */
+void hsflow_default_link_params(hsflow_link_params *lp);
+/* The rule on the host, no device needed: labels_a, labels_b int32 planes of width x height, rows stride_a / stride_b BYTES
+ * apart; u, v fp32 planes, rows flow_stride BYTES apart.  links, side_a, side_b and result may each be null, not all.
+ * HSFLOW_E_ARG: null lp, wrong struct_size, reserved not 0, a cap of 0, a null label or flow plane, a label or flow plane
+ * that is not 4-byte aligned, links, sides or result not 8-byte aligned, nothing asked for, an output that overlaps an
+ * input or another output; HSFLOW_E_SIZE: a non-positive size, a side above 16384, a stride below 4*width or no multiple of
+ * 4, a cap above 2^30, cap_a * cap_b or link_capacity above HSFLOW_LINK_MAX_CELLS. */
+int hsflow_link_regions_host(const int32_t *labels_a, size_t stride_a, const int32_t *labels_b, size_t stride_b, const float *u, const float *v,
+                             size_t flow_stride, int width, int height, const hsflow_link_params *lp, hsflow_link_record *links /* may be null */,
+                             uint32_t link_capacity, hsflow_link_side *side_a /* may be null */, hsflow_link_side *side_b /* may be null */,
+                             hsflow_link_result *result /* may be null */);
+/* Planes anywhere on ctx's device, of the context's width and height.  Only enqueued on ctx's stream: a fixed sequence of
+ * eight launches that does not depend on the data, no memset call, no wait on the host and none between workgroups.  The
+ * outputs are those of hsflow_link_regions_host from the same planes.  The caller orders the producers of the planes before
+ * ctx's stream.  The ordering rules of hsflow_fb_batch_device apply word for word.  The scratch -- per step of the largest
+ * set of launches so far 4 * (cap_a * cap_b + 2 * cap_a + 1) bytes and a few words per cap -- is allocated by the first
+ * call, grown and kept until hsflow_destroy.  Every argument is checked before anything is enqueued.  Errors as the host
+ * form. */
+int hsflow_link_regions_planes_device(hsflow_ctx *ctx, const void *d_labels_a, size_t stride_a, const void *d_labels_b, size_t stride_b, const void *d_u,
+                                      const void *d_v, size_t flow_stride, const hsflow_link_params *lp, hsflow_link_record *d_links, uint32_t link_capacity,
+                                      hsflow_link_side *d_side_a, hsflow_link_side *d_side_b, hsflow_link_result *d_result);
+/* n_steps steps: step i links plane i to plane i + 1 of d_labels -- a host array of n_steps + 1 device pointers, free on
+ * return, none NULL, rows labels_stride bytes apart -- by the context's own flow of the pair first_pair + i.  The steps of
+ * a chunk run in ONE set of launches; a chunk is min(8, HSFLOW_LINK_MAX_CELLS / (cap_a * cap_b)) steps, at least 1, so the
+ * cell scratch stays within 64 MiB.  The caps are arguments: no header of hsflow_regions_batch_device has to be read back in
+ * between.  d_links, d_side_a, d_side_b: NULL, or host arrays of n_steps device pointers whose entries may be NULL; every
+ * link array has link_capacity records; d_results: NULL or n_steps headers.  The flow is read and never changed; no output
+ * may lie in the context's flow planes.  HSFLOW_E_ARG also: n_steps < 1, first_pair < 0, first_pair + n_steps > n_pairs. */
+int hsflow_link_regions_batch_device(hsflow_ctx *ctx, int first_pair, int n_steps, const void *const *d_labels, size_t labels_stride,
+                                     const hsflow_link_params *lp, void *const *d_links, uint32_t link_capacity, void *const *d_side_a, void *const *d_side_b,
+                                     hsflow_link_result *d_results);
+/* A batch of one step. */
+int hsflow_link_regions_device(hsflow_ctx *ctx, int pair, const void *d_labels_a, const void *d_labels_b, size_t labels_stride, const hsflow_link_params *lp,
+                               hsflow_link_record *d_links, uint32_t link_capacity, hsflow_link_side *d_side_a, hsflow_link_side *d_side_b,
+                               hsflow_link_result *d_result);
+/* The same with the label planes from host memory and the outputs in host memory, synchronous: complete on return.  Waits
+ * only for events behind its own work, like hsflow_regions; only the n_written links cross.  The staging is allocated by
+ * the first call that needs a piece, grown and kept until hsflow_destroy. */
+int hsflow_link_regions(hsflow_ctx *ctx, int pair, const int32_t *labels_a, size_t stride_a, const int32_t *labels_b, size_t stride_b,
+                        const hsflow_link_params *lp, hsflow_link_record *links, uint32_t link_capacity, hsflow_link_side *side_a, hsflow_link_side *side_b,
+                        hsflow_link_result *result);
+/* Object ids over a chain of steps from the side records alone, on the host.  side_a[i], side_b[i]: the `cap` records of
+ * step i (frame i -> frame i + 1), i < n_steps; n_regions[k]: the regions of frame k, k <= n_steps; ids: (n_steps + 1) * cap
+ * words, ids[k * cap + label - 1].  Frame 0's regions get the ids 1 .. min(n_regions[0], cap).  In step i region b of frame
+ * i + 1, b ascending, continues the id of a = side_b[i][b-1].best iff a != 0, side_a[i][a-1].best == b and
+ * (uint64)best_px * 256 >= (uint64)min_share_256 * px of that record; otherwise it gets the next fresh id.  Slots above
+ * min(n_regions[k], cap) get 0.  *n_tracks (may be null): the ids handed out.  HSFLOW_E_ARG: a null array or entry,
+ * n_steps < 0, cap 0, min_share_256 above 256; HSFLOW_E_SIZE: cap above 2^30. */
+int hsflow_link_tracks_host(const hsflow_link_side *const *side_a, const hsflow_link_side *const *side_b, const uint32_t *n_regions, int n_steps, uint32_t cap,
+                            uint32_t min_share_256, uint32_t *ids, uint32_t *n_tracks);
 
 /* --- the input files (cvLoadImage) ---------------------------------------------------------- */
 

@@ -151,6 +151,43 @@ class HsflowRegionsResult(ctypes.Structure):
 assert ctypes.sizeof(HsflowRegionsParams) == 32 and ctypes.sizeof(HsflowRegionsRecord) == 64 and ctypes.sizeof(HsflowRegionsResult) == 64
 
 
+LINK_MAX_CELLS = 1 << 24  # HSFLOW_LINK_MAX_CELLS
+LINK_FLAG_OVERFLOW = 1    # HSFLOW_LINK_FLAG_OVERFLOW
+
+
+class HsflowLinkParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("cap_a", ctypes.c_uint32), ("cap_b", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class HsflowLinkRecord(ctypes.Structure):
+    _fields_ = [("a", ctypes.c_uint32), ("b", ctypes.c_uint32), ("px", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class HsflowLinkSide(ctypes.Structure):
+    _fields_ = [("px", ctypes.c_uint32), ("n_links", ctypes.c_uint32), ("best", ctypes.c_uint32), ("best_px", ctypes.c_uint32),
+                ("gone_px", ctypes.c_uint32), ("unmatched_px", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class HsflowLinkResult(ctypes.Structure):
+    _fields_ = [("n_links", ctypes.c_uint32), ("n_written", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_mutual", ctypes.c_uint32),
+                ("voted_px", ctypes.c_uint64), ("gone_px", ctypes.c_uint64), ("unmatched_px", ctypes.c_uint64), ("over_a_px", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64 * 2)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+        d["overflow"] = bool(self.flags & LINK_FLAG_OVERFLOW)
+        return d
+
+
+assert ctypes.sizeof(HsflowLinkParams) == 16 and ctypes.sizeof(HsflowLinkRecord) == 16 and ctypes.sizeof(HsflowLinkSide) == 32 and ctypes.sizeof(HsflowLinkResult) == 64
+
+
 class HsflowMedianParams(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("radius", ctypes.c_int32), ("mode", ctypes.c_int32), ("min_votes", ctypes.c_int32)]
 
@@ -244,6 +281,8 @@ _gp = ctypes.POINTER(HsflowGmotionParams)
 _gr = ctypes.POINTER(HsflowGmotionResult)
 _rgp = ctypes.POINTER(HsflowRegionsParams)
 _rgr = ctypes.POINTER(HsflowRegionsResult)
+_lnp = ctypes.POINTER(HsflowLinkParams)
+_lnr = ctypes.POINTER(HsflowLinkResult)
 _f = ctypes.c_float
 _dp = ctypes.POINTER(HsflowPlaneDiff)
 _vr = ctypes.POINTER(HsflowVerifyReport)
@@ -363,6 +402,13 @@ PROTOTYPES = {
     "hsflow_regions_batch_device": (_i, [_vp, _i, _i, _vp, _sz, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _vp]),
     "hsflow_regions_device": (_i, [_vp, _i, _vp, _sz, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _vp]),
     "hsflow_regions": (_i, [_vp, _i, _vp, _sz, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _rgr]),
+    "hsflow_default_link_params": (None, [_lnp]),
+    "hsflow_link_regions_host": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _sz, _i, _i, _lnp, _vp, ctypes.c_uint32, _vp, _vp, _lnr]),
+    "hsflow_link_regions_planes_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _lnp, _vp, ctypes.c_uint32, _vp, _vp, _vp]),
+    "hsflow_link_regions_batch_device": (_i, [_vp, _i, _i, _vp, _sz, _lnp, _vp, ctypes.c_uint32, _vp, _vp, _vp]),
+    "hsflow_link_regions_device": (_i, [_vp, _i, _vp, _vp, _sz, _lnp, _vp, ctypes.c_uint32, _vp, _vp, _vp]),
+    "hsflow_link_regions": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _lnp, _vp, ctypes.c_uint32, _vp, _vp, _lnr]),
+    "hsflow_link_tracks_host": (_i, [_vp, _vp, _vp, _i, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp]),
     "hsflow_pyramid_plan": (_i, [_i, _i, _yp, _ip, _ip, _ip]),
     "hsflow_pyramid_down_host": (_i, [_vp, _sz, _i, _i, _vp, _sz]),
     "hsflow_pyramid_prolong_host": (_i, [_vp, _sz, _i, _i, _vp, _sz]),

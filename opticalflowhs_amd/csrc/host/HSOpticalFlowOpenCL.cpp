@@ -956,6 +956,104 @@ static int chain_batch(hsflow_ctx *ctx, int m, int W, int H, std::vector<float> 
     return SDK_SUCCESS;
 }
 
+// HSFLOW_CAMERA_OBJECTS=<min_area>[,<share 0..256>] on the batched "-cv -cam" route: every batch writes objects_%04d.txt
+// (numbered like the flow picture of its last pair), the moving objects of its pairs with ids that hold over the batch.  Per
+// batch, all on the device: the fit's foreground mask of every pair (HSFLOW_GMOTION selects the fit, mask values {0, 255, 0,
+// 0}), hsflow_regions_batch_device with min_area and 256 records, hsflow_link_regions_batch_device at caps 256 from each
+// pair's labels to the next pair's, then hsflow_link_tracks_host with the share (default 128) on the records that came back.
+// One line per region: "frame id area x0 y0 x1 y1 sum_x sum_y n_flow sum_qu sum_qv", frame the pair's old frame.  Ids start
+// at 1 in every batch.  0: not set, 1: usable, -1: unusable.
+constexpr uint32_t kObjectsCap = 256;
+
+static int camera_objects(uint32_t &min_area, uint32_t &share)
+{
+    min_area = 1; share = 128;
+    const char *e = getenv("HSFLOW_CAMERA_OBJECTS");
+    if (!e || !*e) return 0;
+    char *rest = nullptr;
+    const long a = strtol(e, &rest, 10);
+    if (rest == e || a < 1 || a > (1L << 30)) return -1;
+    min_area = (uint32_t)a;
+    if (!*rest) return 1;
+    if (*rest != ',') return -1;
+    const char *q = rest + 1;
+    const long sh = strtol(q, &rest, 10);
+    if (rest == q || *rest || sh < 0 || sh > 256) return -1;
+    share = (uint32_t)sh;
+    return 1;
+}
+
+// dBuf / dBufBytes: the batch's planes and records on the device, grown here and kept by the caller across the batches.
+static int objects_batch(hsflow_ctx *ctx, int m, int W, int H, int first_frame, uint32_t min_area, uint32_t share, const std::string &path, void *&dBuf,
+                         size_t &dBufBytes)
+{
+    hsflow_gmotion_params gp;
+    gmotion_choice(gp);
+    gp.value[0] = 0; gp.value[1] = 255; gp.value[2] = 0; gp.value[3] = 0;
+    hsflow_regions_params rp;
+    hsflow_default_regions_params(&rp);
+    rp.min_area = min_area;
+    hsflow_link_params lp;
+    hsflow_default_link_params(&lp);
+    lp.cap_a = lp.cap_b = kObjectsCap;
+    const size_t px = (size_t)W * H, rec_bytes = sizeof(hsflow_regions_record) * kObjectsCap, side_bytes = sizeof(hsflow_link_side) * kObjectsCap;
+    // what comes back first (heads, records, sides), then the label planes and the masks
+    const size_t back_bytes = (sizeof(hsflow_regions_result) + rec_bytes + 2 * side_bytes) * (size_t)m;
+    const size_t need = back_bytes + px * 5 * (size_t)m;
+    if (dBufBytes < need) {
+        if (dBuf) (void)hipFree(dBuf);
+        dBuf = nullptr; dBufBytes = 0;
+        if (hipMalloc(&dBuf, need) != hipSuccess) { std::cout << "hipMalloc of the objects' planes failed" << std::endl; return SDK_FAILURE; }
+        dBufBytes = need;
+    }
+    uint8_t *d = (uint8_t *)dBuf;
+    uint8_t *dHeads = d, *dRecs = dHeads + sizeof(hsflow_regions_result) * (size_t)m, *dSa = dRecs + rec_bytes * (size_t)m, *dSb = dSa + side_bytes * (size_t)m;
+    uint8_t *dLabels = d + back_bytes, *dMasks = dLabels + px * 4 * (size_t)m;
+    std::vector<void *> masks, labels, recs, sa, sb;
+    for (int k = 0; k < m; k++) {
+        masks.push_back(dMasks + px * (size_t)k);
+        labels.push_back(dLabels + px * 4 * (size_t)k);
+        recs.push_back(dRecs + rec_bytes * (size_t)k);
+        sa.push_back(dSa + side_bytes * (size_t)k);
+        sb.push_back(dSb + side_bytes * (size_t)k);
+    }
+    int st = hsflow_gmotion_fit_batch_device(ctx, 0, m, nullptr, 0, &gp, masks.data(), (size_t)W, nullptr, nullptr, 0, nullptr);
+    if (st == HSFLOW_OK)
+        st = hsflow_regions_batch_device(ctx, 0, m, (const void *const *)masks.data(), (size_t)W, &rp, labels.data(), (size_t)W * 4, recs.data(), kObjectsCap,
+                                         (hsflow_regions_result *)dHeads);
+    if (st == HSFLOW_OK && m > 1)
+        st = hsflow_link_regions_batch_device(ctx, 0, m - 1, (const void *const *)labels.data(), (size_t)W * 4, &lp, nullptr, 0, sa.data(), sb.data(), nullptr);
+    if (st == HSFLOW_OK) st = hsflow_synchronize(ctx);
+    std::vector<uint8_t> back(back_bytes);
+    const bool copied = st == HSFLOW_OK && hipMemcpy(back.data(), d, back_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+    if (!copied) { std::cout << "reading the objects' records failed" << std::endl; return SDK_FAILURE; }
+    const hsflow_regions_result *heads = (const hsflow_regions_result *)back.data();
+    const hsflow_regions_record *records = (const hsflow_regions_record *)(back.data() + (dRecs - d));
+    const hsflow_link_side *sides_a = (const hsflow_link_side *)(back.data() + (dSa - d)), *sides_b = (const hsflow_link_side *)(back.data() + (dSb - d));
+    std::vector<const hsflow_link_side *> pa, pb;
+    std::vector<uint32_t> counts;
+    for (int k = 0; k < m; k++) {
+        counts.push_back(heads[k].n_regions);
+        if (k + 1 < m) { pa.push_back(sides_a + (size_t)kObjectsCap * k); pb.push_back(sides_b + (size_t)kObjectsCap * k); }
+    }
+    std::vector<uint32_t> ids((size_t)m * kObjectsCap);
+    if (hsflow_link_tracks_host(pa.data(), pb.data(), counts.data(), m - 1, kObjectsCap, share, ids.data(), nullptr) != HSFLOW_OK) {
+        std::cout << hsflow_last_error(nullptr) << std::endl;
+        return SDK_FAILURE;
+    }
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) { std::cout << "cannot write " << path << std::endl; return SDK_FAILURE; }
+    for (int k = 0; k < m; k++)
+        for (uint32_t j = 0; j < heads[k].n_written; j++) {
+            const hsflow_regions_record &q = records[(size_t)kObjectsCap * k + j];
+            fprintf(f, "%d %u %u %u %u %u %u %llu %llu %u %lld %lld\n", first_frame + k, ids[(size_t)kObjectsCap * k + j], q.area, (unsigned)q.x0, (unsigned)q.y0,
+                    (unsigned)q.x1, (unsigned)q.y1, (unsigned long long)q.sum_x, (unsigned long long)q.sum_y, q.n_flow, (long long)q.sum_qu, (long long)q.sum_qv);
+        }
+    fclose(f);
+    return SDK_SUCCESS;
+}
+
 static bool ends_with_jpg(const std::string &s) { return s.size() >= 4 && s.compare(s.size() - 4, 4, ".jpg") == 0; }
 
 // The same loop with up to n + 1 frames read ahead: ONE hsflow_set_sequence_* call and ONE hsflow_solve per batch on a
@@ -965,7 +1063,7 @@ static bool ends_with_jpg(const std::string &s) { return s.size() >= 4 && s.comp
 // there (| HSFLOW_SEQ_REBLUR_FIRST).  A tail of m < n pairs gets a context of m pairs.  Gray frames are uploaded as they
 // are; with HSFLOW_JPEG_IN_DEVICE=1 and nothing but .jpg frames the files go to the device undecoded.  The flow_%04d.ppm
 // files are byte for byte those of the loop below.
-static int run_camera_batched(float lambda, int it, int nb, bool chain)
+static int run_camera_batched(float lambda, int it, int nb, bool chain, bool objects, uint32_t obj_min_area, uint32_t obj_share)
 {
     struct Frame {
         pnm::Image gray;           // the gray frame, or
@@ -1009,10 +1107,13 @@ static int run_camera_batched(float lambda, int it, int nb, bool chain)
     int ctx_pairs = 0;
     void *dFrames = nullptr; // the batch's gray frames on the device, packed
     size_t dBytes = 0;
+    void *dObjects = nullptr; // HSFLOW_CAMERA_OBJECTS: the planes and records of objects_batch
+    size_t dObjectsBytes = 0;
     const size_t frame_bytes = (size_t)W * H;
     auto done = [&](int code) {
         if (ctx) hsflow_destroy(ctx);
         if (dFrames) (void)hipFree(dFrames);
+        if (dObjects) (void)hipFree(dObjects);
         return code;
     };
     double total = 0.0;
@@ -1099,6 +1200,12 @@ static int run_camera_batched(float lambda, int it, int nb, bool chain)
             snprintf(name, sizeof(name), "chain %04d", count + m);
             std::cout << gmotion_line(name, r, W, H) << std::endl;
         }
+        if (objects && getenv("HSFLOW_CAMERA_OUT")) {
+            char name[64];
+            snprintf(name, sizeof(name), "/objects_%04d.txt", count + m);
+            if (objects_batch(ctx, m, W, H, count, obj_min_area, obj_share, std::string(getenv("HSFLOW_CAMERA_OUT")) + name, dObjects, dObjectsBytes) != SDK_SUCCESS)
+                return done(1);
+        }
         count += m;
         Frame last = std::move(batch.back()); // imgOld = imgNew :118, across the batches
         batch.clear();
@@ -1113,11 +1220,16 @@ int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
 {
     const int chain = camera_chain();
     if (chain < 0) { std::cout << "HSFLOW_CAMERA_CHAIN must be 0 or 1" << std::endl; return 1; }
+    uint32_t obj_min_area = 1, obj_share = 128;
+    const int objects = camera_objects(obj_min_area, obj_share);
+    if (objects < 0) { std::cout << "HSFLOW_CAMERA_OBJECTS must be <min_area 1 .. 2^30>[,<share 0 .. 256>]" << std::endl; return 1; }
+    if (objects && !getenv("HSFLOW_CAMERA_OUT")) { std::cout << "HSFLOW_CAMERA_OBJECTS needs HSFLOW_CAMERA_OUT, the directory of objects_%04d.txt" << std::endl; return 1; }
     if (const int nb = camera_batch()) {
         if (nb < 0) { std::cout << "HSFLOW_CAMERA_BATCH must be 1 .. 256" << std::endl; return 1; }
-        return run_camera_batched(lambda, it, nb, chain == 1);
+        return run_camera_batched(lambda, it, nb, chain == 1, objects == 1, obj_min_area, obj_share);
     }
     if (chain) { std::cout << "HSFLOW_CAMERA_CHAIN needs HSFLOW_CAMERA_BATCH=1 .. 256" << std::endl; return 1; }
+    if (objects) { std::cout << "HSFLOW_CAMERA_OBJECTS needs HSFLOW_CAMERA_BATCH=1 .. 256" << std::endl; return 1; }
     pnm::Image frame, gold, gnew;
     if (!pnm::load_image(camera_frame(0), frame)) { std::cout << "ERROR: capture is NULL \n"; return -1; }
     pnm::to_gray(frame, gold);                                   // cvCvtColor(imgTmp, imgOld, CV_BGR2GRAY) :79

@@ -28,6 +28,10 @@
 // centre cx cy motion mu mv" tell what moves; by the host rules from the flow read back, with HSFLOW_RENDER_DEVICE=1 on the
 // device with only the records read back; the same lines, the picture is unchanged (an unusable value: a message and exit
 // status 1).
+// HSFLOW_CAMERA_OBJECTS=<min_area>[,<share 0..256>] (the batched -cv -cam route, needs HSFLOW_CAMERA_BATCH and HSFLOW_CAMERA_OUT): every batch
+// writes objects_%04d.txt -- the regions of every pair's fit mask (hsflow_regions_batch_device), linked from pair to pair on the
+// device (hsflow_link_regions_batch_device) and given ids that hold over the batch (hsflow_link_tracks_host); one line "frame
+// id area x0 y0 x1 y1 sum_x sum_y n_flow sum_qu sum_qv" per region.  Ids restart with every batch.
 // HSFLOW_PICTURE=fb (the two -hd routes): the pair is solved forwards and, from the same pre-processed frames, backwards
 // (hsflow_set_frames_reversed), and the file is the forward-backward consistency mask (hsflow_fb*: 255 where the two flows
 // cancel, 0 elsewhere) as a gray picture; one line "fb: consistent .. inconsistent .. outside .. unknown .. mse .." tells

@@ -367,6 +367,18 @@ struct hsflow_ctx {
         size_t stage_bytes[3] = {0, 0, 0};
         hsflow_regions_result *dRes = nullptr, *hRes = nullptr;
     } regions;
+    // hsflow_link_regions* (hs_link.hip.h): the kernels' scratch (per step of the largest set of launches so far the rule's
+    // table of cap_a * cap_b + 2 * cap_a + 1 words, one count word per 256 cells and 2 + 2 * cap_a + cap_b words more; the
+    // call's first kernel clears the table, so nothing is carried over), allocated by the first call and grown; the
+    // staging of the synchronous form -- 0 labels of a, 1 labels of b, 2 links, 3 side_a, 4 side_b -- and one result header
+    // on the device and in page-locked memory.
+    struct LinkScratch {
+        void *scr = nullptr;
+        size_t bytes = 0;
+        uint8_t *stage[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        size_t stage_bytes[5] = {0, 0, 0, 0, 0};
+        hsflow_link_result *dRes = nullptr, *hRes = nullptr;
+    } link;
 };
 
 namespace {

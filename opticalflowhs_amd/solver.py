@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (HsflowRegionsParams, HsflowRegionsRecord, HsflowRegionsResult, HsflowGmotionParams, HsflowGmotionResult, GMOTION_TRANSLATION, GMOTION_SIMILARITY, GMOTION_AFFINE, GMOTION_THRESHOLD_FIXED, GMOTION_THRESHOLD_AUTO, COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowChainParams, HsflowChainStats, CHAIN_MAX_PAIRS, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (HsflowLinkParams, HsflowLinkRecord, HsflowLinkSide, HsflowLinkResult, HsflowRegionsParams, HsflowRegionsRecord, HsflowRegionsResult, HsflowGmotionParams, HsflowGmotionResult, GMOTION_TRANSLATION, GMOTION_SIMILARITY, GMOTION_AFFINE, GMOTION_THRESHOLD_FIXED, GMOTION_THRESHOLD_AUTO, COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowChainParams, HsflowChainStats, CHAIN_MAX_PAIRS, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -301,7 +301,7 @@ def _plane(x, height, width, dtype, what, device):
         raise ValueError("%s must be %s" % (what, "a CUDA tensor" if device else "a NumPy array"))
     if str(x.dtype) not in (dtype, "torch." + dtype) or tuple(x.shape) != (height, width):
         raise ValueError("%s must be %s of shape (height, width)" % (what, dtype))
-    size = 4 if dtype == "float32" else 1
+    size = 4 if dtype in ("float32", "int32") else 1
     strides = tuple(st * size for st in x.stride()) if device else x.strides
     if strides[1] != size:
         raise ValueError("%s must have packed elements" % what)
@@ -449,6 +449,56 @@ def _regions_call(height, width, device_index, mask, labels, records, capacity, 
     prm = params if params is not None else make_regions_params()
     rec, rref = _stats_record(HsflowRegionsResult, result, device, device_index)
     return (mp, ms, ctypes.byref(prm), lp, ls, rp_, capacity, rref), rec, labels, records
+
+
+def make_link_params(cap_a=64, cap_b=None):
+    """hsflow_link_params of a linking step: labels of frame k above `cap_a` only count into over_a_px, labels of frame
+    k + 1 above `cap_b` (None: cap_a) are unmatched; cap_a * cap_b is at most 2^24.  include/hsflow.h has the rule."""
+    lp = HsflowLinkParams()
+    _lib.load().hsflow_default_link_params(ctypes.byref(lp))
+    lp.cap_a, lp.cap_b = int(cap_a), int(cap_a if cap_b is None else cap_b)
+    return lp
+
+
+def _link_records(x, count, cls, what, device, device_index):
+    """One record array of the linking entries: x False / None (absent), True (`count` records of `cls` allocated here: on
+    the host a ctypes array, on the device a CUDA uint8 tensor) or such an array.  Returns (array, pointer)."""
+    size = ctypes.sizeof(cls)
+    if x is None or x is False:
+        return None, None
+    if x is True:
+        if device:
+            import torch
+            x = torch.empty(max(count, 1) * size, dtype=torch.uint8, device="cuda:%d" % device_index)
+        else:
+            x = (cls * max(count, 1))()
+    if device:
+        if not _is_device_tensor(x) or str(x.dtype) != "torch.uint8" or not x.is_contiguous() or x.numel() < count * size:
+            raise ValueError("%s must be a contiguous CUDA uint8 tensor of at least %d bytes" % (what, count * size))
+        return x, _ptr(x)
+    if ctypes.sizeof(x) < count * size:
+        raise ValueError("%s must hold at least %d records" % (what, count))
+    return x, ctypes.cast(x, ctypes.c_void_p)
+
+
+def _link_call(device_index, links, link_capacity, side_a, side_b, result, params, device):
+    """What the linking entries share from the params on: (the C call's arguments, result, links, side_a, side_b)."""
+    prm = params if params is not None else make_link_params()
+    link_capacity = int(link_capacity)
+    links, kp = _link_records(links, link_capacity, HsflowLinkRecord, "links", device, device_index)
+    side_a, ap = _link_records(side_a, prm.cap_a, HsflowLinkSide, "side_a", device, device_index)
+    side_b, bp = _link_records(side_b, prm.cap_b, HsflowLinkSide, "side_b", device, device_index)
+    rec, rref = _stats_record(HsflowLinkResult, result, device, device_index)
+    return (ctypes.byref(prm), kp, link_capacity, ap, bp, rref), rec, links, side_a, side_b
+
+
+def _link_list(items, n, count, cls, what):
+    """One list of record arrays of a device batch: None, or n entries, each None or a CUDA uint8 tensor."""
+    if items is None:
+        return None
+    if len(items) != n:
+        raise ValueError("%s must hold one entry per step" % what)
+    return (ctypes.c_void_p * n)(*[_link_records(x, count, cls, what, True, 0)[1].value if x is not None else None for x in items])
 
 
 def make_chain_params(values=(255, 0, 0, 0)):
@@ -1137,6 +1187,57 @@ class HSFlow(object):
                                                            _check_stats_tensor(results, n, HsflowRegionsResult)))
         return results
 
+    def link_regions(self, pair=0, labels_a=None, labels_b=None, links=True, link_capacity=256, side_a=True, side_b=True, result=True, params=None,
+                     device=False):
+        """The regions of frame k (int32 label plane `labels_a`, (H, W)) linked to those of frame k + 1 (`labels_b`) by the
+        current flow of `pair`: how many pixels of region a arrive in region b (`hsflow_link_regions[_device]`,
+        `make_link_params`; include/hsflow.h has the rule).  links, side_a, side_b: False, True (allocated here) or the
+        array; result: True or False.  Host planes: synchronous, the result an `HsflowLinkResult`, the links a ctypes array
+        of `HsflowLinkRecord` of which the first `n_written` are valid, the sides ctypes arrays of `HsflowLinkSide`.  CUDA
+        tensors (or device=True): only enqueued on the context's stream, everything a CUDA uint8 tensor that
+        `link_result_from` / `link_records_from` / `link_sides_from` read.  Returns (result, links, side_a, side_b), None for
+        what was not asked for."""
+        device = _chain_device(device, labels_a, labels_b)
+        (ap, as_), (bp, bs) = [_plane(x, self.height, self.width, "int32", "labels", device) for x in (labels_a, labels_b)]
+        args, rec, links, side_a, side_b = _link_call(self.device, links, link_capacity, side_a, side_b, result, params, device)
+        if device:
+            if as_ != bs:
+                raise ValueError("the two label planes share one row stride")
+            self._check(self._lib.hsflow_link_regions_device(self._h, int(pair), ap, bp, as_, *args))
+        else:
+            self._check(self._lib.hsflow_link_regions(self._h, int(pair), ap, as_, bp, bs, *args))
+        return rec, links, side_a, side_b
+
+    def link_regions_planes_device(self, labels_a, labels_b, u, v, links=True, link_capacity=256, side_a=True, side_b=True, result=True, params=None):
+        """`link_regions` on the device of caller planes: CUDA int32 label planes and CUDA float32 flow planes (H, W), u and
+        v of one row stride (`hsflow_link_regions_planes_device`).  Only enqueued."""
+        (ap, as_), (bp, bs) = [_plane(x, self.height, self.width, "int32", "labels", True) for x in (labels_a, labels_b)]
+        (up, us), (vp, vs) = [_plane(x, self.height, self.width, "float32", "flow", True) for x in (u, v)]
+        if us != vs:
+            raise ValueError("the two flow planes share one row stride")
+        args, rec, links, side_a, side_b = _link_call(self.device, links, link_capacity, side_a, side_b, result, params, True)
+        self._check(self._lib.hsflow_link_regions_planes_device(self._h, ap, as_, bp, bs, up, vp, us, *args))
+        return rec, links, side_a, side_b
+
+    def link_regions_batch_device(self, first_pair=0, n_steps=None, labels=None, links=None, link_capacity=256, side_a=None, side_b=None, results=None,
+                                  params=None):
+        """`link_regions` on the device for n_steps steps (None: all pairs from first_pair): step i links labels[i] to
+        labels[i + 1] -- n_steps + 1 CUDA int32 planes of one row stride -- by the flow of pair first_pair + i
+        (`hsflow_link_regions_batch_device`).  links, side_a, side_b: None, or lists of n_steps entries, each None or a
+        contiguous CUDA uint8 tensor of link_capacity * 16, cap_a * 32, cap_b * 32 bytes.  results: None, or a CUDA uint8
+        tensor of n_steps * 64 bytes (`link_result_from`).  Only enqueued."""
+        first_pair, n = self._batch_range(first_pair, n_steps)
+        prm = params if params is not None else make_link_params()
+        ll, ls = _chain_list(labels, n + 1, self.height, self.width, "int32", "labels", True)
+        if ll is None:
+            raise ValueError("labels is needed: n_steps + 1 planes")
+        self._check(self._lib.hsflow_link_regions_batch_device(self._h, first_pair, n, ll, ls, ctypes.byref(prm),
+                                                                _link_list(links, n, int(link_capacity), HsflowLinkRecord, "links"), int(link_capacity),
+                                                                _link_list(side_a, n, prm.cap_a, HsflowLinkSide, "side_a"),
+                                                                _link_list(side_b, n, prm.cap_b, HsflowLinkSide, "side_b"),
+                                                                _check_stats_tensor(results, n, HsflowLinkResult)))
+        return results
+
     def gmotion_warp(self, model, src, ref=None, out=None, t=1.0, border="constant", fill=0, return_stats=False, params=None, picture=True):
         """`src` warped backwards by the motion `model` (six floats or an `HsflowGmotionResult`) alone, no flow plane read
         (`hsflow_gmotion_warp[_device]`); everything else as `warp` takes and returns it."""
@@ -1584,6 +1685,70 @@ def regions_host(mask=None, u=None, v=None, labels=False, records=True, capacity
     if st != _lib.OK:
         raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
     return rec, labels, records
+
+
+def link_result_from(results, n=1):
+    """The `HsflowLinkResult` headers a device call left in the CUDA uint8 tensor `results` (after `synchronize()`): one
+    for n=1, else a list of n."""
+    raw = results.cpu().numpy().tobytes()
+    recs = [HsflowLinkResult.from_buffer_copy(raw[i * 64:(i + 1) * 64]) for i in range(n)]
+    return recs[0] if n == 1 else recs
+
+
+def link_records_from(links, n):
+    """The first n `HsflowLinkRecord` of a link array: a CUDA uint8 tensor (after `synchronize()`) or the ctypes array of
+    the host forms; a list."""
+    raw = links.cpu().numpy().tobytes() if _is_device_tensor(links) else bytes(links)
+    return [HsflowLinkRecord.from_buffer_copy(raw[i * 16:(i + 1) * 16]) for i in range(n)]
+
+
+def link_sides_from(sides, n):
+    """The first n `HsflowLinkSide` of a side array (record k - 1 is label k): a CUDA uint8 tensor (after `synchronize()`)
+    or the ctypes array of the host forms; a ctypes array, as `link_tracks` takes it."""
+    raw = sides.cpu().numpy().tobytes() if _is_device_tensor(sides) else bytes(sides)
+    return (HsflowLinkSide * n).from_buffer_copy(raw[:32 * n])
+
+
+def link_regions_host(labels_a, labels_b, u, v, links=True, link_capacity=256, side_a=True, side_b=True, result=True, params=None):
+    """A linking step by the rule on the host (`hsflow_link_regions_host`, no GPU work): int32 label arrays and float32
+    flow arrays of one shape (H, W), padded rows taken as they are.  links, link_capacity, side_a, side_b, result as
+    `HSFlow.link_regions` takes them.  Returns (result, links, side_a, side_b) -- byte for byte what the device forms give
+    from the same planes."""
+    u, v = (np.asarray(a, np.float32) for a in (u, v))
+    if u.ndim != 2 or u.shape != v.shape:
+        raise ValueError("u and v must be 2-D arrays of one shape")
+    if any(a.strides[1] != 4 or a.strides[0] % 4 for a in (u, v)) or u.strides[0] != v.strides[0]:
+        u, v = np.ascontiguousarray(u), np.ascontiguousarray(v)
+    H, W = u.shape
+    (ap, as_), (bp, bs) = [_plane(x, H, W, "int32", "labels", False) for x in (labels_a, labels_b)]
+    args, rec, links, side_a, side_b = _link_call(0, links, link_capacity, side_a, side_b, result, params, False)
+    st = _lib.load().hsflow_link_regions_host(ap, as_, bp, bs, _ptr(u), _ptr(v), u.strides[0], W, H, *args)
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return rec, links, side_a, side_b
+
+
+def link_tracks(side_a, side_b, n_regions, cap, min_share_256=128):
+    """Object ids over a chain of steps (`hsflow_link_tracks_host`): side_a, side_b lists of n_steps ctypes arrays of `cap`
+    `HsflowLinkSide` each (`link_sides_from`), n_regions the n_steps + 1 region counts of the frames.  A region continues
+    the id of its best sender when that is mutual and the sender gives it at least min_share_256 / 256 of its pixels; else
+    it starts a fresh id.  Returns (ids, n_tracks): ids a uint32 array (n_steps + 1, cap), ids[k, label - 1], 0 for slots
+    that hold no region."""
+    n_steps = len(side_a)
+    if len(side_b) != n_steps or len(n_regions) != n_steps + 1:
+        raise ValueError("side_a and side_b hold one array per step, n_regions one count per frame")
+    for x in list(side_a) + list(side_b):
+        if not isinstance(x, ctypes.Array) or ctypes.sizeof(x) < 32 * int(cap):
+            raise ValueError("a side array must be a ctypes array of at least cap HsflowLinkSide")
+    pa = (ctypes.c_void_p * max(n_steps, 1))(*[ctypes.addressof(x) for x in side_a])
+    pb = (ctypes.c_void_p * max(n_steps, 1))(*[ctypes.addressof(x) for x in side_b])
+    counts = (ctypes.c_uint32 * (n_steps + 1))(*[int(x) for x in n_regions])
+    ids = np.zeros((n_steps + 1, max(int(cap), 1)), np.uint32)
+    n_tracks = ctypes.c_uint32(0)
+    st = _lib.load().hsflow_link_tracks_host(pa, pb, counts, n_steps, int(cap), int(min_share_256), _ptr(ids), ctypes.byref(n_tracks))
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return ids, int(n_tracks.value)
 
 
 def global_motion_host(u, v, state=None, mask=False, residual=False, result=True, params=None):
