@@ -69,6 +69,10 @@
  *                                          no counterpart in the reference: the regions of consecutive pairs linked by
  *                                          the flow -- how many pixels of region a arrive in region b of the next frame --
  *                                          where labels and flow lie, and object ids over the sequence from those records
+ *   hsflow_corners[_host|_device|_batch_device|_planes_device]
+ *                                          cvGoodFeaturesToTrack of the reference's OpenCV 2.1, which the reference never
+ *                                          calls: the points worth following, found in the gray planes where they lie and
+ *                                          handed to hsflow_track_points_device without a read-back
  *   hsflow_set_frames_jpeg .............. cvLoadImage of both input files in front of it (OpticalFlowOpenCV.cpp:15,18,
  *                                          HSOpticalFlowOpenCL.cpp:721,732): the files' entropy-coded bytes cross PCIe,
  *                                          the pictures are decoded on the device
@@ -104,7 +108,7 @@ extern "C" {
 #endif
 
 #define HSFLOW_VERSION_MAJOR 0
-#define HSFLOW_VERSION_MINOR 25 /* 0.25: hsflow_link_regions[_host|_device|_batch_device|_planes_device], hsflow_link_tracks_host, hsflow_default_link_params, hsflow_link_params, hsflow_link_record, hsflow_link_side, hsflow_link_result, HSFLOW_LINK_*; 0.24: hsflow_regions[_host|_device|_batch_device|_planes_device], hsflow_default_regions_params, hsflow_regions_params, hsflow_regions_record, hsflow_regions_result, HSFLOW_REGIONS_*; 0.23: hsflow_gmotion_fit[_host|_device|_batch_device|_planes_device], hsflow_gmotion_warp[_host|_device], hsflow_gmotion_compose_host, hsflow_gmotion_invert_host, hsflow_default_gmotion_params, hsflow_gmotion_params, hsflow_gmotion_result, HSFLOW_GMOTION_*; 0.22: hsflow_chain_flow[_host|_device], hsflow_chain_planes_device, hsflow_track_points[_host|_device], hsflow_default_chain_params, hsflow_chain_params, hsflow_chain_stats, HSFLOW_CHAIN_*; 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
+#define HSFLOW_VERSION_MINOR 26 /* 0.26: hsflow_corners[_host|_device|_batch_device|_planes_device], hsflow_default_corners_params, hsflow_corners_params, hsflow_corners_record, hsflow_corners_result, HSFLOW_CORNERS_*; 0.25: hsflow_link_regions[_host|_device|_batch_device|_planes_device], hsflow_link_tracks_host, hsflow_default_link_params, hsflow_link_params, hsflow_link_record, hsflow_link_side, hsflow_link_result, HSFLOW_LINK_*; 0.24: hsflow_regions[_host|_device|_batch_device|_planes_device], hsflow_default_regions_params, hsflow_regions_params, hsflow_regions_record, hsflow_regions_result, HSFLOW_REGIONS_*; 0.23: hsflow_gmotion_fit[_host|_device|_batch_device|_planes_device], hsflow_gmotion_warp[_host|_device], hsflow_gmotion_compose_host, hsflow_gmotion_invert_host, hsflow_default_gmotion_params, hsflow_gmotion_params, hsflow_gmotion_result, HSFLOW_GMOTION_*; 0.22: hsflow_chain_flow[_host|_device], hsflow_chain_planes_device, hsflow_track_points[_host|_device], hsflow_default_chain_params, hsflow_chain_params, hsflow_chain_stats, HSFLOW_CHAIN_*; 0.21: hsflow_solve_pyramid, hsflow_pyramid_plan, hsflow_pyramid_down_host, hsflow_pyramid_prolong_host, hsflow_get_pyramid_info, hsflow_pyramid_get_level, hsflow_default_pyramid_params, hsflow_pyramid_params, hsflow_pyramid_info, HSFLOW_PYRAMID_*; 0.20: hsflow_interp[_host|_device|_batch_device], hsflow_project_flow_host, hsflow_project_flow_device, hsflow_pipeline_interp[_device], hsflow_default_interp_params, hsflow_interp_params, hsflow_interp_stats, HSFLOW_INTERP_*; 0.19: hsflow_median[_host|_device|_batch_device|_planes_device|_apply], hsflow_pipeline_median[_apply], hsflow_default_median_params, hsflow_median_params, hsflow_median_stats, HSFLOW_MEDIAN_*; 0.18: hsflow_fb[_host|_device|_batch_device|_planes_device|_planes], hsflow_set_frames_reversed, hsflow_pipeline_fb[_device], hsflow_default_fb_params, hsflow_fb_params, hsflow_fb_stats, HSFLOW_FB_*; 0.17: hsflow_warp[_host|_device|_batch_device], hsflow_pipeline_warp[_device], hsflow_default_warp_params, hsflow_warp_params, hsflow_warp_stats, HSFLOW_WARP_BORDER_*; 0.16: hsflow_color_flow[_host|_device|_batch_device], hsflow_color_flow_jpeg[_device|_batch|_batch_device], hsflow_pipeline_color[_device|_jpeg], hsflow_color_params, HSFLOW_COLOR_SCALE_*; 0.15: hsflow_set_flow_device_ex, HSFLOW_FLOW_SOLVER_MADE; 0.14: hsflow_set_sequence_device_ex, hsflow_set_sequence_jpeg_ex, hsflow_preprocess_sequence_host, HSFLOW_SEQ_REBLUR[_FIRST], HSFLOW_PRE_SEQ_MAX; 0.13: hsflow_jpeg_encode_batch_device, hsflow_render_flow_batch_device, hsflow_render_flow_jpeg_batch[_device], HSFLOW_JPEG_BATCH_MAX; 0.12: hsflow_jpeg_decode_batch_device, hsflow_set_sequence_jpeg, hsflow_set_frames_jpeg_async, hsflow_jpeg_async_status, hsflow_pipeline_submit_jpeg, HSFLOW_JPEGD_BATCH_MAX; 0.11: hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg, HSFLOW_E_DATA; 0.10: hsflow_jpeg_*, hsflow_render_flow_jpeg[_device], hsflow_pipeline_render_jpeg; 0.9: hsflow_set_frames_device_ex, hsflow_push_frame[_device]_ex, hsflow_pipeline_submit_device_ex, hsflow_preprocess_frame_host; 0.8: hsflow_set_pair_termination, hsflow_get_pair_result, hsflow_solve_probe_pairs; 0.7: hsflow_verify, hsflow_compare_*, hsflow_pipeline_verify; 0.6: hsflow_render_*, hsflow_pipeline_render*; 0.5: hsflow_multi_*, hsflow_slab_*, hsflow_set_row_origin, hsflow_get_info_ex */
 
 /* status codes (0 = success, like SDK_SUCCESS) */
 #define HSFLOW_OK 0
@@ -1724,7 +1728,112 @@ int hsflow_link_regions(hsflow_ctx *ctx, int pair, const int32_t *labels_a, size
 int hsflow_link_tracks_host(const hsflow_link_side *const *side_a, const hsflow_link_side *const *side_b, const uint32_t *n_regions, int n_steps, uint32_t cap,
                             uint32_t min_share_256, uint32_t *ids, uint32_t *n_tracks);
 
-/* --- the input files (cvLoadImage) ---------------------------------------------------------- */
+/* --- which points to follow: corner detection (0.26) ----------------------------------------- */
+
+/* The corners of a u8 gray frame -- the points hsflow_track_points* is worth feeding -- found where the frames lie.  The rule
+ * is csrc/hs_corners_rule.h, one header for the host form and the kernels; everything in it is an integer, so the device
+ * and the host agree byte for byte whatever the order of execution.  OpenCV 2.1 has cvGoodFeaturesToTrack for this; its
+ * floating point and its sequential greedy pass over a sorted list are deliberately not reproduced.  A pixel's index is
+ * y * width + x.
+ *   Gradients.  The 3 x 3 Sobel pair with coordinates clamped to the frame: Ix, Iy in -1020 .. 1020.
+ *   Structure tensor.  A = sum Ix^2, B = sum Ix Iy, C = sum Iy^2 over the (2 block_r + 1)^2 window, block_r in 1 .. 3, the
+ *   window's coordinates clamped to the frame as well.
+ *   Score, an int64.  HSFLOW_CORNERS_MIN_EIGEN: S = (A + C) - ceil(sqrt((A - C)^2 + 4 B^2)), twice the smaller eigenvalue
+ *   rounded down, the root an exact integer root; S >= 0.  HSFLOW_CORNERS_HARRIS: S = 25 (A C - B^2) - (A + C)^2, the
+ *   Harris measure with k = 1 / 25 scaled by 25; |S| < 7e16.
+ *   Allowed.  A pixel whose mask byte lies in fg_lo .. fg_hi (no mask: every pixel) and that lies at least `border` pixels
+ *   from every frame edge.  A pixel that is not allowed is no corner and does not count towards the maximum; it still
+ *   competes in the suppression, so a mask never creates corners.
+ *   Threshold.  smax = max(0, max S over the allowed pixels); T = max(min_score, (smax >> 16) * quality_q16).
+ *   Strong.  Allowed and S >= T.
+ *   Survivors.  A strong pixel p that beats every other pixel q of the frame with max(|dx|, |dy|) <= nms_r (1 .. 8): p beats
+ *   q iff S_p > S_q, or S_p == S_q and index_p < index_q.  No two survivors are closer than nms_r + 1 in either axis: the
+ *   operator's minimum distance.
+ *   Candidates.  The first max_candidates (1 .. HSFLOW_CORNERS_MAX_CANDIDATES) survivors in ascending index; more
+ *   survivors set HSFLOW_CORNERS_FLAG_TRUNCATED (the remedy: a higher quality, a larger radius).
+ *   Corners.  The candidates by descending S, ties by ascending index; the first `capacity` are the output.
+ *   Outputs, each may be absent, at least one asked for:
+ *     records  `capacity` records of 16 bytes, record k the corner of rank k; records from n_written on are left alone;
+ *     xy       `capacity` pairs of floats, ((float)x, (float)y) for rank k < n_written, both floats of every later pair
+ *              the quiet NaN 0x7fc00000: the array goes to hsflow_track_points_device with m = capacity as it is and the
+ *              empty slots come back UNKNOWN.  All capacity pairs are written;
+ *     result   64 bytes: n_survivors, n_candidates = min(n_survivors, max_candidates), n_written = min(n_candidates,
+ *              capacity), flags (TRUNCATED; HSFLOW_CORNERS_FLAG_OVERFLOW: n_candidates > capacity), smax, threshold,
+ *              allowed_px, strong_px.  capacity counts whether or not an array is given.
+ *   Not covered: the tickets of a pair pipeline, hsflow_multi_* and slabs have no corners entry.
+ * Time on an MI355X (profiles/corners_time.txt): see the summary there. */
+#define HSFLOW_CORNERS_MIN_EIGEN 0
+#define HSFLOW_CORNERS_HARRIS 1
+#define HSFLOW_CORNERS_MAX_SIDE 16384
+#define HSFLOW_CORNERS_MAX_CANDIDATES 65536u
+#define HSFLOW_CORNERS_MAX_CAPACITY (1u << 24)
+#define HSFLOW_CORNERS_FLAG_OVERFLOW 1u
+#define HSFLOW_CORNERS_FLAG_TRUNCATED 2u
+typedef struct hsflow_corners_params { /* 64 bytes */
+    uint32_t struct_size;    /* = sizeof(hsflow_corners_params)            */
+    int32_t kind;            /* HSFLOW_CORNERS_MIN_EIGEN or _HARRIS        */
+    int32_t block_r;         /* 1 .. 3                                     */
+    int32_t nms_r;           /* 1 .. 8                                     */
+    uint32_t quality_q16;    /* 0 .. 65535, in 1 / 65536 of the maximum    */
+    int32_t border;          /* >= 0                                       */
+    int32_t fg_lo, fg_hi;    /* 0 <= fg_lo <= fg_hi <= 255                 */
+    uint32_t max_candidates; /* 1 .. HSFLOW_CORNERS_MAX_CANDIDATES         */
+    uint32_t reserved0;      /* 0                                          */
+    int64_t min_score;       /* >= 1                                       */
+    uint64_t reserved[2];    /* 0                                          */
+} hsflow_corners_params;
+typedef struct hsflow_corners_record { /* 16 bytes, the same on the device and on the host */
+    uint16_t x, y;
+    uint32_t index; /* y * width + x */
+    int64_t score;
+} hsflow_corners_record;
+typedef struct hsflow_corners_result { /* 64 bytes, the same on the device and on the host */
+    uint32_t n_survivors, n_candidates, n_written, flags;
+    int64_t smax, threshold;
+    uint64_t allowed_px, strong_px;
+    uint64_t reserved[2];
+} hsflow_corners_result;
+/* MIN_EIGEN, block_r 1, nms_r 3, quality_q16 655 (about 1 %), border 0, mask bytes 1 .. 255, max_candidates 65536,
+ * min_score 1.  NULL is ignored. */
+void hsflow_default_corners_params(hsflow_corners_params *cp);
+/* The rule on the host, no device needed: gray a u8 plane of width x height, rows stride bytes apart; mask NULL or such a
+ * plane, rows mask_stride bytes apart.  records, xy and result may each be null, not all.
+ * HSFLOW_E_ARG: null gray or cp, wrong struct_size, reserved not 0, an unknown kind, block_r outside 1 .. 3, nms_r outside
+ * 1 .. 8, quality_q16 above 65535, border negative, fg_lo > fg_hi or outside 0 .. 255, max_candidates outside
+ * 1 .. 65536, min_score below 1, records or result not 8-byte aligned, xy not 4-byte aligned, nothing asked for, an output
+ * that overlaps an input or another output;
+ * HSFLOW_E_SIZE: a non-positive size, a side above 16384, a gray or mask stride below width, a capacity above 2^24. */
+int hsflow_corners_host(const uint8_t *gray, size_t stride, int width, int height, const uint8_t *mask /* may be null */, size_t mask_stride,
+                        const hsflow_corners_params *cp, hsflow_corners_record *records /* may be null */, uint32_t capacity, float *xy /* may be null */,
+                        hsflow_corners_result *result /* may be null */);
+/* Planes anywhere on ctx's device, of the context's width and height.  Only enqueued on ctx's stream: one memset of 32 bytes
+ * per field and a fixed sequence of six launches that does not depend on the data, no wait on the host and none between
+ * workgroups, nothing read back.  The outputs are those of hsflow_corners_host from the same planes.  The caller orders the
+ * producers of the planes before ctx's stream.  The ordering rules of hsflow_fb_batch_device apply word for word.  The
+ * scratch -- per field of the largest set of launches so far a score plane of 8 * width * height bytes, 36 bytes per 256
+ * pixels of a row and 1 MiB of candidates -- is allocated by the first call, grown and kept until hsflow_destroy; a context
+ * that never asks for corners pays nothing.  Every argument is checked before anything is enqueued.  Errors as the host
+ * form. */
+int hsflow_corners_planes_device(hsflow_ctx *ctx, const void *d_gray, size_t stride, const void *d_mask, size_t mask_stride, const hsflow_corners_params *cp,
+                                 hsflow_corners_record *d_records, uint32_t capacity, float *d_xy, hsflow_corners_result *d_result);
+/* The pairs first_pair .. first_pair + n - 1 of the context, each with the context's own pre-processed gray plane of that
+ * pair -- which 0: the prev frame, 1: the curr frame; what hsflow_get_frames_u8 hands out -- by ONE set of launches (8
+ * pairs per set).  d_mask, d_records, d_xy: NULL, or host arrays of n device pointers, free on return, whose entries may be
+ * NULL (every pixel passes / no such output for that pair); d_results: NULL or n headers.  The frames are read and never
+ * changed; no output may lie in them.  HSFLOW_E_ARG also: n < 1, first_pair < 0, first_pair + n > n_pairs, which neither 0
+ * nor 1; HSFLOW_E_STATE: no frames were set. */
+int hsflow_corners_batch_device(hsflow_ctx *ctx, int first_pair, int n, int which, const void *const *d_mask, size_t mask_stride,
+                                const hsflow_corners_params *cp, void *const *d_records, uint32_t capacity, void *const *d_xy, hsflow_corners_result *d_results);
+/* A batch of one. */
+int hsflow_corners_device(hsflow_ctx *ctx, int pair, int which, const void *d_mask, size_t mask_stride, const hsflow_corners_params *cp,
+                          hsflow_corners_record *d_records, uint32_t capacity, float *d_xy, hsflow_corners_result *d_result);
+/* The same with the mask from host memory and the outputs in host memory, synchronous: complete on return.  Waits only for
+ * events behind its own work, like hsflow_regions; only the n_written records cross, and all capacity pairs of xy.  The
+ * staging is allocated by the first call that needs a piece, grown and kept until hsflow_destroy. */
+int hsflow_corners(hsflow_ctx *ctx, int pair, int which, const uint8_t *mask, size_t mask_stride, const hsflow_corners_params *cp,
+                   hsflow_corners_record *records, uint32_t capacity, float *xy, hsflow_corners_result *result);
+
+/* --- the input files (cvLoadImage)---------------------------------------------------------- */
 
 /* The reference reads its two frames with cvLoadImage(path, 1) (OpticalFlowOpenCV.cpp:15,18, HSOpticalFlowOpenCL.cpp:721,
  * 732): libjpeg with its defaults -- baseline Huffman decoding, the "islow" inverse DCT, "fancy" triangle upsampling of

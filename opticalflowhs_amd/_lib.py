@@ -151,6 +151,43 @@ class HsflowRegionsResult(ctypes.Structure):
 assert ctypes.sizeof(HsflowRegionsParams) == 32 and ctypes.sizeof(HsflowRegionsRecord) == 64 and ctypes.sizeof(HsflowRegionsResult) == 64
 
 
+CORNERS_MIN_EIGEN = 0             # HSFLOW_CORNERS_MIN_EIGEN
+CORNERS_HARRIS = 1                # HSFLOW_CORNERS_HARRIS
+CORNERS_MAX_SIDE = 16384          # HSFLOW_CORNERS_MAX_SIDE
+CORNERS_MAX_CANDIDATES = 65536    # HSFLOW_CORNERS_MAX_CANDIDATES
+CORNERS_MAX_CAPACITY = 1 << 24    # HSFLOW_CORNERS_MAX_CAPACITY
+CORNERS_FLAG_OVERFLOW = 1         # HSFLOW_CORNERS_FLAG_OVERFLOW
+CORNERS_FLAG_TRUNCATED = 2        # HSFLOW_CORNERS_FLAG_TRUNCATED
+
+
+class HsflowCornersParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("kind", ctypes.c_int32), ("block_r", ctypes.c_int32), ("nms_r", ctypes.c_int32),
+                ("quality_q16", ctypes.c_uint32), ("border", ctypes.c_int32), ("fg_lo", ctypes.c_int32), ("fg_hi", ctypes.c_int32),
+                ("max_candidates", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("min_score", ctypes.c_int64), ("reserved", ctypes.c_uint64 * 2)]
+
+
+class HsflowCornersRecord(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_uint16), ("y", ctypes.c_uint16), ("index", ctypes.c_uint32), ("score", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class HsflowCornersResult(ctypes.Structure):
+    _fields_ = [("n_survivors", ctypes.c_uint32), ("n_candidates", ctypes.c_uint32), ("n_written", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("smax", ctypes.c_int64), ("threshold", ctypes.c_int64), ("allowed_px", ctypes.c_uint64), ("strong_px", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64 * 2)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+        d["overflow"] = bool(self.flags & CORNERS_FLAG_OVERFLOW)
+        d["truncated"] = bool(self.flags & CORNERS_FLAG_TRUNCATED)
+        return d
+
+
+assert ctypes.sizeof(HsflowCornersParams) == 64 and ctypes.sizeof(HsflowCornersRecord) == 16 and ctypes.sizeof(HsflowCornersResult) == 64
+
+
 LINK_MAX_CELLS = 1 << 24  # HSFLOW_LINK_MAX_CELLS
 LINK_FLAG_OVERFLOW = 1    # HSFLOW_LINK_FLAG_OVERFLOW
 
@@ -281,6 +318,8 @@ _gp = ctypes.POINTER(HsflowGmotionParams)
 _gr = ctypes.POINTER(HsflowGmotionResult)
 _rgp = ctypes.POINTER(HsflowRegionsParams)
 _rgr = ctypes.POINTER(HsflowRegionsResult)
+_cnp = ctypes.POINTER(HsflowCornersParams)
+_cnr = ctypes.POINTER(HsflowCornersResult)
 _lnp = ctypes.POINTER(HsflowLinkParams)
 _lnr = ctypes.POINTER(HsflowLinkResult)
 _f = ctypes.c_float
@@ -402,6 +441,12 @@ PROTOTYPES = {
     "hsflow_regions_batch_device": (_i, [_vp, _i, _i, _vp, _sz, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _vp]),
     "hsflow_regions_device": (_i, [_vp, _i, _vp, _sz, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _vp]),
     "hsflow_regions": (_i, [_vp, _i, _vp, _sz, _rgp, _vp, _sz, _vp, ctypes.c_uint32, _rgr]),
+    "hsflow_default_corners_params": (None, [_cnp]),
+    "hsflow_corners_host": (_i, [_vp, _sz, _i, _i, _vp, _sz, _cnp, _vp, ctypes.c_uint32, _vp, _cnr]),
+    "hsflow_corners_planes_device": (_i, [_vp, _vp, _sz, _vp, _sz, _cnp, _vp, ctypes.c_uint32, _vp, _vp]),
+    "hsflow_corners_batch_device": (_i, [_vp, _i, _i, _i, _vp, _sz, _cnp, _vp, ctypes.c_uint32, _vp, _vp]),
+    "hsflow_corners_device": (_i, [_vp, _i, _i, _vp, _sz, _cnp, _vp, ctypes.c_uint32, _vp, _vp]),
+    "hsflow_corners": (_i, [_vp, _i, _i, _vp, _sz, _cnp, _vp, ctypes.c_uint32, _vp, _cnr]),
     "hsflow_default_link_params": (None, [_lnp]),
     "hsflow_link_regions_host": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _sz, _i, _i, _lnp, _vp, ctypes.c_uint32, _vp, _vp, _lnr]),
     "hsflow_link_regions_planes_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _lnp, _vp, ctypes.c_uint32, _vp, _vp, _vp]),

@@ -1054,6 +1054,89 @@ static int objects_batch(hsflow_ctx *ctx, int m, int W, int H, int first_frame, 
     return SDK_SUCCESS;
 }
 
+// HSFLOW_CAMERA_POINTS=<n>[,<quality_q16>[,<nms_r>]] on the batched "-cv -cam" route: every batch writes points_%04d.txt
+// (numbered like the flow picture of its last pair).  Per batch, all on the device: the n best corners of the batch's first
+// frame as the context holds it (hsflow_corners_device, pair 0, the prev plane; the defaults but for quality and radius),
+// whose xy array goes as it is into hsflow_track_points_device over the batch's pairs (its first HSFLOW_CHAIN_MAX_PAIRS, if
+// the batch is longer) -- no read-back in between.  One line per written corner: "rank x0 y0 score x y status age", x0 y0
+// the corner, x y where the flows took it (nan once it is lost), status and age the tracker's.  0: not set, 1: usable,
+// -1: unusable.
+static int camera_points(uint32_t &n, uint32_t &quality, int &nms_r)
+{
+    hsflow_corners_params cp;
+    hsflow_default_corners_params(&cp);
+    n = 0; quality = cp.quality_q16; nms_r = cp.nms_r;
+    const char *e = getenv("HSFLOW_CAMERA_POINTS");
+    if (!e || !*e) return 0;
+    char *rest = nullptr;
+    const long a = strtol(e, &rest, 10);
+    if (rest == e || a < 1 || a > (long)HSFLOW_CORNERS_MAX_CANDIDATES) return -1;
+    n = (uint32_t)a;
+    if (!*rest) return 1;
+    if (*rest != ',') return -1;
+    const char *q = rest + 1;
+    const long qu = strtol(q, &rest, 10);
+    if (rest == q || qu < 0 || qu > 65535) return -1;
+    quality = (uint32_t)qu;
+    if (!*rest) return 1;
+    if (*rest != ',') return -1;
+    q = rest + 1;
+    const long r = strtol(q, &rest, 10);
+    if (rest == q || *rest || r < 1 || r > 8) return -1;
+    nms_r = (int)r;
+    return 1;
+}
+
+// dBuf / dBufBytes: the batch's records and points on the device, grown here and kept by the caller across the batches.
+static int points_batch(hsflow_ctx *ctx, int m, uint32_t n, uint32_t quality, int nms_r, const std::string &path, void *&dBuf, size_t &dBufBytes)
+{
+    hsflow_corners_params cp;
+    hsflow_default_corners_params(&cp);
+    cp.quality_q16 = quality;
+    cp.nms_r = nms_r;
+    hsflow_chain_params chp;
+    hsflow_default_chain_params(&chp);
+    // what comes back (header, records, last positions, status, age), then the corners' xy, which stays on the device
+    const size_t rec_bytes = sizeof(hsflow_corners_record) * (size_t)n, xy_bytes = 8 * (size_t)n, byte_bytes = ((size_t)n + 7) & ~(size_t)7;
+    const size_t back_bytes = sizeof(hsflow_corners_result) + rec_bytes + xy_bytes + 2 * byte_bytes, need = back_bytes + xy_bytes;
+    if (dBufBytes < need) {
+        if (dBuf) (void)hipFree(dBuf);
+        dBuf = nullptr; dBufBytes = 0;
+        if (hipMalloc(&dBuf, need) != hipSuccess) { std::cout << "hipMalloc of the points failed" << std::endl; return SDK_FAILURE; }
+        dBufBytes = need;
+    }
+    uint8_t *d = (uint8_t *)dBuf;
+    uint8_t *dHead = d, *dRecs = dHead + sizeof(hsflow_corners_result), *dLast = dRecs + rec_bytes, *dStatus = dLast + xy_bytes, *dAge = dStatus + byte_bytes;
+    uint8_t *dXy = d + back_bytes;
+    const int steps = m < HSFLOW_CHAIN_MAX_PAIRS ? m : HSFLOW_CHAIN_MAX_PAIRS;
+    int pairs[HSFLOW_CHAIN_MAX_PAIRS];
+    for (int k = 0; k < steps; k++) pairs[k] = k;
+    int st = hsflow_corners_device(ctx, 0, 0, nullptr, 0, &cp, (hsflow_corners_record *)dRecs, n, (float *)dXy, (hsflow_corners_result *)dHead);
+    if (st == HSFLOW_OK) st = hsflow_track_points_device(ctx, pairs, steps, nullptr, 0, &chp, (const float *)dXy, (int)n, nullptr, (float *)dLast, dStatus, dAge, nullptr);
+    if (st == HSFLOW_OK) st = hsflow_synchronize(ctx);
+    std::vector<uint8_t> back(back_bytes);
+    const bool copied = st == HSFLOW_OK && hipMemcpy(back.data(), d, back_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    if (st != HSFLOW_OK) { std::cout << hsflow_last_error(ctx) << std::endl; return SDK_FAILURE; }
+    if (!copied) { std::cout << "reading the points failed" << std::endl; return SDK_FAILURE; }
+    const hsflow_corners_result *head = (const hsflow_corners_result *)back.data();
+    const hsflow_corners_record *recs = (const hsflow_corners_record *)(back.data() + (dRecs - d));
+    const float *last = (const float *)(back.data() + (dLast - d));
+    const uint8_t *status = back.data() + (dStatus - d), *age = back.data() + (dAge - d);
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) { std::cout << "cannot write " << path << std::endl; return SDK_FAILURE; }
+    auto num = [](float a) {
+        char text[32];
+        if (a != a) snprintf(text, sizeof(text), "nan");
+        else snprintf(text, sizeof(text), "%.9g", (double)a);
+        return std::string(text);
+    };
+    for (uint32_t k = 0; k < head->n_written; k++)
+        fprintf(f, "%u %u %u %lld %s %s %u %u\n", k, (unsigned)recs[k].x, (unsigned)recs[k].y, (long long)recs[k].score, num(last[2 * k]).c_str(),
+                num(last[2 * k + 1]).c_str(), (unsigned)status[k], (unsigned)age[k]);
+    fclose(f);
+    return SDK_SUCCESS;
+}
+
 static bool ends_with_jpg(const std::string &s) { return s.size() >= 4 && s.compare(s.size() - 4, 4, ".jpg") == 0; }
 
 // The same loop with up to n + 1 frames read ahead: ONE hsflow_set_sequence_* call and ONE hsflow_solve per batch on a
@@ -1063,7 +1146,9 @@ static bool ends_with_jpg(const std::string &s) { return s.size() >= 4 && s.comp
 // there (| HSFLOW_SEQ_REBLUR_FIRST).  A tail of m < n pairs gets a context of m pairs.  Gray frames are uploaded as they
 // are; with HSFLOW_JPEG_IN_DEVICE=1 and nothing but .jpg frames the files go to the device undecoded.  The flow_%04d.ppm
 // files are byte for byte those of the loop below.
-static int run_camera_batched(float lambda, int it, int nb, bool chain, bool objects, uint32_t obj_min_area, uint32_t obj_share)
+// pts_n: the corners of HSFLOW_CAMERA_POINTS, 0 without it.
+static int run_camera_batched(float lambda, int it, int nb, bool chain, bool objects, uint32_t obj_min_area, uint32_t obj_share, uint32_t pts_n,
+                              uint32_t pts_quality, int pts_nms_r)
 {
     struct Frame {
         pnm::Image gray;           // the gray frame, or
@@ -1109,11 +1194,14 @@ static int run_camera_batched(float lambda, int it, int nb, bool chain, bool obj
     size_t dBytes = 0;
     void *dObjects = nullptr; // HSFLOW_CAMERA_OBJECTS: the planes and records of objects_batch
     size_t dObjectsBytes = 0;
+    void *dPoints = nullptr; // HSFLOW_CAMERA_POINTS: the records and points of points_batch
+    size_t dPointsBytes = 0;
     const size_t frame_bytes = (size_t)W * H;
     auto done = [&](int code) {
         if (ctx) hsflow_destroy(ctx);
         if (dFrames) (void)hipFree(dFrames);
         if (dObjects) (void)hipFree(dObjects);
+        if (dPoints) (void)hipFree(dPoints);
         return code;
     };
     double total = 0.0;
@@ -1206,6 +1294,11 @@ static int run_camera_batched(float lambda, int it, int nb, bool chain, bool obj
             if (objects_batch(ctx, m, W, H, count, obj_min_area, obj_share, std::string(getenv("HSFLOW_CAMERA_OUT")) + name, dObjects, dObjectsBytes) != SDK_SUCCESS)
                 return done(1);
         }
+        if (pts_n && getenv("HSFLOW_CAMERA_OUT")) {
+            char name[64];
+            snprintf(name, sizeof(name), "/points_%04d.txt", count + m);
+            if (points_batch(ctx, m, pts_n, pts_quality, pts_nms_r, std::string(getenv("HSFLOW_CAMERA_OUT")) + name, dPoints, dPointsBytes) != SDK_SUCCESS) return done(1);
+        }
         count += m;
         Frame last = std::move(batch.back()); // imgOld = imgNew :118, across the batches
         batch.clear();
@@ -1224,12 +1317,18 @@ int OpticalFlowOpenCV::runFromCamera(float lambda, int it)
     const int objects = camera_objects(obj_min_area, obj_share);
     if (objects < 0) { std::cout << "HSFLOW_CAMERA_OBJECTS must be <min_area 1 .. 2^30>[,<share 0 .. 256>]" << std::endl; return 1; }
     if (objects && !getenv("HSFLOW_CAMERA_OUT")) { std::cout << "HSFLOW_CAMERA_OBJECTS needs HSFLOW_CAMERA_OUT, the directory of objects_%04d.txt" << std::endl; return 1; }
+    uint32_t pts_n = 0, pts_quality = 0;
+    int pts_nms_r = 0;
+    const int points = camera_points(pts_n, pts_quality, pts_nms_r);
+    if (points < 0) { std::cout << "HSFLOW_CAMERA_POINTS must be <n 1 .. 65536>[,<quality_q16 0 .. 65535>[,<nms_r 1 .. 8>]]" << std::endl; return 1; }
+    if (points && !getenv("HSFLOW_CAMERA_OUT")) { std::cout << "HSFLOW_CAMERA_POINTS needs HSFLOW_CAMERA_OUT, the directory of points_%04d.txt" << std::endl; return 1; }
     if (const int nb = camera_batch()) {
         if (nb < 0) { std::cout << "HSFLOW_CAMERA_BATCH must be 1 .. 256" << std::endl; return 1; }
-        return run_camera_batched(lambda, it, nb, chain == 1, objects == 1, obj_min_area, obj_share);
+        return run_camera_batched(lambda, it, nb, chain == 1, objects == 1, obj_min_area, obj_share, points == 1 ? pts_n : 0u, pts_quality, pts_nms_r);
     }
     if (chain) { std::cout << "HSFLOW_CAMERA_CHAIN needs HSFLOW_CAMERA_BATCH=1 .. 256" << std::endl; return 1; }
     if (objects) { std::cout << "HSFLOW_CAMERA_OBJECTS needs HSFLOW_CAMERA_BATCH=1 .. 256" << std::endl; return 1; }
+    if (points) { std::cout << "HSFLOW_CAMERA_POINTS needs HSFLOW_CAMERA_BATCH=1 .. 256" << std::endl; return 1; }
     pnm::Image frame, gold, gnew;
     if (!pnm::load_image(camera_frame(0), frame)) { std::cout << "ERROR: capture is NULL \n"; return -1; }
     pnm::to_gray(frame, gold);                                   // cvCvtColor(imgTmp, imgOld, CV_BGR2GRAY) :79

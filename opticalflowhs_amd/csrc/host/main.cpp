@@ -32,6 +32,9 @@
 // writes objects_%04d.txt -- the regions of every pair's fit mask (hsflow_regions_batch_device), linked from pair to pair on the
 // device (hsflow_link_regions_batch_device) and given ids that hold over the batch (hsflow_link_tracks_host); one line "frame
 // id area x0 y0 x1 y1 sum_x sum_y n_flow sum_qu sum_qv" per region.  Ids restart with every batch.
+// HSFLOW_CAMERA_POINTS=<n>[,<quality_q16>[,<nms_r>]] (the same route, needs HSFLOW_CAMERA_BATCH and HSFLOW_CAMERA_OUT): every batch
+// writes points_%04d.txt -- the n best corners of the batch's first frame (hsflow_corners_device), followed through the batch's
+// flows (hsflow_track_points_device) with no read-back in between; one line "rank x0 y0 score x y status age" per corner.
 // HSFLOW_PICTURE=fb (the two -hd routes): the pair is solved forwards and, from the same pre-processed frames, backwards
 // (hsflow_set_frames_reversed), and the file is the forward-backward consistency mask (hsflow_fb*: 255 where the two flows
 // cancel, 0 elsewhere) as a gray picture; one line "fb: consistent .. inconsistent .. outside .. unknown .. mse .." tells

@@ -379,6 +379,18 @@ struct hsflow_ctx {
         size_t stage_bytes[5] = {0, 0, 0, 0, 0};
         hsflow_link_result *dRes = nullptr, *hRes = nullptr;
     } link;
+    // hsflow_corners* (hs_corners.hip.h): the kernels' scratch (per field of the largest chunk so far a score plane of W * H
+    // int64, 65536 candidates of 16 bytes, four ballot words and one offset word per 256 pixels of a row, then the
+    // hsk::CnAcc records, which a memset in front of every set of launches clears; a call reads no other word it has not
+    // written itself), allocated by the first call and grown; the staging of the synchronous form -- 0 mask, 1 records,
+    // 2 xy -- and one result header on the device and in page-locked memory.
+    struct CornersScratch {
+        void *scr = nullptr;
+        size_t bytes = 0;
+        uint8_t *stage[3] = {nullptr, nullptr, nullptr};
+        size_t stage_bytes[3] = {0, 0, 0};
+        hsflow_corners_result *dRes = nullptr, *hRes = nullptr;
+    } corners;
 };
 
 namespace {

@@ -21,6 +21,7 @@
 #include "hs_kernels_gmotion.hip.h"
 #include "hs_kernels_regions.hip.h"
 #include "hs_kernels_link.hip.h"
+#include "hs_kernels_corners.hip.h"
 #include "hs_kernels_verify.hip.h"
 #include "hs_kernels_jpeg.hip.h"
 #include "hs_kernels_jpegd.hip.h"
@@ -48,7 +49,7 @@
 #include "hs_solve.hip.h"
 
 
-namespace { void jpeg_release(hsflow_ctx *c); void jpegd_release(hsflow_ctx *c); void postops_release(hsflow_ctx *c); void pyramid_release(hsflow_ctx *c); void chain_release(hsflow_ctx *c); void gmotion_release(hsflow_ctx *c); void regions_release(hsflow_ctx *c); void link_release(hsflow_ctx *c); } // hs_jpeg.hip.h, hs_jpegd.hip.h, hs_postops.hip.h, hs_pyramid.hip.h, hs_chain.hip.h, hs_gmotion.hip.h, hs_regions.hip.h, hs_link.hip.h
+namespace { void jpeg_release(hsflow_ctx *c); void jpegd_release(hsflow_ctx *c); void postops_release(hsflow_ctx *c); void pyramid_release(hsflow_ctx *c); void chain_release(hsflow_ctx *c); void gmotion_release(hsflow_ctx *c); void regions_release(hsflow_ctx *c); void link_release(hsflow_ctx *c); void corners_release(hsflow_ctx *c); } // hs_jpeg.hip.h, hs_jpegd.hip.h, hs_postops.hip.h, hs_pyramid.hip.h, hs_chain.hip.h, hs_gmotion.hip.h, hs_regions.hip.h, hs_link.hip.h, hs_corners.hip.h
 
 extern "C" {
 
@@ -261,6 +262,7 @@ int hsflow_destroy(hsflow_ctx *c)
     gmotion_release(c);
     regions_release(c);
     link_release(c);
+    corners_release(c);
     if (c->evRender) hipEventDestroy(c->evRender);
     jpeg_release(c);
     jpegd_release(c);
@@ -926,6 +928,7 @@ void hsflow_release_cached(void)
 #include "hs_gmotion.hip.h" // hsflow_gmotion_fit[_host|_device|_batch_device|_planes_device], hsflow_gmotion_warp[_host|_device], hsflow_gmotion_compose_host / _invert_host, hsflow_default_gmotion_params
 #include "hs_regions.hip.h" // hsflow_regions[_host|_device|_batch_device|_planes_device], hsflow_default_regions_params
 #include "hs_link.hip.h"    // hsflow_link_regions[_host|_device|_batch_device|_planes_device], hsflow_link_tracks_host, hsflow_default_link_params
+#include "hs_corners.hip.h" // hsflow_corners[_host|_device|_batch_device|_planes_device], hsflow_default_corners_params
 #include "hs_verify.hip.h" // hsflow_verify, hsflow_compare_flow_device, hsflow_compare_planes_host
 #include "hs_jpeg.hip.h"   // hsflow_jpeg_bound, hsflow_jpeg_encode_host / _device, hsflow_render_flow_jpeg[_device]
 #include "hs_jpegd.hip.h"  // hsflow_jpeg_read_header, hsflow_jpeg_decode[_host|_device], hsflow_set_frames_jpeg, hsflow_push_frame_jpeg

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (HsflowLinkParams, HsflowLinkRecord, HsflowLinkSide, HsflowLinkResult, HsflowRegionsParams, HsflowRegionsRecord, HsflowRegionsResult, HsflowGmotionParams, HsflowGmotionResult, GMOTION_TRANSLATION, GMOTION_SIMILARITY, GMOTION_AFFINE, GMOTION_THRESHOLD_FIXED, GMOTION_THRESHOLD_AUTO, COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowChainParams, HsflowChainStats, CHAIN_MAX_PAIRS, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
+from ._lib import (HsflowCornersParams, HsflowCornersRecord, HsflowCornersResult, HsflowLinkParams, HsflowLinkRecord, HsflowLinkSide, HsflowLinkResult, HsflowRegionsParams, HsflowRegionsRecord, HsflowRegionsResult, HsflowGmotionParams, HsflowGmotionResult, GMOTION_TRANSLATION, GMOTION_SIMILARITY, GMOTION_AFFINE, GMOTION_THRESHOLD_FIXED, GMOTION_THRESHOLD_AUTO, COLOR_SCALE_AUTO, COLOR_SCALE_FIXED, WARP_BORDER_CONSTANT, WARP_BORDER_REPLICATE, HsflowColorParams, HsflowWarpParams, HsflowWarpStats, HsflowFbParams, HsflowFbStats, HsflowChainParams, HsflowChainStats, CHAIN_MAX_PAIRS, HsflowMedianParams, HsflowMedianStats, HsflowInterpParams, HsflowInterpStats, HsflowPyramidParams, HsflowPyramidInfo, MEDIAN_FILTER, MEDIAN_FILL, HsflowError, HsflowInfo, HsflowPairResult, HsflowParams, HsflowPlaneDiff, HsflowRenderParams, HsflowVerifyReport, RENDER_CL, RENDER_CV, KERNEL_AUTO, KERNEL_FUSED, KERNEL_SIMPLE, KERNEL_STRIP, KERNEL_FOLD, KERNEL_PERSIST,
                    MODE_CLASSIC, MODE_CV, TERM_EPS, TERM_ITER)
 
 TermCriteria = collections.namedtuple("TermCriteria", "type max_iter epsilon")
@@ -449,6 +449,54 @@ def _regions_call(height, width, device_index, mask, labels, records, capacity, 
     prm = params if params is not None else make_regions_params()
     rec, rref = _stats_record(HsflowRegionsResult, result, device, device_index)
     return (mp, ms, ctypes.byref(prm), lp, ls, rp_, capacity, rref), rec, labels, records
+
+
+def make_corners_params(kind="min_eigen", block_r=1, nms_r=3, quality_q16=655, border=0, fg=(1, 255), max_candidates=_lib.CORNERS_MAX_CANDIDATES, min_score=1):
+    """hsflow_corners_params of a corner detection: `kind` "min_eigen" or "harris" (or the constant); the structure tensor
+    is summed over (2 block_r + 1)^2 pixels; a corner beats every pixel within `nms_r`; a corner's score is at least
+    `quality_q16` / 65536 of the frame's best and at least `min_score`; `border`: pixels closer to a frame edge are no
+    corners; `fg`: the range (lo, hi) of mask bytes that may be corners.  include/hsflow.h has the rule."""
+    cp = HsflowCornersParams()
+    _lib.load().hsflow_default_corners_params(ctypes.byref(cp))
+    kinds = {"min_eigen": _lib.CORNERS_MIN_EIGEN, "harris": _lib.CORNERS_HARRIS}
+    cp.kind = kinds[kind] if isinstance(kind, str) else int(kind)
+    cp.block_r, cp.nms_r, cp.quality_q16, cp.border = int(block_r), int(nms_r), int(quality_q16), int(border)
+    cp.fg_lo, cp.fg_hi = int(fg[0]), int(fg[1])
+    cp.max_candidates, cp.min_score = int(max_candidates), int(min_score)
+    return cp
+
+
+def _corners_xy(xy, capacity, device, device_index):
+    """The xy array of the corner entries: False / None (absent), True (`capacity` pairs allocated here) or a float32 array
+    (capacity, 2), contiguous.  Returns (array, pointer)."""
+    if xy is None or xy is False:
+        return None, None
+    if xy is True:
+        if device:
+            import torch
+            xy = torch.empty((max(capacity, 1), 2), dtype=torch.float32, device="cuda:%d" % device_index)
+        else:
+            xy = np.empty((max(capacity, 1), 2), np.float32)
+    if device != _is_device_tensor(xy) or (not device and not isinstance(xy, np.ndarray)):
+        raise ValueError("xy must be %s" % ("a CUDA tensor" if device else "a NumPy array"))
+    packed = xy.is_contiguous() if device else xy.flags["C_CONTIGUOUS"]
+    if str(xy.dtype) not in ("float32", "torch.float32") or xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] < capacity or not packed:
+        raise ValueError("xy must be contiguous float32 of shape (at least capacity, 2)")
+    return xy, _ptr(xy)
+
+
+def _corners_call(height, width, device_index, mask, records, capacity, xy, result, params, device):
+    """What the corner entries share from the mask on.  mask: None or the u8 plane; records: False / None, True
+    (`capacity` of them allocated here: on the host a ctypes array of `HsflowCornersRecord`, on the device a CUDA uint8
+    tensor of capacity * 16 bytes) or such an array; xy: False / None, True or the float32 array (capacity, 2); result:
+    True or False.  Returns (the C call's arguments, result, records, xy)."""
+    capacity = int(capacity)
+    mp, ms = _plane(mask, height, width, "uint8", "mask", device) if mask is not None else (None, 0)
+    records, rp_ = _link_records(records, capacity, HsflowCornersRecord, "records", device, device_index)
+    xy, xp = _corners_xy(xy, capacity, device, device_index)
+    prm = params if params is not None else make_corners_params()
+    rec, rref = _stats_record(HsflowCornersResult, result, device, device_index)
+    return (mp, ms, ctypes.byref(prm), rp_, capacity, xp, rref), rec, records, xy
 
 
 def make_link_params(cap_a=64, cap_b=None):
@@ -1187,6 +1235,49 @@ class HSFlow(object):
                                                            _check_stats_tensor(results, n, HsflowRegionsResult)))
         return results
 
+    def corners(self, pair=0, which=0, mask=None, capacity=1024, records=True, xy=False, result=True, params=None, device=False):
+        """The points of a frame worth following: the corners of the context's own pre-processed gray plane of `pair`
+        (`which` 0: the prev frame, 1: the curr frame), by `hsflow_corners[_device]` (`make_corners_params`;
+        include/hsflow.h has the rule).  mask: None or a u8 plane (H, W) of the pixels that may be corners; records: False,
+        True (`capacity` records allocated here) or the array; xy: False, True or a float32 array (capacity, 2), whose slots
+        from n_written on come back NaN -- what `track_points` takes as it is; result: True or False.  Host arrays:
+        synchronous, the result an `HsflowCornersResult`, the records a ctypes array of `HsflowCornersRecord` of which the
+        first `n_written` are valid.  CUDA tensors (or device=True): only enqueued on the context's stream, result and
+        records then CUDA uint8 tensors that `corners_result_from` / `corners_records_from` read.  Returns (result, records,
+        xy), None for what was not asked for."""
+        device = _chain_device(device, mask, xy, records if not isinstance(records, ctypes.Array) else None)
+        args, rec, records, xy = _corners_call(self.height, self.width, self.device, mask, records, capacity, xy, result, params, device)
+        self._check((self._lib.hsflow_corners_device if device else self._lib.hsflow_corners)(self._h, int(pair), int(which), *args))
+        return rec, records, xy
+
+    def corners_planes_device(self, gray, mask=None, capacity=1024, records=True, xy=False, result=True, params=None):
+        """`corners` on the device of a caller's plane: gray a CUDA u8 plane (H, W) of the context's size, any row stride
+        (`hsflow_corners_planes_device`).  Only enqueued."""
+        gp, gs = _plane(gray, self.height, self.width, "uint8", "gray", True)
+        args, rec, records, xy = _corners_call(self.height, self.width, self.device, mask, records, capacity, xy, result, params, True)
+        self._check(self._lib.hsflow_corners_planes_device(self._h, gp, gs, *args))
+        return rec, records, xy
+
+    def corners_batch_device(self, first_pair=0, n=None, which=0, mask=None, records=None, capacity=1024, xy=None, results=None, params=None):
+        """`corners` on the device for the pairs first_pair .. first_pair + n - 1 (n=None: all pairs from first_pair) by one
+        set of launches (`hsflow_corners_batch_device`).  mask: None, or a list of n entries, each None or a CUDA u8 plane
+        (H, W), one row stride.  records: None, or a list of n entries, each None or a contiguous CUDA uint8 tensor of
+        capacity * 16 bytes; xy: None, or a list of n entries, each None or a contiguous CUDA float32 tensor (capacity, 2).
+        results: None, or a CUDA uint8 tensor of n * 64 bytes (`corners_result_from`).  Only enqueued."""
+        first_pair, n = self._batch_range(first_pair, n)
+        capacity = int(capacity)
+        ml, ms = _chain_list(mask, n, self.height, self.width, "uint8", "mask", True, holes=True)
+        rl = _link_list(records, n, capacity, HsflowCornersRecord, "records")
+        xl = None
+        if xy is not None:
+            if len(xy) != n:
+                raise ValueError("xy must hold one entry per pair")
+            xl = (ctypes.c_void_p * n)(*[_corners_xy(x, capacity, True, self.device)[1].value if x is not None else None for x in xy])
+        prm = params if params is not None else make_corners_params()
+        self._check(self._lib.hsflow_corners_batch_device(self._h, first_pair, n, int(which), ml, ms, ctypes.byref(prm), rl, capacity, xl,
+                                                           _check_stats_tensor(results, n, HsflowCornersResult)))
+        return results
+
     def link_regions(self, pair=0, labels_a=None, labels_b=None, links=True, link_capacity=256, side_a=True, side_b=True, result=True, params=None,
                      device=False):
         """The regions of frame k (int32 label plane `labels_a`, (H, W)) linked to those of frame k + 1 (`labels_b`) by the
@@ -1685,6 +1776,37 @@ def regions_host(mask=None, u=None, v=None, labels=False, records=True, capacity
     if st != _lib.OK:
         raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
     return rec, labels, records
+
+
+def corners_result_from(results, n=1):
+    """The `HsflowCornersResult` headers a device call left in the CUDA uint8 tensor `results` (after `synchronize()`):
+    one for n=1, else a list of n."""
+    raw = results.cpu().numpy().tobytes()
+    size = ctypes.sizeof(HsflowCornersResult)
+    recs = [HsflowCornersResult.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(n)]
+    return recs[0] if n == 1 else recs
+
+
+def corners_records_from(records, n):
+    """The first n `HsflowCornersRecord` of a record array: a CUDA uint8 tensor (after `synchronize()`) or the ctypes
+    array of the host forms; a list."""
+    raw = records.cpu().numpy().tobytes() if _is_device_tensor(records) else bytes(records)
+    return [HsflowCornersRecord.from_buffer_copy(raw[i * 16:(i + 1) * 16]) for i in range(n)]
+
+
+def corners_host(gray, mask=None, capacity=1024, records=True, xy=False, result=True, params=None):
+    """The corner detection by the rule on the host (`hsflow_corners_host`, no GPU work): gray a u8 array (H, W), mask
+    None or such an array, padded rows taken as they are.  capacity, records, xy, result as `HSFlow.corners` takes them.
+    Returns (result, records, xy) -- byte for byte what the device forms give from the same planes."""
+    if not isinstance(gray, np.ndarray) or gray.dtype != np.uint8 or gray.ndim != 2:
+        raise ValueError("gray must be a 2-D uint8 NumPy array")
+    H, W = gray.shape
+    gp, gs = _plane(gray, H, W, "uint8", "gray", False)
+    args, rec, records, xy = _corners_call(H, W, 0, mask, records, capacity, xy, result, params, False)
+    st = _lib.load().hsflow_corners_host(gp, gs, W, H, *args)
+    if st != _lib.OK:
+        raise HsflowError(st, (_lib.load().hsflow_last_error(None) or b"").decode())
+    return rec, records, xy
 
 
 def link_result_from(results, n=1):
